@@ -13,11 +13,15 @@ partitioned over the ranks in one of two ways (`--split`):
            Pippenger windows (the bucket-window shard north_star names).
 Either way the only exchange is one RCCL all-gather of the 144-byte Jacobian partial sums + an on-device fold.
 
-After the timed region every leg CHECKS its output at full size ("verified" fields): the MSM against (sum s_i k_i) G
-computed without Pippenger, the NTT at sampled indices against Horner evaluation, the Groth16 proof against the
-trapdoor identity of a valid device-generated key, the KZG commitments / opening proof in the exponent.
+A plain run sets up, warms up, times `--steps` steps and prints ONE JSON line (rank 0) with the contract fields
+(`ms_per_step`: milliseconds per timed step).  `--dump-outputs DIR` writes the point the last timed step computed
+(dump_outputs).
 
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline` and `cpu_baseline`.
+`--full` adds everything else: HIP events around the dominant kernel in the timed region, the other legs, and after
+the timed region every leg CHECKS its output at full size ("verified" fields): the MSM against (sum s_i k_i) G
+computed without Pippenger, the NTT at sampled indices against Horner evaluation, the Groth16 proof against the
+trapdoor identity of a valid device-generated key, the KZG commitments / opening proof in the exponent.  Its line
+adds `roofline`, `cpu_baseline` and one entry per leg; the sidecar file has every leg's full object.
 """
 import argparse
 import csv
@@ -132,7 +136,15 @@ def main():
     ap.add_argument("--child-legs", default="groth16,kzg", help="internal: which group legs the child runs")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: launch the ranks, run the all-gather + fold plumbing over gloo with stand-in partial sums, print the line's frame")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: HIP events around the dominant kernel, the post-timing checks (verified), the other legs, "
+                         "the sharded and device-group legs, the live PMC passes, the CPU baseline and the sidecar (the --no-* options select among them); "
+                         "without it a run sets up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(launch_ranks(args, sys.argv[1:]))
@@ -227,17 +239,35 @@ def main():
         result = step()
     result = drain(result)
     fence()
-    # the timed region carries HIP events around the dominant kernel only (roofline.achieved); the full per-kernel breakdown
-    # comes from three extra, untimed steps below
-    ctx.profile_reset()
-    ctx.profile_filter("msm_bucket_acc")
-    ctx.profile(True)
+    if args.full:
+        # the timed region carries HIP events around the dominant kernel only (roofline.achieved); the full per-kernel breakdown
+        # comes from three extra, untimed steps below
+        ctx.profile_reset()
+        ctx.profile_filter("msm_bucket_acc")
+        ctx.profile(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         result = step()
     result = drain(result)
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(np, zk, ctx, args.dump_outputs, result.cpu().numpy().view(np.uint64).reshape(3, 6))
+    if not args.full:
+        if use_dist:
+            t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            elapsed = float(t.item())
+        if rank == 0:
+            line = headline(args, world, n, windows, elapsed)
+            line["verified"] = None  # the post-timing checks run under --full
+            os.write(json_fd, (json.dumps(line, separators=(",", ":")) + "\n").encode())
+        fence()
+        bases.free()
+        ctx.close()
+        if use_dist:
+            dist.destroy_process_group()
+        return
     ctx.profile(False)
     dom_ms, dom_cnt = ctx.profile_get("msm_bucket_acc")
     ctx.profile_filter("")
@@ -326,29 +356,11 @@ def main():
                      "note": "value: weak scaling (2^log_n points per GPU, one all-gather of 144 B per rank per step); the *_sharded legs are STRONG scaling of fixed jobs "
                              "and saturate at the replicated witness map + the small-MSM floor (DESIGN.md section 9; this line carries only what this run measured)"}
     if rank == 0:
-        ms_per_step = elapsed / args.steps * 1e3
-        value = world * n * args.steps / elapsed / 1e6
         dom_avg_ms = dom_ms / max(1, dom_cnt)
         alg_bytes = ALG_BYTES_PER_POINT * n_local if not windows else ALG_BYTES_PER_POINT * n_local // world  # a rank's share of the job's bytes
         achieved = alg_bytes / (dom_avg_ms * 1e-3) / 1e9 if dom_avg_ms > 0 else 0.0
-        full = {
-            "metric": "MSM Mpoints/sec, BLS12-381 G1 Pippenger, 2^%d points per GPU" % args.log_n,
-            "value": round(value, 4),
-            "unit": "Mpoints/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u32",
-            "dtype_note": "29-bit lazy limbs in u32 registers, 64-bit multiply-accumulate (381-bit Montgomery Fq, 255-bit Fr)",
-            "data": "synthetic",
-            "config": {"workload": "BLS12-381 G1 Pippenger MSM, ONE MSM of %d x 2^%d random points/scalars, bases resident" % (world, args.log_n),
-                       "points_per_gpu": n,
-                       "parallelism": ("window partition x%d (every rank: all points, 1/%d of the window tables)" % (world, world) if windows
-                                       else "point-range partition x%d" % world) + " + one all-gather of the 144-B partial sums"},
+        full = headline(args, world, n, windows, elapsed)
+        full.update({
             "verified": msm_verified,
             "verified_vs": ["(sum s_i k_i) G by the fixed-base kernel"] if msm_verified is not None else [],
             "timing": {"regime": "%d timed steps after %d warm-up steps (%.0f ms timed; the clocks settle over ~100 ms of load: 50/10 reads 3-4 %% above 20/5)"
@@ -361,7 +373,7 @@ def main():
                          "honest_bound": "integer VALU issue (DESIGN.md section 4): the kernel moves 128 algorithmic bytes per ~4.9 k VALU instructions"},
             "kernel_ms_per_step": {k: round(v[0] / 3, 4) for k, v in sorted(prof.items())},
             "kernel_ms_per_step_source": "three extra untimed steps with HIP events around every launch (the timed region times msm_bucket_acc only)",
-        }
+        })
         if dist_info is not None:
             full["dist"] = dist_info
         if world == 1:
@@ -463,6 +475,42 @@ def main():
     ctx.close()
     if use_dist:
         dist.destroy_process_group()
+
+
+def headline(args, world, n, windows, elapsed):
+    """The contract fields of the line: the MSM of the timed steps, whatever else the run does."""
+    return {
+        "metric": "MSM Mpoints/sec, BLS12-381 G1 Pippenger, 2^%d points per GPU" % args.log_n,
+        "value": round(world * n * args.steps / elapsed / 1e6, 4),
+        "unit": "Mpoints/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u32",
+        "dtype_note": "29-bit lazy limbs in u32 registers, 64-bit multiply-accumulate (381-bit Montgomery Fq, 255-bit Fr)",
+        "data": "synthetic",
+        "config": {"workload": "BLS12-381 G1 Pippenger MSM, ONE MSM of %d x 2^%d random points/scalars, bases resident" % (world, args.log_n),
+                   "points_per_gpu": n,
+                   "parallelism": ("window partition x%d (every rank: all points, 1/%d of the window tables)" % (world, world) if windows
+                                   else "point-range partition x%d" % world) + " + one all-gather of the 144-B partial sums"},
+    }
+
+
+def dump_outputs(np, zk, ctx, path, jac):
+    """--dump-outputs DIR: the point the last timed step computed (the job's MSM sum, Jacobian (3, 6) canonical u64 limbs), in affine
+    form -- a Jacobian triple of a point is not unique, its affine coordinates are:
+      msm_affine_xy.npy    (2, 24) float64: x and y as 16-bit little-endian words of their canonical 381-bit values (exact in float64)
+      msm_is_infinity.npy  (1,) float64: 1.0 when the sum is the point at infinity (x, y then zero)
+    The inputs come from fixed seeds, so runs with the same arguments compare output for output."""
+    aff, inf = ctx.jacobian_to_affine(zk.BLS12_381, zk.G1, jac)
+    words = np.ascontiguousarray(aff.reshape(2, 6), dtype="<u8").view("<u2").astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "msm_affine_xy.npy"), words)
+    np.save(os.path.join(path, "msm_is_infinity.npy"), np.array([float(inf)], dtype=np.float64))
 
 
 def write_detail(full, path=None):

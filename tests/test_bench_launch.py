@@ -73,7 +73,7 @@ def test_bench_rccl_path_on_one_gpu(tmp_path):
     all-gather) and the KZG commit with its columns dealt over the ranks (all-gather of the commitments) at world = 1.  stdout must carry exactly one JSON line, every leg verified."""
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                           "--master-port", "29619", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--force-dist",
-                          "--ntt-log-m", "20", "--no-pmc", "--no-cpu-baseline", "--detail", str(tmp_path / "detail.json")],
+                          "--full", "--ntt-log-m", "20", "--no-pmc", "--no-cpu-baseline", "--detail", str(tmp_path / "detail.json")],
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, text=True)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -91,6 +91,39 @@ def test_bench_rccl_path_on_one_gpu(tmp_path):
     assert line["dist"]["backend"] == "rccl" and line["dist"]["world_size"] == 1 and len(line["dist"]["devices"]) == 1
     detail = json.load(open(tmp_path / "detail.json"))   # the sidecar keeps every leg's full object
     assert detail["value"] == line["value"] and "kernel_ms_per_step" in detail and "ms_by_phase" in detail["placeholder_round"]
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_its_last_step(tmp_path, zk, ctx):
+    """Without --full a run times the headline MSM and prints its contract fields, nothing else; --dump-outputs writes the point its last
+    timed step computed, which must be (sum s_i k_i) G over the run's seeded inputs -- computed here by the fixed-base kernel."""
+    import importlib.util
+
+    import numpy as np
+
+    log_n = 12
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--log-n", str(log_n),
+                          "--dump-outputs", str(tmp_path / "out")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, text=True)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = lines_of(out.stdout)
+    assert len(lines) == 1, out.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line)
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert not {"legs", "roofline", "cpu_baseline", "detail"} & set(line), sorted(line)  # those come with --full
+    xy = np.load(tmp_path / "out" / "msm_affine_xy.npy")
+    inf = np.load(tmp_path / "out" / "msm_is_infinity.npy")
+    assert xy.dtype == np.float64 and xy.shape == (2, 24) and inf.tolist() == [0.0]
+    spec = importlib.util.spec_from_file_location("zk_bench_mod3", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    ks, sc = b.random_scalars(np, 1 << log_n, 1000), b.random_scalars(np, 1 << log_n, 2000)  # block 0's seeds
+    e = sum(k * s for k, s in zip(b.to_ints(ks), b.to_ints(sc))) % b.R_BLS
+    eb = ctx.bases_from_scalars(zk.BLS12_381, zk.G1, b.lim(np, e).reshape(1, 4))
+    exp, exp_inf = eb.download()
+    eb.free()
+    assert int(exp_inf[0]) == 0
+    assert (xy.astype(np.uint16).view("<u8").reshape(-1) == exp[0]).all()
 
 
 def test_group_child_failure_costs_the_leg_not_the_line(tmp_path):

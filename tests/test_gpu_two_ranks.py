@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _run(port, extra, tmp_path, ranks=2, log_n=18, ntt_log_m=18):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--dist-backend", "gloo", "--same-device", "--steps", "3", "--warmup", "1", "--log-n", str(log_n),
-           "--no-cpu-baseline", "--no-pmc", "--ntt-log-m", str(ntt_log_m), "--detail", str(tmp_path / "detail.json")] + extra
+           "--full", "--no-cpu-baseline", "--no-pmc", "--ntt-log-m", str(ntt_log_m), "--detail", str(tmp_path / "detail.json")] + extra
     out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, text=True)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
@@ -53,6 +53,39 @@ def test_two_ranks_window_split(tmp_path):
     line, _ = _run(29643, ["--split", "windows", "--no-groth16", "--no-kzg"], tmp_path)
     assert line["n_gpus"] == 2 and line["verified"] is True
     assert "window partition x2" in line["config"]["parallelism"]
+
+
+def test_two_ranks_plain_run(tmp_path, zk, ctx):
+    """Without --full the two ranks time the job's MSM, the exchange of every step included, and rank 0 prints the contract fields alone;
+    its --dump-outputs point is the whole job's sum: (sum of s_i k_i over both ranks' blocks) G, computed here by the fixed-base kernel."""
+    import importlib.util
+
+    import numpy as np
+
+    log_n = 14
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29645",
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--same-device", "--steps", "3", "--warmup", "1", "--log-n", str(log_n),
+           "--dump-outputs", str(tmp_path / "out")]
+    out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, text=True)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]  # rank 0 only
+    line = json.loads(lines[0])
+    assert line["n_gpus"] == 2 and line["steps"] == 3 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert not {"legs", "dist", "roofline", "detail"} & set(line), sorted(line)  # those come with --full
+    xy = np.load(tmp_path / "out" / "msm_affine_xy.npy")
+    spec = importlib.util.spec_from_file_location("zk_bench_two_ranks", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    e = 0
+    for blk in (0, 1):  # rank g's block is seeded by g
+        ks, sc = b.random_scalars(np, 1 << log_n, 1000 + blk), b.random_scalars(np, 1 << log_n, 2000 + blk)
+        e += sum(k * s for k, s in zip(b.to_ints(ks), b.to_ints(sc)))
+    eb = ctx.bases_from_scalars(zk.BLS12_381, zk.G1, b.lim(np, e % b.R_BLS).reshape(1, 4))
+    exp, exp_inf = eb.download()
+    eb.free()
+    assert int(exp_inf[0]) == 0 and np.load(tmp_path / "out" / "msm_is_infinity.npy").tolist() == [0.0]
+    assert (xy.astype(np.uint16).view("<u8").reshape(-1) == exp[0]).all()
 
 
 @pytest.mark.parametrize("split", ["points", "windows"])
