@@ -11,6 +11,7 @@
 #include <cerrno>
 #include <cstdint>
 #include <cstdlib>
+#include <exception>
 #include <future>
 #include <iterator>
 #include <memory>
@@ -18,6 +19,7 @@
 #include <string>
 #include <thread>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include <sys/random.h>
@@ -42,6 +44,26 @@ namespace detail {
             p += k;
             bytes -= (std::size_t)k;
         }
+    }
+    /// the smallest l with 2^l >= n (0 for n <= 1)
+    inline std::size_t ceil_log2(std::size_t n) {
+        std::size_t r = 0;
+        while (((std::size_t)1 << r) < n) ++r;
+        return r;
+    }
+    /// part k of [0, n) cut into `world` contiguous ranges whose sizes differ by at most one (the first n % world are the longer ones)
+    inline std::pair<std::size_t, std::size_t> even_range(std::size_t n, std::size_t world, std::size_t k) {
+        return {n / world * k + std::min(k, n % world), n / world * (k + 1) + std::min(k + 1, n % world)};
+    }
+    /// fn(lo, hi) over [0, n) in contiguous chunks: on up to `max_lanes` host threads (the first chunk on the calling one) from n >= threshold,
+    /// in one call on the calling thread below it
+    template <typename Fn>
+    void host_parallel_for(std::size_t n, std::size_t threshold, std::size_t max_lanes, Fn fn) {
+        const std::size_t lanes = n >= threshold ? std::max<std::size_t>(1, std::min<std::size_t>(max_lanes, std::thread::hardware_concurrency())) : 1;
+        std::vector<std::future<void>> work;
+        for (std::size_t k = 1; k < lanes; ++k) work.push_back(std::async(std::launch::async, [&fn, n, lanes, k]() { fn(n * k / lanes, n * (k + 1) / lanes); }));
+        fn(0, n / lanes);
+        for (auto &w : work) w.get();
     }
 }    // namespace detail
 
@@ -110,7 +132,8 @@ private:
 /// N GPUs behind ONE caller (include/zkhip.h, "device group").  The reference hides its parallelism inside the call -- `chunks =
 /// omp_get_max_threads()` inside r1cs_gg_ppzksnark_prover::process (prover.hpp:94-99), the loop over the batch inside
 /// kzg_commitment_scheme_v2::commit (kzg_v2.hpp:208-226) -- and so do the shim classes that take a device_group: one context per device,
-/// one host thread, the partial sums exchanged INSIDE the library (RCCL all-gather over xGMI, peer copies, or a staged copy).
+/// the partial sums exchanged INSIDE the library (RCCL all-gather over xGMI, peer copies, or a staged copy).  The caller's thread drives
+/// member 0; for_each_member drives members 1..N-1 from host threads of the library's own, which a caller's thread-local state does not reach.
 ///     device_group gpus({0, 1, 2, 3, 4, 5, 6, 7});      // or device_group::from_env(): ZKHIP_DEVICES=0,1,2,3,4,5,6,7
 /// A device may be named more than once (several members on one GPU).
 class device_group {
@@ -173,6 +196,37 @@ public:
         check_group(zkhip_group_copy(g_, (int)dst, d_dst, (int)src, d_src, bytes), "zkhip_group_copy");
     }
     void sync() const { check_group(zkhip_group_sync(g_), "zkhip_group_sync"); }
+    /// fn(k) for every member k: fn(0) on the calling thread, members 1..N-1 on host threads of their own (all in turn on the calling
+    /// thread when `threaded` is false).  Returns when every call has; if any threw, the group is drained (best effort: nothing a member
+    /// enqueued may still run on buffers the caller frees while unwinding) and the first exception, in member order, is rethrown.
+    template <typename Fn>
+    void for_each_member(Fn &&fn, bool threaded = true) const {
+        std::vector<std::exception_ptr> failed(size());
+        std::vector<std::future<void>> others(size());
+        for (std::size_t k = 1; threaded && k < size(); ++k) {
+            try {
+                others[k] = std::async(std::launch::async, [&fn, k]() { fn(k); });
+            } catch (...) {
+                failed[k] = std::current_exception();
+            }
+        }
+        for (std::size_t k = 0; k < size(); ++k) {
+            try {
+                if (others[k].valid()) others[k].get();
+                else if (k == 0 || !threaded) fn(k);    // a member whose thread could not start keeps that failure
+            } catch (...) {
+                failed[k] = std::current_exception();
+            }
+        }
+        for (const auto &e : failed) {
+            if (!e) continue;
+            try {
+                sync();
+            } catch (...) {
+            }
+            std::rethrow_exception(e);
+        }
+    }
 
 private:
     zkhip_device_group *g_ = nullptr;
@@ -208,6 +262,27 @@ private:
     void *p_ = nullptr;
     std::size_t cap_ = 0;
     zkhip_ctx *ctx_ = nullptr;
+};
+
+/// A device buffer that grows on demand and is kept: a larger request waits for the context's stream (earlier work may still use the old
+/// buffer) and reallocates; contents are not preserved when it grows.
+class device_scratch {
+public:
+    void *reserve(const context &ctx, std::size_t bytes) {
+        if (bytes > cap_) {
+            ctx.sync();
+            buf_.reset();
+            cap_ = 0;
+            buf_ = ctx.alloc(bytes);
+            cap_ = bytes;
+        }
+        return buf_.get();
+    }
+    void *get() const { return buf_.get(); }
+
+private:
+    std::shared_ptr<void> buf_;
+    std::size_t cap_ = 0;
 };
 
 /// `count` scalar-field values -> canonical limbs in device memory at d_dst (32 bytes each).
@@ -259,13 +334,9 @@ void download_scalars(const context &ctx, const void *d_src, std::size_t count, 
     } else {
         std::vector<std::uint64_t> h(4 * count);
         ctx.d2h(h.data(), d_src, h.size() * 8);
-        const std::size_t lanes = count >= ((std::size_t)1 << 16) ? std::max(1u, std::min(8u, std::thread::hardware_concurrency())) : 1;
-        std::vector<std::future<void>> work;
-        for (std::size_t k = 0; k < lanes; ++k)
-            work.push_back(std::async(lanes > 1 ? std::launch::async : std::launch::deferred, [&, k]() {
-                for (std::size_t i = count * k / lanes; i < count * (k + 1) / lanes; ++i) out[at + i] = Adapter::scalar_from_limbs(&h[4 * i]);
-            }));
-        for (auto &w : work) w.get();
+        detail::host_parallel_for(count, (std::size_t)1 << 16, 8, [&](std::size_t lo, std::size_t hi) {
+            for (std::size_t i = lo; i < hi; ++i) out[at + i] = Adapter::scalar_from_limbs(&h[4 * i]);
+        });
     }
 }
 
@@ -286,14 +357,9 @@ public:
             const std::size_t n = (std::size_t)(last - first);
             xy.resize(n * 2 * cl);
             inf.resize(n);
-            const std::size_t lanes = n >= ((std::size_t)1 << 14) ? std::max(1u, std::min(8u, std::thread::hardware_concurrency())) : 1;
-            std::vector<std::future<void>> work;
-            for (std::size_t k = 0; k < lanes; ++k)
-                work.push_back(std::async(lanes > 1 ? std::launch::async : std::launch::deferred, [&, k]() {
-                    for (std::size_t i = n * k / lanes; i < n * (k + 1) / lanes; ++i)
-                        inf[i] = adapter::point_to_affine_limbs(first[i], xy.data() + i * 2 * cl) ? 0 : 1;
-                }));
-            for (auto &w : work) w.get();
+            detail::host_parallel_for(n, (std::size_t)1 << 14, 8, [&](std::size_t lo, std::size_t hi) {
+                for (std::size_t i = lo; i < hi; ++i) inf[i] = adapter::point_to_affine_limbs(first[i], xy.data() + i * 2 * cl) ? 0 : 1;
+            });
         } else {
             for (InputIt it = first; it != last; ++it) {
                 xy.resize(xy.size() + 2 * cl);

@@ -16,7 +16,6 @@
 #include <algorithm>
 #include <stdexcept>
 #include <string>
-#include <thread>
 #include <utility>
 #include <vector>
 
@@ -28,17 +27,6 @@ namespace zk {
 namespace hip {
 
 namespace detail {
-    /// fn(lo, hi) over [0, n) in contiguous chunks on up to 32 host threads (the QAP evaluation is embarrassingly parallel)
-    template <typename Fn>
-    void parallel_chunks(std::size_t n, Fn fn) {
-        const std::size_t hw = std::max<std::size_t>(1, std::min<std::size_t>(32, std::thread::hardware_concurrency()));
-        const std::size_t parts = n < (std::size_t)1 << 14 ? 1 : hw, per = (n + parts - 1) / parts;
-        std::vector<std::thread> th;
-        for (std::size_t k = 1; k < parts; ++k)
-            if (k * per < n) th.emplace_back([=]() { fn(k * per, std::min(n, (k + 1) * per)); });
-        fn(0, std::min(n, per));
-        for (auto &t : th) t.join();
-    }
     template <typename Fr>
     Fr pow_u64(Fr b, std::uint64_t e) {
         Fr r = Fr::one();
@@ -46,11 +34,6 @@ namespace detail {
             if (e & 1) r = r * b;
             b = b * b;
         }
-        return r;
-    }
-    inline std::size_t ceil_log2(std::size_t n) {
-        std::size_t r = 0;
-        while (((std::size_t)1 << r) < n) ++r;
         return r;
     }
 }    // namespace detail
@@ -186,7 +169,7 @@ public:
             }
             batch_invert(dinv);
             basic_lagrange(big_m, big_omega, t, L0, u.data());
-            detail::parallel_chunks(big_m, [&](std::size_t lo, std::size_t hi) {
+            detail::host_parallel_for(big_m, (std::size_t)1 << 14, 32, [&](std::size_t lo, std::size_t hi) {
                 for (std::size_t i = lo; i < hi; ++i) u[i] = u[i] * dinv[i % compr];
             });
             const value_type L1 = (detail::pow_u64(t, big_m) - one) * (detail::pow_u64(omega, big_m) - one).inversed();
@@ -258,7 +241,7 @@ private:
     /// out[i] = scale * l_i(t) over {w^i, i < n}: l_i(t) = (t^n - 1) w^i / (n (t - w^i)); one inversion per chunk (Montgomery's trick)
     static void basic_lagrange(std::size_t n, const value_type &w, const value_type &t, const value_type &scale, value_type *out) {
         const value_type z_over_n = (detail::pow_u64(t, n) - value_type::one()) * value_type((std::uint64_t)n).inversed() * scale;
-        detail::parallel_chunks(n, [&](std::size_t lo, std::size_t hi) {
+        detail::host_parallel_for(n, (std::size_t)1 << 14, 32, [&](std::size_t lo, std::size_t hi) {
             std::vector<value_type> pre(hi - lo);
             value_type x = detail::pow_u64(w, lo), acc = value_type::one();
             for (std::size_t i = lo; i < hi; ++i) {

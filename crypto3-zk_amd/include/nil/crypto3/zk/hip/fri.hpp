@@ -165,8 +165,7 @@ public:
 
 private:
     static std::size_t log2_exact(std::size_t n) {
-        std::size_t l = 0;
-        while (((std::size_t)1 << l) < n) ++l;
+        const std::size_t l = detail::ceil_log2(n);
         if (n == 0 || ((std::size_t)1 << l) != n) throw std::runtime_error("device_polynomial_dfs: size must be a power of two");
         return l;
     }
@@ -243,8 +242,7 @@ template <typename CurveType>
 device_polynomial_dfs<CurveType> polynomial_shift(const device_polynomial_dfs<CurveType> &f, int shift, std::size_t domain_size = 0) {
     if (domain_size == 0) domain_size = f.size();
     if (domain_size == 0 || f.size() % domain_size) throw std::invalid_argument("polynomial_shift: the vector is not an extension of the domain");
-    std::size_t log_size = 0;
-    while (((std::size_t)1 << log_size) < f.size()) ++log_size;
+    const std::size_t log_size = detail::ceil_log2(f.size());
     device_polynomial_dfs<CurveType> out(f.ctx(), f.size());
     out.set_degree(f.degree());
     check(zkhip_poly_shift_dev(f.ctx().get(), f.data(), log_size, (std::int64_t)shift * (std::int64_t)(f.size() / domain_size), out.data()),
@@ -258,8 +256,7 @@ template <typename CurveType>
 device_polynomial_dfs<CurveType> fold_polynomial(const device_polynomial_dfs<CurveType> &f, const typename curve_adapter<CurveType>::scalar_value_type &alpha,
                                                  const typename curve_adapter<CurveType>::scalar_value_type &omega) {
     typedef curve_adapter<CurveType> adapter;
-    std::size_t log_size = 0;
-    while (((std::size_t)1 << log_size) < f.size()) ++log_size;
+    const std::size_t log_size = detail::ceil_log2(f.size());
     device_polynomial_dfs<CurveType> out(f.ctx(), f.size() / 2);
     std::uint64_t a[4], w[4];
     adapter::scalar_to_limbs(alpha, a);
@@ -289,8 +286,7 @@ std::vector<typename curve_adapter<CurveType>::scalar_value_type>
         std::size_t j = i;
         while (j < batch && polys[j].size() == polys[i].size()) ++j;
         const std::size_t n = polys[i].size();
-        std::size_t log_n = 0;
-        while (((std::size_t)1 << log_n) < n) ++log_n;
+        const std::size_t log_n = detail::ceil_log2(n);
         if (n == 0 || ((std::size_t)1 << log_n) != n || log_n > log_domain) throw std::runtime_error("precommit: bad polynomial size");
         char *dst = static_cast<char *>(d_ext.get()) + 32 * i * D;
         if (log_n == log_domain) {

@@ -125,8 +125,7 @@ std::vector<typename curve_adapter<CurveType>::g1_value_type>
     if (polys.empty()) return out;
     const context &ctx = params.ctx;
     const std::size_t n = polys[0].size(), batch = polys.size();
-    std::size_t log_n = 0;
-    while (((std::size_t)1 << log_n) < n) ++log_n;
+    const std::size_t log_n = detail::ceil_log2(n);
     if (((std::size_t)1 << log_n) != n || n > params.commitment_key.size()) throw std::runtime_error("kzg_commit_batch: bad polynomial size");
     for (std::size_t b = 0; b < batch; ++b)
         if (polys[b].size() != n) throw std::runtime_error("kzg_commit_batch: ragged batch");

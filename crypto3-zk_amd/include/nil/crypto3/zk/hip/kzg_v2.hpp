@@ -27,13 +27,12 @@
 #include <algorithm>
 #include <array>
 #include <deque>
-#include <exception>
 #include <functional>
-#include <future>
 #include <iterator>
 #include <map>
 #include <memory>
 #include <set>
+#include <tuple>
 #include <vector>
 
 #include "fri.hpp"
@@ -258,73 +257,110 @@ public:
     /// commit(index) (kzg_v2.hpp:208-226): one commitment per polynomial of the batch; the coefficient forms stay
     /// on the device for proof_eval.
     commitment_type commit(std::size_t index) {
-        if (_group_params && _group_params->members.size() > 1) return commit_group(index);
-        const context &ctx = _params.ctx;
         const std::vector<const poly_type *> &polys = _polys[index];
         const auto &resident = _resident[index];    // position -> a polynomial that is already on the device (polys[position] == nullptr)
         const auto &resident_c = _resident_coefficients[index];    // ... and already in coefficient form
-        auto is_coefficients = [&resident_c](std::size_t i) { return resident_c.count(i) != 0; };
-        auto is_zero = [&resident_c](std::size_t i) {    // known to be the zero polynomial: its commitment is the neutral element, no multiexp
-            auto it = resident_c.find(i);
-            return it != resident_c.end() && it->second.known_zero();
-        };
+        const std::size_t count = polys.size(), jl = 3 * adapter::g1_coord_limbs;
         device_batch db;
         std::size_t total = 0;
-        for (std::size_t i = 0; i < polys.size(); ++i) {
-            const std::size_t sz = polys[i] ? polys[i]->size() : is_coefficients(i) ? resident_c.at(i).size() : resident.at(i).size();
+        for (std::size_t i = 0; i < count; ++i) {
+            const std::size_t sz = polys[i] ? polys[i]->size() : is_coefficients(index, i) ? resident_c.at(i).size() : resident.at(i).size();
             if (sz == 0 || (sz & (sz - 1))) throw std::runtime_error("commit: polynomial_dfs size must be a power of two");
             if (sz > _params.commitment_key.size()) throw std::runtime_error("commit: polynomial longer than the commitment key");
             db.offset.push_back(total);
             db.len.push_back(sz);
             total += sz;
         }
-        db.data = ctx.alloc(std::max<std::size_t>(1, total) * 32);
-        const std::size_t count = polys.size(), jl = 3 * adapter::g1_coord_limbs;
-        auto d_res = ctx.alloc(std::max<std::size_t>(1, count) * jl * 8);
-        /* The polynomials go up in chunks on a second in-order stream: while chunk c is transformed (p.coefficients(), kzg.hpp:431:
-           one batched inverse NTT per chunk of equally sized polynomials) and committed (multiexp against the resident key, the
-           chunk's bucket reductions sharing one launch), chunk c + 1 crosses PCIe. */
-        bool any_from_host = false;    // a batch that is resident already has nothing to overlap: one chunk, one shared tail over all its multiexps
-        for (const poly_type *p : polys) any_from_host = any_from_host || p != nullptr;
-        const bool pipelined = upload_chunk != 0 && count > upload_chunk && any_from_host;
-        const context &up = pipelined ? upload_context() : ctx;
-        /* a resident polynomial may still be in the making on ctx's stream (polynomial_product, resize do not synchronise): the stream that
-           copies it waits for ctx once */
-        if (pipelined && (!resident.empty() || !resident_c.empty())) up.wait_for(ctx);
-        for (std::size_t i = 0; i < count;) {
-            std::size_t j = i;
+        db.data = _params.ctx.alloc(std::max<std::size_t>(1, total) * 32);
+        /* the caller's root-of-unity function is called from THIS thread only (it need not be thread-safe): one root per distinct size, up front */
+        root_map roots;
+        for (std::size_t i = 0; i < count; ++i) {
+            const std::size_t log_n = detail::ceil_log2(db.len[i]);
+            if (!is_coefficients(index, i) && !roots.count(log_n)) adapter::scalar_to_limbs(_root_of_unity(log_n), roots[log_n].data());
+        }
+        std::vector<std::uint64_t> res(count * jl);    // the Jacobian commitments
+        if (_group_params && _group_params->members.size() > 1) commit_group(index, db, roots, res);
+        else {
+            const context &ctx = _params.ctx;
+            auto d_res = ctx.alloc(std::max<std::size_t>(1, count) * jl * 8);
+            /* a batch that is resident already has nothing to overlap: one chunk, one shared tail over all its multiexps */
+            const bool pipelined = upload_chunk != 0 && count > upload_chunk && has_host_columns(index, 0, count);
+            const context &up = pipelined ? upload_context() : ctx;
+            /* a resident polynomial may still be in the making on ctx's stream (polynomial_product, resize do not synchronise): the stream that
+               copies it waits for ctx once */
+            if (pipelined && (!resident.empty() || !resident_c.empty())) up.wait_for(ctx);
             /* the first chunk is a short one: nothing runs on the device until it has arrived */
-            const std::size_t limit = (pipelined && i == 0) ? std::max<std::size_t>(1, upload_chunk / 4) : upload_chunk;
-            while (j < count && db.len[j] == db.len[i] && is_coefficients(j) == is_coefficients(i) && is_zero(j) == is_zero(i) &&
-                   (!pipelined || limit == 0 || j - i < limit))
-                ++j;
-            for (std::size_t p = i; p < j; ++p) {
-                if (polys[p]) upload_scalars<adapter>(up, db.at(p), detail::poly_data<adapter>(*polys[p]), polys[p]->size());
-                else
-                    check(zkhip_memcpy_d2d_async(up.get(), db.at(p), is_coefficients(p) ? resident_c.at(p).data() : resident.at(p).data(), db.len[p] * 32),
-                          "zkhip_memcpy_d2d_async", up.get());
-            }
-            if (pipelined) ctx.wait_for(up);
-            if (!is_coefficients(i)) {
-                std::size_t log_n = 0;
-                while (((std::size_t)1 << log_n) < db.len[i]) ++log_n;
-                std::uint64_t w[4];
-                adapter::scalar_to_limbs(_root_of_unity(log_n), w);
-                check(zkhip_ntt_dev(ctx.get(), adapter::id, db.at(i), log_n, j - i, w, 1, nullptr), "zkhip_ntt_dev", ctx.get());
-            }
-            if (!is_zero(i)) commit_resident(db, i, j, d_res.get());    // the coefficients of a known-zero polynomial still go into db (proof_eval reads them)
-            i = j;
+            commit_columns(index, db, 0, count, static_cast<char *>(db.data.get()), ctx, up, _params.commitment_key.get(), d_res.get(), roots,
+                           pipelined ? std::max<std::size_t>(1, upload_chunk / 4) : 0, pipelined ? upload_chunk : 0, true);
+            if (count) ctx.d2h(res.data(), d_res.get(), res.size() * 8);
         }
         commitment_type out;
-        if (count) {
-            std::vector<std::uint64_t> res(count * jl);
-            ctx.d2h(res.data(), d_res.get(), res.size() * 8);
-            for (std::size_t i = 0; i < count; ++i) out.push_back(is_zero(i) ? single_commitment_type::zero() : adapter::g1_from_jacobian(&res[i * jl]));
-        }
+        for (std::size_t i = 0; i < count; ++i) out.push_back(is_zero(index, i) ? single_commitment_type::zero() : adapter::g1_from_jacobian(&res[i * jl]));
         return commit_done(index, std::move(db), std::move(out));
     }
 
 private:
+    typedef std::map<std::size_t, std::array<std::uint64_t, 4>> root_map;    // log_n -> the limbs of the primitive 2^log_n-th root
+
+    /* what commit(index) asks of the batch's columns; .at(): commit() has created the batch's entries (the member threads read them) */
+    bool is_coefficients(std::size_t index, std::size_t i) const { return _resident_coefficients.at(index).count(i) != 0; }
+    /// known to be the zero polynomial: its commitment is the neutral element, no multiexp
+    bool is_zero(std::size_t index, std::size_t i) const {
+        const auto &resident_c = _resident_coefficients.at(index);
+        auto it = resident_c.find(i);
+        return it != resident_c.end() && it->second.known_zero();
+    }
+    bool has_host_columns(std::size_t index, std::size_t lo, std::size_t hi) const {
+        for (std::size_t p = lo; p < hi; ++p)
+            if (_polys.at(index)[p]) return true;
+        return false;
+    }
+
+    /// The pipeline of one device: columns [lo, hi) of batch `index` into `base` (column p at base + 32 (offset[p] - offset[lo])), committed
+    /// against `key` on `ctx`, Jacobian results at d_res + (p - lo) * 3 * coordinate limbs (enqueued only).  The host columns go up in chunks
+    /// on `up`, a second in-order stream of the same GPU (or ctx itself: no overlap): while chunk c is transformed (p.coefficients(),
+    /// kzg.hpp:431: one batched inverse NTT per chunk of equally sized polynomials) and committed (the chunk's multiexps as one batch,
+    /// their bucket reductions sharing one launch), chunk c + 1 crosses PCIe.  At most `first_chunk` columns in the first chunk, `chunk` in
+    /// the others (0: no limit); resident columns are copied on `up` too when `copy_resident`, else they are in place already.
+    void commit_columns(std::size_t index, const device_batch &db, std::size_t lo, std::size_t hi, char *base, const context &ctx, const context &up,
+                        const zkhip_bases *key, void *d_res, const root_map &roots, std::size_t first_chunk, std::size_t chunk, bool copy_resident) const {
+        const std::vector<const poly_type *> &polys = _polys.at(index);
+        const auto &resident = _resident.at(index);
+        const auto &resident_c = _resident_coefficients.at(index);
+        const std::size_t jl = 3 * adapter::g1_coord_limbs;
+        auto at = [&](std::size_t p) { return base + 32 * (db.offset[p] - db.offset[lo]); };
+        for (std::size_t i = lo; i < hi;) {
+            const std::size_t limit = i == lo ? first_chunk : chunk;
+            const bool coefficients = resident_c.count(i) != 0, zero = is_zero(index, i);
+            std::size_t j = i;
+            while (j < hi && db.len[j] == db.len[i] && (resident_c.count(j) != 0) == coefficients && is_zero(index, j) == zero && (limit == 0 || j - i < limit)) ++j;
+            for (std::size_t p = i; p < j; ++p) {
+                if (polys[p]) upload_scalars<adapter>(up, at(p), detail::poly_data<adapter>(*polys[p]), polys[p]->size());
+                else if (copy_resident)
+                    check(zkhip_memcpy_d2d_async(up.get(), at(p), resident_c.count(p) ? resident_c.at(p).data() : resident.at(p).data(), db.len[p] * 32),
+                          "zkhip_memcpy_d2d_async", up.get());
+            }
+            if (&up != &ctx) ctx.wait_for(up);
+            if (!coefficients) {
+                const std::size_t log_n = detail::ceil_log2(db.len[i]);
+                check(zkhip_ntt_dev(ctx.get(), adapter::id, at(i), log_n, j - i, roots.at(log_n).data(), 1, nullptr), "zkhip_ntt_dev", ctx.get());
+            }
+            if (!zero) {    // the coefficients of a known-zero polynomial still go into the batch (proof_eval reads them)
+                const std::size_t cnt = j - i;
+                std::vector<const zkhip_bases *> qb(cnt, key);
+                std::vector<std::size_t> qo(cnt, 0), qn(db.len.begin() + i, db.len.begin() + j);
+                std::vector<const void *> qs(cnt);
+                std::vector<void *> qr(cnt);
+                for (std::size_t c = 0; c < cnt; ++c) {
+                    qs[c] = at(i + c);
+                    qr[c] = static_cast<std::uint64_t *>(d_res) + (i + c - lo) * jl;
+                }
+                check(zkhip_msm_batch_dev(ctx.get(), cnt, qb.data(), qo.data(), qn.data(), qs.data(), qr.data()), "zkhip_msm_batch_dev", ctx.get());
+            }
+            i = j;
+        }
+    }
+
     /// state_commited (batched_commitment.hpp:163-166).  The host polynomials are not read again: lent ones may go; copies and
     /// handed-over ones are released with the scheme (freeing gigabytes of host memory here costs ~100 ms: more than the upload)
     commitment_type commit_done(std::size_t index, device_batch &&db, commitment_type &&out) {
@@ -340,146 +376,56 @@ private:
     }
 
     /// commit(index) over the device group: member k takes the k-th contiguous range of the batch's columns.  Resident polynomials (they
-    /// live on member 0's GPU) are dealt first, device to device, from this thread; then every member runs on a host thread of its own --
-    /// uploads of its host columns (the members' PCIe links work side by side), one batched inverse transform per run of equal sizes, its
-    /// multiexps as one batch, one small download of its commitments -- and what is left for this thread is to pull the coefficient forms
-    /// of the other members into member 0's batch buffer, where proof_eval expects them.
-    commitment_type commit_group(std::size_t index) {
+    /// live on member 0's GPU) are dealt first, device to device, from this thread; then every member runs commit_columns on a host thread of
+    /// its own -- uploads of its host columns (the members' PCIe links work side by side) on its own upload stream, a third of its columns
+    /// per chunk at most --, and one small download of its commitments into `res`.  What is left for this thread is to pull the coefficient
+    /// forms of the other members into member 0's batch buffer, where proof_eval expects them.
+    void commit_group(std::size_t index, const device_batch &db, const root_map &roots, std::vector<std::uint64_t> &res) {
         const group_params_type &gp = *_group_params;
         const device_group &group = gp.group;
-        const std::size_t world = gp.members.size(), jl = 3 * adapter::g1_coord_limbs;
-        const context &root = _params.ctx;
-        const std::vector<const poly_type *> &polys = _polys[index];
-        const auto &resident = _resident[index];
-        const auto &resident_c = _resident_coefficients[index];
-        auto is_coefficients = [&resident_c](std::size_t i) { return resident_c.count(i) != 0; };
-        auto is_zero = [&resident_c](std::size_t i) {
-            auto it = resident_c.find(i);
-            return it != resident_c.end() && it->second.known_zero();
-        };
-        const std::size_t count = polys.size();
-        device_batch db;
-        std::size_t total = 0;
-        for (std::size_t i = 0; i < count; ++i) {
-            const std::size_t sz = polys[i] ? polys[i]->size() : is_coefficients(i) ? resident_c.at(i).size() : resident.at(i).size();
-            if (sz == 0 || (sz & (sz - 1))) throw std::runtime_error("commit: polynomial_dfs size must be a power of two");
-            if (sz > _params.commitment_key.size()) throw std::runtime_error("commit: polynomial longer than the commitment key");
-            db.offset.push_back(total);
-            db.len.push_back(sz);
-            total += sz;
-        }
-        db.data = root.alloc(std::max<std::size_t>(1, total) * 32);
+        const std::size_t world = gp.members.size(), count = db.len.size(), jl = 3 * adapter::g1_coord_limbs;
         /* member k's columns [lo, hi): a contiguous range, so its coefficient forms are ONE contiguous piece of the batch buffer */
         struct part {
-            std::size_t lo = 0, hi = 0;
+            std::size_t lo = 0, hi = 0, elems = 0;
             std::shared_ptr<void> data, d_res;    // data: the member's own buffer (member 0 works in the batch buffer itself)
             char *base = nullptr;
-            std::vector<std::uint64_t> res;
         };
         std::vector<part> parts(world);
         for (std::size_t k = 0; k < world; ++k) {
             part &pt = parts[k];
-            pt.lo = count / world * k + std::min(k, count % world);
-            pt.hi = count / world * (k + 1) + std::min(k + 1, count % world);
+            std::tie(pt.lo, pt.hi) = detail::even_range(count, world, k);
             if (pt.hi == pt.lo) continue;
-            const std::size_t elems = (pt.hi < count ? db.offset[pt.hi] : total) - db.offset[pt.lo];
+            pt.elems = (pt.hi < count ? db.offset[pt.hi] : db.offset.back() + db.len.back()) - db.offset[pt.lo];
             if (k == 0) pt.base = static_cast<char *>(db.at(pt.lo));
             else {
-                pt.data = group[k].alloc(elems * 32);
+                pt.data = group[k].alloc(pt.elems * 32);
                 pt.base = static_cast<char *>(pt.data.get());
             }
             pt.d_res = group[k].alloc((pt.hi - pt.lo) * jl * 8);
-            pt.res.resize((pt.hi - pt.lo) * jl);
             /* resident polynomials: off member 0's GPU, in the order of this (the group's) thread */
             for (std::size_t p = pt.lo; p < pt.hi; ++p) {
-                if (polys[p]) continue;
-                const void *src = is_coefficients(p) ? resident_c.at(p).data() : resident.at(p).data();
+                if (_polys.at(index)[p]) continue;
+                const void *src = is_coefficients(index, p) ? _resident_coefficients.at(index).at(p).data() : _resident.at(index).at(p).data();
                 group.copy(k, pt.base + 32 * (db.offset[p] - db.offset[pt.lo]), 0, src, db.len[p] * 32);
             }
         }
-        /* the caller's root-of-unity function is called from THIS thread only (it need not be thread-safe): one root per distinct size, up front */
-        std::map<std::size_t, std::array<std::uint64_t, 4>> root_limbs;
-        for (std::size_t i = 0; i < count; ++i) {
-            if (is_coefficients(i)) continue;
-            std::size_t log_n = 0;
-            while (((std::size_t)1 << log_n) < db.len[i]) ++log_n;
-            if (!root_limbs.count(log_n)) adapter::scalar_to_limbs(_root_of_unity(log_n), root_limbs[log_n].data());
-        }
-        auto member_work = [&](std::size_t k) {
-            part &pt = parts[k];
+        _member_up.resize(world);
+        group.for_each_member([&](std::size_t k) {
+            const part &pt = parts[k];
             if (pt.hi == pt.lo) return;
             const context &ctx = group[k];
-            const kzg_params_hip<CurveType> &params = *gp.members[k];
-            auto at = [&](std::size_t p) { return pt.base + 32 * (db.offset[p] - db.offset[pt.lo]); };
-            /* the member's own pipeline, as commit() runs it on one device: its host columns go up in chunks on a second in-order stream of
-               ITS GPU while the chunk before is transformed and committed (a third of the member's columns per chunk, at most upload_chunk) */
-            bool any_from_host = false;
-            for (std::size_t p = pt.lo; p < pt.hi; ++p) any_from_host = any_from_host || polys[p] != nullptr;
             const std::size_t mine = pt.hi - pt.lo, chunk = upload_chunk ? std::max<std::size_t>(1, std::min(upload_chunk, (mine + 2) / 3)) : 0;
-            const bool pipelined = chunk != 0 && mine > chunk && any_from_host;
-            std::unique_ptr<context> up_own;
-            if (pipelined) up_own.reset(new context(ctx.device()));
-            const context &up = pipelined ? *up_own : ctx;
-            for (std::size_t i = pt.lo; i < pt.hi;) {
-                std::size_t j = i;
-                while (j < pt.hi && db.len[j] == db.len[i] && is_coefficients(j) == is_coefficients(i) && is_zero(j) == is_zero(i) && (!pipelined || j - i < chunk)) ++j;
-                for (std::size_t p = i; p < j; ++p)
-                    if (polys[p]) upload_scalars<adapter>(up, at(p), detail::poly_data<adapter>(*polys[p]), polys[p]->size());
-                if (pipelined) ctx.wait_for(up);
-                if (!is_coefficients(i)) {
-                    std::size_t log_n = 0;
-                    while (((std::size_t)1 << log_n) < db.len[i]) ++log_n;
-                    check(zkhip_ntt_dev(ctx.get(), adapter::id, at(i), log_n, j - i, root_limbs.at(log_n).data(), 1, nullptr), "zkhip_ntt_dev", ctx.get());
-                }
-                if (!is_zero(i)) {
-                    const std::size_t cnt = j - i;
-                    std::vector<const zkhip_bases *> qb(cnt, params.commitment_key.get());
-                    std::vector<std::size_t> qo(cnt, 0), qn(db.len.begin() + i, db.len.begin() + j);
-                    std::vector<const void *> qs(cnt);
-                    std::vector<void *> qr(cnt);
-                    for (std::size_t c = 0; c < cnt; ++c) {
-                        qs[c] = at(i + c);
-                        qr[c] = static_cast<std::uint64_t *>(pt.d_res.get()) + (i + c - pt.lo) * jl;
-                    }
-                    check(zkhip_msm_batch_dev(ctx.get(), cnt, qb.data(), qo.data(), qn.data(), qs.data(), qr.data()), "zkhip_msm_batch_dev", ctx.get());
-                }
-                i = j;
-            }
-            ctx.d2h(pt.res.data(), pt.d_res.get(), pt.res.size() * 8);    // synchronises this member's stream (its upload stream has drained: every upload is a synchronous copy)
-        };
-        {
-            std::vector<std::future<void>> others;
-            for (std::size_t k = 1; k < world; ++k) others.push_back(std::async(std::launch::async, member_work, k));
-            std::exception_ptr failed;
-            try {
-                member_work(0);
-            } catch (...) {
-                failed = std::current_exception();
-            }
-            for (auto &f : others) {
-                try {
-                    f.get();
-                } catch (...) {
-                    if (!failed) failed = std::current_exception();
-                }
-            }
-            if (failed) std::rethrow_exception(failed);
-        }
+            const bool pipelined = chunk != 0 && mine > chunk && has_host_columns(index, pt.lo, pt.hi);
+            if (pipelined && !_member_up[k]) _member_up[k].reset(new context(ctx.device()));
+            commit_columns(index, db, pt.lo, pt.hi, pt.base, ctx, pipelined ? *_member_up[k] : ctx, gp.members[k]->commitment_key.get(), pt.d_res.get(), roots,
+                           pipelined ? chunk : 0, pipelined ? chunk : 0, false);
+            ctx.d2h(res.data() + pt.lo * jl, pt.d_res.get(), mine * jl * 8);    // synchronises this member's stream (its upload stream has drained: every upload is a synchronous copy)
+        });
         /* the other members' coefficient forms join the batch on member 0 (xGMI peer copies; proof_eval reads them there) */
-        for (std::size_t k = 1; k < world; ++k) {
-            const part &pt = parts[k];
-            if (pt.hi == pt.lo) continue;
-            const std::size_t elems = (pt.hi < count ? db.offset[pt.hi] : total) - db.offset[pt.lo];
-            group.copy(0, db.at(pt.lo), k, pt.base, elems * 32);
-        }
-        root.sync();    // the copies ran on member 0's stream: the members' buffers may go
-        commitment_type out;
-        for (std::size_t k = 0; k < world; ++k)
-            for (std::size_t p = parts[k].lo; p < parts[k].hi; ++p)
-                out.push_back(is_zero(p) ? single_commitment_type::zero() : adapter::g1_from_jacobian(&parts[k].res[(p - parts[k].lo) * jl]));
-        return commit_done(index, std::move(db), std::move(out));
+        for (std::size_t k = 1; k < world; ++k)
+            if (parts[k].hi != parts[k].lo) group.copy(0, db.at(parts[k].lo), k, parts[k].base, parts[k].elems * 32);
+        _params.ctx.sync();    // the copies ran on member 0's stream: the members' buffers may go
     }
-
 public:
 
     /// polynomials per upload chunk (0: the whole batch in one transfer, one shared bucket reduction)
@@ -492,22 +438,6 @@ public:
     const std::map<std::size_t, commitment_type> &commitments() const { return _ind_commitments; }
 
 protected:
-    /// multiexp(commitment_key[0 .. len), coefficients) for polynomials [first, last) of a resident batch, as one device batch
-    /// (enqueued only); results: Jacobian points at d_res + i * 3 * coordinate limbs
-    void commit_resident(const device_batch &db, std::size_t first, std::size_t last, void *d_res) const {
-        const context &ctx = _params.ctx;
-        const std::size_t count = last - first, jl = 3 * adapter::g1_coord_limbs;
-        if (count == 0) return;
-        std::vector<const zkhip_bases *> qb(count, _params.commitment_key.get());
-        std::vector<std::size_t> qo(count, 0), qn(db.len.begin() + first, db.len.begin() + last);
-        std::vector<const void *> qs(count);
-        std::vector<void *> qr(count);
-        for (std::size_t i = 0; i < count; ++i) {
-            qs[i] = db.at(first + i);
-            qr[i] = static_cast<std::uint64_t *>(d_res) + (first + i) * jl;
-        }
-        check(zkhip_msm_batch_dev(ctx.get(), count, qb.data(), qo.data(), qn.data(), qs.data(), qr.data()), "zkhip_msm_batch_dev", ctx.get());
-    }
     /// the second stream the uploads of commit() ride on (created on first use, same GPU)
     const context &upload_context() const {
         if (!_upload_ctx) _upload_ctx.reset(new context(_params.ctx.device()));
@@ -538,7 +468,7 @@ protected:
         std::vector<const void *> send(world);
         std::vector<void *> recv(world, nullptr);
         for (std::size_t k = 0; k < world; ++k) {
-            const std::size_t lo = len / world * k + std::min(k, len % world), hi = len / world * (k + 1) + std::min(k + 1, len % world);
+            const auto [lo, hi] = detail::even_range(len, world, k);
             const void *sc = static_cast<const char *>(d_coeffs) + 32 * lo;
             d_part[k] = group[k].alloc(jl * 8);
             if (k != 0) {
@@ -670,6 +600,7 @@ protected:
     std::map<std::size_t, commitment_type> _ind_commitments;
     std::vector<scalar_value_type> _merged_points;
     mutable std::unique_ptr<context> _upload_ctx;
+    std::vector<std::unique_ptr<context>> _member_up;    // over a device group: each member's upload stream (created on first use, same GPU)
     const group_params_type *_group_params = nullptr;    // set: commit(batch) deals its columns over this group's members
     mutable std::size_t _group_multiexps = 0;
 };

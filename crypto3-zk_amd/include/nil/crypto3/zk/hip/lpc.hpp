@@ -44,12 +44,11 @@
 #include <chrono>
 #include <deque>
 #include <functional>
-#include <future>
 #include <iterator>
 #include <map>
 #include <memory>
 #include <set>
-#include <thread>
+#include <tuple>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -207,7 +206,6 @@ public:
 
     /// commit(index) (lpc.hpp:101-106): precommit<FRI>(polys, D[0], step_list.front()) -> the tree's root
     commitment_type commit(std::size_t index) {
-        if (_group && _group->size() > 1 && !_polys[index].empty()) return commit_group(index);
         ZKHIP_PROFILE_SCOPE("Basic FRI Precommit time");    // commit = precommit<FRI> + root (lpc.hpp:101-106; the scope of basic_fri.hpp:449)
         const std::vector<const poly_type *> &polys = _polys[index];
         _locked[index] = true;    // state_commited (batched_commitment.hpp:163-166)
@@ -221,30 +219,21 @@ public:
             total += p->size();
         }
         db.data = _ctx.alloc(std::max<std::size_t>(1, total) * 32);
-        /* poly.resize(D[0]->size()) for every polynomial (basic_fri.hpp:452-455): one call per chunk of equally sized polynomials; it
-           leaves the COEFFICIENTS in the source buffer, which is what proof_eval reads later.  The chunks go up on a second in-order
-           stream: chunk c + 1 crosses PCIe while chunk c is transformed. */
         const std::size_t D = domain_size(0), count = polys.size();
-        void *d_ext = scratch(_scratch_ext, _scratch_ext_cap, std::max<std::size_t>(1, count) * D * 32);    // kept across commits: no GB-sized hipMalloc per batch
-        std::uint64_t wd[4];
-        adapter::scalar_to_limbs(_fri_params.root_of_unity(_fri_params.log_domain), wd);
-        const bool pipelined = upload_chunk != 0 && count > upload_chunk;
-        const context &up = pipelined ? upload_context() : _ctx;
-        for (std::size_t i = 0; i < count;) {
-            std::size_t j = i;
-            while (j < count && db.len[j] == db.len[i] && (upload_chunk == 0 || j - i < upload_chunk)) ++j;
-            for (std::size_t p = i; p < j; ++p) upload_scalars<adapter>(up, db.at(p), detail::poly_data<adapter>(*polys[p]), polys[p]->size());
-            if (pipelined) _ctx.wait_for(up);
-            const std::size_t log_n = log2_of(db.len[i]);
-            std::uint64_t wn[4];
-            adapter::scalar_to_limbs(_fri_params.root_of_unity(log_n), wn);
-            check(zkhip_poly_resize_dev(_ctx.get(), adapter::id, db.at(i), log_n, j - i, wn, static_cast<char *>(d_ext) + 32 * i * D,
-                                        _fri_params.log_domain, wd),
-                  "zkhip_poly_resize_dev", _ctx.get());
-            i = j;
+        /* the caller's root-of-unity function is called from THIS thread only: one root per distinct size, up front */
+        root_map roots;
+        adapter::scalar_to_limbs(_fri_params.root_of_unity(_fri_params.log_domain), roots[_fri_params.log_domain].data());
+        for (std::size_t i = 0; i < count; ++i) {
+            const std::size_t log_n = detail::ceil_log2(db.len[i]);
+            if (!roots.count(log_n)) adapter::scalar_to_limbs(_fri_params.root_of_unity(log_n), roots[log_n].data());
         }
-        _trees.erase(index);
-        _trees.emplace(index, build_tree(d_ext, count, _fri_params.log_domain, _fri_params.step_list.front()));
+        if (_group && _group->size() > 1 && count) commit_group(index, polys, db, roots);
+        else {
+            char *d_ext = static_cast<char *>(_scratch_ext.reserve(_ctx, std::max<std::size_t>(1, count) * D * 32));    // kept across commits: no GB-sized hipMalloc per batch
+            extend_columns(polys, db, 0, count, static_cast<char *>(db.data.get()), _ctx, _upload_ctx, d_ext, roots);
+            _trees.erase(index);
+            _trees.emplace(index, build_tree(d_ext, count, _fri_params.log_domain, _fri_params.step_list.front()));
+        }
         _dev[index] = std::move(db);
         /* the host polynomials are not read again: lent ones may go; copies and handed-over ones are released with the scheme (freeing
            gigabytes of host memory here would cost more than the commit's device work) */
@@ -261,8 +250,40 @@ public:
     /// elements per slice handed to a streaming tree builder (rounded up to whole leaves)
     std::size_t leaf_slice_elements = (std::size_t)1 << 21;
 
+protected:
+    struct device_batch {
+        std::shared_ptr<void> data;    // after commit: the coefficient forms
+        std::vector<std::size_t> offset, len;
+        void *at(std::size_t i) const { return static_cast<char *>(data.get()) + 32 * offset[i]; }
+    };
+    typedef std::map<std::size_t, std::array<std::uint64_t, 4>> root_map;    // log_n -> the limbs of the primitive 2^log_n-th root
+
+    /// poly.resize(D[0]->size()) (basic_fri.hpp:452-455) for polys [lo, hi) of a batch on `ctx`, one call per chunk of equally sized
+    /// polynomials: uploaded into `base` (polynomial p at base + 32 (offset[p] - offset[lo])), where the call leaves the COEFFICIENTS proof_eval
+    /// reads later, and extended to d_ext + 32 (p - lo) D.  The chunks go up on a second in-order stream (`up`, created on first use, same
+    /// GPU): chunk c + 1 crosses PCIe while chunk c is transformed.  Enqueued only.
+    void extend_columns(const std::vector<const poly_type *> &polys, const device_batch &db, std::size_t lo, std::size_t hi, char *base, const context &ctx,
+                        std::unique_ptr<context> &up, char *d_ext, const root_map &roots) const {
+        const std::size_t D = domain_size(0);
+        const bool pipelined = upload_chunk != 0 && hi - lo > upload_chunk;
+        if (pipelined && !up) up.reset(new context(ctx.device()));
+        const context &upc = pipelined ? *up : ctx;
+        auto at = [&](std::size_t p) { return base + 32 * (db.offset[p] - db.offset[lo]); };
+        for (std::size_t i = lo; i < hi;) {
+            std::size_t j = i;
+            while (j < hi && db.len[j] == db.len[i] && (upload_chunk == 0 || j - i < upload_chunk)) ++j;
+            for (std::size_t p = i; p < j; ++p) upload_scalars<adapter>(upc, at(p), detail::poly_data<adapter>(*polys[p]), polys[p]->size());
+            if (pipelined) ctx.wait_for(upc);
+            const std::size_t log_n = detail::ceil_log2(db.len[i]);
+            check(zkhip_poly_resize_dev(ctx.get(), adapter::id, at(i), log_n, j - i, roots.at(log_n).data(), d_ext + 32 * (i - lo) * D, _fri_params.log_domain,
+                                        roots.at(_fri_params.log_domain).data()),
+                  "zkhip_poly_resize_dev", ctx.get());
+            i = j;
+        }
+    }
+
     /// commit(index) over the device group.  Member k takes the k-th contiguous range of the batch's polynomials: its host thread uploads them
-    /// over the member's own link (chunked, a second in-order stream, as on one device) and extends them to D[0] on the member's GPU.  The
+    /// over the member's own link and extends them to D[0] on the member's GPU (extend_columns, as on one device).  The
     /// leaves are then cut by RANGE over the first 2^k members (the leaf owners): leaf x reads, of every polynomial, the positions
     /// x + j D / 2^step (fri_leaf_gather, poly.hip), so an owner's L = D / 2^step / owners consecutive leaves read 2^step segments of L
     /// consecutive evaluations per polynomial -- packed side by side they ARE the evaluations over a domain of D / owners points as far as the
@@ -271,21 +292,8 @@ public:
     /// owner's buffer (zkhip_group_copy: ordered after the extension on the source's stream, on the owner's stream); owners x members
     /// copies of count / members x D / owners elements each.  Each owner then sends its leaves to the host over its own link while the
     /// caller hashes.  The coefficient forms the extension leaves behind are gathered on member 0 for proof_eval.
-    commitment_type commit_group(std::size_t index) {
-        ZKHIP_PROFILE_SCOPE("Basic FRI Precommit time");
+    void commit_group(std::size_t index, const std::vector<const poly_type *> &polys, const device_batch &db, const root_map &roots) {
         const device_group &group = *_group;
-        const std::vector<const poly_type *> &polys = _polys[index];
-        _locked[index] = true;
-        _points[index].resize(polys.size());
-        device_batch db;
-        std::size_t total = 0;
-        for (const poly_type *p : polys) {
-            if (p->size() == 0 || (p->size() & (p->size() - 1)) || p->size() > domain_size(0)) throw std::runtime_error("lpc commit: bad polynomial size");
-            db.offset.push_back(total);
-            db.len.push_back(p->size());
-            total += p->size();
-        }
-        db.data = _ctx.alloc(std::max<std::size_t>(1, total) * 32);
         const std::size_t D = domain_size(0), count = polys.size(), world = group.size(), step = _fri_params.step_list.front();
         std::size_t log_owners = 0;    // owners: a power of two (the compact domain is one), every owner with at least one leaf
         while (((std::size_t)2 << log_owners) <= world && _fri_params.log_domain >= step + log_owners + 1) ++log_owners;
@@ -298,52 +306,30 @@ public:
         std::vector<part> parts(world);
         for (std::size_t k = 0; k < world; ++k) {
             part &pt = parts[k];
-            pt.lo = count / world * k + std::min(k, count % world);
-            pt.hi = count / world * (k + 1) + std::min(k + 1, count % world);
+            std::tie(pt.lo, pt.hi) = detail::even_range(count, world, k);
             group_scratch &gs = _gs[k];
             if (k < owners) {
-                grow(group[k], gs.cmp, gs.cmp_cap, count * Ds * 32);
-                grow(group[k], gs.leaves, gs.leaves_cap, count * Ds * 32);
+                gs.cmp.reserve(group[k], count * Ds * 32);
+                gs.leaves.reserve(group[k], count * Ds * 32);
             }
             if (pt.hi == pt.lo) continue;
-            pt.elems = (pt.hi < count ? db.offset[pt.hi] : total) - db.offset[pt.lo];
+            pt.elems = (pt.hi < count ? db.offset[pt.hi] : db.offset.back() + db.len.back()) - db.offset[pt.lo];
             if (k == 0) pt.base = static_cast<char *>(db.at(pt.lo));
             else {
                 pt.data = group[k].alloc(pt.elems * 32);
                 pt.base = static_cast<char *>(pt.data.get());
             }
-            grow(group[k], gs.ext, gs.ext_cap, (pt.hi - pt.lo) * D * 32);
-            grow(group[k], gs.send, gs.send_cap, (pt.hi - pt.lo) * D * 32);    // owners blocks of (hi - lo) * Ds
+            gs.ext.reserve(group[k], (pt.hi - pt.lo) * D * 32);
+            gs.send.reserve(group[k], (pt.hi - pt.lo) * D * 32);    // owners blocks of (hi - lo) * Ds
         }
-        /* the caller's root-of-unity function is called from THIS thread only: one root per distinct size, up front */
-        std::map<std::size_t, std::array<std::uint64_t, 4>> root_limbs;
-        adapter::scalar_to_limbs(_fri_params.root_of_unity(_fri_params.log_domain), root_limbs[_fri_params.log_domain].data());
-        for (std::size_t i = 0; i < count; ++i) {
-            const std::size_t log_n = log2_of(db.len[i]);
-            if (!root_limbs.count(log_n)) adapter::scalar_to_limbs(_fri_params.root_of_unity(log_n), root_limbs[log_n].data());
-        }
-        auto member_work = [&](std::size_t k) {
-            part &pt = parts[k];
+        group.for_each_member([&](std::size_t k) {
+            const part &pt = parts[k];
             if (pt.hi == pt.lo) return;
             const context &ctx = group[k];
             group_scratch &gs = _gs[k];
             const std::size_t mine = pt.hi - pt.lo;
-            auto at = [&](std::size_t p) { return pt.base + 32 * (db.offset[p] - db.offset[pt.lo]); };
-            const bool pipelined = upload_chunk != 0 && mine > upload_chunk;
-            if (pipelined && !gs.up) gs.up.reset(new context(ctx.device()));
-            const context &up = pipelined ? *gs.up : ctx;
             char *d_ext = static_cast<char *>(gs.ext.get());
-            for (std::size_t i = pt.lo; i < pt.hi;) {
-                std::size_t j = i;
-                while (j < pt.hi && db.len[j] == db.len[i] && (upload_chunk == 0 || j - i < upload_chunk)) ++j;
-                for (std::size_t p = i; p < j; ++p) upload_scalars<adapter>(up, at(p), detail::poly_data<adapter>(*polys[p]), polys[p]->size());
-                if (pipelined) ctx.wait_for(up);
-                const std::size_t log_n = log2_of(db.len[i]);
-                check(zkhip_poly_resize_dev(ctx.get(), adapter::id, at(i), log_n, j - i, root_limbs.at(log_n).data(), d_ext + 32 * (i - pt.lo) * D,
-                                            _fri_params.log_domain, root_limbs.at(_fri_params.log_domain).data()),
-                      "zkhip_poly_resize_dev", ctx.get());
-                i = j;
-            }
+            extend_columns(polys, db, pt.lo, pt.hi, pt.base, ctx, gs.up, d_ext, roots);
             /* per owner: the 2^step segments [d seg + j D / 2^step, + seg) of each of my polynomials, side by side (rows of seg elements at a
                pitch of D / 2^step in, seg out) -- straight into my own buffer where I am the owner */
             for (std::size_t d = 0; d < owners; ++d) {
@@ -351,32 +337,7 @@ public:
                 check(zkhip_memcpy_2d_d2d_async(ctx.get(), dst, seg * 32, d_ext + 32 * d * seg, (D >> step) * 32, seg * 32, mine * rows_per_poly),
                       "zkhip_memcpy_2d_d2d_async", ctx.get());
             }
-        };
-        {
-            std::vector<std::future<void>> others;
-            for (std::size_t k = 1; k < world; ++k)
-                if (parts[k].hi != parts[k].lo) others.push_back(std::async(std::launch::async, member_work, k));
-            std::exception_ptr failed;
-            try {
-                member_work(0);
-            } catch (...) {
-                failed = std::current_exception();
-            }
-            for (auto &o : others) {
-                try {
-                    o.get();
-                } catch (...) {
-                    if (!failed) failed = std::current_exception();
-                }
-            }
-            if (failed) {
-                try {
-                    group.sync();    // nothing of this batch may still be running on buffers that are about to go
-                } catch (...) {
-                }
-                std::rethrow_exception(failed);
-            }
-        }
+        });
         /* the exchange, from this thread: blocks to their owners, coefficient forms to member 0 */
         for (std::size_t k = 0; k < world; ++k) {
             const part &pt = parts[k];
@@ -399,11 +360,9 @@ public:
         group.sync();    // the members' own coefficient buffers go with `parts`: every copy out of them has finished
         ++_group_commits;
         _last_owners = owners;
-        _dev[index] = std::move(db);
-        _polys[index].clear();    // no pointer to a lent polynomial outlives the call
-        return _trees.at(index).root();
     }
 
+public:
     /// proof_eval (lpc.hpp:113-200) up to and including the FRI commit phase (basic_fri.hpp:705-742)
     proof_type proof_eval(transcript_type &transcript) {
         /* ZKHIP_LPC_PHASES=1: host wall time of the phases on stderr */
@@ -560,21 +519,11 @@ public:
     }
 
 protected:
-    struct device_batch {
-        std::shared_ptr<void> data;    // after commit: the coefficient forms
-        std::vector<std::size_t> offset, len;
-        void *at(std::size_t i) const { return static_cast<char *>(data.get()) + 32 * offset[i]; }
-    };
     std::size_t domain_size(std::size_t t) const { return (std::size_t)1 << (_fri_params.log_domain - t); }
-    static std::size_t log2_of(std::size_t n) {
-        std::size_t l = 0;
-        while (((std::size_t)1 << l) < n) ++l;
-        return l;
-    }
     /// the leaf layout of `batch` polynomials resident as evaluations over the 2^log_domain-point domain -> the caller's tree
     precommitment_type build_tree(const void *d_evals, std::size_t batch, std::size_t log_domain, std::size_t fri_step) const {
         const std::size_t D = (std::size_t)1 << log_domain, total = batch * D, per_leaf = batch * ((std::size_t)1 << fri_step);
-        void *d_leaves = scratch(_scratch_leaves, _scratch_leaves_cap, std::max<std::size_t>(1, total) * 32);
+        void *d_leaves = _scratch_leaves.reserve(_ctx, std::max<std::size_t>(1, total) * 32);
         check(zkhip_fri_leaves_dev(_ctx.get(), d_evals, log_domain, batch, fri_step, d_leaves), "zkhip_fri_leaves_dev", _ctx.get());
         if constexpr (builder_kind == detail::tree_builder_kind::streaming) {
             /* slices of whole leaves through two page-locked buffers: the copy of slice k + 1 is in flight while the caller absorbs slice k */
@@ -645,16 +594,6 @@ protected:
             }
         }
     }
-    /// a member's device buffer that grows on demand and is kept across commits
-    static void *grow(const context &ctx, std::shared_ptr<void> &buf, std::size_t &cap, std::size_t bytes) {
-        if (bytes > cap) {
-            ctx.sync();
-            buf.reset();
-            buf = ctx.alloc(bytes);
-            cap = bytes;
-        }
-        return buf.get();
-    }
     /// `count` canonical 32-byte elements in host memory as scalar-field values: in place when the scalar type IS four canonical
     /// limbs, through a converted copy (host threads) otherwise
     const value_type *host_values(const void *limbs, std::size_t count) const {
@@ -664,29 +603,11 @@ protected:
         } else {
             _conv.resize(count);
             const std::uint64_t *h = static_cast<const std::uint64_t *>(limbs);
-            const std::size_t lanes = count >= ((std::size_t)1 << 16) ? std::max(1u, std::min(8u, std::thread::hardware_concurrency())) : 1;
-            std::vector<std::future<void>> work;
-            for (std::size_t k = 0; k < lanes; ++k)
-                work.push_back(std::async(lanes > 1 ? std::launch::async : std::launch::deferred, [&, k]() {
-                    for (std::size_t i = count * k / lanes; i < count * (k + 1) / lanes; ++i) _conv[i] = adapter::scalar_from_limbs(h + 4 * i);
-                }));
-            for (auto &w : work) w.get();
+            detail::host_parallel_for(count, (std::size_t)1 << 16, 8, [&](std::size_t lo, std::size_t hi) {
+                for (std::size_t i = lo; i < hi; ++i) _conv[i] = adapter::scalar_from_limbs(h + 4 * i);
+            });
             return _conv.data();
         }
-    }
-    const context &upload_context() const {
-        if (!_upload_ctx) _upload_ctx.reset(new context(_ctx.device()));
-        return *_upload_ctx;
-    }
-    /// a device scratch buffer that grows on demand and is kept (every use is ordered on the context's stream)
-    void *scratch(std::shared_ptr<void> &buf, std::size_t &cap, std::size_t bytes) const {
-        if (bytes > cap) {
-            _ctx.sync();
-            buf.reset();
-            buf = _ctx.alloc(bytes);
-            cap = bytes;
-        }
-        return buf.get();
     }
     void own(std::size_t index, poly_type &&poly) {
         if (_locked[index]) throw std::runtime_error("append_to_batch: batch already committed");
@@ -753,8 +674,7 @@ protected:
 
     /// per member of the group, kept across commits: extensions, blocks to send, the owner's compact evaluations and its leaves
     struct group_scratch {
-        std::shared_ptr<void> ext, send, cmp, leaves;
-        std::size_t ext_cap = 0, send_cap = 0, cmp_cap = 0, leaves_cap = 0;
+        device_scratch ext, send, cmp, leaves;
         pinned_buffer pin[2];
         std::unique_ptr<context> up;    // the member's upload stream
     };
@@ -767,11 +687,10 @@ protected:
     value_type _etha;
     std::map<std::size_t, std::vector<const poly_type *>> _polys;    // in append order: copies held in _owned, or the caller's (lent)
     std::map<std::size_t, std::deque<poly_type>> _owned;
-    mutable std::unique_ptr<context> _upload_ctx;
+    mutable std::unique_ptr<context> _upload_ctx;    // the second stream the uploads of commit() ride on
     mutable pinned_buffer _pin[2];
     mutable std::vector<value_type> _leaf_vec, _conv;
-    mutable std::shared_ptr<void> _scratch_ext, _scratch_leaves;
-    mutable std::size_t _scratch_ext_cap = 0, _scratch_leaves_cap = 0;
+    mutable device_scratch _scratch_ext, _scratch_leaves;    // kept across commits (every use is ordered on _ctx's stream)
     std::map<std::size_t, bool> _locked, _batch_fixed;
     std::map<std::size_t, std::vector<std::vector<value_type>>> _points;
     std::map<std::size_t, device_batch> _dev;

@@ -53,9 +53,10 @@ struct placeholder_lookup_hip {
         if (p.size() == new_domain_size) return p;
         const context &ctx = p.ctx();
         dfs_type out(ctx, new_domain_size);
+        const std::size_t lp = detail::ceil_log2(p.size()), ln = detail::ceil_log2(new_domain_size);
+        if (((std::size_t)1 << lp) != p.size() || ((std::size_t)1 << ln) != new_domain_size) throw std::invalid_argument("lookup argument: sizes must be powers of two");
         std::uint64_t unused[4] = {1, 0, 0, 0};
-        check(zkhip_poly_resize_dev(ctx.get(), adapter::id, p.data(), log2_of(p.size()), 1, unused, out.data(), log2_of(new_domain_size), unused), "zkhip_poly_resize_dev",
-              ctx.get());
+        check(zkhip_poly_resize_dev(ctx.get(), adapter::id, p.data(), lp, 1, unused, out.data(), ln, unused), "zkhip_poly_resize_dev", ctx.get());
         return out;
     }
 
@@ -246,12 +247,6 @@ struct placeholder_lookup_hip {
     }
 
 private:
-    static std::size_t log2_of(std::size_t n) {
-        std::size_t l = 0;
-        while (((std::size_t)1 << l) < n) ++l;
-        if (n == 0 || ((std::size_t)1 << l) != n) throw std::invalid_argument("lookup argument: sizes must be powers of two");
-        return l;
-    }
     static dfs_type minus(const dfs_type &a, const dfs_type &b, const root_of_unity_type &root) { return placeholder_permutation_hip<CurveType>::minus(a, b, root); }
 };
 

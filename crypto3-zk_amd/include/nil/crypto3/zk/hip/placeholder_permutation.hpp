@@ -227,9 +227,7 @@ struct placeholder_permutation_hip {
         if (p.size() == n) return p;
         if (p.size() < n || p.size() % n) throw std::invalid_argument("permutation argument: not an extension of the basic domain");
         dfs_type out(p.ctx(), n);
-        std::size_t lp = 0, ln = 0;
-        while (((std::size_t)1 << lp) < p.size()) ++lp;
-        while (((std::size_t)1 << ln) < n) ++ln;
+        const std::size_t lp = detail::ceil_log2(p.size()), ln = detail::ceil_log2(n);
         std::uint64_t unused[4] = {1, 0, 0, 0};
         check(zkhip_poly_resize_dev(p.ctx().get(), adapter::id, p.data(), lp, 1, unused, out.data(), ln, unused), "zkhip_poly_resize_dev", p.ctx().get());
         return out;

@@ -77,9 +77,7 @@ struct placeholder_quotient_hip {
         const dfs_type &mask_polynomial = mask_ptr ? *mask_ptr : *products[0].factors[0];
         const std::size_t mask_degree = mask_ptr ? mask_ptr->degree() : 0;
         const std::size_t n = mask_polynomial.size();
-        std::size_t log_n = 0, log_e = 0;
-        while (((std::size_t)1 << log_n) < n) ++log_n;
-        while (((std::size_t)1 << log_e) < extended_size) ++log_e;
+        const std::size_t log_n = detail::ceil_log2(n), log_e = detail::ceil_log2(extended_size);
         if (((std::size_t)1 << log_n) != n || ((std::size_t)1 << log_e) != extended_size || extended_size < n)
             throw std::invalid_argument("gate_argument: domain sizes must be powers of two, extended >= original");
         const std::int64_t stretch = (std::int64_t)(extended_size / n);    // one row of the original domain = this many of the extended one
@@ -187,9 +185,7 @@ struct placeholder_quotient_hip {
         dfs_type F(ctx, extended_size);
         bool first = true;
         const std::size_t n = mask_polynomial.size();
-        std::size_t log_n = 0, log_e = 0;
-        while (((std::size_t)1 << log_n) < n) ++log_n;
-        while (((std::size_t)1 << log_e) < extended_size) ++log_e;
+        const std::size_t log_n = detail::ceil_log2(n), log_e = detail::ceil_log2(extended_size);
         if (((std::size_t)1 << log_n) != n || ((std::size_t)1 << log_e) != extended_size || extended_size < n)
             throw std::invalid_argument("gate_argument: domain sizes must be powers of two, extended >= original");
         std::uint64_t wn[4], we[4];
@@ -332,8 +328,7 @@ struct placeholder_quotient_hip {
             }
             auto acc = ctx.alloc(gsize * 32);    // sum_i alpha_i F_i over this domain, then its coefficients in place
             check(zkhip_poly_lincomb_dev(ctx.get(), adapter::id, gp.size(), gp.data(), gl.data(), gc.data(), 1, acc.get(), gsize, 0), "zkhip_poly_lincomb_dev", ctx.get());
-            std::size_t log_g = 0;
-            while (((std::size_t)1 << log_g) < gsize) ++log_g;
+            const std::size_t log_g = detail::ceil_log2(gsize);
             if (((std::size_t)1 << log_g) != gsize) throw std::invalid_argument("quotient_polynomial: a part's size is not a power of two");
             std::uint64_t w[4];
             adapter::scalar_to_limbs(root(log_g), w);
@@ -366,8 +361,7 @@ struct placeholder_quotient_hip {
         if (chunks > split_polynomial_size) throw std::invalid_argument("quotient_polynomial_split_dfs: the quotient needs more parts than split_polynomial_size");
         if (dfs_size < rows_amount) throw std::invalid_argument("quotient_polynomial_split_dfs: dfs_size < rows_amount");
         std::vector<dfs_type> out;
-        std::size_t log_size = 0;
-        while (((std::size_t)1 << log_size) < dfs_size) ++log_size;
+        const std::size_t log_size = detail::ceil_log2(dfs_size);
         std::uint64_t w[4];
         adapter::scalar_to_limbs(root(log_size), w);
         for (std::size_t k = 0; k < split_polynomial_size; ++k) {

@@ -27,8 +27,7 @@ std::vector<typename detail::jac_result<CurveType, Group>::type>
     typedef curve_adapter<CurveType> adapter;
     typedef detail::jac_result<CurveType, Group> R;
     const std::size_t m = std::distance(powers_begin, powers_end), cl = R::limbs / 3;
-    std::size_t log_m = 0;
-    while (((std::size_t)1 << log_m) < m) ++log_m;
+    const std::size_t log_m = detail::ceil_log2(m);
     if (m == 0 || ((std::size_t)1 << log_m) != m) throw std::runtime_error("evaluate_all_lagrange_polynomials: the domain size must be a power of two");
     /* canonical Jacobian (x, y, 1) of every power; (0, 0, 0) for the point at infinity */
     std::vector<std::uint64_t> jac(m * R::limbs, 0);

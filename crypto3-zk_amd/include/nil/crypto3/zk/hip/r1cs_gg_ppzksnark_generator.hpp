@@ -71,7 +71,7 @@ qap_instance_evaluation_hip<CurveType> instance_map_with_evaluation(const Constr
     /* A_j(t) = sum_i u_i A_ij (r1cs_to_qap.hpp:164-178), split over host threads BY VARIABLE RANGE: every thread walks all the
        constraints and takes the terms whose variable falls into its range -- no two threads write the same entry, and the field
        products (the cost) are shared out; coefficients 1 (most of a circuit) need no product at all */
-    detail::parallel_chunks(N + 1, [&](std::size_t lo, std::size_t hi) {
+    detail::host_parallel_for(N + 1, (std::size_t)1 << 14, 32, [&](std::size_t lo, std::size_t hi) {
         const Fr one = Fr::one();
         auto take = [&](std::vector<Fr> &dst, const decltype(cs.constraints[0].a.terms) &terms, const Fr &ui) {
             for (const auto &term : terms) {
@@ -87,7 +87,7 @@ qap_instance_evaluation_hip<CurveType> instance_map_with_evaluation(const Constr
         }
     });
     q.Ht.resize(m + 1);
-    detail::parallel_chunks(m + 1, [&](std::size_t lo, std::size_t hi) {
+    detail::host_parallel_for(m + 1, (std::size_t)1 << 14, 32, [&](std::size_t lo, std::size_t hi) {
         Fr ti = detail::pow_u64(t, lo);
         for (std::size_t i = lo; i < hi; ++i) {
             q.Ht[i] = ti;
@@ -151,13 +151,13 @@ public:
         lap("instance_map_with_evaluation");
         /* The delta inverse product component: (beta*A_i(t) + alpha*B_i(t) + C_i(t)) * delta^{-1} (generator.hpp:296-304) */
         std::vector<Fr> Lt(N - n);
-        detail::parallel_chunks(N - n, [&](std::size_t lo, std::size_t hi) {
+        detail::host_parallel_for(N - n, (std::size_t)1 << 14, 32, [&](std::size_t lo, std::size_t hi) {
             for (std::size_t i = lo; i < hi; ++i) Lt[i] = (beta * qap.At[n + 1 + i] + alpha * qap.Bt[n + 1 + i] + qap.Ct[n + 1 + i]) * delta_inverse;
         });
         /* H for Groth's proof system is degree d - 2: Ht loses its top two entries (:310-315); coefficient Zt / delta (:353-355) */
         std::vector<Fr> Hs(m - 1);
         const Fr zd = qap.Zt * delta_inverse;
-        detail::parallel_chunks(m - 1, [&](std::size_t lo, std::size_t hi) {
+        detail::host_parallel_for(m - 1, (std::size_t)1 << 14, 32, [&](std::size_t lo, std::size_t hi) {
             for (std::size_t i = lo; i < hi; ++i) Hs[i] = qap.Ht[i] * zd;
         });
         /* B query: sparse over the non-zero B_i(t) (kc_batch_exp, knowledge_commitment_multiexp.hpp:143-208) */

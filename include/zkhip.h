@@ -17,7 +17,8 @@
  *   - omega and the coset generator are ARGUMENTS (arithmetic_params<F> lives in crypto3-algebra).
  *   - One context per GPU per process (one process per GPU); a context is not thread-safe.  A caller that wants SEVERAL GPUs behind
  *     one call -- the shape of the reference, whose parallelism sits inside process() / commit() -- takes a device group
- *     (zkhip_group_init below): one context per GPU, one host thread, the exchange inside the library.
+ *     (zkhip_group_init below): one context per GPU, the exchange inside the library.  The shim drives member 0 from the caller's
+ *     thread and members 1..N-1 from host threads of its own (a caller's thread-local state does not reach them).
  *   - The library has no CPU fallback: without a usable HIP device every call fails with
  *     ZKHIP_ERR_NO_DEVICE.
  */
@@ -386,8 +387,10 @@ int zkhip_gate_eval_dev(zkhip_ctx *ctx, int curve, const zkhip_gate_program *pro
  * `chunks = omp_get_max_threads()` pieces (r1cs_gg_ppzksnark/prover.hpp:94-99, 108-139) and kzg_commitment_scheme_v2::commit loops
  * over the batch (commitments/polynomial/kzg_v2.hpp:208-226) -- the caller sees one call and one result.  A group is the same for
  * GPUs: one zkhip_ctx per entry of device_ids (SURVEY 8b sketched this as `zkhip_init(const int *device_ids, int n_dev, ...)`),
- * all driven from ONE host thread (every entry point of this ABI is asynchronous on its context's stream), with the one exchange the
- * path has -- the partial sums of a sharded multiexp, <= 864 bytes per member for a Groth16 proof -- INSIDE the library.
+ * every entry point asynchronous on its member's stream, with the one exchange the path has -- the partial sums of a sharded
+ * multiexp, <= 864 bytes per member for a Groth16 proof -- INSIDE the library.  The shim's group paths (device_group::for_each_member)
+ * drive member 0 from the caller's thread and members 1..N-1 from host threads of their own: a caller's thread-local state does not
+ * reach them.
  * device_ids may name a device more than once (several members on one GPU: a 1-GPU box, tests).
  * Members are ordinary contexts (zkhip_group_ctx): every other entry point of this header works on them; they are destroyed with
  * the group.  A group is not thread-safe. */

@@ -2,15 +2,19 @@
 // stub backend (stub_backend.cpp: no GPU, nothing computed).  What runs here is everything the shim does on host threads --
 // std::async conversions and uploads (backend.hpp), the prover's regrouped host products and two-thread assembly
 // (r1cs_gg_ppzksnark.hpp), the generator's thread pool and the evaluation domains' chunked Lagrange evaluation, the chunked /
-// lent uploads of the KZG and LPC schemes and the LPC leaf streaming -- and a mutation loop over proving_key_from_bytes
-// (marshalling.hpp), which parses untrusted blobs: truncations at every framing boundary, oversized and zero counts,
-// non-increasing / out-of-range B indices, random byte flips.  The parser must throw or succeed; the sanitizers decide the rest.
+// lent uploads of the KZG and LPC schemes and the LPC leaf streaming, the fan-out over a device group's members -- and a
+// mutation loop over proving_key_from_bytes (marshalling.hpp), which parses untrusted blobs: truncations at every framing
+// boundary, oversized and zero counts, non-increasing / out-of-range B indices, random byte flips.  The parser must throw or
+// succeed; the sanitizers decide the rest.
+#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <functional>
 #include <random>
+#include <stdexcept>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include <nil/crypto3/zk/hip/column_polynomial.hpp>
@@ -500,6 +504,57 @@ void bulk_transfers() {
     EXPECT(b.size() == pts.size());
 }
 
+/// the helpers the group paths share (backend.hpp): the fan-out over a group's members, the even cut of a range, ceil_log2
+void group_helpers() {
+    EXPECT(detail::ceil_log2(0) == 0 && detail::ceil_log2(1) == 0 && detail::ceil_log2(2) == 1 && detail::ceil_log2(3) == 2);
+    for (std::size_t l = 2; l < 62; ++l) {
+        const std::size_t p = (std::size_t)1 << l;
+        EXPECT(detail::ceil_log2(p - 1) == l && detail::ceil_log2(p) == l && detail::ceil_log2(p + 1) == l + 1);
+    }
+    for (std::size_t world : {1, 2, 3, 5, 8})
+        for (std::size_t n : {0, 1, 2, 4, 5, 7, 8, 9, 1000}) {
+            std::size_t at = 0;
+            for (std::size_t k = 0; k < world; ++k) {
+                const auto [lo, hi] = detail::even_range(n, world, k);
+                EXPECT(lo == at && hi - lo == n / world + (k < n % world ? 1 : 0));    // consecutive; the first n % world one longer
+                at = hi;
+            }
+            EXPECT(at == n);
+        }
+    typedef std::pair<std::size_t, std::size_t> range;
+    EXPECT(detail::even_range(0, 3, 2) == range(0, 0) && detail::even_range(2, 5, 1) == range(1, 2) && detail::even_range(2, 5, 4) == range(2, 2));
+    EXPECT(detail::even_range(10, 3, 0) == range(0, 4) && detail::even_range(10, 3, 2) == range(7, 10));
+
+    /* five members, 2 and 4 throw (4 at once, 2 after a while): every other member runs to the end, member 0 on the calling thread, and the
+       caller sees member 2's exception -- the first in member order */
+    device_group grp(std::vector<int>(5, 0));
+    for (bool threaded : {true, false}) {
+        std::vector<int> done(5, 0);
+        std::vector<std::thread::id> who(5);
+        std::string caught;
+        try {
+            grp.for_each_member(
+                [&](std::size_t k) {
+                    who[k] = std::this_thread::get_id();
+                    if (k == 4) throw std::runtime_error("member 4");
+                    std::this_thread::sleep_for(std::chrono::milliseconds(20));
+                    if (k == 2) throw std::runtime_error("member 2");
+                    done[k] = 1;
+                },
+                threaded);
+        } catch (const std::runtime_error &e) {
+            caught = e.what();
+        }
+        EXPECT(caught == "member 2");
+        EXPECT(done == std::vector<int>({1, 1, 0, 1, 0}));
+        EXPECT(who[0] == std::this_thread::get_id());
+        for (std::size_t k = 1; k < 5; ++k) EXPECT((who[k] == std::this_thread::get_id()) != threaded);
+    }
+    std::vector<int> all(5, 0);
+    grp.for_each_member([&](std::size_t k) { all[k] = (int)k + 1; });
+    EXPECT(all == std::vector<int>({1, 2, 3, 4, 5}));
+}
+
 // ---- the parser fuzz ---------------------------------------------------------------------------------------------------
 struct blob_writer {
     std::vector<std::uint8_t> b;
@@ -619,6 +674,7 @@ int main(int argc, char **argv) {
         placeholder_reference_entry_points<converting_curve>();
         bulk_transfers<converting_curve>();
         bulk_transfers<bls12_381>();
+        group_helpers();
     }
     if (what == "all" || what == "fuzz") parser_fuzz();
     fprintf(stderr, failures ? "sanitize_main: %d FAILED expectation(s)\n" : "sanitize_main: ok\n", failures);
