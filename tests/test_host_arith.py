@@ -86,6 +86,30 @@ def test_fq2_ops(shim, field, curve):
             assert unpack(out) == F.inv(a)
 
 
+@pytest.mark.parametrize("t", [6, 7, 8, 9])
+def test_raw_limbs_at_the_contract_bounds(shim, t):
+    """zkt_fu_raw: the C++ bodies of fu.hpp on raw limbs as a kernel holds them, at the corners of the written contract (tests/arith_cases.py):
+    canonical edges, non-normalised product operands, the column-accumulator maximising pairs, a b (+ c d) just below R p, every sub<K>
+    at its subtrahend bound.  Each result against the big-integer residue and the written postcondition (exact sums and differences,
+    normalised limbs, products < 2p)."""
+    import arith_cases as ac
+    L = ac.TYPES[t][1]
+    counted = 0
+    for op, k, cases in ac.raw_suite(t):
+        rc, out = ac.run_raw(shim.zkt_fu_raw, t, op, *zip(*cases))
+        assert rc == 0, (t, op)
+        for case, r in zip(cases, out):
+            err = ac.check_raw(t, op, *case, r, k=k)
+            assert err is None, (t, op, k, err, [hex(ac.value(x)) for x in case], r)
+        counted += len(cases)
+    assert counted > 800
+    z = [[0] * L]
+    assert ac.run_raw(shim.zkt_fu_raw, t, 11, z)[0] == -1     # no such op
+    assert ac.run_raw(shim.zkt_fu_raw, 5, 0, z)[0] == -1      # a saturated type has no raw limbs
+    if t == 8:                                                # BLS12-381 r: no 128 p spread constant
+        assert ac.run_raw(shim.zkt_fu_raw, t, ac.op_sub(128), z)[0] == -1
+
+
 def _chain(shim, field, curve, group, pts, infs, negs, mode, k=0):
     arr = pts_arr(curve, group, pts).view(np.uint32).reshape(len(pts), -1) if len(pts) else np.zeros((0, 1), dtype=np.uint32)
     arr = np.ascontiguousarray(arr)
@@ -220,3 +244,30 @@ def test_generated_asm_blocks_compute_montgomery_products():
     for _ in range(20):
         ops = {"a": rng.randrange(1 << 386), "b": rng.randrange(1 << 386)}
         assert sim.montgomery_check(k, sim.BLS_Q, ops) == sim.montgomery_check(u, sim.BLS_Q, ops)
+
+
+@pytest.mark.parametrize("kind", ["mul", "sqr", "mul2"])
+def test_generated_asm_blocks_at_the_contract_corners(kind):
+    """The emitted blocks on raw limbs as a lazy kernel holds them (tests/arith_cases.py): non-normalised product operands (limbs up to
+    2^30), the pairs that fill the 64-bit column accumulator the most under a b < R p, squares and shared-reduction pairs just below
+    R p -- each against the big-integer Montgomery product and the written postcondition (normalised limbs)."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import arith_cases as ac
+    import sim_mont_asm as sim
+    from gen_mont_asm import Block
+    for L, modulus, t in ((9, sim.BLS_R, 8), (10, sim.BN_Q, 7), (14, sim.BLS_Q, 6)):
+        assert ac.TYPES[t][0] == modulus and ac.TYPES[t][1] == L
+        blk = Block(L, 29, False, kind)
+        blk.build()
+        crng = random.Random(L)
+        if kind == "mul":
+            cases = [{"a": a, "b": b} for a, b in ac.mul_cases(t, crng)]
+        elif kind == "sqr":
+            cases = [{"a": a} for a in ac.sqr_cases(t, crng)]
+        else:
+            cases = [dict(zip("abcd", v)) for v in ac.mul2_cases(t, crng)]
+        assert len(cases) >= 14
+        for ops in cases:
+            r, ok = sim.montgomery_check(blk, modulus, ops, raw=True)
+            assert ok, (L, kind, {k: hex(ac.value(v)) for k, v in ops.items()}, r)

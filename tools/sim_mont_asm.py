@@ -80,17 +80,26 @@ def run_block(blk, values):
     return val
 
 
-def montgomery_check(blk, modulus, operands):
-    """run an UNSIGNED block (kinds mul, sqr, mul2, kmul) on big-integer operands; returns (result, expected residue check)"""
+def montgomery_check(blk, modulus, operands, raw=False):
+    """run an UNSIGNED block (kinds mul, sqr, mul2, kmul) on big-integer operands; returns (result, expected residue check).
+    raw=True: each operand is a list of L limbs passed as they are (non-normalised limbs up to 2^30, a top limb holding more than
+    B bits), the form a lazy kernel value takes; the residue is checked against the value those limbs hold."""
     L, B = blk.L, blk.B
     mask = (1 << B) - 1
     limbs = lambda x: [(x >> (B * i)) & mask for i in range(L)]  # noqa: E731
     values = {'ninv': (-pow(modulus, -1, 1 << B)) % (1 << B)}
     for i, v in enumerate(limbs(modulus)):
         values['p%d' % i] = v
-    for name, x in operands.items():
-        for i, v in enumerate(limbs(x)):
-            values['%s%d' % (name, i)] = v
+    if raw:
+        for name, x in operands.items():
+            assert len(x) == L and all(0 <= v < 1 << 32 for v in x)
+            for i, v in enumerate(x):
+                values['%s%d' % (name, i)] = v
+        operands = {name: sum(v << (B * i) for i, v in enumerate(x)) for name, x in operands.items()}
+    else:
+        for name, x in operands.items():
+            for i, v in enumerate(limbs(x)):
+                values['%s%d' % (name, i)] = v
     out = run_block(blk, values)
     r = [out['r%d' % i] for i in range(L)]
     if blk.kind == 'sqr':
