@@ -14,6 +14,8 @@ from .zkhip import (  # noqa: F401
     Context,
     DeviceGroup,
     GroupBases,
+    HASH_SHA2_256,
+    MerkleTree,
     R1CS,
     ZkhipError,
     build,

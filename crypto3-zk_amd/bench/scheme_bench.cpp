@@ -14,6 +14,7 @@
 #include <vector>
 
 #include <nil/crypto3/zk/hip/lpc.hpp>
+#include <nil/crypto3/zk/hip/merkle.hpp>
 #include <nil/crypto3/zk/hip/placeholder_lookup.hpp>
 #include <nil/crypto3/zk/hip/placeholder_permutation.hpp>
 #include <nil/crypto3/zk/hip/placeholder_quotient.hpp>
@@ -332,6 +333,47 @@ int zkhip_bench_lpc_scheme(int device, size_t log_n, size_t cols, size_t expand,
         return 0;
     } catch (const std::exception &e) {
         fprintf(stderr, "zkhip_bench_lpc_scheme: %s\n", e.what());
+        return -1;
+    }
+}
+
+/* The same commit (same seeded polynomials, same parameters) with the DEVICE tree builder (hip/merkle.hpp): the SHA2-256 Merkle tree is built on the
+ * GPU straight from the extension -- no leaf layout, no leaf over PCIe -- and commit returns its root.  ms: `steps` commit times; root: the last one. */
+int zkhip_bench_lpc_scheme_device(int device, size_t log_n, size_t cols, size_t expand, int steps, double *ms, uint8_t *root) {
+    try {
+        const size_t n = (size_t)1 << log_n;
+        context ctx(device);
+        fri_params_hip<C> params;
+        params.log_domain = log_n + expand;
+        params.step_list.assign(log_n + expand - 4, 1);
+        params.root_of_unity = bls_root;
+        uint64_t seed = 5;
+        auto sm = [&seed]() {
+            uint64_t z = (seed += 0x9E3779B97F4A7C15ull);
+            z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+            z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+            return z ^ (z >> 31);
+        };
+        std::vector<polynomial_dfs<C>> polys(cols);
+        for (auto &p : polys) {
+            p.values.resize(n);
+            for (auto &v : p.values) {
+                uint64_t w[4] = {sm(), sm(), sm(), sm() & 0x0fffffffffffffffull};
+                v = A::scalar_from_limbs(w);
+            }
+        }
+        std::vector<std::reference_wrapper<const polynomial_dfs<C>>> lent(polys.begin(), polys.end());
+        lpc_commitment_scheme_hip<C, counting_transcript, device_merkle_builder<>> scheme(ctx, params, device_merkle_builder<>());
+        for (int rep = 0; rep < steps; ++rep) {
+            auto t0 = std::chrono::steady_clock::now();
+            scheme.append_to_batch(rep, lent);
+            const auto r = scheme.commit(rep);
+            ms[rep] = ms_since(t0);
+            if (root) std::memcpy(root, r.data(), 32);
+        }
+        return 0;
+    } catch (const std::exception &e) {
+        fprintf(stderr, "zkhip_bench_lpc_scheme_device: %s\n", e.what());
         return -1;
     }
 }

@@ -1,12 +1,14 @@
 // TEST SHIM (never loaded by the product path): runs the __host__ __device__ field / curve / recoding
 // code of fp.hpp, fu.hpp, curve.hpp and msm_recode.hpp on the CPU so the no-GPU test-suite can compare the
-// exact device arithmetic against the oracle.  Built with --offload-host-only into libzkhip_hosttest.so.
+// exact device arithmetic against the oracle, and the SHA2-256 core of sha256.hpp (the Merkle kernels' hash) against hashlib.
+// Built with --offload-host-only into libzkhip_hosttest.so.
 #include <cstring>
 #include <vector>
 
 #define ZK_NOINLINE_MUL 1  // keeps this shim's build time short; fu_sqr is reached through op 9
 #include "arith_ops.h"
 #include "msm_recode.hpp"
+#include "sha256.hpp"
 
 using namespace zkhip;
 using namespace zkhip::arith;
@@ -95,6 +97,26 @@ int zkt_recode_folded(int curve, const uint32_t *scalar, int c, int32_t *digits)
     if (flip)
         for (int w = 0; w < W; ++w) digits[w] = -digits[w];
     return W;
+}
+
+// SHA2-256 of n >= 1 field elements (canonical little-endian limbs, hashed as their 32-byte big-endian encodings): merkle.hip's leaf digest
+int zkt_sha256_elements(const uint64_t *elems, size_t n, uint8_t *digest) {
+    if (!elems || !digest || n == 0) return -1;
+    sha256::hash_elements(elems, n, digest);
+    return 0;
+}
+
+// the whole tree over n_leaves x per_leaf elements, as zkhip_merkle_build_dev lays it out: (2 n_leaves - 1) x 32 bytes, leaf digests first, root last
+int zkt_merkle_tree(const uint64_t *leaves, size_t n_leaves, size_t per_leaf, uint8_t *digests) {
+    if (!leaves || !digests || n_leaves == 0 || (n_leaves & (n_leaves - 1)) || per_leaf == 0) return -1;
+    for (size_t x = 0; x < n_leaves; ++x) sha256::hash_elements(leaves + 4 * x * per_leaf, per_leaf, digests + 32 * x);
+    uint8_t *level = digests;
+    for (size_t n = n_leaves / 2; n >= 1; n /= 2) {
+        uint8_t *up = level + 64 * n;
+        for (size_t j = 0; j < n; ++j) sha256::hash_node(level + 64 * j, level + 64 * j + 32, up + 32 * j);
+        level = up;
+    }
+    return 0;
 }
 
 }  // extern "C"

@@ -15,8 +15,12 @@
 //           Q = sum_points (sum_k theta^k (g_k - z_k)) / (X - point)  (lpc.hpp:139-186; one pass over the resident
 //           coefficients + one synthetic division per point), its extension, and the FRI commit phase
 //           (fold_polynomial rounds + per-round leaf layouts, basic_fri.hpp:705-742).
-//   caller  hashing: the TreeBuilder builds the Merkle tree of a precommitment and exposes .root() (containers::merkle_tree +
-//           the scheme's hash, outside this tree's scope: SURVEY 2).  Three shapes, best first (see tree_builder_kind):
+//           hashing, WITH A DEVICE TREE BUILDER (tree_builder_kind::device; hip/merkle.hpp's device_merkle_builder: SHA2-256): the builder is
+//           handed the resident evaluations -- b(ctx, d_evals, batch, log_domain, fri_step) -- and builds the Merkle tree of commit(batch), of
+//           the combined quotient and of every FRI round on the GPU, leaf hashing fused with the leaf gather: no leaf layout is written and
+//           no leaf crosses PCIe; the tree stays resident for the query phase's paths and only its 32-byte root comes back.
+//   caller  hashing, with a host tree builder: the TreeBuilder builds the Merkle tree of a precommitment and exposes .root()
+//           (containers::merkle_tree + the scheme's hash).  Three host shapes, best first (see tree_builder_kind):
 //             streaming  b.begin(total_elements, elements_per_leaf); b.absorb(ptr, first_element, count) ...; b.finish()
 //                        -- the leaves arrive in slices of whole leaves through two page-locked buffers: slice k + 1 crosses
 //                        PCIe while the caller hashes slice k, nothing is materialised;
@@ -32,7 +36,8 @@
 // their own PCIe links, extensions on their own GPUs --, then the path's one exchange: the leaf range of every LEAF OWNER (the first 2^k
 // members) is made of 2^fri_step segments of every polynomial, which the members pack and push to the owners; each owner lays out ITS
 // leaves and sends them to the host over ITS link while the caller hashes.  Same leaves, same order, same roots as on one device; the
-// coefficient forms are gathered on member 0, where proof_eval runs as before.  See commit_group.
+// coefficient forms are gathered on member 0, where proof_eval runs as before.  See commit_group.  A device tree builder over a group is
+// not supported (the leaf owners would each hold a subtree): the group constructor refuses it at compile time.
 //---------------------------------------------------------------------------//
 #ifndef ZKHIP_SHIM_LPC_HPP
 #define ZKHIP_SHIM_LPC_HPP
@@ -77,8 +82,8 @@ struct fri_params_hip {
 };
 
 namespace detail {
-    /// which of the three tree-builder shapes a type offers (see the header comment)
-    enum class tree_builder_kind { streaming, span, vector };
+    /// which of the tree-builder shapes a type offers (see the header comment): three that hash on the host, one that hashes on the device
+    enum class tree_builder_kind { streaming, span, vector, device };
     template <typename B, typename V, typename = void>
     struct is_streaming_builder : std::false_type { };
     template <typename B, typename V>
@@ -90,8 +95,18 @@ namespace detail {
     struct is_span_builder : std::false_type { };
     template <typename B, typename V>
     struct is_span_builder<B, V, std::void_t<decltype(std::declval<B &>()(static_cast<const V *>(nullptr), std::size_t(), std::size_t()))>> : std::true_type { };
+    template <typename B, typename = void>
+    struct is_device_builder : std::false_type { };
+    template <typename B>
+    struct is_device_builder<B, std::void_t<decltype(std::declval<B &>()(std::declval<const context &>(), static_cast<const void *>(nullptr), std::size_t(),
+                                                                         std::size_t(), std::size_t()))>> : std::true_type { };
     template <typename B, typename V, tree_builder_kind K>
     struct tree_builder_result;
+    template <typename B, typename V>
+    struct tree_builder_result<B, V, tree_builder_kind::device> {
+        typedef typename std::decay<decltype(std::declval<B &>()(std::declval<const context &>(), static_cast<const void *>(nullptr), std::size_t(), std::size_t(),
+                                                                  std::size_t()))>::type type;
+    };
     template <typename B, typename V>
     struct tree_builder_result<B, V, tree_builder_kind::streaming> {
         typedef typename std::decay<decltype(std::declval<B &>().finish())>::type type;
@@ -120,9 +135,11 @@ public:
     typedef PolynomialType poly_type;
     typedef eval_storage_hip<CurveType> eval_storage_type;
     static constexpr detail::tree_builder_kind builder_kind =
-        detail::is_streaming_builder<TreeBuilder, value_type>::value
-            ? detail::tree_builder_kind::streaming
-            : (detail::is_span_builder<TreeBuilder, value_type>::value ? detail::tree_builder_kind::span : detail::tree_builder_kind::vector);
+        detail::is_device_builder<TreeBuilder>::value
+            ? detail::tree_builder_kind::device
+            : detail::is_streaming_builder<TreeBuilder, value_type>::value
+                  ? detail::tree_builder_kind::streaming
+                  : (detail::is_span_builder<TreeBuilder, value_type>::value ? detail::tree_builder_kind::span : detail::tree_builder_kind::vector);
     typedef typename detail::tree_builder_result<TreeBuilder, value_type, builder_kind>::type precommitment_type;
     typedef typename std::decay<decltype(std::declval<const precommitment_type &>().root())>::type commitment_type;
     typedef std::map<std::size_t, std::vector<value_type>> preprocessed_data_type;
@@ -148,6 +165,8 @@ public:
     /// the scheme over a device group: commit(batch) spreads over the members (commit_group), everything else runs on member 0
     lpc_commitment_scheme_hip(const device_group &group, const params_type &fri_params, TreeBuilder builder) :
         lpc_commitment_scheme_hip(group.root(), fri_params, std::move(builder)) {
+        static_assert(builder_kind != detail::tree_builder_kind::device,
+                      "lpc over a device group takes a host tree builder: a device tree builder (hip/merkle.hpp) works on one context only");
         _group = &group;
         _gs.reset(new group_scratch[group.size()]);
     }
@@ -520,8 +539,13 @@ public:
 
 protected:
     std::size_t domain_size(std::size_t t) const { return (std::size_t)1 << (_fri_params.log_domain - t); }
-    /// the leaf layout of `batch` polynomials resident as evaluations over the 2^log_domain-point domain -> the caller's tree
+    /// the leaf layout of `batch` polynomials resident as evaluations over the 2^log_domain-point domain -> the caller's tree; a device
+    /// builder takes the evaluations as they lie: no leaf layout, no copy to the host
     precommitment_type build_tree(const void *d_evals, std::size_t batch, std::size_t log_domain, std::size_t fri_step) const {
+        if constexpr (builder_kind == detail::tree_builder_kind::device) return _builder(_ctx, d_evals, batch, log_domain, fri_step);
+        else return build_tree_host(d_evals, batch, log_domain, fri_step);
+    }
+    precommitment_type build_tree_host(const void *d_evals, std::size_t batch, std::size_t log_domain, std::size_t fri_step) const {
         const std::size_t D = (std::size_t)1 << log_domain, total = batch * D, per_leaf = batch * ((std::size_t)1 << fri_step);
         void *d_leaves = _scratch_leaves.reserve(_ctx, std::max<std::size_t>(1, total) * 32);
         check(zkhip_fri_leaves_dev(_ctx.get(), d_evals, log_domain, batch, fri_step, d_leaves), "zkhip_fri_leaves_dev", _ctx.get());
@@ -560,7 +584,9 @@ protected:
     precommitment_type build_tree_group(const std::vector<const void *> &d_leaves, std::size_t block, std::size_t per_leaf) const {
         const device_group &group = *_group;
         const std::size_t owners = d_leaves.size(), total = owners * block;
-        if constexpr (builder_kind == detail::tree_builder_kind::streaming) {
+        if constexpr (builder_kind == detail::tree_builder_kind::device) {
+            throw std::logic_error("lpc: a device tree builder over a device group is not supported");    // unreachable: the group constructor does not compile
+        } else if constexpr (builder_kind == detail::tree_builder_kind::streaming) {
             const std::size_t slice = std::max<std::size_t>(1, (leaf_slice_elements + per_leaf - 1) / std::max<std::size_t>(1, per_leaf)) * std::max<std::size_t>(1, per_leaf);
             const std::size_t first = std::min(slice, block);
             _builder.begin(total, per_leaf);

@@ -1,0 +1,102 @@
+//---------------------------------------------------------------------------//
+// zkhip shim: the Merkle trees of the LPC / FRI commitments, built and kept on the MI355X.
+//
+// Stands where containers::merkle_tree<hashes::sha2<256>, 2> stands in precommit<FRI> (zk/commitments/detail/polynomial/basic_fri.hpp:375-409,
+// 461-496): `device_merkle_tree` is the tree -- root(), the authentication paths the query phase reads --, `device_merkle_builder` the tree
+// builder lpc_commitment_scheme_hip takes (hip/lpc.hpp, tree_builder_kind::device): it is handed the evaluations where they lie on the device
+// and hashes the coset-ordered leaves straight out of them.
+//
+// Conventions (include/zkhip.h, "Merkle trees"): an element is the 32-byte big-endian encoding of its canonical integer, a leaf digest the
+// SHA2-256 of the leaf's elements in leaf order, an inner node SHA2-256(left || right), arity 2, a power-of-two leaf count.
+//
+// This header is the only one of the shim that refers to the zkhip_merkle_* entry points: code that never names a device tree builder does
+// not need them at link time.
+//---------------------------------------------------------------------------//
+#ifndef ZKHIP_SHIM_MERKLE_HPP
+#define ZKHIP_SHIM_MERKLE_HPP
+
+#include <array>
+#include <cstdint>
+#include <memory>
+#include <vector>
+
+#include "backend.hpp"
+
+namespace nil {
+namespace crypto3 {
+namespace zk {
+namespace hip {
+
+/// A Merkle tree resident on the device (RAII over zkhip_merkle; copies share the tree).  The context must outlive it.
+class device_merkle_tree {
+public:
+    typedef std::array<std::uint8_t, 32> digest_type;
+    typedef std::vector<digest_type> proof_type;    // the sibling digests of a leaf's ancestors, leaf level first
+
+    device_merkle_tree() = default;
+    /// takes the handle over; the root is fetched here, once
+    device_merkle_tree(const context &ctx, zkhip_merkle *tree) : ctx_(&ctx) {
+        zkhip_ctx *c = ctx.get();
+        tree_ = std::shared_ptr<zkhip_merkle>(tree, [c](zkhip_merkle *t) { zkhip_merkle_free(c, t); });
+        check(zkhip_merkle_root(c, tree, root_.data()), "zkhip_merkle_root", c);
+    }
+    /// the tree over `batch` polynomials resident as evaluations over the 2^log_domain-point domain, leaves as precommit<FRI> lays them out
+    static device_merkle_tree from_evaluations(const context &ctx, int hash, const void *d_evals, std::size_t batch, std::size_t log_domain,
+                                               std::size_t fri_step) {
+        zkhip_merkle *t = nullptr;
+        check(zkhip_merkle_build_fri_dev(ctx.get(), hash, d_evals, log_domain, batch, fri_step, &t), "zkhip_merkle_build_fri_dev", ctx.get());
+        return device_merkle_tree(ctx, t);
+    }
+    /// the tree over a leaf layout on the device: n_leaves leaves of elements_per_leaf elements
+    static device_merkle_tree from_leaves(const context &ctx, int hash, const void *d_leaves, std::size_t n_leaves, std::size_t elements_per_leaf) {
+        zkhip_merkle *t = nullptr;
+        check(zkhip_merkle_build_dev(ctx.get(), hash, d_leaves, n_leaves, elements_per_leaf, &t), "zkhip_merkle_build_dev", ctx.get());
+        return device_merkle_tree(ctx, t);
+    }
+
+    const digest_type &root() const { return root_; }
+    std::size_t leaves() const { return zkhip_merkle_leaves(tree_.get()); }
+    std::size_t depth() const { return zkhip_merkle_depth(tree_.get()); }
+    const zkhip_merkle *get() const { return tree_.get(); }
+
+    /// the authentication path of one leaf: depth() sibling digests
+    proof_type proof(std::size_t leaf_index) const { return proofs(std::vector<std::size_t> {leaf_index}).front(); }
+    /// the paths of many leaves in one device pass and one copy (the query phase's lambda openings of a round)
+    std::vector<proof_type> proofs(const std::vector<std::size_t> &leaf_indices) const {
+        const std::size_t d = depth();
+        std::vector<std::uint64_t> idx(leaf_indices.begin(), leaf_indices.end());
+        std::vector<std::uint8_t> flat(idx.size() * d * 32);
+        check(zkhip_merkle_paths(ctx_->get(), tree_.get(), idx.data(), idx.size(), flat.data()), "zkhip_merkle_paths", ctx_->get());
+        std::vector<proof_type> out(idx.size(), proof_type(d));
+        for (std::size_t k = 0; k < idx.size(); ++k)
+            for (std::size_t l = 0; l < d; ++l) std::copy_n(flat.data() + (k * d + l) * 32, 32, out[k][l].begin());
+        return out;
+    }
+    /// every digest: the leaves() leaf digests, then each level above, the root last
+    std::vector<digest_type> digests() const {
+        std::vector<digest_type> out(2 * leaves() - 1);
+        check(zkhip_merkle_digests(ctx_->get(), tree_.get(), out.front().data()), "zkhip_merkle_digests", ctx_->get());
+        return out;
+    }
+
+private:
+    const context *ctx_ = nullptr;
+    std::shared_ptr<zkhip_merkle> tree_;
+    digest_type root_ {};
+};
+
+/// The tree builder that keeps lpc_commitment_scheme_hip's hashing on the device.  `Hash`: a ZKHIP_HASH_* id.
+template <int Hash = ZKHIP_HASH_SHA2_256>
+struct device_merkle_builder {
+    static_assert(Hash == ZKHIP_HASH_SHA2_256, "device_merkle_builder: SHA2-256 is the only hash built for the device");
+    device_merkle_tree operator()(const context &ctx, const void *d_evals, std::size_t batch, std::size_t log_domain, std::size_t fri_step) const {
+        return device_merkle_tree::from_evaluations(ctx, Hash, d_evals, batch, log_domain, fri_step);
+    }
+};
+
+}    // namespace hip
+}    // namespace zk
+}    // namespace crypto3
+}    // namespace nil
+
+#endif    // ZKHIP_SHIM_MERKLE_HPP

@@ -10,6 +10,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 BLS12_381, BN254 = 0, 1
 G1, G2 = 1, 2
+HASH_SHA2_256 = 0
 _FQ = {BLS12_381: 6, BN254: 4}
 
 EXPORTS = [
@@ -20,6 +21,8 @@ EXPORTS = [
     "zkhip_domain_choice", "zkhip_domain_fft_dev", "zkhip_domain_lagrange_dev",
     "zkhip_r1cs_upload", "zkhip_r1cs_free", "zkhip_r1cs_set_domain", "zkhip_r1cs_domain_size", "zkhip_r1cs_domain_kind", "zkhip_groth16_scratch_bytes", "zkhip_groth16_witness_h_dev", "zkhip_groth16_witness_h_domain_dev", "zkhip_fr_gather_dev", "zkhip_poly_resize_dev", "zkhip_fri_fold_dev", "zkhip_fri_leaves_dev", "zkhip_ec_ntt_dev",
     "zkhip_fr_vec_op_dev", "zkhip_fr_vec_affine_dev", "zkhip_fr_vec_mul_div_dev", "zkhip_fr_vec_prod_dev", "zkhip_poly_shift_dev", "zkhip_poly_eval_dev", "zkhip_poly_div_linear_dev", "zkhip_poly_div_vanishing_dev", "zkhip_poly_lincomb_dev", "zkhip_perm_grand_product_dev", "zkhip_lookup_grand_product_dev", "zkhip_lookup_sort_dev", "zkhip_perm_factor_products_dev", "zkhip_gate_eval_dev",
+    "zkhip_merkle_build_dev", "zkhip_merkle_build_fri_dev", "zkhip_merkle_leaves", "zkhip_merkle_depth", "zkhip_merkle_root", "zkhip_merkle_digests", "zkhip_merkle_paths",
+    "zkhip_merkle_free",
     "zkhip_group_init", "zkhip_group_destroy", "zkhip_group_size", "zkhip_group_ctx", "zkhip_group_last_error", "zkhip_group_set_transport", "zkhip_group_transport",
     "zkhip_group_all_gather", "zkhip_group_copy", "zkhip_group_sync", "zkhip_group_bases_upload", "zkhip_group_bases_from_scalars", "zkhip_group_bases_free",
     "zkhip_group_bases_size", "zkhip_group_bases_member", "zkhip_group_msm", "zkhip_group_ntt",
@@ -125,6 +128,12 @@ def load_library() -> ctypes.CDLL:
     lib.zkhip_group_bases_size.argtypes = [ctypes.c_void_p]
     lib.zkhip_group_bases_member.restype = ctypes.c_void_p
     lib.zkhip_group_bases_member.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+    lib.zkhip_merkle_leaves.restype = ctypes.c_size_t
+    lib.zkhip_merkle_leaves.argtypes = [ctypes.c_void_p]
+    lib.zkhip_merkle_depth.restype = ctypes.c_size_t
+    lib.zkhip_merkle_depth.argtypes = [ctypes.c_void_p]
+    lib.zkhip_merkle_free.restype = None
+    lib.zkhip_merkle_free.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     _LIB = lib
     return lib
 
@@ -498,6 +507,25 @@ class Context:
         self._check(self.lib.zkhip_poly_lincomb_dev(self.h, curve, ctypes.c_size_t(count), ptrs, ls, _p(cf), ctypes.c_size_t(taps), ctypes.c_void_p(d_acc),
                                                     ctypes.c_size_t(acc_len), 1 if accumulate else 0), "poly_lincomb_dev")
 
+    # ---- Merkle trees of the LPC / FRI commitments (zkhip_merkle_*)
+    def fri_leaves_dev(self, d_polys: int, log_domain: int, batch: int, fri_step: int, d_out: int):
+        self._check(self.lib.zkhip_fri_leaves_dev(self.h, ctypes.c_void_p(d_polys), ctypes.c_size_t(log_domain), ctypes.c_size_t(batch), ctypes.c_size_t(fri_step),
+                                                  ctypes.c_void_p(d_out)), "zkhip_fri_leaves_dev")
+
+    def merkle_build(self, d_leaves: int, n_leaves: int, elements_per_leaf: int, hash_id: int = HASH_SHA2_256) -> "MerkleTree":
+        """the tree over a leaf layout on the device: n_leaves leaves of elements_per_leaf 32-byte elements"""
+        h = ctypes.c_void_p()
+        self._check(self.lib.zkhip_merkle_build_dev(self.h, int(hash_id), ctypes.c_void_p(d_leaves), ctypes.c_size_t(n_leaves), ctypes.c_size_t(elements_per_leaf),
+                                                    ctypes.byref(h)), "zkhip_merkle_build_dev")
+        return MerkleTree(self, h)
+
+    def merkle_build_fri(self, d_polys: int, log_domain: int, batch: int, fri_step: int, hash_id: int = HASH_SHA2_256) -> "MerkleTree":
+        """the tree over the leaves precommit<FRI> lays out for `batch` vectors of 2^log_domain evaluations at d_polys, hashed straight from them"""
+        h = ctypes.c_void_p()
+        self._check(self.lib.zkhip_merkle_build_fri_dev(self.h, int(hash_id), ctypes.c_void_p(d_polys), ctypes.c_size_t(log_domain), ctypes.c_size_t(batch),
+                                                        ctypes.c_size_t(fri_step), ctypes.byref(h)), "zkhip_merkle_build_fri_dev")
+        return MerkleTree(self, h)
+
     def profile(self, on: bool):
         self._check(self.lib.zkhip_profile_enable(self.h, 1 if on else 0), "zkhip_profile_enable")
 
@@ -522,6 +550,44 @@ class Context:
             name, ms, cnt = line.rsplit(" ", 2)
             out[name] = (float(ms), int(cnt))
         return out
+
+
+class MerkleTree:
+    """Resident Merkle tree (zkhip_merkle): digests of 32 bytes, the leaves' first, the root last."""
+
+    def __init__(self, ctx: "Context", h):
+        self.ctx, self.h = ctx, h
+        self.leaves = ctx.lib.zkhip_merkle_leaves(h)
+        self.depth = ctx.lib.zkhip_merkle_depth(h)
+
+    def root(self) -> bytes:
+        out = np.zeros(32, dtype=np.uint8)
+        self.ctx._check(self.ctx.lib.zkhip_merkle_root(self.ctx.h, self.h, _p(out)), "zkhip_merkle_root")
+        return out.tobytes()
+
+    def digests(self) -> np.ndarray:
+        """(2 leaves - 1, 32) u8"""
+        out = np.zeros((2 * self.leaves - 1, 32), dtype=np.uint8)
+        self.ctx._check(self.ctx.lib.zkhip_merkle_digests(self.ctx.h, self.h, _p(out)), "zkhip_merkle_digests")
+        return out
+
+    def paths(self, leaf_indices) -> np.ndarray:
+        """(count, depth, 32) u8: per leaf index the sibling digests from the leaf level up"""
+        idx = np.ascontiguousarray(leaf_indices, dtype=np.uint64).reshape(-1)
+        out = np.zeros((len(idx), self.depth, 32), dtype=np.uint8)
+        self.ctx._check(self.ctx.lib.zkhip_merkle_paths(self.ctx.h, self.h, _p(idx), ctypes.c_size_t(len(idx)), _p(out)), "zkhip_merkle_paths")
+        return out
+
+    def free(self):
+        if self.h is not None and self.ctx.h:
+            self.ctx.lib.zkhip_merkle_free(self.ctx.h, self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class R1CS:

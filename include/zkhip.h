@@ -272,8 +272,39 @@ int zkhip_fri_fold_dev(zkhip_ctx *ctx, int curve, const void *d_f, size_t log_si
 /* The leaf layout precommit<FRI> feeds to the Merkle tree (basic_fri.hpp:456-492, FRI::m = 2): `batch` vectors of
  * 2^log_domain evaluations at d_polys -> d_out, 2^log_domain / 2^fri_step leaves of batch * 2^fri_step elements each:
  * leaf x = for every polynomial, the pairs (f[s_i], f[s_i + D/2]) in the reference's coset order.  Hashing is
- * the caller's. */
+ * the caller's, or zkhip_merkle_build_fri_dev's below. */
 int zkhip_fri_leaves_dev(zkhip_ctx *ctx, const void *d_polys, size_t log_domain, size_t batch, size_t fri_step, void *d_out);
+
+/* ---- Merkle trees (SHA2-256) of the LPC / FRI commitments, built and kept on the device ----------------------------
+ * The tree precommit<FRI> builds with make_merkle_tree<Hash, 2> over the leaves above (basic_fri.hpp:375-409, 461-496), for
+ * Hash = hashes::sha2<256>.  THE CONTRACT (crypto3's containers::merkle_tree was not at hand when this was written, so the
+ * layout below is stated here and checked against an independent SHA2-256, not pinned to a reference vector):
+ *   element bytes   a field element is 32 bytes: the BIG-ENDIAN encoding of its canonical integer (marshalling's
+ *                   field_element with option::big_endian, basic_fri.hpp:96-97), for both curves' Fr;
+ *   leaf digest     SHA2-256 of the leaf's elements concatenated in leaf order (the order zkhip_fri_leaves_dev writes);
+ *   inner node      SHA2-256(left digest || right digest), 64 bytes;
+ *   shape           arity 2, L leaves, L a power of two >= 1; with one leaf the root is that leaf's digest;
+ *   digest array    (2L - 1) x 32 bytes: the leaf digests at [0, L), the next level at [L, L + L/2), ..., the root last.
+ * A tree stays resident (64 MB at 2^20 leaves) until zkhip_merkle_free.  `hash` selects the hash function: only
+ * ZKHIP_HASH_SHA2_256 exists.
+ * Errors: unknown hash, null pointers, a leaf count that is not a power of two, no elements per leaf -> ZKHIP_ERR_INVALID;
+ * a leaf index >= L, fri_step outside zkhip_fri_leaves_dev's range -> ZKHIP_ERR_RANGE; allocation failure -> ZKHIP_ERR_OOM. */
+#define ZKHIP_HASH_SHA2_256 0
+typedef struct zkhip_merkle zkhip_merkle;
+/* over a leaf layout on the device: n_leaves leaves of elements_per_leaf elements each */
+int zkhip_merkle_build_dev(zkhip_ctx *ctx, int hash, const void *d_leaves, size_t n_leaves, size_t elements_per_leaf, zkhip_merkle **out);
+/* over the leaves zkhip_fri_leaves_dev would write for the same arguments, hashed straight from the evaluations at d_polys
+ * (the leaf layout is never materialised); byte for byte the tree of zkhip_fri_leaves_dev + zkhip_merkle_build_dev */
+int zkhip_merkle_build_fri_dev(zkhip_ctx *ctx, int hash, const void *d_polys, size_t log_domain, size_t batch, size_t fri_step, zkhip_merkle **out);
+size_t zkhip_merkle_leaves(const zkhip_merkle *t);
+size_t zkhip_merkle_depth(const zkhip_merkle *t); /* log2(L): the length of a path */
+int zkhip_merkle_root(zkhip_ctx *ctx, const zkhip_merkle *t, uint8_t out[32]);
+int zkhip_merkle_digests(zkhip_ctx *ctx, const zkhip_merkle *t, uint8_t *out /* host, (2L - 1) x 32 */);
+/* the authentication paths of `count` leaves: per index the `depth` sibling digests from the leaf level up, gathered on the
+ * device and fetched in one copy */
+int zkhip_merkle_paths(zkhip_ctx *ctx, const zkhip_merkle *t, const uint64_t *leaf_indices /* host */, size_t count,
+                       uint8_t *out /* host, count x depth x 32 */);
+void zkhip_merkle_free(zkhip_ctx *ctx, zkhip_merkle *t);
 
 /* ---- DFT over group elements -------------------------------------------------------------------------------
  * evaluation_domain<Fr, G>::evaluate_all_lagrange_polynomials(powers_begin, powers_end) as the powers-of-tau result uses
