@@ -206,6 +206,41 @@ struct zkhip_ctx {
     }
 };
 
+// Workspace layouts.  A call declares its buffers ONCE, as an object with a member
+//     template <class Arena> void layout(Arena &a) { a.take(first, count); a.take(second, count); ... }
+// which is walked twice: by WsCount to size the reservation, and by WsBump to hand the pointers out in the same order.
+struct WsCount {
+    size_t bytes = 0;
+    template <class T>
+    void take(T *&, size_t count) { bytes += zkhip_ctx::ws_round(count * sizeof(T)); }
+};
+struct WsBump {
+    zkhip_ctx *ctx;
+    template <class T>
+    void take(T *&p, size_t count) { p = ctx->ws_take<T>(count); }
+};
+template <class Layout>
+size_t ws_bytes(Layout &l) {
+    WsCount a;
+    l.layout(a);
+    return a.bytes;
+}
+// reserve the layout's bytes (+ `above`: room the caller hands out later) over ws_floor, place the buffers there and check that the
+// walk stayed inside what was reserved
+template <class Layout>
+int ws_place(zkhip_ctx *ctx, Layout &l, size_t above = 0) {
+    const size_t end = ctx->ws_floor + ws_bytes(l);
+    ZK_TRY(ctx->ws_reserve(end + above));
+    ctx->ws_reset();
+    WsBump a{ctx};
+    l.layout(a);
+    if (ctx->ws_off > end || end + above > ctx->ws_cap) {
+        ctx->last_error = "workspace layout took " + std::to_string(ctx->ws_off - ctx->ws_floor) + " bytes of " + std::to_string(end - ctx->ws_floor) + " reserved";
+        return ZKHIP_ERR_RANGE;
+    }
+    return 0;
+}
+
 // raise a kernel's dynamic-LDS limit once per context (the attribute is per device: a process may hold contexts on
 // several GPUs, so a process-wide flag would skip it on the second device)
 #define ZK_MAX_LDS(ctx, kernel, bytes)                                                                                              \

@@ -30,7 +30,7 @@
 // Kernels (all integer VALU; no MFMA -- this is modular arithmetic, not a dense contraction):
 //   msm_digits_only   scalar -> signed digits                           (streams 32 B/scalar, coalesced)
 //   msm_sort_*        two-level counting sort of the entries by (set, bucket), counters in LDS only, tiles staged in LDS
-//   msm_scan_*        exclusive prefix (local scan, top scan, add-back), shared by both sorts
+//   msm_scan_*        exclusive prefix (local scan, top scan, add-back), shared by both sorts; every LDS scan is block_inclusive_scan
 //   msm_size_*        order of the buckets by descending size
 //   msm_bucket_acc_lds  one lane per bucket (G1) or one even / odd lane pair per bucket (G2, fu2_pair.hpp): gather affine
 //                     points, XYZZ mixed additions, accumulator coordinates in LDS                          <- dominant
@@ -43,6 +43,10 @@
 //   msm_window_sum    LDS tree over the per-workgroup partials of a set
 //   msm_final         (Horner over the windows when there are no tables,) XYZZ -> Jacobian, Montgomery -> canonical
 //   msm_final_fold    the same after msm_fold: COL sum + 2^log2(C) ROW sum
+//   msm_final_batch   the same for every member of a batch
+// (msm_final, msm_final_fold and msm_write_infinity store through xyzz_store_canonical_jacobian.  msm_final_batch and jac_sum_k keep the three
+// stores spelled out, msm_bucket_large its own copy of block_tree_sum's loop, and the three batch inversions their back-substitution step: with
+// the shared helper those kernels compiled to other register / scratch counts.)
 // Point order inside a bucket depends on LDS-atomic arrival order; the group law is exact, so the sum
 // (compared in affine) does not.
 #pragma once
@@ -78,6 +82,19 @@ constexpr uint32_t MSM_LARGE_CHUNK = 4096;  // entries per task of a split bucke
 #define MSM_G2_WAVES 2
 #endif
 
+// Hillis-Steele inclusive scan over one LDS word per lane, in place; every lane has written its own word
+template <uint32_t THREADS>
+ZK_D void block_inclusive_scan(uint32_t *scratch) {
+    const uint32_t t = threadIdx.x;
+    __syncthreads();
+    for (uint32_t d = 1; d < THREADS; d <<= 1) {
+        uint32_t x = t >= d ? scratch[t - d] : 0;
+        __syncthreads();
+        scratch[t] += x;
+        __syncthreads();
+    }
+}
+
 // exclusive scan of `count` u32 counters in three launches: per-block (1024 counters) local scan + block
 // totals, scan of the totals by one workgroup, add-back.  offs[count] = total; cursor = copy of offs.
 __global__ __launch_bounds__(256) void msm_scan_local(const uint32_t *__restrict__ hist, uint32_t count, uint32_t *__restrict__ offs,
@@ -91,13 +108,7 @@ __global__ __launch_bounds__(256) void msm_scan_local(const uint32_t *__restrict
         s += v[k];
     }
     part[t] = s;
-    __syncthreads();
-    for (uint32_t d = 1; d < 256; d <<= 1) {
-        uint32_t x = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += x;
-        __syncthreads();
-    }
+    block_inclusive_scan<256>(part);
     uint32_t run = part[t] - s;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -115,13 +126,7 @@ __global__ __launch_bounds__(1024) void msm_scan_top(uint32_t *__restrict__ bloc
     uint32_t s = 0;
     for (uint32_t i = lo; i < hi; ++i) s += block_sums[i];
     part[t] = s;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
-        uint32_t x = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += x;
-        __syncthreads();
-    }
+    block_inclusive_scan<1024>(part);
     uint32_t run = part[t] - s;
     for (uint32_t i = lo; i < hi; ++i) {
         uint32_t x = block_sums[i];
@@ -157,13 +162,7 @@ __global__ __launch_bounds__(1024) void msm_scan_single(const uint32_t *__restri
     for (uint32_t base = 0; base < count; base += 1024) {
         const uint32_t v = base + t < count ? hist[base + t] : 0;
         part[t] = v;
-        __syncthreads();
-        for (uint32_t d = 1; d < 1024; d <<= 1) {
-            uint32_t x = t >= d ? part[t - d] : 0;
-            __syncthreads();
-            part[t] += x;
-            __syncthreads();
-        }
+        block_inclusive_scan<1024>(part);
         const uint32_t excl = carry + part[t] - v;
         if (base + t < count) {
             offs[base + t] = excl;
@@ -279,13 +278,7 @@ ZK_D uint32_t block_excl_scan(uint32_t *v, uint32_t count, uint32_t *scratch /* 
     uint32_t s = 0;
     for (uint32_t k = lo; k < hi; ++k) s += v[k];
     scratch[t] = s;
-    __syncthreads();
-    for (uint32_t d = 1; d < SORT_THREADS; d <<= 1) {
-        uint32_t x = t >= d ? scratch[t - d] : 0;
-        __syncthreads();
-        scratch[t] += x;
-        __syncthreads();
-    }
+    block_inclusive_scan<SORT_THREADS>(scratch);
     const uint32_t total = scratch[SORT_THREADS - 1];
     uint32_t run = scratch[t] - s;
     for (uint32_t k = lo; k < hi; ++k) {
@@ -356,13 +349,7 @@ ZK_D void block_scan_counts(const uint32_t *cnt, uint32_t *excl, uint32_t *scrat
 #pragma unroll
     for (uint32_t k = 0; k < CPT; ++k) s += cnt[t * CPT + k];
     scratch[t] = s;
-    __syncthreads();
-    for (uint32_t d = 1; d < THREADS; d <<= 1) {
-        uint32_t x = t >= d ? scratch[t - d] : 0;
-        __syncthreads();
-        scratch[t] += x;
-        __syncthreads();
-    }
+    block_inclusive_scan<THREADS>(scratch);
     uint32_t run = scratch[t] - s;
 #pragma unroll
     for (uint32_t k = 0; k < CPT; ++k) {
@@ -715,6 +702,16 @@ __global__ __launch_bounds__(MSM_TAIL_THREADS, ZK_TAIL_WAVES) void msm_fold(cons
     }
 }
 
+// what every MSM result leaves the device as: XYZZ -> Jacobian, Montgomery -> canonical (X | Y | Z, CANON_WORDS each)
+template <class F>
+ZK_D void xyzz_store_canonical_jacobian(uint32_t *dst, const XYZZ<F> &p) {
+    constexpr int CW = FieldOps<F>::CANON_WORDS;
+    Jacobian<F> j = xyzz_to_jacobian(p);
+    FieldOps<F>::to_canonical(dst, j.X);
+    FieldOps<F>::to_canonical(dst + CW, j.Y);
+    FieldOps<F>::to_canonical(dst + 2 * CW, j.Z);
+}
+
 // out[i] = winsum[2 i] + 2^shift winsum[2 i + 1] as canonical Jacobian; outs == nullptr: the single output `out`
 template <class F, int LPB>
 __global__ __launch_bounds__(64) void msm_final_fold(const uint32_t *__restrict__ winsum, uint32_t count, uint32_t shift, uint32_t *const *__restrict__ outs,
@@ -725,12 +722,7 @@ __global__ __launch_bounds__(64) void msm_final_fold(const uint32_t *__restrict_
     if (!acc.is_inf())
         for (uint32_t i = 0; i < shift; ++i) acc = xyzz_dbl(acc);
     acc = xyzz_add(acc, xyzz_load<F>(winsum + (size_t)2 * blockIdx.x * (4 * NL)));
-    Jacobian<F> j = xyzz_to_jacobian(acc);
-    constexpr int CW = FieldOps<F>::CANON_WORDS;
-    uint32_t *dst = outs ? outs[blockIdx.x] : out;
-    FieldOps<F>::to_canonical(dst, j.X);
-    FieldOps<F>::to_canonical(dst + CW, j.Y);
-    FieldOps<F>::to_canonical(dst + 2 * CW, j.Z);
+    xyzz_store_canonical_jacobian<F>(outs ? outs[blockIdx.x] : out, acc);
 }
 
 // result = sum_w 2^off(w) winsum[w]  (Horner from the top window; a single set with tables), emitted as canonical Jacobian
@@ -744,11 +736,7 @@ __global__ __launch_bounds__(64) void msm_final(const uint32_t *__restrict__ win
             for (int i = 0; i < win.width(w); ++i) acc = xyzz_dbl(acc);
         acc = xyzz_add(acc, xyzz_load<F>(winsum + (size_t)w * (4 * NL)));
     }
-    Jacobian<F> j = xyzz_to_jacobian(acc);
-    constexpr int CW = FieldOps<F>::CANON_WORDS;
-    FieldOps<F>::to_canonical(out_jac, j.X);
-    FieldOps<F>::to_canonical(out_jac + CW, j.Y);
-    FieldOps<F>::to_canonical(out_jac + 2 * CW, j.Z);
+    xyzz_store_canonical_jacobian<F>(out_jac, acc);
 }
 
 // ---- bases maintenance ----------------------------------------------------------------------------
@@ -951,10 +939,7 @@ __global__ void jac_sum_k(const uint32_t *__restrict__ jac, uint32_t count, uint
 template <class F>
 __global__ void msm_write_infinity(uint32_t *out_jac) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    constexpr int CW = FieldOps<F>::CANON_WORDS;
-    FieldOps<F>::to_canonical(out_jac, F::one());
-    FieldOps<F>::to_canonical(out_jac + CW, F::one());
-    FieldOps<F>::to_canonical(out_jac + 2 * CW, F::zero());
+    xyzz_store_canonical_jacobian<F>(out_jac, XYZZ<F>::infinity());
 }
 
 // one workgroup per MSM of a batch: set sum -> canonical Jacobian at that MSM's output pointer
@@ -971,13 +956,18 @@ __global__ __launch_bounds__(64) void msm_final_batch(const uint32_t *__restrict
 }
 
 // ---- host side ------------------------------------------------------------------------------------
+// Each fact has one home.  msm_call_plan settles a call before its first launch (MsmCall) and touches nothing; MsmBuffers, MsmFoldBuffers,
+// MsmBatchArea, FixedMulBuffers and BasesTmp each declare a workspace ONCE as layout(arena), walked by ws_bytes to size it and by ws_place
+// (ctx.hpp) to hand it out and check the walk against the reservation; msm_stages enqueues an MSM up to its merged buckets for both entries
+// (msm_run_t, msm_batch_member); msm_tail is the only place that launches msm_bucket_red and msm_window_sum, with the shape msm_tail_geom gives
+// and the final kernel of its caller.
 
 // Buckets per tail lane (segment length L).  Every operation of the tail is a full addition or doubling on a chain: a
 // segment costs 2 L (running sums) + ~38 (the multiple seg L, a 20-bit double-and-add whose additions run on every step of
 // a diverged wave) + 8 (LDS tree) dependent operations, each ~13.6 us on one lane, 9.2 us on a lane pair (fu_pair.hpp).
 // Measured (tools/msm_profile.py, 2^19 buckets, G1): one lane per bucket L = 8: 0.84 ms, 16: 1.06, 4: 1.38; lane pairs
 // L = 16: 0.72, 8: 0.92 (two waves per SIMD: the operations slow down more than the chain shortens).
-inline uint32_t msm_tail_segment(const zkhip_ctx *ctx, uint32_t B, size_t sets, int lanes_per_point, bool g2) {
+inline uint32_t msm_tail_segment(const zkhip_ctx *ctx, uint32_t B, size_t sets, int lanes_per_point) {
     uint32_t L = 1;
     if (ctx->opt_msm_segment_log >= 0) L = 1u << std::min(ctx->opt_msm_segment_log, 8);
     else {
@@ -985,11 +975,52 @@ inline uint32_t msm_tail_segment(const zkhip_ctx *ctx, uint32_t B, size_t sets, 
         // one wave per SIMD (2^16 lanes) is where an operation is fastest -- the lane-pair group law (fu_pair.hpp: 9.2 us per
         // operation alone on a SIMD, 14.8 us when two waves share it), G2's pair-split Fq2 likewise: L doubles up to 16 to get
         // there, and beyond only when the lanes would otherwise exceed ~4 waves per SIMD (batches of many MSMs)
-        (void)g2;
         while (L < 16 && lanes / L > 65536) L <<= 1;
         while (L < 64 && lanes / L > 262144) L <<= 1;
     }
     return std::min(B, L);
+}
+
+// The launch shape of the tail over `sets` sets of B buckets.  Lane (TailLane<F>, QuadLane<F> or BucketLane<F>): what a lane holds and how
+// many lanes share a point.
+struct MsmTailGeom {
+    uint32_t L, nseg;       // buckets per segment (= per point slot), segments per set
+    uint32_t slots, nblk;   // point slots per msm_bucket_red workgroup, workgroups per set
+    uint32_t wthreads;      // lanes of a msm_window_sum workgroup
+    size_t lds_red, lds_win;  // dynamic LDS of the two kernels: one XYZZ point per slot
+};
+template <class Lane>
+MsmTailGeom msm_tail_geom(const zkhip_ctx *ctx, uint32_t B, size_t sets) {
+    constexpr size_t point_bytes = (size_t)4 * FieldOps<typename Lane::type>::WORDS * 4;
+    constexpr int XL = Lane::LANES;
+    MsmTailGeom t;
+    t.L = msm_tail_segment(ctx, B, sets, XL);
+    t.nseg = B / t.L;
+    t.slots = MSM_TAIL_THREADS / XL;
+    t.nblk = (t.nseg + t.slots - 1) / t.slots;
+    t.wthreads = msm_window_threads(t.nblk, XL);
+    t.lds_red = t.slots * point_bytes;  // 256 XYZZ points with one lane each: 56 KiB for G1, 128 KiB for BLS12-381 G2
+    t.lds_win = t.wthreads / XL * point_bytes;
+    return t;
+}
+
+// The tail, for every caller: sets[nsets][B] buckets -> segsum (room for segsum_blocks workgroup partials) -> winsum[nsets], then `final`,
+// which launches the kernel that turns the set sums into results.
+// (a variant of msm_bucket_red compiled for one-bucket segments only spills 37 instead of 173 registers and measures the same: 0.156 ms)
+template <class Lane, class Final>
+int msm_tail(zkhip_ctx *ctx, const uint32_t *sets, size_t nsets, uint32_t B, uint32_t *segsum, size_t segsum_blocks, uint32_t *winsum, Final final) {
+    typedef typename Lane::type TX;
+    constexpr int XL = Lane::LANES;
+    const MsmTailGeom t = msm_tail_geom<Lane>(ctx, B, nsets);
+    if (nsets * t.nblk > segsum_blocks) {
+        ctx->last_error = "MSM tail of " + std::to_string(nsets * t.nblk) + " workgroups over a partial-sum buffer for " + std::to_string(segsum_blocks);
+        return ZKHIP_ERR_RANGE;
+    }
+    ZK_MAX_LDS(ctx, (msm_bucket_red<TX, XL>), t.lds_red);
+    ZK_LAUNCH(ctx, "msm_bucket_red", (msm_bucket_red<TX, XL>), dim3((unsigned)(nsets * t.nblk)), dim3(MSM_TAIL_THREADS), t.lds_red, sets, B, t.L, t.nseg, t.nblk,
+              segsum);
+    ZK_LAUNCH(ctx, "msm_window_sum", (msm_window_sum<TX, XL>), dim3((unsigned)nsets), dim3(t.wthreads), t.lds_win, segsum, t.nblk, winsum);
+    return final();
 }
 
 // ---- the two-level tail on the host: buffers and launches --------------------------------------------------------------------
@@ -1005,73 +1036,49 @@ bool msm_fold_applies(const zkhip_ctx *ctx, uint32_t B, bool tables) {
     const uint32_t sa = MSM_TAIL_THREADS / BucketLane<F>::LANES;
     return g.m_col >= 1 && g.m_row <= sa && g.m_col <= sa && B >= sa * g.run && g.m_row * g.run == g.C && g.m_col * g.run == g.R;
 }
+template <class F>
 struct MsmFoldBuffers {
-    MsmFold g;
-    size_t level2_words, segsum_words, winsum_words;
+    static constexpr size_t PW = (size_t)4 * FieldOps<F>::WORDS;  // words per XYZZ point
+    MsmFold g{};
+    size_t nsets = 0;
     uint32_t *level2 = nullptr, *segsum = nullptr, *winsum = nullptr;
-    size_t need() const { return zkhip_ctx::ws_round(level2_words * 4) + zkhip_ctx::ws_round(segsum_words * 4) + zkhip_ctx::ws_round(winsum_words * 4); }
-    void take(zkhip_ctx *ctx) {
-        level2 = ctx->ws_take<uint32_t>(level2_words);
-        segsum = ctx->ws_take<uint32_t>(segsum_words);
-        winsum = ctx->ws_take<uint32_t>(winsum_words);
+    MsmFoldBuffers() = default;
+    MsmFoldBuffers(const zkhip_ctx *ctx, uint32_t B, size_t nsets_) : g(msm_fold_geom(ctx, B)), nsets(nsets_) {}
+    size_t level2_words() const { return nsets * 2 * g.C * PW; }
+    size_t segsum_blocks() const { return nsets * 2 * ((g.C + 63) / 64); }  // segments of >= 1 bucket, >= 64 of them per workgroup
+    template <class Arena>
+    void layout(Arena &a) {
+        a.take(level2, level2_words());
+        a.take(segsum, segsum_blocks() * PW);
+        a.take(winsum, nsets * 2 * PW);
     }
 };
-template <class F>
-MsmFoldBuffers msm_fold_buffers(const zkhip_ctx *ctx, uint32_t B, size_t nsets) {
-    constexpr size_t PW = (size_t)4 * FieldOps<F>::WORDS;  // words per XYZZ point
-    MsmFoldBuffers fb;
-    fb.g = msm_fold_geom(ctx, B);
-    fb.level2_words = nsets * 2 * fb.g.C * PW;
-    fb.segsum_words = nsets * 2 * ((fb.g.C + 63) / 64) * PW;  // segments of >= 1 bucket, >= 64 of them per workgroup
-    fb.winsum_words = nsets * 2 * PW;
-    return fb;
-}
 
-// the old tail over the 2 nsets level-2 sets with lane type TX, then the outputs
-template <class TX, int XL, bool G2>
-int msm_fold_level2(zkhip_ctx *ctx, const MsmFoldBuffers &fb, size_t nsets, uint32_t *const *d_outs, uint32_t *d_out) {
-    constexpr int NL = FieldOps<TX>::WORDS;
-    const size_t sets2 = 2 * nsets;
-    const uint32_t C = fb.g.C, L2 = msm_tail_segment(ctx, C, sets2, XL, G2), slots = MSM_TAIL_THREADS / XL;
-    const uint32_t nseg = C / L2, nblk = (nseg + slots - 1) / slots;
-    // (a variant of msm_bucket_red compiled for one-bucket segments only spills 37 instead of 173 registers and measures the same: 0.156 ms)
-    ZK_MAX_LDS(ctx, (msm_bucket_red<TX, XL>), (size_t)slots * 4 * NL * 4);
-    ZK_LAUNCH(ctx, "msm_bucket_red", (msm_bucket_red<TX, XL>), dim3((unsigned)(sets2 * nblk)), dim3(MSM_TAIL_THREADS), (size_t)slots * 4 * NL * 4, fb.level2, C, L2,
-              nseg, nblk, fb.segsum);
-    const uint32_t wt = msm_window_threads(nblk, XL);
-    ZK_LAUNCH(ctx, "msm_window_sum", (msm_window_sum<TX, XL>), dim3((unsigned)sets2), dim3(wt), (size_t)wt / XL * 4 * NL * 4, fb.segsum, nblk, fb.winsum);
-    ZK_LAUNCH(ctx, "msm_final", (msm_final_fold<TX, XL>), dim3((unsigned)nsets), dim3(64), 0, fb.winsum, (uint32_t)nsets, fb.g.log_c, d_outs, d_out);
-    return 0;
-}
-
-// sets[nsets][B] merged buckets -> nsets canonical Jacobian results (d_outs: device array of output pointers, or the one output d_out).
-// TL / TLPB: the lane shape of the level-2 tail when the quads do not apply.
-template <class F, class TL, int TLPB>
-int msm_fold_tail(zkhip_ctx *ctx, const uint32_t *sets, size_t nsets, const MsmFoldBuffers &fb, uint32_t *const *d_outs, uint32_t *d_out) {
+// sets[nsets][B] merged buckets -> nsets canonical Jacobian results (d_outs: device array of output pointers, or the one output d_out):
+// msm_fold, then the tail over the 2 nsets level-2 sets.  Lane: the lane shape of that tail when the quads do not apply.
+template <class F, class Lane>
+int msm_fold_tail(zkhip_ctx *ctx, const uint32_t *sets, const MsmFoldBuffers<F> &fb, uint32_t *const *d_outs, uint32_t *d_out) {
     constexpr int NL = FieldOps<F>::WORDS;
-    constexpr bool G2 = FieldOps<F>::WORDS > 16;
     typedef typename BucketLane<F>::type FL;
     constexpr int LPB = BucketLane<F>::LANES;
     typedef typename QuadLane<F>::type TQ;  // the trees are latency: quads where the field has them (else this IS the tail lane)
     constexpr int QL = QuadLane<F>::LANES;
     const MsmFold &g = fb.g;
-    ZK_HIP_CHECK(ctx, hipMemsetAsync(fb.level2, 0, fb.level2_words * 4, ctx->stream));  // empty buckets (the second set's upper part stays so)
+    const size_t nsets = fb.nsets;
+    ZK_HIP_CHECK(ctx, hipMemsetAsync(fb.level2, 0, fb.level2_words() * 4, ctx->stream));  // empty buckets (the second set's upper part stays so)
     const size_t lds = (size_t)MSM_TAIL_THREADS / LPB * 4 * NL * 4;
     ZK_MAX_LDS(ctx, (msm_fold<FL, LPB, TQ, QL>), lds);
     ZK_LAUNCH(ctx, "msm_fold", (msm_fold<FL, LPB, TQ, QL>), dim3((unsigned)(nsets * (g.B / (MSM_TAIL_THREADS / LPB * g.run)) * 2)), dim3(MSM_TAIL_THREADS), lds,
               sets, g, fb.level2);
-    if (QuadLane<F>::AVAILABLE && ctx->opt_msm_tail_quads && 2 * nsets * g.C <= ((size_t)1 << 18))
-        return msm_fold_level2<TQ, QL, G2>(ctx, fb, nsets, d_outs, d_out);
-    return msm_fold_level2<TL, TLPB, G2>(ctx, fb, nsets, d_outs, d_out);
-}
-
-// the tail workgroups keep 256 XYZZ points in LDS (56 KiB for G1, 128 KiB for BLS12-381 G2)
-template <class F>
-int msm_tail_attr(zkhip_ctx *ctx) {
-    typedef typename TailLane<F>::type TL;
-    constexpr int TLPB = TailLane<F>::LANES;
-    ZK_MAX_LDS(ctx, (msm_bucket_red<TL, TLPB>), MSM_TAIL_THREADS / TLPB * 4 * FieldOps<F>::WORDS * 4);
-    return 0;
+    auto level2 = [&](auto lane) -> int {  // the tail over the level-2 sets with one lane shape
+        typedef decltype(lane) X;
+        return msm_tail<X>(ctx, fb.level2, 2 * nsets, g.C, fb.segsum, fb.segsum_blocks(), fb.winsum, [&]() -> int {
+            ZK_LAUNCH(ctx, "msm_final", (msm_final_fold<typename X::type, X::LANES>), dim3((unsigned)nsets), dim3(64), 0, fb.winsum, (uint32_t)nsets, g.log_c, d_outs, d_out);
+            return 0;
+        });
+    };
+    if (QuadLane<F>::AVAILABLE && ctx->opt_msm_tail_quads && 2 * nsets * g.C <= ((size_t)1 << 18)) return level2(QuadLane<F>());
+    return level2(Lane());
 }
 
 // The geometry of one MSM call: window size, windows, sets, buckets.
@@ -1111,146 +1118,147 @@ inline MsmPlan msm_plan(const zkhip_ctx *ctx, const zkhip_bases *bases, size_t n
     return p;
 }
 
-// the sort's launch sequence for one tile shape
+// the sort's launch sequence for one tile shape (bh / bo: g.nsuper x g.W x g.ntile counters and their scan)
 template <class SZ>
-int msm_sort_run(zkhip_ctx *ctx, const SortGeom &g, int W, uint32_t nb, uint32_t nbh, uint32_t nblk, const uint32_t *dig, uint32_t *bh, uint32_t *bo,
-                 uint32_t *bsums, uint32_t *tmp_idx, uint16_t *tmp_key, uint32_t *offs, uint32_t *idx) {
+int msm_sort_run(zkhip_ctx *ctx, const SortGeom &g, uint32_t nbh, const uint32_t *dig, uint32_t *bh, uint32_t *bo, uint32_t *bsums, uint32_t *tmp_idx,
+                 uint16_t *tmp_key, uint32_t *offs, uint32_t *idx) {
     const size_t lds_hist = (size_t)g.nsuper * 4;
     const size_t lds_split = ((size_t)3 * g.nsuper + 1 + SZ::THREADS + 2 * SZ::TILE) * 4;
     const size_t lds_final = (size_t)SZ::TILE * 6;
     if (lds_split > 48 * 1024) ZK_MAX_LDS(ctx, msm_sort_split<SZ>, 160 * 1024 - 256);
     if (lds_final > 40 * 1024) ZK_MAX_LDS(ctx, msm_sort_final<SZ>, 160 * 1024 - (4 * SORT_NLOW_MAX + SZ::THREADS) * 4 - 256);
-    ZK_LAUNCH(ctx, "msm_sort_hist", msm_sort_hist<SZ>, dim3(g.ntile, W), dim3(SZ::THREADS), lds_hist, dig, g, bh);
-    (void)nblk;
+    ZK_LAUNCH(ctx, "msm_sort_hist", msm_sort_hist<SZ>, dim3(g.ntile, g.W), dim3(SZ::THREADS), lds_hist, dig, g, bh);
     ZK_TRY(msm_scan(ctx, "msm_scan", bh, nbh, bo, bsums));
-    ZK_LAUNCH(ctx, "msm_sort_split", msm_sort_split<SZ>, dim3(g.ntile, W), dim3(SZ::THREADS), lds_split, dig, g, bo, tmp_idx, tmp_key);
-    ZK_LAUNCH(ctx, "msm_sort_final", msm_sort_final<SZ>, dim3(g.nsuper), dim3(SZ::THREADS), lds_final, tmp_idx, tmp_key, g, nb, bo, offs, idx);
+    ZK_LAUNCH(ctx, "msm_sort_split", msm_sort_split<SZ>, dim3(g.ntile, g.W), dim3(SZ::THREADS), lds_split, dig, g, bo, tmp_idx, tmp_key);
+    ZK_LAUNCH(ctx, "msm_sort_final", msm_sort_final<SZ>, dim3(g.nsuper), dim3(SZ::THREADS), lds_final, tmp_idx, tmp_key, g, g.S * g.B, bo, offs, idx);
     return 0;
 }
 
+// Everything one MSM call settles before its first launch.  msm_call_plan fills it from the context's options and the bases object and
+// touches neither; the workspace (MsmBuffers) and every grid below are functions of it.
+struct MsmCall {
+    MsmPlan P;
+    SortGeom g;
+    bool big_tiles;               // the sort's tile shape (SortBig / SortSmall)
+    uint32_t nbh;                 // counters of the sort's (super-bucket, window, tile) histogram
+    uint32_t sblk, nsh;           // size sort: workgroups of 1024 buckets, counters of its (bin, workgroup) histogram
+    int Sr;                       // sets left after the equal-weight merge = sets the tail sees
+    uint32_t segsum_blocks;       // msm_bucket_red workgroups per set, the most over the lane shapes the tail may take
+    bool fold;                    // the two-level tail applies (never to a batch member: batches fold once, for all members -- msm_batch_tail)
+    // large buckets: split threshold, and the worst-case plan (every entry in a large bucket)
+    uint32_t large_thresh, large_cap, task_cap;
+    size_t entries() const { return (size_t)P.W * g.n; }
+};
+
 template <class F>
-int msm_run_t(zkhip_ctx *ctx, const zkhip_bases *bases, size_t offset, size_t n, const uint32_t *d_scalars, uint32_t *d_out_jac,
-              uint32_t *batch_slot = nullptr, size_t *need_out = nullptr, bool reuse_sort = false) {
-    constexpr int NL = FieldOps<F>::WORDS;
-    typedef typename BucketLane<F>::type FL;           // what a lane holds in the bucket kernels
-    constexpr int LPB = BucketLane<F>::LANES;          // lanes per point (2 for G2: fu2_pair.hpp)
-    typedef typename TailLane<F>::type TL;             // ... and in the latency-bound tail (G1: group law over a lane pair, fu_pair.hpp)
-    constexpr int TLPB = TailLane<F>::LANES;
-    constexpr bool G2 = FieldOps<F>::WORDS > 16;
-    const MsmPlan P = msm_plan(ctx, bases, n);
-    const int W = P.W;
-    const uint32_t B = P.B, S = P.S, nb = P.nb;
+int msm_call_plan(const zkhip_ctx *ctx, const zkhip_bases *bases, size_t offset, size_t n, bool batch_member, MsmCall &c, std::string &error) {
+    const MsmPlan &P = c.P = msm_plan(ctx, bases, n);
     // every sort offset / prefix sum / idx position is a u32 over the W * n entries, and an entry addresses a table row
-    if ((uint64_t)W * n >= (1ull << 32) || (uint64_t)bases->nslots * bases->n >= (1ull << 31)) {
-        ctx->last_error = "MSM of " + std::to_string(n) + " points x " + std::to_string(W) + " windows exceeds the 32-bit entry index (split the range)";
+    if ((uint64_t)P.W * n >= (1ull << 32) || (uint64_t)bases->nslots * bases->n >= (1ull << 31)) {
+        error = "MSM of " + std::to_string(n) + " points x " + std::to_string(P.W) + " windows exceeds the 32-bit entry index (split the range)";
         return ZKHIP_ERR_RANGE;
     }
-    const int Sr = P.tables ? 1 : W;  // sets left after the equal-weight merge
-    const uint32_t L = msm_tail_segment(ctx, B, Sr, TLPB, G2);  // buckets per tail segment
-    const uint32_t tail_slots = MSM_TAIL_THREADS / TLPB;  // points per tail workgroup
-    const uint32_t nseg = B / L, nblk_tail = (nseg + tail_slots - 1) / tail_slots;
-    // the quad variant of the tail (below) may cut the set into more workgroups: the partial-sum buffer holds either
-    const uint32_t Lq_cap = msm_tail_segment(ctx, B, Sr, QuadLane<F>::LANES, G2);
-    const uint32_t nblk_cap = std::max(nblk_tail, (B / Lq_cap + MSM_TAIL_THREADS / QuadLane<F>::LANES - 1) / (MSM_TAIL_THREADS / QuadLane<F>::LANES));
     // two-level LDS counting sort (see msm_sort_*): the low bits inside a super-bucket, the rest across super-buckets
-    SortGeom g;
+    SortGeom &g = c.g;
     g.n = (uint32_t)n;
-    g.W = (uint32_t)W;
-    g.B = B;
-    g.S = S;
+    g.W = (uint32_t)P.W;
+    g.B = P.B;
+    g.S = P.S;
     g.lowb = (uint32_t)std::min<int>(SORT_MAX_LOW, P.c - 1);
-    g.nsuper = (nb + (1u << g.lowb) - 1) >> g.lowb;
-    const bool big_tiles = ctx->opt_msm_sort_tile_log >= 14;
-    g.tile = big_tiles ? SortBig::TILE : SortSmall::TILE;
+    g.nsuper = (P.nb + (1u << g.lowb) - 1) >> g.lowb;
+    c.big_tiles = ctx->opt_msm_sort_tile_log >= 14;
+    g.tile = c.big_tiles ? SortBig::TILE : SortSmall::TILE;
     g.ntile = (uint32_t)((n + g.tile - 1) / g.tile);
     g.tables = P.tables ? 1u : 0u;
     g.slot0 = P.tables ? (uint32_t)bases->slot_of_local(0) : 0u;
     g.bases_n = (uint32_t)bases->n;
     g.base_off = (uint32_t)offset;
     if (g.nsuper > SORT_MAX_SUPER) return ZKHIP_ERR_RANGE;
-    const size_t ncol = (size_t)W * g.ntile;
-    const size_t nbh64 = (size_t)g.nsuper * ncol;
+    const size_t nbh64 = (size_t)g.nsuper * g.W * g.ntile;
     if (nbh64 >= (1ull << 31)) return ZKHIP_ERR_RANGE;
-    const uint32_t nbh = (uint32_t)nbh64, nblk = (nbh + 1023) / 1024;
+    c.nbh = (uint32_t)nbh64;
+    c.sblk = (P.nb + 1023) / 1024;
+    c.nsh = SIZE_BINS * c.sblk;
+    c.Sr = P.tables ? 1 : P.W;
+    // the quad variant of the tail (msm_run_t) may cut the set into more workgroups than the default one: the partial-sum buffer holds either
+    c.segsum_blocks = std::max(msm_tail_geom<TailLane<F>>(ctx, P.B, c.Sr).nblk, msm_tail_geom<QuadLane<F>>(ctx, P.B, c.Sr).nblk);
+    c.fold = !batch_member && msm_fold_applies<F>(ctx, P.B, P.tables);
+    c.large_thresh = (uint32_t)std::max<size_t>(MSM_LARGE_BUCKET, 4 * ((c.entries() + P.nb - 1) / P.nb));
+    c.large_cap = (uint32_t)(c.entries() / c.large_thresh + 1);
+    c.task_cap = (uint32_t)(c.entries() / MSM_LARGE_CHUNK + c.large_cap + 1);
+    return 0;
+}
 
-    size_t need = 0;
-    need += zkhip_ctx::ws_round((size_t)W * n * 4);        // dig
-    need += zkhip_ctx::ws_round((size_t)nbh * 4);          // per-tile super-bucket histogram
-    need += zkhip_ctx::ws_round(((size_t)nbh + 1) * 4);    // its exclusive scan
-    need += zkhip_ctx::ws_round((size_t)nblk * 4);         // block sums
-    need += zkhip_ctx::ws_round((size_t)W * n * 4);        // tmp_idx
-    need += zkhip_ctx::ws_round((size_t)W * n * 2);        // tmp_key
-    need += zkhip_ctx::ws_round(((size_t)nb + 1) * 4);     // offs
-    need += zkhip_ctx::ws_round((size_t)W * n * 4);        // idx
-    need += zkhip_ctx::ws_round((size_t)nb * 4 * NL * 4);  // buckets
-    const uint32_t sblk = (nb + 1023) / 1024, nsh = SIZE_BINS * sblk, sblk2 = (nsh + 1023) / 1024;
-    need += 2 * zkhip_ctx::ws_round(((size_t)nsh + 1) * 4) + zkhip_ctx::ws_round((size_t)sblk2 * 4) + zkhip_ctx::ws_round((size_t)nb * 4);  // size sort
-    need += zkhip_ctx::ws_round((size_t)Sr * nblk_cap * 4 * NL * 4);
-    need += zkhip_ctx::ws_round((size_t)std::max(1, Sr) * 4 * NL * 4);
-    const bool fold = !batch_slot && msm_fold_applies<F>(ctx, B, P.tables);  // batches fold once, for all members (msm_batch_tail)
-    MsmFoldBuffers fb;
-    if (fold) {
-        fb = msm_fold_buffers<F>(ctx, B, 1);
-        need += fb.need();
+// The per-call workspace of one MSM, in the order it lies in memory.
+template <class F>
+struct MsmBuffers {
+    static constexpr size_t PW = (size_t)4 * FieldOps<F>::WORDS;  // words per XYZZ point
+    const MsmCall &c;
+    uint32_t *dig, *bh, *bo, *bsums, *tmp_idx;  // digits; the sort's histogram, its exclusive scan, the scan's block sums
+    uint16_t *tmp_key;
+    uint32_t *offs, *idx, *buckets;
+    uint32_t *sh, *so, *ssums, *order;  // size sort: histogram, its scan, block sums; bucket ids by descending size
+    uint32_t *segsum, *winsum;
+    MsmFoldBuffers<F> fb;
+    uint32_t *plan, *tasks, *large, *partials;  // large buckets (msm_plan_large)
+    MsmBuffers(const zkhip_ctx *ctx, const MsmCall &call) : c(call) {
+        if (c.fold) fb = MsmFoldBuffers<F>(ctx, c.P.B, 1);
     }
-    // worst-case plan of the large-bucket path: every entry in a large bucket
-    const size_t entries = (size_t)W * n;
-    const uint32_t large_thresh = (uint32_t)std::max<size_t>(MSM_LARGE_BUCKET, 4 * ((entries + nb - 1) / nb));
-    const uint32_t large_cap = (uint32_t)(entries / large_thresh + 1);
-    const uint32_t task_cap = (uint32_t)(entries / MSM_LARGE_CHUNK + large_cap + 1);
-    need += zkhip_ctx::ws_round(16) + zkhip_ctx::ws_round((size_t)task_cap * 12) + zkhip_ctx::ws_round((size_t)large_cap * 12);
-    need += zkhip_ctx::ws_round((size_t)task_cap * 4 * NL * 4);
-    if (need_out) {  // dry run: workspace size only
-        *need_out = need;
-        return 0;
+    template <class Arena>
+    void layout(Arena &a) {
+        a.take(dig, c.entries());
+        a.take(bh, c.nbh);
+        a.take(bo, (size_t)c.nbh + 1);
+        a.take(bsums, (c.nbh + 1023) / 1024);
+        a.take(tmp_idx, c.entries());
+        a.take(tmp_key, c.entries());
+        a.take(offs, (size_t)c.P.nb + 1);
+        a.take(idx, c.entries());
+        a.take(buckets, c.P.nb * PW);
+        a.take(sh, (size_t)c.nsh + 1);
+        a.take(so, (size_t)c.nsh + 1);
+        a.take(ssums, (c.nsh + 1023) / 1024);
+        a.take(order, c.P.nb);
+        a.take(segsum, (size_t)c.Sr * c.segsum_blocks * PW);
+        a.take(winsum, (size_t)std::max(1, c.Sr) * PW);
+        if (c.fold) fb.layout(a);
+        a.take(plan, 4);
+        a.take(tasks, (size_t)c.task_cap * 3);
+        a.take(large, (size_t)c.large_cap * 3);
+        a.take(partials, c.task_cap * PW);
     }
-    ZK_TRY(ctx->ws_reserve(ctx->ws_floor + need));
-    ctx->ws_reset();
-    uint32_t *dig = ctx->ws_take<uint32_t>((size_t)W * n);
-    uint32_t *bh = ctx->ws_take<uint32_t>(nbh);
-    uint32_t *bo = ctx->ws_take<uint32_t>((size_t)nbh + 1);
-    uint32_t *bsums = ctx->ws_take<uint32_t>(nblk);
-    uint32_t *tmp_idx = ctx->ws_take<uint32_t>((size_t)W * n);
-    uint16_t *tmp_key = ctx->ws_take<uint16_t>((size_t)W * n);
-    uint32_t *offs = ctx->ws_take<uint32_t>((size_t)nb + 1);
-    uint32_t *idx = ctx->ws_take<uint32_t>((size_t)W * n);
-    uint32_t *buckets = ctx->ws_take<uint32_t>((size_t)nb * 4 * NL);
-    if (batch_slot && S == 1) buckets = batch_slot;  // a batch member with ONE set accumulates straight into its slot of the batch (no copy of 2^19 buckets = 117 MB)
-    uint32_t *sh = ctx->ws_take<uint32_t>((size_t)nsh + 1);
-    uint32_t *so = ctx->ws_take<uint32_t>((size_t)nsh + 1);
-    uint32_t *ssums = ctx->ws_take<uint32_t>(sblk2);
-    uint32_t *order = ctx->ws_take<uint32_t>(nb);
-    uint32_t *segsum = ctx->ws_take<uint32_t>((size_t)Sr * nblk_cap * 4 * NL);
-    uint32_t *winsum = ctx->ws_take<uint32_t>((size_t)std::max(1, Sr) * 4 * NL);
-    if (fold) fb.take(ctx);
-    uint32_t *plan = ctx->ws_take<uint32_t>(4);
-    uint32_t *tasks = ctx->ws_take<uint32_t>((size_t)task_cap * 3);
-    uint32_t *large = ctx->ws_take<uint32_t>((size_t)large_cap * 3);
-    uint32_t *partials = ctx->ws_take<uint32_t>((size_t)task_cap * 4 * NL);
+};
 
+// The stages of one MSM up to the merged buckets: digits, sort, size order, accumulation, large buckets, merge of the equal-weight sets.
+// reuse_sort (batches: the previous member had the SAME scalars over an entry-compatible bases object -- msm_same_entries): the
+// sorted entries, bucket offsets, size order and large-bucket plan in the workspace are this member's too (same sizes, so the same
+// addresses); only the gathers read another table
+template <class F>
+int msm_stages(zkhip_ctx *ctx, const zkhip_bases *bases, const MsmCall &c, const MsmBuffers<F> &w, const uint32_t *d_scalars, bool reuse_sort) {
+    constexpr int NL = FieldOps<F>::WORDS;
+    typedef typename BucketLane<F>::type FL;   // what a lane holds in the bucket kernels
+    constexpr int LPB = BucketLane<F>::LANES;  // lanes per point (2 for G2: fu2_pair.hpp)
+    const MsmPlan &P = c.P;
+    const uint32_t n = c.g.n, nb = P.nb;
     const uint32_t *d_b = bases->d;  // entries address table rows from the start of the bases object
-
-    // reuse_sort (batches: the previous member had the SAME scalars over an entry-compatible bases object -- msm_same_entries): the
-    // sorted entries, bucket offsets, size order and large-bucket plan in the workspace are this member's too (same sizes, so the same
-    // addresses); only the gathers read another table
     if (!reuse_sort) {
         unsigned gn = (unsigned)((n + 255) / 256);
         if (bases->curve == CURVE_BLS12_381)
-            ZK_LAUNCH(ctx, "msm_digits", msm_digits_only<BlsFr>, dim3(gn), dim3(256), 0, d_scalars, (uint32_t)n, P.win, P.wrank, P.wworld, dig);
-        else ZK_LAUNCH(ctx, "msm_digits", msm_digits_only<BnFr>, dim3(gn), dim3(256), 0, d_scalars, (uint32_t)n, P.win, P.wrank, P.wworld, dig);
-        ZK_TRY((big_tiles ? msm_sort_run<SortBig> : msm_sort_run<SortSmall>)(ctx, g, W, nb, nbh, nblk, dig, bh, bo, bsums, tmp_idx, tmp_key, offs, idx));
+            ZK_LAUNCH(ctx, "msm_digits", msm_digits_only<BlsFr>, dim3(gn), dim3(256), 0, d_scalars, n, P.win, P.wrank, P.wworld, w.dig);
+        else ZK_LAUNCH(ctx, "msm_digits", msm_digits_only<BnFr>, dim3(gn), dim3(256), 0, d_scalars, n, P.win, P.wrank, P.wworld, w.dig);
+        ZK_TRY((c.big_tiles ? msm_sort_run<SortBig> : msm_sort_run<SortSmall>)(ctx, c.g, c.nbh, w.dig, w.bh, w.bo, w.bsums, w.tmp_idx, w.tmp_key, w.offs, w.idx));
         // buckets by descending size
-        ZK_LAUNCH(ctx, "msm_size_sort", msm_size_hist, dim3(sblk), dim3(256), 0, offs, nb, sblk, large_thresh, sh);
-        ZK_TRY(msm_scan(ctx, "msm_size_sort", sh, nsh, so, ssums));
-        ZK_LAUNCH(ctx, "msm_size_sort", msm_size_scatter, dim3(sblk), dim3(256), 0, offs, nb, sblk, large_thresh, so, order);
+        ZK_LAUNCH(ctx, "msm_size_sort", msm_size_hist, dim3(c.sblk), dim3(256), 0, w.offs, nb, c.sblk, c.large_thresh, w.sh);
+        ZK_TRY(msm_scan(ctx, "msm_size_sort", w.sh, c.nsh, w.so, w.ssums));
+        ZK_LAUNCH(ctx, "msm_size_sort", msm_size_scatter, dim3(c.sblk), dim3(256), 0, w.offs, nb, c.sblk, c.large_thresh, w.so, w.order);
     }
     if constexpr (FieldOps<F>::WORDS <= 16) {
         // G1: accumulator coordinates in LDS, three waves per SIMD
         constexpr int NT = MSM_G1_THREADS;
         size_t lds_acc = LdsAcc<F, NT>::BYTES;
         ZK_MAX_LDS(ctx, (msm_bucket_acc_lds<F, NT, 3>), lds_acc);
-        ZK_LAUNCH(ctx, "msm_bucket_acc", (msm_bucket_acc_lds<F, NT, 3>), dim3((nb + NT - 1) / NT), dim3(NT), lds_acc, d_b, offs, idx, nb, large_thresh,
-                  order, buckets);
+        ZK_LAUNCH(ctx, "msm_bucket_acc", (msm_bucket_acc_lds<F, NT, 3>), dim3((nb + NT - 1) / NT), dim3(NT), lds_acc, d_b, w.offs, w.idx, nb, c.large_thresh,
+                  w.order, w.buckets);
     } else {
         // G2: every bucket is an even / odd lane pair, each lane holding one component of the Fq2 coordinates
         // (fu2_pair.hpp): a lane then carries what a G1 lane carries -- two waves per SIMD instead of one.
@@ -1258,58 +1266,75 @@ int msm_run_t(zkhip_ctx *ctx, const zkhip_bases *bases, size_t offset, size_t n,
         size_t lds_acc = LdsAcc<FL, NT>::BYTES;
         ZK_MAX_LDS(ctx, (msm_bucket_acc_lds<FL, NT, WAVES, LPB>), lds_acc);
         ZK_LAUNCH(ctx, "msm_bucket_acc", (msm_bucket_acc_lds<FL, NT, WAVES, LPB>), dim3((unsigned)(((size_t)nb * LPB + NT - 1) / NT)), dim3(NT), lds_acc, d_b,
-                  offs, idx, nb, large_thresh, order, buckets);
+                  w.offs, w.idx, nb, c.large_thresh, w.order, w.buckets);
     }
     // large buckets: plan on the device (no host round trip), then fixed-size grids that read the plan
     if (!reuse_sort) {
-        ZK_HIP_CHECK(ctx, hipMemsetAsync(plan, 0, 16, ctx->stream));
-        ZK_LAUNCH(ctx, "msm_plan_large", msm_plan_large, dim3((nb + 255) / 256), dim3(256), 0, offs, nb, plan, tasks, large, task_cap, large_cap, large_thresh,
-                  ctx->d_status);
+        ZK_HIP_CHECK(ctx, hipMemsetAsync(w.plan, 0, 16, ctx->stream));
+        ZK_LAUNCH(ctx, "msm_plan_large", msm_plan_large, dim3((nb + 255) / 256), dim3(256), 0, w.offs, nb, w.plan, w.tasks, w.large, c.task_cap, c.large_cap,
+                  c.large_thresh, ctx->d_status);
     }
     {
         size_t lds_large = (size_t)128 / LPB * 4 * NL * 4;
         if (lds_large > 48 * 1024) ZK_MAX_LDS(ctx, (msm_bucket_large<FL, LPB>), lds_large);
-        unsigned grid_large = (unsigned)std::min<size_t>(task_cap, 512);  // persistent: workgroups loop over the task list
-        ZK_LAUNCH(ctx, "msm_bucket_large", (msm_bucket_large<FL, LPB>), dim3(grid_large), dim3(128), lds_large, d_b, idx, plan, tasks, partials);
-        ZK_LAUNCH(ctx, "msm_bucket_large", (msm_large_combine<FL, LPB>), dim3((unsigned)std::min<uint32_t>(large_cap, 256)), dim3(64),
-                  (size_t)64 / LPB * 4 * NL * 4, plan, large, partials, buckets);
+        unsigned grid_large = (unsigned)std::min<size_t>(c.task_cap, 512);  // persistent: workgroups loop over the task list
+        ZK_LAUNCH(ctx, "msm_bucket_large", (msm_bucket_large<FL, LPB>), dim3(grid_large), dim3(128), lds_large, d_b, w.idx, w.plan, w.tasks, w.partials);
+        ZK_LAUNCH(ctx, "msm_bucket_large", (msm_large_combine<FL, LPB>), dim3((unsigned)std::min<uint32_t>(c.large_cap, 256)), dim3(64),
+                  (size_t)64 / LPB * 4 * NL * 4, w.plan, w.large, w.partials, w.buckets);
     }
     if (P.tables) {
-        for (uint32_t cur = S; cur > 1;) {
+        for (uint32_t cur = P.S; cur > 1;) {
             const uint32_t q = (cur + 3) / 4;
-            ZK_LAUNCH(ctx, "msm_bucket_merge", (msm_bucket_merge<FL, LPB>), dim3((unsigned)(((size_t)q * B * LPB + 255) / 256)), dim3(256), 0, buckets, B, q,
+            ZK_LAUNCH(ctx, "msm_bucket_merge", (msm_bucket_merge<FL, LPB>), dim3((unsigned)(((size_t)q * P.B * LPB + 255) / 256)), dim3(256), 0, w.buckets, P.B, q,
                       cur);
             cur = q;
         }
     }
-    if (batch_slot) {  // batched call: hand the merged buckets over, the reduction runs once for the whole batch
-        if (buckets != batch_slot) ZK_HIP_CHECK(ctx, hipMemcpyAsync(batch_slot, buckets, (size_t)B * 4 * NL * 4, hipMemcpyDeviceToDevice, ctx->stream));
-        return 0;
-    }
-    if (fold) return msm_fold_tail<F, TL, TLPB>(ctx, buckets, 1, fb, nullptr, d_out_jac);
-    // Small bucket sets leave lanes to spare even as pairs: the group law then runs over lane QUADS (fu_quad.hpp: 4 product steps per
-    // addition instead of 7) with segments twice as long -- from 2^18 buckets down; at 2^19 the longer segments eat the gain.
-    if (QuadLane<F>::AVAILABLE && ctx->opt_msm_tail_quads && (size_t)Sr * B <= ((size_t)1 << 18)) {
-        typedef typename QuadLane<F>::type TQ;
-        constexpr int QL = QuadLane<F>::LANES;
-        const uint32_t Lq = msm_tail_segment(ctx, B, Sr, QL, G2), slots_q = MSM_TAIL_THREADS / QL;
-        const uint32_t nseg_q = B / Lq, nblk_q = (nseg_q + slots_q - 1) / slots_q;  // <= nblk_cap: the partial-sum buffer fits
-        ZK_MAX_LDS(ctx, (msm_bucket_red<TQ, QL>), MSM_TAIL_THREADS / QL * 4 * NL * 4);
-        ZK_LAUNCH(ctx, "msm_bucket_red", (msm_bucket_red<TQ, QL>), dim3((unsigned)Sr * nblk_q), dim3(MSM_TAIL_THREADS), (size_t)slots_q * 4 * NL * 4, buckets, B,
-                  Lq, nseg_q, nblk_q, segsum);
-        const uint32_t wt = msm_window_threads(nblk_q, QL);
-        ZK_LAUNCH(ctx, "msm_window_sum", (msm_window_sum<TQ, QL>), dim3(Sr), dim3(wt), (size_t)wt / QL * 4 * NL * 4, segsum, nblk_q, winsum);
-        ZK_LAUNCH(ctx, "msm_final", (msm_final<TQ, QL>), dim3(1), dim3(64), 0, winsum, Sr, P.win, d_out_jac);
-        return 0;
-    }
-    ZK_TRY(msm_tail_attr<F>(ctx));
-    ZK_LAUNCH(ctx, "msm_bucket_red", (msm_bucket_red<TL, TLPB>), dim3((unsigned)Sr * nblk_tail), dim3(MSM_TAIL_THREADS), (size_t)tail_slots * 4 * NL * 4, buckets, B,
-              L, nseg, nblk_tail, segsum);
-    const uint32_t wthreads = msm_window_threads(nblk_tail, TLPB);
-    ZK_LAUNCH(ctx, "msm_window_sum", (msm_window_sum<TL, TLPB>), dim3(Sr), dim3(wthreads), (size_t)wthreads / TLPB * 4 * NL * 4, segsum, nblk_tail, winsum);
-    ZK_LAUNCH(ctx, "msm_final", (msm_final<TL, TLPB>), dim3(1), dim3(64), 0, winsum, Sr, P.win, d_out_jac);
     return 0;
 }
+
+// one MSM: plan, workspace, stages, tail
+template <class F>
+int msm_run_t(zkhip_ctx *ctx, const zkhip_bases *bases, size_t offset, size_t n, const uint32_t *d_scalars, uint32_t *d_out_jac) {
+    MsmCall c;
+    ZK_TRY(msm_call_plan<F>(ctx, bases, offset, n, false, c, ctx->last_error));
+    MsmBuffers<F> w(ctx, c);
+    ZK_TRY(ws_place(ctx, w));
+    ZK_TRY(msm_stages<F>(ctx, bases, c, w, d_scalars, false));
+    if (c.fold) return msm_fold_tail<F, TailLane<F>>(ctx, w.buckets, w.fb, nullptr, d_out_jac);
+    // without tables the sets are the windows: Horner over them in msm_final
+    auto tail = [&](auto lane) -> int {  // (in the tail a G1 lane holds half a point: the group law over a lane pair, fu_pair.hpp)
+        typedef decltype(lane) X;
+        return msm_tail<X>(ctx, w.buckets, (size_t)c.Sr, c.P.B, w.segsum, (size_t)c.Sr * c.segsum_blocks, w.winsum, [&]() -> int {
+            ZK_LAUNCH(ctx, "msm_final", (msm_final<typename X::type, X::LANES>), dim3(1), dim3(64), 0, w.winsum, c.Sr, c.P.win, d_out_jac);
+            return 0;
+        });
+    };
+    // Small bucket sets leave lanes to spare even as pairs: the group law then runs over lane QUADS (fu_quad.hpp: 4 product steps per
+    // addition instead of 7) with segments twice as long -- from 2^18 buckets down; at 2^19 the longer segments eat the gain.
+    if (QuadLane<F>::AVAILABLE && ctx->opt_msm_tail_quads && (size_t)c.Sr * c.P.B <= ((size_t)1 << 18)) return tail(QuadLane<F>());
+    return tail(TailLane<F>());
+}
+
+// one member of a batch: the stages into `slot` (B buckets of the batch area); the tail runs once for the whole batch.
+template <class F>
+int msm_batch_member(zkhip_ctx *ctx, const zkhip_bases *bases, size_t offset, size_t n, const uint32_t *d_scalars, uint32_t *slot, bool reuse_sort) {
+    MsmCall c;
+    ZK_TRY(msm_call_plan<F>(ctx, bases, offset, n, true, c, ctx->last_error));
+    MsmBuffers<F> w(ctx, c);
+    ZK_TRY(ws_place(ctx, w));
+    if (c.P.S == 1) w.buckets = slot;  // ONE set: accumulate straight into the slot (no copy of 2^19 buckets = 117 MB)
+    ZK_TRY(msm_stages<F>(ctx, bases, c, w, d_scalars, reuse_sort));
+    if (w.buckets != slot) ZK_HIP_CHECK(ctx, hipMemcpyAsync(slot, w.buckets, c.P.B * MsmBuffers<F>::PW * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    return 0;
+}
+
+struct BasesTmp {  // bases_precompute_range's parked points: 5 field elements per (kept window, point of the largest chunk)
+    size_t words;
+    uint32_t *tmp;
+    template <class Arena>
+    void layout(Arena &a) { a.take(tmp, words); }
+};
 
 // Build the window tables of a bases object whose slot 0 (the points) is filled (called once at upload).
 template <class F>
@@ -1319,12 +1344,11 @@ int bases_precompute_t(zkhip_ctx *ctx, zkhip_bases *b) {
     const size_t chunk = 1u << 18;  // bounds the temporary to kept * 2^18 * 5 field elements
     const int kept = b->local_windows() - (b->win_rank == 0 ? 1 : 0);  // window 0 is the points themselves
     if (kept <= 0) return 0;
-    size_t per = (size_t)kept * 5 * NL * 4;
-    ZK_TRY(ctx->ws_reserve(per * std::min(chunk, b->n) + 4096));
+    BasesTmp w = {(size_t)kept * 5 * NL * std::min(chunk, b->n), nullptr};  // every chunk parks its points in the same place
+    ZK_TRY(ws_place(ctx, w));
+    uint32_t *tmp = w.tmp;
     for (size_t lo = 0; lo < b->n; lo += chunk) {
         size_t cnt = std::min(chunk, b->n - lo);
-        ctx->ws_reset();
-        uint32_t *tmp = ctx->ws_take<uint32_t>(per / 4 * cnt);
         ZK_LAUNCH(ctx, "bases_precompute", bases_precompute_range<F>, dim3((unsigned)((cnt + 63) / 64)), dim3(64), 0, b->d, (uint32_t)b->n,
                   (uint32_t)lo, (uint32_t)cnt, msm_make_windows(zk_scalar_bits(b->curve), b->ntab), (uint32_t)b->win_rank, (uint32_t)b->win_world, tmp);
     }
@@ -1340,45 +1364,54 @@ inline bool msm_same_entries(const zkhip_bases *a, size_t off_a, size_t n_a, con
            a->win_rank == b->win_rank && a->win_world == b->win_world && a->nslots == b->nslots && a->tables() && b->tables();
 }
 
+template <class F>
+struct MsmBatchArea {  // below the members' workspaces: a bucket set per member, the shared tail's sums, the output pointers
+    static constexpr size_t PW = MsmBuffers<F>::PW;
+    size_t count, slot_words, segsum_blocks;
+    bool fold;
+    uint32_t *slots, *segsum, *winsum, **d_ptrs;
+    MsmFoldBuffers<F> fb;
+    template <class Arena>
+    void layout(Arena &a) {
+        a.take(slots, count * slot_words);
+        a.take(segsum, segsum_blocks * PW);
+        a.take(winsum, count * PW);
+        a.take(d_ptrs, count);
+        if (fold) fb.layout(a);
+    }
+};
+
 // Several MSMs over table-backed bases of one group with one window size: per MSM digits / sort / accumulate /
 // merge as usual, then ONE bucket reduction, set sum and output conversion for the whole batch.
-// TL / TLPB: what a lane of the shared tail holds.  A few members: the latency-bound shape of a single MSM (G1: the group law over
+// Lane: what a lane of the shared tail holds.  A few members: the latency-bound shape of a single MSM (G1: the group law over
 // lane pairs).  Many members (50 KZG columns x 2^19 buckets) have lanes to spare and are bound by WORK: one lane per point then
 // does the same additions without the pair's selects and DPP swaps (measured: msm_bucket_red of a 50-column 2^20-row commit
 // 16.2 -> 13.7 ms).
-template <class F, class TL, int TLPB>
+template <class F, class Lane>
 int msm_batch_tail(zkhip_ctx *ctx, size_t count, const zkhip_bases *const *bases, const size_t *offsets, const size_t *ns,
                    const uint32_t *const *d_scalars, uint32_t *const *d_outs) {
-    constexpr int NL = FieldOps<F>::WORDS;
-    const int c = bases[0]->c_tab;
-    const uint32_t B = 1u << (c - 1);
-    const uint32_t L = msm_tail_segment(ctx, B, count, TLPB, FieldOps<F>::WORDS > 16);
-    const uint32_t tail_slots = MSM_TAIL_THREADS / TLPB;  // points per tail workgroup
-    const uint32_t nseg = B / L, nblk_tail = (nseg + tail_slots - 1) / tail_slots;
+    const uint32_t B = 1u << (bases[0]->c_tab - 1);
+    // the members' own workspaces follow the batch area, one after the other in the same place.  Each is sized as the lone call it would be (the
+    // fold buffers of one set more than a member takes), which keeps the reservation, and so every address, where it has always been
     size_t max_need = 0;
     for (size_t i = 0; i < count; ++i) {
-        size_t need = 0;
         if (ns[i] == 0 || bases[i]->local_windows() == 0) continue;
-        ZK_TRY(msm_run_t<F>(ctx, bases[i], offsets[i], ns[i], nullptr, nullptr, nullptr, &need));
-        max_need = std::max(max_need, need);
+        MsmCall c;
+        ZK_TRY(msm_call_plan<F>(ctx, bases[i], offsets[i], ns[i], false, c, ctx->last_error));
+        MsmBuffers<F> w(ctx, c);
+        max_need = std::max(max_need, ws_bytes(w));
     }
-    const size_t slot_words = (size_t)B * 4 * NL;
-    size_t fixed = zkhip_ctx::ws_round(count * slot_words * 4) + zkhip_ctx::ws_round(count * nblk_tail * 4 * NL * 4) +
-                   zkhip_ctx::ws_round(count * 4 * NL * 4) + zkhip_ctx::ws_round(count * sizeof(void *));
-    const bool fold = msm_fold_applies<F>(ctx, B, true);
-    MsmFoldBuffers fb;
-    if (fold) {
-        fb = msm_fold_buffers<F>(ctx, B, count);
-        fixed += fb.need();
-    }
+    MsmBatchArea<F> area;
+    area.count = count;
+    area.slot_words = B * area.PW;
+    area.segsum_blocks = count * msm_tail_geom<Lane>(ctx, B, count).nblk;
+    area.fold = msm_fold_applies<F>(ctx, B, true);
+    if (area.fold) area.fb = MsmFoldBuffers<F>(ctx, B, count);
     ctx->ws_floor = 0;
-    ZK_TRY(ctx->ws_reserve(fixed + max_need));
-    ctx->ws_reset();
-    uint32_t *slots = ctx->ws_take<uint32_t>(count * slot_words);
-    uint32_t *segsum = ctx->ws_take<uint32_t>(count * nblk_tail * 4 * NL);
-    uint32_t *winsum = ctx->ws_take<uint32_t>(count * 4 * NL);
-    uint32_t **d_ptrs = ctx->ws_take<uint32_t *>(count);
-    if (fold) fb.take(ctx);
+    ZK_TRY(ws_place(ctx, area, max_need));
+    uint32_t *const slots = area.slots;
+    const size_t slot_words = area.slot_words;
+    uint32_t **d_ptrs = area.d_ptrs;
     ctx->ws_floor = ctx->ws_off;  // the per-MSM stages bump-allocate above the batch area
     int rc = 0;
     size_t prev = (size_t)-1;  // the member whose sort the workspace holds
@@ -1389,7 +1422,7 @@ int msm_batch_tail(zkhip_ctx *ctx, size_t count, const zkhip_bases *const *bases
         } else {
             const bool reuse = ctx->opt_msm_share_sort && prev != (size_t)-1 &&
                                msm_same_entries(bases[prev], offsets[prev], ns[prev], d_scalars[prev], bases[i], offsets[i], ns[i], d_scalars[i]);
-            rc = msm_run_t<F>(ctx, bases[i], offsets[i], ns[i], d_scalars[i], nullptr, slots + i * slot_words, nullptr, reuse);
+            rc = msm_batch_member<F>(ctx, bases[i], offsets[i], ns[i], d_scalars[i], slots + i * slot_words, reuse);
             prev = i;
         }
     }
@@ -1401,34 +1434,25 @@ int msm_batch_tail(zkhip_ctx *ctx, size_t count, const zkhip_bases *const *bases
         ctx->batch_ptrs.assign(d_outs, d_outs + count);
         ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_ptrs, ctx->batch_ptrs.data(), count * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
     }
-    if (fold) return msm_fold_tail<F, TL, TLPB>(ctx, slots, count, fb, d_ptrs, nullptr);
-    ZK_MAX_LDS(ctx, (msm_bucket_red<TL, TLPB>), MSM_TAIL_THREADS / TLPB * 4 * NL * 4);
-    ZK_LAUNCH(ctx, "msm_bucket_red", (msm_bucket_red<TL, TLPB>), dim3((unsigned)count * nblk_tail), dim3(MSM_TAIL_THREADS), (size_t)tail_slots * 4 * NL * 4, slots,
-              B, L, nseg, nblk_tail, segsum);
-    const uint32_t wthreads = msm_window_threads(nblk_tail, TLPB);
-    ZK_LAUNCH(ctx, "msm_window_sum", (msm_window_sum<TL, TLPB>), dim3((unsigned)count), dim3(wthreads), (size_t)wthreads / TLPB * 4 * NL * 4, segsum, nblk_tail, winsum);
-    ZK_LAUNCH(ctx, "msm_final", (msm_final_batch<TL, TLPB>), dim3((unsigned)count), dim3(64), 0, winsum, (uint32_t)count, d_ptrs);
-    return 0;
+    if (area.fold) return msm_fold_tail<F, Lane>(ctx, slots, area.fb, d_ptrs, nullptr);
+    return msm_tail<Lane>(ctx, slots, count, B, area.segsum, area.segsum_blocks, area.winsum, [&]() -> int {
+        ZK_LAUNCH(ctx, "msm_final", (msm_final_batch<typename Lane::type, Lane::LANES>), dim3((unsigned)count), dim3(64), 0, area.winsum, (uint32_t)count, d_ptrs);
+        return 0;
+    });
 }
 
 template <class F>
 int msm_batch_t(zkhip_ctx *ctx, size_t count, const zkhip_bases *const *bases, const size_t *offsets, const size_t *ns,
                 const uint32_t *const *d_scalars, uint32_t *const *d_outs) {
-    typedef typename BucketLane<F>::type FL;
-    typedef typename TailLane<F>::type TL;
     const size_t buckets = count << (bases[0]->c_tab - 1);
     // >= 2^21 buckets in all (the four G1 multiexps of a proof: msm_bucket_red 2.16 -> 1.87 ms; 50 KZG columns: 16.2 -> 13.7):
     // the one-lane shape keeps every SIMD busy by itself -- work-bound
-    if (!std::is_same<FL, TL>::value && buckets >= ((size_t)1 << 21))
-        return msm_batch_tail<F, FL, BucketLane<F>::LANES>(ctx, count, bases, offsets, ns, d_scalars, d_outs);
-    return msm_batch_tail<F, TL, TailLane<F>::LANES>(ctx, count, bases, offsets, ns, d_scalars, d_outs);
+    if (!std::is_same<typename BucketLane<F>::type, typename TailLane<F>::type>::value && buckets >= ((size_t)1 << 21))
+        return msm_batch_tail<F, BucketLane<F>>(ctx, count, bases, offsets, ns, d_scalars, d_outs);
+    return msm_batch_tail<F, TailLane<F>>(ctx, count, bases, offsets, ns, d_scalars, d_outs);
 }
 
 // ---- the per-(curve, group) operation table ----------------------------------------------------------------------
-template <class F>
-int op_run(zkhip_ctx *ctx, const zkhip_bases *bases, size_t offset, size_t n, const uint32_t *d_scalars, uint32_t *d_out_jac) {
-    return msm_run_t<F>(ctx, bases, offset, n, d_scalars, d_out_jac);
-}
 template <class F>
 int op_to_mont(zkhip_ctx *ctx, zkhip_bases *b, const uint32_t *d_canonical, const uint8_t *d_inf) {
     ZK_LAUNCH(ctx, "bases_to_mont", bases_to_mont<F>, dim3((unsigned)((b->n + 255) / 256)), dim3(256), 0, d_canonical, d_inf, (uint32_t)b->n, b->d);
@@ -1441,18 +1465,26 @@ int op_from_mont(zkhip_ctx *ctx, const zkhip_bases *b, size_t offset, size_t n, 
     return 0;
 }
 template <class F>
+struct FixedMulBuffers {  // the table, and five field elements per table entry (while it is built) or per point (afterwards)
+    size_t n;
+    uint32_t *tab, *tmp;
+    template <class Arena>
+    void layout(Arena &a) {
+        a.take(tab, (size_t)FIXED_NW * FIXED_ROW * 2 * FieldOps<F>::WORDS);
+        a.take(tmp, std::max<size_t>((size_t)FIXED_NW * FIXED_ROW, n) * 5 * FieldOps<F>::WORDS);
+    }
+};
+template <class F>
 int op_mul(zkhip_ctx *ctx, zkhip_bases *b, const uint32_t *d_base_canonical, const uint32_t *d_scalars) {
-    constexpr int NL = FieldOps<F>::WORDS;
     if (b->n < 4096) {  // a handful of points: the table would cost more than it saves
         ZK_LAUNCH(ctx, "bases_mul", bases_mul<F>, dim3((unsigned)((b->n + 63) / 64)), dim3(64), 0, b->d, d_base_canonical, d_scalars, (uint32_t)b->n);
         return 0;
     }
     // fixed-base windows: a 32 x 256-entry affine table of the base, then <= 32 mixed additions per point (round 4: a 2^20-constraint
     // key's batch exponentiations were 256 doublings + ~128 additions + one Fermat inversion PER POINT)
-    const size_t tab_words = (size_t)FIXED_NW * FIXED_ROW * 2 * NL, tmp_words = std::max<size_t>((size_t)FIXED_NW * FIXED_ROW, b->n) * 5 * NL;
-    ZK_TRY(ctx->ws_reserve(zkhip_ctx::ws_round(tab_words * 4) + zkhip_ctx::ws_round(tmp_words * 4)));
-    ctx->ws_reset();
-    uint32_t *tab = ctx->ws_take<uint32_t>(tab_words), *tmp = ctx->ws_take<uint32_t>(tmp_words);
+    FixedMulBuffers<F> w = {b->n, nullptr, nullptr};
+    ZK_TRY(ws_place(ctx, w));
+    uint32_t *tab = w.tab, *tmp = w.tmp;
     ZK_LAUNCH(ctx, "bases_mul", bases_fixed_table<F>, dim3(1), dim3(64), 0, d_base_canonical, tab, tmp);
     const size_t lanes = (b->n + FIXED_CHUNK - 1) / FIXED_CHUNK;
     ZK_LAUNCH(ctx, "bases_mul", bases_mul_fixed<F>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, b->d, tab, d_scalars, (uint32_t)b->n, tmp);
@@ -1476,7 +1508,7 @@ int op_write_infinity(zkhip_ctx *ctx, uint32_t *d_out_jac) {
 
 template <class F>
 const MsmOps *msm_make_ops() {
-    static const MsmOps ops = {op_run<F>,        msm_batch_t<F>,      bases_precompute_t<F>, op_to_mont<F>,        op_from_mont<F>, op_mul<F>,
+    static const MsmOps ops = {msm_run_t<F>,        msm_batch_t<F>,      bases_precompute_t<F>, op_to_mont<F>,        op_from_mont<F>, op_mul<F>,
                                op_jac_to_affine<F>, op_jac_sum<F>, op_write_infinity<F>, (size_t)2 * FieldOps<F>::WORDS};
     return &ops;
 }

@@ -163,12 +163,21 @@ def test_msm_over_device_generated_bases(ctx, curve, group, n):
     b.free()
 
 
-@pytest.mark.parametrize("curve,group,n", [(0, 1, 500), (1, 2, 60)])
+@pytest.mark.parametrize("curve,group,n", [(0, 1, 500), (1, 2, 60), (0, 1, 4101), (1, 2, 4101)])
 def test_bases_from_scalars(ctx, curve, group, n):
-    """device-side fixed-base batch exponentiation (generator.hpp:187-214) against the oracle"""
+    """device-side fixed-base batch exponentiation (generator.hpp:187-214) against the oracle.
+    n = 4101 is past the 4096-point switch to the fixed-base table and no multiple of the 8 points that share one
+    inversion there; zero scalars (points at infinity, left out of the shared inversion) sit first, last and in the
+    middle of a chunk, fill a whole chunk, and fall into the short last chunk."""
     ks = cp.random_fr(curve, 42, n)
     ks[0] = 0
     ks[1] = [1, 0, 0, 0]
+    if n > 4096:
+        ks[80] = 0       # first of chunk 10
+        ks[167] = 0      # last of chunk 20
+        ks[243] = 0      # middle of chunk 30
+        ks[320:328] = 0  # all of chunk 40
+        ks[4098] = 0     # in the short chunk 4096 .. 4100
     exp, einf = cp.batch_mul(curve, group, ks)
     b = ctx.bases_from_scalars(curve, group, ks)
     got, ginf = b.download()
