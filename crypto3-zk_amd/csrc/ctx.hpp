@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include "../../include/zkhip.h"
+#include "table_cache.hpp"
 
 #define ZK_HIP_CHECK(ctx, expr)                                                                  \
     do {                                                                                         \
@@ -64,8 +66,54 @@ struct ZkProfile {
     std::map<std::string, std::pair<double, uint64_t>> acc;
 };
 
-struct NttTables;  // ntt.hip
-struct DomTables;  // domain.hip
+// an owned device allocation, freed when it goes out of scope: a table set below frees itself, and a build that returns early leaks nothing
+struct DevBuf {
+    uint32_t *p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { (void)hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc((void **)&p, bytes); }
+    operator uint32_t *() const { return p; }
+};
+
+// The device tables a context keeps across calls (the caches at the end of zkhip_ctx; protocol: table_cache.hpp)
+static constexpr int NTT_MAX_PASSES = 32;  // log_m <= 32 at radix 2
+struct NttTables {  // one radix-2 transform (ntt.hip: ntt_get_tables)
+    int curve;
+    size_t log_m;
+    int inverse;
+    bool has_coset;
+    int smax, tile_log;  // the radix plan the per-pass tables were built for
+    uint64_t omega[4], coset[4];
+    int lo_bits;
+    DevBuf d_tw[NTT_MAX_PASSES];     // store factors of pass i (i < passes - 1): m x 8 u32, Montgomery, saturated limbs
+    DevBuf d_stage[NTT_MAX_PASSES];  // omega_R^q, q < R/2, Fu form (SL words)
+    DevBuf d_prepost;                // coset: g^i (forward) or (1/m) g^-i (inverse), m x 8 u32
+    DevBuf d_lo, d_hi;               // omega^i, omega^(i << lo_bits)          (Montgomery, SL words each)
+    DevBuf d_clo, d_chi;             // g^i, g^(i << lo_bits), g = coset or coset^-1
+    DevBuf d_scale;                  // [0] = 1/m (inverse) or 1 (forward), Montgomery
+    DevBuf d_base;                   // [omega_eff, g_eff] (Montgomery)
+};
+struct NttExtTables {  // the coset factors of an n -> K n extension (ntt.hip: ntt_extend_t)
+    int curve;
+    size_t log_m, log_k;
+    uint64_t omega_big[4];
+    DevBuf d_pre;
+};
+struct DomTables {  // a step / extended radix-2 domain, or the 1 / Z entry of a basic domain's coset (domain.hip)
+    int curve, kind;
+    size_t m, n0, n1;
+    uint64_t omega[4], shift[4], coset[4];
+    bool has_coset;
+    DevBuf d_T;       // step: (omega g)^i, i < big        (Montgomery, 8 words each)
+    DevBuf d_Tinv;    // step: (omega g)^-i, i < small
+    DevBuf d_consts;  // DC_* entries, Montgomery, 8 words each
+    DevBuf d_zinv;    // has_coset: 1 / Z(g x_i) for part 0 by i mod nz, then one entry for part 1
+    size_t nz = 1;
+    uint64_t w0[4], w1[4];  // roots of the two sub-transforms
+    uint64_t coset1[4];     // extended: g shift (the coset of the second sub-transform)
+};
 
 // a captured launch sequence (HIP graph) of one MSM / MSM batch, replayed when the same call comes again
 struct ZkGraph {
@@ -129,8 +177,11 @@ struct zkhip_ctx {
     int opt_stream_priority = 0;      // < 0: the own stream was recreated with the highest priority, > 0: the lowest
     int opt_msm_precompute_min = 32;  // without tables the windows are combined by a serial Horner pass (~255 doublings on one lane: 3.8 ms)
     ZkProfile prof;
-    std::vector<NttTables *> ntt_tables;
-    std::vector<DomTables *> dom_tables;  // step / extended radix-2 domains (domain.hip)
+    // the per-index tables are m x 32 B each: the caches hold a few entries per size (a prover alternates between a handful of
+    // (direction, coset) variants of one or two sizes), oldest out first
+    TableCache<NttTables> ntt_tables{24};
+    TableCache<NttExtTables> ntt_ext_tables{16};
+    TableCache<DomTables> dom_tables{8};  // step / extended radix-2 domains and the basic domains' 1 / Z entries
     char *dom_ws = nullptr;               // scratch of zkhip_domain_fft_dev (the NTTs inside it use `ws`)
     size_t dom_ws_cap = 0;
 
@@ -161,14 +212,12 @@ struct zkhip_ctx {
         return 0;
     }
     void ws_reset() { ws_off = ws_floor; }
-    template <class T>
-    T *ws_take(size_t count) {
-        size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
-        T *p = reinterpret_cast<T *>(ws + ws_off);
-        ws_off += bytes;
-        return p;
-    }
     static size_t ws_round(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+    // the `drain` of the table caches' publish(): nothing enqueued may still read the entry that is about to go
+    int stream_drain() {
+        ZK_HIP_CHECK(this, hipStreamSynchronize(stream));
+        return 0;
+    }
 
     // ---- profiler
     void prof_begin(const char *name) {
@@ -217,7 +266,17 @@ struct WsCount {
 struct WsBump {
     zkhip_ctx *ctx;
     template <class T>
-    void take(T *&p, size_t count) { p = ctx->ws_take<T>(count); }
+    void take(T *&p, size_t count) {
+        p = reinterpret_cast<T *>(ctx->ws + ctx->ws_off);
+        ctx->ws_off += zkhip_ctx::ws_round(count * sizeof(T));
+    }
+};
+template <class T>
+struct WsOne {  // the layout of a call with a single buffer
+    size_t count;
+    T *p;
+    template <class Arena>
+    void layout(Arena &a) { a.take(p, count); }
 };
 template <class Layout>
 size_t ws_bytes(Layout &l) {

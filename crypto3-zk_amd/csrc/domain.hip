@@ -28,19 +28,6 @@
 
 using namespace zkhip;
 
-struct DomTables {
-    int curve, kind;
-    size_t m, n0, n1;
-    uint64_t omega[4], shift[4], coset[4];
-    bool has_coset;
-    uint32_t *d_T = nullptr;      // step: (omega g)^i, i < big        (Montgomery, 8 words each)
-    uint32_t *d_Tinv = nullptr;   // step: (omega g)^-i, i < small
-    uint32_t *d_consts = nullptr; // DC_* entries, Montgomery, 8 words each
-    uint32_t *d_zinv = nullptr;   // has_coset: 1 / Z(g x_i) for part 0 by i mod nz, then one entry for part 1
-    size_t nz = 1;
-    uint64_t w0[4], w1[4];        // roots of the two sub-transforms
-    uint64_t coset1[4];           // extended: g shift (the coset of the second sub-transform)
-};
 enum { DC_BASE = 0, DC_BASEINV, DC_G, DC_HALF, DC_HALF_GINV, DC_S, DC_GS, DC_K, DC_K_GINV, DC_Z_STEP, DC_Z_A, DC_Z_B, DC_Z1, DC_COUNT };
 
 // ---- host-side field helpers (the same __host__ __device__ arithmetic the kernels use) --------------------------------
@@ -216,13 +203,6 @@ __global__ __launch_bounds__(64) void dom_zinv_table(int kind, const uint32_t *_
 }
 
 void zk_dom_free_tables(zkhip_ctx *ctx) {
-    for (DomTables *t : ctx->dom_tables) {
-        (void)hipFree(t->d_T);
-        (void)hipFree(t->d_Tinv);
-        (void)hipFree(t->d_consts);
-        (void)hipFree(t->d_zinv);
-        delete t;
-    }
     ctx->dom_tables.clear();
     (void)hipFree(ctx->dom_ws);
     ctx->dom_ws = nullptr;
@@ -231,12 +211,11 @@ void zk_dom_free_tables(zkhip_ctx *ctx) {
 
 template <class U>
 static int dom_get_tables(zkhip_ctx *ctx, int curve, const ZkDomain &d, const uint64_t *coset, DomTables **out) {
-    for (DomTables *t : ctx->dom_tables)
-        if (t->curve == curve && t->kind == d.kind && t->m == d.m && t->has_coset == (coset != nullptr) && memcmp(t->omega, d.omega, 32) == 0 &&
-            (d.kind != ZKHIP_DOMAIN_EXTENDED_RADIX2 || memcmp(t->shift, d.shift, 32) == 0) && (!coset || memcmp(t->coset, coset, 32) == 0)) {
-            *out = t;
-            return 0;
-        }
+    *out = ctx->dom_tables.find([&](const DomTables &t) {
+        return t.curve == curve && t.kind == d.kind && t.m == d.m && t.has_coset == (coset != nullptr) && memcmp(t.omega, d.omega, 32) == 0 &&
+               (d.kind != ZKHIP_DOMAIN_EXTENDED_RADIX2 || memcmp(t.shift, d.shift, 32) == 0) && (!coset || memcmp(t.coset, coset, 32) == 0);
+    });
+    if (*out) return 0;
     // the roots must be what the domain says they are: anything else transforms over another point set
     uint64_t t1[4], t2[4];
     if (d.kind == ZKHIP_DOMAIN_STEP_RADIX2) {
@@ -253,34 +232,10 @@ static int dom_get_tables(zkhip_ctx *ctx, int curve, const ZkDomain &d, const ui
             return ZKHIP_ERR_INVALID;
         }
     }
-    if (ctx->dom_tables.size() >= 8) {
-        ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        DomTables *old = ctx->dom_tables.front();
-        (void)hipFree(old->d_T);
-        (void)hipFree(old->d_Tinv);
-        (void)hipFree(old->d_consts);
-        (void)hipFree(old->d_zinv);
-        delete old;
-        ctx->dom_tables.erase(ctx->dom_tables.begin());
-    }
     // Built in a local owner and PUBLISHED only after the last launch has completed: an allocation, copy or launch that fails on
-    // the way (out of memory on d_T, say) must not leave a half-built entry in the cache for the next call to hit (ADVICE r3).
-    struct Building {
-        DomTables *t = new DomTables();
-        uint32_t *d_in = nullptr;
-        ~Building() {
-            (void)hipFree(d_in);
-            if (t) {
-                (void)hipFree(t->d_T);
-                (void)hipFree(t->d_Tinv);
-                (void)hipFree(t->d_consts);
-                (void)hipFree(t->d_zinv);
-                delete t;
-            }
-        }
-    } building;
-    DomTables *t = building.t;
-    uint32_t *&d_in = building.d_in;
+    // the way (out of memory on d_T, say) must not leave a half-built entry in the cache for the next call to hit.
+    auto t = std::make_unique<DomTables>();
+    DevBuf d_in;
     t->curve = curve;
     t->kind = d.kind;
     t->m = d.m;
@@ -291,8 +246,8 @@ static int dom_get_tables(zkhip_ctx *ctx, int curve, const ZkDomain &d, const ui
     t->has_coset = coset != nullptr;
     if (coset) memcpy(t->coset, coset, 32);
     const uint64_t one[4] = {1, 0, 0, 0};
-    ZK_HIP_CHECK(ctx, hipMalloc((void **)&d_in, 96));
-    ZK_HIP_CHECK(ctx, hipMalloc((void **)&t->d_consts, DC_COUNT * 32));
+    ZK_HIP_CHECK(ctx, d_in.alloc(96));
+    ZK_HIP_CHECK(ctx, t->d_consts.alloc(DC_COUNT * 32));
     ZK_HIP_CHECK(ctx, hipMemsetAsync(t->d_consts, 0, DC_COUNT * 32, ctx->stream));
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_in, d.omega, 32, hipMemcpyHostToDevice, ctx->stream));
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_in + 8, d.kind == ZKHIP_DOMAIN_EXTENDED_RADIX2 ? d.shift : one, 32, hipMemcpyHostToDevice, ctx->stream));
@@ -302,8 +257,8 @@ static int dom_get_tables(zkhip_ctx *ctx, int curve, const ZkDomain &d, const ui
         const size_t compr = d.n0 / d.n1;
         h_mul<U>(d.omega, d.omega, t->w0);
         h_pow<U>(d.omega, 2 * compr, t->w1);
-        ZK_HIP_CHECK(ctx, hipMalloc((void **)&t->d_T, d.n0 * 32));
-        ZK_HIP_CHECK(ctx, hipMalloc((void **)&t->d_Tinv, d.n1 * 32));
+        ZK_HIP_CHECK(ctx, t->d_T.alloc(d.n0 * 32));
+        ZK_HIP_CHECK(ctx, t->d_Tinv.alloc(d.n1 * 32));
         ZK_LAUNCH(ctx, "dom_setup", dom_pow_table<U>, dim3((unsigned)((d.n0 + 255) / 256)), dim3(256), 0, t->d_consts, (int)DC_BASE, (uint64_t)d.n0, t->d_T);
         ZK_LAUNCH(ctx, "dom_setup", dom_pow_table<U>, dim3((unsigned)((d.n1 + 255) / 256)), dim3(256), 0, t->d_consts, (int)DC_BASEINV, (uint64_t)d.n1, t->d_Tinv);
         t->nz = compr;
@@ -315,14 +270,12 @@ static int dom_get_tables(zkhip_ctx *ctx, int curve, const ZkDomain &d, const ui
         t->nz = 1;
     }
     if (coset) {
-        ZK_HIP_CHECK(ctx, hipMalloc((void **)&t->d_zinv, (t->nz + 1) * 32));
+        ZK_HIP_CHECK(ctx, t->d_zinv.alloc((t->nz + 1) * 32));
         ZK_LAUNCH(ctx, "dom_setup", dom_zinv_table<U>, dim3((unsigned)((t->nz + 1 + 63) / 64)), dim3(64), 0, d.kind, t->d_consts, (uint64_t)t->nz, t->d_zinv);
     }
     ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->dom_tables.push_back(t);
-    building.t = nullptr;  // the cache owns it now; d_in goes with `building`
-    *out = t;
-    return 0;
+    *out = t.get();
+    return ctx->dom_tables.publish(std::move(t), [&] { return ctx->stream_drain(); });
 }
 
 // ---- step domain: column sums ------------------------------------------------------------------------------------------
@@ -574,13 +527,16 @@ static int dom_zinv_t(zkhip_ctx *ctx, int curve, const ZkDomain &d, const uint64
         return 0;
     }
     // basic: Z(g x) = g^m - 1 everywhere; cached as a table set of its own (kind basic, with coset)
-    for (DomTables *t : ctx->dom_tables)
-        if (t->curve == curve && t->kind == d.kind && t->m == d.m && t->has_coset && memcmp(t->coset, coset, 32) == 0) {
-            *d_zinv = t->d_zinv;
-            *nz = 1;
-            return 0;
-        }
-    DomTables *t = new DomTables();
+    DomTables *hit = ctx->dom_tables.find([&](const DomTables &t) {
+        return t.curve == curve && t.kind == d.kind && t.m == d.m && t.has_coset && memcmp(t.coset, coset, 32) == 0;
+    });
+    *nz = 1;
+    if (hit) {
+        *d_zinv = hit->d_zinv;
+        return 0;
+    }
+    auto t = std::make_unique<DomTables>();
+    DevBuf d_in;
     t->curve = curve;
     t->kind = d.kind;
     t->m = d.m;
@@ -589,17 +545,13 @@ static int dom_zinv_t(zkhip_ctx *ctx, int curve, const ZkDomain &d, const uint64
     memcpy(t->omega, d.omega, 32);
     t->has_coset = true;
     memcpy(t->coset, coset, 32);
-    ctx->dom_tables.push_back(t);
-    uint32_t *d_in = nullptr;
-    ZK_HIP_CHECK(ctx, hipMalloc((void **)&d_in, 32));
-    ZK_HIP_CHECK(ctx, hipMalloc((void **)&t->d_zinv, 64));
+    ZK_HIP_CHECK(ctx, d_in.alloc(32));
+    ZK_HIP_CHECK(ctx, t->d_zinv.alloc(64));
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_in, coset, 32, hipMemcpyHostToDevice, ctx->stream));
     ZK_LAUNCH(ctx, "dom_setup", dom_zinv_basic<U>, dim3(1), dim3(64), 0, d_in, (uint64_t)d.m, t->d_zinv);
     ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(d_in);
     *d_zinv = t->d_zinv;
-    *nz = 1;
-    return 0;
+    return ctx->dom_tables.publish(std::move(t), [&] { return ctx->stream_drain(); });
 }
 int zk_dom_zinv(zkhip_ctx *ctx, int curve, const ZkDomain &d, const uint64_t *coset, const uint32_t **d_zinv, size_t *nz) {
     if (!coset) return ZKHIP_ERR_INVALID;
@@ -696,16 +648,25 @@ static int lagrange_launch(zkhip_ctx *ctx, uint32_t *d_consts, uint32_t *h_const
     return ZKHIP_OK;
 }
 
+struct LagrangeBuffers {
+    size_t compr;  // step domain: big / small, the distinct denominators x^small - omega^small; else 0
+    uint32_t *consts, *dinv;
+    template <class Arena>
+    void layout(Arena &a) {
+        a.take(consts, 4 * 32);  // four launches' constants
+        if (compr) a.take(dinv, compr * 8);
+    }
+};
 template <class U>
 static int dom_lagrange_t(zkhip_ctx *ctx, const ZkDomain &d, const uint64_t *t_c, uint32_t *d_out) {
     typedef HF<U> F;
     const F one = F::one(), t = F::from(t_c), w = F::from(d.omega);
     // constants of up to four launches, staged in page-able host memory that must outlive the copies: kept in the context
     ctx->lagrange_stage.assign(4 * 32, 0u);
-    uint32_t *h = ctx->lagrange_stage.data(), *dc = nullptr;
-    ZK_TRY(ctx->ws_reserve(zkhip_ctx::ws_round(4 * 128) + zkhip_ctx::ws_round((d.n1 ? d.n0 / d.n1 : 1) * 32)));
-    ctx->ws_reset();
-    dc = ctx->ws_take<uint32_t>(4 * 32);
+    uint32_t *h = ctx->lagrange_stage.data();
+    LagrangeBuffers wsb = {d.kind == ZKHIP_DOMAIN_STEP_RADIX2 ? d.n0 / d.n1 : 0};
+    ZK_TRY(ws_place(ctx, wsb));
+    uint32_t *const dc = wsb.consts, *const d_dinv = wsb.dinv;
     auto basic = [&](int slot, const F &root, const F &at, const F &scale, size_t n, size_t off) {
         // scale * l_i(at) over <root>: l_i = (at^n - 1) root^i / (n (at - root^i))
         const F c = (at.pow(n) - one) * F::u64(n).inv() * scale;
@@ -727,7 +688,6 @@ static int dom_lagrange_t(zkhip_ctx *ctx, const ZkDomain &d, const uint64_t *t_c
         const size_t big = d.n0, small = d.n1, compr = big / small;
         const F big_w = w * w, small_w = w.pow(2 * compr), w_sm = w.pow(small), L0 = t.pow(small) - w_sm;
         if ((t.pow(big) - one).is_zero() || L0.is_zero()) return ZKHIP_ERR_INVALID;
-        uint32_t *d_dinv = ctx->ws_take<uint32_t>(compr * 8);
         rc = lagrange_launch<U>(ctx, dc, h, 0, big_w.pow(small), w_sm, one, compr, 1, d_dinv, 0);  // 1 / (step^j - omega^small)
         if (rc == ZKHIP_OK) rc = basic(1, big_w, t, L0, big, 0);
         if (rc == ZKHIP_OK)

@@ -296,6 +296,18 @@ __global__ __launch_bounds__(64) void ec_ntt_store(const uint32_t *__restrict__ 
     O::to_canonical(o + 2 * CW, j.Z);
 }
 
+struct EcNttBuffers {  // sizes in u32 words
+    size_t pts_words, rec_words, tbl_words;
+    uint32_t *pts, *rec, *rec_last, *consts, *tbl;
+    template <class Arena>
+    void layout(Arena &a) {
+        a.take(pts, pts_words);
+        a.take(rec, rec_words);
+        a.take(rec_last, rec_words);
+        a.take(consts, 128);
+        a.take(tbl, tbl_words);
+    }
+};
 template <class F, class U, class G>
 int ec_ntt_t(zkhip_ctx *ctx, uint32_t *d_jac, size_t log_m, const uint64_t *omega, int inverse) {
     constexpr int NL = FieldOps<F>::WORDS, PW = 4 * NL, HALVES = G::ENABLED ? 2 : 1;
@@ -304,15 +316,9 @@ int ec_ntt_t(zkhip_ctx *ctx, uint32_t *d_jac, size_t log_m, const uint64_t *omeg
     const size_t slot_bytes = (size_t)8 * HALVES * PW * 4;
     const size_t slot_cap = ctx->opt_ec_ntt_table_lanes ? ((size_t)ctx->opt_ec_ntt_table_lanes + 63) / 64 * 64 : ((size_t)1 << 30) / slot_bytes / 64 * 64;
     const uint32_t slots = (uint32_t)std::max<size_t>(64, std::min<size_t>(((size_t)m + 63) / 64 * 64, slot_cap));
-    const size_t need = zkhip_ctx::ws_round((size_t)m * PW * 4) + 2 * zkhip_ctx::ws_round((size_t)ntw * REC_WORDS * 4) + zkhip_ctx::ws_round(512) +
-                        zkhip_ctx::ws_round((size_t)slots * slot_bytes);
-    ZK_TRY(ctx->ws_reserve(need));
-    ctx->ws_reset();
-    uint32_t *pts = ctx->ws_take<uint32_t>((size_t)m * PW);
-    uint32_t *rec = ctx->ws_take<uint32_t>((size_t)ntw * REC_WORDS);
-    uint32_t *rec_last = ctx->ws_take<uint32_t>((size_t)ntw * REC_WORDS);
-    uint32_t *consts = ctx->ws_take<uint32_t>(128);
-    uint32_t *tbl = ctx->ws_take<uint32_t>((size_t)slots * slot_bytes / 4);
+    EcNttBuffers w = {(size_t)m * PW, (size_t)ntw * REC_WORDS, (size_t)slots * slot_bytes / 4};
+    ZK_TRY(ws_place(ctx, w));
+    uint32_t *pts = w.pts, *rec = w.rec, *rec_last = w.rec_last, *consts = w.consts, *tbl = w.tbl;
     uint32_t *d_w = consts + 32, *d_one = consts + 48, *rec_minv = consts + 64;
     uint32_t one[8] = {1, 0, 0, 0, 0, 0, 0, 0};
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_w, omega, 32, hipMemcpyHostToDevice, ctx->stream));

@@ -99,6 +99,15 @@ __global__ __launch_bounds__(256) void gate_eval(const uint32_t *const *__restri
         __VA_ARGS__;                    \
     }
 
+struct GateBuffers {  // the program's image as uploaded; its coefficients in Montgomery form (16-word slots)
+    size_t img_words, terms;
+    uint32_t *img, *mont;
+    template <class Arena>
+    void layout(Arena &a) {
+        a.take(img, img_words);
+        a.take(mont, terms * 16);
+    }
+};
 extern "C" int zkhip_gate_eval_dev(zkhip_ctx *ctx, int curve, const zkhip_gate_program *prog, const void *const *d_slots, size_t log_size, const void *d_mask,
                                    int accumulate, void *d_out) {
     if (!ctx || !prog || !d_out) return ZKHIP_ERR_INVALID;
@@ -148,11 +157,10 @@ extern "C" int zkhip_gate_eval_dev(zkhip_ctx *ctx, int curve, const zkhip_gate_p
     for (uint32_t f = 0; f < F; ++f) h_fac[2 * f] = prog->factor_slot[f], h_fac[2 * f + 1] = (uint32_t)prog->factor_rot[f];
     if (T) memcpy(h_coeff, prog->term_coeff, (size_t)T * 32);
 
-    const size_t img_bytes = img.size() * 4, mont_bytes = std::max<size_t>(1, T) * 16 * 4;
-    ZK_TRY(ctx->ws_reserve(zkhip_ctx::ws_round(img_bytes) + zkhip_ctx::ws_round(mont_bytes)));
-    ctx->ws_reset();
-    uint32_t *d_img = ctx->ws_take<uint32_t>(img.size());
-    uint32_t *d_mont = ctx->ws_take<uint32_t>(std::max<size_t>(1, T) * 16);
+    const size_t img_bytes = img.size() * 4;
+    GateBuffers w = {img.size(), std::max<size_t>(1, T)};
+    ZK_TRY(ws_place(ctx, w));
+    uint32_t *d_img = w.img, *d_mont = w.mont;
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_img, img.data(), img_bytes, hipMemcpyHostToDevice, ctx->stream));
     ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // pageable source: the staging vector may be refilled by the next call
     const uint32_t *dd_coeff = d_img;

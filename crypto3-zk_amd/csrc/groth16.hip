@@ -232,9 +232,9 @@ static int witness_h_t(zkhip_ctx *ctx, const zkhip_r1cs *r, const uint32_t *d_z,
         if (r->n_long[k]) {
             // slices of ~4096 terms, at most 64 per row; per-slice partial sums live in the context workspace
             uint32_t nslice = (uint32_t)std::max<size_t>(1, std::min<size_t>(64, r->long_terms[k] / ((size_t)r->n_long[k] * 4096)));
-            ZK_TRY(ctx->ws_reserve((size_t)r->n_long[k] * nslice * U::SL * 4 + 256));
-            ctx->ws_reset();
-            uint32_t *partial = ctx->ws_take<uint32_t>((size_t)r->n_long[k] * nslice * U::SL);
+            WsOne<uint32_t> w = {(size_t)r->n_long[k] * nslice * U::SL};
+            ZK_TRY(ws_place(ctx, w));
+            uint32_t *partial = w.p;
             ZK_LAUNCH(ctx, "r1cs_eval_long", r1cs_eval_long<U>, dim3(r->n_long[k], nslice), dim3(256), 0, r->long_rows[k], r->rowptr[k], r->col[k],
                       r->coeff[k], d_z, partial);
             ZK_LAUNCH(ctx, "r1cs_eval_long", r1cs_long_combine<U>, dim3((r->n_long[k] + 63) / 64), dim3(64), 0, r->long_rows[k], r->n_long[k], nslice,

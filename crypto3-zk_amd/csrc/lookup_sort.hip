@@ -265,6 +265,28 @@ __global__ __launch_bounds__(LS_THREADS) void ls_emit(const uint32_t *const *__r
 
 }  // namespace
 
+struct LookupSortBuffers {
+    size_t kk, lv, vt, table;
+    const uint32_t **ptrs;  // inputs | values | outputs
+    uint32_t *run, *st, *canon, *cnt;
+    uint8_t *start;
+    uint32_t *off, *tile_a, *tile_b, *slots;
+    uint32_t *scal;  // [0] runs, [1] emitted entries
+    template <class Arena>
+    void layout(Arena &a) {
+        a.take(ptrs, 2 * kk);
+        a.take(run, lv);
+        a.take(st, lv);
+        a.take(canon, lv);
+        a.take(cnt, lv);
+        a.take(start, lv + 4);
+        a.take(off, lv + 1);
+        a.take(tile_a, vt + 1);
+        a.take(tile_b, vt + 1);
+        a.take(slots, table);
+        a.take(scal, 16);
+    }
+};
 extern "C" int zkhip_lookup_sort_dev(zkhip_ctx *ctx, size_t k_in, const void *const *d_input, size_t k_val, const void *const *d_value, size_t n, size_t usable_rows,
                                      void *const *d_sorted) {
     if (!ctx || (k_in && !d_input) || (k_val && !d_value) || !d_sorted) return ZKHIP_ERR_INVALID;
@@ -286,17 +308,12 @@ extern "C" int zkhip_lookup_sort_dev(zkhip_ctx *ctx, size_t k_in, const void *co
     const uint32_t vt = (lv + LS_TILE - 1) / LS_TILE;  // tiles over the values = upper bound of the tiles over the runs
     uint32_t table = 1024;
     while (table < 2 * (size_t)lv) table <<= 1;  // load factor <= 1/2 whatever the number of runs
-    size_t need = zkhip_ctx::ws_round(2 * kk * sizeof(void *)) + zkhip_ctx::ws_round((size_t)lv * 4) * 4 + zkhip_ctx::ws_round((size_t)lv + 4) +
-                  zkhip_ctx::ws_round(((size_t)lv + 1) * 4) + zkhip_ctx::ws_round(((size_t)vt + 1) * 4) * 2 + zkhip_ctx::ws_round((size_t)table * 4) + zkhip_ctx::ws_round(64);
-    ZK_TRY(ctx->ws_reserve(need));
-    ctx->ws_reset();
-    const uint32_t **d_ptrs = ctx->ws_take<const uint32_t *>(2 * kk);  // inputs | values | outputs
-    uint32_t *d_run = ctx->ws_take<uint32_t>(lv), *d_st = ctx->ws_take<uint32_t>(lv), *d_canon = ctx->ws_take<uint32_t>(lv), *d_cnt = ctx->ws_take<uint32_t>(lv);
-    uint8_t *d_start = ctx->ws_take<uint8_t>((size_t)lv + 4);
-    uint32_t *d_off = ctx->ws_take<uint32_t>((size_t)lv + 1);
-    uint32_t *d_tile_a = ctx->ws_take<uint32_t>((size_t)vt + 1), *d_tile_b = ctx->ws_take<uint32_t>((size_t)vt + 1);
-    uint32_t *d_slots = ctx->ws_take<uint32_t>(table);
-    uint32_t *d_scal = ctx->ws_take<uint32_t>(16);  // [0] runs, [1] emitted entries
+    LookupSortBuffers w = {kk, lv, vt, table};
+    ZK_TRY(ws_place(ctx, w));
+    const uint32_t **d_ptrs = w.ptrs;
+    uint32_t *d_run = w.run, *d_st = w.st, *d_canon = w.canon, *d_cnt = w.cnt, *d_off = w.off, *d_tile_a = w.tile_a, *d_tile_b = w.tile_b, *d_slots = w.slots,
+             *d_scal = w.scal;
+    uint8_t *d_start = w.start;
     ctx->batch_ptrs.clear();
     for (size_t i = 0; i < k_in; ++i) ctx->batch_ptrs.push_back((uint32_t *)d_input[i]);
     for (size_t i = 0; i < k_val; ++i) ctx->batch_ptrs.push_back((uint32_t *)d_value[i]);

@@ -125,6 +125,17 @@ static int merkle_hash_fri_leaves(zkhip_ctx *ctx, zkhip_merkle *t, const void *d
     return merkle_levels(ctx, t);
 }
 
+struct PathBuffers {  // zkhip_merkle_paths: the leaf indices and the gathered digests (two uint4 each)
+    size_t count, nodes;
+    uint64_t *idx;
+    uint4 *out;
+    template <class Arena>
+    void layout(Arena &a) {
+        a.take(idx, count);
+        a.take(out, nodes * 2);
+    }
+};
+
 extern "C" {
 
 int zkhip_merkle_build_dev(zkhip_ctx *ctx, int hash, const void *d_leaves, size_t n_leaves, size_t elements_per_leaf, zkhip_merkle **out) {
@@ -173,10 +184,10 @@ int zkhip_merkle_paths(zkhip_ctx *ctx, const zkhip_merkle *t, const uint64_t *le
     if (count == 0 || t->depth == 0) return ZKHIP_OK;
     ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t nodes = count * t->depth;
-    ZK_TRY(ctx->ws_reserve(zkhip_ctx::ws_round(count * 8) + zkhip_ctx::ws_round(nodes * 32)));
-    ctx->ws_reset();
-    uint64_t *d_idx = ctx->ws_take<uint64_t>(count);
-    uint4 *d_out = ctx->ws_take<uint4>(nodes * 2);
+    PathBuffers w = {count, nodes};
+    ZK_TRY(ws_place(ctx, w));
+    uint64_t *d_idx = w.idx;
+    uint4 *d_out = w.out;
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_idx, leaf_indices, count * 8, hipMemcpyHostToDevice, ctx->stream));
     ZK_LAUNCH(ctx, "merkle_path_gather", merkle_path_gather, dim3((unsigned)((nodes * 2 + 255) / 256)), dim3(256), 0, (const uint4 *)t->d, t->leaves,
               (uint32_t)t->depth, d_idx, nodes * 2, d_out);

@@ -39,25 +39,7 @@
 
 using namespace zkhip;
 
-static constexpr int NTT_MAX_PASSES = 32;  // log_m <= 32 at radix 2
 static constexpr uint32_t NTT_PAD = 0;  // extra elements per LDS row (see lds_get)
-
-struct NttTables {
-    int curve;
-    size_t log_m;
-    int inverse;
-    bool has_coset;
-    int smax, tile_log;  // the radix plan the per-pass tables were built for
-    uint64_t omega[4], coset[4];
-    int lo_bits;
-    uint32_t *d_tw[NTT_MAX_PASSES] = {};     // store factors of pass i (i < passes - 1): m x 8 u32, Montgomery, saturated limbs
-    uint32_t *d_stage[NTT_MAX_PASSES] = {};  // omega_R^q, q < R/2, Fu form (SL words)
-    uint32_t *d_prepost = nullptr;           // coset: g^i (forward) or (1/m) g^-i (inverse), m x 8 u32
-    uint32_t *d_lo = nullptr, *d_hi = nullptr;    // omega^i, omega^(i << lo_bits)          (Montgomery, SL words each)
-    uint32_t *d_clo = nullptr, *d_chi = nullptr;  // g^i, g^(i << lo_bits), g = coset or coset^-1
-    uint32_t *d_scale = nullptr;                  // [0] = 1/m (inverse) or 1 (forward), Montgomery
-    uint32_t *d_base = nullptr;                   // [omega_eff, g_eff] (Montgomery)
-};
 
 struct NttPass {
     const uint32_t *in;
@@ -403,26 +385,9 @@ __global__ __launch_bounds__(256) void ntt_pass(NttPass p) {
 }
 
 // ---- host side ------------------------------------------------------------------------------------
-static void ntt_free_one(NttTables *t) {
-    (void)hipFree(t->d_lo);
-    (void)hipFree(t->d_hi);
-    (void)hipFree(t->d_clo);
-    (void)hipFree(t->d_chi);
-    (void)hipFree(t->d_scale);
-    (void)hipFree(t->d_base);
-    (void)hipFree(t->d_prepost);
-    for (int i = 0; i < NTT_MAX_PASSES; ++i) {
-        (void)hipFree(t->d_tw[i]);
-        (void)hipFree(t->d_stage[i]);
-    }
-    delete t;
-}
-
-void zk_ntt_free_ext_tables(zkhip_ctx *ctx);
 void zk_ntt_free_tables(zkhip_ctx *ctx) {
-    for (NttTables *t : ctx->ntt_tables) ntt_free_one(t);
     ctx->ntt_tables.clear();
-    zk_ntt_free_ext_tables(ctx);
+    ctx->ntt_ext_tables.clear();
 }
 
 // the radix plan: log_m split into np nearly equal radices (larger first), tile widths
@@ -445,23 +410,16 @@ static NttPlan ntt_plan(size_t log_m, int smax, int tile_log) {
 template <class U>
 static int ntt_get_tables(zkhip_ctx *ctx, int curve, size_t log_m, const uint64_t *omega, int inverse, const uint64_t *coset, int smax, int tile_log,
                           NttTables **out) {
-    for (NttTables *t : ctx->ntt_tables) {
-        if (t->curve == curve && t->log_m == log_m && t->inverse == inverse && t->has_coset == (coset != nullptr) && t->smax == smax &&
-            t->tile_log == tile_log && memcmp(t->omega, omega, 32) == 0 && (coset == nullptr || memcmp(t->coset, coset, 32) == 0)) {
-            *out = t;
-            return 0;
-        }
-    }
+    *out = ctx->ntt_tables.find([&](const NttTables &t) {
+        return t.curve == curve && t.log_m == log_m && t.inverse == inverse && t.has_coset == (coset != nullptr) && t.smax == smax &&
+               t.tile_log == tile_log && memcmp(t.omega, omega, 32) == 0 && (coset == nullptr || memcmp(t.coset, coset, 32) == 0);
+    });
+    if (*out) return 0;
     if ((int)((log_m + smax - 1) / smax) > NTT_MAX_PASSES) return ZKHIP_ERR_RANGE;
     const NttPlan pl = ntt_plan(log_m, smax, tile_log);
-    // the per-index tables are m x 32 B each: keep the cache within a few entries per size (a prover alternates between a
-    // handful of (direction, coset) variants of one or two sizes)
-    if (ctx->ntt_tables.size() >= 24) {
-        ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        ntt_free_one(ctx->ntt_tables.front());
-        ctx->ntt_tables.erase(ctx->ntt_tables.begin());
-    }
-    NttTables *t = new NttTables();
+    // built in a local owner and published only after the last launch has completed: any return on the way destroys it, d_in included
+    auto t = std::make_unique<NttTables>();
+    DevBuf d_in;
     t->curve = curve;
     t->log_m = log_m;
     t->inverse = inverse;
@@ -476,13 +434,11 @@ static int ntt_get_tables(zkhip_ctx *ctx, int curve, size_t log_m, const uint64_
     const uint32_t nhi = (uint32_t)(((size_t)1 << log_m) >> t->lo_bits) + 1;
     const size_t eb = U::SL * 4;  // bytes per power-table entry
     const size_t m = (size_t)1 << log_m;
-    ctx->ntt_tables.push_back(t);  // owned by the context from here on (freed in zk_ntt_free_tables)
-    uint32_t *d_in = nullptr;
-    ZK_HIP_CHECK(ctx, hipMalloc((void **)&d_in, 64));
-    ZK_HIP_CHECK(ctx, hipMalloc((void **)&t->d_base, 2 * eb));
-    ZK_HIP_CHECK(ctx, hipMalloc((void **)&t->d_scale, eb));
-    ZK_HIP_CHECK(ctx, hipMalloc((void **)&t->d_lo, (size_t)nlo * eb));
-    ZK_HIP_CHECK(ctx, hipMalloc((void **)&t->d_hi, (size_t)nhi * eb));
+    ZK_HIP_CHECK(ctx, d_in.alloc(64));
+    ZK_HIP_CHECK(ctx, t->d_base.alloc(2 * eb));
+    ZK_HIP_CHECK(ctx, t->d_scale.alloc(eb));
+    ZK_HIP_CHECK(ctx, t->d_lo.alloc((size_t)nlo * eb));
+    ZK_HIP_CHECK(ctx, t->d_hi.alloc((size_t)nhi * eb));
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_in, omega, 32, hipMemcpyHostToDevice, ctx->stream));
     if (coset) ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_in + 8, coset, 32, hipMemcpyHostToDevice, ctx->stream));
     ZK_LAUNCH(ctx, "ntt_setup", ntt_setup<U>, dim3(1), dim3(64), 0, d_in, coset ? d_in + 8 : (const uint32_t *)nullptr, inverse,
@@ -491,13 +447,13 @@ static int ntt_get_tables(zkhip_ctx *ctx, int curve, size_t log_m, const uint64_
     ZK_LAUNCH(ctx, "ntt_pow_table", ntt_pow_table<U>, dim3((nhi + 255) / 256), dim3(256), 0, t->d_base, nhi, (uint32_t)t->lo_bits, t->d_hi);
     const unsigned gm = (unsigned)((m + 255) / 256);
     if (coset) {
-        ZK_HIP_CHECK(ctx, hipMalloc((void **)&t->d_clo, (size_t)nlo * eb));
-        ZK_HIP_CHECK(ctx, hipMalloc((void **)&t->d_chi, (size_t)nhi * eb));
+        ZK_HIP_CHECK(ctx, t->d_clo.alloc((size_t)nlo * eb));
+        ZK_HIP_CHECK(ctx, t->d_chi.alloc((size_t)nhi * eb));
         ZK_LAUNCH(ctx, "ntt_pow_table", ntt_pow_table<U>, dim3((nlo + 255) / 256), dim3(256), 0, t->d_base + U::SL, nlo, 0u, t->d_clo);
         ZK_LAUNCH(ctx, "ntt_pow_table", ntt_pow_table<U>, dim3((nhi + 255) / 256), dim3(256), 0, t->d_base + U::SL, nhi, (uint32_t)t->lo_bits,
                   t->d_chi);
         // g^i while loading (forward) / (1/m) g^-i while storing (inverse): one entry per index
-        ZK_HIP_CHECK(ctx, hipMalloc((void **)&t->d_prepost, m * 36));
+        ZK_HIP_CHECK(ctx, t->d_prepost.alloc(m * 36));
         ZK_LAUNCH(ctx, "ntt_build_tw", ntt_build_powers<U>, dim3(gm), dim3(256), 0, t->d_clo, t->d_chi, (uint32_t)t->lo_bits, (uint32_t)log_m,
                   inverse ? t->d_scale : (const uint32_t *)nullptr, t->d_prepost);
     }
@@ -507,7 +463,7 @@ static int ntt_get_tables(zkhip_ctx *ctx, int curve, size_t log_m, const uint64_
     uint32_t log_ns = 0;
     for (int i = 0; i < pl.np; ++i) {
         const uint32_t s = (uint32_t)pl.sv[i], half = std::max<uint32_t>(1, (1u << s) / 2);
-        ZK_HIP_CHECK(ctx, hipMalloc((void **)&t->d_stage[i], (size_t)half * eb));
+        ZK_HIP_CHECK(ctx, t->d_stage[i].alloc((size_t)half * eb));
         ZK_LAUNCH(ctx, "ntt_build_tw", ntt_build_stage<U>, dim3((half + 255) / 256), dim3(256), 0, t->d_lo, t->d_hi, (uint32_t)t->lo_bits,
                   (uint32_t)log_m - s, half, t->d_stage[i]);
         if (i + 1 < pl.np) {
@@ -520,7 +476,7 @@ static int ntt_get_tables(zkhip_ctx *ctx, int curve, size_t log_m, const uint64_
             g.hi = t->d_hi;
             g.lo_bits = (uint32_t)t->lo_bits;
             g.scale = (inverse && !coset && i == 0) ? t->d_scale : nullptr;
-            ZK_HIP_CHECK(ctx, hipMalloc((void **)&t->d_tw[i], m * 36));
+            ZK_HIP_CHECK(ctx, t->d_tw[i].alloc(m * 36));
             ZK_LAUNCH(ctx, "ntt_build_tw", ntt_build_tw<U>, dim3(gm), dim3(256), 0, g, t->d_tw[i]);
         }
         log_ns += s;
@@ -533,20 +489,17 @@ static int ntt_get_tables(zkhip_ctx *ctx, int curve, size_t log_m, const uint64_
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(w_m, t->d_hi + (size_t)(nhi - 1) * U::SL, sizeof(w_m), hipMemcpyDeviceToHost, ctx->stream));
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(w_half, d_half, sizeof(w_half), hipMemcpyDeviceToHost, ctx->stream));
     ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(d_in);
     bool m_is_one = true, half_is_one = true;
     for (int i = 0; i < U::L; ++i) {
         m_is_one = m_is_one && w_m[i] == U::r1(i);
         half_is_one = half_is_one && w_half[i] == U::r1(i);
     }
     if (!m_is_one || half_is_one) {
-        ctx->ntt_tables.pop_back();
-        ntt_free_one(t);
         ctx->last_error = "omega is not a primitive 2^" + std::to_string(log_m) + "-th root of unity";
         return ZKHIP_ERR_INVALID;
     }
-    *out = t;
-    return 0;
+    *out = t.get();
+    return ctx->ntt_tables.publish(std::move(t), [&] { return ctx->stream_drain(); });
 }
 
 // the extension mode of a forward transform (zk_ntt_extend): `batch` = the launch's polynomials = sources x k1 cosets
@@ -554,6 +507,19 @@ struct NttExt {
     uint32_t k1, log_k;
     const uint32_t *pre;
     uint32_t *out;
+};
+
+// intermediates between passes live in the workspace in limb form (36 B = 9 words per element: no unpack / pack at a boundary),
+// two buffers alternating; the first pass reads and the last pass writes the caller's canonical vector
+struct NttPassBuffers {
+    size_t words;
+    int np;
+    uint32_t *ws2[2] = {nullptr, nullptr};
+    template <class Arena>
+    void layout(Arena &a) {
+        a.take(ws2[0], words);
+        if (np > 2) a.take(ws2[1], words);
+    }
 };
 
 template <class U>
@@ -566,21 +532,12 @@ static int ntt_run_t(zkhip_ctx *ctx, int curve, uint32_t *d_data, size_t log_m, 
     const NttPlan pl = ntt_plan(log_m, smax, ctx->opt_ntt_tile_log);
     const int np = pl.np;
     const size_t m = (size_t)1 << log_m;
-    // intermediates between passes live in the workspace in limb form (36 B per element: no unpack / pack at a boundary),
-    // two buffers alternating; the first pass reads and the last pass writes the caller's canonical vector
-    const size_t lbytes = batch * m * 36;
-    uint32_t *ws2[2] = {nullptr, nullptr};
-    if (np > 1) {
-        size_t need = zkhip_ctx::ws_round(lbytes) * (np > 2 ? 2 : 1);
-        ZK_TRY(ctx->ws_reserve(need));
-        ctx->ws_reset();
-        ws2[0] = ctx->ws_take<uint32_t>(lbytes / 4);
-        if (np > 2) ws2[1] = ctx->ws_take<uint32_t>(lbytes / 4);
-    }
+    NttPassBuffers w = {batch * m * 9, np};
+    if (np > 1) ZK_TRY(ws_place(ctx, w));
     uint32_t log_ns = 0;
     const uint32_t *src = d_data;
     for (int i = 0; i < np; ++i) {
-        uint32_t *dst = i == np - 1 ? (ext ? ext->out : d_data) : ws2[i & 1];  // np == 1: in place (the single tile is read fully into LDS before any store)
+        uint32_t *dst = i == np - 1 ? (ext ? ext->out : d_data) : w.ws2[i & 1];  // np == 1: in place (the single tile is read fully into LDS before any store)
         NttPass p;
         p.in = src;
         p.out = dst;
@@ -668,75 +625,28 @@ __global__ __launch_bounds__(256) void ntt_build_ext_pre(const uint32_t *__restr
     l_store<U>(out + (size_t)(j - 1) * ((size_t)9 << log_m), (size_t)8 << log_m, i, fu_cond_sub_p(r));
 }
 
-struct NttExtTables {
-    int curve;
-    size_t log_m, log_k;
-    uint64_t omega_big[4];
-    uint32_t *d_pre = nullptr;
-};
-static std::vector<std::pair<zkhip_ctx *, NttExtTables *>> g_ext_tables;  // owned per context; freed with the context's NTT tables
-static std::mutex g_ext_mutex;
-
-void zk_ntt_free_ext_tables(zkhip_ctx *ctx) {
-    std::lock_guard<std::mutex> lock(g_ext_mutex);
-    for (size_t i = g_ext_tables.size(); i-- > 0;)
-        if (g_ext_tables[i].first == ctx) {
-            (void)hipFree(g_ext_tables[i].second->d_pre);
-            delete g_ext_tables[i].second;
-            g_ext_tables.erase(g_ext_tables.begin() + i);
-        }
-}
-
 template <class U>
 static int ntt_extend_t(zkhip_ctx *ctx, int curve, uint32_t *d_coeffs, size_t log_m, size_t batch, const uint64_t *omega, uint32_t *d_out, size_t log_k,
                         const uint64_t *omega_big) {
     const size_t m = (size_t)1 << log_m, k1 = ((size_t)1 << log_k) - 1;
-    NttExtTables *t = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(g_ext_mutex);
-        size_t mine = 0;
-        for (auto &e : g_ext_tables) {
-            if (e.first != ctx) continue;
-            ++mine;
-            if (e.second->curve == curve && e.second->log_m == log_m && e.second->log_k == log_k && memcmp(e.second->omega_big, omega_big, 32) == 0) t = e.second;
-        }
-        if (!t && mine >= 16) {  // keep the cache bounded: drop this context's oldest entry
-            for (size_t i = 0; i < g_ext_tables.size(); ++i)
-                if (g_ext_tables[i].first == ctx) {
-                    ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-                    (void)hipFree(g_ext_tables[i].second->d_pre);
-                    delete g_ext_tables[i].second;
-                    g_ext_tables.erase(g_ext_tables.begin() + i);
-                    break;
-                }
-        }
-    }
+    NttExtTables *t = ctx->ntt_ext_tables.find([&](const NttExtTables &e) {
+        return e.curve == curve && e.log_m == log_m && e.log_k == log_k && memcmp(e.omega_big, omega_big, 32) == 0;
+    });
     if (!t) {
-        t = new NttExtTables();
-        t->curve = curve;
-        t->log_m = log_m;
-        t->log_k = log_k;
-        memcpy(t->omega_big, omega_big, 32);
-        uint32_t *d_w = nullptr;
-        // a HIP call that fails half way must not leak the table object or its device memory
-        auto build = [&]() -> int {
-            ZK_HIP_CHECK(ctx, hipMalloc((void **)&t->d_pre, k1 * m * 36));
-            ZK_HIP_CHECK(ctx, hipMalloc((void **)&d_w, 32));
-            ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_w, omega_big, 32, hipMemcpyHostToDevice, ctx->stream));
-            const size_t entries = k1 * m;
-            ZK_LAUNCH(ctx, "ntt_build_tw", ntt_build_ext_pre<U>, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, d_w, (uint32_t)log_m, (uint32_t)k1, t->d_pre);
-            ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-            return 0;
-        };
-        const int rc = build();
-        if (d_w) (void)hipFree(d_w);
-        if (rc != 0) {
-            if (t->d_pre) (void)hipFree(t->d_pre);
-            delete t;
-            return rc;
-        }
-        std::lock_guard<std::mutex> lock(g_ext_mutex);
-        g_ext_tables.emplace_back(ctx, t);
+        auto built = std::make_unique<NttExtTables>();
+        DevBuf d_w;
+        built->curve = curve;
+        built->log_m = log_m;
+        built->log_k = log_k;
+        memcpy(built->omega_big, omega_big, 32);
+        ZK_HIP_CHECK(ctx, built->d_pre.alloc(k1 * m * 36));
+        ZK_HIP_CHECK(ctx, d_w.alloc(32));
+        ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_w, omega_big, 32, hipMemcpyHostToDevice, ctx->stream));
+        const size_t entries = k1 * m;
+        ZK_LAUNCH(ctx, "ntt_build_tw", ntt_build_ext_pre<U>, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, d_w, (uint32_t)log_m, (uint32_t)k1, built->d_pre);
+        ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        t = built.get();
+        ZK_TRY(ctx->ntt_ext_tables.publish(std::move(built), [&] { return ctx->stream_drain(); }));
     }
     NttExt ext{(uint32_t)k1, (uint32_t)log_k, t->d_pre, d_out};
     return ntt_run_t<U>(ctx, curve, d_coeffs, log_m, batch * k1, omega, 0, nullptr, &ext);

@@ -313,6 +313,34 @@ __global__ void gp_setup(const uint32_t *__restrict__ in, uint32_t *__restrict__
     p_store_raw<U>(out, C_PART1, from_mont(mmul(opb, gamma_m)));
 }
 
+struct RowsHead {  // what a row functor reads: its device pointer table and the constants of gp_setup
+    size_t count;
+    const uint32_t **ptrs;
+    uint32_t *consts;  // C_SLOTS constants | beta, gamma as uploaded | the first-zero-row cell
+    uint32_t *in() const { return consts + C_SLOTS * 8; }
+    uint32_t *zero_row() const { return consts + (C_SLOTS + 2) * 8; }
+    template <class Arena>
+    void layout(Arena &a) {
+        a.take(ptrs, count);
+        a.take(consts, (C_SLOTS + 2) * 8 + 16);
+    }
+};
+struct ScanBuffers {
+    RowsHead head;
+    size_t n_slots, nblk;
+    uint32_t *nom, *den, *lpre, *lsuf, *bn, *bd;
+    template <class Arena>
+    void layout(Arena &a) {
+        head.layout(a);
+        a.take(nom, n_slots * 8);
+        a.take(den, n_slots * 8);
+        a.take(lpre, nblk * PERM_THREADS * 8);
+        a.take(lsuf, nblk * PERM_THREADS * 8);
+        a.take(bn, nblk * 8);
+        a.take(bd, nblk * 8);
+    }
+};
+
 // the passes over `n` entries of which the first `rows` carry ratios; ptrs: the device pointer table of the row functor (count entries)
 template <class U, class MakeRows>
 int scan_run(zkhip_ctx *ctx, size_t count, MakeRows make_rows, size_t n, size_t rows, uint32_t f_nom, uint32_t f_den, uint32_t pow_opb, const uint64_t *beta,
@@ -321,16 +349,10 @@ int scan_run(zkhip_ctx *ctx, size_t count, MakeRows make_rows, size_t n, size_t 
     if (nblk > (size_t)PERM_THREADS * 4096) return ZKHIP_ERR_RANGE;
     const uint32_t per = (uint32_t)((nblk + PERM_THREADS - 1) / PERM_THREADS);
     const size_t n_slots = nblk * PERM_THREADS * PERM_CHUNK;  // perm_slot stays inside the row's block: whole blocks of scratch
-    size_t need = zkhip_ctx::ws_round(count * sizeof(void *)) + zkhip_ctx::ws_round((C_SLOTS + 2) * 32 + 64) + 2 * zkhip_ctx::ws_round(n_slots * 32) +
-                  2 * zkhip_ctx::ws_round(nblk * PERM_THREADS * 32) + 2 * zkhip_ctx::ws_round(nblk * 32);
-    ZK_TRY(ctx->ws_reserve(need));
-    ctx->ws_reset();
-    const uint32_t **d_ptrs = ctx->ws_take<const uint32_t *>(count);
-    uint32_t *d_consts = ctx->ws_take<uint32_t>((C_SLOTS + 2) * 8 + 16);  // C_SLOTS constants | beta, gamma as uploaded | the first-zero-row cell
-    uint32_t *d_nom = ctx->ws_take<uint32_t>(n_slots * 8), *d_den = ctx->ws_take<uint32_t>(n_slots * 8);
-    uint32_t *d_lpre = ctx->ws_take<uint32_t>(nblk * PERM_THREADS * 8), *d_lsuf = ctx->ws_take<uint32_t>(nblk * PERM_THREADS * 8);
-    uint32_t *d_bn = ctx->ws_take<uint32_t>(nblk * 8), *d_bd = ctx->ws_take<uint32_t>(nblk * 8);
-    uint32_t *d_in = d_consts + C_SLOTS * 8, *d_z = d_consts + (C_SLOTS + 2) * 8;
+    ScanBuffers w = {{count}, n_slots, nblk};
+    ZK_TRY(ws_place(ctx, w));
+    const uint32_t **d_ptrs = w.head.ptrs;
+    uint32_t *d_consts = w.head.consts, *d_in = w.head.in(), *d_z = w.head.zero_row();
     ctx->lagrange_stage.assign(16, 0u);  // host copies alive until the asynchronous copies ran (synchronised below); batch_ptrs filled by the caller
     memcpy(ctx->lagrange_stage.data(), beta, 32);
     memcpy(ctx->lagrange_stage.data() + 8, gamma, 32);
@@ -340,10 +362,10 @@ int scan_run(zkhip_ctx *ctx, size_t count, MakeRows make_rows, size_t n, size_t 
     auto rows_of = make_rows(d_ptrs);
     if (rows)
         ZK_LAUNCH(ctx, "perm_grand_product", (gp_rows<U, decltype(rows_of)>), dim3((unsigned)((rows + PERM_THREADS - 1) / PERM_THREADS)), dim3(PERM_THREADS), 0, rows_of,
-                  rows, d_consts, d_nom, d_den, d_z);
-    ZK_LAUNCH(ctx, "perm_grand_product", gp_local<U>, dim3((unsigned)nblk), dim3(PERM_THREADS), 0, rows, d_nom, d_den, d_lpre, d_lsuf, d_bn, d_bd);
-    ZK_LAUNCH(ctx, "perm_grand_product", gp_top<U>, dim3(1), dim3(PERM_THREADS), 0, d_bn, d_bd, (uint32_t)nblk, per, d_consts);
-    ZK_LAUNCH(ctx, "perm_grand_product", gp_apply<U>, dim3((unsigned)nblk), dim3(PERM_THREADS), 0, d_nom, d_den, d_lpre, d_lsuf, d_bn, d_bd, d_consts, d_z, n, rows, d_vp);
+                  rows, d_consts, w.nom, w.den, d_z);
+    ZK_LAUNCH(ctx, "perm_grand_product", gp_local<U>, dim3((unsigned)nblk), dim3(PERM_THREADS), 0, rows, w.nom, w.den, w.lpre, w.lsuf, w.bn, w.bd);
+    ZK_LAUNCH(ctx, "perm_grand_product", gp_top<U>, dim3(1), dim3(PERM_THREADS), 0, w.bn, w.bd, (uint32_t)nblk, per, d_consts);
+    ZK_LAUNCH(ctx, "perm_grand_product", gp_apply<U>, dim3((unsigned)nblk), dim3(PERM_THREADS), 0, w.nom, w.den, w.lpre, w.lsuf, w.bn, w.bd, d_consts, d_z, n, rows, d_vp);
     ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // the staged pointers / constants may be reused after return
     return ZKHIP_OK;
 }
@@ -364,11 +386,10 @@ int perm_run(zkhip_ctx *ctx, size_t k, const void *const *d_cols, const void *co
 template <class U>
 int perm_products_run(zkhip_ctx *ctx, size_t k, const void *const *d_cols, const void *const *d_sid, const void *const *d_ssig, size_t n, const uint64_t *beta,
                       const uint64_t *gamma, uint32_t *d_g, uint32_t *d_h) {
-    ZK_TRY(ctx->ws_reserve(zkhip_ctx::ws_round(3 * k * sizeof(void *)) + zkhip_ctx::ws_round((C_SLOTS + 2) * 32 + 64)));
-    ctx->ws_reset();
-    const uint32_t **d_ptrs = ctx->ws_take<const uint32_t *>(3 * k);
-    uint32_t *d_consts = ctx->ws_take<uint32_t>((C_SLOTS + 2) * 8 + 16);
-    uint32_t *d_in = d_consts + C_SLOTS * 8, *d_z = d_consts + (C_SLOTS + 2) * 8;
+    RowsHead w = {3 * k};
+    ZK_TRY(ws_place(ctx, w));
+    const uint32_t **d_ptrs = w.ptrs;
+    uint32_t *d_consts = w.consts, *d_in = w.in(), *d_z = w.zero_row();
     ctx->batch_ptrs.resize(3 * k);
     for (size_t i = 0; i < k; ++i) {
         ctx->batch_ptrs[i] = (uint32_t *)d_cols[i];
@@ -460,21 +481,29 @@ __global__ __launch_bounds__(PERM_THREADS) void md_apply(const uint32_t *a, cons
     }
 }
 
+struct MulDivBuffers {
+    size_t count, nblk;
+    uint32_t *consts, *cm, *lpre, *lsuf, *bp, *bs;
+    template <class Arena>
+    void layout(Arena &a) {
+        a.take(consts, C_SLOTS * 8);
+        a.take(cm, count * 8);
+        a.take(lpre, nblk * PERM_THREADS * 8);
+        a.take(lsuf, nblk * PERM_THREADS * 8);
+        a.take(bp, nblk * 8);
+        a.take(bs, nblk * 8);
+    }
+};
 template <class U>
 int mul_div_run(zkhip_ctx *ctx, const uint32_t *a, const uint32_t *b, const uint32_t *c, uint32_t *out, size_t count) {
     const size_t lanes = (count + PERM_CHUNK - 1) / PERM_CHUNK, nblk = (lanes + PERM_THREADS - 1) / PERM_THREADS;
     if (nblk > (size_t)PERM_THREADS * 4096) return ZKHIP_ERR_RANGE;
     const uint32_t per = (uint32_t)((nblk + PERM_THREADS - 1) / PERM_THREADS);
-    size_t need = zkhip_ctx::ws_round(C_SLOTS * 32) + zkhip_ctx::ws_round(count * 32) + 2 * zkhip_ctx::ws_round(nblk * PERM_THREADS * 32) + 2 * zkhip_ctx::ws_round(nblk * 32);
-    ZK_TRY(ctx->ws_reserve(need));
-    ctx->ws_reset();
-    uint32_t *d_consts = ctx->ws_take<uint32_t>(C_SLOTS * 8);
-    uint32_t *d_cm = ctx->ws_take<uint32_t>(count * 8);
-    uint32_t *d_lpre = ctx->ws_take<uint32_t>(nblk * PERM_THREADS * 8), *d_lsuf = ctx->ws_take<uint32_t>(nblk * PERM_THREADS * 8);
-    uint32_t *d_bp = ctx->ws_take<uint32_t>(nblk * 8), *d_bs = ctx->ws_take<uint32_t>(nblk * 8);
-    ZK_LAUNCH(ctx, "fr_vec_mul_div", md_local<U>, dim3((unsigned)nblk), dim3(PERM_THREADS), 0, c, count, d_cm, d_lpre, d_lsuf, d_bp, d_bs);
-    ZK_LAUNCH(ctx, "fr_vec_mul_div", gp_top<U>, dim3(1), dim3(PERM_THREADS), 0, d_bp, d_bs, (uint32_t)nblk, per, d_consts);
-    ZK_LAUNCH(ctx, "fr_vec_mul_div", md_apply<U>, dim3((unsigned)nblk), dim3(PERM_THREADS), 0, a, b, d_cm, d_lpre, d_lsuf, d_bp, d_bs, d_consts, count, out);
+    MulDivBuffers w = {count, nblk};
+    ZK_TRY(ws_place(ctx, w));
+    ZK_LAUNCH(ctx, "fr_vec_mul_div", md_local<U>, dim3((unsigned)nblk), dim3(PERM_THREADS), 0, c, count, w.cm, w.lpre, w.lsuf, w.bp, w.bs);
+    ZK_LAUNCH(ctx, "fr_vec_mul_div", gp_top<U>, dim3(1), dim3(PERM_THREADS), 0, w.bp, w.bs, (uint32_t)nblk, per, w.consts);
+    ZK_LAUNCH(ctx, "fr_vec_mul_div", md_apply<U>, dim3((unsigned)nblk), dim3(PERM_THREADS), 0, a, b, w.cm, w.lpre, w.lsuf, w.bp, w.bs, w.consts, count, out);
     return ZKHIP_OK;
 }
 

@@ -363,30 +363,56 @@ __global__ __launch_bounds__(256) void poly_lincomb(const uint32_t *const *__res
 }
 
 
-// shared front half of evaluation and division: per-(polynomial, point) workgroup partials and the pass over them
+struct HornerBuffers {
+    size_t npoints, total, nblk, sl;  // sl: words per element in limb form
+    uint32_t *pts, *zpow, *part, *carry, *values;
+    template <class Arena>
+    void layout(Arena &a) {
+        a.take(pts, npoints * 8);
+        a.take(zpow, npoints * 10 * sl);
+        a.take(part, total * nblk * sl);
+        a.take(carry, total * nblk * sl);
+        a.take(values, total * 8);
+    }
+};
+// shared front half of evaluation and division: per-(polynomial, point) workgroup partials and the pass over them; w holds zpow, carry and values
 template <class U>
-static int horner_run(zkhip_ctx *ctx, const uint32_t *d_polys, size_t n, size_t stride, size_t batch, const uint64_t *points, size_t npoints,
-                      uint32_t **zpow_out, uint32_t **carry_out, uint32_t **values_out, bool want_carry) {
+static int horner_run(zkhip_ctx *ctx, const uint32_t *d_polys, size_t n, size_t stride, size_t batch, const uint64_t *points, size_t npoints, HornerBuffers &w,
+                      bool want_carry) {
     const uint32_t nblk = (uint32_t)((n + HORNER_BLOCK - 1) / HORNER_BLOCK);
     const size_t total = batch * npoints;
-    size_t need = zkhip_ctx::ws_round(npoints * 32) + zkhip_ctx::ws_round(npoints * 10 * U::SL * 4) + zkhip_ctx::ws_round(total * nblk * U::SL * 4) +
-                  zkhip_ctx::ws_round(total * nblk * U::SL * 4) + zkhip_ctx::ws_round(total * 32);
-    ZK_TRY(ctx->ws_reserve(need));
-    ctx->ws_reset();
-    uint32_t *d_pts = ctx->ws_take<uint32_t>(npoints * 8);
-    uint32_t *zpow = ctx->ws_take<uint32_t>(npoints * 10 * U::SL);
-    uint32_t *part = ctx->ws_take<uint32_t>(total * nblk * U::SL);
-    uint32_t *carry = ctx->ws_take<uint32_t>(total * nblk * U::SL);
-    uint32_t *values = ctx->ws_take<uint32_t>(total * 8);
-    ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_pts, points, npoints * 32, hipMemcpyHostToDevice, ctx->stream));
-    ZK_LAUNCH(ctx, "poly_horner_setup", horner_setup<U>, dim3((unsigned)((npoints + 63) / 64)), dim3(64), 0, d_pts, (uint32_t)npoints, zpow);
+    w = {npoints, total, nblk, U::SL};
+    ZK_TRY(ws_place(ctx, w));
+    ZK_HIP_CHECK(ctx, hipMemcpyAsync(w.pts, points, npoints * 32, hipMemcpyHostToDevice, ctx->stream));
+    ZK_LAUNCH(ctx, "poly_horner_setup", horner_setup<U>, dim3((unsigned)((npoints + 63) / 64)), dim3(64), 0, w.pts, (uint32_t)npoints, w.zpow);
     ZK_LAUNCH(ctx, "poly_block_horner", poly_block_horner<U>, dim3(nblk, (unsigned)batch, (unsigned)npoints), dim3(256), 0, d_polys, n, stride, nblk,
-              (uint32_t)npoints, zpow, part);
-    ZK_LAUNCH(ctx, "poly_block_carry", poly_block_carry<U>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, part, nblk, (uint32_t)npoints, (uint32_t)total,
-              zpow, want_carry ? carry : nullptr, values);
-    *zpow_out = zpow, *carry_out = carry, *values_out = values;
+              (uint32_t)npoints, w.zpow, w.part);
+    ZK_LAUNCH(ctx, "poly_block_carry", poly_block_carry<U>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, w.part, nblk, (uint32_t)npoints, (uint32_t)total,
+              w.zpow, want_carry ? w.carry : nullptr, w.values);
     return ZKHIP_OK;
 }
+
+struct FriFoldBuffers {
+    uint32_t *in, *consts;  // alpha, omega as uploaded; what fri_fold_setup makes of them
+    template <class Arena>
+    void layout(Arena &a) {
+        a.take(in, 16);
+        a.take(consts, 64);
+    }
+};
+struct LincombBuffers {
+    size_t nc, count;
+    uint32_t *c, *m;  // coefficients as uploaded, in Montgomery form (16-word slots)
+    const uint32_t **p;
+    uint64_t *l;
+    template <class Arena>
+    void layout(Arena &a) {
+        a.take(c, nc * 8);
+        a.take(m, nc * 16);
+        a.take(p, count + 1);
+        a.take(l, count + 1);
+    }
+};
 
 // omega_out^(2^log_k) == omega_n ?  (host arithmetic: the C++ bodies of fu.hpp) -- what the coset extension below relies on
 template <class U>
@@ -444,10 +470,9 @@ int zkhip_fri_fold_dev(zkhip_ctx *ctx, int curve, const void *d_f, size_t log_si
     if (log_size < 1 || log_size > 32) return ZKHIP_ERR_RANGE;
     if (curve != CURVE_BLS12_381 && curve != CURVE_BN254) return ZKHIP_ERR_INVALID;
     ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    ZK_TRY(ctx->ws_reserve(4096));
-    ctx->ws_reset();
-    uint32_t *d_c = ctx->ws_take<uint32_t>(16);
-    uint32_t *consts = ctx->ws_take<uint32_t>(64);
+    FriFoldBuffers w;
+    ZK_TRY(ws_place(ctx, w));
+    uint32_t *d_c = w.in, *consts = w.consts;
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_c, alpha, 32, hipMemcpyHostToDevice, ctx->stream));
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_c + 8, omega, 32, hipMemcpyHostToDevice, ctx->stream));
     size_t half = (size_t)1 << (log_size - 1), lanes = (half + FOLD_CHUNK - 1) / FOLD_CHUNK;
@@ -506,9 +531,9 @@ int zkhip_poly_div_vanishing_dev(zkhip_ctx *ctx, int curve, const void *d_f, siz
     if (nonzero_remainders) *nonzero_remainders = 0;
     if (len == 0) return ZKHIP_OK;
     ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    ZK_TRY(ctx->ws_reserve(zkhip_ctx::ws_round(4)));
-    ctx->ws_reset();
-    uint32_t *d_bad = ctx->ws_take<uint32_t>(1);
+    WsOne<uint32_t> w = {1};
+    ZK_TRY(ws_place(ctx, w));
+    uint32_t *d_bad = w.p;
     ZK_HIP_CHECK(ctx, hipMemsetAsync(d_bad, 0, 4, ctx->stream));
     const size_t lanes = std::min(n, len);
     ZK_FR_DISPATCH(curve, ZK_LAUNCH(ctx, "poly_div_vanishing", poly_div_vanishing<U>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0,
@@ -530,9 +555,9 @@ int zkhip_fr_vec_prod_dev(zkhip_ctx *ctx, int curve, size_t count, const void *c
         if (n && !d_in[k]) return ZKHIP_ERR_INVALID;
     if (n == 0) return ZKHIP_OK;
     ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    ZK_TRY(ctx->ws_reserve(zkhip_ctx::ws_round(count * sizeof(void *))));
-    ctx->ws_reset();
-    const uint32_t **d_ptrs = ctx->ws_take<const uint32_t *>(count);
+    WsOne<const uint32_t *> w = {count};
+    ZK_TRY(ws_place(ctx, w));
+    const uint32_t **d_ptrs = w.p;
     ctx->batch_ptrs.assign((uint32_t *const *)d_in, (uint32_t *const *)d_in + count);  // host copy alive until the async copy ran
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_ptrs, ctx->batch_ptrs.data(), count * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
     ZK_FR_DISPATCH(curve, ZK_LAUNCH(ctx, "fr_vec_prod", fr_vec_prod<U>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, d_ptrs, (uint32_t)count, n,
@@ -558,9 +583,9 @@ int zkhip_poly_eval_dev(zkhip_ctx *ctx, int curve, const void *d_polys, size_t n
     if (stride < n || batch >= 65536 || npoints >= 65536 || n >= ((size_t)1 << 40)) return ZKHIP_ERR_RANGE;
     if (batch == 0 || npoints == 0) return ZKHIP_OK;
     ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    uint32_t *zpow, *carry, *values;
-    ZK_FR_DISPATCH(curve, ZK_TRY(horner_run<U>(ctx, (const uint32_t *)d_polys, n, stride, batch, points, npoints, &zpow, &carry, &values, false)));
-    ZK_HIP_CHECK(ctx, hipMemcpyAsync(out, values, batch * npoints * 32, hipMemcpyDeviceToHost, ctx->stream));
+    HornerBuffers w;
+    ZK_FR_DISPATCH(curve, ZK_TRY(horner_run<U>(ctx, (const uint32_t *)d_polys, n, stride, batch, points, npoints, w, false)));
+    ZK_HIP_CHECK(ctx, hipMemcpyAsync(out, w.values, batch * npoints * 32, hipMemcpyDeviceToHost, ctx->stream));
     ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return ZKHIP_OK;
 }
@@ -574,13 +599,13 @@ int zkhip_poly_div_linear_dev(zkhip_ctx *ctx, int curve, const void *d_f, size_t
         return ZKHIP_OK;
     }
     ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    uint32_t *zpow, *carry, *values;
+    HornerBuffers w;
     const uint32_t nblk = (uint32_t)((n + HORNER_BLOCK - 1) / HORNER_BLOCK);
-    ZK_FR_DISPATCH(curve, ZK_TRY(horner_run<U>(ctx, (const uint32_t *)d_f, n, n, 1, z, 1, &zpow, &carry, &values, true));
-                   ZK_LAUNCH(ctx, "poly_div_finish", poly_div_finish<U>, dim3(nblk), dim3(256), 0, (const uint32_t *)d_f, n, nblk, zpow, carry,
+    ZK_FR_DISPATCH(curve, ZK_TRY(horner_run<U>(ctx, (const uint32_t *)d_f, n, n, 1, z, 1, w, true));
+                   ZK_LAUNCH(ctx, "poly_div_finish", poly_div_finish<U>, dim3(nblk), dim3(256), 0, (const uint32_t *)d_f, n, nblk, w.zpow, w.carry,
                              (uint32_t *)d_out));
     if (remainder) {
-        ZK_HIP_CHECK(ctx, hipMemcpyAsync(remainder, values, 32, hipMemcpyDeviceToHost, ctx->stream));
+        ZK_HIP_CHECK(ctx, hipMemcpyAsync(remainder, w.values, 32, hipMemcpyDeviceToHost, ctx->stream));
         ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     }
     return ZKHIP_OK;
@@ -594,13 +619,11 @@ int zkhip_poly_lincomb_dev(zkhip_ctx *ctx, int curve, size_t count, const void *
     if (acc_len == 0) return ZKHIP_OK;
     ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t nc = std::max<size_t>(1, count * taps);
-    size_t need = zkhip_ctx::ws_round(nc * 32) + zkhip_ctx::ws_round(nc * 16 * 4) + zkhip_ctx::ws_round((count + 1) * 8) * 2;
-    ZK_TRY(ctx->ws_reserve(need));
-    ctx->ws_reset();
-    uint32_t *d_c = ctx->ws_take<uint32_t>(nc * 8);
-    uint32_t *d_m = ctx->ws_take<uint32_t>(nc * 16);
-    const uint32_t **d_p = ctx->ws_take<const uint32_t *>(count + 1);
-    uint64_t *d_l = ctx->ws_take<uint64_t>(count + 1);
+    LincombBuffers w = {nc, count};
+    ZK_TRY(ws_place(ctx, w));
+    uint32_t *d_c = w.c, *d_m = w.m;
+    const uint32_t **d_p = w.p;
+    uint64_t *d_l = w.l;
     if (count) {
         // the pointer / length / coefficient tables are staged through the context so the caller's arrays may die on return
         ctx->lincomb_stage.resize(count * 2);

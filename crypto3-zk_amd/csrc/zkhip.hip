@@ -14,6 +14,28 @@ static int check_device(zkhip_ctx *ctx) {
     return 0;
 }
 
+struct DownloadBuffers {  // zkhip_bases_download: n affine points of `words` u32 each and their infinity flags
+    size_t n, words;
+    uint32_t *xy;
+    uint8_t *inf;
+    template <class Arena>
+    void layout(Arena &a) {
+        a.take(xy, n * words);
+        a.take(inf, n);
+    }
+};
+struct ToAffineBuffers {  // zkhip_jacobian_to_affine: one point in, one out; cw = u32 words per coordinate
+    size_t cw;
+    uint32_t *jac, *aff;
+    uint8_t *inf;
+    template <class Arena>
+    void layout(Arena &a) {
+        a.take(jac, 3 * cw);
+        a.take(aff, 2 * cw);
+        a.take(inf, 16);
+    }
+};
+
 extern "C" {
 
 const char *zkhip_strerror(int status) {
@@ -640,10 +662,10 @@ int zkhip_bases_download(zkhip_ctx *ctx, const zkhip_bases *b, size_t offset, si
     if (n == 0) return ZKHIP_OK;
     ZK_TRY(check_device(ctx));
     size_t pbytes = n * 2 * zk_coord_limbs64(b->curve, b->group) * 8;
-    ZK_TRY(ctx->ws_reserve(zkhip_ctx::ws_round(pbytes) + zkhip_ctx::ws_round(n)));
-    ctx->ws_reset();
-    uint32_t *d_out = ctx->ws_take<uint32_t>(pbytes / 4);
-    uint8_t *d_inf = ctx->ws_take<uint8_t>(n);
+    DownloadBuffers w = {n, 4 * zk_coord_limbs64(b->curve, b->group)};
+    ZK_TRY(ws_place(ctx, w));
+    uint32_t *d_out = w.xy;
+    uint8_t *d_inf = w.inf;
     ZK_TRY(zk_bases_from_mont(ctx, b, offset, n, d_out, d_inf));
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(affine_xy, d_out, pbytes, hipMemcpyDeviceToHost, ctx->stream));
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(is_infinity, d_inf, n, hipMemcpyDeviceToHost, ctx->stream));
@@ -727,11 +749,10 @@ int zkhip_jacobian_to_affine(zkhip_ctx *ctx, int curve, int group, const uint64_
     if ((curve != CURVE_BLS12_381 && curve != CURVE_BN254) || (group != GROUP_G1 && group != GROUP_G2)) return ZKHIP_ERR_INVALID;
     ZK_TRY(check_device(ctx));
     size_t cl = zk_coord_limbs64(curve, group) * 8;
-    ZK_TRY(ctx->ws_reserve(4096));
-    ctx->ws_reset();
-    uint32_t *d_j = ctx->ws_take<uint32_t>(3 * cl / 4);
-    uint32_t *d_a = ctx->ws_take<uint32_t>(2 * cl / 4);
-    uint8_t *d_i = ctx->ws_take<uint8_t>(16);
+    ToAffineBuffers w = {cl / 4};
+    ZK_TRY(ws_place(ctx, w));
+    uint32_t *d_j = w.jac, *d_a = w.aff;
+    uint8_t *d_i = w.inf;
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_j, jacobian, 3 * cl, hipMemcpyHostToDevice, ctx->stream));
     ZK_TRY(zk_jac_to_affine(ctx, curve, group, d_j, d_a, d_i));
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(affine_xy, d_a, 2 * cl, hipMemcpyDeviceToHost, ctx->stream));

@@ -5,8 +5,10 @@
 // lent uploads of the KZG and LPC schemes and the LPC leaf streaming, the fan-out over a device group's members -- and a
 // mutation loop over proving_key_from_bytes (marshalling.hpp), which parses untrusted blobs: truncations at every framing
 // boundary, oversized and zero counts, non-increasing / out-of-range B indices, random byte flips.  The parser must throw or
-// succeed; the sanitizers decide the rest.
+// succeed; the sanitizers decide the rest.  Also the context's table cache (csrc/table_cache.hpp) over an entry type that counts its
+// constructions and destructions: eviction order, the drain before each eviction, a build abandoned before publish().
 #include <chrono>
+#include <memory>
 #include <cstdio>
 #include <cstring>
 #include <functional>
@@ -24,6 +26,8 @@
 #include <nil/crypto3/zk/hip/placeholder_lookup.hpp>
 #include <nil/crypto3/zk/hip/placeholder_quotient.hpp>
 #include <nil/crypto3/zk/hip/r1cs_gg_ppzksnark_generator.hpp>
+
+#include "../../../crypto3-zk_amd/csrc/table_cache.hpp"
 
 using namespace nil::crypto3::zk::hip;
 
@@ -658,6 +662,57 @@ void parser_fuzz() {
     fprintf(stderr, "parser fuzz: %zu blobs accepted, %zu refused\n", accepted, refused);
     EXPECT(refused > 100);
 }
+
+// an entry that counts how many of its kind were made and destroyed
+struct counted_entry {
+    static int made, gone;
+    int key;
+    explicit counted_entry(int k) : key(k) { ++made; }
+    ~counted_entry() { ++gone; }
+};
+int counted_entry::made = 0, counted_entry::gone = 0;
+
+void table_cache_protocol() {
+    const auto has = [](int k) { return [k](const counted_entry &e) { return e.key == k; }; };
+    {
+        TableCache<counted_entry> cache(3);
+        int drains = 0;
+        bool drained_first = true;  // at every drain the cache is still full and its oldest entry still findable
+        int oldest = 0;
+        for (int k = 0; k < 5; ++k) {
+            auto e = std::make_unique<counted_entry>(k);
+            counted_entry *raw = e.get();
+            const int rc = cache.publish(std::move(e), [&]() -> int {
+                ++drains;
+                drained_first = drained_first && cache.size() == 3 && cache.find(has(oldest)) != nullptr && counted_entry::gone == oldest;
+                return 0;
+            });
+            EXPECT(rc == 0 && cache.find(has(k)) == raw);
+            if (k >= 3) ++oldest;
+        }
+        EXPECT(drains == 2 && drained_first);
+        EXPECT(cache.size() == 3 && counted_entry::gone == 2);
+        EXPECT(!cache.find(has(0)) && !cache.find(has(1)));
+        EXPECT(cache.find(has(2)) && cache.find(has(3)) && cache.find(has(4)));
+        // a build that returns before publish(): the cache is as it was, the abandoned entry destroyed exactly once
+        const int gone_before = counted_entry::gone;
+        const auto abandoned_build = [&]() -> int {
+            auto e = std::make_unique<counted_entry>(7);
+            if (e->key == 7) return -1;  // the early return of a failed allocation or launch
+            return cache.publish(std::move(e), [] { return 0; });
+        };
+        EXPECT(abandoned_build() == -1);
+        EXPECT(counted_entry::gone == gone_before + 1 && cache.size() == 3 && !cache.find(has(7)));
+        EXPECT(cache.find(has(2)) && cache.find(has(3)) && cache.find(has(4)));
+        // a drain that fails hands its code back: nothing evicted, the new entry destroyed
+        EXPECT(cache.publish(std::make_unique<counted_entry>(8), [] { return -3; }) == -3);
+        EXPECT(cache.size() == 3 && cache.find(has(2)) && !cache.find(has(8)) && counted_entry::gone == gone_before + 2);
+        cache.clear();
+        EXPECT(cache.size() == 0 && counted_entry::made == 7 && counted_entry::gone == 7);
+        EXPECT(cache.publish(std::make_unique<counted_entry>(9), [] { return 0; }) == 0);  // left for the destructor
+    }
+    EXPECT(counted_entry::made == 8 && counted_entry::made == counted_entry::gone);
+}
 }    // namespace
 
 int main(int argc, char **argv) {
@@ -677,6 +732,7 @@ int main(int argc, char **argv) {
         group_helpers();
     }
     if (what == "all" || what == "fuzz") parser_fuzz();
+    if (what == "all" || what == "table_cache") table_cache_protocol();
     fprintf(stderr, failures ? "sanitize_main: %d FAILED expectation(s)\n" : "sanitize_main: ok\n", failures);
     return failures ? 1 : 0;
 }

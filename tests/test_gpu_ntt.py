@@ -212,8 +212,11 @@ def test_poly_resize_coset_extension(ctx, curve, log_n, expand, batch):
 
 def test_ntt_rejects_a_root_of_the_wrong_order(zk, ctx):
     """omega must be a PRIMITIVE 2^log_m-th root of unity (a key generated over another domain must fail loudly,
-    not transform over the wrong domain): the square of the right root (order m / 2), 1, and the root of the next size are refused."""
+    not transform over the wrong domain): the square of the right root (order m / 2), 1, and the root of the next size are refused.
+    A refused build leaves no entry in the table cache: the same wrong root is refused again (no hit on a half-built entry), and the
+    right root of the same size then transforms correctly; the same for a step domain whose omega has the wrong order."""
     C = po.BLS12_381
+    invalid = ctx.lib.zkhip_strerror(-2).decode()  # ZKHIP_ERR_INVALID
     log_m = 8
     a = cp.random_fr(0, 3, 1 << log_m).reshape(1, -1, 4)
     w = C.root_of_unity(log_m)
@@ -221,6 +224,118 @@ def test_ntt_rejects_a_root_of_the_wrong_order(zk, ctx):
     for bad in (w * w % C.r, 1, C.root_of_unity(log_m + 1), C.r - 1):
         with pytest.raises(zk.ZkhipError):
             ctx.ntt(0, a, log_m, limbs(bad, 4))
+    # a size whose right root has not been seen by a fresh context: wrong, wrong again, right
+    c = zk.Context(0)
+    try:
+        log_m = 7
+        a = cp.random_fr(0, 4, 1 << log_m).reshape(1, -1, 4)
+        w = C.root_of_unity(log_m)
+        for _ in range(2):
+            with pytest.raises(zk.ZkhipError) as e:
+                c.ntt(0, a, log_m, limbs(w * w % C.r, 4))
+            assert invalid in str(e.value) and "not a primitive" in str(e.value)
+        assert (c.ntt(0, a, log_m, limbs(w, 4)) == cp.ntt(0, a, log_m, limbs(w, 4))).all()
+        dom, zd = qap_domains(zk, 0, 20)
+        assert dom.kind == zk.zkhip.DOMAIN_STEP
+        bad = zk.zkhip.Domain.make(dom.kind, dom.m, limbs(C.root_of_unity(4), 4))
+        v = cp.random_fr(0, 5, dom.m).reshape(1, dom.m, 4)
+        for _ in range(2):
+            with pytest.raises(zk.zkhip.ZkhipError) as e:
+                c.domain_fft(0, bad, v)
+            assert invalid in str(e.value) and "not a primitive" in str(e.value)
+        assert (c.domain_fft(0, zd, v)[0] == cp.domain_fft(0, dom.kind, v[0], limbs(dom.omega, 4), limbs(dom.shift, 4))).all()
+    finally:
+        c.close()
+
+
+def test_ntt_table_cache_evicts_and_rebuilds(zk):
+    """The context keeps 24 NTT table sets, oldest out first: 26 distinct keys (2^1 .. 2^13, forward and inverse) on one context, then
+    the first -- evicted by then -- again.  Every transform bit-equal to the oracle's."""
+    C = po.BLS12_381
+    keys = [(log_m, inv) for log_m in range(1, 14) for inv in (False, True)]
+    assert len(keys) == 26
+    c = zk.Context(0)
+    try:
+        for log_m, inv in keys + keys[:1]:
+            w = limbs(C.root_of_unity(log_m), 4)
+            a = cp.random_fr(0, 2000 + log_m, 1 << log_m).reshape(1, -1, 4)
+            assert (c.ntt(0, a, log_m, w, inverse=inv) == cp.ntt(0, a, log_m, w, inverse=inv)).all(), (log_m, inv)
+    finally:
+        c.close()
+
+
+def test_ntt_extension_table_cache_evicts_and_rebuilds(zk):
+    """The context keeps 16 coset-extension table sets: zkhip_poly_resize_dev over 17 distinct (log_n, log_k) pairs, then the first
+    again; each output bit-equal to the inverse transform plus K n-point transform (poly_coset_extend = 0 on a second context)."""
+    import ctypes
+
+    C = po.BLS12_381
+    pairs = [(log_n, log_k) for log_n in range(3, 9) for log_k in (1, 2, 3)][:17]
+    P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    c, ref = zk.Context(0), zk.Context(0)
+    ref.set_option("poly_coset_extend", 0)
+
+    def resize(cx, evals, log_n, log_out):
+        wn, wm = limbs(C.root_of_unity(log_n), 4), limbs(C.root_of_unity(log_out), 4)
+        out = np.zeros((1, 1 << log_out, 4), dtype=np.uint64)
+        d_in, d_out = cx.malloc(evals.nbytes), cx.malloc(out.nbytes)
+        cx.h2d(d_in, evals)
+        rc = cx.lib.zkhip_poly_resize_dev(cx.h, 0, ctypes.c_void_p(d_in), ctypes.c_size_t(log_n), ctypes.c_size_t(1), P(wn), ctypes.c_void_p(d_out),
+                                          ctypes.c_size_t(log_out), P(wm))
+        assert rc == 0
+        cx.d2h(out, d_out)
+        cx.free(d_in)
+        cx.free(d_out)
+        return out
+
+    try:
+        for log_n, log_k in pairs + pairs[:1]:
+            evals = cp.random_fr(0, 3000 + 8 * log_n + log_k, 1 << log_n).reshape(1, -1, 4)
+            got = resize(c, evals, log_n, log_n + log_k)
+            assert (got == resize(ref, evals, log_n, log_n + log_k)).all(), (log_n, log_k)
+            assert (got[:, :: 1 << log_k] == evals).all()
+    finally:
+        c.close()
+        ref.close()
+
+
+def test_domain_table_cache_evicts_and_rebuilds(zk):
+    """The context keeps 8 domain table sets, the basic domains' 1 / Z entries among them: the nine smallest step / extended domains of
+    test_domain_fft_all_kinds, two 1 / Z requests over a basic domain with different cosets (the Groth16 witness map), then the first
+    domain again.  Forward matches the oracle's evaluation over the point set, forward then inverse returns the input."""
+    curve = 0
+    C = CURVES[curve]
+    cases = [(3, None), (5, None), (12, None), (20, None), (48, None), (65, None), (1040, None), (2048 + 256, None), (4096 + 512, None),
+             (4096 + 2048, None), (8192 + 1024, None), (32768 + 16, None), (8, 2), (64, 5), (2048, 10)]
+    doms = sorted((qap_domains(zk, curve, n, two_adicity=s) for n, s in cases), key=lambda d: d[0].m)
+    doms = [d for d in doms if d[0].kind != zk.zkhip.DOMAIN_BASIC][:9]
+    assert len(doms) == 9 and len({(d.kind, d.m) for d, _ in doms}) == 9
+    c = zk.Context(0)
+
+    def round_trip(dom, zd):
+        a = cp.random_fr(curve, 4000 + dom.m, 2 * dom.m).reshape(2, dom.m, 4)
+        exp = np.stack([cp.domain_fft(curve, dom.kind, a[b], limbs(dom.omega, 4), limbs(dom.shift, 4)) for b in range(2)])
+        got = c.domain_fft(curve, zd, a)
+        assert (got == exp).all(), dom.describe()
+        assert (c.domain_fft(curve, zd, got, inverse=True) == a).all(), dom.describe()
+
+    try:
+        for dom, zd in doms:
+            round_trip(dom, zd)
+        M, n = 13, 3
+        g16 = cp.Groth16(curve, M, n, seed=3)
+        r1cs = c.upload_r1cs(curve, g16.M, g16.n, g16.N, g16.csr(0), g16.csr(1), g16.csr(2))
+        z = np.concatenate([np.array([[1, 0, 0, 0]], dtype=np.uint64), g16.assignment()])
+        m2 = 1 << (M + n).bit_length()
+        r1cs.set_domain(zk.zkhip.DOMAIN_BASIC, m2)
+        w = limbs(C.root_of_unity(m2.bit_length() - 1), 4)
+        for e in (1, 3):
+            gen = limbs(pow(C.fr_generator, e, C.r), 4)
+            assert (c.groth16_witness_h(r1cs, z, w, gen) == g16.witness_map(w, gen)).all(), e
+        r1cs.free()
+        round_trip(*doms[0])
+    finally:
+        c.close()
 
 
 @pytest.mark.parametrize("curve", [0, 1])

@@ -23,20 +23,21 @@ def _run(exe, what, env_extra):
     return out.returncode, out.stdout
 
 
-@pytest.mark.parametrize("what", ["threads", "fuzz"])
+@pytest.mark.parametrize("what", ["threads", "fuzz", "table_cache"])
 def test_host_shim_under_asan_ubsan(what):
     rc, log = _run(_build("sanitize/sanitize_asan"), what, {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"})
     assert rc == 0 and "sanitize_main: ok" in log, log[-4000:]
     assert "AddressSanitizer" not in log and "runtime error" not in log and "LeakSanitizer" not in log, log[-4000:]
     if what == "fuzz":
         assert "blobs accepted" in log
-    else:
+    elif what == "threads":
         # the driver is built with ZK_PLACEHOLDER_PROFILING_ENABLED: the one reference profiler region that lies inside replaced code
         # (basic_fri.hpp:449) reports under the reference's name and format
         assert "Basic FRI Precommit time: " in log and " ms" in log
 
 
 def test_host_shim_under_tsan():
-    rc, log = _run(_build("sanitize/sanitize_tsan"), "threads", {"TSAN_OPTIONS": "halt_on_error=0"})
-    assert rc == 0 and "sanitize_main: ok" in log, log[-4000:]
-    assert "ThreadSanitizer" not in log, log[-4000:]
+    for what in ("threads", "table_cache"):
+        rc, log = _run(_build("sanitize/sanitize_tsan"), what, {"TSAN_OPTIONS": "halt_on_error=0"})
+        assert rc == 0 and "sanitize_main: ok" in log, log[-4000:]
+        assert "ThreadSanitizer" not in log, log[-4000:]
