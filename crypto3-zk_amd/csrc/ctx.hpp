@@ -9,11 +9,14 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <unordered_set>
+#include <utility>
 #include <vector>
 
 #include "../../include/zkhip.h"
+#include "options.hpp"
 #include "table_cache.hpp"
 
 #define ZK_HIP_CHECK(ctx, expr)                                                                  \
@@ -36,11 +39,76 @@ static constexpr int ZK_MSM_MAX_C = 21;  // largest Pippenger window (bits); 2^(
 // bits of the sticky device status word (kernels atomicOr them in; zkhip_device_status reports and clears)
 enum : uint32_t { ZK_STATUS_GATHER_RANGE = 1u, ZK_STATUS_MSM_PLAN_OVERFLOW = 2u, ZK_STATUS_LOOKUP_NOT_IN_TABLE = 4u, ZK_STATUS_LOOKUP_SORT_OVERFLOW = 8u };
 
+struct zkhip_ctx;
+
+// Owners of what the host holds on the device (last paragraph).  Each releases its resource when it goes out of scope, so a
+// handle or a table set frees itself and a function that returns early leaks nothing.
+// A device allocation:
+struct DevBuf {
+    uint32_t *p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) {
+            reset();
+            p = o.p;
+            o.p = nullptr;
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    void reset() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+    int alloc(zkhip_ctx *ctx, size_t bytes);  // 0, or ZKHIP_ERR_OOM with ctx->last_error set
+    operator uint32_t *() const { return p; }
+    template <class T>
+    T *as() const { return reinterpret_cast<T *>(p); }
+};
+// A buffer in device (or page-locked host) memory that is kept across calls and only grows:
+template <bool Pinned = false>
+struct GrowBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    GrowBuf() = default;
+    GrowBuf(const GrowBuf &) = delete;
+    GrowBuf &operator=(const GrowBuf &) = delete;
+    GrowBuf(GrowBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    ~GrowBuf() { reset(); }
+    void reset() {
+        if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        cap = 0;
+    }
+    // room for `bytes`; a buffer that is too small is replaced by one of bytes + slack once ctx's stream has drained
+    int reserve(zkhip_ctx *ctx, size_t bytes, size_t slack = 0);
+    template <class T>
+    T *as() const { return static_cast<T *>(p); }
+};
+// Events, a stream the context created itself, an instantiated graph:
+struct ZkHipDelete {
+    void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); }
+    void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); }
+    void operator()(hipGraphExec_t g) const { (void)hipGraphExecDestroy(g); }
+};
+using EventOwner = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, ZkHipDelete>;
+using StreamOwner = std::unique_ptr<std::remove_pointer_t<hipStream_t>, ZkHipDelete>;
+using GraphExecOwner = std::unique_ptr<std::remove_pointer_t<hipGraphExec_t>, ZkHipDelete>;
+inline hipError_t zk_event_create(EventOwner &e, unsigned flags = hipEventDefault) {
+    hipEvent_t raw = nullptr;
+    const hipError_t rc = hipEventCreateWithFlags(&raw, flags);
+    e.reset(raw);
+    return rc;
+}
+
 struct zkhip_bases {
     int curve, group;
     size_t n;
     size_t stride_u32;  // u32 words per affine point (2 * coordinate limbs)
-    uint32_t *d;        // nslots tables of n Montgomery-form affine points each, (0,0) = infinity;
+    DevBuf d;           // nslots tables of n Montgomery-form affine points each, (0,0) = infinity;
                         // the table of window w holds 2^off(w) P_i ("window tables": no Horner pass over the windows)
     int c_tab = 0, ntab = 1;  // window size the tables were built for (0: no tables) and the number of windows W
     // Window partition over GPUs: this object holds the tables of windows {w : w mod win_world == win_rank}
@@ -54,7 +122,7 @@ struct zkhip_bases {
 };
 
 struct ZkEventPair {
-    hipEvent_t a, b;
+    EventOwner a, b;
 };
 
 struct ZkProfile {
@@ -64,17 +132,6 @@ struct ZkProfile {
     std::vector<std::pair<std::string, ZkEventPair>> pending;
     std::vector<ZkEventPair> pool;
     std::map<std::string, std::pair<double, uint64_t>> acc;
-};
-
-// an owned device allocation, freed when it goes out of scope: a table set below frees itself, and a build that returns early leaks nothing
-struct DevBuf {
-    uint32_t *p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc((void **)&p, bytes); }
-    operator uint32_t *() const { return p; }
 };
 
 // The device tables a context keeps across calls (the caches at the end of zkhip_ctx; protocol: table_cache.hpp)
@@ -117,16 +174,16 @@ struct DomTables {  // a step / extended radix-2 domain, or the 1 / Z entry of a
 
 // a captured launch sequence (HIP graph) of one MSM / MSM batch, replayed when the same call comes again
 struct ZkGraph {
-    hipGraphExec_t exec = nullptr;
-    uint64_t ws_epoch = 0;   // the workspace allocation the graph's addresses refer to
-    void *d_ptrs = nullptr;  // batch: device array of the output pointers (kept with the graph)
+    GraphExecOwner exec;
+    uint64_t ws_epoch = 0;  // the workspace allocation the graph's addresses refer to
+    DevBuf d_ptrs;          // batch: device array of the output pointers (kept with the graph)
 };
 
 struct zkhip_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
-    bool own_stream = false;
-    hipEvent_t order_event = nullptr;  // zkhip_stream_wait: marks this context's stream for another context to wait on
+    StreamOwner own_stream;  // holds `stream` while it is the one the context created; empty on a borrowed stream (zkhip_set_stream)
+    EventOwner order_event;  // zkhip_stream_wait: marks this context's stream for another context to wait on
     std::string last_error;
     // zkhip_malloc / zkhip_free keep freed blocks for reuse (sizes rounded to 64 KiB; a request takes a cached block up to 1/8 larger):
     // the polynomial-layer chains allocate the same GB-class temporaries again and again, and a raw hipMalloc / hipFree pair costs
@@ -137,10 +194,10 @@ struct zkhip_ctx {
     size_t alloc_cached_bytes = 0, opt_alloc_cache_bytes = (size_t)16 << 30;
     std::mutex alloc_mutex;
     std::vector<uint32_t> lagrange_stage;  // host constants of zkhip_domain_lagrange_dev, alive until its copies ran
-    uint32_t *d_status = nullptr;  // sticky device-side error flags (ZK_STATUS_*), read and cleared by zkhip_device_status
+    DevBuf d_status;  // sticky device-side error flags (ZK_STATUS_*), read and cleared by zkhip_device_status
     // bump-allocated workspace, grown on demand, reused across calls
-    char *ws = nullptr;
-    size_t ws_cap = 0, ws_off = 0, ws_floor = 0;  // ws_floor: start of the per-call region (a batch parks data below it)
+    GrowBuf<> ws;
+    size_t ws_off = 0, ws_floor = 0;  // ws_floor: start of the per-call region (a batch parks data below it)
     std::unordered_set<const void *> lds_configured;  // kernels whose dynamic-LDS limit was raised on this context's device
     std::vector<uint64_t> lincomb_stage, lincomb_coeffs;  // host staging of zkhip_poly_lincomb_dev's tables
     std::vector<uint32_t> gate_stage;                     // host image of zkhip_gate_eval_dev's program
@@ -152,16 +209,12 @@ struct zkhip_ctx {
     bool capturing = false;
     void *batch_dptrs_override = nullptr;  // during a batch capture: the graph-owned output-pointer array
     int opt_msm_graphs = 0;  // off: replaying the captured launch sequence measured no faster than issuing it
-    uint32_t *msm_host_buf = nullptr;  // zkhip_msm (scalars in host memory): result + scalars on the device, kept across calls
-    size_t msm_host_cap = 0;
-    // pinned staging for small results
-    void *pinned = nullptr;
-    size_t pinned_cap = 0;
-    // options
+    GrowBuf<> msm_host_buf;  // zkhip_msm (scalars in host memory): result + scalars on the device, kept across calls
+    // options (each is a row of options.hpp)
     int opt_msm_window_bits = 0;
     int opt_msm_sets = 0;          // bucket sets S with window tables (entry (i, w) -> set w mod S); 0: from the lane target
     int opt_msm_sort_tile_log = 14;  // 14: 2^14-entry sort tiles (the MSM owns the GPU); 12: 2^12 (kernels of another context run alongside)
-    uint32_t opt_ec_ntt_table_lanes = 0;  // EC-NTT: lanes per multiplication launch = window tables held at once (0: as many as fit 1 GiB)
+    int opt_ec_ntt_table_lanes = 0;  // EC-NTT: lanes per multiplication launch = window tables held at once (0: as many as fit 1 GiB)
     int opt_msm_share_sort = 1;    // batches: consecutive members over the same scalars and table geometry share one sort (msm_same_entries)
     int opt_msm_tail_quads = 1;    // group law over lane quads in the tail of small bucket sets (fu_quad.hpp); 0: pairs everywhere
     int opt_msm_tail_fold = 16;    // two-level tail (msm_core.hpp: row / column sums of the bucket index, then the old tail over 2 sets of ~sqrt(B) buckets) for table-backed sets of >= 2^k buckets; 0: off
@@ -182,34 +235,19 @@ struct zkhip_ctx {
     TableCache<NttTables> ntt_tables{24};
     TableCache<NttExtTables> ntt_ext_tables{16};
     TableCache<DomTables> dom_tables{8};  // step / extended radix-2 domains and the basic domains' 1 / Z entries
-    char *dom_ws = nullptr;               // scratch of zkhip_domain_fft_dev (the NTTs inside it use `ws`)
-    size_t dom_ws_cap = 0;
+    GrowBuf<> dom_ws;                     // scratch of zkhip_domain_fft_dev (the NTTs inside it use `ws`)
+
+    zkhip_ctx() = default;
+    ~zkhip_ctx();  // zkhip.hip: the release order of everything above
 
     int ws_reserve(size_t bytes) {
-        if (bytes <= ws_cap) return 0;
+        if (bytes <= ws.cap) return 0;
         if (capturing) {  // growing means a synchronisation and new addresses: not inside a stream capture
             last_error = "workspace growth during graph capture";
             return ZKHIP_ERR_HIP;
         }
         ++ws_epoch;
-        if (ws) {
-            hipError_t e = hipStreamSynchronize(stream);
-            if (e != hipSuccess) {
-                last_error = hipGetErrorString(e);
-                return ZKHIP_ERR_HIP;
-            }
-            (void)hipFree(ws);
-            ws = nullptr;
-            ws_cap = 0;
-        }
-        size_t cap = bytes + (bytes >> 3) + (1 << 20);
-        hipError_t e = hipMalloc((void **)&ws, cap);
-        if (e != hipSuccess) {
-            last_error = std::string("hipMalloc(workspace): ") + hipGetErrorString(e);
-            return ZKHIP_ERR_OOM;
-        }
-        ws_cap = cap;
-        return 0;
+        return ws.reserve(this, bytes, (bytes >> 3) + (1 << 20));
     }
     void ws_reset() { ws_off = ws_floor; }
     static size_t ws_round(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
@@ -227,33 +265,57 @@ struct zkhip_ctx {
         prof.last_recorded = true;
         ZkEventPair ev;
         if (!prof.pool.empty()) {
-            ev = prof.pool.back();
+            ev = std::move(prof.pool.back());
             prof.pool.pop_back();
         } else {
-            (void)hipEventCreate(&ev.a);
-            (void)hipEventCreate(&ev.b);
+            (void)zk_event_create(ev.a);
+            (void)zk_event_create(ev.b);
         }
-        (void)hipEventRecord(ev.a, stream);
-        prof.pending.emplace_back(name, ev);
+        (void)hipEventRecord(ev.a.get(), stream);
+        prof.pending.emplace_back(name, std::move(ev));
     }
     void prof_end() {
         if (!prof.on || !prof.last_recorded) return;
-        (void)hipEventRecord(prof.pending.back().second.b, stream);
+        (void)hipEventRecord(prof.pending.back().second.b.get(), stream);
     }
     void prof_collect() {
         if (prof.pending.empty()) return;
         (void)hipStreamSynchronize(stream);
         for (auto &p : prof.pending) {
             float ms = 0;
-            (void)hipEventElapsedTime(&ms, p.second.a, p.second.b);
+            (void)hipEventElapsedTime(&ms, p.second.a.get(), p.second.b.get());
             auto &a = prof.acc[p.first];
             a.first += ms;
             a.second += 1;
-            prof.pool.push_back(p.second);
+            prof.pool.push_back(std::move(p.second));
         }
         prof.pending.clear();
     }
 };
+
+inline int DevBuf::alloc(zkhip_ctx *ctx, size_t bytes) {
+    reset();
+    const hipError_t e = hipMalloc((void **)&p, bytes);
+    if (e == hipSuccess) return 0;
+    (void)hipGetLastError();
+    ctx->last_error = "hipMalloc(" + std::to_string(bytes) + " bytes): " + hipGetErrorString(e);
+    return ZKHIP_ERR_OOM;
+}
+template <bool Pinned>
+int GrowBuf<Pinned>::reserve(zkhip_ctx *ctx, size_t bytes, size_t slack) {
+    if (bytes <= cap) return 0;
+    if (p) ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // nothing enqueued may still use the old buffer
+    reset();
+    const hipError_t e = Pinned ? hipHostMalloc(&p, bytes + slack, hipHostMallocPortable) : hipMalloc(&p, bytes + slack);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        p = nullptr;
+        ctx->last_error = std::string(Pinned ? "hipHostMalloc(" : "hipMalloc(") + std::to_string(bytes + slack) + " bytes): " + hipGetErrorString(e);
+        return ZKHIP_ERR_OOM;
+    }
+    cap = bytes + slack;
+    return 0;
+}
 
 // Workspace layouts.  A call declares its buffers ONCE, as an object with a member
 //     template <class Arena> void layout(Arena &a) { a.take(first, count); a.take(second, count); ... }
@@ -267,7 +329,7 @@ struct WsBump {
     zkhip_ctx *ctx;
     template <class T>
     void take(T *&p, size_t count) {
-        p = reinterpret_cast<T *>(ctx->ws + ctx->ws_off);
+        p = reinterpret_cast<T *>(ctx->ws.as<char>() + ctx->ws_off);
         ctx->ws_off += zkhip_ctx::ws_round(count * sizeof(T));
     }
 };
@@ -293,7 +355,7 @@ int ws_place(zkhip_ctx *ctx, Layout &l, size_t above = 0) {
     ctx->ws_reset();
     WsBump a{ctx};
     l.layout(a);
-    if (ctx->ws_off > end || end + above > ctx->ws_cap) {
+    if (ctx->ws_off > end || end + above > ctx->ws.cap) {
         ctx->last_error = "workspace layout took " + std::to_string(ctx->ws_off - ctx->ws_floor) + " bytes of " + std::to_string(end - ctx->ws_floor) + " reserved";
         return ZKHIP_ERR_RANGE;
     }
@@ -339,5 +401,3 @@ int zk_ntt_run(zkhip_ctx *ctx, int curve, uint32_t *d_data, size_t log_m, size_t
 int zk_ntt_extend(zkhip_ctx *ctx, int curve, uint32_t *d_coeffs, size_t log_m, size_t batch, const uint64_t *omega, uint32_t *d_out, size_t log_k,
                   const uint64_t *omega_big);
 int zk_msm_host_reserve(zkhip_ctx *ctx, size_t n);  // zkhip.hip: ctx->msm_host_buf holds 512 B of result + n scalars
-void zk_ntt_free_tables(zkhip_ctx *ctx);
-void zk_dom_free_tables(zkhip_ctx *ctx);

@@ -202,13 +202,6 @@ __global__ __launch_bounds__(64) void dom_zinv_table(int kind, const uint32_t *_
     e_store<U>(out, j, fu_cond_sub_p(fu_inv(z)));
 }
 
-void zk_dom_free_tables(zkhip_ctx *ctx) {
-    ctx->dom_tables.clear();
-    (void)hipFree(ctx->dom_ws);
-    ctx->dom_ws = nullptr;
-    ctx->dom_ws_cap = 0;
-}
-
 template <class U>
 static int dom_get_tables(zkhip_ctx *ctx, int curve, const ZkDomain &d, const uint64_t *coset, DomTables **out) {
     *out = ctx->dom_tables.find([&](const DomTables &t) {
@@ -246,8 +239,8 @@ static int dom_get_tables(zkhip_ctx *ctx, int curve, const ZkDomain &d, const ui
     t->has_coset = coset != nullptr;
     if (coset) memcpy(t->coset, coset, 32);
     const uint64_t one[4] = {1, 0, 0, 0};
-    ZK_HIP_CHECK(ctx, d_in.alloc(96));
-    ZK_HIP_CHECK(ctx, t->d_consts.alloc(DC_COUNT * 32));
+    ZK_TRY(d_in.alloc(ctx, 96));
+    ZK_TRY(t->d_consts.alloc(ctx, DC_COUNT * 32));
     ZK_HIP_CHECK(ctx, hipMemsetAsync(t->d_consts, 0, DC_COUNT * 32, ctx->stream));
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_in, d.omega, 32, hipMemcpyHostToDevice, ctx->stream));
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_in + 8, d.kind == ZKHIP_DOMAIN_EXTENDED_RADIX2 ? d.shift : one, 32, hipMemcpyHostToDevice, ctx->stream));
@@ -257,8 +250,8 @@ static int dom_get_tables(zkhip_ctx *ctx, int curve, const ZkDomain &d, const ui
         const size_t compr = d.n0 / d.n1;
         h_mul<U>(d.omega, d.omega, t->w0);
         h_pow<U>(d.omega, 2 * compr, t->w1);
-        ZK_HIP_CHECK(ctx, t->d_T.alloc(d.n0 * 32));
-        ZK_HIP_CHECK(ctx, t->d_Tinv.alloc(d.n1 * 32));
+        ZK_TRY(t->d_T.alloc(ctx, d.n0 * 32));
+        ZK_TRY(t->d_Tinv.alloc(ctx, d.n1 * 32));
         ZK_LAUNCH(ctx, "dom_setup", dom_pow_table<U>, dim3((unsigned)((d.n0 + 255) / 256)), dim3(256), 0, t->d_consts, (int)DC_BASE, (uint64_t)d.n0, t->d_T);
         ZK_LAUNCH(ctx, "dom_setup", dom_pow_table<U>, dim3((unsigned)((d.n1 + 255) / 256)), dim3(256), 0, t->d_consts, (int)DC_BASEINV, (uint64_t)d.n1, t->d_Tinv);
         t->nz = compr;
@@ -270,7 +263,7 @@ static int dom_get_tables(zkhip_ctx *ctx, int curve, const ZkDomain &d, const ui
         t->nz = 1;
     }
     if (coset) {
-        ZK_HIP_CHECK(ctx, t->d_zinv.alloc((t->nz + 1) * 32));
+        ZK_TRY(t->d_zinv.alloc(ctx, (t->nz + 1) * 32));
         ZK_LAUNCH(ctx, "dom_setup", dom_zinv_table<U>, dim3((unsigned)((t->nz + 1 + 63) / 64)), dim3(64), 0, d.kind, t->d_consts, (uint64_t)t->nz, t->d_zinv);
     }
     ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -545,8 +538,8 @@ static int dom_zinv_t(zkhip_ctx *ctx, int curve, const ZkDomain &d, const uint64
     memcpy(t->omega, d.omega, 32);
     t->has_coset = true;
     memcpy(t->coset, coset, 32);
-    ZK_HIP_CHECK(ctx, d_in.alloc(32));
-    ZK_HIP_CHECK(ctx, t->d_zinv.alloc(64));
+    ZK_TRY(d_in.alloc(ctx, 32));
+    ZK_TRY(t->d_zinv.alloc(ctx, 64));
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_in, coset, 32, hipMemcpyHostToDevice, ctx->stream));
     ZK_LAUNCH(ctx, "dom_setup", dom_zinv_basic<U>, dim3(1), dim3(64), 0, d_in, (uint64_t)d.m, t->d_zinv);
     ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -727,15 +720,8 @@ int zkhip_domain_fft_dev(zkhip_ctx *ctx, int curve, const zkhip_domain *dom, voi
     if (d.kind == ZKHIP_DOMAIN_BASIC_RADIX2) return zk_ntt_run(ctx, curve, (uint32_t *)d_data, ceil_log2(d.m), batch, d.omega, inverse, coset_gen);
     // split copy of the batch + the step domain's partial sums, in a scratch buffer the context keeps
     const size_t need = (batch * d.m + zk_dom_scratch_elems(d, batch)) * 32;
-    if (need > ctx->dom_ws_cap) {
-        ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->dom_ws);
-        ctx->dom_ws = nullptr;
-        ctx->dom_ws_cap = 0;
-        ZK_HIP_CHECK(ctx, hipMalloc((void **)&ctx->dom_ws, need + (need >> 3)));
-        ctx->dom_ws_cap = need + (need >> 3);
-    }
-    uint32_t *p0 = (uint32_t *)ctx->dom_ws, *p1 = p0 + batch * d.n0 * 8, *scratch = p1 + batch * d.n1 * 8;
+    ZK_TRY(ctx->dom_ws.reserve(ctx, need, need >> 3));
+    uint32_t *p0 = ctx->dom_ws.as<uint32_t>(), *p1 = p0 + batch * d.n0 * 8, *scratch = p1 + batch * d.n1 * 8;
     const uint64_t total = (uint64_t)batch * d.m;
     if (total >= ((uint64_t)1 << 39)) return ZKHIP_ERR_RANGE;
     const unsigned grid = (unsigned)((total + 255) / 256);

@@ -26,10 +26,8 @@ struct zkhip_r1cs {
     int dkind = ZKHIP_DOMAIN_BASIC_RADIX2;  // the evaluation domain's kind and split (domain.hpp): m = n0 + n1
     size_t n0 = 0, n1 = 0;
     // CSR, three matrices; coefficients in Montgomery form of the lazy Fr type (SL words each)
-    uint32_t *rowptr[3] = {nullptr, nullptr, nullptr};
-    uint32_t *col[3] = {nullptr, nullptr, nullptr};
-    uint32_t *coeff[3] = {nullptr, nullptr, nullptr};
-    uint32_t *long_rows[3] = {nullptr, nullptr, nullptr};  // rows with more than LONG_ROW terms
+    DevBuf rowptr[3], col[3], coeff[3];
+    DevBuf long_rows[3];  // rows with more than LONG_ROW terms
     uint32_t n_long[3] = {0, 0, 0};
     size_t nnz[3] = {0, 0, 0};
     size_t long_terms[3] = {0, 0, 0};  // total terms in long rows
@@ -187,9 +185,9 @@ static int r1cs_upload_t(zkhip_ctx *ctx, zkhip_r1cs *r, const uint32_t *const ro
     for (int k = 0; k < 3; ++k) {
         size_t nnz = rowptr[k][r->M];
         r->nnz[k] = nnz;
-        ZK_HIP_CHECK(ctx, hipMalloc((void **)&r->rowptr[k], (r->M + 1) * 4));
-        ZK_HIP_CHECK(ctx, hipMalloc((void **)&r->col[k], std::max<size_t>(1, nnz) * 4));
-        ZK_HIP_CHECK(ctx, hipMalloc((void **)&r->coeff[k], std::max<size_t>(1, nnz) * U::SL * 4));
+        ZK_TRY(r->rowptr[k].alloc(ctx, (r->M + 1) * 4));
+        ZK_TRY(r->col[k].alloc(ctx, std::max<size_t>(1, nnz) * 4));
+        ZK_TRY(r->coeff[k].alloc(ctx, std::max<size_t>(1, nnz) * U::SL * 4));
         ZK_HIP_CHECK(ctx, hipMemcpyAsync(r->rowptr[k], rowptr[k], (r->M + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
         std::vector<uint32_t> lr;
         for (size_t i = 0; i < r->M; ++i) {
@@ -203,17 +201,16 @@ static int r1cs_upload_t(zkhip_ctx *ctx, zkhip_r1cs *r, const uint32_t *const ro
             if (col[k][j] > r->N) return ZKHIP_ERR_RANGE;
         r->n_long[k] = (uint32_t)lr.size();
         if (!lr.empty()) {
-            ZK_HIP_CHECK(ctx, hipMalloc((void **)&r->long_rows[k], lr.size() * 4));
+            ZK_TRY(r->long_rows[k].alloc(ctx, lr.size() * 4));
             ZK_HIP_CHECK(ctx, hipMemcpyAsync(r->long_rows[k], lr.data(), lr.size() * 4, hipMemcpyHostToDevice, ctx->stream));
         }
         if (nnz) {
-            uint32_t *d_c = nullptr;
-            ZK_HIP_CHECK(ctx, hipMalloc((void **)&d_c, nnz * 32));
+            DevBuf d_c;  // the canonical coefficients, until the conversion below has run
+            ZK_TRY(d_c.alloc(ctx, nnz * 32));
             ZK_HIP_CHECK(ctx, hipMemcpyAsync(r->col[k], col[k], nnz * 4, hipMemcpyHostToDevice, ctx->stream));
             ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_c, coeff[k], nnz * 32, hipMemcpyHostToDevice, ctx->stream));
             ZK_LAUNCH(ctx, "r1cs_coeff_to_mont", r1cs_coeff_to_mont<U>, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, d_c, nnz, r->coeff[k]);
             ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-            (void)hipFree(d_c);
         }
         ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     }
@@ -279,7 +276,7 @@ int zkhip_r1cs_upload(zkhip_ctx *ctx, int curve, size_t num_constraints, size_t 
     if (curve != CURVE_BLS12_381 && curve != CURVE_BN254) return ZKHIP_ERR_INVALID;
     if (num_inputs > num_variables || num_constraints == 0 || num_constraints >= (1ull << 31)) return ZKHIP_ERR_RANGE;
     ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    zkhip_r1cs *r = new zkhip_r1cs();
+    std::unique_ptr<zkhip_r1cs> r(new zkhip_r1cs());
     r->curve = curve;
     r->M = num_constraints;
     r->n = num_inputs;
@@ -289,19 +286,12 @@ int zkhip_r1cs_upload(zkhip_ctx *ctx, int curve, size_t num_constraints, size_t 
     {
         int kind = 0;
         size_t m = 0;
-        if (!zk_dom_choice(r->M + r->n + 1, (size_t)zk_dom_two_adicity(curve), &kind, &m) || r1cs_shape(r, kind, m) != ZKHIP_OK) {
-            delete r;
-            return ZKHIP_ERR_RANGE;
-        }
+        if (!zk_dom_choice(r->M + r->n + 1, (size_t)zk_dom_two_adicity(curve), &kind, &m) || r1cs_shape(r.get(), kind, m) != ZKHIP_OK) return ZKHIP_ERR_RANGE;
     }
     const uint32_t *rp[3] = {rowptr_a, rowptr_b, rowptr_c}, *cl[3] = {col_a, col_b, col_c};
     const uint64_t *cf[3] = {coeff_a, coeff_b, coeff_c};
-    int rc = curve == CURVE_BLS12_381 ? r1cs_upload_t<BlsFrU>(ctx, r, rp, cl, cf) : r1cs_upload_t<BnFrU>(ctx, r, rp, cl, cf);
-    if (rc) {
-        zkhip_r1cs_free(ctx, r);
-        return rc;
-    }
-    *out = r;
+    ZK_TRY(curve == CURVE_BLS12_381 ? r1cs_upload_t<BlsFrU>(ctx, r.get(), rp, cl, cf) : r1cs_upload_t<BnFrU>(ctx, r.get(), rp, cl, cf));
+    *out = r.release();
     return ZKHIP_OK;
 }
 
@@ -310,12 +300,6 @@ void zkhip_r1cs_free(zkhip_ctx *ctx, zkhip_r1cs *r) {
     if (ctx) {
         (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);
-    }
-    for (int k = 0; k < 3; ++k) {
-        (void)hipFree(r->rowptr[k]);
-        (void)hipFree(r->col[k]);
-        (void)hipFree(r->coeff[k]);
-        (void)hipFree(r->long_rows[k]);
     }
     delete r;
 }

@@ -80,7 +80,7 @@ RcclApi *rccl_api(std::string &err) {
 }  // namespace
 
 struct zkhip_device_group {
-    std::vector<zkhip_ctx *> members;
+    std::vector<zkhip_ctx *> members;  // destroyed by the group, after everything below
     std::vector<int> devices;
     bool distinct = true;  // pairwise distinct devices (what RCCL needs)
     int transport_req = ZKHIP_GROUP_AUTO, transport = ZKHIP_GROUP_AUTO;
@@ -88,16 +88,15 @@ struct zkhip_device_group {
     // RCCL
     RcclApi *rccl = nullptr;
     std::vector<ncclComm_t> comms;
-    std::vector<void *> rccl_recv;  // per member: where an all-gather lands when the caller gave no receive buffer (RCCL needs one on every rank)
-    size_t rccl_recv_cap = 0;
+    std::vector<GrowBuf<>> rccl_recv;  // per member: where an all-gather lands when the caller gave no receive buffer (RCCL needs one on every rank)
     // PEER: one event per member marks "this member's stream up to here"
-    std::vector<hipEvent_t> ev;
+    std::vector<EventOwner> ev;
     // STAGED
-    void *h_stage = nullptr;
-    size_t h_stage_cap = 0;
+    GrowBuf<true> h_stage;
     // zkhip_group_msm: partial sums (member k: 512 B at d_part[k]), the gathered sums and the fold on member 0
-    std::vector<void *> d_part;
-    void *d_all = nullptr;
+    std::vector<DevBuf> d_part;
+    DevBuf d_all;
+    ~zkhip_device_group();
 };
 
 struct zkhip_group_bases {
@@ -164,14 +163,32 @@ static int resolve_transport(zkhip_device_group *g) {
     return ZKHIP_OK;
 }
 
+// the staging buffer is page-locked for every device; member 0's stream stands for "whoever used it last" (every user drains before it returns)
 static int stage_reserve(zkhip_device_group *g, size_t bytes) {
-    if (bytes <= g->h_stage_cap) return ZKHIP_OK;
-    if (g->h_stage) (void)hipHostFree(g->h_stage);
-    g->h_stage = nullptr;
-    g->h_stage_cap = 0;
-    ZK_GROUP_HIP(g, hipHostMalloc(&g->h_stage, bytes, hipHostMallocPortable));
-    g->h_stage_cap = bytes;
+    ZK_GROUP_TRY(g, g->members[0], g->h_stage.reserve(g->members[0], bytes));
     return ZKHIP_OK;
+}
+
+// Every member's stream drains, the communicators go, then each member's event and buffers with ITS device current, the shared buffers, and
+// the member contexts last.  The per-member vectors have one (possibly empty) owner per requested member from the start of zkhip_group_init.
+zkhip_device_group::~zkhip_device_group() {
+    for (size_t k = 0; k < members.size(); ++k) {
+        (void)hipSetDevice(devices[k]);
+        (void)hipStreamSynchronize(members[k]->stream);
+    }
+    if (rccl)
+        for (ncclComm_t c : comms)
+            if (c) (void)rccl->CommDestroy(c);
+    for (size_t k = 0; k < members.size(); ++k) {
+        (void)hipSetDevice(devices[k]);
+        ev[k].reset();
+        d_part[k].reset();
+        rccl_recv[k].reset();
+    }
+    if (!devices.empty()) (void)hipSetDevice(devices[0]);  // d_all lives on member 0's device
+    d_all.reset();
+    h_stage.reset();
+    for (zkhip_ctx *c : members) zkhip_destroy(c);
 }
 
 extern "C" {
@@ -181,28 +198,23 @@ int zkhip_group_init(const int *device_ids, int n_dev, zkhip_device_group **out)
     *out = nullptr;
     if (!device_ids || n_dev < 1 || n_dev > 64) return ZKHIP_ERR_INVALID;
     std::unique_ptr<zkhip_device_group> g(new zkhip_device_group());
-    int rc = ZKHIP_OK;
-    for (int k = 0; k < n_dev && rc == ZKHIP_OK; ++k) {
+    g->ev.resize(n_dev);
+    g->d_part.resize(n_dev);
+    g->rccl_recv.resize(n_dev);
+    for (int k = 0; k < n_dev; ++k) {
         zkhip_ctx *c = nullptr;
-        rc = zkhip_init(device_ids[k], &c);
-        if (rc != ZKHIP_OK) break;
+        ZK_TRY(zkhip_init(device_ids[k], &c));
         g->members.push_back(c);
         g->devices.push_back(device_ids[k]);
         for (int j = 0; j < k; ++j)
             if (device_ids[j] == device_ids[k]) g->distinct = false;
     }
-    for (size_t k = 0; k < g->members.size() && rc == ZKHIP_OK; ++k) {
-        hipEvent_t e = nullptr;
-        void *p = nullptr;
-        if (hipSetDevice(g->devices[k]) != hipSuccess || hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) rc = ZKHIP_ERR_HIP;
-        else if (hipMalloc(&p, 512) != hipSuccess) rc = ZKHIP_ERR_OOM;
-        if (e) g->ev.push_back(e);
-        if (p) g->d_part.push_back(p);
+    for (int k = 0; k < n_dev; ++k) {
+        if (hipSetDevice(g->devices[k]) != hipSuccess || zk_event_create(g->ev[k], hipEventDisableTiming) != hipSuccess) return ZKHIP_ERR_HIP;
+        ZK_TRY(g->d_part[k].alloc(g->members[k], 512));
     }
-    if (rc == ZKHIP_OK) {
-        if (hipSetDevice(g->devices[0]) != hipSuccess || hipMalloc(&g->d_all, 512 * (size_t)n_dev + 512) != hipSuccess) rc = ZKHIP_ERR_OOM;
-    }
-    if (rc == ZKHIP_OK && g->distinct && n_dev > 1) {
+    if (hipSetDevice(g->devices[0]) != hipSuccess || g->d_all.alloc(g->members[0], 512 * (size_t)n_dev + 512) != 0) return ZKHIP_ERR_OOM;
+    if (g->distinct && n_dev > 1) {
         // direct xGMI copies between the members' memories (hipMemcpyPeerAsync works without it, through the host); "already enabled" and
         // "not supported" are both fine here
         for (int a = 0; a < n_dev; ++a) {
@@ -215,34 +227,11 @@ int zkhip_group_init(const int *device_ids, int n_dev, zkhip_device_group **out)
         }
         (void)hipGetLastError();
     }
-    if (rc != ZKHIP_OK) {
-        zkhip_group_destroy(g.release());
-        return rc;
-    }
     *out = g.release();
     return ZKHIP_OK;
 }
 
-void zkhip_group_destroy(zkhip_device_group *g) {
-    if (!g) return;
-    for (size_t k = 0; k < g->members.size(); ++k) {
-        (void)hipSetDevice(g->devices[k]);
-        (void)hipStreamSynchronize(g->members[k]->stream);
-    }
-    if (g->rccl)
-        for (ncclComm_t c : g->comms)
-            if (c) (void)g->rccl->CommDestroy(c);
-    for (size_t k = 0; k < g->members.size(); ++k) {
-        (void)hipSetDevice(g->devices[k]);
-        if (k < g->ev.size()) (void)hipEventDestroy(g->ev[k]);
-        if (k < g->d_part.size()) (void)hipFree(g->d_part[k]);
-        if (k < g->rccl_recv.size() && g->rccl_recv[k]) (void)hipFree(g->rccl_recv[k]);
-    }
-    if (g->d_all) (void)hipFree(g->d_all);
-    if (g->h_stage) (void)hipHostFree(g->h_stage);
-    for (zkhip_ctx *c : g->members) zkhip_destroy(c);
-    delete g;
-}
+void zkhip_group_destroy(zkhip_device_group *g) { delete g; }
 
 int zkhip_group_size(const zkhip_device_group *g) { return g ? (int)g->members.size() : 0; }
 zkhip_ctx *zkhip_group_ctx(const zkhip_device_group *g, int member) {
@@ -276,20 +265,18 @@ int zkhip_group_all_gather(zkhip_device_group *g, const void *const *d_send, voi
         // every rank of an RCCL all-gather receives: members without a buffer of the caller's land in one the group keeps
         bool need_own = false;
         for (size_t k = 0; k < n; ++k) need_own = need_own || !d_recv[k];
-        if (need_own && g->rccl_recv_cap < n * bytes) {
+        bool grow = false;  // any member's: a growth that failed half-way is taken up again by the next call
+        for (size_t k = 0; k < n; ++k) grow = grow || g->rccl_recv[k].cap < n * bytes;
+        if (need_own && grow) {
             ZK_TRY(zkhip_group_sync(g));
-            g->rccl_recv.resize(n, nullptr);
             for (size_t k = 0; k < n; ++k) {
                 ZK_GROUP_HIP(g, hipSetDevice(g->devices[k]));
-                if (g->rccl_recv[k]) (void)hipFree(g->rccl_recv[k]);
-                g->rccl_recv[k] = nullptr;
-                ZK_GROUP_HIP(g, hipMalloc(&g->rccl_recv[k], n * bytes));
+                ZK_GROUP_TRY(g, g->members[k], g->rccl_recv[k].reserve(g->members[k], n * bytes));
             }
-            g->rccl_recv_cap = n * bytes;
         }
         ncclResult_t r = g->rccl->GroupStart();
         for (size_t k = 0; k < n && r == ncclSuccess; ++k)
-            r = g->rccl->AllGather(d_send[k], d_recv[k] ? d_recv[k] : g->rccl_recv[k], bytes, ncclUint8, g->comms[k], g->members[k]->stream);
+            r = g->rccl->AllGather(d_send[k], d_recv[k] ? d_recv[k] : g->rccl_recv[k].p, bytes, ncclUint8, g->comms[k], g->members[k]->stream);
         const ncclResult_t r2 = g->rccl->GroupEnd();
         if (r != ncclSuccess || r2 != ncclSuccess) {
             g->last_error = std::string("ncclAllGather: ") + g->rccl->GetErrorString(r != ncclSuccess ? r : r2);
@@ -301,13 +288,13 @@ int zkhip_group_all_gather(zkhip_device_group *g, const void *const *d_send, voi
         ZK_TRY(stage_reserve(g, n * bytes));
         for (size_t k = 0; k < n; ++k) {
             ZK_GROUP_HIP(g, hipSetDevice(g->devices[k]));
-            ZK_GROUP_HIP(g, hipMemcpyAsync(static_cast<char *>(g->h_stage) + k * bytes, d_send[k], bytes, hipMemcpyDeviceToHost, g->members[k]->stream));
+            ZK_GROUP_HIP(g, hipMemcpyAsync(g->h_stage.as<char>() + k * bytes, d_send[k], bytes, hipMemcpyDeviceToHost, g->members[k]->stream));
         }
         for (size_t k = 0; k < n; ++k) ZK_GROUP_HIP(g, hipStreamSynchronize(g->members[k]->stream));
         for (size_t k = 0; k < n; ++k)
             if (d_recv[k]) {
                 ZK_GROUP_HIP(g, hipSetDevice(g->devices[k]));
-                ZK_GROUP_HIP(g, hipMemcpyAsync(d_recv[k], g->h_stage, n * bytes, hipMemcpyHostToDevice, g->members[k]->stream));
+                ZK_GROUP_HIP(g, hipMemcpyAsync(d_recv[k], g->h_stage.p, n * bytes, hipMemcpyHostToDevice, g->members[k]->stream));
             }
         // the staging buffer is the group's: the copies out of it have finished before the next exchange may fill it again
         for (size_t k = 0; k < n; ++k)
@@ -317,14 +304,14 @@ int zkhip_group_all_gather(zkhip_device_group *g, const void *const *d_send, voi
     // PEER: every source stream is marked, every receiving stream waits for the marks and pulls
     for (size_t k = 0; k < n; ++k) {
         ZK_GROUP_HIP(g, hipSetDevice(g->devices[k]));
-        ZK_GROUP_HIP(g, hipEventRecord(g->ev[k], g->members[k]->stream));
+        ZK_GROUP_HIP(g, hipEventRecord(g->ev[k].get(), g->members[k]->stream));
     }
     for (size_t j = 0; j < n; ++j) {
         if (!d_recv[j]) continue;
         ZK_GROUP_HIP(g, hipSetDevice(g->devices[j]));
         hipStream_t s = g->members[j]->stream;
         for (size_t k = 0; k < n; ++k) {
-            if (k != j) ZK_GROUP_HIP(g, hipStreamWaitEvent(s, g->ev[k], 0));
+            if (k != j) ZK_GROUP_HIP(g, hipStreamWaitEvent(s, g->ev[k].get(), 0));
             char *dst = static_cast<char *>(d_recv[j]) + k * bytes;
             // the peer form also between members that share a GPU: the call a multi-GPU box makes is the call the one-GPU tests make
             ZK_GROUP_HIP(g, hipMemcpyPeerAsync(dst, g->devices[j], d_send[k], g->devices[k], bytes, s));
@@ -342,19 +329,19 @@ int zkhip_group_copy(zkhip_device_group *g, int dst_member, void *d_dst, int src
     if (g->transport == ZKHIP_GROUP_STAGED && src != dst) {  // through the host whatever the devices: the fallback is the same code on every box (and testable on one GPU)
         ZK_TRY(stage_reserve(g, bytes));
         ZK_GROUP_HIP(g, hipSetDevice(src->device));
-        ZK_GROUP_HIP(g, hipMemcpyAsync(g->h_stage, d_src, bytes, hipMemcpyDeviceToHost, src->stream));
+        ZK_GROUP_HIP(g, hipMemcpyAsync(g->h_stage.p, d_src, bytes, hipMemcpyDeviceToHost, src->stream));
         ZK_GROUP_HIP(g, hipStreamSynchronize(src->stream));
         ZK_GROUP_HIP(g, hipSetDevice(dst->device));
-        ZK_GROUP_HIP(g, hipMemcpyAsync(d_dst, g->h_stage, bytes, hipMemcpyHostToDevice, dst->stream));
+        ZK_GROUP_HIP(g, hipMemcpyAsync(d_dst, g->h_stage.p, bytes, hipMemcpyHostToDevice, dst->stream));
         ZK_GROUP_HIP(g, hipStreamSynchronize(dst->stream));
         return ZKHIP_OK;
     }
     if (src != dst) {
         ZK_GROUP_HIP(g, hipSetDevice(src->device));
-        ZK_GROUP_HIP(g, hipEventRecord(g->ev[src_member], src->stream));
+        ZK_GROUP_HIP(g, hipEventRecord(g->ev[src_member].get(), src->stream));
     }
     ZK_GROUP_HIP(g, hipSetDevice(dst->device));
-    if (src != dst) ZK_GROUP_HIP(g, hipStreamWaitEvent(dst->stream, g->ev[src_member], 0));
+    if (src != dst) ZK_GROUP_HIP(g, hipStreamWaitEvent(dst->stream, g->ev[src_member].get(), 0));
     ZK_GROUP_HIP(g, hipMemcpyPeerAsync(d_dst, dst->device, d_src, src->device, bytes, dst->stream));
     return ZKHIP_OK;
 }
@@ -424,11 +411,11 @@ int zkhip_group_msm(zkhip_device_group *g, const zkhip_group_bases *bases, size_
         const size_t lo = std::max(bases->first[k], offset), hi = std::min(bases->first[k + 1], offset + n), cnt = hi > lo ? hi - lo : 0;
         ZK_GROUP_HIP(g, hipSetDevice(c->device));
         ZK_GROUP_TRY(g, c, zk_msm_host_reserve(c, cnt));
-        uint32_t *d_s = c->msm_host_buf + 128;
+        uint32_t *d_s = c->msm_host_buf.as<uint32_t>() + 128;
         if (cnt) ZK_GROUP_HIP(g, hipMemcpyAsync(d_s, scalars + 4 * (lo - offset), cnt * 32, hipMemcpyHostToDevice, c->stream));
         // an empty slice yields the point at infinity (Z = 0) like any empty multiexp
-        ZK_GROUP_TRY(g, c, zk_msm_run(c, bases->member[k], cnt ? lo - bases->first[k] : 0, cnt, d_s, static_cast<uint32_t *>(g->d_part[k])));
-        send[k] = g->d_part[k];
+        ZK_GROUP_TRY(g, c, zk_msm_run(c, bases->member[k], cnt ? lo - bases->first[k] : 0, cnt, d_s, g->d_part[k]));
+        send[k] = g->d_part[k].p;
     }
     zkhip_ctx *root = g->members[0];
     if (world == 1) {
@@ -436,11 +423,11 @@ int zkhip_group_msm(zkhip_device_group *g, const zkhip_group_bases *bases, size_
         ZK_GROUP_HIP(g, hipStreamSynchronize(root->stream));
         return ZKHIP_OK;
     }
-    recv[0] = g->d_all;
+    recv[0] = g->d_all.p;
     ZK_TRY(zkhip_group_all_gather(g, send.data(), recv.data(), obytes));
     ZK_GROUP_HIP(g, hipSetDevice(root->device));
-    uint32_t *d_sum = reinterpret_cast<uint32_t *>(static_cast<char *>(g->d_all) + 512 * world);
-    ZK_GROUP_TRY(g, root, zk_jac_sum(root, bases->curve, bases->group, static_cast<const uint32_t *>(g->d_all), world, d_sum));
+    uint32_t *d_sum = g->d_all + 128 * world;
+    ZK_GROUP_TRY(g, root, zk_jac_sum(root, bases->curve, bases->group, g->d_all, world, d_sum));
     ZK_GROUP_HIP(g, hipMemcpyAsync(out_jacobian, d_sum, obytes, hipMemcpyDeviceToHost, root->stream));
     // every member's stream drains: its d_part may be overwritten by the next call, and a failed member must not go unnoticed
     for (size_t k = 0; k < world; ++k) ZK_GROUP_HIP(g, hipStreamSynchronize(g->members[k]->stream));

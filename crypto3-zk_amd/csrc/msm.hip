@@ -113,11 +113,7 @@ static int zk_msm_run_direct(zkhip_ctx *ctx, const zkhip_bases *bases, size_t of
 // dependent kernels are on the device side, not in the host's launch path) -- so the option "msm_graphs" is OFF by
 // default; the path stays for runtimes where graph launches are cheaper, and is covered by the GPU tests.
 void zk_graphs_clear(zkhip_ctx *ctx) {
-    for (auto &g : ctx->graphs) {
-        if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
-        if (g.second.d_ptrs) (void)hipFree(g.second.d_ptrs);
-    }
-    ctx->graphs.clear();
+    ctx->graphs.clear();  // each entry destroys its graph and frees its pointer array
     ctx->graph_seen.clear();
 }
 
@@ -127,7 +123,7 @@ static void key_add(std::string &k, const T &v) {
 }
 static void key_add_bases(std::string &k, const zkhip_bases *b) {
     key_add(k, b);
-    key_add(k, b->d);
+    key_add(k, b->d.p);
     key_add(k, b->n);
     key_add(k, b->c_tab);
     key_add(k, b->ntab);
@@ -139,15 +135,8 @@ static void key_add_bases(std::string &k, const zkhip_bases *b) {
 static std::string key_begin(zkhip_ctx *ctx, char kind) {
     std::string k(1, kind);
     key_add(k, ctx->stream);
-    key_add(k, ctx->opt_msm_window_bits);
-    key_add(k, ctx->opt_msm_segment_log);
-    key_add(k, ctx->opt_msm_sets);
-    key_add(k, ctx->opt_msm_tail_quads);
-    key_add(k, ctx->opt_msm_tail_fold);
-    key_add(k, ctx->opt_msm_fold_run);
-    key_add(k, ctx->opt_msm_tail_fold_g2);
-    key_add(k, ctx->opt_msm_share_sort);
-    key_add(k, ctx->opt_msm_sort_tile_log);  // the captured launch sequence depends on the sort's tile shape
+    for (const OptRow<zkhip_ctx> &r : zk_options<zkhip_ctx>)
+        if (r.msm_graph_key) key_add(k, ctx->*r.member);
     return k;
 }
 
@@ -157,48 +146,42 @@ static int zk_graph_run(zkhip_ctx *ctx, const std::string &key, Enqueue &&enqueu
     auto it = ctx->graphs.find(key);
     if (it != ctx->graphs.end()) {
         if (it->second.ws_epoch == ctx->ws_epoch) {
-            ZK_HIP_CHECK(ctx, hipGraphLaunch(it->second.exec, ctx->stream));
+            ZK_HIP_CHECK(ctx, hipGraphLaunch(it->second.exec.get(), ctx->stream));
             return 0;
         }
-        (void)hipGraphExecDestroy(it->second.exec);  // the workspace moved: recapture below
-        if (it->second.d_ptrs) (void)hipFree(it->second.d_ptrs);
-        ctx->graphs.erase(it);
+        ctx->graphs.erase(it);  // the workspace moved: recapture below
     }
     int &seen = ctx->graph_seen[key];
     if (seen < 0 || ++seen < 3) return enqueue();
     if (ctx->graphs.size() >= 64) zk_graphs_clear(ctx);
     ZkGraph g;
-    if (nptrs) {
-        if (hipMalloc(&g.d_ptrs, nptrs * sizeof(void *)) != hipSuccess) return enqueue();
-        if (hipMemcpy(g.d_ptrs, ptrs, nptrs * sizeof(void *), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(g.d_ptrs);
-            return enqueue();
-        }
-    }
+    // a failure here is no error of the call (it runs uncaptured): allocated without DevBuf::alloc, which would leave its message in last_error
+    if (nptrs && (hipMalloc((void **)&g.d_ptrs.p, nptrs * sizeof(void *)) != hipSuccess || hipMemcpy(g.d_ptrs, ptrs, nptrs * sizeof(void *), hipMemcpyHostToDevice) != hipSuccess))
+        return enqueue();
     if (hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-        if (g.d_ptrs) (void)hipFree(g.d_ptrs);
         ctx->graph_seen[key] = -1;
         return enqueue();
     }
     ctx->capturing = true;
-    ctx->batch_dptrs_override = g.d_ptrs;
+    ctx->batch_dptrs_override = g.d_ptrs.p;
     const int rc = enqueue();
     ctx->batch_dptrs_override = nullptr;
     ctx->capturing = false;
     hipGraph_t graph = nullptr;
     const hipError_t e_end = hipStreamEndCapture(ctx->stream, &graph);
     bool ok = rc == 0 && e_end == hipSuccess && graph != nullptr;
-    if (ok) ok = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0) == hipSuccess;
+    hipGraphExec_t exec = nullptr;
+    if (ok) ok = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
+    g.exec.reset(exec);
     if (graph) (void)hipGraphDestroy(graph);
     if (!ok) {  // nothing ran during the capture: do it directly, and stop trying for this call shape
         (void)hipGetLastError();
-        if (g.d_ptrs) (void)hipFree(g.d_ptrs);
         ctx->graph_seen[key] = -1;
         return enqueue();
     }
     g.ws_epoch = ctx->ws_epoch;
-    ctx->graphs[key] = g;
-    ZK_HIP_CHECK(ctx, hipGraphLaunch(g.exec, ctx->stream));
+    ctx->graphs[key] = std::move(g);
+    ZK_HIP_CHECK(ctx, hipGraphLaunch(exec, ctx->stream));
     return 0;
 }
 

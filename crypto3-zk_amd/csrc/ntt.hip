@@ -385,11 +385,6 @@ __global__ __launch_bounds__(256) void ntt_pass(NttPass p) {
 }
 
 // ---- host side ------------------------------------------------------------------------------------
-void zk_ntt_free_tables(zkhip_ctx *ctx) {
-    ctx->ntt_tables.clear();
-    ctx->ntt_ext_tables.clear();
-}
-
 // the radix plan: log_m split into np nearly equal radices (larger first), tile widths
 struct NttPlan {
     int np;
@@ -434,11 +429,11 @@ static int ntt_get_tables(zkhip_ctx *ctx, int curve, size_t log_m, const uint64_
     const uint32_t nhi = (uint32_t)(((size_t)1 << log_m) >> t->lo_bits) + 1;
     const size_t eb = U::SL * 4;  // bytes per power-table entry
     const size_t m = (size_t)1 << log_m;
-    ZK_HIP_CHECK(ctx, d_in.alloc(64));
-    ZK_HIP_CHECK(ctx, t->d_base.alloc(2 * eb));
-    ZK_HIP_CHECK(ctx, t->d_scale.alloc(eb));
-    ZK_HIP_CHECK(ctx, t->d_lo.alloc((size_t)nlo * eb));
-    ZK_HIP_CHECK(ctx, t->d_hi.alloc((size_t)nhi * eb));
+    ZK_TRY(d_in.alloc(ctx, 64));
+    ZK_TRY(t->d_base.alloc(ctx, 2 * eb));
+    ZK_TRY(t->d_scale.alloc(ctx, eb));
+    ZK_TRY(t->d_lo.alloc(ctx, (size_t)nlo * eb));
+    ZK_TRY(t->d_hi.alloc(ctx, (size_t)nhi * eb));
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_in, omega, 32, hipMemcpyHostToDevice, ctx->stream));
     if (coset) ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_in + 8, coset, 32, hipMemcpyHostToDevice, ctx->stream));
     ZK_LAUNCH(ctx, "ntt_setup", ntt_setup<U>, dim3(1), dim3(64), 0, d_in, coset ? d_in + 8 : (const uint32_t *)nullptr, inverse,
@@ -447,13 +442,13 @@ static int ntt_get_tables(zkhip_ctx *ctx, int curve, size_t log_m, const uint64_
     ZK_LAUNCH(ctx, "ntt_pow_table", ntt_pow_table<U>, dim3((nhi + 255) / 256), dim3(256), 0, t->d_base, nhi, (uint32_t)t->lo_bits, t->d_hi);
     const unsigned gm = (unsigned)((m + 255) / 256);
     if (coset) {
-        ZK_HIP_CHECK(ctx, t->d_clo.alloc((size_t)nlo * eb));
-        ZK_HIP_CHECK(ctx, t->d_chi.alloc((size_t)nhi * eb));
+        ZK_TRY(t->d_clo.alloc(ctx, (size_t)nlo * eb));
+        ZK_TRY(t->d_chi.alloc(ctx, (size_t)nhi * eb));
         ZK_LAUNCH(ctx, "ntt_pow_table", ntt_pow_table<U>, dim3((nlo + 255) / 256), dim3(256), 0, t->d_base + U::SL, nlo, 0u, t->d_clo);
         ZK_LAUNCH(ctx, "ntt_pow_table", ntt_pow_table<U>, dim3((nhi + 255) / 256), dim3(256), 0, t->d_base + U::SL, nhi, (uint32_t)t->lo_bits,
                   t->d_chi);
         // g^i while loading (forward) / (1/m) g^-i while storing (inverse): one entry per index
-        ZK_HIP_CHECK(ctx, t->d_prepost.alloc(m * 36));
+        ZK_TRY(t->d_prepost.alloc(ctx, m * 36));
         ZK_LAUNCH(ctx, "ntt_build_tw", ntt_build_powers<U>, dim3(gm), dim3(256), 0, t->d_clo, t->d_chi, (uint32_t)t->lo_bits, (uint32_t)log_m,
                   inverse ? t->d_scale : (const uint32_t *)nullptr, t->d_prepost);
     }
@@ -463,7 +458,7 @@ static int ntt_get_tables(zkhip_ctx *ctx, int curve, size_t log_m, const uint64_
     uint32_t log_ns = 0;
     for (int i = 0; i < pl.np; ++i) {
         const uint32_t s = (uint32_t)pl.sv[i], half = std::max<uint32_t>(1, (1u << s) / 2);
-        ZK_HIP_CHECK(ctx, t->d_stage[i].alloc((size_t)half * eb));
+        ZK_TRY(t->d_stage[i].alloc(ctx, (size_t)half * eb));
         ZK_LAUNCH(ctx, "ntt_build_tw", ntt_build_stage<U>, dim3((half + 255) / 256), dim3(256), 0, t->d_lo, t->d_hi, (uint32_t)t->lo_bits,
                   (uint32_t)log_m - s, half, t->d_stage[i]);
         if (i + 1 < pl.np) {
@@ -476,7 +471,7 @@ static int ntt_get_tables(zkhip_ctx *ctx, int curve, size_t log_m, const uint64_
             g.hi = t->d_hi;
             g.lo_bits = (uint32_t)t->lo_bits;
             g.scale = (inverse && !coset && i == 0) ? t->d_scale : nullptr;
-            ZK_HIP_CHECK(ctx, t->d_tw[i].alloc(m * 36));
+            ZK_TRY(t->d_tw[i].alloc(ctx, m * 36));
             ZK_LAUNCH(ctx, "ntt_build_tw", ntt_build_tw<U>, dim3(gm), dim3(256), 0, g, t->d_tw[i]);
         }
         log_ns += s;
@@ -639,8 +634,8 @@ static int ntt_extend_t(zkhip_ctx *ctx, int curve, uint32_t *d_coeffs, size_t lo
         built->log_m = log_m;
         built->log_k = log_k;
         memcpy(built->omega_big, omega_big, 32);
-        ZK_HIP_CHECK(ctx, built->d_pre.alloc(k1 * m * 36));
-        ZK_HIP_CHECK(ctx, d_w.alloc(32));
+        ZK_TRY(built->d_pre.alloc(ctx, k1 * m * 36));
+        ZK_TRY(d_w.alloc(ctx, 32));
         ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_w, omega_big, 32, hipMemcpyHostToDevice, ctx->stream));
         const size_t entries = k1 * m;
         ZK_LAUNCH(ctx, "ntt_build_tw", ntt_build_ext_pre<U>, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, d_w, (uint32_t)log_m, (uint32_t)k1, built->d_pre);

@@ -65,75 +65,61 @@ int zkhip_init(int device_id, zkhip_ctx **out) {
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return ZKHIP_ERR_NO_DEVICE;
     if (device_id < 0 || device_id >= count) return ZKHIP_ERR_INVALID;
     if (hipSetDevice(device_id) != hipSuccess) return ZKHIP_ERR_NO_DEVICE;
-    zkhip_ctx *ctx = new zkhip_ctx();
+    std::unique_ptr<zkhip_ctx> ctx(new zkhip_ctx());
     ctx->device = device_id;
-    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete ctx;
-        return ZKHIP_ERR_HIP;
-    }
-    ctx->own_stream = true;
-    if (hipMalloc((void **)&ctx->d_status, 4) != hipSuccess || hipMemset(ctx->d_status, 0, 4) != hipSuccess) {
-        (void)hipStreamDestroy(ctx->stream);
-        delete ctx;
-        return ZKHIP_ERR_OOM;
-    }
-    *out = ctx;
+    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) return ZKHIP_ERR_HIP;
+    ctx->own_stream.reset(ctx->stream);
+    if (ctx->d_status.alloc(ctx.get(), 4) != 0 || hipMemset(ctx->d_status, 0, 4) != hipSuccess) return ZKHIP_ERR_OOM;
     {
         std::lock_guard<std::mutex> g(g_alloc_mutex);
-        g_contexts.insert(ctx);
+        g_contexts.insert(ctx.get());
     }
     // A/B runs of programs that create their own contexts (the bench library, the shim's default context): ZKHIP_OPTIONS="name=value,name=value"
     // is applied to every new context; an unknown name or a malformed entry is ignored (the variable is for measurements, not for deployments)
-    if (const char *env = getenv("ZKHIP_OPTIONS")) {
-        std::string all(env);
-        size_t at = 0;
-        while (at < all.size()) {
-            const size_t end = all.find(',', at);
-            const std::string item = all.substr(at, end == std::string::npos ? std::string::npos : end - at);
-            const size_t eq = item.find('=');
-            if (eq != std::string::npos && eq > 0) (void)zkhip_set_option(ctx, item.substr(0, eq).c_str(), (int64_t)atoll(item.c_str() + eq + 1));
-            if (end == std::string::npos) break;
-            at = end + 1;
-        }
-    }
+    if (const char *env = getenv("ZKHIP_OPTIONS"))
+        zk_options_parse(env, [&](const char *name, int64_t value) { (void)zkhip_set_option(ctx.get(), name, value); });
+    *out = ctx.release();
     return ZKHIP_OK;
 }
 
 static void alloc_cache_flush(zkhip_ctx *ctx);
 
-void zkhip_destroy(zkhip_ctx *ctx) {
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    zk_ntt_free_tables(ctx);
-    zk_dom_free_tables(ctx);
-    for (auto &p : ctx->prof.pending) {
-        (void)hipEventDestroy(p.second.a);
-        (void)hipEventDestroy(p.second.b);
-    }
-    for (auto &e : ctx->prof.pool) {
-        (void)hipEventDestroy(e.a);
-        (void)hipEventDestroy(e.b);
-    }
-    zk_graphs_clear(ctx);
-    if (ctx->order_event) (void)hipEventDestroy(ctx->order_event);
+}  // extern "C"
+
+// Everything the context holds goes here, in this order: the stream drains first, the tables, events and graphs go while it still exists,
+// the buffers after the allocator cache, the stream -- if the context created it -- last.
+zkhip_ctx::~zkhip_ctx() {
+    (void)hipSetDevice(device);
+    (void)hipStreamSynchronize(stream);
+    ntt_tables.clear();
+    ntt_ext_tables.clear();
+    dom_tables.clear();
+    dom_ws.reset();
+    prof.pending.clear();
+    prof.pool.clear();
+    zk_graphs_clear(this);
+    order_event.reset();
     {
         /* the cached blocks go back to the driver; blocks the caller still HOLDS (a shared_ptr handle of the shim that outlives its context)
            are left alone and lose their owner: a later zkhip_free through any context hands them to hipFree (they used to be
            freed here, under the handle) */
         std::lock_guard<std::mutex> g(g_alloc_mutex);
-        std::lock_guard<std::mutex> lock(ctx->alloc_mutex);
-        alloc_cache_flush(ctx);
-        for (auto &e : ctx->alloc_live) g_block_owner.erase(e.first);
-        ctx->alloc_live.clear();
-        g_contexts.erase(ctx);
+        std::lock_guard<std::mutex> lock(alloc_mutex);
+        alloc_cache_flush(this);
+        for (auto &e : alloc_live) g_block_owner.erase(e.first);
+        alloc_live.clear();
+        g_contexts.erase(this);
     }
-    if (ctx->msm_host_buf) (void)hipFree(ctx->msm_host_buf);
-    if (ctx->ws) (void)hipFree(ctx->ws);
-    if (ctx->d_status) (void)hipFree(ctx->d_status);
-    if (ctx->pinned) (void)hipHostFree(ctx->pinned);
-    if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    msm_host_buf.reset();
+    ws.reset();
+    d_status.reset();
+    own_stream.reset();
+}
+
+extern "C" {
+
+void zkhip_destroy(zkhip_ctx *ctx) {
+    if (ctx) delete ctx;
 }
 
 int zkhip_device(const zkhip_ctx *ctx) { return ctx ? ctx->device : -1; }
@@ -142,9 +128,9 @@ int zkhip_stream_wait(zkhip_ctx *waiter, zkhip_ctx *signal) {
     if (!waiter || !signal || waiter->device != signal->device) return ZKHIP_ERR_INVALID;
     if (waiter == signal) return ZKHIP_OK;
     ZK_HIP_CHECK(waiter, hipSetDevice(waiter->device));
-    if (!signal->order_event) ZK_HIP_CHECK(waiter, hipEventCreateWithFlags(&signal->order_event, hipEventDisableTiming));
-    ZK_HIP_CHECK(waiter, hipEventRecord(signal->order_event, signal->stream));
-    ZK_HIP_CHECK(waiter, hipStreamWaitEvent(waiter->stream, signal->order_event, 0));
+    if (!signal->order_event) ZK_HIP_CHECK(waiter, zk_event_create(signal->order_event, hipEventDisableTiming));
+    ZK_HIP_CHECK(waiter, hipEventRecord(signal->order_event.get(), signal->stream));
+    ZK_HIP_CHECK(waiter, hipStreamWaitEvent(waiter->stream, signal->order_event.get(), 0));
     return ZKHIP_OK;
 }
 
@@ -154,9 +140,8 @@ int zkhip_set_stream(zkhip_ctx *ctx, void *hip_stream) {
     if (!ctx) return ZKHIP_ERR_INVALID;
     ZK_TRY(check_device(ctx));
     ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
+    ctx->own_stream.reset();
     ctx->stream = reinterpret_cast<hipStream_t>(hip_stream);
-    ctx->own_stream = false;
     return ZKHIP_OK;
 }
 
@@ -185,42 +170,26 @@ int zkhip_device_status(zkhip_ctx *ctx, uint32_t *flags) {
 
 int zkhip_set_option(zkhip_ctx *ctx, const char *name, int64_t value) {
     if (!ctx || !name) return ZKHIP_ERR_INVALID;
-    std::string n(name);
-    if (n == "msm_window_bits") ctx->opt_msm_window_bits = (int)value;
-    else if (n == "msm_segment_log") ctx->opt_msm_segment_log = (int)value;
-    else if (n == "msm_sets") ctx->opt_msm_sets = (int)value;
-    else if (n == "msm_tail_quads") ctx->opt_msm_tail_quads = (int)value;
-    else if (n == "msm_tail_fold") ctx->opt_msm_tail_fold = (int)value;
-    else if (n == "msm_fold_run") ctx->opt_msm_fold_run = (int)value;
-    else if (n == "msm_tail_fold_g2") ctx->opt_msm_tail_fold_g2 = (int)value;
-    else if (n == "msm_share_sort") ctx->opt_msm_share_sort = (int)value;
-    else if (n == "ec_ntt_table_lanes") ctx->opt_ec_ntt_table_lanes = value < 0 ? 0 : (uint32_t)std::min<int64_t>(value, 1 << 24);
-    else if (n == "msm_sort_tile_log") ctx->opt_msm_sort_tile_log = (int)value;
-    else if (n == "ntt_radix_log") ctx->opt_ntt_radix_log = (int)value;
-    else if (n == "ntt_tile_log") ctx->opt_ntt_tile_log = (int)value;
-    else if (n == "ntt_pair") ctx->opt_ntt_pair = (int)value;
-    else if (n == "poly_coset_extend") ctx->opt_poly_coset_extend = value != 0;
-    else if (n == "msm_precompute") ctx->opt_msm_precompute = (int)value;
-    else if (n == "msm_precompute_min") ctx->opt_msm_precompute_min = (int)value;
-    else if (n == "msm_shard_world") {
-        if (value < 1 || value > 64) return ZKHIP_ERR_RANGE;
-        ctx->opt_msm_shard_world = (int)value;
-        if (ctx->opt_msm_shard_rank >= ctx->opt_msm_shard_world) ctx->opt_msm_shard_rank = 0;
-    } else if (n == "msm_shard_rank") {
-        if (value < 0 || value >= ctx->opt_msm_shard_world) return ZKHIP_ERR_RANGE;
-        ctx->opt_msm_shard_rank = (int)value;
-    }
-    else if (n == "msm_graphs") ctx->opt_msm_graphs = (int)value;
-    else if (n == "alloc_cache_mb") {
+    const OptRow<zkhip_ctx> *row = zk_option_find<zkhip_ctx>(name);
+    if (!row) return ZKHIP_ERR_INVALID;
+    if (row->admit != OPT_CUSTOM) {
+        zk_option_store(*ctx, *row, value);
+    } else if (!row->member) {  // alloc_cache_mb
         if (value < 0) return ZKHIP_ERR_RANGE;
         std::lock_guard<std::mutex> g(g_alloc_mutex);
         std::lock_guard<std::mutex> lock(ctx->alloc_mutex);
         ctx->opt_alloc_cache_bytes = (size_t)value << 20;
         if (ctx->alloc_cached_bytes > ctx->opt_alloc_cache_bytes) alloc_cache_flush(ctx);
-    }
-    else if (n == "stream_priority") {
-        // the context's OWN stream is recreated with a scheduling priority: < 0 the highest the device offers, > 0 the lowest, 0 the
-        // default.  Two contexts on one GPU (the Groth16 shim's main and G2 streams) can so decide whose workgroups go first.
+    } else if (row->member == &zkhip_ctx::opt_msm_shard_world) {
+        if (value < 1 || value > 64) return ZKHIP_ERR_RANGE;
+        ctx->opt_msm_shard_world = (int)value;
+        if (ctx->opt_msm_shard_rank >= ctx->opt_msm_shard_world) ctx->opt_msm_shard_rank = 0;
+    } else if (row->member == &zkhip_ctx::opt_msm_shard_rank) {
+        if (value < 0 || value >= ctx->opt_msm_shard_world) return ZKHIP_ERR_RANGE;
+        ctx->opt_msm_shard_rank = (int)value;
+    } else if (row->member == &zkhip_ctx::opt_stream_priority) {
+        // the context's OWN stream is recreated with a scheduling priority: < 0 the highest the device offers, > 0 the
+        // lowest, 0 the default.  Two contexts on one GPU (the Groth16 shim's main and G2 streams) can so decide whose workgroups go first.
         if (!ctx->own_stream) return ZKHIP_ERR_INVALID;
         ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
         int least = 0, greatest = 0;
@@ -228,40 +197,21 @@ int zkhip_set_option(zkhip_ctx *ctx, const char *name, int64_t value) {
         ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         hipStream_t s = nullptr;
         ZK_HIP_CHECK(ctx, hipStreamCreateWithPriority(&s, hipStreamNonBlocking, value < 0 ? greatest : (value > 0 ? least : 0)));
-        (void)hipStreamDestroy(ctx->stream);
+        ctx->own_stream.reset(s);
         ctx->stream = s;
         ctx->opt_stream_priority = (int)value;
         zk_graphs_clear(ctx);
+    } else {
+        return ZKHIP_ERR_INVALID;  // an OPT_CUSTOM row without its code above
     }
-    else return ZKHIP_ERR_INVALID;
     return ZKHIP_OK;
 }
 
 int zkhip_get_option(const zkhip_ctx *ctx, const char *name, int64_t *value) {
     if (!ctx || !name || !value) return ZKHIP_ERR_INVALID;
-    std::string n(name);
-    if (n == "msm_window_bits") *value = ctx->opt_msm_window_bits;
-    else if (n == "alloc_cache_mb") *value = (int64_t)(ctx->opt_alloc_cache_bytes >> 20);
-    else if (n == "msm_segment_log") *value = ctx->opt_msm_segment_log;
-    else if (n == "msm_sets") *value = ctx->opt_msm_sets;
-    else if (n == "msm_tail_quads") *value = ctx->opt_msm_tail_quads;
-    else if (n == "msm_tail_fold") *value = ctx->opt_msm_tail_fold;
-    else if (n == "msm_fold_run") *value = ctx->opt_msm_fold_run;
-    else if (n == "msm_tail_fold_g2") *value = ctx->opt_msm_tail_fold_g2;
-    else if (n == "msm_share_sort") *value = ctx->opt_msm_share_sort;
-    else if (n == "ec_ntt_table_lanes") *value = ctx->opt_ec_ntt_table_lanes;
-    else if (n == "msm_sort_tile_log") *value = ctx->opt_msm_sort_tile_log;
-    else if (n == "ntt_radix_log") *value = ctx->opt_ntt_radix_log;
-    else if (n == "ntt_tile_log") *value = ctx->opt_ntt_tile_log;
-    else if (n == "ntt_pair") *value = ctx->opt_ntt_pair;
-    else if (n == "poly_coset_extend") *value = ctx->opt_poly_coset_extend;
-    else if (n == "msm_precompute") *value = ctx->opt_msm_precompute;
-    else if (n == "msm_precompute_min") *value = ctx->opt_msm_precompute_min;
-    else if (n == "msm_shard_world") *value = ctx->opt_msm_shard_world;
-    else if (n == "msm_shard_rank") *value = ctx->opt_msm_shard_rank;
-    else if (n == "msm_graphs") *value = ctx->opt_msm_graphs;
-    else if (n == "stream_priority") *value = ctx->opt_stream_priority;
-    else return ZKHIP_ERR_INVALID;
+    const OptRow<zkhip_ctx> *row = zk_option_find<zkhip_ctx>(name);
+    if (!row) return ZKHIP_ERR_INVALID;
+    *value = row->member ? ctx->*row->member : (int64_t)(ctx->opt_alloc_cache_bytes >> 20);
     return ZKHIP_OK;
 }
 
@@ -407,17 +357,13 @@ int zkhip_memcpy_2d_d2d_async(zkhip_ctx *ctx, void *dst, size_t dst_pitch, const
 }
 
 // ---- bases ------------------------------------------------------------------------------------------
-static int bases_alloc(zkhip_ctx *ctx, int curve, int group, size_t n, zkhip_bases **out) {
+static int bases_alloc(zkhip_ctx *ctx, int curve, int group, size_t n, std::unique_ptr<zkhip_bases> &out) {
     if ((curve != CURVE_BLS12_381 && curve != CURVE_BN254) || (group != GROUP_G1 && group != GROUP_G2)) return ZKHIP_ERR_INVALID;
-    zkhip_bases *b = new zkhip_bases();
+    std::unique_ptr<zkhip_bases> b(new zkhip_bases());
     b->curve = curve;
     b->group = group;
     b->n = n;
     b->stride_u32 = zk_point_words(curve, group);
-    b->d = nullptr;
-    b->ntab = 1;
-    b->c_tab = 0;
-    b->nslots = 1;
     const bool shard = ctx->opt_msm_shard_world > 1;
     if (ctx->opt_msm_precompute && n >= (size_t)ctx->opt_msm_precompute_min) {
         b->c_tab = ctx->opt_msm_window_bits > 0 ? std::max(2, std::min(ZK_MSM_MAX_C, ctx->opt_msm_window_bits)) : zk_msm_auto_window(n);
@@ -433,117 +379,71 @@ static int bases_alloc(zkhip_ctx *ctx, int curve, int group, size_t n, zkhip_bas
         b->win_rank = ctx->opt_msm_shard_rank;
         b->win_world = ctx->opt_msm_shard_world;
     }
-    hipError_t e = hipMalloc((void **)&b->d, std::max<size_t>(1, n) * b->nslots * b->stride_u32 * 4);
-    if (e != hipSuccess && b->tables() && !shard) {
+    int rc = b->d.alloc(ctx, std::max<size_t>(1, n) * b->nslots * b->stride_u32 * 4);
+    if (rc && b->tables() && !shard) {
         // the window tables do not fit (ntab x n points): keep the points alone; the MSM then folds the windows by the
         // Horner pass of msm_final instead of bucket-wise
-        (void)hipGetLastError();
         b->ntab = 1;
         b->c_tab = 0;
         b->nslots = 1;
-        e = hipMalloc((void **)&b->d, std::max<size_t>(1, n) * b->stride_u32 * 4);
+        rc = b->d.alloc(ctx, std::max<size_t>(1, n) * b->stride_u32 * 4);
     }
-    if (e != hipSuccess) {
-        ctx->last_error = std::string("hipMalloc(bases): ") + hipGetErrorString(e);
-        delete b;
-        return ZKHIP_ERR_OOM;
-    }
-    *out = b;
+    ZK_TRY(rc);
+    out = std::move(b);
     return 0;
+}
+
+// the end of every constructor of bases: the window tables, the stream drained (the caller's temporaries go when it returns), the handle handed over
+static int bases_finish(zkhip_ctx *ctx, std::unique_ptr<zkhip_bases> &b, zkhip_bases **out) {
+    ZK_TRY(zk_bases_precompute(ctx, b.get()));
+    ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    *out = b.release();
+    return ZKHIP_OK;
 }
 
 int zkhip_bases_upload(zkhip_ctx *ctx, int curve, int group, const uint64_t *affine_xy, const uint8_t *is_infinity, size_t n,
                        zkhip_bases **out) {
     if (!ctx || !out || (n && !affine_xy)) return ZKHIP_ERR_INVALID;
     ZK_TRY(check_device(ctx));
-    zkhip_bases *b = nullptr;
-    ZK_TRY(bases_alloc(ctx, curve, group, n, &b));
-    uint8_t *d_inf = nullptr;
-    uint32_t *d_canon = nullptr;
-    const size_t cbytes = n * 2 * zk_coord_limbs64(curve, group) * 8;
-    int rc = 0;
-    do {
-        if (n == 0) break;
-        if (hipMalloc((void **)&d_canon, cbytes) != hipSuccess) {
-            rc = ZKHIP_ERR_OOM;
-            break;
-        }
-        if (hipMemcpyAsync(d_canon, affine_xy, cbytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-            rc = ZKHIP_ERR_HIP;
-            break;
-        }
+    std::unique_ptr<zkhip_bases> b;
+    ZK_TRY(bases_alloc(ctx, curve, group, n, b));
+    DevBuf d_canon, d_inf;
+    if (n) {
+        const size_t cbytes = n * 2 * zk_coord_limbs64(curve, group) * 8;
+        ZK_TRY(d_canon.alloc(ctx, cbytes));
+        ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_canon, affine_xy, cbytes, hipMemcpyHostToDevice, ctx->stream));
         if (is_infinity) {
-            if (hipMalloc((void **)&d_inf, n) != hipSuccess) {
-                rc = ZKHIP_ERR_OOM;
-                break;
-            }
-            if (hipMemcpyAsync(d_inf, is_infinity, n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-                rc = ZKHIP_ERR_HIP;
-                break;
-            }
+            ZK_TRY(d_inf.alloc(ctx, n));
+            ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_inf, is_infinity, n, hipMemcpyHostToDevice, ctx->stream));
         }
-        rc = zk_bases_to_mont(ctx, b, d_canon, d_inf);
-        if (rc) break;
-        rc = zk_bases_precompute(ctx, b);
-        if (rc) break;
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = ZKHIP_ERR_HIP;
-    } while (0);
-    if (d_inf) (void)hipFree(d_inf);
-    if (d_canon) (void)hipFree(d_canon);
-    if (rc) {
-        (void)hipFree(b->d);
-        delete b;
-        return rc;
+        ZK_TRY(zk_bases_to_mont(ctx, b.get(), d_canon, d_inf.as<uint8_t>()));
     }
-    *out = b;
-    return ZKHIP_OK;
+    return bases_finish(ctx, b, out);
 }
 
 int zkhip_bases_upload_compressed(zkhip_ctx *ctx, int curve, int group, const uint8_t *octets, size_t n, zkhip_bases **out) {
     if (!ctx || !out || (n && !octets)) return ZKHIP_ERR_INVALID;
     if (curve != CURVE_BLS12_381) return ZKHIP_ERR_INVALID;
     ZK_TRY(check_device(ctx));
-    zkhip_bases *b = nullptr;
-    ZK_TRY(bases_alloc(ctx, curve, group, n, &b));
-    const size_t bytes = n * (group == GROUP_G2 ? 96 : 48);
-    uint8_t *d_oct = nullptr;
-    uint32_t rejected = 0;
-    int rc = 0;
-    do {
-        if (n == 0) break;
-        if (hipMalloc((void **)&d_oct, bytes + 16) != hipSuccess) {
-            rc = ZKHIP_ERR_OOM;
-            break;
-        }
-        uint32_t *d_err = reinterpret_cast<uint32_t *>(d_oct + ((bytes + 3) & ~(size_t)3));
-        if (hipMemcpyAsync(d_oct, octets, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-            hipMemsetAsync(d_err, 0, 4, ctx->stream) != hipSuccess) {
-            rc = ZKHIP_ERR_HIP;
-            break;
-        }
-        rc = zk_bases_decompress(ctx, b, d_oct, d_err);
-        if (rc) break;
-        if (hipMemcpyAsync(&rejected, d_err, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
-            rc = ZKHIP_ERR_HIP;
-            break;
-        }
+    std::unique_ptr<zkhip_bases> b;
+    ZK_TRY(bases_alloc(ctx, curve, group, n, b));
+    DevBuf d_oct;
+    if (n) {
+        const size_t bytes = n * (group == GROUP_G2 ? 96 : 48);
+        ZK_TRY(d_oct.alloc(ctx, bytes + 16));
+        uint32_t *d_err = reinterpret_cast<uint32_t *>(d_oct.as<uint8_t>() + ((bytes + 3) & ~(size_t)3));
+        ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_oct, octets, bytes, hipMemcpyHostToDevice, ctx->stream));
+        ZK_HIP_CHECK(ctx, hipMemsetAsync(d_err, 0, 4, ctx->stream));
+        ZK_TRY(zk_bases_decompress(ctx, b.get(), d_oct.as<uint8_t>(), d_err));
+        uint32_t rejected = 0;
+        ZK_HIP_CHECK(ctx, hipMemcpyAsync(&rejected, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
+        ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         if (rejected) {
             ctx->last_error = std::to_string(rejected) + " point encoding(s) rejected (flags, x >= p, or x not on the curve)";
-            rc = ZKHIP_ERR_INVALID;
-            break;
+            return ZKHIP_ERR_INVALID;
         }
-        rc = zk_bases_precompute(ctx, b);
-        if (rc) break;
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = ZKHIP_ERR_HIP;
-    } while (0);
-    if (d_oct) (void)hipFree(d_oct);
-    if (rc) {
-        (void)hipFree(b->d);
-        delete b;
-        return rc;
     }
-    *out = b;
-    return ZKHIP_OK;
+    return bases_finish(ctx, b, out);
 }
 
 // standard generators, canonical u32 limbs (x | y)
@@ -565,38 +465,20 @@ int zkhip_bases_from_scalars(zkhip_ctx *ctx, int curve, int group, const uint64_
                              zkhip_bases **out) {
     if (!ctx || !out || (n && !scalars)) return ZKHIP_ERR_INVALID;
     ZK_TRY(check_device(ctx));
-    zkhip_bases *b = nullptr;
-    ZK_TRY(bases_alloc(ctx, curve, group, n, &b));
+    std::unique_ptr<zkhip_bases> b;
+    ZK_TRY(bases_alloc(ctx, curve, group, n, b));
     const uint64_t *gen = base_affine_xy;
     if (!gen) gen = curve == CURVE_BLS12_381 ? (group == GROUP_G1 ? GEN_BLS_G1 : GEN_BLS_G2) : (group == GROUP_G1 ? GEN_BN_G1 : GEN_BN_G2);
-    uint32_t *d_s = nullptr, *d_g = nullptr;
-    int rc = 0;
-    do {
-        if (n == 0) break;
-        if (hipMalloc((void **)&d_s, n * 32) != hipSuccess || hipMalloc((void **)&d_g, 2 * zk_coord_limbs64(curve, group) * 8) != hipSuccess) {
-            rc = ZKHIP_ERR_OOM;
-            break;
-        }
-        if (hipMemcpyAsync(d_s, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-            hipMemcpyAsync(d_g, gen, 2 * zk_coord_limbs64(curve, group) * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-            rc = ZKHIP_ERR_HIP;
-            break;
-        }
-        rc = zk_bases_mul(ctx, b, d_g, d_s);
-        if (rc) break;
-        rc = zk_bases_precompute(ctx, b);
-        if (rc) break;
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = ZKHIP_ERR_HIP;
-    } while (0);
-    if (d_s) (void)hipFree(d_s);
-    if (d_g) (void)hipFree(d_g);
-    if (rc) {
-        (void)hipFree(b->d);
-        delete b;
-        return rc;
+    DevBuf d_s, d_g;
+    if (n) {
+        const size_t gbytes = 2 * zk_coord_limbs64(curve, group) * 8;
+        ZK_TRY(d_s.alloc(ctx, n * 32));
+        ZK_TRY(d_g.alloc(ctx, gbytes));
+        ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_s, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
+        ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_g, gen, gbytes, hipMemcpyHostToDevice, ctx->stream));
+        ZK_TRY(zk_bases_mul(ctx, b.get(), d_g, d_s));
     }
-    *out = b;
-    return ZKHIP_OK;
+    return bases_finish(ctx, b, out);
 }
 
 // out row d_rows[j] (or first + j) <- src row j; a row is `stride` words
@@ -620,40 +502,17 @@ int zkhip_bases_spread(zkhip_ctx *ctx, const zkhip_bases *src, const uint32_t *d
     if (n_total >= ((size_t)1 << 32) || (!d_rows && first + src->n > n_total)) return ZKHIP_ERR_RANGE;
     if (src->n * src->stride_u32 >= ((size_t)1 << 39)) return ZKHIP_ERR_RANGE;  // one lane per word: the grid must fit 32 bits
     ZK_TRY(check_device(ctx));
-    zkhip_bases *b = nullptr;
-    ZK_TRY(bases_alloc(ctx, src->curve, src->group, n_total, &b));
-    int rc = 0;
-    do {
-        if (n_total == 0) break;
-        const size_t words = n_total * b->stride_u32;
-        if (hipMemsetAsync(b->d, 0, words * 4, ctx->stream) != hipSuccess) {  // (0, 0): the point at infinity
-            rc = ZKHIP_ERR_HIP;
-            break;
-        }
+    std::unique_ptr<zkhip_bases> b;
+    ZK_TRY(bases_alloc(ctx, src->curve, src->group, n_total, b));
+    if (n_total) {
+        ZK_HIP_CHECK(ctx, hipMemsetAsync(b->d, 0, n_total * b->stride_u32 * 4, ctx->stream));  // (0, 0): the point at infinity
         if (src->n) {
             const size_t lanes = src->n * src->stride_u32;
-            ctx->prof_begin("bases_spread_rows");
-            hipLaunchKernelGGL(bases_spread_rows, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, ctx->stream, src->d, src->n, (uint32_t)src->stride_u32,
-                               d_rows, (uint32_t)first, (uint32_t)n_total, b->d, ctx->d_status);
-            ctx->prof_end();
-            const hipError_t le = hipGetLastError();
-            if (le != hipSuccess) {
-                ctx->last_error = std::string("bases_spread_rows: ") + hipGetErrorString(le);
-                rc = ZKHIP_ERR_HIP;
-                break;
-            }
+            ZK_LAUNCH(ctx, "bases_spread_rows", bases_spread_rows, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, src->d, src->n,
+                      (uint32_t)src->stride_u32, d_rows, (uint32_t)first, (uint32_t)n_total, b->d, ctx->d_status);
         }
-        rc = zk_bases_precompute(ctx, b);
-        if (rc) break;
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = ZKHIP_ERR_HIP;
-    } while (0);
-    if (rc) {
-        (void)hipFree(b->d);
-        delete b;
-        return rc;
     }
-    *out = b;
-    return ZKHIP_OK;
+    return bases_finish(ctx, b, out);
 }
 
 int zkhip_bases_download(zkhip_ctx *ctx, const zkhip_bases *b, size_t offset, size_t n, uint64_t *affine_xy, uint8_t *is_infinity) {
@@ -681,7 +540,6 @@ void zkhip_bases_free(zkhip_ctx *ctx, zkhip_bases *b) {
         (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);
     }
-    (void)hipFree(b->d);
     delete b;
 }
 
@@ -708,18 +566,10 @@ int zkhip_msm_batch_dev(zkhip_ctx *ctx, size_t count, const zkhip_bases *const *
 // call after call, so the launch sequence replays as a HIP graph like the resident path's.
 int zk_msm_host_reserve(zkhip_ctx *ctx, size_t n) {
     const size_t want = std::max<size_t>(1, n) * 32 + 512;
-    if (ctx->msm_host_cap >= want) return 0;
-    ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->msm_host_buf) (void)hipFree(ctx->msm_host_buf);
-    ctx->msm_host_buf = nullptr;
-    ctx->msm_host_cap = 0;
-    zk_graphs_clear(ctx);  // graphs over the old buffer
-    if (hipMalloc((void **)&ctx->msm_host_buf, want) != hipSuccess) {
-        (void)hipGetLastError();
-        return ZKHIP_ERR_OOM;
-    }
-    ctx->msm_host_cap = want;
-    return 0;
+    if (ctx->msm_host_buf.cap >= want) return 0;
+    ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // on a first allocation too: a graph may still be replaying
+    zk_graphs_clear(ctx);                                  // graphs over the old buffer
+    return ctx->msm_host_buf.reserve(ctx, want);
 }
 
 extern "C" {
@@ -729,7 +579,7 @@ int zkhip_msm(zkhip_ctx *ctx, const zkhip_bases *bases, size_t offset, size_t n,
     ZK_TRY(check_device(ctx));
     const size_t obytes = 3 * zk_coord_limbs64(bases->curve, bases->group) * 8;
     ZK_TRY(zk_msm_host_reserve(ctx, n));
-    uint32_t *d_o = ctx->msm_host_buf, *d_s = ctx->msm_host_buf + 128;
+    uint32_t *d_o = ctx->msm_host_buf.as<uint32_t>(), *d_s = d_o + 128;
     if (n) ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_s, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
     ZK_TRY(zk_msm_run(ctx, bases, offset, n, d_s, d_o));
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(out_jacobian, d_o, obytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -776,24 +626,13 @@ int zkhip_ntt(zkhip_ctx *ctx, int curve, uint64_t *data, size_t log_m, size_t ba
     if (batch == 0) return ZKHIP_OK;
     ZK_TRY(check_device(ctx));
     size_t bytes = (batch << log_m) * 32;
-    uint32_t *d = nullptr;
-    ZK_HIP_CHECK(ctx, hipMalloc((void **)&d, bytes));
-    int rc = 0;
-    do {
-        if (hipMemcpyAsync(d, data, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-            rc = ZKHIP_ERR_HIP;
-            break;
-        }
-        rc = zk_ntt_run(ctx, curve, d, log_m, batch, omega, inverse ? 1 : 0, coset_gen);
-        if (rc) break;
-        if (hipMemcpyAsync(data, d, bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess) {
-            ctx->last_error = hipGetErrorString(hipGetLastError());
-            rc = ZKHIP_ERR_HIP;
-        }
-    } while (0);
-    (void)hipFree(d);
-    return rc;
+    DevBuf d;
+    ZK_TRY(d.alloc(ctx, bytes));
+    ZK_HIP_CHECK(ctx, hipMemcpyAsync(d, data, bytes, hipMemcpyHostToDevice, ctx->stream));
+    ZK_TRY(zk_ntt_run(ctx, curve, d, log_m, batch, omega, inverse ? 1 : 0, coset_gen));
+    ZK_HIP_CHECK(ctx, hipMemcpyAsync(data, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return ZKHIP_OK;
 }
 
 // ---- profiling ----------------------------------------------------------------------------------------

@@ -6,7 +6,8 @@
 // mutation loop over proving_key_from_bytes (marshalling.hpp), which parses untrusted blobs: truncations at every framing
 // boundary, oversized and zero counts, non-increasing / out-of-range B indices, random byte flips.  The parser must throw or
 // succeed; the sanitizers decide the rest.  Also the context's table cache (csrc/table_cache.hpp) over an entry type that counts its
-// constructions and destructions: eviction order, the drain before each eviction, a build abandoned before publish().
+// constructions and destructions: eviction order, the drain before each eviction, a build abandoned before publish().  And the option table
+// (csrc/options.hpp) over a plain struct: unique names, set / get round trips, the admission rules, the ZKHIP_OPTIONS parser.
 #include <chrono>
 #include <memory>
 #include <cstdio>
@@ -27,6 +28,7 @@
 #include <nil/crypto3/zk/hip/placeholder_quotient.hpp>
 #include <nil/crypto3/zk/hip/r1cs_gg_ppzksnark_generator.hpp>
 
+#include "../../../crypto3-zk_amd/csrc/options.hpp"
 #include "../../../crypto3-zk_amd/csrc/table_cache.hpp"
 
 using namespace nil::crypto3::zk::hip;
@@ -713,6 +715,74 @@ void table_cache_protocol() {
     }
     EXPECT(counted_entry::made == 8 && counted_entry::made == counted_entry::gone);
 }
+
+// the members the option table names, and nothing else
+struct plain_options {
+    int opt_msm_window_bits = 0, opt_msm_segment_log = -1, opt_msm_sets = 0, opt_msm_tail_quads = 1, opt_msm_tail_fold = 16, opt_msm_fold_run = 0,
+        opt_msm_tail_fold_g2 = 1, opt_msm_share_sort = 1, opt_msm_sort_tile_log = 14, opt_ec_ntt_table_lanes = 0, opt_ntt_radix_log = 8,
+        opt_ntt_tile_log = 3, opt_ntt_pair = 1, opt_poly_coset_extend = 1, opt_msm_precompute = 1, opt_msm_precompute_min = 32, opt_msm_graphs = 0,
+        opt_msm_shard_world = 1, opt_msm_shard_rank = 0, opt_stream_priority = 0;
+};
+// what zkhip_set_option does with a row that is not OPT_CUSTOM; everything else is refused here
+int plain_set(plain_options &o, const char *name, std::int64_t value) {
+    const OptRow<plain_options> *row = zk_option_find<plain_options>(name);
+    if (!row || row->admit == OPT_CUSTOM) return -1;
+    zk_option_store(o, *row, value);
+    return 0;
+}
+
+void option_table() {
+    typedef OptRow<plain_options> row_t;
+    std::size_t rows = 0, keyed = 0, custom = 0, without_member = 0;
+    for (const row_t &r : zk_options<plain_options>) {
+        ++rows;
+        keyed += r.msm_graph_key;
+        custom += r.admit == OPT_CUSTOM;
+        without_member += r.member == nullptr;
+        EXPECT(zk_option_find<plain_options>(r.name) == &r);    // found under its own name, by the FIRST row of that name: names are unique
+        for (const row_t &q : zk_options<plain_options>) EXPECT(&q == &r || (strcmp(q.name, r.name) != 0 && (!q.member || q.member != r.member)));
+        EXPECT(r.member || r.admit == OPT_CUSTOM);
+        EXPECT(!r.msm_graph_key || r.admit == OPT_INT);
+    }
+    EXPECT(rows == 21 && keyed == 9 && custom == 4 && without_member == 1);
+    EXPECT(!zk_option_find<plain_options>("bogus") && !zk_option_find<plain_options>("") && !zk_option_find<plain_options>("msm_sets "));
+    plain_options o;
+    int k = 0;
+    for (const row_t &r : zk_options<plain_options>) {    // set, then get, through the plain struct; no row disturbs another
+        if (r.admit != OPT_INT) continue;
+        const plain_options before = o;
+        EXPECT(plain_set(o, r.name, 100 + ++k) == 0 && o.*r.member == 100 + k);
+        for (const row_t &q : zk_options<plain_options>) EXPECT(&q == &r || !q.member || o.*q.member == before.*q.member);
+        EXPECT(plain_set(o, r.name, ((std::int64_t)1 << 32) - 5) == 0 && o.*r.member == -5);    // truncated to int
+    }
+    EXPECT(k == 15);
+    EXPECT(plain_set(o, "poly_coset_extend", 5) == 0 && o.opt_poly_coset_extend == 1);
+    EXPECT(plain_set(o, "poly_coset_extend", 0) == 0 && o.opt_poly_coset_extend == 0);
+    EXPECT(plain_set(o, "poly_coset_extend", -7) == 0 && o.opt_poly_coset_extend == 1);
+    EXPECT(plain_set(o, "ec_ntt_table_lanes", -1) == 0 && o.opt_ec_ntt_table_lanes == 0);
+    EXPECT(plain_set(o, "ec_ntt_table_lanes", (std::int64_t)1 << 30) == 0 && o.opt_ec_ntt_table_lanes == 1 << 24);
+    EXPECT(plain_set(o, "ec_ntt_table_lanes", (std::int64_t)1 << 40) == 0 && o.opt_ec_ntt_table_lanes == 1 << 24);
+    EXPECT(plain_set(o, "ec_ntt_table_lanes", 777) == 0 && o.opt_ec_ntt_table_lanes == 777);
+    EXPECT(plain_set(o, "bogus", 1) == -1 && plain_set(o, "alloc_cache_mb", 1) == -1 && plain_set(o, "msm_shard_rank", 0) == -1);
+    /* the ZKHIP_OPTIONS parser: what is well formed is applied, the rest ignored */
+    auto parse = [](const char *text, plain_options &into) {
+        std::vector<std::string> seen;
+        zk_options_parse(text, [&](const char *name, std::int64_t value) {
+            seen.push_back(name);
+            (void)plain_set(into, name, value);
+        });
+        return seen;
+    };
+    typedef std::vector<std::string> names;
+    plain_options p, fresh;
+    EXPECT(parse("", p).empty() && parse("a", p).empty() && parse("=3", p).empty() && parse(",", p).empty());
+    EXPECT(parse("a=,b=2,,", p) == names({"a", "b"}));
+    EXPECT(parse("bogus=1", p) == names({"bogus"}));
+    EXPECT(memcmp(&p, &fresh, sizeof(p)) == 0);    // nothing of the above named an option
+    EXPECT(parse("ntt_pair=0,bogus=1,msm_sets=2", p) == names({"ntt_pair", "bogus", "msm_sets"}) && p.opt_ntt_pair == 0 && p.opt_msm_sets == 2);
+    EXPECT(parse("msm_tail_fold=,ntt_tile_log=-4,=9,ntt_radix_log", p) == names({"msm_tail_fold", "ntt_tile_log"}));    // no trailing entry; "name=" reads as 0
+    EXPECT(p.opt_msm_tail_fold == 0 && p.opt_ntt_tile_log == -4 && p.opt_ntt_radix_log == 8);
+}
 }    // namespace
 
 int main(int argc, char **argv) {
@@ -733,6 +803,7 @@ int main(int argc, char **argv) {
     }
     if (what == "all" || what == "fuzz") parser_fuzz();
     if (what == "all" || what == "table_cache") table_cache_protocol();
+    if (what == "all" || what == "options") option_table();
     fprintf(stderr, failures ? "sanitize_main: %d FAILED expectation(s)\n" : "sanitize_main: ok\n", failures);
     return failures ? 1 : 0;
 }

@@ -84,3 +84,18 @@ def test_malformed_encodings_are_rejected(ctx, zk, group):
             ctx.upload_bases_compressed(0, group, good + enc, 2)
     with pytest.raises(zk.ZkhipError):
         ctx.upload_bases_compressed(1, group, good, 1)  # BN254: no pinned wire format
+    # 64 encodings, one flag byte corrupted: refused as invalid, twice; then the context loads the intact key and computes with it
+    n = 64
+    pts, inf = cp.batch_mul(0, group, cp.random_fr(0, 93, n))
+    blob = b"".join(po.bls12_381_compress(group, pt_from_limbs(0, group, pts[i], inf[i])) for i in range(n))
+    at = 17 * 48 * group
+    broken = blob[:at] + bytes([blob[at] & 0x7F]) + blob[at + 1:]
+    for _ in range(2):
+        with pytest.raises(zk.ZkhipError, match="invalid argument"):
+            ctx.upload_bases_compressed(0, group, broken, n)
+    b = ctx.upload_bases_compressed(0, group, blob, n)
+    sc = cp.random_fr(0, 94, n)
+    aff, is_inf = ctx.msm_affine(b, sc)
+    exp, einf = cp.msm(0, group, pts, sc, chunks=2)
+    assert is_inf == einf and (aff == exp).all()
+    b.free()
