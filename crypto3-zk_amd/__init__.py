@@ -13,6 +13,7 @@ from .zkhip import (  # noqa: F401
     Bases,
     Context,
     DeviceGroup,
+    ERR_NOT_FOUND,
     GroupBases,
     HASH_SHA2_256,
     MerkleTree,
@@ -22,4 +23,5 @@ from .zkhip import (  # noqa: F401
     coord_limbs,
     lib_path,
     load_library,
+    sha256_host,
 )

@@ -18,6 +18,7 @@
 #include <nil/crypto3/zk/hip/placeholder_lookup.hpp>
 #include <nil/crypto3/zk/hip/placeholder_permutation.hpp>
 #include <nil/crypto3/zk/hip/placeholder_quotient.hpp>
+#include <nil/crypto3/zk/hip/transcript.hpp>
 
 using namespace nil::crypto3::zk::hip;
 
@@ -465,6 +466,49 @@ int zkhip_bench_lpc_proof_eval(int device, size_t log_n, size_t cols, size_t exp
         return 0;
     } catch (const std::exception &e) {
         fprintf(stderr, "zkhip_bench_lpc_proof_eval: %s\n", e.what());
+        return -1;
+    }
+}
+
+/* The same proof_eval with the DEVICE tree builder and the SHA2-256 sequential transcript (hip/transcript.hpp), without grinding (mask == 0:
+ * use_grinding stays false) and with it (fri_params.use_grinding, grinding_parameter = mask; basic_fri.hpp:743-745: the proof of work searched
+ * on the device, hip/proof_of_work.hpp).  ms: steps x {commit, proof_eval}.  nonces: steps proof-of-work values (the search starts at
+ * std::rand(), so the work per proof varies as it does for the reference). */
+int zkhip_bench_lpc_proof_eval_grinding(int device, size_t log_n, size_t cols, size_t expand, int steps, uint32_t mask, double *ms, uint32_t *nonces) {
+    try {
+        const size_t n = (size_t)1 << log_n;
+        context ctx(device);
+        fri_params_hip<C> params;
+        params.log_domain = log_n + expand;
+        params.step_list.assign(log_n + expand - 4, 1);
+        params.root_of_unity = bls_root;
+        params.use_grinding = mask != 0;
+        if (mask) params.grinding_parameter = mask;
+        splitmix sm {15};
+        std::vector<polynomial_dfs<C>> polys(cols);
+        for (auto &p : polys) {
+            p.values.resize(n);
+            for (auto &v : p.values) v = sm.nonzero();
+        }
+        std::vector<std::reference_wrapper<const polynomial_dfs<C>>> lent(polys.begin(), polys.end());
+        const Fr y = sm.nonzero(), w = bls_root(log_n);
+        for (int rep = 0; rep < steps; ++rep) {
+            lpc_commitment_scheme_hip<C, sha256_transcript<C>, device_merkle_builder<>> scheme(ctx, params, device_merkle_builder<>());
+            auto t0 = std::chrono::steady_clock::now();
+            scheme.append_to_batch(0, lent);
+            (void)scheme.commit(0);
+            ms[2 * rep] = ms_since(t0);
+            scheme.append_eval_point(0, y);
+            scheme.append_eval_point(0, y * w);
+            sha256_transcript<C> tr;
+            t0 = std::chrono::steady_clock::now();
+            auto proof = scheme.proof_eval(tr);
+            ms[2 * rep + 1] = ms_since(t0);
+            if (nonces) nonces[rep] = proof.fri_proof.proof_of_work;
+        }
+        return 0;
+    } catch (const std::exception &e) {
+        fprintf(stderr, "zkhip_bench_lpc_proof_eval_grinding: %s\n", e.what());
         return -1;
     }
 }

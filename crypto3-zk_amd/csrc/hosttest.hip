@@ -1,6 +1,7 @@
 // TEST SHIM (never loaded by the product path): runs the __host__ __device__ field / curve / recoding
 // code of fp.hpp, fu.hpp, curve.hpp and msm_recode.hpp on the CPU so the no-GPU test-suite can compare the
-// exact device arithmetic against the oracle, and the SHA2-256 core of sha256.hpp (the Merkle kernels' hash) against hashlib.
+// exact device arithmetic against the oracle, and the SHA2-256 core of sha256.hpp (the Merkle kernels' hash) and the proof-of-work
+// candidate function of pow.hpp (the grinding kernel's) against hashlib.
 // Built with --offload-host-only into libzkhip_hosttest.so.
 #include <cstring>
 #include <vector>
@@ -8,6 +9,7 @@
 #define ZK_NOINLINE_MUL 1  // keeps this shim's build time short; fu_sqr is reached through op 9
 #include "arith_ops.h"
 #include "msm_recode.hpp"
+#include "pow.hpp"
 #include "sha256.hpp"
 
 using namespace zkhip;
@@ -116,6 +118,27 @@ int zkt_merkle_tree(const uint64_t *leaves, size_t n_leaves, size_t per_leaf, ui
         for (size_t j = 0; j < n; ++j) sha256::hash_node(level + 64 * j, level + 64 * j + 32, up + 32 * j);
         level = up;
     }
+    return 0;
+}
+
+// candidate(state, nonce) of the proof of work (pow.hpp): the low 32 bits of SHA256(SHA256(state || be32(nonce))) as a big-endian integer
+uint32_t zkt_pow_candidate(const uint8_t *state, uint32_t nonce) { return pow::candidate(pow::prepare(state), nonce); }
+
+// the reference's grinding loop on one host thread: the first nonce start + k, k < max_tries (0: the whole 2^32 space), the mask accepts.
+// 0 with *nonce and *tried = k + 1; 1 with *tried = max_tries when there is none; -1 for bad arguments
+int zkt_pow_grind_cpu(const uint8_t *state, uint32_t start, uint32_t mask, uint64_t max_tries, uint32_t *nonce, uint64_t *tried) {
+    if (!state || !nonce || !tried || max_tries > ((uint64_t)1 << 32)) return -1;
+    const uint64_t total = max_tries ? max_tries : (uint64_t)1 << 32, k = pow::first_hit(pow::prepare(state), start, mask, total);
+    *tried = k < total ? k + 1 : total;
+    if (k == total) return 1;
+    *nonce = start + (uint32_t)k;
+    return 0;
+}
+
+// SHA2-256 of a byte string: what zkhip_sha256_host computes
+int zkt_sha256_bytes(const uint8_t *msg, size_t len, uint8_t *digest) {
+    if (!digest || (!msg && len)) return -1;
+    pow::hash_bytes(msg, len, digest);
     return 0;
 }
 

@@ -46,6 +46,7 @@ const char *zkhip_strerror(int status) {
         case ZKHIP_ERR_HIP: return "HIP runtime error (see zkhip_last_error)";
         case ZKHIP_ERR_OOM: return "out of device memory";
         case ZKHIP_ERR_RANGE: return "size or offset out of range";
+        case ZKHIP_ERR_NOT_FOUND: return "search ended without a result";
         default: return "unknown status";
     }
 }

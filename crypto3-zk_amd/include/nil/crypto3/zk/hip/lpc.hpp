@@ -31,6 +31,10 @@
 //           proof_eval<FRI> (basic_fri.hpp:747-930: lambda Merkle openings at transcript-derived indices) reads only
 //           trees and a few evaluations and is left to the caller, who finds everything it needs through
 //           trees() / fri_trees() / fri_round_polynomial(i) / fri_alphas().
+//   device  grinding (basic_fri.hpp:743-745), when fri_params.use_grinding is set: the proof of work between the commit and the query phase
+//           is searched on the GPU (hip/proof_of_work.hpp: proof_of_work_hip over the transcript's state()) and returned in
+//           fri_proof.proof_of_work.  It needs the SHA2-256 sequential transcript (hip/transcript.hpp, or any type with its state()); without
+//           use_grinding nothing is launched and the transcript sees the calls it always saw.
 //
 // Over a device group (constructor taking a device_group): commit(batch) deals the batch's polynomials over the members -- uploads over
 // their own PCIe links, extensions on their own GPUs --, then the path's one exchange: the leaf range of every LEAF OWNER (the first 2^k
@@ -60,6 +64,7 @@
 
 #include "fri.hpp"
 #include "kzg_v2.hpp"
+#include "proof_of_work.hpp"
 
 namespace nil {
 namespace crypto3 {
@@ -74,6 +79,9 @@ struct fri_params_hip {
     std::size_t log_domain = 0;
     std::vector<std::size_t> step_list;
     std::function<value_type(std::size_t log_n)> root_of_unity;
+    /// basic_fri.hpp:123-124, defaults as :156-157 (trailing, so that aggregate initialisation of the members above stays as it was)
+    bool use_grinding = false;
+    std::uint32_t grinding_parameter = 0xFFFF;    // the mask a nonce's int_challenge must clear
     /// the roots the reference's domains D[i] = make_evaluation_domain(2^(log_domain - i)) carry (fri params, basic_fri.hpp:84-118),
     /// from the curve adapter's field constants
     static fri_params_hip standard(std::size_t log_domain, std::vector<std::size_t> step_list) {
@@ -100,6 +108,11 @@ namespace detail {
     template <typename B>
     struct is_device_builder<B, std::void_t<decltype(std::declval<B &>()(std::declval<const context &>(), static_cast<const void *>(nullptr), std::size_t(),
                                                                          std::size_t(), std::size_t()))>> : std::true_type { };
+    /// a transcript that shows its state(): what the device's proof-of-work search starts from
+    template <typename T, typename = void>
+    struct has_state : std::false_type { };
+    template <typename T>
+    struct has_state<T, std::void_t<decltype(std::declval<const T &>().state())>> : std::true_type { };
     template <typename B, typename V, tree_builder_kind K>
     struct tree_builder_result;
     template <typename B, typename V>
@@ -146,6 +159,7 @@ public:
     struct fri_proof_type {
         std::vector<commitment_type> fri_roots;
         std::vector<value_type> final_polynomial;    // coefficients (math::polynomial(f.coefficients()), basic_fri.hpp:736-742)
+        std::uint32_t proof_of_work = 0;             // the grinding nonce (basic_fri.hpp:296, 743-745); 0 without use_grinding
         /* query_proofs: the caller's (see the header) */
     };
     struct proof_type {
@@ -382,7 +396,7 @@ protected:
     }
 
 public:
-    /// proof_eval (lpc.hpp:113-200) up to and including the FRI commit phase (basic_fri.hpp:705-742)
+    /// proof_eval (lpc.hpp:113-200) up to and including the FRI commit phase (basic_fri.hpp:705-742) and the grinding behind it (:743-745)
     proof_type proof_eval(transcript_type &transcript) {
         /* ZKHIP_LPC_PHASES=1: host wall time of the phases on stderr */
         const bool phases = std::getenv("ZKHIP_LPC_PHASES") != nullptr;
@@ -518,6 +532,14 @@ public:
             std::vector<std::uint64_t> h(4 * f.size());
             _ctx.d2h(h.data(), d_c.get(), h.size() * 8);
             for (std::size_t k = 0; k < f.size(); ++k) proof.fri_proof.final_polynomial.push_back(adapter::scalar_from_limbs(&h[4 * k]));
+        }
+        if (_fri_params.use_grinding) {    // Grinding (basic_fri.hpp:743-745); over a device group _ctx is member 0
+            if constexpr (detail::has_state<transcript_type>::value) {
+                proof.fri_proof.proof_of_work = proof_of_work_hip<transcript_type>::generate(_ctx, transcript, _fri_params.grinding_parameter);
+                lap("grinding");
+            } else {
+                throw std::invalid_argument("lpc proof_eval: use_grinding needs a transcript with state() (hip/transcript.hpp)");
+            }
         }
         proof.z = _z;
         return proof;

@@ -22,7 +22,7 @@ EXPORTS = [
     "zkhip_r1cs_upload", "zkhip_r1cs_free", "zkhip_r1cs_set_domain", "zkhip_r1cs_domain_size", "zkhip_r1cs_domain_kind", "zkhip_groth16_scratch_bytes", "zkhip_groth16_witness_h_dev", "zkhip_groth16_witness_h_domain_dev", "zkhip_fr_gather_dev", "zkhip_poly_resize_dev", "zkhip_fri_fold_dev", "zkhip_fri_leaves_dev", "zkhip_ec_ntt_dev",
     "zkhip_fr_vec_op_dev", "zkhip_fr_vec_affine_dev", "zkhip_fr_vec_mul_div_dev", "zkhip_fr_vec_prod_dev", "zkhip_poly_shift_dev", "zkhip_poly_eval_dev", "zkhip_poly_div_linear_dev", "zkhip_poly_div_vanishing_dev", "zkhip_poly_lincomb_dev", "zkhip_perm_grand_product_dev", "zkhip_lookup_grand_product_dev", "zkhip_lookup_sort_dev", "zkhip_perm_factor_products_dev", "zkhip_gate_eval_dev",
     "zkhip_merkle_build_dev", "zkhip_merkle_build_fri_dev", "zkhip_merkle_leaves", "zkhip_merkle_depth", "zkhip_merkle_root", "zkhip_merkle_digests", "zkhip_merkle_paths",
-    "zkhip_merkle_free",
+    "zkhip_merkle_free", "zkhip_pow_grind", "zkhip_sha256_host",
     "zkhip_group_init", "zkhip_group_destroy", "zkhip_group_size", "zkhip_group_ctx", "zkhip_group_last_error", "zkhip_group_set_transport", "zkhip_group_transport",
     "zkhip_group_all_gather", "zkhip_group_copy", "zkhip_group_sync", "zkhip_group_bases_upload", "zkhip_group_bases_from_scalars", "zkhip_group_bases_free",
     "zkhip_group_bases_size", "zkhip_group_bases_member", "zkhip_group_msm", "zkhip_group_ntt",
@@ -32,6 +32,9 @@ EXPORTS = [
 
 class ZkhipError(RuntimeError):
     pass
+
+
+ERR_NOT_FOUND = -6
 
 
 DOMAIN_BASIC, DOMAIN_EXTENDED, DOMAIN_STEP = 0, 1, 2
@@ -134,8 +137,20 @@ def load_library() -> ctypes.CDLL:
     lib.zkhip_merkle_depth.argtypes = [ctypes.c_void_p]
     lib.zkhip_merkle_free.restype = None
     lib.zkhip_merkle_free.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.zkhip_pow_grind.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_size_t,
+                                    ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)]
+    lib.zkhip_sha256_host.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p]
     _LIB = lib
     return lib
+
+
+def sha256_host(msg: bytes) -> bytes:
+    """zkhip_sha256_host: SHA2-256 of a byte string over the library's own core, on the host (no context, no GPU)"""
+    out = ctypes.create_string_buffer(32)
+    rc = load_library().zkhip_sha256_host(bytes(msg), ctypes.c_size_t(len(msg)), out)
+    if rc != 0:
+        raise ZkhipError(f"zkhip_sha256_host: {rc}")
+    return out.raw
 
 
 def _p(a):
@@ -525,6 +540,20 @@ class Context:
         self._check(self.lib.zkhip_merkle_build_fri_dev(self.h, int(hash_id), ctypes.c_void_p(d_polys), ctypes.c_size_t(log_domain), ctypes.c_size_t(batch),
                                                         ctypes.c_size_t(fri_step), ctypes.byref(h)), "zkhip_merkle_build_fri_dev")
         return MerkleTree(self, h)
+
+    # ---- proof of work (FRI grinding) over the SHA2-256 sequential transcript (zkhip_pow_grind)
+    def pow_grind(self, state: bytes, start: int, mask: int, max_tries: int = 0, chunk_log: int = 0, hash_id: int = HASH_SHA2_256):
+        """(nonce, tried): the first nonce start + k (mod 2^32), k < max_tries (0: the whole space), with candidate(state, nonce) & mask == 0, and
+        tried = k + 1; (None, tried = max_tries) when there is none (ZKHIP_ERR_NOT_FOUND)"""
+        state = bytes(state)
+        assert len(state) == 32
+        nonce, tried = ctypes.c_uint32(), ctypes.c_uint64()
+        rc = self.lib.zkhip_pow_grind(self.h, int(hash_id), state, start & 0xFFFFFFFF, mask & 0xFFFFFFFF, int(max_tries), int(chunk_log), ctypes.byref(nonce),
+                                      ctypes.byref(tried))
+        if rc == ERR_NOT_FOUND:
+            return None, tried.value
+        self._check(rc, "zkhip_pow_grind")
+        return nonce.value, tried.value
 
     def profile(self, on: bool):
         self._check(self.lib.zkhip_profile_enable(self.h, 1 if on else 0), "zkhip_profile_enable")

@@ -43,7 +43,8 @@ enum zkhip_status {
     ZKHIP_ERR_INVALID = -2,
     ZKHIP_ERR_HIP = -3,
     ZKHIP_ERR_OOM = -4,
-    ZKHIP_ERR_RANGE = -5
+    ZKHIP_ERR_RANGE = -5,
+    ZKHIP_ERR_NOT_FOUND = -6 /* a bounded search ended without a result (zkhip_pow_grind) */
 };
 
 /* ---- context -------------------------------------------------------------------------------- */
@@ -305,6 +306,33 @@ int zkhip_merkle_digests(zkhip_ctx *ctx, const zkhip_merkle *t, uint8_t *out /* 
 int zkhip_merkle_paths(zkhip_ctx *ctx, const zkhip_merkle *t, const uint64_t *leaf_indices /* host */, size_t count,
                        uint8_t *out /* host, count x depth x 32 */);
 void zkhip_merkle_free(zkhip_ctx *ctx, zkhip_merkle *t);
+
+/* ---- Proof of work (FRI grinding) over the SHA2-256 sequential transcript, searched on the device ---------------------
+ * proof_of_work<hashes::sha2<256>, std::uint32_t>::generate (commitments/detail/polynomial/proof_of_work.hpp:47-68), which
+ * proof_eval<FRI> calls between its commit and query phases when fri_params.use_grinding is set (basic_fri.hpp:743-745), over
+ * transcript::fiat_shamir_heuristic_sequential<sha2<256>> (zk/transcript/fiat_shamir.hpp:134-199).  THE CONTRACT (as for the
+ * Merkle trees: crypto3-hash and crypto3-marshalling were not at hand, and the reference's own test only checks verify() after a
+ * random start, so the bytes below are stated here and checked against an independent SHA2-256, not pinned to a crypto3 vector):
+ *   transcript     its state is one 32-byte digest; absorbing bytes makes it SHA256(state || bytes); int_challenge<uint32_t>
+ *                  makes it SHA256(state) and returns the low 32 bits of the state's BIG-ENDIAN integer (its bytes 28..31, big-endian);
+ *   nonce bytes    a nonce n is absorbed as its four bytes, most significant first (proof_of_work.hpp:54-57);
+ *   candidate      candidate(state, n) = the low 32 bits of the big-endian integer of SHA256(SHA256(state || be32(n)));
+ *   acceptance     n is accepted when (candidate(state, n) & mask) == 0;
+ *   search order   start, start + 1, start + 2, ... (mod 2^32): the reference's loop from its (there random) first value.
+ * zkhip_pow_grind returns the FIRST accepted nonce in that order: the smallest offset k < max_tries with start + k accepted --
+ * exactly what the reference's loop returns for the same start, whichever lane of the device finds a hit first.
+ *   max_tries      offsets to try, at most 2^32 (0: the whole 2^32 space);
+ *   chunk_log      the search runs in launches of 2^chunk_log consecutive offsets, the host looking for a hit between them
+ *                  (8..32; 0: the library's default) -- the result does not depend on it;
+ *   *nonce         the accepted nonce;  *tried (nullable): k + 1 on success, max_tries (2^32 for 0) when nothing was found.
+ * Returns ZKHIP_ERR_NOT_FOUND when no offset below max_tries is accepted.  Errors, before anything is launched: a null ctx /
+ * state / nonce or a hash other than ZKHIP_HASH_SHA2_256 -> ZKHIP_ERR_INVALID; chunk_log outside [8, 32] (0 aside) or
+ * max_tries > 2^32 -> ZKHIP_ERR_RANGE. */
+int zkhip_pow_grind(zkhip_ctx *ctx, int hash, const uint8_t state[32], uint32_t start, uint32_t mask, uint64_t max_tries, size_t chunk_log,
+                    uint32_t *nonce, uint64_t *tried);
+/* SHA2-256 of `len` bytes on the HOST, over the same core as the device's (needs no context and no GPU): what the shim's
+ * transcript (hip/transcript.hpp) hashes with.  ZKHIP_ERR_INVALID for a null `out`, or a null `msg` with len > 0. */
+int zkhip_sha256_host(const uint8_t *msg, size_t len, uint8_t out[32]);
 
 /* ---- DFT over group elements -------------------------------------------------------------------------------
  * evaluation_domain<Fr, G>::evaluate_all_lagrange_polynomials(powers_begin, powers_end) as the powers-of-tau result uses
