@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cassert>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -18,6 +20,7 @@
 #include "../../include/zkhip.h"
 #include "options.hpp"
 #include "table_cache.hpp"
+#include "zk_defs.hpp"
 
 #define ZK_HIP_CHECK(ctx, expr)                                                                  \
     do {                                                                                         \
@@ -33,6 +36,25 @@
         int rc__ = (expr);        \
         if (rc__ != 0) return rc__; \
     } while (0)
+
+// The head of an entry point, in two halves: ZK_ARGS refuses a null context or an unknown curve id before any HIP call, ZK_ENTER selects the
+// context's device.  A function's own argument and range checks and its "nothing to do" return sit between the two, so argument errors
+// never depend on the device and an empty call does not touch it.
+inline bool zk_curve_known(int curve) { return curve == zkhip::CURVE_BLS12_381 || curve == zkhip::CURVE_BN254; }
+inline bool zk_group_known(int group) { return group == zkhip::GROUP_G1 || group == zkhip::GROUP_G2; }
+#define ZK_ARGS(ctx, curve) if (!(ctx) || !zk_curve_known(curve)) return ZKHIP_ERR_INVALID
+#define ZK_ENTER(ctx) ZK_HIP_CHECK(ctx, hipSetDevice((ctx)->device))
+inline bool zk_any_null(const void *const *p, size_t count) {  // a host table of device pointers with a hole in it
+    return std::any_of(p, p + count, [](const void *q) { return !q; });
+}
+
+// The 1-D grid of one lane per element, `threads` lanes per workgroup.  A grid holds fewer than 2^31 workgroups: the entry points' documented
+// limits (count < 2^39 at 256 lanes, log_size <= 31, ...) all lie below that, which is asserted here and at no call site.
+inline dim3 grid_1d(size_t count, unsigned threads = 256) {
+    const size_t groups = (count + threads - 1) / threads;
+    assert(groups < ((size_t)1 << 31));
+    return dim3((unsigned)groups);
+}
 
 static constexpr int ZK_MSM_MAX_C = 21;  // largest Pippenger window (bits); 2^(c-1) buckets per set (the sort handles <= 2^20 x sets / 1024 super-buckets)
 
@@ -193,15 +215,11 @@ struct zkhip_ctx {
     std::unordered_map<void *, size_t> alloc_live;
     size_t alloc_cached_bytes = 0, opt_alloc_cache_bytes = (size_t)16 << 30;
     std::mutex alloc_mutex;
-    std::vector<uint32_t> lagrange_stage;  // host constants of zkhip_domain_lagrange_dev, alive until its copies ran
     DevBuf d_status;  // sticky device-side error flags (ZK_STATUS_*), read and cleared by zkhip_device_status
     // bump-allocated workspace, grown on demand, reused across calls
     GrowBuf<> ws;
     size_t ws_off = 0, ws_floor = 0;  // ws_floor: start of the per-call region (a batch parks data below it)
     std::unordered_set<const void *> lds_configured;  // kernels whose dynamic-LDS limit was raised on this context's device
-    std::vector<uint64_t> lincomb_stage, lincomb_coeffs;  // host staging of zkhip_poly_lincomb_dev's tables
-    std::vector<uint32_t> gate_stage;                     // host image of zkhip_gate_eval_dev's program
-    std::vector<uint32_t *> batch_ptrs;            // host copy of a batch's output pointers (alive until the copy ran)
     // HIP graphs of repeated MSM calls (msm.hip: zk_graph_run)
     std::unordered_map<std::string, ZkGraph> graphs;
     std::unordered_map<std::string, int> graph_seen;
@@ -359,6 +377,20 @@ int ws_place(zkhip_ctx *ctx, Layout &l, size_t above = 0) {
         ctx->last_error = "workspace layout took " + std::to_string(ctx->ws_off - ctx->ws_floor) + " bytes of " + std::to_string(end - ctx->ws_floor) + " reserved";
         return ZKHIP_ERR_RANGE;
     }
+    return 0;
+}
+
+// How a small per-call table (pointers, challenges, a program image) gets to the device: this one route.  Its source is the caller's array or
+// a function-local vector, and either may die when the call returns: by the runtime's own rule (hip_runtime_api.h, the note on hipMemcpyAsync:
+// "if host or dest are not pinned, the memcpy will be performed synchronously") a source that is not page-locked has been consumed when
+// hipMemcpyAsync returns.  That rule is also why a stream capture cannot take such a copy: inside one, a table must already sit in device
+// memory the capture owns (msm.hip: ZkGraph::d_ptrs, handed over as batch_dptrs_override), so there is nothing to upload and the helper refuses.
+inline int ws_upload(zkhip_ctx *ctx, void *d_dst, const void *src, size_t bytes) {
+    if (ctx->capturing) {
+        ctx->last_error = "host table upload during graph capture";
+        return ZKHIP_ERR_HIP;
+    }
+    ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
     return 0;
 }
 

@@ -74,7 +74,7 @@ bool zk_dom_choice(size_t min_size, size_t s, int *kind, size_t *m) {
 
 int zk_dom_parse(int curve, const zkhip_domain *d, ZkDomain *out) {
     if (!d || !out) return ZKHIP_ERR_INVALID;
-    if (curve != CURVE_BLS12_381 && curve != CURVE_BN254) return ZKHIP_ERR_INVALID;
+    if (!zk_curve_known(curve)) return ZKHIP_ERR_INVALID;
     ZkDomain z;
     z.kind = d->kind;
     z.m = d->m;
@@ -242,9 +242,9 @@ static int dom_get_tables(zkhip_ctx *ctx, int curve, const ZkDomain &d, const ui
     ZK_TRY(d_in.alloc(ctx, 96));
     ZK_TRY(t->d_consts.alloc(ctx, DC_COUNT * 32));
     ZK_HIP_CHECK(ctx, hipMemsetAsync(t->d_consts, 0, DC_COUNT * 32, ctx->stream));
-    ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_in, d.omega, 32, hipMemcpyHostToDevice, ctx->stream));
-    ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_in + 8, d.kind == ZKHIP_DOMAIN_EXTENDED_RADIX2 ? d.shift : one, 32, hipMemcpyHostToDevice, ctx->stream));
-    ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_in + 16, coset ? coset : one, 32, hipMemcpyHostToDevice, ctx->stream));
+    ZK_TRY(ws_upload(ctx, d_in, d.omega, 32));
+    ZK_TRY(ws_upload(ctx, d_in + 8, d.kind == ZKHIP_DOMAIN_EXTENDED_RADIX2 ? d.shift : one, 32));
+    ZK_TRY(ws_upload(ctx, d_in + 16, coset ? coset : one, 32));
     ZK_LAUNCH(ctx, "dom_setup", dom_setup<U>, dim3(1), dim3(64), 0, d.kind, d_in, (uint64_t)d.n0, (uint64_t)d.n1, t->d_consts);
     if (d.kind == ZKHIP_DOMAIN_STEP_RADIX2) {
         const size_t compr = d.n0 / d.n1;
@@ -252,8 +252,8 @@ static int dom_get_tables(zkhip_ctx *ctx, int curve, const ZkDomain &d, const ui
         h_pow<U>(d.omega, 2 * compr, t->w1);
         ZK_TRY(t->d_T.alloc(ctx, d.n0 * 32));
         ZK_TRY(t->d_Tinv.alloc(ctx, d.n1 * 32));
-        ZK_LAUNCH(ctx, "dom_setup", dom_pow_table<U>, dim3((unsigned)((d.n0 + 255) / 256)), dim3(256), 0, t->d_consts, (int)DC_BASE, (uint64_t)d.n0, t->d_T);
-        ZK_LAUNCH(ctx, "dom_setup", dom_pow_table<U>, dim3((unsigned)((d.n1 + 255) / 256)), dim3(256), 0, t->d_consts, (int)DC_BASEINV, (uint64_t)d.n1, t->d_Tinv);
+        ZK_LAUNCH(ctx, "dom_setup", dom_pow_table<U>, grid_1d(d.n0), dim3(256), 0, t->d_consts, (int)DC_BASE, (uint64_t)d.n0, t->d_T);
+        ZK_LAUNCH(ctx, "dom_setup", dom_pow_table<U>, grid_1d(d.n1), dim3(256), 0, t->d_consts, (int)DC_BASEINV, (uint64_t)d.n1, t->d_Tinv);
         t->nz = compr;
     } else {
         memcpy(t->w0, d.omega, 32);
@@ -264,7 +264,7 @@ static int dom_get_tables(zkhip_ctx *ctx, int curve, const ZkDomain &d, const ui
     }
     if (coset) {
         ZK_TRY(t->d_zinv.alloc(ctx, (t->nz + 1) * 32));
-        ZK_LAUNCH(ctx, "dom_setup", dom_zinv_table<U>, dim3((unsigned)((t->nz + 1 + 63) / 64)), dim3(64), 0, d.kind, t->d_consts, (uint64_t)t->nz, t->d_zinv);
+        ZK_LAUNCH(ctx, "dom_setup", dom_zinv_table<U>, grid_1d(t->nz + 1, 64), dim3(64), 0, d.kind, t->d_consts, (uint64_t)t->nz, t->d_zinv);
     }
     ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     *out = t.get();
@@ -449,11 +449,11 @@ static int dom_fft_split_t(zkhip_ctx *ctx, int curve, const ZkDomain &d, uint32_
     if (batch >= (1u << 16)) return ZKHIP_ERR_RANGE;
     if (d.kind == ZKHIP_DOMAIN_EXTENDED_RADIX2) {
         const uint64_t total = (uint64_t)batch * d.n0;
-        const unsigned grid = (unsigned)((total + 255) / 256);
-        if (!inverse) ZK_LAUNCH(ctx, "dom_mix", ext_mix<U>, dim3(grid), dim3(256), 0, p0, p1, total, 0, t->d_consts);
+        const dim3 grid = grid_1d(total);
+        if (!inverse) ZK_LAUNCH(ctx, "dom_mix", ext_mix<U>, grid, dim3(256), 0, p0, p1, total, 0, t->d_consts);
         ZK_TRY(zk_ntt_run(ctx, curve, p0, l0, batch, t->w0, inverse, coset));
         ZK_TRY(zk_ntt_run(ctx, curve, p1, l1, batch, t->w1, inverse, t->coset1));
-        if (inverse) ZK_LAUNCH(ctx, "dom_mix", ext_mix<U>, dim3(grid), dim3(256), 0, p0, p1, total, 1, t->d_consts);
+        if (inverse) ZK_LAUNCH(ctx, "dom_mix", ext_mix<U>, grid, dim3(256), 0, p0, p1, total, 1, t->d_consts);
         return 0;
     }
     // step
@@ -483,7 +483,7 @@ static int dom_fft_split_t(zkhip_ctx *ctx, int curve, const ZkDomain &d, uint32_
         ZK_TRY(zk_ntt_run(ctx, curve, p0, l0, batch, t->w0, 1, coset));
         ZK_TRY(zk_ntt_run(ctx, curve, p1, l1, batch, t->w1, 1, nullptr));
         ZK_TRY(colsums(nullptr, colsum));
-        ZK_LAUNCH(ctx, "dom_mix", step_inv_post<U>, dim3((unsigned)((d.n1 + 255) / 256), (unsigned)batch), dim3(256), 0, p0, p1, (uint64_t)d.n0, (uint64_t)d.n1,
+        ZK_LAUNCH(ctx, "dom_mix", step_inv_post<U>, dim3(grid_1d(d.n1).x, (unsigned)batch), dim3(256), 0, p0, p1, (uint64_t)d.n0, (uint64_t)d.n1,
                   colsum, t->d_Tinv, t->d_consts);
     }
     return 0;
@@ -492,9 +492,7 @@ static int dom_fft_split_t(zkhip_ctx *ctx, int curve, const ZkDomain &d, uint32_
 int zk_dom_fft_split(zkhip_ctx *ctx, int curve, const ZkDomain &d, uint32_t *p0, uint32_t *p1, size_t batch, int inverse, const uint64_t *coset,
                      uint32_t *scratch) {
     if (batch == 0) return 0;
-    if (curve == CURVE_BLS12_381) return dom_fft_split_t<BlsFrU>(ctx, curve, d, p0, p1, batch, inverse, coset, scratch);
-    if (curve == CURVE_BN254) return dom_fft_split_t<BnFrU>(ctx, curve, d, p0, p1, batch, inverse, coset, scratch);
-    return ZKHIP_ERR_INVALID;
+    return fr_dispatch(curve, [&](auto u) -> int { return dom_fft_split_t<typename decltype(u)::type>(ctx, curve, d, p0, p1, batch, inverse, coset, scratch); });
 }
 
 // 1 / Z on the coset g * domain: *d_zinv holds nz entries for part 0 (entry i mod nz) followed by the entry of part 1
@@ -540,7 +538,7 @@ static int dom_zinv_t(zkhip_ctx *ctx, int curve, const ZkDomain &d, const uint64
     memcpy(t->coset, coset, 32);
     ZK_TRY(d_in.alloc(ctx, 32));
     ZK_TRY(t->d_zinv.alloc(ctx, 64));
-    ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_in, coset, 32, hipMemcpyHostToDevice, ctx->stream));
+    ZK_TRY(ws_upload(ctx, d_in, coset, 32));
     ZK_LAUNCH(ctx, "dom_setup", dom_zinv_basic<U>, dim3(1), dim3(64), 0, d_in, (uint64_t)d.m, t->d_zinv);
     ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     *d_zinv = t->d_zinv;
@@ -548,9 +546,7 @@ static int dom_zinv_t(zkhip_ctx *ctx, int curve, const ZkDomain &d, const uint64
 }
 int zk_dom_zinv(zkhip_ctx *ctx, int curve, const ZkDomain &d, const uint64_t *coset, const uint32_t **d_zinv, size_t *nz) {
     if (!coset) return ZKHIP_ERR_INVALID;
-    if (curve == CURVE_BLS12_381) return dom_zinv_t<BlsFrU>(ctx, curve, d, coset, d_zinv, nz);
-    if (curve == CURVE_BN254) return dom_zinv_t<BnFrU>(ctx, curve, d, coset, d_zinv, nz);
-    return ZKHIP_ERR_INVALID;
+    return fr_dispatch(curve, [&](auto u) -> int { return dom_zinv_t<typename decltype(u)::type>(ctx, curve, d, coset, d_zinv, nz); });
 }
 
 // ---- every Lagrange polynomial of a domain at one point (key generation: r1cs_to_qap.hpp:152-153) ----------------------------------
@@ -628,16 +624,16 @@ struct HF {
 
 // one dom_lagrange launch: out[off + i] = c w^i / (t - w^i) or c / (w^i - t)
 template <class U>
-static int lagrange_launch(zkhip_ctx *ctx, uint32_t *d_consts, uint32_t *h_consts, int slot, const HF<U> &w, const HF<U> &t, const HF<U> &c, size_t n, int unit,
-                           uint32_t *d_out, size_t off) {
-    uint32_t *h = h_consts + slot * 32, *d = d_consts + slot * 32;
+static int lagrange_launch(zkhip_ctx *ctx, uint32_t *d_consts, int slot, const HF<U> &w, const HF<U> &t, const HF<U> &c, size_t n, int unit, uint32_t *d_out,
+                           size_t off) {
+    uint32_t h[32], *d = d_consts + slot * 32;
     w.store_mont(h);
     w.inv().store_mont(h + 8);
     t.store_mont(h + 16);
     c.store_mont(h + 24);
-    ZK_HIP_CHECK(ctx, hipMemcpyAsync(d, h, 128, hipMemcpyHostToDevice, ctx->stream));
+    ZK_TRY(ws_upload(ctx, d, h, 128));
     const size_t lanes = (n + LAG_CHUNK - 1) / LAG_CHUNK;
-    ZK_LAUNCH(ctx, "dom_lagrange", dom_lagrange<U>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, d, (uint64_t)n, unit, d_out, (uint64_t)off);
+    ZK_LAUNCH(ctx, "dom_lagrange", dom_lagrange<U>, grid_1d(lanes, 64), dim3(64), 0, d, (uint64_t)n, unit, d_out, (uint64_t)off);
     return ZKHIP_OK;
 }
 
@@ -654,16 +650,13 @@ template <class U>
 static int dom_lagrange_t(zkhip_ctx *ctx, const ZkDomain &d, const uint64_t *t_c, uint32_t *d_out) {
     typedef HF<U> F;
     const F one = F::one(), t = F::from(t_c), w = F::from(d.omega);
-    // constants of up to four launches, staged in page-able host memory that must outlive the copies: kept in the context
-    ctx->lagrange_stage.assign(4 * 32, 0u);
-    uint32_t *h = ctx->lagrange_stage.data();
     LagrangeBuffers wsb = {d.kind == ZKHIP_DOMAIN_STEP_RADIX2 ? d.n0 / d.n1 : 0};
     ZK_TRY(ws_place(ctx, wsb));
     uint32_t *const dc = wsb.consts, *const d_dinv = wsb.dinv;
     auto basic = [&](int slot, const F &root, const F &at, const F &scale, size_t n, size_t off) {
         // scale * l_i(at) over <root>: l_i = (at^n - 1) root^i / (n (at - root^i))
         const F c = (at.pow(n) - one) * F::u64(n).inv() * scale;
-        return lagrange_launch<U>(ctx, dc, h, slot, root, at, c, n, 0, d_out, off);
+        return lagrange_launch<U>(ctx, dc, slot, root, at, c, n, 0, d_out, off);
     };
     int rc = ZKHIP_OK;
     if (d.kind == ZKHIP_DOMAIN_BASIC_RADIX2) {
@@ -681,15 +674,15 @@ static int dom_lagrange_t(zkhip_ctx *ctx, const ZkDomain &d, const uint64_t *t_c
         const size_t big = d.n0, small = d.n1, compr = big / small;
         const F big_w = w * w, small_w = w.pow(2 * compr), w_sm = w.pow(small), L0 = t.pow(small) - w_sm;
         if ((t.pow(big) - one).is_zero() || L0.is_zero()) return ZKHIP_ERR_INVALID;
-        rc = lagrange_launch<U>(ctx, dc, h, 0, big_w.pow(small), w_sm, one, compr, 1, d_dinv, 0);  // 1 / (step^j - omega^small)
+        rc = lagrange_launch<U>(ctx, dc, 0, big_w.pow(small), w_sm, one, compr, 1, d_dinv, 0);  // 1 / (step^j - omega^small)
         if (rc == ZKHIP_OK) rc = basic(1, big_w, t, L0, big, 0);
         if (rc == ZKHIP_OK)
-            ZK_LAUNCH(ctx, "dom_lagrange", dom_scale_by_table<U>, dim3((unsigned)((big + 255) / 256)), dim3(256), 0, d_out, (uint64_t)big, d_dinv, (uint64_t)compr);
+            ZK_LAUNCH(ctx, "dom_lagrange", dom_scale_by_table<U>, grid_1d(big), dim3(256), 0, d_out, (uint64_t)big, d_dinv, (uint64_t)compr);
         const F L1 = (t.pow(big) - one) * (w.pow(big) - one).inv();
         if (rc == ZKHIP_OK) rc = basic(2, small_w, t * w.inv(), L1, small, big);
     }
     if (rc != ZKHIP_OK) return rc;
-    ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // the staged constants and the workspace table may be reused after return
+    ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // kept: return-after-completion is current behaviour (EXPERIMENTS 18: guards nothing now)
     return ZKHIP_OK;
 }
 
@@ -706,9 +699,8 @@ int zkhip_domain_lagrange_dev(zkhip_ctx *ctx, int curve, const zkhip_domain *dom
     if (!ctx || !dom || !t || !d_out) return ZKHIP_ERR_INVALID;
     ZkDomain d;
     ZK_TRY(zk_dom_parse(curve, dom, &d));
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (curve == CURVE_BLS12_381) return dom_lagrange_t<BlsFrU>(ctx, d, t, (uint32_t *)d_out);
-    return dom_lagrange_t<BnFrU>(ctx, d, t, (uint32_t *)d_out);
+    ZK_ENTER(ctx);
+    return fr_dispatch(curve, [&](auto u) -> int { return dom_lagrange_t<typename decltype(u)::type>(ctx, d, t, (uint32_t *)d_out); });
 }
 
 int zkhip_domain_fft_dev(zkhip_ctx *ctx, int curve, const zkhip_domain *dom, void *d_data, size_t batch, int inverse, const uint64_t *coset_gen) {
@@ -716,7 +708,7 @@ int zkhip_domain_fft_dev(zkhip_ctx *ctx, int curve, const zkhip_domain *dom, voi
     ZkDomain d;
     ZK_TRY(zk_dom_parse(curve, dom, &d));
     if (batch == 0) return ZKHIP_OK;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ZK_ENTER(ctx);
     if (d.kind == ZKHIP_DOMAIN_BASIC_RADIX2) return zk_ntt_run(ctx, curve, (uint32_t *)d_data, ceil_log2(d.m), batch, d.omega, inverse, coset_gen);
     // split copy of the batch + the step domain's partial sums, in a scratch buffer the context keeps
     const size_t need = (batch * d.m + zk_dom_scratch_elems(d, batch)) * 32;
@@ -724,10 +716,10 @@ int zkhip_domain_fft_dev(zkhip_ctx *ctx, int curve, const zkhip_domain *dom, voi
     uint32_t *p0 = ctx->dom_ws.as<uint32_t>(), *p1 = p0 + batch * d.n0 * 8, *scratch = p1 + batch * d.n1 * 8;
     const uint64_t total = (uint64_t)batch * d.m;
     if (total >= ((uint64_t)1 << 39)) return ZKHIP_ERR_RANGE;
-    const unsigned grid = (unsigned)((total + 255) / 256);
-    ZK_LAUNCH(ctx, "dom_split", dom_split_copy, dim3(grid), dim3(256), 0, (uint4 *)d_data, (uint4 *)p0, (uint4 *)p1, (uint64_t)d.m, (uint64_t)d.n0, total, 1);
+    const dim3 grid = grid_1d(total);
+    ZK_LAUNCH(ctx, "dom_split", dom_split_copy, grid, dim3(256), 0, (uint4 *)d_data, (uint4 *)p0, (uint4 *)p1, (uint64_t)d.m, (uint64_t)d.n0, total, 1);
     ZK_TRY(zk_dom_fft_split(ctx, curve, d, p0, p1, batch, inverse, coset_gen, scratch));
-    ZK_LAUNCH(ctx, "dom_split", dom_split_copy, dim3(grid), dim3(256), 0, (uint4 *)d_data, (uint4 *)p0, (uint4 *)p1, (uint64_t)d.m, (uint64_t)d.n0, total, 0);
+    ZK_LAUNCH(ctx, "dom_split", dom_split_copy, grid, dim3(256), 0, (uint4 *)d_data, (uint4 *)p0, (uint4 *)p1, (uint64_t)d.m, (uint64_t)d.n0, total, 0);
     return ZKHIP_OK;
 }
 

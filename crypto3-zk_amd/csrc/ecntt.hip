@@ -314,34 +314,34 @@ int ec_ntt_t(zkhip_ctx *ctx, uint32_t *d_jac, size_t log_m, const uint64_t *omeg
     const uint32_t m = 1u << log_m, ntw = std::max<uint32_t>(1, m / 2);
     // table slots: the lanes of one multiplication launch (<= 1 GiB of tables; a pass over more lanes runs in several launches)
     const size_t slot_bytes = (size_t)8 * HALVES * PW * 4;
-    const size_t slot_cap = ctx->opt_ec_ntt_table_lanes ? ((size_t)ctx->opt_ec_ntt_table_lanes + 63) / 64 * 64 : ((size_t)1 << 30) / slot_bytes / 64 * 64;
-    const uint32_t slots = (uint32_t)std::max<size_t>(64, std::min<size_t>(((size_t)m + 63) / 64 * 64, slot_cap));
+    const size_t slot_cap = ctx->opt_ec_ntt_table_lanes ? (((size_t)ctx->opt_ec_ntt_table_lanes + 63) & ~(size_t)63) : ((size_t)1 << 30) / slot_bytes / 64 * 64;
+    const uint32_t slots = (uint32_t)std::max<size_t>(64, std::min<size_t>(((size_t)m + 63) & ~(size_t)63, slot_cap));
     EcNttBuffers w = {(size_t)m * PW, (size_t)ntw * REC_WORDS, (size_t)slots * slot_bytes / 4};
     ZK_TRY(ws_place(ctx, w));
     uint32_t *pts = w.pts, *rec = w.rec, *rec_last = w.rec_last, *consts = w.consts, *tbl = w.tbl;
     uint32_t *d_w = consts + 32, *d_one = consts + 48, *rec_minv = consts + 64;
     uint32_t one[8] = {1, 0, 0, 0, 0, 0, 0, 0};
-    ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_w, omega, 32, hipMemcpyHostToDevice, ctx->stream));
+    ZK_TRY(ws_upload(ctx, d_w, omega, 32));
     ZK_LAUNCH(ctx, "ec_ntt_setup", ec_ntt_setup<U>, dim3(1), dim3(64), 0, d_w, (uint32_t)log_m, inverse, consts);
-    ZK_LAUNCH(ctx, "ec_ntt_records", (ec_ntt_records<U, G>), dim3((ntw + 255) / 256), dim3(256), 0, consts, (const uint32_t *)nullptr, ntw, rec);
+    ZK_LAUNCH(ctx, "ec_ntt_records", (ec_ntt_records<U, G>), grid_1d(ntw), dim3(256), 0, consts, (const uint32_t *)nullptr, ntw, rec);
     if (inverse && log_m > 0) {
-        ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_one, one, 32, hipMemcpyHostToDevice, ctx->stream));
-        ZK_LAUNCH(ctx, "ec_ntt_records", (ec_ntt_records<U, G>), dim3((ntw + 255) / 256), dim3(256), 0, consts, consts + U::NL, ntw, rec_last);
+        ZK_TRY(ws_upload(ctx, d_one, one, 32));
+        ZK_LAUNCH(ctx, "ec_ntt_records", (ec_ntt_records<U, G>), grid_1d(ntw), dim3(256), 0, consts, consts + U::NL, ntw, rec_last);
         ZK_LAUNCH(ctx, "ec_ntt_records", (ec_ntt_records<U, G>), dim3(1), dim3(256), 0, d_one, consts + U::NL, 1u, rec_minv);
     }
-    ZK_LAUNCH(ctx, "ec_ntt_load", ec_ntt_load<F>, dim3((m + 63) / 64), dim3(64), 0, d_jac, (uint32_t)log_m, pts);
+    ZK_LAUNCH(ctx, "ec_ntt_load", ec_ntt_load<F>, grid_1d(m, 64), dim3(64), 0, d_jac, (uint32_t)log_m, pts);
     for (uint32_t s = 1; s <= log_m; ++s) {
         const int mode = (inverse && s == log_m) ? 1 : 0;
         const uint32_t total = mode ? m : m / 2;
         if (mode == 1 || s > 1)  // stage 1 has no twiddle but 1
             for (uint32_t first = 0; first < total; first += slots) {
                 const uint32_t lanes = std::min(slots, total - first);
-                ZK_LAUNCH(ctx, "ec_ntt_mul_pass", (ec_ntt_mul_pass<F, G>), dim3((lanes + 63) / 64), dim3(64), 0, pts, rec, rec_last, rec_minv, (uint32_t)log_m, s,
+                ZK_LAUNCH(ctx, "ec_ntt_mul_pass", (ec_ntt_mul_pass<F, G>), grid_1d(lanes, 64), dim3(64), 0, pts, rec, rec_last, rec_minv, (uint32_t)log_m, s,
                           mode, first, total, tbl);
             }
-        ZK_LAUNCH(ctx, "ec_ntt_butterflies", ec_ntt_butterflies<F>, dim3((m / 2 + 63) / 64), dim3(64), 0, pts, (uint32_t)log_m, s);
+        ZK_LAUNCH(ctx, "ec_ntt_butterflies", ec_ntt_butterflies<F>, grid_1d(m / 2, 64), dim3(64), 0, pts, (uint32_t)log_m, s);
     }
-    ZK_LAUNCH(ctx, "ec_ntt_store", ec_ntt_store<F>, dim3((m + 63) / 64), dim3(64), 0, pts, m, d_jac);
+    ZK_LAUNCH(ctx, "ec_ntt_store", ec_ntt_store<F>, grid_1d(m, 64), dim3(64), 0, pts, m, d_jac);
     return ZKHIP_OK;
 }
 
@@ -350,7 +350,7 @@ int ec_ntt_t(zkhip_ctx *ctx, uint32_t *d_jac, size_t log_m, const uint64_t *omeg
 extern "C" int zkhip_ec_ntt_dev(zkhip_ctx *ctx, int curve, int group, void *d_jacobian, size_t log_m, const uint64_t *omega, int inverse) {
     if (!ctx || !d_jacobian || !omega) return ZKHIP_ERR_INVALID;
     if (log_m > 26) return ZKHIP_ERR_RANGE;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ZK_ENTER(ctx);
     uint32_t *d = (uint32_t *)d_jacobian;
     if (curve == CURVE_BLS12_381 && group == GROUP_G1) return ec_ntt_t<CurveTraits<CURVE_BLS12_381, GROUP_G1>::F, BlsFrU, BlsGlv>(ctx, d, log_m, omega, inverse);
     if (curve == CURVE_BLS12_381 && group == GROUP_G2) return ec_ntt_t<CurveTraits<CURVE_BLS12_381, GROUP_G2>::F, BlsFrU, NoGlv>(ctx, d, log_m, omega, inverse);

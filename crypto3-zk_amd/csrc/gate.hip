@@ -90,15 +90,6 @@ __global__ __launch_bounds__(256) void gate_eval(const uint32_t *const *__restri
 
 }  // namespace
 
-#define ZK_FR_DISPATCH(curve, ...)      \
-    if ((curve) == CURVE_BLS12_381) {   \
-        typedef BlsFrU U;               \
-        __VA_ARGS__;                    \
-    } else {                            \
-        typedef BnFrU U;                \
-        __VA_ARGS__;                    \
-    }
-
 struct GateBuffers {  // the program's image as uploaded; its coefficients in Montgomery form (16-word slots)
     size_t img_words, terms;
     uint32_t *img, *mont;
@@ -110,9 +101,9 @@ struct GateBuffers {  // the program's image as uploaded; its coefficients in Mo
 };
 extern "C" int zkhip_gate_eval_dev(zkhip_ctx *ctx, int curve, const zkhip_gate_program *prog, const void *const *d_slots, size_t log_size, const void *d_mask,
                                    int accumulate, void *d_out) {
-    if (!ctx || !prog || !d_out) return ZKHIP_ERR_INVALID;
-    if (curve != CURVE_BLS12_381 && curve != CURVE_BN254) return ZKHIP_ERR_INVALID;
-    if (log_size > 31) return ZKHIP_ERR_RANGE;  // one lane per row: (size + 255) / 256 workgroups within the grid limit
+    ZK_ARGS(ctx, curve);
+    if (!prog || !d_out) return ZKHIP_ERR_INVALID;
+    if (log_size > 31) return ZKHIP_ERR_RANGE;  // one lane per row
     const uint32_t G = prog->n_gates, T = prog->n_terms, F = prog->n_factors, S = prog->n_slots;
     if ((G && (!prog->gate_terms || !prog->gate_selector || !prog->gate_selector_rot)) || (T && (!prog->term_factors || !prog->term_coeff)) ||
         (F && (!prog->factor_slot || !prog->factor_rot)) || (S && !d_slots))
@@ -134,14 +125,12 @@ extern "C" int zkhip_gate_eval_dev(zkhip_ctx *ctx, int curve, const zkhip_gate_p
     } else if (F) return ZKHIP_ERR_INVALID;
     for (uint32_t f = 0; f < F; ++f)
         if (prog->factor_slot[f] >= S) return ZKHIP_ERR_RANGE;
-    for (uint32_t s = 0; s < S; ++s)
-        if (!d_slots[s]) return ZKHIP_ERR_INVALID;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (zk_any_null(d_slots, S)) return ZKHIP_ERR_INVALID;
+    ZK_ENTER(ctx);
 
     // host image: canonical coefficients (32-byte entries first: aligned) | pointers | gates | terms | factors | lifts, one upload
     const size_t w_coeff = (size_t)T * 8, w_ptr = (size_t)S * 2, w_gate = (size_t)G * 4, w_term = (size_t)T * 2, w_fac = (size_t)F * 2, w_lift = T;
-    std::vector<uint32_t> &img = ctx->gate_stage;
-    img.assign(w_coeff + w_ptr + w_gate + w_term + w_fac + w_lift + 8, 0);
+    std::vector<uint32_t> img(w_coeff + w_ptr + w_gate + w_term + w_fac + w_lift + 8, 0);
     uint32_t *h_coeff = img.data(), *h_ptr = h_coeff + w_coeff, *h_gate = h_ptr + w_ptr, *h_term = h_gate + w_gate, *h_fac = h_term + w_term, *h_lift = h_fac + w_fac;
     for (uint32_t s = 0; s < S; ++s) {
         const uint64_t p = (uint64_t)(uintptr_t)d_slots[s];
@@ -157,19 +146,20 @@ extern "C" int zkhip_gate_eval_dev(zkhip_ctx *ctx, int curve, const zkhip_gate_p
     for (uint32_t f = 0; f < F; ++f) h_fac[2 * f] = prog->factor_slot[f], h_fac[2 * f + 1] = (uint32_t)prog->factor_rot[f];
     if (T) memcpy(h_coeff, prog->term_coeff, (size_t)T * 32);
 
-    const size_t img_bytes = img.size() * 4;
     GateBuffers w = {img.size(), std::max<size_t>(1, T)};
     ZK_TRY(ws_place(ctx, w));
-    uint32_t *d_img = w.img, *d_mont = w.mont;
-    ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_img, img.data(), img_bytes, hipMemcpyHostToDevice, ctx->stream));
-    ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // pageable source: the staging vector may be refilled by the next call
-    const uint32_t *dd_coeff = d_img;
-    const uint32_t *const *dd_ptr = reinterpret_cast<const uint32_t *const *>(d_img + w_coeff);
-    const uint32_t *dd_gate = d_img + w_coeff + w_ptr, *dd_term = dd_gate + w_gate, *dd_fac = dd_term + w_term, *dd_lift = dd_fac + w_fac;
+    ZK_TRY(ws_upload(ctx, w.img, img.data(), img.size() * 4));
+    ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // kept: this point has always waited for the stream (EXPERIMENTS 18: guards nothing now)
+    const uint32_t *dd_coeff = w.img;
+    const uint32_t *const *dd_ptr = reinterpret_cast<const uint32_t *const *>(w.img + w_coeff);
+    const uint32_t *dd_gate = w.img + w_coeff + w_ptr, *dd_term = dd_gate + w_gate, *dd_fac = dd_term + w_term, *dd_lift = dd_fac + w_fac;
     const size_t size = (size_t)1 << log_size;
-    ZK_FR_DISPATCH(curve, static_assert(U::SL <= 16, "coefficient slot");
-                   if (T) ZK_LAUNCH(ctx, "gate_coeff_setup", gate_coeff_setup<U>, dim3((T + 63) / 64), dim3(64), 0, dd_coeff, dd_lift, T, d_mont);
-                   ZK_LAUNCH(ctx, "gate_eval", gate_eval<U>, dim3((unsigned)((size + 255) / 256)), dim3(256), 0, dd_ptr, dd_gate, dd_term, dd_fac, d_mont, G,
-                             (uint32_t)log_size, (const uint32_t *)d_mask, accumulate, (uint32_t *)d_out));
-    return ZKHIP_OK;
+    return fr_dispatch(curve, [&](auto u) -> int {
+        using U = typename decltype(u)::type;
+        static_assert(U::SL <= 16, "coefficient slot");
+        if (T) ZK_LAUNCH(ctx, "gate_coeff_setup", gate_coeff_setup<U>, grid_1d(T, 64), dim3(64), 0, dd_coeff, dd_lift, T, w.mont);
+        ZK_LAUNCH(ctx, "gate_eval", gate_eval<U>, grid_1d(size), dim3(256), 0, dd_ptr, dd_gate, dd_term, dd_fac, w.mont, G, (uint32_t)log_size,
+                  (const uint32_t *)d_mask, accumulate, (uint32_t *)d_out);
+        return ZKHIP_OK;
+    });
 }

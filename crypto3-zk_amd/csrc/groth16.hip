@@ -209,7 +209,7 @@ static int r1cs_upload_t(zkhip_ctx *ctx, zkhip_r1cs *r, const uint32_t *const ro
             ZK_TRY(d_c.alloc(ctx, nnz * 32));
             ZK_HIP_CHECK(ctx, hipMemcpyAsync(r->col[k], col[k], nnz * 4, hipMemcpyHostToDevice, ctx->stream));
             ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_c, coeff[k], nnz * 32, hipMemcpyHostToDevice, ctx->stream));
-            ZK_LAUNCH(ctx, "r1cs_coeff_to_mont", r1cs_coeff_to_mont<U>, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, d_c, nnz, r->coeff[k]);
+            ZK_LAUNCH(ctx, "r1cs_coeff_to_mont", r1cs_coeff_to_mont<U>, grid_1d(nnz), dim3(256), 0, d_c, nnz, r->coeff[k]);
             ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         }
         ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -225,7 +225,7 @@ static int witness_h_t(zkhip_ctx *ctx, const zkhip_r1cs *r, const uint32_t *d_z,
     uint32_t *p0 = d_scratch, *p1 = p0 + (size_t)3 * n0 * 8, *dscr = p1 + (size_t)3 * n1 * 8;
     for (int k = 0; k < 3; ++k) {
         const SplitVec out{p0 + (size_t)k * n0 * 8, p1 + (size_t)k * n1 * 8, n0};
-        ZK_LAUNCH(ctx, "r1cs_eval_rows", r1cs_eval_rows<U>, dim3((M + 255) / 256), dim3(256), 0, r->rowptr[k], r->col[k], r->coeff[k], d_z, M, out);
+        ZK_LAUNCH(ctx, "r1cs_eval_rows", r1cs_eval_rows<U>, grid_1d(M), dim3(256), 0, r->rowptr[k], r->col[k], r->coeff[k], d_z, M, out);
         if (r->n_long[k]) {
             // slices of ~4096 terms, at most 64 per row; per-slice partial sums live in the context workspace
             uint32_t nslice = (uint32_t)std::max<size_t>(1, std::min<size_t>(64, r->long_terms[k] / ((size_t)r->n_long[k] * 4096)));
@@ -234,11 +234,11 @@ static int witness_h_t(zkhip_ctx *ctx, const zkhip_r1cs *r, const uint32_t *d_z,
             uint32_t *partial = w.p;
             ZK_LAUNCH(ctx, "r1cs_eval_long", r1cs_eval_long<U>, dim3(r->n_long[k], nslice), dim3(256), 0, r->long_rows[k], r->rowptr[k], r->col[k],
                       r->coeff[k], d_z, partial);
-            ZK_LAUNCH(ctx, "r1cs_eval_long", r1cs_long_combine<U>, dim3((r->n_long[k] + 63) / 64), dim3(64), 0, r->long_rows[k], r->n_long[k], nslice,
+            ZK_LAUNCH(ctx, "r1cs_eval_long", r1cs_long_combine<U>, grid_1d(r->n_long[k], 64), dim3(64), 0, r->long_rows[k], r->n_long[k], nslice,
                       partial, out);
         }
     }
-    if (m > M) ZK_LAUNCH(ctx, "r1cs_fill_tail", r1cs_fill_tail<U>, dim3((3 * (m - M) + 255) / 256), dim3(256), 0, p0, p1, n0, n1, d_z, M, (uint32_t)r->n, m);
+    if (m > M) ZK_LAUNCH(ctx, "r1cs_fill_tail", r1cs_fill_tail<U>, grid_1d(3 * (m - M)), dim3(256), 0, p0, p1, n0, n1, d_z, M, (uint32_t)r->n, m);
     // coefficients, then evaluations on the coset g * domain
     ZK_TRY(zk_dom_fft_split(ctx, r->curve, dom, p0, p1, 3, 1, nullptr, dscr));
     ZK_TRY(zk_dom_fft_split(ctx, r->curve, dom, p0, p1, 3, 0, coset, dscr));
@@ -246,7 +246,7 @@ static int witness_h_t(zkhip_ctx *ctx, const zkhip_r1cs *r, const uint32_t *d_z,
     const uint32_t *zinv = nullptr;
     size_t nz = 1;
     ZK_TRY(zk_dom_zinv(ctx, r->curve, dom, coset, &zinv, &nz));
-    ZK_LAUNCH(ctx, "groth16_h_pointwise", groth16_h_pointwise<U>, dim3((m + 255) / 256), dim3(256), 0, p0, p1, n0, n1, zinv, (uint32_t)nz, d_h);
+    ZK_LAUNCH(ctx, "groth16_h_pointwise", groth16_h_pointwise<U>, grid_1d(m), dim3(256), 0, p0, p1, n0, n1, zinv, (uint32_t)nz, d_h);
     ZK_TRY(zk_dom_fft_split(ctx, r->curve, dom, d_h, d_h + (size_t)n0 * 8, 1, 1, coset, dscr));
     ZK_LAUNCH(ctx, "fr_zero_one", fr_zero_one<U>, dim3(1), dim3(64), 0, d_h + (size_t)m * U::NL);
     return 0;
@@ -272,10 +272,10 @@ extern "C" {
 int zkhip_r1cs_upload(zkhip_ctx *ctx, int curve, size_t num_constraints, size_t num_inputs, size_t num_variables, const uint32_t *rowptr_a,
                       const uint32_t *col_a, const uint64_t *coeff_a, const uint32_t *rowptr_b, const uint32_t *col_b, const uint64_t *coeff_b,
                       const uint32_t *rowptr_c, const uint32_t *col_c, const uint64_t *coeff_c, zkhip_r1cs **out) {
-    if (!ctx || !out || !rowptr_a || !rowptr_b || !rowptr_c) return ZKHIP_ERR_INVALID;
-    if (curve != CURVE_BLS12_381 && curve != CURVE_BN254) return ZKHIP_ERR_INVALID;
+    ZK_ARGS(ctx, curve);
+    if (!out || !rowptr_a || !rowptr_b || !rowptr_c) return ZKHIP_ERR_INVALID;
     if (num_inputs > num_variables || num_constraints == 0 || num_constraints >= (1ull << 31)) return ZKHIP_ERR_RANGE;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ZK_ENTER(ctx);
     std::unique_ptr<zkhip_r1cs> r(new zkhip_r1cs());
     r->curve = curve;
     r->M = num_constraints;
@@ -290,7 +290,7 @@ int zkhip_r1cs_upload(zkhip_ctx *ctx, int curve, size_t num_constraints, size_t 
     }
     const uint32_t *rp[3] = {rowptr_a, rowptr_b, rowptr_c}, *cl[3] = {col_a, col_b, col_c};
     const uint64_t *cf[3] = {coeff_a, coeff_b, coeff_c};
-    ZK_TRY(curve == CURVE_BLS12_381 ? r1cs_upload_t<BlsFrU>(ctx, r.get(), rp, cl, cf) : r1cs_upload_t<BnFrU>(ctx, r.get(), rp, cl, cf));
+    ZK_TRY(fr_dispatch(curve, [&](auto u) -> int { return r1cs_upload_t<typename decltype(u)::type>(ctx, r.get(), rp, cl, cf); }));
     *out = r.release();
     return ZKHIP_OK;
 }
@@ -307,8 +307,8 @@ void zkhip_r1cs_free(zkhip_ctx *ctx, zkhip_r1cs *r) {
 int zkhip_fr_gather_dev(zkhip_ctx *ctx, const void *d_src, size_t src_count, const void *d_indices, size_t count, void *d_dst) {
     if (!ctx || (count && (!d_src || !d_indices || !d_dst))) return ZKHIP_ERR_INVALID;
     if (count == 0) return ZKHIP_OK;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    ZK_LAUNCH(ctx, "fr_gather", fr_gather, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (const uint4 *)d_src, src_count,
+    ZK_ENTER(ctx);
+    ZK_LAUNCH(ctx, "fr_gather", fr_gather, grid_1d(count), dim3(256), 0, (const uint4 *)d_src, src_count,
               (const uint32_t *)d_indices, count, (uint4 *)d_dst, ctx->d_status);
     return ZKHIP_OK;
 }
@@ -339,10 +339,10 @@ int zkhip_groth16_witness_h_domain_dev(zkhip_ctx *ctx, const zkhip_r1cs *r, cons
         ctx->last_error = "the domain passed differs from the constraint system's (zkhip_r1cs_set_domain)";
         return ZKHIP_ERR_INVALID;
     }
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (r->curve == CURVE_BLS12_381)
-        return witness_h_t<BlsFrU>(ctx, r, (const uint32_t *)d_assignment, d, coset_gen, (uint32_t *)d_h, (uint32_t *)d_scratch);
-    return witness_h_t<BnFrU>(ctx, r, (const uint32_t *)d_assignment, d, coset_gen, (uint32_t *)d_h, (uint32_t *)d_scratch);
+    ZK_ENTER(ctx);
+    return fr_dispatch(r->curve, [&](auto u) -> int {
+        return witness_h_t<typename decltype(u)::type>(ctx, r, (const uint32_t *)d_assignment, d, coset_gen, (uint32_t *)d_h, (uint32_t *)d_scratch);
+    });
 }
 
 int zkhip_groth16_witness_h_dev(zkhip_ctx *ctx, const zkhip_r1cs *r, const void *d_assignment, const uint64_t *omega, const uint64_t *coset_gen,

@@ -296,57 +296,47 @@ extern "C" int zkhip_lookup_sort_dev(zkhip_ctx *ctx, size_t k_in, const void *co
     if (n && usable_rows >= n) return ZKHIP_ERR_RANGE;
     if (kk * usable_rows >= ((size_t)1 << 31) || kk * n >= ((size_t)1 << 38)) return ZKHIP_ERR_RANGE;  // positions and emission indices are u32
     if (k_val * usable_rows >= ((size_t)1 << 30)) return ZKHIP_ERR_RANGE;                                // the hash table (2 slots per table entry, a power of two) is indexed by u32
-    for (size_t i = 0; n && i < k_in; ++i)
-        if (!d_input[i]) return ZKHIP_ERR_INVALID;
-    for (size_t i = 0; n && i < k_val; ++i)
-        if (!d_value[i]) return ZKHIP_ERR_INVALID;
-    for (size_t i = 0; n && i < kk; ++i)
-        if (!d_sorted[i]) return ZKHIP_ERR_INVALID;
+    if (n && (zk_any_null(d_input, k_in) || zk_any_null(d_value, k_val) || zk_any_null(d_sorted, kk))) return ZKHIP_ERR_INVALID;
     if (n == 0) return ZKHIP_OK;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ZK_ENTER(ctx);
     const uint32_t u = (uint32_t)usable_rows, lv = (uint32_t)(k_val * usable_rows), li = (uint32_t)(k_in * usable_rows);
     const uint32_t vt = (lv + LS_TILE - 1) / LS_TILE;  // tiles over the values = upper bound of the tiles over the runs
     uint32_t table = 1024;
     while (table < 2 * (size_t)lv) table <<= 1;  // load factor <= 1/2 whatever the number of runs
     LookupSortBuffers w = {kk, lv, vt, table};
     ZK_TRY(ws_place(ctx, w));
-    const uint32_t **d_ptrs = w.ptrs;
-    uint32_t *d_run = w.run, *d_st = w.st, *d_canon = w.canon, *d_cnt = w.cnt, *d_off = w.off, *d_tile_a = w.tile_a, *d_tile_b = w.tile_b, *d_slots = w.slots,
-             *d_scal = w.scal;
-    uint8_t *d_start = w.start;
-    ctx->batch_ptrs.clear();
-    for (size_t i = 0; i < k_in; ++i) ctx->batch_ptrs.push_back((uint32_t *)d_input[i]);
-    for (size_t i = 0; i < k_val; ++i) ctx->batch_ptrs.push_back((uint32_t *)d_value[i]);
-    for (size_t i = 0; i < kk; ++i) ctx->batch_ptrs.push_back((uint32_t *)d_sorted[i]);
-    ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_ptrs, ctx->batch_ptrs.data(), 2 * kk * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
-    const uint32_t *const *p_in = d_ptrs, *const *p_val = d_ptrs + k_in;
-    uint32_t *const *p_out = (uint32_t *const *)(d_ptrs + kk);
-    ZK_HIP_CHECK(ctx, hipMemsetAsync(d_scal, 0, 64, ctx->stream));
+    std::vector<const void *> ptrs(d_input, d_input + k_in);
+    ptrs.insert(ptrs.end(), d_value, d_value + k_val);
+    ptrs.insert(ptrs.end(), d_sorted, d_sorted + kk);
+    ZK_TRY(ws_upload(ctx, w.ptrs, ptrs.data(), 2 * kk * sizeof(void *)));
+    const uint32_t *const *p_in = w.ptrs, *const *p_val = w.ptrs + k_in;
+    uint32_t *const *p_out = (uint32_t *const *)(w.ptrs + kk);
+    ZK_HIP_CHECK(ctx, hipMemsetAsync(w.scal, 0, 64, ctx->stream));
     if (lv) {
-        ZK_HIP_CHECK(ctx, hipMemsetAsync(d_cnt, 0, (size_t)lv * 4, ctx->stream));
-        ZK_HIP_CHECK(ctx, hipMemsetAsync(d_slots, 0xff, (size_t)table * 4, ctx->stream));
-        ZK_LAUNCH(ctx, "lookup_sort", ls_starts, dim3(vt), dim3(LS_THREADS), 0, p_val, u, lv, d_run, d_start, d_tile_a);
-        ZK_LAUNCH(ctx, "lookup_sort", ls_scan_top, dim3(1), dim3(LS_THREADS), 0, d_tile_a, vt, d_scal, 0xffffffffu);
-        const dim3 per_value((lv + LS_THREADS - 1) / LS_THREADS);
-        ZK_LAUNCH(ctx, "lookup_sort", ls_heads, per_value, dim3(LS_THREADS), 0, d_run, d_start, d_tile_a, lv, d_st);
+        ZK_HIP_CHECK(ctx, hipMemsetAsync(w.cnt, 0, (size_t)lv * 4, ctx->stream));
+        ZK_HIP_CHECK(ctx, hipMemsetAsync(w.slots, 0xff, (size_t)table * 4, ctx->stream));
+        ZK_LAUNCH(ctx, "lookup_sort", ls_starts, dim3(vt), dim3(LS_THREADS), 0, p_val, u, lv, w.run, w.start, w.tile_a);
+        ZK_LAUNCH(ctx, "lookup_sort", ls_scan_top, dim3(1), dim3(LS_THREADS), 0, w.tile_a, vt, w.scal, 0xffffffffu);
+        const dim3 per_value = grid_1d(lv, LS_THREADS);
+        ZK_LAUNCH(ctx, "lookup_sort", ls_heads, per_value, dim3(LS_THREADS), 0, w.run, w.start, w.tile_a, lv, w.st);
         // the run count stays on the device: the per-run kernels are launched over its upper bound lv and read it
-        ZK_LAUNCH(ctx, "lookup_sort", ls_insert, per_value, dim3(LS_THREADS), 0, p_val, u, lv, d_st, d_scal, d_slots, table - 1, d_canon, d_cnt);
+        ZK_LAUNCH(ctx, "lookup_sort", ls_insert, per_value, dim3(LS_THREADS), 0, p_val, u, lv, w.st, w.scal, w.slots, table - 1, w.canon, w.cnt);
         if (li)
-            ZK_LAUNCH(ctx, "lookup_sort", ls_count_inputs, dim3((li + LS_THREADS - 1) / LS_THREADS), dim3(LS_THREADS), 0, p_in, p_val, u, li, d_st, d_slots, table - 1, d_cnt,
+            ZK_LAUNCH(ctx, "lookup_sort", ls_count_inputs, grid_1d(li, LS_THREADS), dim3(LS_THREADS), 0, p_in, p_val, u, li, w.st, w.slots, table - 1, w.cnt,
                       ctx->d_status);
         const uint32_t cap1 = (uint32_t)(kk * usable_rows) + 1;  // emission sizes and offsets saturate one above what the vectors hold
-        ZK_LAUNCH(ctx, "lookup_sort", ls_sizes, dim3(vt), dim3(LS_THREADS), 0, p_val, u, d_st, d_scal, d_canon, d_cnt, d_off, d_tile_b, cap1);
-        ZK_LAUNCH(ctx, "lookup_sort", ls_scan_top, dim3(1), dim3(LS_THREADS), 0, d_tile_b, vt, d_scal + 1, cap1);
-        ZK_LAUNCH(ctx, "lookup_sort", ls_offsets, per_value, dim3(LS_THREADS), 0, d_off, d_tile_b, d_scal, d_scal + 1, (uint32_t)(kk * usable_rows), ctx->d_status);
+        ZK_LAUNCH(ctx, "lookup_sort", ls_sizes, dim3(vt), dim3(LS_THREADS), 0, p_val, u, w.st, w.scal, w.canon, w.cnt, w.off, w.tile_b, cap1);
+        ZK_LAUNCH(ctx, "lookup_sort", ls_scan_top, dim3(1), dim3(LS_THREADS), 0, w.tile_b, vt, w.scal + 1, cap1);
+        ZK_LAUNCH(ctx, "lookup_sort", ls_offsets, per_value, dim3(LS_THREADS), 0, w.off, w.tile_b, w.scal, w.scal + 1, (uint32_t)(kk * usable_rows), ctx->d_status);
     } else if (li) {
         // inputs without a table: nothing they could be found in
-        ZK_HIP_CHECK(ctx, hipMemsetAsync(d_slots, 0xff, (size_t)table * 4, ctx->stream));
-        ZK_LAUNCH(ctx, "lookup_sort", ls_count_inputs, dim3((li + LS_THREADS - 1) / LS_THREADS), dim3(LS_THREADS), 0, p_in, p_val, u, li, d_st, d_slots, table - 1, d_cnt,
+        ZK_HIP_CHECK(ctx, hipMemsetAsync(w.slots, 0xff, (size_t)table * 4, ctx->stream));
+        ZK_LAUNCH(ctx, "lookup_sort", ls_count_inputs, grid_1d(li, LS_THREADS), dim3(LS_THREADS), 0, p_in, p_val, u, li, w.st, w.slots, table - 1, w.cnt,
                   ctx->d_status);
     }
     const size_t total = kk * n;
-    ZK_LAUNCH(ctx, "lookup_sort", ls_emit, dim3((unsigned)((total + LS_THREADS - 1) / LS_THREADS)), dim3(LS_THREADS), 0, p_val, u, d_st, d_off, d_scal, p_out, (uint32_t)n,
+    ZK_LAUNCH(ctx, "lookup_sort", ls_emit, grid_1d(total, LS_THREADS), dim3(LS_THREADS), 0, p_val, u, w.st, w.off, w.scal, p_out, (uint32_t)n,
               (uint32_t)kk);
-    ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // the staged pointer table may be reused after return
+    ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // kept: return-after-completion is current behaviour (EXPERIMENTS 18: guards nothing now)
     return ZKHIP_OK;
 }

@@ -80,7 +80,7 @@ __global__ __launch_bounds__(256) void merkle_path_gather(const uint4 *__restric
 static int merkle_levels(zkhip_ctx *ctx, zkhip_merkle *t) {
     for (size_t l = 1; l <= t->depth; ++l) {
         const size_t n = t->leaves >> l;
-        ZK_LAUNCH(ctx, "merkle_level_hash", merkle_level_hash, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+        ZK_LAUNCH(ctx, "merkle_level_hash", merkle_level_hash, grid_1d(n), dim3(256), 0,
                   t->d + 8 * merkle_level_offset(t->leaves, l - 1), n, t->d + 8 * merkle_level_offset(t->leaves, l));
     }
     return ZKHIP_OK;
@@ -114,13 +114,13 @@ static int merkle_done(zkhip_ctx *ctx, zkhip_merkle *t, int rc, zkhip_merkle **o
 }
 
 static int merkle_hash_leaves(zkhip_ctx *ctx, zkhip_merkle *t, const void *d_leaves, size_t per_leaf) {
-    ZK_LAUNCH(ctx, "merkle_leaf_hash", merkle_leaf_hash, dim3((unsigned)((t->leaves + 255) / 256)), dim3(256), 0, (const uint4 *)d_leaves, per_leaf, t->leaves,
+    ZK_LAUNCH(ctx, "merkle_leaf_hash", merkle_leaf_hash, grid_1d(t->leaves), dim3(256), 0, (const uint4 *)d_leaves, per_leaf, t->leaves,
               t->d);
     return merkle_levels(ctx, t);
 }
 
 static int merkle_hash_fri_leaves(zkhip_ctx *ctx, zkhip_merkle *t, const void *d_polys, size_t log_domain, size_t batch, size_t fri_step) {
-    ZK_LAUNCH(ctx, "merkle_fri_leaf_hash", merkle_fri_leaf_hash, dim3((unsigned)((t->leaves + 255) / 256)), dim3(256), 0, (const uint4 *)d_polys,
+    ZK_LAUNCH(ctx, "merkle_fri_leaf_hash", merkle_fri_leaf_hash, grid_1d(t->leaves), dim3(256), 0, (const uint4 *)d_polys,
               (uint32_t)log_domain, (uint32_t)batch, (uint32_t)fri_step, t->leaves, t->d);
     return merkle_levels(ctx, t);
 }
@@ -142,7 +142,7 @@ int zkhip_merkle_build_dev(zkhip_ctx *ctx, int hash, const void *d_leaves, size_
     if (!ctx || !out || !d_leaves || hash != ZKHIP_HASH_SHA2_256) return ZKHIP_ERR_INVALID;
     if (n_leaves == 0 || (n_leaves & (n_leaves - 1)) || elements_per_leaf == 0) return ZKHIP_ERR_INVALID;
     if (n_leaves > ((size_t)1 << 32) || elements_per_leaf >= ((size_t)1 << 32)) return ZKHIP_ERR_RANGE;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ZK_ENTER(ctx);
     zkhip_merkle *t = nullptr;
     ZK_TRY(merkle_alloc(ctx, hash, n_leaves, &t));
     return merkle_done(ctx, t, merkle_hash_leaves(ctx, t, d_leaves, elements_per_leaf), out);
@@ -151,7 +151,7 @@ int zkhip_merkle_build_dev(zkhip_ctx *ctx, int hash, const void *d_leaves, size_
 int zkhip_merkle_build_fri_dev(zkhip_ctx *ctx, int hash, const void *d_polys, size_t log_domain, size_t batch, size_t fri_step, zkhip_merkle **out) {
     if (!ctx || !out || !d_polys || hash != ZKHIP_HASH_SHA2_256 || batch == 0) return ZKHIP_ERR_INVALID;
     if (fri_step < 1 || fri_step > log_domain || log_domain > 32 || batch >= ((size_t)1 << 31)) return ZKHIP_ERR_RANGE;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ZK_ENTER(ctx);
     zkhip_merkle *t = nullptr;
     ZK_TRY(merkle_alloc(ctx, hash, (size_t)1 << (log_domain - fri_step), &t));
     return merkle_done(ctx, t, merkle_hash_fri_leaves(ctx, t, d_polys, log_domain, batch, fri_step), out);
@@ -162,7 +162,7 @@ size_t zkhip_merkle_depth(const zkhip_merkle *t) { return t ? t->depth : 0; }
 
 int zkhip_merkle_digests(zkhip_ctx *ctx, const zkhip_merkle *t, uint8_t *out) {
     if (!ctx || !t || !out) return ZKHIP_ERR_INVALID;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ZK_ENTER(ctx);
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(out, t->d, (2 * t->leaves - 1) * 32, hipMemcpyDeviceToHost, ctx->stream));
     ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return ZKHIP_OK;
@@ -170,7 +170,7 @@ int zkhip_merkle_digests(zkhip_ctx *ctx, const zkhip_merkle *t, uint8_t *out) {
 
 int zkhip_merkle_root(zkhip_ctx *ctx, const zkhip_merkle *t, uint8_t out[32]) {
     if (!ctx || !t || !out) return ZKHIP_ERR_INVALID;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ZK_ENTER(ctx);
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(out, t->d + 8 * (2 * t->leaves - 2), 32, hipMemcpyDeviceToHost, ctx->stream));
     ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return ZKHIP_OK;
@@ -182,17 +182,15 @@ int zkhip_merkle_paths(zkhip_ctx *ctx, const zkhip_merkle *t, const uint64_t *le
     for (size_t k = 0; k < count; ++k)
         if (leaf_indices[k] >= t->leaves) return ZKHIP_ERR_RANGE;
     if (count == 0 || t->depth == 0) return ZKHIP_OK;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ZK_ENTER(ctx);
     const size_t nodes = count * t->depth;
     PathBuffers w = {count, nodes};
     ZK_TRY(ws_place(ctx, w));
-    uint64_t *d_idx = w.idx;
-    uint4 *d_out = w.out;
-    ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_idx, leaf_indices, count * 8, hipMemcpyHostToDevice, ctx->stream));
-    ZK_LAUNCH(ctx, "merkle_path_gather", merkle_path_gather, dim3((unsigned)((nodes * 2 + 255) / 256)), dim3(256), 0, (const uint4 *)t->d, t->leaves,
-              (uint32_t)t->depth, d_idx, nodes * 2, d_out);
-    ZK_HIP_CHECK(ctx, hipMemcpyAsync(out, d_out, nodes * 32, hipMemcpyDeviceToHost, ctx->stream));
-    ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // the caller's index array may go on return
+    ZK_TRY(ws_upload(ctx, w.idx, leaf_indices, count * 8));
+    ZK_LAUNCH(ctx, "merkle_path_gather", merkle_path_gather, grid_1d(nodes * 2), dim3(256), 0, (const uint4 *)t->d, t->leaves, (uint32_t)t->depth, w.idx, nodes * 2,
+              w.out);
+    ZK_HIP_CHECK(ctx, hipMemcpyAsync(out, w.out, nodes * 32, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // the digests are in `out` when the call returns
     return ZKHIP_OK;
 }
 

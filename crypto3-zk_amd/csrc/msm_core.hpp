@@ -1242,10 +1242,9 @@ int msm_stages(zkhip_ctx *ctx, const zkhip_bases *bases, const MsmCall &c, const
     const uint32_t n = c.g.n, nb = P.nb;
     const uint32_t *d_b = bases->d;  // entries address table rows from the start of the bases object
     if (!reuse_sort) {
-        unsigned gn = (unsigned)((n + 255) / 256);
         if (bases->curve == CURVE_BLS12_381)
-            ZK_LAUNCH(ctx, "msm_digits", msm_digits_only<BlsFr>, dim3(gn), dim3(256), 0, d_scalars, n, P.win, P.wrank, P.wworld, w.dig);
-        else ZK_LAUNCH(ctx, "msm_digits", msm_digits_only<BnFr>, dim3(gn), dim3(256), 0, d_scalars, n, P.win, P.wrank, P.wworld, w.dig);
+            ZK_LAUNCH(ctx, "msm_digits", msm_digits_only<BlsFr>, grid_1d(n), dim3(256), 0, d_scalars, n, P.win, P.wrank, P.wworld, w.dig);
+        else ZK_LAUNCH(ctx, "msm_digits", msm_digits_only<BnFr>, grid_1d(n), dim3(256), 0, d_scalars, n, P.win, P.wrank, P.wworld, w.dig);
         ZK_TRY((c.big_tiles ? msm_sort_run<SortBig> : msm_sort_run<SortSmall>)(ctx, c.g, c.nbh, w.dig, w.bh, w.bo, w.bsums, w.tmp_idx, w.tmp_key, w.offs, w.idx));
         // buckets by descending size
         ZK_LAUNCH(ctx, "msm_size_sort", msm_size_hist, dim3(c.sblk), dim3(256), 0, w.offs, nb, c.sblk, c.large_thresh, w.sh);
@@ -1271,7 +1270,7 @@ int msm_stages(zkhip_ctx *ctx, const zkhip_bases *bases, const MsmCall &c, const
     // large buckets: plan on the device (no host round trip), then fixed-size grids that read the plan
     if (!reuse_sort) {
         ZK_HIP_CHECK(ctx, hipMemsetAsync(w.plan, 0, 16, ctx->stream));
-        ZK_LAUNCH(ctx, "msm_plan_large", msm_plan_large, dim3((nb + 255) / 256), dim3(256), 0, w.offs, nb, w.plan, w.tasks, w.large, c.task_cap, c.large_cap,
+        ZK_LAUNCH(ctx, "msm_plan_large", msm_plan_large, grid_1d(nb), dim3(256), 0, w.offs, nb, w.plan, w.tasks, w.large, c.task_cap, c.large_cap,
                   c.large_thresh, ctx->d_status);
     }
     {
@@ -1285,7 +1284,7 @@ int msm_stages(zkhip_ctx *ctx, const zkhip_bases *bases, const MsmCall &c, const
     if (P.tables) {
         for (uint32_t cur = P.S; cur > 1;) {
             const uint32_t q = (cur + 3) / 4;
-            ZK_LAUNCH(ctx, "msm_bucket_merge", (msm_bucket_merge<FL, LPB>), dim3((unsigned)(((size_t)q * P.B * LPB + 255) / 256)), dim3(256), 0, w.buckets, P.B, q,
+            ZK_LAUNCH(ctx, "msm_bucket_merge", (msm_bucket_merge<FL, LPB>), grid_1d((size_t)q * P.B * LPB), dim3(256), 0, w.buckets, P.B, q,
                       cur);
             cur = q;
         }
@@ -1349,7 +1348,7 @@ int bases_precompute_t(zkhip_ctx *ctx, zkhip_bases *b) {
     uint32_t *tmp = w.tmp;
     for (size_t lo = 0; lo < b->n; lo += chunk) {
         size_t cnt = std::min(chunk, b->n - lo);
-        ZK_LAUNCH(ctx, "bases_precompute", bases_precompute_range<F>, dim3((unsigned)((cnt + 63) / 64)), dim3(64), 0, b->d, (uint32_t)b->n,
+        ZK_LAUNCH(ctx, "bases_precompute", bases_precompute_range<F>, grid_1d(cnt, 64), dim3(64), 0, b->d, (uint32_t)b->n,
                   (uint32_t)lo, (uint32_t)cnt, msm_make_windows(zk_scalar_bits(b->curve), b->ntab), (uint32_t)b->win_rank, (uint32_t)b->win_world, tmp);
     }
     return 0;
@@ -1431,8 +1430,7 @@ int msm_batch_tail(zkhip_ctx *ctx, size_t count, const zkhip_bases *const *bases
     if (ctx->batch_dptrs_override) {  // graph capture: the output pointers already sit in a device array owned by the graph
         d_ptrs = static_cast<uint32_t **>(ctx->batch_dptrs_override);
     } else {
-        ctx->batch_ptrs.assign(d_outs, d_outs + count);
-        ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_ptrs, ctx->batch_ptrs.data(), count * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
+        ZK_TRY(ws_upload(ctx, d_ptrs, d_outs, count * sizeof(void *)));
     }
     if (area.fold) return msm_fold_tail<F, Lane>(ctx, slots, area.fb, d_ptrs, nullptr);
     return msm_tail<Lane>(ctx, slots, count, B, area.segsum, area.segsum_blocks, area.winsum, [&]() -> int {
@@ -1455,13 +1453,13 @@ int msm_batch_t(zkhip_ctx *ctx, size_t count, const zkhip_bases *const *bases, c
 // ---- the per-(curve, group) operation table ----------------------------------------------------------------------
 template <class F>
 int op_to_mont(zkhip_ctx *ctx, zkhip_bases *b, const uint32_t *d_canonical, const uint8_t *d_inf) {
-    ZK_LAUNCH(ctx, "bases_to_mont", bases_to_mont<F>, dim3((unsigned)((b->n + 255) / 256)), dim3(256), 0, d_canonical, d_inf, (uint32_t)b->n, b->d);
+    ZK_LAUNCH(ctx, "bases_to_mont", bases_to_mont<F>, grid_1d(b->n), dim3(256), 0, d_canonical, d_inf, (uint32_t)b->n, b->d);
     return 0;
 }
 template <class F>
 int op_from_mont(zkhip_ctx *ctx, const zkhip_bases *b, size_t offset, size_t n, uint32_t *d_out, uint8_t *d_inf) {
     const uint32_t *src = b->d + offset * b->stride_u32;
-    ZK_LAUNCH(ctx, "bases_from_mont", bases_from_mont<F>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, src, (uint32_t)n, d_out, d_inf);
+    ZK_LAUNCH(ctx, "bases_from_mont", bases_from_mont<F>, grid_1d(n), dim3(256), 0, src, (uint32_t)n, d_out, d_inf);
     return 0;
 }
 template <class F>
@@ -1477,7 +1475,7 @@ struct FixedMulBuffers {  // the table, and five field elements per table entry 
 template <class F>
 int op_mul(zkhip_ctx *ctx, zkhip_bases *b, const uint32_t *d_base_canonical, const uint32_t *d_scalars) {
     if (b->n < 4096) {  // a handful of points: the table would cost more than it saves
-        ZK_LAUNCH(ctx, "bases_mul", bases_mul<F>, dim3((unsigned)((b->n + 63) / 64)), dim3(64), 0, b->d, d_base_canonical, d_scalars, (uint32_t)b->n);
+        ZK_LAUNCH(ctx, "bases_mul", bases_mul<F>, grid_1d(b->n, 64), dim3(64), 0, b->d, d_base_canonical, d_scalars, (uint32_t)b->n);
         return 0;
     }
     // fixed-base windows: a 32 x 256-entry affine table of the base, then <= 32 mixed additions per point (round 4: a 2^20-constraint
@@ -1487,7 +1485,7 @@ int op_mul(zkhip_ctx *ctx, zkhip_bases *b, const uint32_t *d_base_canonical, con
     uint32_t *tab = w.tab, *tmp = w.tmp;
     ZK_LAUNCH(ctx, "bases_mul", bases_fixed_table<F>, dim3(1), dim3(64), 0, d_base_canonical, tab, tmp);
     const size_t lanes = (b->n + FIXED_CHUNK - 1) / FIXED_CHUNK;
-    ZK_LAUNCH(ctx, "bases_mul", bases_mul_fixed<F>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, b->d, tab, d_scalars, (uint32_t)b->n, tmp);
+    ZK_LAUNCH(ctx, "bases_mul", bases_mul_fixed<F>, grid_1d(lanes, 64), dim3(64), 0, b->d, tab, d_scalars, (uint32_t)b->n, tmp);
     return 0;
 }
 template <class F>

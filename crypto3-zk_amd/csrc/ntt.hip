@@ -434,22 +434,22 @@ static int ntt_get_tables(zkhip_ctx *ctx, int curve, size_t log_m, const uint64_
     ZK_TRY(t->d_scale.alloc(ctx, eb));
     ZK_TRY(t->d_lo.alloc(ctx, (size_t)nlo * eb));
     ZK_TRY(t->d_hi.alloc(ctx, (size_t)nhi * eb));
-    ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_in, omega, 32, hipMemcpyHostToDevice, ctx->stream));
-    if (coset) ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_in + 8, coset, 32, hipMemcpyHostToDevice, ctx->stream));
+    ZK_TRY(ws_upload(ctx, d_in, omega, 32));
+    if (coset) ZK_TRY(ws_upload(ctx, d_in + 8, coset, 32));
     ZK_LAUNCH(ctx, "ntt_setup", ntt_setup<U>, dim3(1), dim3(64), 0, d_in, coset ? d_in + 8 : (const uint32_t *)nullptr, inverse,
               (uint32_t)log_m, t->d_base, t->d_scale);
-    ZK_LAUNCH(ctx, "ntt_pow_table", ntt_pow_table<U>, dim3((nlo + 255) / 256), dim3(256), 0, t->d_base, nlo, 0u, t->d_lo);
-    ZK_LAUNCH(ctx, "ntt_pow_table", ntt_pow_table<U>, dim3((nhi + 255) / 256), dim3(256), 0, t->d_base, nhi, (uint32_t)t->lo_bits, t->d_hi);
-    const unsigned gm = (unsigned)((m + 255) / 256);
+    ZK_LAUNCH(ctx, "ntt_pow_table", ntt_pow_table<U>, grid_1d(nlo), dim3(256), 0, t->d_base, nlo, 0u, t->d_lo);
+    ZK_LAUNCH(ctx, "ntt_pow_table", ntt_pow_table<U>, grid_1d(nhi), dim3(256), 0, t->d_base, nhi, (uint32_t)t->lo_bits, t->d_hi);
+    const dim3 gm = grid_1d(m);
     if (coset) {
         ZK_TRY(t->d_clo.alloc(ctx, (size_t)nlo * eb));
         ZK_TRY(t->d_chi.alloc(ctx, (size_t)nhi * eb));
-        ZK_LAUNCH(ctx, "ntt_pow_table", ntt_pow_table<U>, dim3((nlo + 255) / 256), dim3(256), 0, t->d_base + U::SL, nlo, 0u, t->d_clo);
-        ZK_LAUNCH(ctx, "ntt_pow_table", ntt_pow_table<U>, dim3((nhi + 255) / 256), dim3(256), 0, t->d_base + U::SL, nhi, (uint32_t)t->lo_bits,
+        ZK_LAUNCH(ctx, "ntt_pow_table", ntt_pow_table<U>, grid_1d(nlo), dim3(256), 0, t->d_base + U::SL, nlo, 0u, t->d_clo);
+        ZK_LAUNCH(ctx, "ntt_pow_table", ntt_pow_table<U>, grid_1d(nhi), dim3(256), 0, t->d_base + U::SL, nhi, (uint32_t)t->lo_bits,
                   t->d_chi);
         // g^i while loading (forward) / (1/m) g^-i while storing (inverse): one entry per index
         ZK_TRY(t->d_prepost.alloc(ctx, m * 36));
-        ZK_LAUNCH(ctx, "ntt_build_tw", ntt_build_powers<U>, dim3(gm), dim3(256), 0, t->d_clo, t->d_chi, (uint32_t)t->lo_bits, (uint32_t)log_m,
+        ZK_LAUNCH(ctx, "ntt_build_tw", ntt_build_powers<U>, gm, dim3(256), 0, t->d_clo, t->d_chi, (uint32_t)t->lo_bits, (uint32_t)log_m,
                   inverse ? t->d_scale : (const uint32_t *)nullptr, t->d_prepost);
     }
     // per pass: stage twiddles omega_R^q = omega^(q m / R); per boundary: the store factors in output order.  An inverse
@@ -459,7 +459,7 @@ static int ntt_get_tables(zkhip_ctx *ctx, int curve, size_t log_m, const uint64_
     for (int i = 0; i < pl.np; ++i) {
         const uint32_t s = (uint32_t)pl.sv[i], half = std::max<uint32_t>(1, (1u << s) / 2);
         ZK_TRY(t->d_stage[i].alloc(ctx, (size_t)half * eb));
-        ZK_LAUNCH(ctx, "ntt_build_tw", ntt_build_stage<U>, dim3((half + 255) / 256), dim3(256), 0, t->d_lo, t->d_hi, (uint32_t)t->lo_bits,
+        ZK_LAUNCH(ctx, "ntt_build_tw", ntt_build_stage<U>, grid_1d(half), dim3(256), 0, t->d_lo, t->d_hi, (uint32_t)t->lo_bits,
                   (uint32_t)log_m - s, half, t->d_stage[i]);
         if (i + 1 < pl.np) {
             NttTwGeom g;
@@ -472,7 +472,7 @@ static int ntt_get_tables(zkhip_ctx *ctx, int curve, size_t log_m, const uint64_
             g.lo_bits = (uint32_t)t->lo_bits;
             g.scale = (inverse && !coset && i == 0) ? t->d_scale : nullptr;
             ZK_TRY(t->d_tw[i].alloc(ctx, m * 36));
-            ZK_LAUNCH(ctx, "ntt_build_tw", ntt_build_tw<U>, dim3(gm), dim3(256), 0, g, t->d_tw[i]);
+            ZK_LAUNCH(ctx, "ntt_build_tw", ntt_build_tw<U>, gm, dim3(256), 0, g, t->d_tw[i]);
         }
         log_ns += s;
     }
@@ -636,9 +636,9 @@ static int ntt_extend_t(zkhip_ctx *ctx, int curve, uint32_t *d_coeffs, size_t lo
         memcpy(built->omega_big, omega_big, 32);
         ZK_TRY(built->d_pre.alloc(ctx, k1 * m * 36));
         ZK_TRY(d_w.alloc(ctx, 32));
-        ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_w, omega_big, 32, hipMemcpyHostToDevice, ctx->stream));
+        ZK_TRY(ws_upload(ctx, d_w, omega_big, 32));
         const size_t entries = k1 * m;
-        ZK_LAUNCH(ctx, "ntt_build_tw", ntt_build_ext_pre<U>, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, d_w, (uint32_t)log_m, (uint32_t)k1, built->d_pre);
+        ZK_LAUNCH(ctx, "ntt_build_tw", ntt_build_ext_pre<U>, grid_1d(entries), dim3(256), 0, d_w, (uint32_t)log_m, (uint32_t)k1, built->d_pre);
         ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         t = built.get();
         ZK_TRY(ctx->ntt_ext_tables.publish(std::move(built), [&] { return ctx->stream_drain(); }));
@@ -653,15 +653,11 @@ int zk_ntt_extend(zkhip_ctx *ctx, int curve, uint32_t *d_coeffs, size_t log_m, s
                   const uint64_t *omega_big) {
     if (log_m + log_k > 32 || log_k == 0 || log_k > 4) return ZKHIP_ERR_RANGE;
     if (batch * (((size_t)1 << log_k) - 1) >= ((size_t)1 << 20)) return ZKHIP_ERR_RANGE;
-    if (curve == CURVE_BLS12_381) return ntt_extend_t<BlsFrU>(ctx, curve, d_coeffs, log_m, batch, omega, d_out, log_k, omega_big);
-    if (curve == CURVE_BN254) return ntt_extend_t<BnFrU>(ctx, curve, d_coeffs, log_m, batch, omega, d_out, log_k, omega_big);
-    return ZKHIP_ERR_INVALID;
+    return fr_dispatch(curve, [&](auto u) -> int { return ntt_extend_t<typename decltype(u)::type>(ctx, curve, d_coeffs, log_m, batch, omega, d_out, log_k, omega_big); });
 }
 
 int zk_ntt_run(zkhip_ctx *ctx, int curve, uint32_t *d_data, size_t log_m, size_t batch, const uint64_t *omega, int inverse,
                const uint64_t *coset) {
     if (log_m > 32) return ZKHIP_ERR_RANGE;
-    if (curve == CURVE_BLS12_381) return ntt_run_t<BlsFrU>(ctx, curve, d_data, log_m, batch, omega, inverse, coset);
-    if (curve == CURVE_BN254) return ntt_run_t<BnFrU>(ctx, curve, d_data, log_m, batch, omega, inverse, coset);
-    return ZKHIP_ERR_INVALID;
+    return fr_dispatch(curve, [&](auto u) -> int { return ntt_run_t<typename decltype(u)::type>(ctx, curve, d_data, log_m, batch, omega, inverse, coset); });
 }

@@ -341,46 +341,54 @@ struct ScanBuffers {
     }
 };
 
-// the passes over `n` entries of which the first `rows` carry ratios; ptrs: the device pointer table of the row functor (count entries)
+// the head's uploads and gp_setup: `ptrs` is the host pointer table of the row functor, beta and gamma the caller's
+template <class U>
+int rows_head_run(zkhip_ctx *ctx, const char *name, const RowsHead &h, const std::vector<const void *> &ptrs, const uint64_t *beta, const uint64_t *gamma, uint32_t f_nom,
+                  uint32_t f_den, uint32_t pow_opb) {
+    ZK_TRY(ws_upload(ctx, h.ptrs, ptrs.data(), ptrs.size() * sizeof(void *)));
+    ZK_TRY(ws_upload(ctx, h.in(), beta, 32));
+    ZK_TRY(ws_upload(ctx, h.in() + 8, gamma, 32));
+    ZK_LAUNCH(ctx, name, gp_setup<U>, dim3(1), dim3(64), 0, h.in(), h.consts, f_nom, f_den, pow_opb, h.zero_row());
+    return ZKHIP_OK;
+}
+
+// the passes over `n` entries of which the first `rows` carry ratios; ptrs: the host pointer table of the row functor
 template <class U, class MakeRows>
-int scan_run(zkhip_ctx *ctx, size_t count, MakeRows make_rows, size_t n, size_t rows, uint32_t f_nom, uint32_t f_den, uint32_t pow_opb, const uint64_t *beta,
-             const uint64_t *gamma, uint32_t *d_vp) {
+int scan_run(zkhip_ctx *ctx, const std::vector<const void *> &ptrs, MakeRows make_rows, size_t n, size_t rows, uint32_t f_nom, uint32_t f_den, uint32_t pow_opb,
+             const uint64_t *beta, const uint64_t *gamma, uint32_t *d_vp) {
     const size_t lanes = (n + PERM_CHUNK - 1) / PERM_CHUNK, nblk = (lanes + PERM_THREADS - 1) / PERM_THREADS;
     if (nblk > (size_t)PERM_THREADS * 4096) return ZKHIP_ERR_RANGE;
     const uint32_t per = (uint32_t)((nblk + PERM_THREADS - 1) / PERM_THREADS);
     const size_t n_slots = nblk * PERM_THREADS * PERM_CHUNK;  // perm_slot stays inside the row's block: whole blocks of scratch
-    ScanBuffers w = {{count}, n_slots, nblk};
+    ScanBuffers w = {{ptrs.size()}, n_slots, nblk};
     ZK_TRY(ws_place(ctx, w));
-    const uint32_t **d_ptrs = w.head.ptrs;
-    uint32_t *d_consts = w.head.consts, *d_in = w.head.in(), *d_z = w.head.zero_row();
-    ctx->lagrange_stage.assign(16, 0u);  // host copies alive until the asynchronous copies ran (synchronised below); batch_ptrs filled by the caller
-    memcpy(ctx->lagrange_stage.data(), beta, 32);
-    memcpy(ctx->lagrange_stage.data() + 8, gamma, 32);
-    ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_ptrs, ctx->batch_ptrs.data(), count * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
-    ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_in, ctx->lagrange_stage.data(), 64, hipMemcpyHostToDevice, ctx->stream));
-    ZK_LAUNCH(ctx, "perm_grand_product", gp_setup<U>, dim3(1), dim3(64), 0, d_in, d_consts, f_nom, f_den, pow_opb, d_z);
-    auto rows_of = make_rows(d_ptrs);
+    uint32_t *d_consts = w.head.consts, *d_z = w.head.zero_row();
+    ZK_TRY(rows_head_run<U>(ctx, "perm_grand_product", w.head, ptrs, beta, gamma, f_nom, f_den, pow_opb));
+    auto rows_of = make_rows(w.head.ptrs);
     if (rows)
-        ZK_LAUNCH(ctx, "perm_grand_product", (gp_rows<U, decltype(rows_of)>), dim3((unsigned)((rows + PERM_THREADS - 1) / PERM_THREADS)), dim3(PERM_THREADS), 0, rows_of,
-                  rows, d_consts, w.nom, w.den, d_z);
+        ZK_LAUNCH(ctx, "perm_grand_product", (gp_rows<U, decltype(rows_of)>), grid_1d(rows, PERM_THREADS), dim3(PERM_THREADS), 0, rows_of, rows, d_consts, w.nom, w.den,
+                  d_z);
     ZK_LAUNCH(ctx, "perm_grand_product", gp_local<U>, dim3((unsigned)nblk), dim3(PERM_THREADS), 0, rows, w.nom, w.den, w.lpre, w.lsuf, w.bn, w.bd);
     ZK_LAUNCH(ctx, "perm_grand_product", gp_top<U>, dim3(1), dim3(PERM_THREADS), 0, w.bn, w.bd, (uint32_t)nblk, per, d_consts);
     ZK_LAUNCH(ctx, "perm_grand_product", gp_apply<U>, dim3((unsigned)nblk), dim3(PERM_THREADS), 0, w.nom, w.den, w.lpre, w.lsuf, w.bn, w.bd, d_consts, d_z, n, rows, d_vp);
-    ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // the staged pointers / constants may be reused after return
+    ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // kept: return-after-completion is current behaviour (EXPERIMENTS 18: guards nothing now)
     return ZKHIP_OK;
+}
+
+// the permutation argument's pointer table: columns | S_id | S_sigma, k of each
+std::vector<const void *> perm_table(size_t k, const void *const *d_cols, const void *const *d_sid, const void *const *d_ssig) {
+    std::vector<const void *> t(d_cols, d_cols + k);
+    t.insert(t.end(), d_sid, d_sid + k);
+    t.insert(t.end(), d_ssig, d_ssig + k);
+    return t;
 }
 
 template <class U>
 int perm_run(zkhip_ctx *ctx, size_t k, const void *const *d_cols, const void *const *d_sid, const void *const *d_ssig, size_t n, const uint64_t *beta,
              const uint64_t *gamma, uint32_t *d_gv, uint32_t *d_hv, uint32_t *d_vp) {
-    ctx->batch_ptrs.resize(3 * k);
-    for (size_t i = 0; i < k; ++i) {
-        ctx->batch_ptrs[i] = (uint32_t *)d_cols[i];
-        ctx->batch_ptrs[k + i] = (uint32_t *)d_sid[i];
-        ctx->batch_ptrs[2 * k + i] = (uint32_t *)d_ssig[i];
-    }
     return scan_run<U>(
-        ctx, 3 * k, [&](const uint32_t **p) { return PermRows<U>{p, p + k, p + 2 * k, (uint32_t)k, n, d_gv, d_hv}; }, n, n, (uint32_t)k, (uint32_t)k, 0, beta, gamma, d_vp);
+        ctx, perm_table(k, d_cols, d_sid, d_ssig), [&](const uint32_t **p) { return PermRows<U>{p, p + k, p + 2 * k, (uint32_t)k, n, d_gv, d_hv}; }, n, n, (uint32_t)k,
+        (uint32_t)k, 0, beta, gamma, d_vp);
 }
 
 template <class U>
@@ -388,37 +396,21 @@ int perm_products_run(zkhip_ctx *ctx, size_t k, const void *const *d_cols, const
                       const uint64_t *gamma, uint32_t *d_g, uint32_t *d_h) {
     RowsHead w = {3 * k};
     ZK_TRY(ws_place(ctx, w));
-    const uint32_t **d_ptrs = w.ptrs;
-    uint32_t *d_consts = w.consts, *d_in = w.in(), *d_z = w.zero_row();
-    ctx->batch_ptrs.resize(3 * k);
-    for (size_t i = 0; i < k; ++i) {
-        ctx->batch_ptrs[i] = (uint32_t *)d_cols[i];
-        ctx->batch_ptrs[k + i] = (uint32_t *)d_sid[i];
-        ctx->batch_ptrs[2 * k + i] = (uint32_t *)d_ssig[i];
-    }
-    ctx->lagrange_stage.assign(16, 0u);
-    memcpy(ctx->lagrange_stage.data(), beta, 32);
-    memcpy(ctx->lagrange_stage.data() + 8, gamma, 32);
-    ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_ptrs, ctx->batch_ptrs.data(), 3 * k * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
-    ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_in, ctx->lagrange_stage.data(), 64, hipMemcpyHostToDevice, ctx->stream));
-    ZK_LAUNCH(ctx, "perm_factor_products", gp_setup<U>, dim3(1), dim3(64), 0, d_in, d_consts, (uint32_t)k, (uint32_t)k, 0u, d_z);
-    PermRows<U> rows_of{d_ptrs, d_ptrs + k, d_ptrs + 2 * k, (uint32_t)k, n, nullptr, nullptr};
-    ZK_LAUNCH(ctx, "perm_factor_products", (gp_products<U, PermRows<U>>), dim3((unsigned)((n + PERM_THREADS - 1) / PERM_THREADS)), dim3(PERM_THREADS), 0, rows_of, n,
-              d_consts, d_g, d_h);
-    ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // the staged pointers / constants may be reused after return
+    ZK_TRY(rows_head_run<U>(ctx, "perm_factor_products", w, perm_table(k, d_cols, d_sid, d_ssig), beta, gamma, (uint32_t)k, (uint32_t)k, 0u));
+    PermRows<U> rows_of{w.ptrs, w.ptrs + k, w.ptrs + 2 * k, (uint32_t)k, n, nullptr, nullptr};
+    ZK_LAUNCH(ctx, "perm_factor_products", (gp_products<U, PermRows<U>>), grid_1d(n, PERM_THREADS), dim3(PERM_THREADS), 0, rows_of, n, w.consts, d_g, d_h);
+    ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // kept: return-after-completion is current behaviour (EXPERIMENTS 18: guards nothing now)
     return ZKHIP_OK;
 }
 
 template <class U>
 int lookup_run(zkhip_ctx *ctx, size_t k_in, const void *const *d_in, size_t k_val, const void *const *d_val, size_t k_sorted, const void *const *d_sorted, size_t n,
                size_t usable_rows, const uint64_t *beta, const uint64_t *gamma, uint32_t *d_vl) {
-    ctx->batch_ptrs.clear();
-    for (size_t i = 0; i < k_in; ++i) ctx->batch_ptrs.push_back((uint32_t *)d_in[i]);
-    for (size_t i = 0; i < k_val; ++i) ctx->batch_ptrs.push_back((uint32_t *)d_val[i]);
-    for (size_t i = 0; i < k_sorted; ++i) ctx->batch_ptrs.push_back((uint32_t *)d_sorted[i]);
+    std::vector<const void *> ptrs(d_in, d_in + k_in);
+    ptrs.insert(ptrs.end(), d_val, d_val + k_val);
+    ptrs.insert(ptrs.end(), d_sorted, d_sorted + k_sorted);
     return scan_run<U>(
-        ctx, k_in + k_val + k_sorted,
-        [&](const uint32_t **p) { return LookupRows<U>{p, p + k_in, p + k_in + k_val, (uint32_t)k_in, (uint32_t)k_val, (uint32_t)k_sorted, n}; }, n, usable_rows,
+        ctx, ptrs, [&](const uint32_t **p) { return LookupRows<U>{p, p + k_in, p + k_in + k_val, (uint32_t)k_in, (uint32_t)k_val, (uint32_t)k_sorted, n}; }, n, usable_rows,
         (uint32_t)(k_in + k_val), (uint32_t)k_sorted, (uint32_t)k_in, beta, gamma, d_vl);
 }
 
@@ -510,60 +502,56 @@ int mul_div_run(zkhip_ctx *ctx, const uint32_t *a, const uint32_t *b, const uint
 }  // namespace
 
 extern "C" int zkhip_fr_vec_mul_div_dev(zkhip_ctx *ctx, int curve, const void *d_a, const void *d_b, const void *d_c, void *d_out, size_t count) {
-    if (!ctx || (count && (!d_a || !d_b || !d_c || !d_out))) return ZKHIP_ERR_INVALID;
-    if (curve != CURVE_BLS12_381 && curve != CURVE_BN254) return ZKHIP_ERR_INVALID;
+    ZK_ARGS(ctx, curve);
+    if (count && (!d_a || !d_b || !d_c || !d_out)) return ZKHIP_ERR_INVALID;
     if (count >= ((size_t)1 << 39)) return ZKHIP_ERR_RANGE;
     if (count == 0) return ZKHIP_OK;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (curve == CURVE_BLS12_381) return mul_div_run<BlsFrU>(ctx, (const uint32_t *)d_a, (const uint32_t *)d_b, (const uint32_t *)d_c, (uint32_t *)d_out, count);
-    return mul_div_run<BnFrU>(ctx, (const uint32_t *)d_a, (const uint32_t *)d_b, (const uint32_t *)d_c, (uint32_t *)d_out, count);
+    ZK_ENTER(ctx);
+    return fr_dispatch(curve, [&](auto u) -> int {
+        return mul_div_run<typename decltype(u)::type>(ctx, (const uint32_t *)d_a, (const uint32_t *)d_b, (const uint32_t *)d_c, (uint32_t *)d_out, count);
+    });
 }
 
 extern "C" int zkhip_perm_grand_product_dev(zkhip_ctx *ctx, int curve, size_t k, const void *const *d_cols, const void *const *d_sid, const void *const *d_ssigma,
                                             size_t n, const uint64_t *beta, const uint64_t *gamma, void *d_g, void *d_h, void *d_vp) {
-    if (!ctx || k == 0 || !d_cols || !d_sid || !d_ssigma || !beta || !gamma || (n && !d_vp)) return ZKHIP_ERR_INVALID;
-    if (curve != CURVE_BLS12_381 && curve != CURVE_BN254) return ZKHIP_ERR_INVALID;
+    ZK_ARGS(ctx, curve);
+    if (k == 0 || !d_cols || !d_sid || !d_ssigma || !beta || !gamma || (n && !d_vp)) return ZKHIP_ERR_INVALID;
     if (k >= 4096 || n >= ((size_t)1 << 32)) return ZKHIP_ERR_RANGE;
-    for (size_t i = 0; i < k; ++i)
-        if (n && (!d_cols[i] || !d_sid[i] || !d_ssigma[i])) return ZKHIP_ERR_INVALID;
+    if (n && (zk_any_null(d_cols, k) || zk_any_null(d_sid, k) || zk_any_null(d_ssigma, k))) return ZKHIP_ERR_INVALID;
     if (n == 0) return ZKHIP_OK;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (curve == CURVE_BLS12_381) return perm_run<BlsFrU>(ctx, k, d_cols, d_sid, d_ssigma, n, beta, gamma, (uint32_t *)d_g, (uint32_t *)d_h, (uint32_t *)d_vp);
-    return perm_run<BnFrU>(ctx, k, d_cols, d_sid, d_ssigma, n, beta, gamma, (uint32_t *)d_g, (uint32_t *)d_h, (uint32_t *)d_vp);
+    ZK_ENTER(ctx);
+    return fr_dispatch(curve, [&](auto u) -> int {
+        return perm_run<typename decltype(u)::type>(ctx, k, d_cols, d_sid, d_ssigma, n, beta, gamma, (uint32_t *)d_g, (uint32_t *)d_h, (uint32_t *)d_vp);
+    });
 }
 
 /* prod_i (column_i + beta S_id_i + gamma) and prod_i (column_i + beta S_sigma_i + gamma), pointwise over n entries of vectors on ANY domain: the g and
  * h polynomials of the permutation argument (permutation_argument.hpp:140-160) on the extended domain, from the extended columns in one pass */
 extern "C" int zkhip_perm_factor_products_dev(zkhip_ctx *ctx, int curve, size_t k, const void *const *d_cols, const void *const *d_sid, const void *const *d_ssigma,
                                               size_t n, const uint64_t *beta, const uint64_t *gamma, void *d_g, void *d_h) {
-    if (!ctx || k == 0 || !d_cols || !d_sid || !d_ssigma || !beta || !gamma || (n && (!d_g || !d_h))) return ZKHIP_ERR_INVALID;
-    if (curve != CURVE_BLS12_381 && curve != CURVE_BN254) return ZKHIP_ERR_INVALID;
+    ZK_ARGS(ctx, curve);
+    if (k == 0 || !d_cols || !d_sid || !d_ssigma || !beta || !gamma || (n && (!d_g || !d_h))) return ZKHIP_ERR_INVALID;
     if (k >= 4096 || n >= ((size_t)1 << 38)) return ZKHIP_ERR_RANGE;
-    for (size_t i = 0; i < k; ++i)
-        if (n && (!d_cols[i] || !d_sid[i] || !d_ssigma[i])) return ZKHIP_ERR_INVALID;
+    if (n && (zk_any_null(d_cols, k) || zk_any_null(d_sid, k) || zk_any_null(d_ssigma, k))) return ZKHIP_ERR_INVALID;
     if (n == 0) return ZKHIP_OK;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (curve == CURVE_BLS12_381) return perm_products_run<BlsFrU>(ctx, k, d_cols, d_sid, d_ssigma, n, beta, gamma, (uint32_t *)d_g, (uint32_t *)d_h);
-    return perm_products_run<BnFrU>(ctx, k, d_cols, d_sid, d_ssigma, n, beta, gamma, (uint32_t *)d_g, (uint32_t *)d_h);
+    ZK_ENTER(ctx);
+    return fr_dispatch(curve, [&](auto u) -> int {
+        return perm_products_run<typename decltype(u)::type>(ctx, k, d_cols, d_sid, d_ssigma, n, beta, gamma, (uint32_t *)d_g, (uint32_t *)d_h);
+    });
 }
 
 /* V_L of the lookup argument (lookup_argument.hpp:375-409): V_L[0] = 1, V_L[k] = V_L[k - 1] g(k - 1) / h(k - 1) for k <= usable_rows, zero behind */
 extern "C" int zkhip_lookup_grand_product_dev(zkhip_ctx *ctx, int curve, size_t k_in, const void *const *d_input, size_t k_val, const void *const *d_value,
                                               size_t k_sorted, const void *const *d_sorted, size_t n, size_t usable_rows, const uint64_t *beta, const uint64_t *gamma,
                                               void *d_vl) {
-    if (!ctx || !beta || !gamma || (n && !d_vl) || (k_in && !d_input) || (k_val && !d_value) || (k_sorted && !d_sorted)) return ZKHIP_ERR_INVALID;
-    if (curve != CURVE_BLS12_381 && curve != CURVE_BN254) return ZKHIP_ERR_INVALID;
+    ZK_ARGS(ctx, curve);
+    if (!beta || !gamma || (n && !d_vl) || (k_in && !d_input) || (k_val && !d_value) || (k_sorted && !d_sorted)) return ZKHIP_ERR_INVALID;
     if (k_in >= 4096 || k_val >= 4096 || k_sorted >= 4096 || n >= ((size_t)1 << 32)) return ZKHIP_ERR_RANGE;
     if (n && usable_rows >= n) return ZKHIP_ERR_RANGE;
-    for (size_t i = 0; n && i < k_in; ++i)
-        if (!d_input[i]) return ZKHIP_ERR_INVALID;
-    for (size_t i = 0; n && i < k_val; ++i)
-        if (!d_value[i]) return ZKHIP_ERR_INVALID;
-    for (size_t i = 0; n && i < k_sorted; ++i)
-        if (!d_sorted[i]) return ZKHIP_ERR_INVALID;
+    if (n && (zk_any_null(d_input, k_in) || zk_any_null(d_value, k_val) || zk_any_null(d_sorted, k_sorted))) return ZKHIP_ERR_INVALID;
     if (n == 0) return ZKHIP_OK;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (curve == CURVE_BLS12_381)
-        return lookup_run<BlsFrU>(ctx, k_in, d_input, k_val, d_value, k_sorted, d_sorted, n, usable_rows, beta, gamma, (uint32_t *)d_vl);
-    return lookup_run<BnFrU>(ctx, k_in, d_input, k_val, d_value, k_sorted, d_sorted, n, usable_rows, beta, gamma, (uint32_t *)d_vl);
+    ZK_ENTER(ctx);
+    return fr_dispatch(curve, [&](auto u) -> int {
+        return lookup_run<typename decltype(u)::type>(ctx, k_in, d_input, k_val, d_value, k_sorted, d_sorted, n, usable_rows, beta, gamma, (uint32_t *)d_vl);
+    });
 }

@@ -5,22 +5,13 @@
 //                           domain -> coefficients (inverse NTT) -> evaluations on the larger 2^log_out-point domain.
 //   zkhip_fri_fold_dev      detail::fold_polynomial, DFS form (zk/commitments/detail/polynomial/fold_polynomial.hpp:68-93):
 //                           f'(i) = 1/2 [ (1 + alpha w^-i) f(i) + (1 - alpha w^-i) f(i + size/2) ],  i < size/2.
-// The Merkle / hashing side of LPC is out of scope.
+// The Merkle / hashing side of LPC is merkle.hip.
 #include <algorithm>
 
 #include "ctx.hpp"
 #include "fu.hpp"
 
 using namespace zkhip;
-
-#define ZK_FR_DISPATCH(curve, ...)                 \
-    if ((curve) == CURVE_BLS12_381) {           \
-        typedef BlsFrU U;                       \
-        __VA_ARGS__;                            \
-    } else {                                    \
-        typedef BnFrU U;                        \
-        __VA_ARGS__;                            \
-    }
 
 // out[b][i] = in[b][i] for i < n, 0 for n <= i < m   (32-byte elements)
 __global__ __launch_bounds__(256) void poly_pad_copy(const uint4 *__restrict__ in, uint32_t log_n, uint32_t log_m, size_t total,
@@ -383,11 +374,11 @@ static int horner_run(zkhip_ctx *ctx, const uint32_t *d_polys, size_t n, size_t 
     const size_t total = batch * npoints;
     w = {npoints, total, nblk, U::SL};
     ZK_TRY(ws_place(ctx, w));
-    ZK_HIP_CHECK(ctx, hipMemcpyAsync(w.pts, points, npoints * 32, hipMemcpyHostToDevice, ctx->stream));
-    ZK_LAUNCH(ctx, "poly_horner_setup", horner_setup<U>, dim3((unsigned)((npoints + 63) / 64)), dim3(64), 0, w.pts, (uint32_t)npoints, w.zpow);
+    ZK_TRY(ws_upload(ctx, w.pts, points, npoints * 32));
+    ZK_LAUNCH(ctx, "poly_horner_setup", horner_setup<U>, grid_1d(npoints, 64), dim3(64), 0, w.pts, (uint32_t)npoints, w.zpow);
     ZK_LAUNCH(ctx, "poly_block_horner", poly_block_horner<U>, dim3(nblk, (unsigned)batch, (unsigned)npoints), dim3(256), 0, d_polys, n, stride, nblk,
               (uint32_t)npoints, w.zpow, w.part);
-    ZK_LAUNCH(ctx, "poly_block_carry", poly_block_carry<U>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, w.part, nblk, (uint32_t)npoints, (uint32_t)total,
+    ZK_LAUNCH(ctx, "poly_block_carry", poly_block_carry<U>, grid_1d(total, 64), dim3(64), 0, w.part, nblk, (uint32_t)npoints, (uint32_t)total,
               w.zpow, want_carry ? w.carry : nullptr, w.values);
     return ZKHIP_OK;
 }
@@ -430,13 +421,13 @@ int zkhip_poly_resize_dev(zkhip_ctx *ctx, int curve, void *d_in, size_t log_n, s
                           const uint64_t *omega_out) {
     if (!ctx || !omega_n || !omega_out || (batch && (!d_in || !d_out))) return ZKHIP_ERR_INVALID;
     if (log_out > 32 || log_n > 32) return ZKHIP_ERR_RANGE;
-    if (curve != CURVE_BLS12_381 && curve != CURVE_BN254) return ZKHIP_ERR_INVALID;
+    ZK_ARGS(ctx, curve);
     if (batch == 0) return ZKHIP_OK;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ZK_ENTER(ctx);
     if (log_out < log_n) {  // smaller domain: every 2^(log_n - log_out)-th evaluation (the caller vouches for degree < 2^log_out); d_in is left as it is
         const size_t tot = batch << log_out;
-        if (batch >= ((size_t)1 << 31) || tot >= ((size_t)1 << 39)) return ZKHIP_ERR_RANGE;  // (tot + 255) / 256 workgroups < 2^31
-        ZK_LAUNCH(ctx, "poly_subsample", poly_subsample, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (const uint4 *)d_in, (uint32_t)log_n,
+        if (batch >= ((size_t)1 << 31) || tot >= ((size_t)1 << 39)) return ZKHIP_ERR_RANGE;
+        ZK_LAUNCH(ctx, "poly_subsample", poly_subsample, grid_1d(tot), dim3(256), 0, (const uint4 *)d_in, (uint32_t)log_n,
                   (uint32_t)log_out, tot, (uint4 *)d_out);
         return ZKHIP_OK;
     }
@@ -445,14 +436,15 @@ int zkhip_poly_resize_dev(zkhip_ctx *ctx, int curve, void *d_in, size_t log_n, s
     // vector only when the two roots are NESTED, omega_out^K == omega_n (roots taken from one generator always are).  Any other pair of
     // primitive roots takes the general path below, which is correct for every pair (the relation used to be assumed).
     bool nested = false;
-    if (log_k >= 1 && log_k <= 4) { ZK_FR_DISPATCH(curve, nested = roots_nested<U>(omega_out, log_k, omega_n)); }
+    if (log_k >= 1 && log_k <= 4)
+        nested = fr_dispatch(curve, [&](auto u) -> int { return (int)roots_nested<typename decltype(u)::type>(omega_out, log_k, omega_n); }) == 1;
     if (ctx->opt_poly_coset_extend && nested && log_n >= 1 && batch * (((size_t)1 << log_k) - 1) < ((size_t)1 << 20)) {
         // Round 5: the K n-point domain is the n-point one and its K - 1 cosets omega_out^j <omega_n>.  The n known values are copied to their
         // places, the coefficients (inverse transform in place: d_in is consumed as before) are evaluated on the K - 1 new cosets by n-point
         // transforms that store straight into theirs: K n transform points instead of (K + 1) n, in transforms of the smaller size, and a lone
         // polynomial still fills the pairs-per-workgroup kernel with two of its cosets.
         const size_t tot = batch << log_n;
-        ZK_LAUNCH(ctx, "poly_spread", poly_spread, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (const uint4 *)d_in, (uint32_t)log_k, tot, (uint32_t)log_n,
+        ZK_LAUNCH(ctx, "poly_spread", poly_spread, grid_1d(tot), dim3(256), 0, (const uint4 *)d_in, (uint32_t)log_k, tot, (uint32_t)log_n,
                   (uint4 *)d_out);
         ZK_TRY(zk_ntt_run(ctx, curve, (uint32_t *)d_in, log_n, batch, omega_n, 1, nullptr));
         return zk_ntt_extend(ctx, curve, (uint32_t *)d_in, log_n, batch, omega_n, (uint32_t *)d_out, log_k, omega_out);
@@ -460,7 +452,7 @@ int zkhip_poly_resize_dev(zkhip_ctx *ctx, int curve, void *d_in, size_t log_n, s
     // coefficients in place (d_in is consumed), zero-extended copy, evaluation on the larger domain
     ZK_TRY(zk_ntt_run(ctx, curve, (uint32_t *)d_in, log_n, batch, omega_n, 1, nullptr));
     size_t total = batch << log_out;
-    ZK_LAUNCH(ctx, "poly_pad_copy", poly_pad_copy, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (const uint4 *)d_in, (uint32_t)log_n,
+    ZK_LAUNCH(ctx, "poly_pad_copy", poly_pad_copy, grid_1d(total), dim3(256), 0, (const uint4 *)d_in, (uint32_t)log_n,
               (uint32_t)log_out, total, (uint4 *)d_out);
     return zk_ntt_run(ctx, curve, (uint32_t *)d_out, log_out, batch, omega_out, 0, nullptr);
 }
@@ -468,76 +460,80 @@ int zkhip_poly_resize_dev(zkhip_ctx *ctx, int curve, void *d_in, size_t log_n, s
 int zkhip_fri_fold_dev(zkhip_ctx *ctx, int curve, const void *d_f, size_t log_size, const uint64_t *alpha, const uint64_t *omega, void *d_out) {
     if (!ctx || !d_f || !alpha || !omega || !d_out) return ZKHIP_ERR_INVALID;
     if (log_size < 1 || log_size > 32) return ZKHIP_ERR_RANGE;
-    if (curve != CURVE_BLS12_381 && curve != CURVE_BN254) return ZKHIP_ERR_INVALID;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ZK_ARGS(ctx, curve);
+    ZK_ENTER(ctx);
     FriFoldBuffers w;
     ZK_TRY(ws_place(ctx, w));
-    uint32_t *d_c = w.in, *consts = w.consts;
-    ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_c, alpha, 32, hipMemcpyHostToDevice, ctx->stream));
-    ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_c + 8, omega, 32, hipMemcpyHostToDevice, ctx->stream));
-    size_t half = (size_t)1 << (log_size - 1), lanes = (half + FOLD_CHUNK - 1) / FOLD_CHUNK;
-    dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
-    if (curve == CURVE_BLS12_381) {
-        ZK_LAUNCH(ctx, "fri_fold_setup", fri_fold_setup<BlsFrU>, dim3(1), dim3(64), 0, d_c, d_c + 8, (uint32_t)log_size, consts);
-        ZK_LAUNCH(ctx, "fri_fold", fri_fold<BlsFrU>, grid, block, 0, (const uint32_t *)d_f, (uint32_t)log_size, consts, (uint32_t *)d_out);
-    } else {
-        ZK_LAUNCH(ctx, "fri_fold_setup", fri_fold_setup<BnFrU>, dim3(1), dim3(64), 0, d_c, d_c + 8, (uint32_t)log_size, consts);
-        ZK_LAUNCH(ctx, "fri_fold", fri_fold<BnFrU>, grid, block, 0, (const uint32_t *)d_f, (uint32_t)log_size, consts, (uint32_t *)d_out);
-    }
-    return ZKHIP_OK;
+    ZK_TRY(ws_upload(ctx, w.in, alpha, 32));
+    ZK_TRY(ws_upload(ctx, w.in + 8, omega, 32));
+    const size_t half = (size_t)1 << (log_size - 1), lanes = (half + FOLD_CHUNK - 1) / FOLD_CHUNK;
+    return fr_dispatch(curve, [&](auto u) -> int {
+        using U = typename decltype(u)::type;
+        ZK_LAUNCH(ctx, "fri_fold_setup", fri_fold_setup<U>, dim3(1), dim3(64), 0, w.in, w.in + 8, (uint32_t)log_size, w.consts);
+        ZK_LAUNCH(ctx, "fri_fold", fri_fold<U>, grid_1d(lanes), dim3(256), 0, (const uint32_t *)d_f, (uint32_t)log_size, w.consts, (uint32_t *)d_out);
+        return ZKHIP_OK;
+    });
 }
 
 int zkhip_fri_leaves_dev(zkhip_ctx *ctx, const void *d_polys, size_t log_domain, size_t batch, size_t fri_step, void *d_out) {
     if (!ctx || (batch && (!d_polys || !d_out))) return ZKHIP_ERR_INVALID;
     if (fri_step < 1 || fri_step > log_domain || log_domain > 32 || batch >= ((size_t)1 << 31)) return ZKHIP_ERR_RANGE;
     if (batch == 0) return ZKHIP_OK;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ZK_ENTER(ctx);
     const size_t total = (batch << log_domain) >> 1;  // pairs
-    ZK_LAUNCH(ctx, "fri_leaf_gather", fri_leaf_gather, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (const uint4 *)d_polys, (uint32_t)log_domain,
+    ZK_LAUNCH(ctx, "fri_leaf_gather", fri_leaf_gather, grid_1d(total), dim3(256), 0, (const uint4 *)d_polys, (uint32_t)log_domain,
               (uint32_t)batch, (uint32_t)fri_step, total, (uint4 *)d_out);
     return ZKHIP_OK;
 }
 
 int zkhip_fr_vec_op_dev(zkhip_ctx *ctx, int curve, int op, const void *d_a, const void *d_b, void *d_out, size_t count) {
-    if (!ctx || (count && (!d_a || !d_b || !d_out)) || op < 0 || op > 2) return ZKHIP_ERR_INVALID;
-    if (curve != CURVE_BLS12_381 && curve != CURVE_BN254) return ZKHIP_ERR_INVALID;
+    ZK_ARGS(ctx, curve);
+    if ((count && (!d_a || !d_b || !d_out)) || op < 0 || op > 2) return ZKHIP_ERR_INVALID;
     if (count == 0) return ZKHIP_OK;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    ZK_FR_DISPATCH(curve, ZK_LAUNCH(ctx, "fr_vec_op", fr_vec_op<U>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (const uint32_t *)d_a,
-                                    (const uint32_t *)d_b, count, op, (uint32_t *)d_out));
-    return ZKHIP_OK;
+    ZK_ENTER(ctx);
+    return fr_dispatch(curve, [&](auto u) -> int {
+        using U = typename decltype(u)::type;
+        ZK_LAUNCH(ctx, "fr_vec_op", fr_vec_op<U>, grid_1d(count), dim3(256), 0, (const uint32_t *)d_a, (const uint32_t *)d_b, count, op, (uint32_t *)d_out);
+        return ZKHIP_OK;
+    });
 }
 
 int zkhip_fr_vec_affine_dev(zkhip_ctx *ctx, int curve, const void *d_x, const void *d_y, const uint64_t *a, const uint64_t *b, const uint64_t *c, void *d_out,
                             size_t count) {
-    if (!ctx || !a || !c || (d_y && !b) || (count && (!d_x || !d_out))) return ZKHIP_ERR_INVALID;
-    if (curve != CURVE_BLS12_381 && curve != CURVE_BN254) return ZKHIP_ERR_INVALID;
+    ZK_ARGS(ctx, curve);
+    if (!a || !c || (d_y && !b) || (count && (!d_x || !d_out))) return ZKHIP_ERR_INVALID;
     if (count >= ((size_t)1 << 39)) return ZKHIP_ERR_RANGE;
     if (count == 0) return ZKHIP_OK;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ZK_ENTER(ctx);
     FrWords wa, wb = {}, wc;
     memcpy(wa.w, a, 32);
     if (b) memcpy(wb.w, b, 32);
     memcpy(wc.w, c, 32);
-    ZK_FR_DISPATCH(curve, ZK_LAUNCH(ctx, "fr_vec_affine", fr_vec_affine<U>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (const uint32_t *)d_x,
-                                    (const uint32_t *)d_y, wa, wb, wc, count, (uint32_t *)d_out));
-    return ZKHIP_OK;
+    return fr_dispatch(curve, [&](auto u) -> int {
+        using U = typename decltype(u)::type;
+        ZK_LAUNCH(ctx, "fr_vec_affine", fr_vec_affine<U>, grid_1d(count), dim3(256), 0, (const uint32_t *)d_x, (const uint32_t *)d_y, wa, wb, wc, count,
+                  (uint32_t *)d_out);
+        return ZKHIP_OK;
+    });
 }
 
 int zkhip_poly_div_vanishing_dev(zkhip_ctx *ctx, int curve, const void *d_f, size_t len, size_t n, void *d_quot, uint64_t *nonzero_remainders) {
-    if (!ctx || n == 0 || (len && !d_f) || (len > n && !d_quot)) return ZKHIP_ERR_INVALID;
-    if (curve != CURVE_BLS12_381 && curve != CURVE_BN254) return ZKHIP_ERR_INVALID;
+    ZK_ARGS(ctx, curve);
+    if (n == 0 || (len && !d_f) || (len > n && !d_quot)) return ZKHIP_ERR_INVALID;
     if (n >= ((size_t)1 << 39) || len >= ((size_t)1 << 40)) return ZKHIP_ERR_RANGE;
     if (nonzero_remainders) *nonzero_remainders = 0;
     if (len == 0) return ZKHIP_OK;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ZK_ENTER(ctx);
     WsOne<uint32_t> w = {1};
     ZK_TRY(ws_place(ctx, w));
     uint32_t *d_bad = w.p;
     ZK_HIP_CHECK(ctx, hipMemsetAsync(d_bad, 0, 4, ctx->stream));
     const size_t lanes = std::min(n, len);
-    ZK_FR_DISPATCH(curve, ZK_LAUNCH(ctx, "poly_div_vanishing", poly_div_vanishing<U>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0,
-                                    (const uint32_t *)d_f, len, n, (uint32_t *)d_quot, d_bad));
+    ZK_TRY(fr_dispatch(curve, [&](auto u) -> int {
+        using U = typename decltype(u)::type;
+        ZK_LAUNCH(ctx, "poly_div_vanishing", poly_div_vanishing<U>, grid_1d(lanes), dim3(256), 0, (const uint32_t *)d_f, len, n, (uint32_t *)d_quot, d_bad);
+        return ZKHIP_OK;
+    }));
     if (nonzero_remainders) {
         uint32_t bad = 0;
         ZK_HIP_CHECK(ctx, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -548,62 +544,66 @@ int zkhip_poly_div_vanishing_dev(zkhip_ctx *ctx, int curve, const void *d_f, siz
 }
 
 int zkhip_fr_vec_prod_dev(zkhip_ctx *ctx, int curve, size_t count, const void *const *d_in, void *d_out, size_t n) {
-    if (!ctx || !d_in || count == 0 || (n && !d_out)) return ZKHIP_ERR_INVALID;
-    if (curve != CURVE_BLS12_381 && curve != CURVE_BN254) return ZKHIP_ERR_INVALID;
-    if (count >= 65536 || n >= ((size_t)1 << 39)) return ZKHIP_ERR_RANGE;  // (n + 255) / 256 workgroups < 2^31
-    for (size_t k = 0; k < count; ++k)
-        if (n && !d_in[k]) return ZKHIP_ERR_INVALID;
+    ZK_ARGS(ctx, curve);
+    if (!d_in || count == 0 || (n && !d_out)) return ZKHIP_ERR_INVALID;
+    if (count >= 65536 || n >= ((size_t)1 << 39)) return ZKHIP_ERR_RANGE;
+    if (n && zk_any_null(d_in, count)) return ZKHIP_ERR_INVALID;
     if (n == 0) return ZKHIP_OK;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ZK_ENTER(ctx);
     WsOne<const uint32_t *> w = {count};
     ZK_TRY(ws_place(ctx, w));
-    const uint32_t **d_ptrs = w.p;
-    ctx->batch_ptrs.assign((uint32_t *const *)d_in, (uint32_t *const *)d_in + count);  // host copy alive until the async copy ran
-    ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_ptrs, ctx->batch_ptrs.data(), count * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
-    ZK_FR_DISPATCH(curve, ZK_LAUNCH(ctx, "fr_vec_prod", fr_vec_prod<U>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, d_ptrs, (uint32_t)count, n,
-                                    (uint32_t *)d_out));
-    return ZKHIP_OK;
+    ZK_TRY(ws_upload(ctx, w.p, d_in, count * sizeof(void *)));
+    return fr_dispatch(curve, [&](auto u) -> int {
+        using U = typename decltype(u)::type;
+        ZK_LAUNCH(ctx, "fr_vec_prod", fr_vec_prod<U>, grid_1d(n), dim3(256), 0, w.p, (uint32_t)count, n, (uint32_t *)d_out);
+        return ZKHIP_OK;
+    });
 }
 
 int zkhip_poly_shift_dev(zkhip_ctx *ctx, const void *d_in, size_t log_size, int64_t rotation, void *d_out) {
     if (!ctx || !d_in || !d_out || d_in == d_out) return ZKHIP_ERR_INVALID;
-    if (log_size > 31) return ZKHIP_ERR_RANGE;  // one lane per element: (n + 255) / 256 workgroups must fit the 2^31 grid limit
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (log_size > 31) return ZKHIP_ERR_RANGE;  // one lane per element
+    ZK_ENTER(ctx);
     const size_t n = (size_t)1 << log_size;
     const int64_t m = (int64_t)n;
     const size_t rot = (size_t)(((rotation % m) + m) % m);
-    ZK_LAUNCH(ctx, "poly_rotate", poly_rotate, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const uint4 *)d_in, (uint32_t)log_size, rot, (uint4 *)d_out);
+    ZK_LAUNCH(ctx, "poly_rotate", poly_rotate, grid_1d(n), dim3(256), 0, (const uint4 *)d_in, (uint32_t)log_size, rot, (uint4 *)d_out);
     return ZKHIP_OK;
 }
 
 int zkhip_poly_eval_dev(zkhip_ctx *ctx, int curve, const void *d_polys, size_t n, size_t stride, size_t batch, const uint64_t *points, size_t npoints,
                         uint64_t *out) {
-    if (!ctx || !out || (batch && npoints && (!d_polys || !points))) return ZKHIP_ERR_INVALID;
-    if (curve != CURVE_BLS12_381 && curve != CURVE_BN254) return ZKHIP_ERR_INVALID;
+    ZK_ARGS(ctx, curve);
+    if (!out || (batch && npoints && (!d_polys || !points))) return ZKHIP_ERR_INVALID;
     if (stride < n || batch >= 65536 || npoints >= 65536 || n >= ((size_t)1 << 40)) return ZKHIP_ERR_RANGE;
     if (batch == 0 || npoints == 0) return ZKHIP_OK;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ZK_ENTER(ctx);
     HornerBuffers w;
-    ZK_FR_DISPATCH(curve, ZK_TRY(horner_run<U>(ctx, (const uint32_t *)d_polys, n, stride, batch, points, npoints, w, false)));
+    ZK_TRY(fr_dispatch(curve, [&](auto u) -> int {
+        return horner_run<typename decltype(u)::type>(ctx, (const uint32_t *)d_polys, n, stride, batch, points, npoints, w, false);
+    }));
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(out, w.values, batch * npoints * 32, hipMemcpyDeviceToHost, ctx->stream));
     ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return ZKHIP_OK;
 }
 
 int zkhip_poly_div_linear_dev(zkhip_ctx *ctx, int curve, const void *d_f, size_t n, const uint64_t *z, void *d_out, uint64_t *remainder) {
-    if (!ctx || !z || (n && (!d_f || !d_out))) return ZKHIP_ERR_INVALID;
-    if (curve != CURVE_BLS12_381 && curve != CURVE_BN254) return ZKHIP_ERR_INVALID;
+    ZK_ARGS(ctx, curve);
+    if (!z || (n && (!d_f || !d_out))) return ZKHIP_ERR_INVALID;
     if (n >= ((size_t)1 << 40)) return ZKHIP_ERR_RANGE;
     if (n == 0) {
         if (remainder) remainder[0] = remainder[1] = remainder[2] = remainder[3] = 0;
         return ZKHIP_OK;
     }
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ZK_ENTER(ctx);
     HornerBuffers w;
     const uint32_t nblk = (uint32_t)((n + HORNER_BLOCK - 1) / HORNER_BLOCK);
-    ZK_FR_DISPATCH(curve, ZK_TRY(horner_run<U>(ctx, (const uint32_t *)d_f, n, n, 1, z, 1, w, true));
-                   ZK_LAUNCH(ctx, "poly_div_finish", poly_div_finish<U>, dim3(nblk), dim3(256), 0, (const uint32_t *)d_f, n, nblk, w.zpow, w.carry,
-                             (uint32_t *)d_out));
+    ZK_TRY(fr_dispatch(curve, [&](auto u) -> int {
+        using U = typename decltype(u)::type;
+        ZK_TRY(horner_run<U>(ctx, (const uint32_t *)d_f, n, n, 1, z, 1, w, true));
+        ZK_LAUNCH(ctx, "poly_div_finish", poly_div_finish<U>, dim3(nblk), dim3(256), 0, (const uint32_t *)d_f, n, nblk, w.zpow, w.carry, (uint32_t *)d_out);
+        return ZKHIP_OK;
+    }));
     if (remainder) {
         ZK_HIP_CHECK(ctx, hipMemcpyAsync(remainder, w.values, 32, hipMemcpyDeviceToHost, ctx->stream));
         ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -613,33 +613,29 @@ int zkhip_poly_div_linear_dev(zkhip_ctx *ctx, int curve, const void *d_f, size_t
 
 int zkhip_poly_lincomb_dev(zkhip_ctx *ctx, int curve, size_t count, const void *const *d_polys, const size_t *lens, const uint64_t *coeffs, size_t taps,
                            void *d_acc, size_t acc_len, int accumulate) {
-    if (!ctx || (acc_len && !d_acc) || (count && (!d_polys || !lens || !coeffs || taps == 0))) return ZKHIP_ERR_INVALID;
-    if (curve != CURVE_BLS12_381 && curve != CURVE_BN254) return ZKHIP_ERR_INVALID;
+    ZK_ARGS(ctx, curve);
+    if ((acc_len && !d_acc) || (count && (!d_polys || !lens || !coeffs || taps == 0))) return ZKHIP_ERR_INVALID;
     if (count >= ((size_t)1 << 24) || taps >= 4096) return ZKHIP_ERR_RANGE;
     if (acc_len == 0) return ZKHIP_OK;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ZK_ENTER(ctx);
     const size_t nc = std::max<size_t>(1, count * taps);
     LincombBuffers w = {nc, count};
     ZK_TRY(ws_place(ctx, w));
-    uint32_t *d_c = w.c, *d_m = w.m;
-    const uint32_t **d_p = w.p;
-    uint64_t *d_l = w.l;
     if (count) {
-        // the pointer / length / coefficient tables are staged through the context so the caller's arrays may die on return
-        ctx->lincomb_stage.resize(count * 2);
-        for (size_t i = 0; i < count; ++i) ctx->lincomb_stage[i] = (uint64_t)(uintptr_t)d_polys[i], ctx->lincomb_stage[count + i] = lens[i];
-        ctx->lincomb_coeffs.assign(coeffs, coeffs + count * taps * 4);
-        ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_p, ctx->lincomb_stage.data(), count * 8, hipMemcpyHostToDevice, ctx->stream));
-        ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_l, ctx->lincomb_stage.data() + count, count * 8, hipMemcpyHostToDevice, ctx->stream));
-        ZK_HIP_CHECK(ctx, hipMemcpyAsync(d_c, ctx->lincomb_coeffs.data(), count * taps * 32, hipMemcpyHostToDevice, ctx->stream));
-        ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // pageable sources: the copies above must not outlive the staging vectors' next reuse
+        ZK_TRY(ws_upload(ctx, w.p, d_polys, count * sizeof(void *)));
+        static_assert(sizeof(size_t) == sizeof(uint64_t), "the kernel reads the lengths as the caller wrote them");
+        ZK_TRY(ws_upload(ctx, w.l, lens, count * 8));
+        ZK_TRY(ws_upload(ctx, w.c, coeffs, count * taps * 32));
+        ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // kept: this point has always waited for the stream (EXPERIMENTS 18: guards nothing now)
     }
-    ZK_FR_DISPATCH(curve, static_assert(U::SL <= 16, "coefficient slot");
-                   if (count) ZK_LAUNCH(ctx, "poly_lincomb_setup", fr_table_to_mont<U>, dim3((unsigned)((count * taps + 63) / 64)), dim3(64), 0, d_c,
-                                        (uint32_t)(count * taps), d_m);
-                   ZK_LAUNCH(ctx, "poly_lincomb", poly_lincomb<U>, dim3((unsigned)((acc_len + 255) / 256)), dim3(256), 0, d_p, d_l, (uint32_t)count,
-                             (uint32_t)taps, d_m, acc_len, accumulate, (uint32_t *)d_acc));
-    return ZKHIP_OK;
+    return fr_dispatch(curve, [&](auto u) -> int {
+        using U = typename decltype(u)::type;
+        static_assert(U::SL <= 16, "coefficient slot");
+        if (count) ZK_LAUNCH(ctx, "poly_lincomb_setup", fr_table_to_mont<U>, grid_1d(count * taps, 64), dim3(64), 0, w.c, (uint32_t)(count * taps), w.m);
+        ZK_LAUNCH(ctx, "poly_lincomb", poly_lincomb<U>, grid_1d(acc_len), dim3(256), 0, w.p, w.l, (uint32_t)count, (uint32_t)taps, w.m, acc_len, accumulate,
+                  (uint32_t *)d_acc);
+        return ZKHIP_OK;
+    });
 }
 
 }  // extern "C"

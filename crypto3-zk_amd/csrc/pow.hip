@@ -39,7 +39,7 @@ int zkhip_pow_grind(zkhip_ctx *ctx, int hash, const uint8_t state[32], uint32_t 
     const uint64_t space = (uint64_t)1 << 32;
     if (chunk_log < 8 || chunk_log > 32 || max_tries > space) return ZKHIP_ERR_RANGE;
     const uint64_t total = max_tries ? max_tries : space, chunk = (uint64_t)1 << chunk_log;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ZK_ENTER(ctx);
     WsOne<unsigned long long> word = {1};
     ZK_TRY(ws_place(ctx, word));
     ZK_HIP_CHECK(ctx, hipMemsetAsync(word.p, 0xFF, sizeof(unsigned long long), ctx->stream));  // POW_NO_HIT

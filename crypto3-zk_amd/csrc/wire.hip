@@ -204,7 +204,7 @@ __global__ __launch_bounds__(64) void wire_decompress_g2(const uint8_t *__restri
 int zk_bases_decompress(zkhip_ctx *ctx, zkhip_bases *b, const uint8_t *d_octets, uint32_t *d_err) {
     if (b->curve != CURVE_BLS12_381) return ZKHIP_ERR_INVALID;  // only this curve's wire format is pinned by the reference's vectors
     if (b->n == 0) return 0;
-    dim3 grid((unsigned)((b->n + 63) / 64)), block(64);
+    const dim3 grid = grid_1d(b->n, 64), block(64);
     if (b->group == GROUP_G1) ZK_LAUNCH(ctx, "wire_decompress", wire_decompress_g1<BlsFqU>, grid, block, 0, d_octets, (uint32_t)b->n, b->d, d_err);
     else ZK_LAUNCH(ctx, "wire_decompress", wire_decompress_g2<BlsFqU>, grid, block, 0, d_octets, (uint32_t)b->n, b->d, d_err);
     return 0;

@@ -10,7 +10,7 @@
 using namespace zkhip;
 
 static int check_device(zkhip_ctx *ctx) {
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ZK_ENTER(ctx);
     return 0;
 }
 
@@ -192,7 +192,7 @@ int zkhip_set_option(zkhip_ctx *ctx, const char *name, int64_t value) {
         // the context's OWN stream is recreated with a scheduling priority: < 0 the highest the device offers, > 0 the
         // lowest, 0 the default.  Two contexts on one GPU (the Groth16 shim's main and G2 streams) can so decide whose workgroups go first.
         if (!ctx->own_stream) return ZKHIP_ERR_INVALID;
-        ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+        ZK_ENTER(ctx);
         int least = 0, greatest = 0;
         ZK_HIP_CHECK(ctx, hipDeviceGetStreamPriorityRange(&least, &greatest));
         ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -309,7 +309,7 @@ int zkhip_memcpy_h2d_async(zkhip_ctx *ctx, void *dst, const void *src, size_t by
 }
 int zkhip_host_alloc(zkhip_ctx *ctx, size_t bytes, void **hptr) {
     if (!ctx || !hptr) return ZKHIP_ERR_INVALID;
-    ZK_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ZK_ENTER(ctx);
     ZK_HIP_CHECK(ctx, hipHostMalloc(hptr, bytes ? bytes : 1, hipHostMallocPortable));  // page-locked for EVERY device: a group's members upload from one staging buffer
     return ZKHIP_OK;
 }
@@ -359,7 +359,7 @@ int zkhip_memcpy_2d_d2d_async(zkhip_ctx *ctx, void *dst, size_t dst_pitch, const
 
 // ---- bases ------------------------------------------------------------------------------------------
 static int bases_alloc(zkhip_ctx *ctx, int curve, int group, size_t n, std::unique_ptr<zkhip_bases> &out) {
-    if ((curve != CURVE_BLS12_381 && curve != CURVE_BN254) || (group != GROUP_G1 && group != GROUP_G2)) return ZKHIP_ERR_INVALID;
+    if (!zk_curve_known(curve) || !zk_group_known(group)) return ZKHIP_ERR_INVALID;
     std::unique_ptr<zkhip_bases> b(new zkhip_bases());
     b->curve = curve;
     b->group = group;
@@ -509,7 +509,7 @@ int zkhip_bases_spread(zkhip_ctx *ctx, const zkhip_bases *src, const uint32_t *d
         ZK_HIP_CHECK(ctx, hipMemsetAsync(b->d, 0, n_total * b->stride_u32 * 4, ctx->stream));  // (0, 0): the point at infinity
         if (src->n) {
             const size_t lanes = src->n * src->stride_u32;
-            ZK_LAUNCH(ctx, "bases_spread_rows", bases_spread_rows, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, src->d, src->n,
+            ZK_LAUNCH(ctx, "bases_spread_rows", bases_spread_rows, grid_1d(lanes), dim3(256), 0, src->d, src->n,
                       (uint32_t)src->stride_u32, d_rows, (uint32_t)first, (uint32_t)n_total, b->d, ctx->d_status);
         }
     }
@@ -590,14 +590,14 @@ int zkhip_msm(zkhip_ctx *ctx, const zkhip_bases *bases, size_t offset, size_t n,
 
 int zkhip_jacobian_sum_dev(zkhip_ctx *ctx, int curve, int group, const void *d_points, size_t count, void *d_out_jacobian) {
     if (!ctx || !d_points || !d_out_jacobian) return ZKHIP_ERR_INVALID;
-    if ((curve != CURVE_BLS12_381 && curve != CURVE_BN254) || (group != GROUP_G1 && group != GROUP_G2)) return ZKHIP_ERR_INVALID;
+    if (!zk_curve_known(curve) || !zk_group_known(group)) return ZKHIP_ERR_INVALID;
     ZK_TRY(check_device(ctx));
     return zk_jac_sum(ctx, curve, group, (const uint32_t *)d_points, count, (uint32_t *)d_out_jacobian);
 }
 
 int zkhip_jacobian_to_affine(zkhip_ctx *ctx, int curve, int group, const uint64_t *jacobian, uint64_t *affine_xy, uint8_t *is_infinity) {
     if (!ctx || !jacobian || !affine_xy || !is_infinity) return ZKHIP_ERR_INVALID;
-    if ((curve != CURVE_BLS12_381 && curve != CURVE_BN254) || (group != GROUP_G1 && group != GROUP_G2)) return ZKHIP_ERR_INVALID;
+    if (!zk_curve_known(curve) || !zk_group_known(group)) return ZKHIP_ERR_INVALID;
     ZK_TRY(check_device(ctx));
     size_t cl = zk_coord_limbs64(curve, group) * 8;
     ToAffineBuffers w = {cl / 4};

@@ -1,12 +1,14 @@
 """The context itself (csrc/ctx.hpp, csrc/options.hpp): the options surface of zkhip_set_option / zkhip_get_option / ZKHIP_OPTIONS, the
 life cycle of everything a context and a device group own -- created, used and destroyed several times over, with results that never
 change --, and entry points that fail half-way and must leave the context usable."""
+import ctypes
+
 import numpy as np
 import pytest
 
 import cport as cp
 import pyoracle as po
-from util import CURVES, limbs, qap_domains
+from util import CURVES, fr_arr, fr_ints, limbs, qap_domains
 
 pytestmark = pytest.mark.gpu
 
@@ -221,3 +223,161 @@ def test_bases_spread_out_of_range_leaves_the_context_usable(zk, ctx):
     assert inf == inf_t == einf and (aff == exp).all() and (aff_t == exp).all()
     spread.free()
     tail.free()
+
+
+# ---- per-call host tables (csrc/ctx.hpp: ws_upload) and the entry preamble (ZK_ARGS / ZK_ENTER) ----------------------------------------
+def _dev(ctx, vals):
+    d = ctx.malloc(len(vals) * 32)
+    ctx.h2d(d, fr_arr(vals))
+    return d
+
+
+def _back(ctx, d, n):
+    out = np.zeros((n, 4), dtype=np.uint64)
+    ctx.d2h(out, d)
+    return fr_ints(out)
+
+
+@pytest.mark.parametrize("curve", [0, 1])
+def test_back_to_back_pointer_tables(ctx, curve):
+    """fr_vec_prod with table A (3 inputs), at once again with table B (2 other inputs), then poly_lincomb (2 polynomials, 2 taps): no
+    synchronisation in between, every result against big integers.  The second table must not reach the first call's kernel."""
+    r, n = CURVES[curve].r, 1 << 10
+    v = [fr_ints(cp.random_fr(curve, 900 + i, n)) for i in range(5)]
+    d = [_dev(ctx, x) for x in v]
+    d_a, d_b, d_acc = ctx.malloc(n * 32), ctx.malloc(n * 32), ctx.malloc((n + 1) * 32)
+    cs = [[po.SplitMix64(910 + 2 * i + t).next_mod(r) for t in range(2)] for i in range(2)]
+    ctx.fr_vec_prod_dev(curve, d[:3], d_a, n)
+    ctx.fr_vec_prod_dev(curve, d[3:], d_b, n)
+    ctx.poly_lincomb_dev(curve, [d[0], d[4]], [n, n], fr_arr([x for c in cs for x in c]), 2, d_acc, n + 1, False)
+    assert _back(ctx, d_a, n) == [a * b % r * c % r for a, b, c in zip(v[0], v[1], v[2])]
+    assert _back(ctx, d_b, n) == [a * b % r for a, b in zip(v[3], v[4])]
+    exp = [0] * (n + 1)
+    for p, c in zip((v[0], v[4]), cs):
+        for t in range(2):
+            for j, x in enumerate(p):
+                exp[j + t] = (exp[j + t] + c[t] * x) % r
+    assert _back(ctx, d_acc, n + 1) == exp
+    for p in d + [d_a, d_b, d_acc]:
+        ctx.free(p)
+
+
+def _vp(p):
+    return ctypes.c_void_p(p)
+
+
+def _hp(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def test_callers_arrays_die_on_return(zk, ctx):
+    """perm_factor_products (k = 2, n = 2^10) and gate_eval (log_size 6): the host-side argument arrays are overwritten as soon as the call
+    has returned, before anything is downloaded"""
+    curve, k, n = 0, 2, 1 << 10
+    r = CURVES[curve].r
+    v = [fr_ints(cp.random_fr(curve, 930 + i, n)) for i in range(3 * k)]
+    d = [_dev(ctx, x) for x in v]
+    d_g, d_h = ctx.malloc(n * 32), ctx.malloc(n * 32)
+    beta, gamma = po.SplitMix64(940).next_mod(r), po.SplitMix64(941).next_mod(r)
+
+    def call_and_scribble():
+        tabs = [(ctypes.c_void_p * k)(*d[i * k:(i + 1) * k]) for i in range(3)]
+        b, g = limbs(beta, 4), limbs(gamma, 4)
+        rc = ctx.lib.zkhip_perm_factor_products_dev(ctx.h, curve, ctypes.c_size_t(k), *tabs, ctypes.c_size_t(n), _hp(b), _hp(g), _vp(d_g), _vp(d_h))
+        for t in tabs:
+            ctypes.memset(t, 0x5a, ctypes.sizeof(t))
+        b[:] = 0
+        g[:] = 0
+        return rc
+
+    assert call_and_scribble() == 0
+    cols, sid, ssig = v[:k], v[k:2 * k], v[2 * k:]
+    want = lambda s: [(cols[0][j] + beta * s[0][j] + gamma) * (cols[1][j] + beta * s[1][j] + gamma) % r for j in range(n)]
+    assert _back(ctx, d_g, n) == want(sid) and _back(ctx, d_h, n) == want(ssig)
+
+    # the smallest program of test_gate_eval_flat_program's kind: one gate with a selector, two terms, rotations of both signs
+    log_size, size = 6, 64
+    c0 = po.SplitMix64(950).next_mod(r)
+    keep = [np.array([0, 2], dtype=np.uint32), np.array([2], dtype=np.uint32), np.array([1], dtype=np.int32), np.array([0, 2, 3], dtype=np.uint32),
+            np.array([0, 1, 1], dtype=np.uint32), np.array([0, 1, -1], dtype=np.int32), fr_arr([c0, r - 1])]
+    prog = zk.zkhip.GateProgram(1, 2, 3, 3, *[_hp(a) for a in keep])
+    slots = (ctypes.c_void_p * 3)(*d[:3])
+    d_out = ctx.malloc(size * 32)
+    rc = ctx.lib.zkhip_gate_eval_dev(ctx.h, curve, ctypes.byref(prog), slots, ctypes.c_size_t(log_size), None, 0, _vp(d_out))
+    for a in keep:
+        a[...] = 0x33
+    ctypes.memset(slots, 0x5a, ctypes.sizeof(slots))
+    ctypes.memset(ctypes.byref(prog), 0, ctypes.sizeof(prog))
+    assert rc == 0
+    x = [c[:size] for c in v[:3]]
+    assert _back(ctx, d_out, size) == [(c0 * x[0][j] * x[1][(j + 1) % size] - x[1][(j - 1) % size]) * x[2][(j + 1) % size] % r for j in range(size)]
+    for p in d + [d_g, d_h, d_out]:
+        ctx.free(p)
+
+
+def _preamble_calls(zk, c, curve, d, zero):
+    """(name, call) for every entry point that takes a curve id; zero: an empty call with null buffers, else a small well-formed one over d"""
+    L, h, z = c.lib, c.h, ctypes.c_size_t
+    one = limbs(1, 4)
+    w4 = limbs(CURVES[0].root_of_unity(4), 4)
+    dom = zk.zkhip.Domain.make(zk.zkhip.DOMAIN_BASIC, 16, w4)
+    p = None if zero else _vp(d)
+    cnt = z(0 if zero else 16)
+    tab = (ctypes.c_void_p * 1)(None if zero else d)
+    lens = (ctypes.c_size_t * 1)(16)
+    out = np.zeros(64, dtype=np.uint64)
+    rp = np.zeros(2, dtype=np.uint32)
+    prog = zk.zkhip.GateProgram(0, 0, 0, 0, *([None] * 7))
+    hdl = ctypes.c_void_p()
+    calls = [
+        ("fr_vec_op", lambda: L.zkhip_fr_vec_op_dev(h, curve, 0, p, p, p, cnt)),
+        ("fr_vec_affine", lambda: L.zkhip_fr_vec_affine_dev(h, curve, p, None, _hp(one), None, _hp(one), p, cnt)),
+        ("fr_vec_mul_div", lambda: L.zkhip_fr_vec_mul_div_dev(h, curve, p, p, p, p, cnt)),
+        ("fr_vec_prod", lambda: L.zkhip_fr_vec_prod_dev(h, curve, z(1), tab, p, cnt)),
+        ("poly_eval", lambda: L.zkhip_poly_eval_dev(h, curve, p, z(16), z(16), z(0 if zero else 1), _hp(one), z(1), _hp(out))),
+        ("poly_div_linear", lambda: L.zkhip_poly_div_linear_dev(h, curve, p, cnt, _hp(one), p, _hp(out))),
+        ("poly_div_vanishing", lambda: L.zkhip_poly_div_vanishing_dev(h, curve, p, cnt, z(4), p, None)),
+        ("poly_lincomb", lambda: L.zkhip_poly_lincomb_dev(h, curve, z(1), tab, lens, _hp(one), z(1), p, cnt, 0)),
+        ("poly_resize", lambda: L.zkhip_poly_resize_dev(h, curve, p, z(4), z(0 if zero else 1), _hp(w4), p, z(4), _hp(w4))),
+        ("perm_grand_product", lambda: L.zkhip_perm_grand_product_dev(h, curve, z(1), tab, tab, tab, cnt, _hp(one), _hp(one), None, None, p)),
+        ("perm_factor_products", lambda: L.zkhip_perm_factor_products_dev(h, curve, z(1), tab, tab, tab, cnt, _hp(one), _hp(one), p, p)),
+        ("lookup_grand_product", lambda: L.zkhip_lookup_grand_product_dev(h, curve, z(1), tab, z(1), tab, z(2), (ctypes.c_void_p * 2)(*([None] * 2 if zero else [d, d])),
+                                                                          cnt, z(0 if zero else 8), _hp(one), _hp(one), p)),
+        ("domain_fft", lambda: L.zkhip_domain_fft_dev(h, curve, ctypes.byref(dom), p, z(0 if zero else 1), 0, None)),
+    ]
+    if not zero:    # these have no empty form: a call with an unknown curve only
+        calls += [
+            ("fri_fold", lambda: L.zkhip_fri_fold_dev(h, curve, p, z(4), _hp(one), _hp(w4), p)),
+            ("gate_eval", lambda: L.zkhip_gate_eval_dev(h, curve, ctypes.byref(prog), None, z(4), None, 0, p)),
+            ("domain_lagrange", lambda: L.zkhip_domain_lagrange_dev(h, curve, ctypes.byref(dom), _hp(one), p)),
+            ("ntt_dev", lambda: L.zkhip_ntt_dev(h, curve, p, z(4), z(1), _hp(w4), 0, None)),
+            ("ntt", lambda: L.zkhip_ntt(h, curve, _hp(out), z(4), z(1), _hp(w4), 0, None)),
+            ("ec_ntt", lambda: L.zkhip_ec_ntt_dev(h, curve, 1, p, z(2), _hp(w4), 0)),
+            ("jacobian_sum", lambda: L.zkhip_jacobian_sum_dev(h, curve, 1, p, z(1), p)),
+            ("jacobian_to_affine", lambda: L.zkhip_jacobian_to_affine(h, curve, 1, _hp(out), _hp(out), _hp(out))),
+            ("bases_upload", lambda: L.zkhip_bases_upload(h, curve, 1, _hp(out), None, z(1), ctypes.byref(hdl))),
+            ("bases_upload_compressed", lambda: L.zkhip_bases_upload_compressed(h, curve, 1, _hp(out), z(1), ctypes.byref(hdl))),
+            ("bases_from_scalars", lambda: L.zkhip_bases_from_scalars(h, curve, 1, None, _hp(out), z(1), ctypes.byref(hdl))),
+            ("r1cs_upload", lambda: L.zkhip_r1cs_upload(h, curve, z(1), z(0), z(1), _hp(rp), None, None, _hp(rp), None, None, _hp(rp), None, None, ctypes.byref(hdl))),
+        ]
+    return calls
+
+
+@pytest.mark.parametrize("zero", [False, True], ids=["unknown_curve", "empty_call"])
+def test_entry_preamble(zk, zero):
+    """Every entry point that takes a curve id refuses curve = 7 (ZKHIP_ERR_INVALID = -2); an empty call -- count, n or batch 0, null
+    buffers -- returns ZKHIP_OK.  Neither launches a kernel: the profiler, which records every launch, has counted none."""
+    c = zk.Context(0)
+    try:
+        d = c.malloc(1 << 16)
+        c.h2d(d, np.zeros(1 << 13, dtype=np.uint64))
+        c.profile(True)
+        for name, call in _preamble_calls(zk, c, 0 if zero else 7, d, zero):
+            assert call() == (0 if zero else -2), name
+        assert c.profile_get("")[1] == 0
+        c.profile(False)
+        w = limbs(po.BLS12_381.root_of_unity(4), 4)    # and the context works afterwards
+        a = cp.random_fr(0, 3, 16).reshape(1, 16, 4)
+        assert (c.ntt(0, a, 4, w) == cp.ntt(0, a, 4, w)).all()
+    finally:
+        c.close()
