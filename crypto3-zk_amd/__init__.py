@@ -17,7 +17,9 @@ from .zkhip import (  # noqa: F401
     GroupBases,
     HASH_SHA2_256,
     MerkleTree,
+    PALLAS,
     R1CS,
+    VESTA,
     ZkhipError,
     build,
     coord_limbs,

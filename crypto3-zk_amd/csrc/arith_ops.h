@@ -15,11 +15,19 @@ namespace arith {
 //     10 fu_unpack(first NL words of a), 20 + j: fu_sub<2^j>(a, b) for j = 1 .. 7 where field_consts.hpp defines 2^j p.
 // L u32 in per operand and L u32 out per case, exactly as a kernel holds them (no normalisation on the way in).
 template <class U>
-struct MaxSpread {  // largest K with a spread constant: every lazy type has 128 except the BLS12-381 scalar field
+struct MaxSpread {  // largest K with a spread constant: every lazy type has 128 except the 255-bit scalar fields
     static constexpr int K = 128;
 };
 template <>
 struct MaxSpread<BlsFrU> {
+    static constexpr int K = 64;
+};
+template <>
+struct MaxSpread<PallasFrU> {  // the Pasta primes in the scalar role: 2^261 / p ~ 128, as tight as BLS12-381's r
+    static constexpr int K = 64;
+};
+template <>
+struct MaxSpread<VestaFrU> {
     static constexpr int K = 64;
 };
 

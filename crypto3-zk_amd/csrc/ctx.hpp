@@ -40,9 +40,13 @@
 // The head of an entry point, in two halves: ZK_ARGS refuses a null context or an unknown curve id before any HIP call, ZK_ENTER selects the
 // context's device.  A function's own argument and range checks and its "nothing to do" return sit between the two, so argument errors
 // never depend on the device and an empty call does not touch it.
-inline bool zk_curve_known(int curve) { return curve == zkhip::CURVE_BLS12_381 || curve == zkhip::CURVE_BN254; }
+inline bool zk_curve_known(int curve) { return curve >= zkhip::CURVE_BLS12_381 && curve <= zkhip::CURVE_VESTA; }
+// The pairing-friendly curves: the only ones with a G2, and the only ones the Groth16, wire-format and EC-NTT entry points take (ZK_ARGS_PAIRING).
+inline bool zk_curve_pairing(int curve) { return curve == zkhip::CURVE_BLS12_381 || curve == zkhip::CURVE_BN254; }
 inline bool zk_group_known(int group) { return group == zkhip::GROUP_G1 || group == zkhip::GROUP_G2; }
+inline bool zk_curve_group_known(int curve, int group) { return zk_curve_known(curve) && (group == zkhip::GROUP_G1 || (group == zkhip::GROUP_G2 && zk_curve_pairing(curve))); }
 #define ZK_ARGS(ctx, curve) if (!(ctx) || !zk_curve_known(curve)) return ZKHIP_ERR_INVALID
+#define ZK_ARGS_PAIRING(ctx, curve) if (!(ctx) || !zk_curve_pairing(curve)) return ZKHIP_ERR_INVALID
 #define ZK_ENTER(ctx) ZK_HIP_CHECK(ctx, hipSetDevice((ctx)->device))
 inline bool zk_any_null(const void *const *p, size_t count) {  // a host table of device pointers with a hole in it
     return std::any_of(p, p + count, [](const void *q) { return !q; });

@@ -7,7 +7,7 @@
 // XYZZ mixed addition costs 8M + 2S (vs 7M + 4S for Jacobian) and needs no special-casing of Z = 1,
 // which is why the bucket accumulators of the Pippenger kernels (msm.hip) use it.  All formulas are
 // complete for the cases the bucket method meets: P + P (doubling), P + (-P) (infinity), and either
-// operand at infinity.  (Points of order 2 do not exist: all four groups have odd order.)
+// operand at infinity.  (Points of order 2 do not exist: every group here -- G1 and G2 of BLS12-381 and BN254, Pallas, Vesta -- has odd order.)
 // The reference reaches the group law through crypto3-algebra (`G::value_type` operator+, `mixed_add`:
 // knowledge_commitment_multiexp.hpp:91-97); a sum is coordinate-system independent once normalised to
 // affine, which is what parity is asserted on.
@@ -220,6 +220,14 @@ struct CurveTraits<CURVE_BN254, GROUP_G1> {
 template <>
 struct CurveTraits<CURVE_BN254, GROUP_G2> {
     typedef bn_fqu2 F;
+};
+template <>
+struct CurveTraits<CURVE_PALLAS, GROUP_G1> {
+    typedef pallas_fqu F;
+};
+template <>
+struct CurveTraits<CURVE_VESTA, GROUP_G1> {
+    typedef vesta_fqu F;
 };
 
 }  // namespace zkhip

@@ -52,7 +52,7 @@ static size_t ceil_log2(size_t n) {
     return r;
 }
 
-int zk_dom_two_adicity(int curve) { return curve == CURVE_BLS12_381 ? 32 : curve == CURVE_BN254 ? 28 : -1; }
+int zk_dom_two_adicity(int curve) { return curve == CURVE_BN254 ? 28 : zk_curve_known(curve) ? 32 : -1; }
 
 bool zk_dom_choice(size_t min_size, size_t s, int *kind, size_t *m) {
     auto basic_ok = [&](size_t n) { return n > 1 && n == (size_t)1 << ceil_log2(n) && ceil_log2(n) <= s; };

@@ -348,7 +348,8 @@ int ec_ntt_t(zkhip_ctx *ctx, uint32_t *d_jac, size_t log_m, const uint64_t *omeg
 }  // namespace
 
 extern "C" int zkhip_ec_ntt_dev(zkhip_ctx *ctx, int curve, int group, void *d_jacobian, size_t log_m, const uint64_t *omega, int inverse) {
-    if (!ctx || !d_jacobian || !omega) return ZKHIP_ERR_INVALID;
+    ZK_ARGS_PAIRING(ctx, curve);  // G1 splits its twiddles with the curve's GLV constants, which exist for the two pairing curves only
+    if (!d_jacobian || !omega) return ZKHIP_ERR_INVALID;
     if (log_m > 26) return ZKHIP_ERR_RANGE;
     ZK_ENTER(ctx);
     uint32_t *d = (uint32_t *)d_jacobian;

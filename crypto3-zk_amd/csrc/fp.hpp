@@ -321,6 +321,10 @@ typedef Fp<BlsFq> bls_fq;
 typedef Fp<BlsFr> bls_fr;
 typedef Fp<BnFq> bn_fq;
 typedef Fp<BnFr> bn_fr;
+typedef Fp<PallasFq> pallas_fq;
+typedef Fp<PallasFr> pallas_fr;
+typedef Fp<VestaFq> vesta_fq;
+typedef Fp<VestaFr> vesta_fr;
 typedef Fp2<BlsFq> bls_fq2;
 typedef Fp2<BnFq> bn_fq2;
 

@@ -272,7 +272,7 @@ extern "C" {
 int zkhip_r1cs_upload(zkhip_ctx *ctx, int curve, size_t num_constraints, size_t num_inputs, size_t num_variables, const uint32_t *rowptr_a,
                       const uint32_t *col_a, const uint64_t *coeff_a, const uint32_t *rowptr_b, const uint32_t *col_b, const uint64_t *coeff_b,
                       const uint32_t *rowptr_c, const uint32_t *col_c, const uint64_t *coeff_c, zkhip_r1cs **out) {
-    ZK_ARGS(ctx, curve);
+    ZK_ARGS_PAIRING(ctx, curve);  // Groth16 needs a pairing
     if (!out || !rowptr_a || !rowptr_b || !rowptr_c) return ZKHIP_ERR_INVALID;
     if (num_inputs > num_variables || num_constraints == 0 || num_constraints >= (1ull << 31)) return ZKHIP_ERR_RANGE;
     ZK_ENTER(ctx);

@@ -351,7 +351,7 @@ static int group_bases_make(zkhip_device_group *g, int curve, int group, const u
                             size_t n, zkhip_group_bases **out) {
     if (!g || !out) return ZKHIP_ERR_INVALID;
     *out = nullptr;
-    if (!zk_curve_known(curve) || !zk_group_known(group)) return ZKHIP_ERR_INVALID;
+    if (!zk_curve_group_known(curve, group)) return ZKHIP_ERR_INVALID;
     const size_t world = g->members.size(), words = 2 * zk_coord_limbs64(curve, group);
     std::unique_ptr<zkhip_group_bases> b(new zkhip_group_bases());
     b->curve = curve;

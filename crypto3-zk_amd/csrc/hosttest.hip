@@ -29,13 +29,22 @@ using namespace zkhip::arith;
         case 9: { typedef bn_fru F; __VA_ARGS__; } break;    \
         case 10: { typedef bls_fqu2 F; __VA_ARGS__; } break; \
         case 11: { typedef bn_fqu2 F; __VA_ARGS__; } break;  \
+        case 12: { typedef pallas_fq F; __VA_ARGS__; } break; \
+        case 13: { typedef pallas_fr F; __VA_ARGS__; } break; \
+        case 14: { typedef vesta_fq F; __VA_ARGS__; } break;  \
+        case 15: { typedef vesta_fr F; __VA_ARGS__; } break;  \
+        case 16: { typedef pallas_fqu F; __VA_ARGS__; } break; \
+        case 17: { typedef vesta_fqu F; __VA_ARGS__; } break; \
+        case 18: { typedef pallas_fru F; __VA_ARGS__; } break; \
+        case 19: { typedef vesta_fru F; __VA_ARGS__; } break; \
         default: return -1;                                  \
     }
 
 extern "C" {
 
 // field: 0 BLS Fq, 1 BLS Fr, 2 BN Fq, 3 BN Fr, 4 BLS Fq2, 5 BN Fq2 (saturated reference types);
-//        6 BLS Fq, 7 BN Fq, 8 BLS Fr, 9 BN Fr, 10 BLS Fq2, 11 BN Fq2 (lazy 29-bit-limb compute types).
+//        6 BLS Fq, 7 BN Fq, 8 BLS Fr, 9 BN Fr, 10 BLS Fq2, 11 BN Fq2 (lazy 29-bit-limb compute types);
+//        12 Pallas Fq, 13 Pallas Fr, 14 Vesta Fq, 15 Vesta Fr (saturated), 16 Pallas Fq, 17 Vesta Fq, 18 Pallas Fr, 19 Vesta Fr (lazy).
 // canonical u32 limbs in and out
 int zkt_field_op(int field, int op, const uint32_t *a, const uint32_t *b, uint32_t *out) {
     if (!field_op_valid(op)) return -1;
@@ -43,7 +52,7 @@ int zkt_field_op(int field, int op, const uint32_t *a, const uint32_t *b, uint32
     return -1;
 }
 
-// raw Fu limbs in and out (arith_ops.h, fu_raw_one): type 6 BLS Fq, 7 BN Fq, 8 BLS Fr, 9 BN Fr; a, b, c, d and out hold n cases of
+// raw Fu limbs in and out (arith_ops.h, fu_raw_one): type 6 BLS Fq, 7 BN Fq, 8 BLS Fr, 9 BN Fr, 16 Pallas Fq, 17 Vesta Fq, 18 Pallas Fr, 19 Vesta Fr; a, b, c, d and out hold n cases of
 // L u32 limbs each.  The host twin of tests/cpp/arithdev.hip's zkd_fu_raw: the C++ bodies here, the inline-asm products there.
 int zkt_fu_raw(int type, int op, size_t n, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d, uint32_t *out) {
 #define FU_RAW(U)                                                                                                       \
@@ -57,15 +66,19 @@ int zkt_fu_raw(int type, int op, size_t n, const uint32_t *a, const uint32_t *b,
         case 7: FU_RAW(BnFqU)
         case 8: FU_RAW(BlsFrU)
         case 9: FU_RAW(BnFrU)
+        case 16: FU_RAW(PallasFqU)
+        case 17: FU_RAW(VestaFqU)
+        case 18: FU_RAW(PallasFrU)
+        case 19: FU_RAW(VestaFrU)
         default: return -1;
     }
 #undef FU_RAW
 }
 
-// coordinate field id as above (0/2/4/5 saturated, 6/7/10/11 lazy)
+// coordinate field id as above (0/2/4/5/12/14 saturated, 6/7/10/11/16/17 lazy)
 int zkt_point_chain(int field, const uint32_t *pts, const uint8_t *inf, const uint8_t *neg, size_t n, int mode, uint32_t k,
                     uint32_t *out, uint8_t *out_inf) {
-    if (field == 1 || field == 3 || field == 8 || field == 9) return -1;
+    if (field == 1 || field == 3 || field == 8 || field == 9 || field == 13 || field == 15 || field == 18 || field == 19) return -1;
     FIELD_SWITCH(field, point_chain<F>(pts, inf, neg, n, mode, k, out, out_inf); return 0);
     return -1;
 }
@@ -90,11 +103,16 @@ int zkt_recode(const uint32_t *scalar, int c, int W, int32_t *digits) { return r
 
 // the recoding msm_digits_only performs: fold to |s| <= (r - 1) / 2, then signed digits over the balanced windows
 // MsmWindows{bitlen(r), ceil(bitlen(r) / c)}: value = sum_w digit_w * 2^floor(w * bitlen(r) / W).
-// Returns the window count, or -1 if a carry left the top window (must not happen).  curve: 0 BLS12-381, 1 BN254.
+// Returns the window count, or -1 if a carry left the top window (must not happen).  curve: 0 BLS12-381, 1 BN254, 2 Pallas, 3 Vesta.
 int zkt_recode_folded(int curve, const uint32_t *scalar, int c, int32_t *digits) {
     uint32_t s[8];
-    const bool flip = curve == 0 ? msm_fold_scalar<BlsFr>(scalar, s) : msm_fold_scalar<BnFr>(scalar, s);
-    const int tb = curve == 0 ? 255 : 254, W = msm_windows(tb, c);
+    bool flip = false;
+    if (fr_sat_dispatch(curve, [&](auto fr) -> int {
+            flip = msm_fold_scalar<typename decltype(fr)::type>(scalar, s);
+            return 0;
+        }) != 0)
+        return -1;
+    const int tb = curve == CURVE_BN254 ? 254 : 255, W = msm_windows(tb, c);
     if (recode_windows(s, msm_make_windows(tb, W), digits) != 0) return -1;
     if (flip)
         for (int w = 0; w < W; ++w) digits[w] = -digits[w];

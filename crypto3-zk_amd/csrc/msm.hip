@@ -1,5 +1,5 @@
 // Curve-independent host side of the MSM family: window selection, dispatch to the per-(curve, group) translation
-// units (msm_bls_g1.hip, msm_bls_g2.hip, msm_bn_g1.hip, msm_bn_g2.hip; kernels and per-call logic in msm_core.hpp),
+// units (msm_bls_g1.hip, msm_bls_g2.hip, msm_bn_g1.hip, msm_bn_g2.hip, msm_pallas_g1.hip, msm_vesta_g1.hip; kernels and per-call logic in msm_core.hpp),
 // batching, and the optional HIP-graph replay of repeated calls.
 #include <algorithm>
 #include <cstdlib>
@@ -17,6 +17,8 @@ const MsmOps *zk_msm_ops(int curve, int group) {
     if (curve == CURVE_BLS12_381 && group == GROUP_G2) return zk_msm_ops_bls_g2();
     if (curve == CURVE_BN254 && group == GROUP_G1) return zk_msm_ops_bn_g1();
     if (curve == CURVE_BN254 && group == GROUP_G2) return zk_msm_ops_bn_g2();
+    if (curve == CURVE_PALLAS && group == GROUP_G1) return zk_msm_ops_pallas_g1();  // the Pasta curves have no G2
+    if (curve == CURVE_VESTA && group == GROUP_G1) return zk_msm_ops_vesta_g1();
     return nullptr;
 }
 
@@ -25,7 +27,7 @@ const MsmOps *zk_msm_ops(int curve, int group) {
     if (!ops) return ZKHIP_ERR_INVALID
 
 size_t zk_coord_limbs64(int curve, int group) {
-    size_t fq = curve == CURVE_BLS12_381 ? 6 : 4;
+    size_t fq = curve == CURVE_BLS12_381 ? 6 : 4;  // BN254, Pallas and Vesta: a 254- or 255-bit Fq
     return fq * (group == GROUP_G2 ? 2 : 1);
 }
 
@@ -74,7 +76,7 @@ static int ilog2(size_t v) {
     return l;
 }
 
-int zk_scalar_bits(int curve) { return curve == CURVE_BLS12_381 ? 255 : 254; }  // bit length of r
+int zk_scalar_bits(int curve) { return curve == CURVE_BN254 ? 254 : 255; }  // bit length of r
 
 // Window size from the number of points (tools/msm_window_sweep.py, profiles/r02_msm_window_sweep.json).  With window
 // tables all W = ceil(bitlen(r) / c) windows of a point feed the same bucket set(s) (msm_core.hpp): the work is n W mixed

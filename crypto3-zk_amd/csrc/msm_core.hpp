@@ -1,5 +1,5 @@
 // Pippenger multi-scalar multiplication for gfx950 (MI355X): kernels and per-(curve, group) host logic.
-// Included by one translation unit per (curve, group) -- msm_bls_g1.hip, msm_bls_g2.hip, msm_bn_g1.hip, msm_bn_g2.hip --
+// Included by one translation unit per (curve, group) -- msm_bls_g1.hip, msm_bls_g2.hip, msm_bn_g1.hip, msm_bn_g2.hip, msm_pallas_g1.hip, msm_vesta_g1.hip --
 // so that the four instantiations compile in parallel; msm.hip holds the curve-independent host side.
 //
 // Replaces algebra::multiexp<multiexp_method_BDLO12> / multiexp_with_mixed_addition as called at
@@ -1242,9 +1242,11 @@ int msm_stages(zkhip_ctx *ctx, const zkhip_bases *bases, const MsmCall &c, const
     const uint32_t n = c.g.n, nb = P.nb;
     const uint32_t *d_b = bases->d;  // entries address table rows from the start of the bases object
     if (!reuse_sort) {
-        if (bases->curve == CURVE_BLS12_381)
-            ZK_LAUNCH(ctx, "msm_digits", msm_digits_only<BlsFr>, grid_1d(n), dim3(256), 0, d_scalars, n, P.win, P.wrank, P.wworld, w.dig);
-        else ZK_LAUNCH(ctx, "msm_digits", msm_digits_only<BnFr>, grid_1d(n), dim3(256), 0, d_scalars, n, P.win, P.wrank, P.wworld, w.dig);
+        ZK_TRY(fr_sat_dispatch(bases->curve, [&](auto fr) -> int {
+            typedef typename decltype(fr)::type FR;
+            ZK_LAUNCH(ctx, "msm_digits", msm_digits_only<FR>, grid_1d(n), dim3(256), 0, d_scalars, n, P.win, P.wrank, P.wworld, w.dig);
+            return 0;
+        }));
         ZK_TRY((c.big_tiles ? msm_sort_run<SortBig> : msm_sort_run<SortSmall>)(ctx, c.g, c.nbh, w.dig, w.bh, w.bo, w.bsums, w.tmp_idx, w.tmp_key, w.offs, w.idx));
         // buckets by descending size
         ZK_LAUNCH(ctx, "msm_size_sort", msm_size_hist, dim3(c.sblk), dim3(256), 0, w.offs, nb, c.sblk, c.large_thresh, w.sh);

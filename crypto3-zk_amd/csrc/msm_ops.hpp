@@ -21,6 +21,8 @@ const MsmOps *zk_msm_ops_bls_g1();
 const MsmOps *zk_msm_ops_bls_g2();
 const MsmOps *zk_msm_ops_bn_g1();
 const MsmOps *zk_msm_ops_bn_g2();
+const MsmOps *zk_msm_ops_pallas_g1();
+const MsmOps *zk_msm_ops_vesta_g1();
 const MsmOps *zk_msm_ops(int curve, int group);  // nullptr for an unknown pair
 
 size_t zk_msm_target_lanes();  // buckets (= lanes) the accumulation kernel wants at least: decides the number of bucket sets

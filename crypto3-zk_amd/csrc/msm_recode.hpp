@@ -59,7 +59,7 @@ ZK_HD bool msm_fold_scalar(const uint32_t *s, uint32_t out[8]) {
     uint32_t v[8], t[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] = s[i];
-    for (int it = 0; it < 6; ++it) {  // input that is not canonical is reduced first (2^256 < 6 r for both fields)
+    for (int it = 0; it < 6; ++it) {  // input that is not canonical is reduced first (2^256 < 6 r for every scalar field here)
         uint64_t borrow = 0;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {

@@ -38,7 +38,8 @@ static inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
 namespace zkhip {
 
 // ids shared with include/zkhip.h
-enum : int { CURVE_BLS12_381 = 0, CURVE_BN254 = 1 };
+// A curve id names a group AND its scalar field: "Fr" of CURVE_PALLAS is the Vesta base field F_q, "Fr" of CURVE_VESTA the Pallas base field F_p.
+enum : int { CURVE_BLS12_381 = 0, CURVE_BN254 = 1, CURVE_PALLAS = 2, CURVE_VESTA = 3 };
 enum : int { GROUP_G1 = 1, GROUP_G2 = 2 };
 
 }  // namespace zkhip

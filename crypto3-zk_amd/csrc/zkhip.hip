@@ -4,6 +4,7 @@
 #include <cstdlib>
 
 #include "ctx.hpp"
+#include "field_consts.hpp"
 #include "msm_recode.hpp"
 #include "zk_defs.hpp"
 
@@ -359,7 +360,7 @@ int zkhip_memcpy_2d_d2d_async(zkhip_ctx *ctx, void *dst, size_t dst_pitch, const
 
 // ---- bases ------------------------------------------------------------------------------------------
 static int bases_alloc(zkhip_ctx *ctx, int curve, int group, size_t n, std::unique_ptr<zkhip_bases> &out) {
-    if (!zk_curve_known(curve) || !zk_group_known(group)) return ZKHIP_ERR_INVALID;
+    if (!zk_curve_group_known(curve, group)) return ZKHIP_ERR_INVALID;
     std::unique_ptr<zkhip_bases> b(new zkhip_bases());
     b->curve = curve;
     b->group = group;
@@ -402,9 +403,37 @@ static int bases_finish(zkhip_ctx *ctx, std::unique_ptr<zkhip_bases> &b, zkhip_b
     return ZKHIP_OK;
 }
 
+}  // extern "C"
+
+// Every coordinate of the n affine points (4 u64 limbs each; flagged points skipped) below the modulus of P?
+template <class P>
+static bool coords_canonical(const uint64_t *xy, const uint8_t *inf, size_t n) {
+    uint64_t m[4];
+    for (int i = 0; i < 4; ++i) m[i] = (uint64_t)P::mod(2 * i) | ((uint64_t)P::mod(2 * i + 1) << 32);
+    for (size_t i = 0; i < n; ++i) {
+        if (inf && inf[i]) continue;
+        for (int k = 0; k < 2; ++k) {
+            const uint64_t *c = xy + (2 * i + k) * 4;
+            int j = 3;
+            while (j > 0 && c[j] == m[j]) --j;
+            if (c[j] >= m[j]) return false;
+        }
+    }
+    return true;
+}
+
+extern "C" {
+
 int zkhip_bases_upload(zkhip_ctx *ctx, int curve, int group, const uint64_t *affine_xy, const uint8_t *is_infinity, size_t n,
                        zkhip_bases **out) {
     if (!ctx || !out || (n && !affine_xy)) return ZKHIP_ERR_INVALID;
+    // Pallas and Vesta: a 255-bit modulus in 256-bit words leaves room for values in [p, 2^256).  They are refused here, on the host, before
+    // anything is allocated (the two older ids keep what they have always done with such a coordinate: it is taken mod p).
+    if (group == GROUP_G1 && ((curve == CURVE_PALLAS && !coords_canonical<PallasFq>(affine_xy, is_infinity, n)) ||
+                              (curve == CURVE_VESTA && !coords_canonical<VestaFq>(affine_xy, is_infinity, n)))) {
+        ctx->last_error = "zkhip_bases_upload: a coordinate is not below the base-field modulus";
+        return ZKHIP_ERR_INVALID;
+    }
     ZK_TRY(check_device(ctx));
     std::unique_ptr<zkhip_bases> b;
     ZK_TRY(bases_alloc(ctx, curve, group, n, b));
@@ -423,7 +452,8 @@ int zkhip_bases_upload(zkhip_ctx *ctx, int curve, int group, const uint64_t *aff
 }
 
 int zkhip_bases_upload_compressed(zkhip_ctx *ctx, int curve, int group, const uint8_t *octets, size_t n, zkhip_bases **out) {
-    if (!ctx || !out || (n && !octets)) return ZKHIP_ERR_INVALID;
+    ZK_ARGS_PAIRING(ctx, curve);
+    if (!out || (n && !octets)) return ZKHIP_ERR_INVALID;
     if (curve != CURVE_BLS12_381) return ZKHIP_ERR_INVALID;
     ZK_TRY(check_device(ctx));
     std::unique_ptr<zkhip_bases> b;
@@ -457,6 +487,9 @@ static const uint64_t GEN_BLS_G2[24] = {
     0xe193548608b82801ULL, 0x923ac9cc3baca289ULL, 0x6d429a695160d12cULL, 0xadfd9baa8cbdd3a7ULL, 0x8cc9cdc6da2e351aULL, 0x0ce5d527727d6e11ULL,
     0xaaa9075ff05f79beULL, 0x3f370d275cec1da1ULL, 0x267492ab572e99abULL, 0xcb3e287e85a763afULL, 0x32acd2b02bc28b99ULL, 0x0606c4a02ea734ccULL};
 static const uint64_t GEN_BN_G1[8] = {1, 0, 0, 0, 2, 0, 0, 0};
+// Pallas (p - 1, 2) and Vesta (q - 1, 2): the point (-1, 2) of y^2 = x^3 + 5
+static const uint64_t GEN_PALLAS_G1[8] = {0x992d30ed00000000ULL, 0x224698fc094cf91bULL, 0, 0x4000000000000000ULL, 2, 0, 0, 0};
+static const uint64_t GEN_VESTA_G1[8] = {0x8c46eb2100000000ULL, 0x224698fc0994a8ddULL, 0, 0x4000000000000000ULL, 2, 0, 0, 0};
 static const uint64_t GEN_BN_G2[16] = {0x46debd5cd992f6edULL, 0x674322d4f75edaddULL, 0x426a00665e5c4479ULL, 0x1800deef121f1e76ULL,
                                        0x97e485b7aef312c2ULL, 0xf1aa493335a9e712ULL, 0x7260bfb731fb5d25ULL, 0x198e9393920d483aULL,
                                        0x4ce6cc0166fa7daaULL, 0xe3d1e7690c43d37bULL, 0x4aab71808dcb408fULL, 0x12c85ea5db8c6debULL,
@@ -469,7 +502,11 @@ int zkhip_bases_from_scalars(zkhip_ctx *ctx, int curve, int group, const uint64_
     std::unique_ptr<zkhip_bases> b;
     ZK_TRY(bases_alloc(ctx, curve, group, n, b));
     const uint64_t *gen = base_affine_xy;
-    if (!gen) gen = curve == CURVE_BLS12_381 ? (group == GROUP_G1 ? GEN_BLS_G1 : GEN_BLS_G2) : (group == GROUP_G1 ? GEN_BN_G1 : GEN_BN_G2);
+    if (!gen)
+        gen = curve == CURVE_PALLAS  ? GEN_PALLAS_G1
+              : curve == CURVE_VESTA ? GEN_VESTA_G1
+              : curve == CURVE_BLS12_381 ? (group == GROUP_G1 ? GEN_BLS_G1 : GEN_BLS_G2)
+                                         : (group == GROUP_G1 ? GEN_BN_G1 : GEN_BN_G2);
     DevBuf d_s, d_g;
     if (n) {
         const size_t gbytes = 2 * zk_coord_limbs64(curve, group) * 8;
@@ -590,14 +627,14 @@ int zkhip_msm(zkhip_ctx *ctx, const zkhip_bases *bases, size_t offset, size_t n,
 
 int zkhip_jacobian_sum_dev(zkhip_ctx *ctx, int curve, int group, const void *d_points, size_t count, void *d_out_jacobian) {
     if (!ctx || !d_points || !d_out_jacobian) return ZKHIP_ERR_INVALID;
-    if (!zk_curve_known(curve) || !zk_group_known(group)) return ZKHIP_ERR_INVALID;
+    if (!zk_curve_group_known(curve, group)) return ZKHIP_ERR_INVALID;
     ZK_TRY(check_device(ctx));
     return zk_jac_sum(ctx, curve, group, (const uint32_t *)d_points, count, (uint32_t *)d_out_jacobian);
 }
 
 int zkhip_jacobian_to_affine(zkhip_ctx *ctx, int curve, int group, const uint64_t *jacobian, uint64_t *affine_xy, uint8_t *is_infinity) {
     if (!ctx || !jacobian || !affine_xy || !is_infinity) return ZKHIP_ERR_INVALID;
-    if (!zk_curve_known(curve) || !zk_group_known(group)) return ZKHIP_ERR_INVALID;
+    if (!zk_curve_group_known(curve, group)) return ZKHIP_ERR_INVALID;
     ZK_TRY(check_device(ctx));
     size_t cl = zk_coord_limbs64(curve, group) * 8;
     ToAffineBuffers w = {cl / 4};

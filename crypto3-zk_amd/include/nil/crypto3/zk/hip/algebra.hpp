@@ -4,7 +4,7 @@
 // In a crypto3 tree the curve / field value types come from crypto3-algebra
 // (`CurveType::scalar_field_type::value_type`, `CurveType::template g1_type<>::value_type`, ...).  That library
 // is not part of crypto3-zk, so the shim is written against the small `curve_adapter` concept below and ships a
-// self-contained implementation of it (`native_curve<ZKHIP_BLS12_381>`, `native_curve<ZKHIP_BN254>`), built on
+// self-contained implementation of it (`native_curve<ZKHIP_BLS12_381>`, `native_curve<ZKHIP_BN254>`, and G1-only `native_curve<ZKHIP_PALLAS>`, `native_curve<ZKHIP_VESTA>`), built on
 // the same field / group-law headers the HIP kernels are compiled from (csrc/fu.hpp, csrc/curve.hpp).  A
 // crypto3 maintainer specialises `curve_adapter<nil::crypto3::algebra::curves::bls12<381>>` with the four
 // conversion functions instead (INTEGRATION.md shows it).
@@ -18,6 +18,7 @@
 #include <cstdint>
 #include <cstring>
 #include <stdexcept>
+#include <type_traits>
 #include <vector>
 
 #define ZK_NOINLINE_MUL 1
@@ -43,6 +44,30 @@ namespace detail {
         typedef zkhip::bn_fru fr;
         typedef zkhip::bn_fqu fq;
         typedef zkhip::bn_fqu2 fq2;
+    };
+    // The Pasta cycle (zkhip.h: the id names the group and ITS scalar field, so fr of Pallas is F_q and fr of Vesta is F_p).  No fq2: no G2.
+    template <>
+    struct native_fields<ZKHIP_PALLAS> {
+        typedef zkhip::pallas_fru fr;
+        typedef zkhip::pallas_fqu fq;
+    };
+    template <>
+    struct native_fields<ZKHIP_VESTA> {
+        typedef zkhip::vesta_fru fr;
+        typedef zkhip::vesta_fqu fq;
+    };
+    /// does the curve have a G2 (is it pairing-friendly)?  The KZG and Groth16 classes assert it.
+    template <int Curve>
+    struct has_g2 : std::integral_constant<bool, Curve == ZKHIP_BLS12_381 || Curve == ZKHIP_BN254> {};
+    /// coordinate field of (curve, group); names fq2 only where the curve has one
+    template <int Curve, int Group, bool = has_g2<Curve>::value>
+    struct coord_field {
+        static_assert(Group == ZKHIP_G1, "this curve has no G2: Pallas and Vesta are not pairing-friendly, only their G1 exists");
+        typedef typename native_fields<Curve>::fq type;
+    };
+    template <int Curve>
+    struct coord_field<Curve, ZKHIP_G2, true> {
+        typedef typename native_fields<Curve>::fq2 type;
     };
 }    // namespace detail
 
@@ -134,8 +159,7 @@ struct fr_value {
 /// `Coord` is the coordinate field (Fq for G1, Fq2 for G2), `Words64` the canonical u64 limbs per coordinate.
 template <int Curve, int Group>
 struct group_value {
-    typedef typename std::conditional<Group == ZKHIP_G1, typename detail::native_fields<Curve>::fq,
-                                      typename detail::native_fields<Curve>::fq2>::type F;
+    typedef typename detail::coord_field<Curve, Group>::type F;
     typedef zkhip::FieldOps<F> O;
     static constexpr std::size_t coord_limbs = O::CANON_WORDS / 2;    // u64 limbs per coordinate
     zkhip::XYZZ<F> p = zkhip::XYZZ<F>::infinity();
@@ -255,7 +279,8 @@ struct native_curve {
     static constexpr int id = Curve;
     typedef fr_value<Curve> scalar_value_type;
     typedef group_value<Curve, ZKHIP_G1> g1_value_type;
-    typedef group_value<Curve, ZKHIP_G2> g2_value_type;
+    typedef group_value<Curve, ZKHIP_G2> g2_value_type;    // naming it is harmless; USING it on a curve without G2 is a compile-time error
+    static constexpr bool has_g2 = detail::has_g2<Curve>::value;
 };
 
 /// Adapter: how the shim reads canonical limbs out of / builds values of a curve's types.
@@ -270,7 +295,8 @@ struct curve_adapter<native_curve<Curve>> {
     typedef typename curve_type::g1_value_type g1_value_type;
     typedef typename curve_type::g2_value_type g2_value_type;
     static constexpr std::size_t g1_coord_limbs = g1_value_type::coord_limbs;
-    static constexpr std::size_t g2_coord_limbs = g2_value_type::coord_limbs;
+    static constexpr bool has_g2 = curve_type::has_g2;
+    static constexpr std::size_t g2_coord_limbs = has_g2 ? 2 * g1_coord_limbs : 0;    // (not through g2_value_type: Pallas / Vesta have none)
 
     /// fr_value IS four canonical little-endian u64 limbs: bulk uploads send the caller's vectors as they lie (backend.hpp, upload_scalars)
     static constexpr bool scalars_are_canonical_limbs = true;
@@ -287,13 +313,17 @@ struct curve_adapter<native_curve<Curve>> {
     /// With them the shim offers the reference's own ARITIES (no domain constants, no context in the call): standard_domain_params,
     /// the (pk) key constructor, witness_map(cs, x, w), the scheme classes' default roots.
     static constexpr bool has_field_constants = true;
-    static constexpr unsigned two_adicity = Curve == ZKHIP_BLS12_381 ? 32 : 28;
+    static constexpr unsigned two_adicity = Curve == ZKHIP_BN254 ? 28 : 32;
     static scalar_value_type multiplicative_generator() { return scalar_value_type(Curve == ZKHIP_BLS12_381 ? 7 : 5); }
     static scalar_value_type root_of_unity(std::size_t log_n) {
         if (log_n > two_adicity) throw std::invalid_argument("root_of_unity: the scalar field has no 2^n-th root of unity for this n");
-        const std::uint64_t top[2][4] = {{0x3829971f439f0d2bULL, 0xb63683508c2280b9ULL, 0xd09b681922c813b4ULL, 0x16a2a19edfe81f20ULL},
-                                         {0x9bd61b6e725b19f0ULL, 0x402d111e41112ed4ULL, 0x00e0a7eb8ef62abcULL, 0x2a3c09f0a58a7e85ULL}};
-        scalar_value_type w = scalar_from_limbs(top[Curve == ZKHIP_BLS12_381 ? 0 : 1]);    // generator^((r - 1) / 2^s)
+        static_assert(Curve >= ZKHIP_BLS12_381 && Curve <= ZKHIP_VESTA, "no field constants for this curve id");
+        // indexed by curve id; Pallas: 5^((q - 1) / 2^32) mod q, Vesta: 5^((p - 1) / 2^32) mod p
+        const std::uint64_t top[4][4] = {{0x3829971f439f0d2bULL, 0xb63683508c2280b9ULL, 0xd09b681922c813b4ULL, 0x16a2a19edfe81f20ULL},
+                                         {0x9bd61b6e725b19f0ULL, 0x402d111e41112ed4ULL, 0x00e0a7eb8ef62abcULL, 0x2a3c09f0a58a7e85ULL},
+                                         {0xa70e2c1102b6d05fULL, 0x9bb97ea3c106f049ULL, 0x9e5c4dfd492ae26eULL, 0x2de6a9b8746d3f58ULL},
+                                         {0xbdad6fabd87ea32fULL, 0xea322bf2b7bb7584ULL, 0x362120830561f81aULL, 0x2bce74deac30ebdaULL}};
+        scalar_value_type w = scalar_from_limbs(top[Curve]);    // generator^((r - 1) / 2^s)
         for (std::size_t k = log_n; k < two_adicity; ++k) w = w * w;
         return w;
     }
@@ -303,8 +333,22 @@ struct curve_adapter<native_curve<Curve>> {
     static g2_value_type g2_from_jacobian(const std::uint64_t *xyz) { return g2_value_type::from_jacobian(xyz); }
 };
 
+namespace detail {
+    /// does the adapter's curve have a G2 and a pairing?  An adapter that does not say (`static constexpr bool has_g2`) is taken to have them.
+    template <typename Adapter, typename = void>
+    struct adapter_has_g2 : std::true_type { };
+    template <typename Adapter>
+    struct adapter_has_g2<Adapter, std::void_t<decltype(Adapter::has_g2)>> : std::integral_constant<bool, Adapter::has_g2> { };
+}    // namespace detail
+/// first line of every class that needs a pairing (the KZG family, Groth16): over Pallas / Vesta it stops the build with the reason
+#define ZKHIP_REQUIRE_PAIRING(CurveType, what)                                                                       \
+    static_assert(::nil::crypto3::zk::hip::detail::adapter_has_g2<::nil::crypto3::zk::hip::curve_adapter<CurveType>>::value, \
+                  what " needs a pairing-friendly curve (a G2 and a pairing): Pallas and Vesta have neither -- commit over them with lpc_commitment_scheme_hip")
+
 typedef native_curve<ZKHIP_BLS12_381> bls12_381;
 typedef native_curve<ZKHIP_BN254> alt_bn128_254;
+typedef native_curve<ZKHIP_PALLAS> pallas;    // scalar field F_q; a placeholder instance over pallas::base_field_type binds to vesta (zkhip.h)
+typedef native_curve<ZKHIP_VESTA> vesta;
 
 }    // namespace hip
 }    // namespace zk

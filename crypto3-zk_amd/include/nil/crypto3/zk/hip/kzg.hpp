@@ -52,6 +52,7 @@ namespace detail {
 /// kzg::params_type with the commitment key resident on the device.
 template <typename CurveType>
 struct kzg_params_hip {
+    ZKHIP_REQUIRE_PAIRING(CurveType, "KZG");
     typedef multiexp_method_hip multiexp_method;    // shadows kzg.hpp:82's BDLO12 typedef
     template <typename InputIt>
     kzg_params_hip(const context &ctx, InputIt ck_first, InputIt ck_last) : ctx(ctx), commitment_key(ctx, ck_first, ck_last) { }
@@ -88,6 +89,7 @@ private:
 /// (`root()`), where the coefficient forms are collected for proof_eval.
 template <typename CurveType>
 struct kzg_params_group_hip {
+    ZKHIP_REQUIRE_PAIRING(CurveType, "KZG");
     typedef multiexp_method_hip multiexp_method;
     /// the key from a range of group values: converted and uploaded once (member 0), replicated device to device from there
     template <typename InputIt>

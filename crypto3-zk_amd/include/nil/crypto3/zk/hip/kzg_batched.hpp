@@ -26,6 +26,7 @@ namespace hip {
 /// batched_kzg::public_key_type (kzg.hpp:300-318)
 template <typename CurveType>
 struct kzg_batched_public_key_hip {
+    ZKHIP_REQUIRE_PAIRING(CurveType, "KZG");
     typedef typename curve_adapter<CurveType>::scalar_value_type scalar_value_type;
     typedef typename curve_adapter<CurveType>::g1_value_type single_commitment_type;
     std::vector<single_commitment_type> commits;

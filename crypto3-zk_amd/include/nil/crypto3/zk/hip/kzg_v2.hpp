@@ -154,6 +154,7 @@ typename curve_adapter<CurveType>::g1_value_type kzg_proof_eval(const kzg_params
 /// over (prover.hpp:137-138, 316) included.
 template <typename CurveType, typename TranscriptType, typename PolynomialType = polynomial_dfs<CurveType>>
 class kzg_polys_evaluator_hip {
+    ZKHIP_REQUIRE_PAIRING(CurveType, "KZG");
 protected:
     /// a committed batch on the device: the coefficient forms of its polynomials, one behind the other
     struct device_batch {

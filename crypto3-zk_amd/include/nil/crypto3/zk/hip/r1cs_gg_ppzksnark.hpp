@@ -98,6 +98,7 @@ struct knowledge_commitment_vector {    // container::sparse_vector of (g, h) pa
 
 template <typename CurveType>
 struct r1cs_gg_ppzksnark_proving_key {
+    ZKHIP_REQUIRE_PAIRING(CurveType, "Groth16");
     typedef curve_adapter<CurveType> adapter;
     typename adapter::g1_value_type alpha_g1, beta_g1;
     typename adapter::g2_value_type beta_g2;
@@ -112,6 +113,7 @@ struct r1cs_gg_ppzksnark_proving_key {
 
 template <typename CurveType>
 struct r1cs_gg_ppzksnark_proof {
+    ZKHIP_REQUIRE_PAIRING(CurveType, "Groth16");
     typename curve_adapter<CurveType>::g1_value_type g_A;
     typename curve_adapter<CurveType>::g2_value_type g_B;
     typename curve_adapter<CurveType>::g1_value_type g_C;
@@ -262,6 +264,7 @@ struct query_shard {
 /// own r1cs_gg_ppzksnark_proving_key is just the default.
 template <typename CurveType, typename KeyType = r1cs_gg_ppzksnark_proving_key<CurveType>>
 class r1cs_gg_ppzksnark_proving_key_hip {
+    ZKHIP_REQUIRE_PAIRING(CurveType, "Groth16");
 public:
     typedef curve_adapter<CurveType> adapter;
     typedef KeyType host_key_type;
@@ -518,6 +521,7 @@ public:
 /// reference's r1cs_gg_ppzksnark_proving_key / r1cs_gg_ppzksnark_proof, proof.hpp:41-46: constructible from (g_A, g_B, g_C)).
 template <typename CurveType, typename KeyType = r1cs_gg_ppzksnark_proving_key<CurveType>, typename ProofType = r1cs_gg_ppzksnark_proof<CurveType>>
 class r1cs_gg_ppzksnark_prover_hip {
+    ZKHIP_REQUIRE_PAIRING(CurveType, "Groth16");
     typedef curve_adapter<CurveType> adapter;
 
 public:

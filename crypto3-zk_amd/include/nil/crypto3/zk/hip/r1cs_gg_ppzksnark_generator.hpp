@@ -115,6 +115,7 @@ struct generated_proving_key_group {
 
 template <typename CurveType>
 class r1cs_gg_ppzksnark_generator_hip {
+    ZKHIP_REQUIRE_PAIRING(CurveType, "Groth16");
     typedef curve_adapter<CurveType> adapter;
 
 public:

@@ -8,10 +8,10 @@ import subprocess
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-BLS12_381, BN254 = 0, 1
+BLS12_381, BN254, PALLAS, VESTA = 0, 1, 2, 3    # an id names a group and ITS scalar field: Fr of PALLAS is the Vesta base field and vice versa (zkhip.h)
 G1, G2 = 1, 2
 HASH_SHA2_256 = 0
-_FQ = {BLS12_381: 6, BN254: 4}
+_FQ = {BLS12_381: 6, BN254: 4, PALLAS: 4, VESTA: 4}
 
 EXPORTS = [
     "zkhip_init", "zkhip_destroy", "zkhip_strerror", "zkhip_last_error", "zkhip_set_stream", "zkhip_sync", "zkhip_device_status", "zkhip_stream_wait", "zkhip_device",

@@ -8,7 +8,7 @@
  *   - Plain C, caller owns every host buffer, nothing throws; return 0 on success, negative zkhip_status
  *     otherwise (the reference asserts, compiled out in release: prover.hpp:77,88-89; kzg.hpp:145,413).
  *   - Field elements cross the boundary as CANONICAL (non-Montgomery) little-endian 64-bit limbs:
- *       Fr (both curves) 4 limbs; BLS12-381 Fq 6 limbs; BN254 Fq 4 limbs; Fq2 = c0 limbs then c1 limbs.
+ *       Fr (every curve) 4 limbs; BLS12-381 Fq 6 limbs; BN254, Pallas and Vesta Fq 4 limbs; Fq2 = c0 limbs then c1 limbs.
  *     G1 affine = x | y; G2 affine = x.c0 | x.c1 | y.c0 | y.c1.  Infinity travels as a separate flag.
  *     The reference's in-memory representation lives in crypto3-multiprecision (not observable from the
  *     zk tree), so the shim converts through canonical integers and never memcpy's reference objects.
@@ -35,7 +35,16 @@ extern "C" {
 typedef struct zkhip_ctx zkhip_ctx;
 typedef struct zkhip_bases zkhip_bases;
 
-enum zkhip_curve { ZKHIP_BLS12_381 = 0, ZKHIP_BN254 = 1 };
+/* A curve id names a GROUP and ITS SCALAR FIELD -- for the Pasta cycle this is easy to get backwards:
+ *     p = 0x40000000000000000000000000000000224698fc094cf91b992d30ed00000001   Pallas base field  = Vesta scalar field
+ *     q = 0x40000000000000000000000000000000224698fc0994a8dd8c46eb2100000001   Pallas scalar field = Vesta base field
+ *   ZKHIP_PALLAS: points of y^2 = x^3 + 5 over F_p (generator (p - 1, 2)); its "Fr" -- scalars, NTT, polynomial and argument kernels -- is F_q.
+ *   ZKHIP_VESTA:  points of y^2 = x^3 + 5 over F_q (generator (q - 1, 2)); its "Fr" is F_p.
+ * A placeholder proof over pallas::base_field_type (= F_p) therefore runs under ZKHIP_VESTA.
+ * Both have 4-limb Fq and Fr, G1 only (ZKHIP_G2 with either id is ZKHIP_ERR_INVALID), two-adicity 32.  The entry points that need a
+ * pairing-friendly curve -- zkhip_r1cs_* / zkhip_groth16_*, zkhip_bases_upload_compressed (the wire format) and zkhip_ec_ntt_dev (GLV
+ * constants) -- answer ZKHIP_ERR_INVALID for them. */
+enum zkhip_curve { ZKHIP_BLS12_381 = 0, ZKHIP_BN254 = 1, ZKHIP_PALLAS = 2, ZKHIP_VESTA = 3 };
 enum zkhip_group { ZKHIP_G1 = 1, ZKHIP_G2 = 2 };
 enum zkhip_status {
     ZKHIP_OK = 0,
@@ -111,7 +120,8 @@ int zkhip_host_free(zkhip_ctx *ctx, void *hptr);
  * Replaces the `bases_begin, bases_end` iterator pair of algebra::multiexp at
  *   r1cs_gg_ppzksnark/prover.hpp:108-139 (A_query, B_query, H_query, L_query; layout proving_key.hpp:43-56)
  *   commitments/polynomial/kzg.hpp:143-148, 409-435 (params.commitment_key)
- * Upload once, reuse for every proof. */
+ * Upload once, reuse for every proof.
+ * ZKHIP_PALLAS / ZKHIP_VESTA: a coordinate that is not below the base-field modulus (their 4 limbs can hold one) is ZKHIP_ERR_INVALID. */
 int zkhip_bases_upload(zkhip_ctx *ctx, int curve, int group, const uint64_t *affine_xy, const uint8_t *is_infinity /* nullable */,
                        size_t n, zkhip_bases **out);
 /* out[i] = scalars[i] * base (base == NULL: the standard generator), computed on the device and left
@@ -194,7 +204,7 @@ typedef struct zkhip_domain {
     uint64_t omega[4]; /* see above */
     uint64_t shift[4]; /* extended: detail::coset_shift<F>() (= multiplicative_generator^2); ignored otherwise */
 } zkhip_domain;
-/* (kind, m) make_evaluation_domain(min_size) picks over the curve's scalar field (two-adicity 32 for BLS12-381, 28 for BN254).
+/* (kind, m) make_evaluation_domain(min_size) picks over the curve's scalar field (two-adicity 32 for BLS12-381, Pallas and Vesta, 28 for BN254).
  * ZKHIP_ERR_RANGE when only a geometric / arithmetic sequence domain would do (beyond 2^(s+1) points: out of scope). */
 int zkhip_domain_choice(int curve, size_t min_size, int *kind, size_t *m);
 /* evaluation_domain::evaluate_all_lagrange_polynomials(t) (reductions/r1cs_to_qap.hpp:152-153, the key generator's QAP evaluation
