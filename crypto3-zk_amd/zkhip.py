@@ -21,6 +21,7 @@ EXPORTS = [
     "zkhip_domain_choice", "zkhip_domain_fft_dev", "zkhip_domain_lagrange_dev",
     "zkhip_r1cs_upload", "zkhip_r1cs_free", "zkhip_r1cs_set_domain", "zkhip_r1cs_domain_size", "zkhip_r1cs_domain_kind", "zkhip_groth16_scratch_bytes", "zkhip_groth16_witness_h_dev", "zkhip_groth16_witness_h_domain_dev", "zkhip_fr_gather_dev", "zkhip_poly_resize_dev", "zkhip_fri_fold_dev", "zkhip_fri_leaves_dev", "zkhip_ec_ntt_dev",
     "zkhip_fr_vec_op_dev", "zkhip_fr_vec_affine_dev", "zkhip_fr_vec_mul_div_dev", "zkhip_fr_vec_prod_dev", "zkhip_poly_shift_dev", "zkhip_poly_eval_dev", "zkhip_poly_div_linear_dev", "zkhip_poly_div_vanishing_dev", "zkhip_poly_lincomb_dev", "zkhip_perm_grand_product_dev", "zkhip_lookup_grand_product_dev", "zkhip_lookup_sort_dev", "zkhip_perm_factor_products_dev", "zkhip_gate_eval_dev",
+    "zkhip_bases_fold", "zkhip_fr_inner_product_dev", "zkhip_fr_powers_lincomb_dev", "zkhip_fr_challenge_products_dev",
     "zkhip_merkle_build_dev", "zkhip_merkle_build_fri_dev", "zkhip_merkle_leaves", "zkhip_merkle_depth", "zkhip_merkle_root", "zkhip_merkle_digests", "zkhip_merkle_paths",
     "zkhip_merkle_free", "zkhip_pow_grind", "zkhip_sha256_host",
     "zkhip_group_init", "zkhip_group_destroy", "zkhip_group_size", "zkhip_group_ctx", "zkhip_group_last_error", "zkhip_group_set_transport", "zkhip_group_transport",
@@ -282,6 +283,31 @@ class Context:
         self._check(self.lib.zkhip_bases_from_scalars(self.h, curve, group, _p(b), _p(scalars), ctypes.c_size_t(n), ctypes.byref(h)),
                     "zkhip_bases_from_scalars")
         return Bases(self, h, curve, group, n)
+
+    def bases_fold(self, bases: "Bases", offset_lo: int, offset_hi: int, half: int, c) -> "Bases":
+        """out[i] = c * bases[offset_hi + i] + bases[offset_lo + i], i < half: a new bases object without window tables (zkhip_bases_fold)"""
+        h = ctypes.c_void_p()
+        self._check(self.lib.zkhip_bases_fold(self.h, bases.h, ctypes.c_size_t(offset_lo), ctypes.c_size_t(offset_hi), ctypes.c_size_t(half),
+                                              _p(_u64(c).reshape(4)), ctypes.byref(h)), "zkhip_bases_fold")
+        return Bases(self, h, bases.curve, bases.group, half)
+
+    # ---- inner-product argument: scalar vectors
+    def fr_inner_product_dev(self, curve: int, d_a: int, d_b: int, n: int, d_out: int):
+        self._check(self.lib.zkhip_fr_inner_product_dev(self.h, curve, ctypes.c_void_p(d_a or None), ctypes.c_void_p(d_b or None), ctypes.c_size_t(n),
+                                                        ctypes.c_void_p(d_out)), "zkhip_fr_inner_product_dev")
+
+    def fr_powers_lincomb_dev(self, curve: int, points, scales, d_out: int, n: int):
+        """d_out[i] = sum_e scales[e] * points[e]^i, i < n"""
+        pts, sc = _u64(points).reshape(-1, 4), _u64(scales).reshape(-1, 4)
+        assert pts.shape == sc.shape
+        self._check(self.lib.zkhip_fr_powers_lincomb_dev(self.h, curve, _p(pts), _p(sc), ctypes.c_size_t(pts.shape[0]), ctypes.c_void_p(d_out),
+                                                         ctypes.c_size_t(n)), "zkhip_fr_powers_lincomb_dev")
+
+    def fr_challenge_products_dev(self, curve: int, chals, d_out: int):
+        """d_out[i] = prod over the set bits t of i of chals[rounds - 1 - t], i < 2^rounds"""
+        ch = _u64(chals).reshape(-1, 4)
+        self._check(self.lib.zkhip_fr_challenge_products_dev(self.h, curve, _p(ch) if ch.shape[0] else None, ctypes.c_size_t(ch.shape[0]),
+                                                             ctypes.c_void_p(d_out)), "zkhip_fr_challenge_products_dev")
 
     # ---- MSM
     def msm(self, bases: "Bases", scalars: np.ndarray, offset: int = 0, n=None) -> np.ndarray:

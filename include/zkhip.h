@@ -425,6 +425,35 @@ int zkhip_lookup_sort_dev(zkhip_ctx *ctx, size_t k_in, const void *const *d_inpu
 int zkhip_poly_lincomb_dev(zkhip_ctx *ctx, int curve, size_t count, const void *const *d_polys, const size_t *lens, const uint64_t *coeffs,
                            size_t taps, void *d_acc, size_t acc_len, int accumulate);
 
+/* ---- inner-product argument: what kimchi_pedersen needs beyond the MSM (zk/commitments/polynomial/kimchi_pedersen.hpp) ----------
+ * The Pedersen / inner-product-argument commitment of the pairing-less curves rests on multiexp more than any other scheme: one MSM per
+ * chunk to commit (:334-383), 2 log n half-size MSMs, 2 log n inner products and 3 log n vector folds to open (:385-559), one MSM over the
+ * whole SRS to verify (:645-755).  The MSMs run over sub-ranges of resident bases (zkhip_msm_dev / zkhip_msm_batch_dev), the folds of the
+ * scalar vectors are zkhip_fr_vec_affine_dev, `a` is accumulated by zkhip_poly_lincomb_dev, L and R are completed by a two-point MSM and
+ * zkhip_jacobian_sum_dev; the four entry points below are the rest.  Conventions: G1 of every curve id; scalars are canonical Fr
+ * elements (4 limbs), vectors of them resident on the device; everything is asynchronous on the context's stream except
+ * zkhip_bases_fold, which like every constructor of bases returns with the stream drained.  ZKHIP_ERR_INVALID: a null pointer, an
+ * unknown curve id, bases of ZKHIP_G2, a scalar that is not below r; ZKHIP_ERR_RANGE: a range beyond an object's size, a size
+ * beyond the stated limit.
+ *
+ * The generator fold g = g_high * u + g_low (`compress_function_u`, :524-534): a NEW bases object of `half` points,
+ *     out[i] = c * b[offset_hi + i] + b[offset_lo + i],   i < half < 2^31,
+ * one variable-base scalar multiplication and one mixed addition per point (points at infinity, c = 0, c * hi = +-lo included).  The two
+ * ranges may overlap or coincide; b is left as it is (only its points are read: whatever window tables it has play no part).  `out`
+ * holds the points alone, affine, and carries NO window tables whatever its size -- it feeds two MSMs and the next fold, and tables
+ * would cost more than they save; an MSM over it combines the windows by the Horner pass.  Free it with zkhip_bases_free. */
+int zkhip_bases_fold(zkhip_ctx *ctx, const zkhip_bases *b, size_t offset_lo, size_t offset_hi, size_t half, const uint64_t *c /* 4 limbs */,
+                     zkhip_bases **out);
+/* d_out[0] = sum_{i < n} d_a[i] d_b[i] (algebra::inner_product, :472-475, :500-506), one canonical Fr element on the device; n < 2^39,
+ * n = 0 gives zero.  The additions form a fixed tree (per wave, per workgroup, one last workgroup; no atomics). */
+int zkhip_fr_inner_product_dev(zkhip_ctx *ctx, int curve, const void *d_a, const void *d_b, size_t n, void *d_out);
+/* d_out[i] = sum_{e < npoints} scales[e] * points[e]^i for i < n: the vector b of proof_eval (:460-470: scales[e] = evalscale^e).
+ * points / scales: host, canonical Fr; npoints < 65536 (0: the zero vector), n < 2^39. */
+int zkhip_fr_powers_lincomb_dev(zkhip_ctx *ctx, int curve, const uint64_t *points, const uint64_t *scales, size_t npoints, void *d_out, size_t n);
+/* d_out[i] = prod over the set bits t of i of chals[rounds - 1 - t], i < 2^rounds: b_poly_coefficents (:629-643), the vector s of
+ * verify_eval.  chals: host, canonical Fr (nullable when rounds = 0: d_out[0] = 1); rounds <= 31. */
+int zkhip_fr_challenge_products_dev(zkhip_ctx *ctx, int curve, const uint64_t *chals, size_t rounds, void *d_out);
+
 /* ---- the gate argument's sum over a flat program -------------------------------------------------------------------------
  * placeholder's gates argument (ph/gates_argument.hpp:93-121, 203-216) computes, on the extended domain of 2^log_size points,
  *     F = mask * sum_gates selector_g * sum_constraints theta^k * constraint(columns, rotated).
