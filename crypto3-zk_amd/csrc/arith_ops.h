@@ -13,6 +13,10 @@ namespace arith {
 // op: 0 fu_mul(a, b), 1 fu_sqr(a), 2 fu_mul2(a, b, c, d), 3 fu_add(a, b), 4 fu_cond_sub_p(a), 5 fu_canon(a),
 //     6 fu_is_zero_lt2p(a) (out[0] = 0 / 1), 7 fu_inv(a), 8 fu_inv_gcd(a), 9 fu_pack(a) (NL saturated words out),
 //     10 fu_unpack(first NL words of a), 20 + j: fu_sub<2^j>(a, b) for j = 1 .. 7 where field_consts.hpp defines 2^j p.
+//     The element layer of the scalar-field kernels: 30 fu_mulm(a, b), 31 fu_addm(a, b), 32 fu_from_mont(a), 33 fu_pow(a, e),
+//     34 fu_pow_onto(c, a, e) -- e the 64-bit integer in b's first two words -- and, where NL = 8, 35 fu_store8 / fu_load8 of a through
+//     element 1 of a 16-byte aligned three-element buffer (out: the element read back, or all-ones limbs if a neighbour changed) and
+//     36 a^e for the 256-bit e in b's first 8 words: fu_pow_onto word by word from the top, fu_pow(r, 2^32) between.
 // L u32 in per operand and L u32 out per case, exactly as a kernel holds them (no normalisation on the way in).
 template <class U>
 struct MaxSpread {  // largest K with a spread constant: every lazy type has 128 except the 255-bit scalar fields
@@ -33,7 +37,8 @@ struct MaxSpread<VestaFrU> {
 
 template <class U>
 ZK_HD bool fu_raw_valid(int op) {
-    if (op >= 0 && op <= 10) return true;
+    if ((op >= 0 && op <= 10) || (op >= 30 && op <= 34)) return true;
+    if (op == 35 || op == 36) return U::NL == 8;
     return op >= 21 && op <= 27 && (1 << (op - 20)) <= MaxSpread<U>::K;
 }
 
@@ -41,6 +46,28 @@ template <int K, class U>
 ZK_HD Fu<U> sub_k(const Fu<U> &a, const Fu<U> &b) {
     if constexpr (K <= MaxSpread<U>::K) return fu_sub<K>(a, b);
     return Fu<U>::zero();
+}
+
+// ops 35 and 36, which only the 8-word types have
+template <class U>
+ZK_HD Fu<U> fu_raw_words8(int op, const Fu<U> &x, const uint32_t *b) {
+    Fu<U> r = Fu<U>::zero();
+    if constexpr (U::NL == 8) {
+        if (op == 35) {
+            alignas(16) uint32_t buf[24];
+            for (int i = 0; i < 24; ++i) buf[i] = 0xA5A5A5A5u + i;
+            fu_store8<U>(buf, 1, x);
+            r = fu_load8<U>(buf, 1);
+            bool kept = true;
+            for (int i = 0; i < 8; ++i) kept = kept && buf[i] == 0xA5A5A5A5u + i && buf[16 + i] == 0xA5A5A5A5u + 16 + i;
+            if (!kept)  // no element reads back as this
+                for (int i = 0; i < U::L; ++i) r.v[i] = 0xFFFFFFFFu;
+        } else {
+            r = Fu<U>::one();
+            for (int w = 7; w >= 0; --w) r = fu_pow_onto(fu_pow(r, (uint64_t)1 << 32), x, b[w]);
+        }
+    }
+    return r;
 }
 
 template <class U>
@@ -65,6 +92,13 @@ ZK_HD void fu_raw_one(int op, const uint32_t *a, const uint32_t *b, const uint32
             break;
         }
         case 10: r = fu_unpack<U>(a); break;
+        case 30: r = fu_mulm(x, y); break;
+        case 31: r = fu_addm(x, y); break;
+        case 32: r = fu_from_mont(x); break;
+        case 33: r = fu_pow(x, (uint64_t)b[0] | ((uint64_t)b[1] << 32)); break;
+        case 34: r = fu_pow_onto(z, x, (uint64_t)b[0] | ((uint64_t)b[1] << 32)); break;
+        case 35:
+        case 36: r = fu_raw_words8(op, x, b); break;
         case 21: r = sub_k<2>(x, y); break;
         case 22: r = sub_k<4>(x, y); break;
         case 23: r = sub_k<8>(x, y); break;

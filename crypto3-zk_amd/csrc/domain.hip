@@ -33,17 +33,12 @@ enum { DC_BASE = 0, DC_BASEINV, DC_G, DC_HALF, DC_HALF_GINV, DC_S, DC_GS, DC_K, 
 // ---- host-side field helpers (the same __host__ __device__ arithmetic the kernels use) --------------------------------
 template <class U>
 static void h_pow(const uint64_t *base, uint64_t e, uint64_t *out) {
-    Fu<U> b = fu_from_canonical<U>(reinterpret_cast<const uint32_t *>(base)), r = Fu<U>::one();
-    for (; e; e >>= 1) {
-        if (e & 1) r = fu_mul(r, b);
-        b = fu_mul(b, b);
-    }
-    fu_to_canonical<U>(reinterpret_cast<uint32_t *>(out), r);
+    fu_to_canonical<U>(reinterpret_cast<uint32_t *>(out), fu_pow(fu_from_canonical<U>(reinterpret_cast<const uint32_t *>(base)), e));
 }
 template <class U>
 static void h_mul(const uint64_t *a, const uint64_t *b, uint64_t *out) {
     fu_to_canonical<U>(reinterpret_cast<uint32_t *>(out),
-                       fu_mul(fu_from_canonical<U>(reinterpret_cast<const uint32_t *>(a)), fu_from_canonical<U>(reinterpret_cast<const uint32_t *>(b))));
+                       fu_mulm(fu_from_canonical<U>(reinterpret_cast<const uint32_t *>(a)), fu_from_canonical<U>(reinterpret_cast<const uint32_t *>(b))));
 }
 static bool is_one(const uint64_t *a) { return a[0] == 1 && a[1] == 0 && a[2] == 0 && a[3] == 0; }
 static size_t ceil_log2(size_t n) {
@@ -103,44 +98,15 @@ int zk_dom_parse(int curve, const zkhip_domain *d, ZkDomain *out) {
     return ZKHIP_OK;
 }
 
-// 32-byte elements in global memory <-> lazy limbs (value unchanged: canonical stays canonical, Montgomery stays Montgomery)
-template <class U>
-ZK_D Fu<U> e_load(const uint32_t *p, size_t i) {
-    const uint4 *q = reinterpret_cast<const uint4 *>(p) + 2 * i;
-    const uint4 a = q[0], b = q[1];
-    const uint32_t s[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return fu_unpack<U>(s);
-}
-template <class U>
-ZK_D void e_store(uint32_t *p, size_t i, const Fu<U> &x) {  // x normalised, < 2^256
-    uint32_t s[8];
-    fu_pack<U>(s, x);
-    uint4 *q = reinterpret_cast<uint4 *>(p) + 2 * i;
-    q[0] = make_uint4(s[0], s[1], s[2], s[3]);
-    q[1] = make_uint4(s[4], s[5], s[6], s[7]);
-}
-template <class U>
-ZK_D Fu<U> addm(const Fu<U> &a, const Fu<U> &b) { return fu_cond_sub_p(fu_add(a, b)); }  // a, b < p -> a + b mod p
-template <class U>
-ZK_D Fu<U> mulm(const Fu<U> &a, const Fu<U> &b) { return fu_cond_sub_p(fu_mul(a, b)); }  // canonical x Montgomery -> canonical < p
-
 // ---- table construction -----------------------------------------------------------------------------------------------
 // in: omega, shift, coset (canonical; coset = 1 when the transform has none)
 template <class U>
 __global__ void dom_setup(int kind, const uint32_t *__restrict__ in, uint64_t n0, uint64_t n1, uint32_t *__restrict__ consts) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    auto powu = [](Fu<U> b, uint64_t e) {
-        Fu<U> r = Fu<U>::one();
-        for (; e; e >>= 1) {
-            if (e & 1) r = fu_mul_call(r, b);
-            b = fu_mul_call(b, b);
-        }
-        return r;
-    };
-    auto put = [&](int slot, const Fu<U> &x) { e_store<U>(consts, slot, fu_cond_sub_p(x)); };
+    auto put = [&](int slot, const Fu<U> &x) { fu_store8<U>(consts, slot, fu_cond_sub_p(x)); };
     const Fu<U> w = fu_from_canonical<U>(in), sh = fu_from_canonical<U>(in + 8), g = fu_from_canonical<U>(in + 16), one = Fu<U>::one();
     const Fu<U> half = fu_inv(fu_add(one, one));
-    const Fu<U> G = powu(g, n0), Ginv = fu_inv(G);
+    const Fu<U> G = fu_pow<FuMulCall>(g, n0), Ginv = fu_inv(G);
     put(DC_G, G);
     put(DC_HALF, half);
     put(DC_HALF_GINV, fu_mul_call(half, Ginv));
@@ -149,15 +115,15 @@ __global__ void dom_setup(int kind, const uint32_t *__restrict__ in, uint64_t n0
         put(DC_BASE, base);
         put(DC_BASEINV, fu_inv(base));
         // divide_by_z_on_coset: Z(g omega^(2i)) = (g^big - 1)(g^small omega^(2 small i) - omega^small), compr = big / small values
-        const Fu<U> Z0 = fu_sub<4>(G, one), w_sm = powu(w, n1);
-        put(DC_Z_STEP, powu(w, 2 * n1));
-        put(DC_Z_A, fu_mul_call(powu(g, n1), Z0));
+        const Fu<U> Z0 = fu_sub<4>(G, one), w_sm = fu_pow<FuMulCall>(w, n1);
+        put(DC_Z_STEP, fu_pow<FuMulCall>(w, 2 * n1));
+        put(DC_Z_A, fu_mul_call(fu_pow<FuMulCall>(g, n1), Z0));
         put(DC_Z_B, fu_mul_call(w_sm, Z0));
         // Z(g omega x), x in <omega_small>: ((g omega)^big - 1)((g omega)^small - omega^small)
         const Fu<U> gw = fu_mul_call(g, w);
-        put(DC_Z1, fu_inv(fu_mul_call(fu_sub<4>(powu(gw, n0), one), fu_sub<4>(powu(gw, n1), w_sm))));
+        put(DC_Z1, fu_inv(fu_mul_call(fu_sub<4>(fu_pow<FuMulCall>(gw, n0), one), fu_sub<4>(fu_pow<FuMulCall>(gw, n1), w_sm))));
     } else {  // extended
-        const Fu<U> S = powu(sh, n0), k = fu_inv(fu_sub<4>(one, S));
+        const Fu<U> S = fu_pow<FuMulCall>(sh, n0), k = fu_inv(fu_sub<4>(one, S));
         put(DC_S, S);
         put(DC_GS, fu_mul_call(G, S));
         put(DC_K, k);
@@ -173,12 +139,12 @@ template <class U>
 __global__ __launch_bounds__(256) void dom_pow_table(const uint32_t *__restrict__ consts, int slot, uint64_t count, uint32_t *__restrict__ out) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
-    Fu<U> b = e_load<U>(consts, slot), r = Fu<U>::one();
-    for (uint64_t e = i; e; e >>= 1) {
+    Fu<U> b = fu_load8<U>(consts, slot), r = Fu<U>::one();
+    for (uint64_t e = i; e; e >>= 1) {  // spelled out, like the two below: fu_pow here moves the kernel's scalar code (EXPERIMENTS 20)
         if (e & 1) r = fu_mul(r, b);
         b = fu_mul(b, b);
     }
-    e_store<U>(out, i, fu_cond_sub_p(r));
+    fu_store8<U>(out, i, fu_cond_sub_p(r));
 }
 // step: zinv[j] = 1 / (A step^j - B), j < nz;  zinv[nz] = Z1 (already inverted).  extended: zinv[0] = DC_Z_A, zinv[1] = DC_Z1
 template <class U>
@@ -186,20 +152,20 @@ __global__ __launch_bounds__(64) void dom_zinv_table(int kind, const uint32_t *_
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j > nz) return;
     if (j == nz) {
-        e_store<U>(out, nz, e_load<U>(consts, DC_Z1));
+        fu_store8<U>(out, nz, fu_load8<U>(consts, DC_Z1));
         return;
     }
     if (kind != ZKHIP_DOMAIN_STEP_RADIX2) {
-        e_store<U>(out, 0, e_load<U>(consts, DC_Z_A));
+        fu_store8<U>(out, 0, fu_load8<U>(consts, DC_Z_A));
         return;
     }
-    Fu<U> b = e_load<U>(consts, DC_Z_STEP), r = Fu<U>::one();
+    Fu<U> b = fu_load8<U>(consts, DC_Z_STEP), r = Fu<U>::one();
     for (uint64_t e = j; e; e >>= 1) {
         if (e & 1) r = fu_mul_call(r, b);
         b = fu_mul_call(b, b);
     }
-    const Fu<U> z = fu_sub<2>(fu_mul_call(e_load<U>(consts, DC_Z_A), r), e_load<U>(consts, DC_Z_B));
-    e_store<U>(out, j, fu_cond_sub_p(fu_inv(z)));
+    const Fu<U> z = fu_sub<2>(fu_mul_call(fu_load8<U>(consts, DC_Z_A), r), fu_load8<U>(consts, DC_Z_B));
+    fu_store8<U>(out, j, fu_cond_sub_p(fu_inv(z)));
 }
 
 template <class U>
@@ -283,14 +249,14 @@ struct StepArgs {
 // d_i = T[i] x_i with x_i = a[i] - G a[big + i] (i < small; also rewrites a[i] += G a[big + i]) or a[i]; inverse: 0 for i < small
 template <class U>
 ZK_D Fu<U> step_term(const StepArgs &s, size_t b, uint64_t i, const Fu<U> &G) {
-    Fu<U> x = e_load<U>(s.p0, b * s.big + i);
+    Fu<U> x = fu_load8<U>(s.p0, b * s.big + i);
     if (i < s.small) {
         if (s.p1 == nullptr) return Fu<U>::zero();
-        const Fu<U> gh = mulm(e_load<U>(s.p1, b * s.small + i), G);
-        e_store<U>(s.p0, b * s.big + i, addm(x, gh));
+        const Fu<U> gh = fu_mulm(fu_load8<U>(s.p1, b * s.small + i), G);
+        fu_store8<U>(s.p0, b * s.big + i, fu_addm(x, gh));
         x = fu_sub<2>(x, gh);
     }
-    return mulm(x, e_load<U>(s.T, i));
+    return fu_mulm(x, fu_load8<U>(s.T, i));
 }
 // regime A (small <= 256): a block sums a tile of 256 K consecutive indices by column (= thread index mod small)
 template <class U>
@@ -298,12 +264,12 @@ __global__ __launch_bounds__(256) void step_colsum_a(StepArgs s) {
     __shared__ uint32_t part[256 * U::L];
     const uint32_t t = threadIdx.x;
     const size_t b = blockIdx.y;
-    const Fu<U> G = e_load<U>(s.consts, DC_G);
+    const Fu<U> G = fu_load8<U>(s.consts, DC_G);
     Fu<U> acc = Fu<U>::zero();
     const uint64_t base = (uint64_t)blockIdx.x * 256 * s.K;
     for (uint32_t k = 0; k < s.K; ++k) {
         const uint64_t i = base + t + 256ull * k;
-        if (i < s.big) acc = addm(acc, step_term<U>(s, b, i, G));
+        if (i < s.big) acc = fu_addm(acc, step_term<U>(s, b, i, G));
     }
     if (s.small < 256) {
 #pragma unroll
@@ -314,25 +280,25 @@ __global__ __launch_bounds__(256) void step_colsum_a(StepArgs s) {
                 Fu<U> o;
 #pragma unroll
                 for (int i = 0; i < U::L; ++i) o.v[i] = part[i * 256 + t + d];
-                acc = addm(acc, o);
+                acc = fu_addm(acc, o);
 #pragma unroll
                 for (int i = 0; i < U::L; ++i) part[i * 256 + t] = acc.v[i];
             }
             __syncthreads();
         }
     }
-    if (t < s.small) e_store<U>(s.partial, (b * s.P + blockIdx.x) * s.small + t, acc);
+    if (t < s.small) fu_store8<U>(s.partial, (b * s.P + blockIdx.x) * s.small + t, acc);
 }
 // regime B (small >= 512): a block owns 256 columns and R rows of the (big / small) x small matrix
 template <class U>
 __global__ __launch_bounds__(256) void step_colsum_b(StepArgs s) {
     const size_t b = blockIdx.z;
     const uint64_t col = (uint64_t)blockIdx.x * 256 + threadIdx.x, rows = s.big / s.small;
-    const Fu<U> G = e_load<U>(s.consts, DC_G);
+    const Fu<U> G = fu_load8<U>(s.consts, DC_G);
     Fu<U> acc = Fu<U>::zero();
     const uint64_t r0 = (uint64_t)blockIdx.y * s.R, r1 = min(rows, r0 + s.R);
-    for (uint64_t r = r0; r < r1; ++r) acc = addm(acc, step_term<U>(s, b, r * s.small + col, G));
-    e_store<U>(s.partial, (b * s.P + blockIdx.y) * s.small + col, acc);
+    for (uint64_t r = r0; r < r1; ++r) acc = fu_addm(acc, step_term<U>(s, b, r * s.small + col, G));
+    fu_store8<U>(s.partial, (b * s.P + blockIdx.y) * s.small + col, acc);
 }
 // out[b][col] = sum_p partial[b][p][col]
 template <class U>
@@ -343,12 +309,12 @@ __global__ __launch_bounds__(256) void step_colsum_finish(const uint32_t *__rest
     Fu<U> acc = Fu<U>::zero();
     if (small >= 256) {
         const uint64_t col = (uint64_t)blockIdx.x * 256 + t;
-        for (uint32_t p = 0; p < P; ++p) acc = addm(acc, e_load<U>(partial, (b * P + p) * small + col));
-        e_store<U>(out, b * small + col, acc);
+        for (uint32_t p = 0; p < P; ++p) acc = fu_addm(acc, fu_load8<U>(partial, (b * P + p) * small + col));
+        fu_store8<U>(out, b * small + col, acc);
         return;
     }
     const uint32_t col = t & ((uint32_t)small - 1), lanes = 256 / (uint32_t)small;
-    for (uint32_t p = t / (uint32_t)small; p < P; p += lanes) acc = addm(acc, e_load<U>(partial, (b * P + p) * small + col));
+    for (uint32_t p = t / (uint32_t)small; p < P; p += lanes) acc = fu_addm(acc, fu_load8<U>(partial, (b * P + p) * small + col));
 #pragma unroll
     for (int i = 0; i < U::L; ++i) part[i * 256 + t] = acc.v[i];
     __syncthreads();
@@ -357,13 +323,13 @@ __global__ __launch_bounds__(256) void step_colsum_finish(const uint32_t *__rest
             Fu<U> o;
 #pragma unroll
             for (int i = 0; i < U::L; ++i) o.v[i] = part[i * 256 + t + d];
-            acc = addm(acc, o);
+            acc = fu_addm(acc, o);
 #pragma unroll
             for (int i = 0; i < U::L; ++i) part[i * 256 + t] = acc.v[i];
         }
         __syncthreads();
     }
-    if (t < small) e_store<U>(out, b * small + t, acc);
+    if (t < small) fu_store8<U>(out, b * small + t, acc);
 }
 // the last step of the inverse transform, j < small (see the file header)
 template <class U>
@@ -373,10 +339,10 @@ __global__ __launch_bounds__(256) void step_inv_post(uint32_t *__restrict__ p0, 
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t b = blockIdx.y;
     if (j >= small) return;
-    const Fu<U> v0 = e_load<U>(p0, b * big + j), v1 = e_load<U>(p1, b * small + j), s = e_load<U>(colsum, b * small + j);
-    const Fu<U> u = mulm(fu_sub<2>(v1, s), e_load<U>(Tinv, j));
-    e_store<U>(p0, b * big + j, mulm(fu_add(v0, u), e_load<U>(consts, DC_HALF)));
-    e_store<U>(p1, b * small + j, mulm(fu_sub<2>(v0, u), e_load<U>(consts, DC_HALF_GINV)));
+    const Fu<U> v0 = fu_load8<U>(p0, b * big + j), v1 = fu_load8<U>(p1, b * small + j), s = fu_load8<U>(colsum, b * small + j);
+    const Fu<U> u = fu_mulm(fu_sub<2>(v1, s), fu_load8<U>(Tinv, j));
+    fu_store8<U>(p0, b * big + j, fu_mulm(fu_add(v0, u), fu_load8<U>(consts, DC_HALF)));
+    fu_store8<U>(p1, b * small + j, fu_mulm(fu_sub<2>(v0, u), fu_load8<U>(consts, DC_HALF_GINV)));
 }
 // ---- extended domain ---------------------------------------------------------------------------------------------------
 // forward: (lo, hi) -> (lo + G hi, lo + G S hi);  inverse: (W0, W1) -> ((W1 - S W0) k, (W0 - W1) k / G)
@@ -385,14 +351,14 @@ __global__ __launch_bounds__(256) void ext_mix(uint32_t *__restrict__ p0, uint32
                                                const uint32_t *__restrict__ consts) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
-    const Fu<U> a = e_load<U>(p0, i), c = e_load<U>(p1, i);
+    const Fu<U> a = fu_load8<U>(p0, i), c = fu_load8<U>(p1, i);
     if (!inverse) {
-        e_store<U>(p0, i, addm(a, mulm(c, e_load<U>(consts, DC_G))));
-        e_store<U>(p1, i, addm(a, mulm(c, e_load<U>(consts, DC_GS))));
+        fu_store8<U>(p0, i, fu_addm(a, fu_mulm(c, fu_load8<U>(consts, DC_G))));
+        fu_store8<U>(p1, i, fu_addm(a, fu_mulm(c, fu_load8<U>(consts, DC_GS))));
     } else {
-        const Fu<U> sw0 = mulm(a, e_load<U>(consts, DC_S));
-        e_store<U>(p0, i, mulm(fu_sub<2>(c, sw0), e_load<U>(consts, DC_K)));
-        e_store<U>(p1, i, mulm(fu_sub<2>(a, c), e_load<U>(consts, DC_K_GINV)));
+        const Fu<U> sw0 = fu_mulm(a, fu_load8<U>(consts, DC_S));
+        fu_store8<U>(p0, i, fu_mulm(fu_sub<2>(c, sw0), fu_load8<U>(consts, DC_K)));
+        fu_store8<U>(p1, i, fu_mulm(fu_sub<2>(a, c), fu_load8<U>(consts, DC_K_GINV)));
     }
 }
 
@@ -505,8 +471,8 @@ __global__ void dom_zinv_basic(const uint32_t *__restrict__ coset_c, uint64_t m,
         g = fu_mul_call(g, g);
     }
     const Fu<U> z = fu_cond_sub_p(fu_inv(fu_sub<4>(r, Fu<U>::one())));
-    e_store<U>(out, 0, z);
-    e_store<U>(out, 1, z);
+    fu_store8<U>(out, 0, z);
+    fu_store8<U>(out, 1, z);
 }
 template <class U>
 static int dom_zinv_t(zkhip_ctx *ctx, int curve, const ZkDomain &d, const uint64_t *coset, const uint32_t **d_zinv, size_t *nz) {
@@ -560,9 +526,9 @@ __global__ __launch_bounds__(64) void dom_lagrange(const uint32_t *__restrict__ 
     const uint64_t lo = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * LAG_CHUNK;
     if (lo >= n) return;
     const uint32_t cnt = (uint32_t)(n - lo < LAG_CHUNK ? n - lo : LAG_CHUNK);
-    const Fu<U> w = e_load<U>(consts, 0), winv = e_load<U>(consts, 1), t = e_load<U>(consts, 2), c = e_load<U>(consts, 3);
+    const Fu<U> w = fu_load8<U>(consts, 0), winv = fu_load8<U>(consts, 1), t = fu_load8<U>(consts, 2), c = fu_load8<U>(consts, 3);
     Fu<U> x = Fu<U>::one(), b = w;
-    for (uint64_t e = lo; e; e >>= 1) {
+    for (uint64_t e = lo; e; e >>= 1) {  // spelled out: fu_pow here changes the kernel's scratch size (EXPERIMENTS 20)
         if (e & 1) x = fu_mul_call(x, b);
         b = fu_mul_call(b, b);
     }
@@ -576,13 +542,12 @@ __global__ __launch_bounds__(64) void dom_lagrange(const uint32_t *__restrict__ 
         if (k + 1 < cnt) x = fu_cond_sub_p(fu_mul_call(x, w));
     }
     Fu<U> inv = fu_inv(acc);  // x is now w^(lo + cnt - 1)
-    Fu<U> plain = Fu<U>::zero();
-    plain.v[0] = 1;
+    const Fu<U> plain = Fu<U>::plain_one();
     for (uint32_t k = cnt; k-- > 0;) {
         const Fu<U> den = unit ? fu_sub<2>(x, t) : fu_sub<2>(t, x);
         Fu<U> r = fu_mul_call(fu_mul_call(inv, pre[k]), c);  // c / den_k
         if (!unit) r = fu_mul_call(r, x);
-        e_store<U>(out, out_off + lo + k, fu_cond_sub_p(fu_mul_call(r, plain)));  // out of Montgomery form
+        fu_store8<U>(out, out_off + lo + k, fu_cond_sub_p(fu_mul_call(r, plain)));  // out of Montgomery form
         inv = fu_mul_call(inv, den);
         x = fu_cond_sub_p(fu_mul_call(x, winv));
     }
@@ -592,7 +557,7 @@ template <class U>
 __global__ __launch_bounds__(256) void dom_scale_by_table(uint32_t *__restrict__ out, uint64_t n, const uint32_t *__restrict__ tab, uint64_t nz) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    e_store<U>(out, i, fu_cond_sub_p(fu_mul(fu_mul(e_load<U>(out, i), e_load<U>(tab, i % nz)), Fu<U>::r2())));
+    fu_store8<U>(out, i, fu_mulm(fu_mul(fu_load8<U>(out, i), fu_load8<U>(tab, i % nz)), Fu<U>::r2()));
 }
 
 // host side of zkhip_domain_lagrange_dev: field arithmetic on canonical limbs with the kernels' own code
@@ -605,17 +570,10 @@ struct HF {
         const uint64_t c[4] = {x, 0, 0, 0};
         return from(c);
     }
-    HF operator*(const HF &o) const { return {fu_cond_sub_p(fu_mul(v, o.v))}; }
+    HF operator*(const HF &o) const { return {fu_mulm(v, o.v)}; }
     HF operator-(const HF &o) const { return {fu_canon(fu_sub<4>(v, o.v))}; }
     HF inv() const { return {fu_cond_sub_p(fu_inv(v))}; }
-    HF pow(uint64_t e) const {
-        HF r = one(), b = *this;
-        for (; e; e >>= 1) {
-            if (e & 1) r = r * b;
-            b = b * b;
-        }
-        return r;
-    }
+    HF pow(uint64_t e) const { return {fu_pow<FuMulm>(v, e)}; }
     bool is_zero() const { return fu_canon(v).limbs_zero(); }
     void store_mont(uint32_t *dst) const {  // 8 words, canonical representative of the Montgomery form
         fu_pack<U>(dst, fu_canon(v));

@@ -81,10 +81,7 @@ __global__ __launch_bounds__(256) void gate_eval(const uint32_t *const *__restri
     }
     Fu<U> last;
     if (mask) last = fu_unpack<U>(mask + row * U::NL);
-    else {
-        last = Fu<U>::zero();
-        last.v[0] = 1;
-    }
+    else last = Fu<U>::plain_one();
     fu_pack<U>(out + row * U::NL, fu_cond_sub_p(fu_mul(total, last)));
 }
 

@@ -95,12 +95,6 @@ __global__ __launch_bounds__(64) void ipa_bases_fold(const uint32_t *__restrict_
 }
 
 // ---- scalar-field kernels -------------------------------------------------------------------------------------------------------------
-// x + y for canonical representatives, canonical again
-template <class U>
-ZK_D Fu<U> fr_add_canon(const Fu<U> &x, const Fu<U> &y) {
-    return fu_cond_sub_p(fu_add(x, y));
-}
-
 constexpr uint32_t IP_THREADS = 256, IP_MAX_BLOCKS = 1024;
 
 // The sum of one value per lane over the workgroup, in a fixed order: down the wave by lane shuffles, the waves' sums through LDS, added up
@@ -112,13 +106,13 @@ ZK_D Fu<U> ip_block_sum(Fu<U> v, uint32_t *lds) {
         Fu<U> o;
 #pragma unroll
         for (int l = 0; l < L; ++l) o.v[l] = (uint32_t)__shfl_down((int)v.v[l], off, 64);
-        v = fr_add_canon(v, o);
+        v = fu_addm(v, o);
     }
     const uint32_t wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) fu_store<U>(lds + (size_t)wave * U::SL, v);
     __syncthreads();
     if (threadIdx.x == 0)
-        for (uint32_t w = 1; w < IP_THREADS / 64; ++w) v = fr_add_canon(v, fu_load<U>(lds + (size_t)w * U::SL));
+        for (uint32_t w = 1; w < IP_THREADS / 64; ++w) v = fu_addm(v, fu_load<U>(lds + (size_t)w * U::SL));
     return v;
 }
 
@@ -129,7 +123,7 @@ __global__ __launch_bounds__(IP_THREADS) void ipa_inner_product_blocks(const uin
     __shared__ __attribute__((aligned(16))) uint32_t lds[(IP_THREADS / 64) * U::SL];
     Fu<U> acc = Fu<U>::zero();
     for (size_t i = (size_t)blockIdx.x * IP_THREADS + threadIdx.x; i < n; i += (size_t)gridDim.x * IP_THREADS)
-        acc = fr_add_canon(acc, fu_cond_sub_p(fu_mul(fu_unpack<U>(a + i * U::NL), fu_unpack<U>(b + i * U::NL))));
+        acc = fu_addm(acc, fu_mulm(fu_unpack<U>(a + i * U::NL), fu_unpack<U>(b + i * U::NL)));
     acc = ip_block_sum<U>(acc, lds);
     if (threadIdx.x == 0) fu_store<U>(part + (size_t)blockIdx.x * U::SL, acc);
 }
@@ -139,9 +133,9 @@ template <class U>
 __global__ __launch_bounds__(IP_THREADS) void ipa_inner_product_final(const uint32_t *__restrict__ part, uint32_t nparts, uint32_t *__restrict__ out) {
     __shared__ __attribute__((aligned(16))) uint32_t lds[(IP_THREADS / 64) * U::SL];
     Fu<U> acc = Fu<U>::zero();
-    for (uint32_t i = threadIdx.x; i < nparts; i += IP_THREADS) acc = fr_add_canon(acc, fu_load<U>(part + (size_t)i * U::SL));
+    for (uint32_t i = threadIdx.x; i < nparts; i += IP_THREADS) acc = fu_addm(acc, fu_load<U>(part + (size_t)i * U::SL));
     acc = ip_block_sum<U>(acc, lds);
-    if (threadIdx.x == 0) fu_pack<U>(out, fu_cond_sub_p(fu_mul(acc, Fu<U>::r2())));
+    if (threadIdx.x == 0) fu_pack<U>(out, fu_mulm(acc, Fu<U>::r2()));
 }
 
 constexpr uint32_t POWERS_CHUNK = 32;  // consecutive exponents per lane: one power by square-and-multiply, then a running product
@@ -155,26 +149,14 @@ __global__ __launch_bounds__(256) void ipa_powers_lincomb(const uint32_t *__rest
     const size_t hi = n - i0 < POWERS_CHUNK ? n : i0 + POWERS_CHUNK;
     for (uint32_t e = 0; e < npoints; ++e) {
         const Fu<U> x = fu_cond_sub_p(fu_from_canonical<U>(pts + (size_t)e * U::NL));  // Montgomery
-        Fu<U> pw = fu_unpack<U>(pts + (size_t)(npoints + e) * U::NL), sq = x;       // plain: scale * x^i0 below
-        for (size_t k = i0; k; k >>= 1) {
-            if (k & 1) pw = fu_mul(pw, sq);
-            sq = fu_mul(sq, sq);
-        }
+        Fu<U> pw = fu_pow_onto(fu_unpack<U>(pts + (size_t)(npoints + e) * U::NL), x, i0);  // plain: scale * x^i0
         for (size_t i = i0; i < hi; ++i) {
             Fu<U> v = fu_cond_sub_p(pw);
-            if (e) v = fr_add_canon(v, fu_unpack<U>(out + i * U::NL));
+            if (e) v = fu_addm(v, fu_unpack<U>(out + i * U::NL));
             fu_pack<U>(out + i * U::NL, v);
             pw = fu_mul(pw, x);
         }
     }
-}
-
-// canonical -> Montgomery (canonical representative) for a short table of constants, SL words per entry
-template <class U>
-__global__ void ipa_table_to_mont(const uint32_t *__restrict__ canon, uint32_t count, uint32_t *__restrict__ mont) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    fu_store<U>(mont + (size_t)i * U::SL, fu_cond_sub_p(fu_from_canonical<U>(canon + (size_t)i * U::NL)));
 }
 
 // out[i] = prod over the set bits t of i of chal[rounds - 1 - t], i < 2^rounds; chal in Montgomery form
@@ -182,8 +164,7 @@ template <class U>
 __global__ __launch_bounds__(256) void ipa_challenge_products(const uint32_t *__restrict__ chal, uint32_t rounds, uint32_t *__restrict__ out) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >> rounds) return;
-    Fu<U> acc = Fu<U>::zero();
-    acc.v[0] = 1;  // the plain 1: products with Montgomery factors stay plain
+    Fu<U> acc = Fu<U>::plain_one();  // products with Montgomery factors stay plain
     for (uint32_t t = 0; t < rounds; ++t)
         if ((i >> t) & 1) acc = fu_mul(acc, fu_load<U>(chal + (size_t)(rounds - 1 - t) * U::SL));
     fu_pack<U>(out + i * U::NL, fu_cond_sub_p(acc));
@@ -309,7 +290,7 @@ int zkhip_fr_challenge_products_dev(zkhip_ctx *ctx, int curve, const uint64_t *c
     return fr_dispatch(curve, [&](auto u) -> int {
         using U = typename decltype(u)::type;
         static_assert(U::SL <= 16, "challenge slot");
-        if (rounds) ZK_LAUNCH(ctx, "ipa_challenge_setup", ipa_table_to_mont<U>, grid_1d(rounds, 64), dim3(64), 0, w.c, (uint32_t)rounds, w.m);
+        if (rounds) ZK_LAUNCH(ctx, "ipa_challenge_setup", fr_table_to_mont<U>, grid_1d(rounds, 64), dim3(64), 0, w.c, (uint32_t)rounds, w.m);
         ZK_LAUNCH(ctx, "ipa_challenge_products", ipa_challenge_products<U>, grid_1d((size_t)1 << rounds), dim3(256), 0, w.m, (uint32_t)rounds, (uint32_t *)d_out);
         return ZKHIP_OK;
     });

@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256) void ntt_pow_table(const uint32_t *__restrict_
     if (i >= count) return;
     Fu<U> b = fu_load<U>(base), r = Fu<U>::one();
     uint64_t e = (uint64_t)i << shift;
-    while (e) {
+    while (e) {  // spelled out: fu_pow here costs the Pasta instances a scalar register (EXPERIMENTS 20)
         if (e & 1) r = fu_mul(r, b);
         b = fu_mul(b, b);
         e >>= 1;
@@ -114,7 +114,7 @@ ZK_D Fu<U> tw_lookup(const uint32_t *__restrict__ lo, const uint32_t *__restrict
     uint32_t eh = (uint32_t)(e >> lo_bits);
     Fu<U> a = fu_load<U>(lo + (size_t)el * U::SL);
     if (eh == 0) return a;
-    return fu_cond_sub_p(fu_mul(a, fu_load<U>(hi + (size_t)eh * U::SL)));  // canonical, like the table entries
+    return fu_mulm(a, fu_load<U>(hi + (size_t)eh * U::SL));  // canonical, like the table entries
 }
 
 ZK_D uint32_t bitrev(uint32_t v, uint32_t bits) { return bits == 0 ? 0 : (__brev(v) >> (32 - bits)); }
@@ -140,23 +140,6 @@ ZK_D void lds_put(uint4 *lds, uint32_t slots, uint32_t e, const Fu<U> &x) {
     reinterpret_cast<uint32_t *>(lds + 2 * slots)[e] = x.v[8];
 }
 ZK_HD uint32_t ntt_tile_u4(uint32_t slots) { return 2 * slots + (slots + 3) / 4; }  // uint4 units of one tile's three planes
-
-// canonical 8 x u32 in global memory <-> lazy limbs
-template <class U>
-ZK_D Fu<U> g_load(const uint32_t *p) {
-    const uint4 *q = reinterpret_cast<const uint4 *>(p);
-    uint4 a = q[0], b = q[1];
-    uint32_t s[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return fu_unpack<U>(s);
-}
-template <class U>
-ZK_D void g_store(uint32_t *p, const Fu<U> &x) {
-    uint32_t s[8];
-    fu_pack<U>(s, x);
-    uint4 *q = reinterpret_cast<uint4 *>(p);
-    q[0] = make_uint4(s[0], s[1], s[2], s[3]);
-    q[1] = make_uint4(s[4], s[5], s[6], s[7]);
-}
 
 // "limb form": the 9 x 29-bit limbs as they are -- limbs 0-7 in 32 bytes at element index i, limb 8 in a 4-byte plane
 // `planeb` words behind the array's base.  The factor tables and the intermediate vectors between passes use it: no
@@ -216,7 +199,7 @@ __global__ __launch_bounds__(256) void ntt_build_tw(NttTwGeom g, uint32_t *__res
     const uint64_t jn = oi & ((1ull << n_log_stride) - 1), tn = oi >> n_log_stride;
     const uint64_t ex = ((jn & ((1ull << n_log_ns) - 1)) * tn) << n_tw_shift;
     Fu<U> f = tw_lookup<U>(g.lo, g.hi, g.lo_bits, ex);
-    if (g.scale != nullptr) f = fu_cond_sub_p(fu_mul(f, fu_load<U>(g.scale)));
+    if (g.scale != nullptr) f = fu_mulm(f, fu_load<U>(g.scale));
     l_store<U>(out, (size_t)8 << g.log_m, oi, f);
 }
 // out[i] = scale * base^i (the coset factors), same format
@@ -226,7 +209,7 @@ __global__ __launch_bounds__(256) void ntt_build_powers(const uint32_t *__restri
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >> log_m) return;
     Fu<U> f = tw_lookup<U>(lo, hi, lo_bits, i);
-    if (scale != nullptr) f = fu_cond_sub_p(fu_mul(f, fu_load<U>(scale)));
+    if (scale != nullptr) f = fu_mulm(f, fu_load<U>(scale));
     l_store<U>(out, (size_t)8 << log_m, i, f);
 }
 // stage[q] = omega^(q << shift), q < count, Fu form
@@ -279,11 +262,11 @@ __global__ __launch_bounds__(256) void ntt_pass(NttPass p) {
                 if (p.in_lazy) {
                     x = l_load<U>(p.in, p.planeb, ei);
                 } else {  // the source's coefficient times this coset's g^index
-                    x = g_load<U>(p.in + ((((size_t)ext_src[b]) << p.log_m) + gi) * 8);
+                    x = fu_load8<U>(p.in, (((size_t)ext_src[b]) << p.log_m) + gi);
                     x = fu_mul(x, l_load<U>(p.ext_pre + (size_t)ext_j[b] * ((size_t)9 << p.log_m), (size_t)8 << p.log_m, gi));
                 }
             } else {
-                x = p.in_lazy ? l_load<U>(p.in, p.planeb, ei) : g_load<U>(p.in + ei * 8);
+                x = p.in_lazy ? l_load<U>(p.in, p.planeb, ei) : fu_load8<U>(p.in, ei);
                 if (p.pre) x = fu_mul(x, g);
             }
             lds_put(lds + b * tile_u4, slots, slot, x);
@@ -372,13 +355,13 @@ __global__ __launch_bounds__(256) void ntt_pass(NttPass p) {
                 l_store<U>(p.out, p.planeb, eo, fu_mul(x, f));
                 continue;
             }
-            if (ftab) x = fu_cond_sub_p(fu_mul(x, f));
-            else if (p.scale) x = fu_cond_sub_p(fu_mul(x, scale));
+            if (ftab) x = fu_mulm(x, f);
+            else if (p.scale) x = fu_mulm(x, scale);
             else x = fu_reduce_small(x);
             if constexpr (EXT) {
-                g_store<U>(p.out + ((((size_t)ext_src[b]) << (p.log_m + p.ext_log_k)) + ((size_t)oi << p.ext_log_k) + ext_j[b] + 1) * 8, x);
+                fu_store8<U>(p.out, (((size_t)ext_src[b]) << (p.log_m + p.ext_log_k)) + ((size_t)oi << p.ext_log_k) + ext_j[b] + 1, x);
             } else {
-                g_store<U>(p.out + eo * 8, x);
+                fu_store8<U>(p.out, eo, x);
             }
         }
     }
@@ -612,11 +595,7 @@ __global__ __launch_bounds__(256) void ntt_build_ext_pre(const uint32_t *__restr
     const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if ((e >> log_m) >= k1) return;
     const uint64_t j = (e >> log_m) + 1, i = e & (((uint64_t)1 << log_m) - 1);
-    Fu<U> b = fu_cond_sub_p(fu_from_canonical<U>(omega_big_c)), r = Fu<U>::one();
-    for (uint64_t x = j * i; x; x >>= 1) {
-        if (x & 1) r = fu_mul(r, b);
-        b = fu_mul(b, b);
-    }
+    const Fu<U> r = fu_pow(fu_cond_sub_p(fu_from_canonical<U>(omega_big_c)), j * i);
     l_store<U>(out + (size_t)(j - 1) * ((size_t)9 << log_m), (size_t)8 << log_m, i, fu_cond_sub_p(r));
 }
 

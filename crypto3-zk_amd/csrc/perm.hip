@@ -35,29 +35,6 @@ ZK_D size_t perm_slot(size_t row) {
 }
 enum : uint32_t { C_BETA_M = 0, C_GAMMA = 1, C_ACC_NOM = 2, C_ACC_DEN = 3, C_PART1 = 4, C_SLOTS = 8 };  // the constants' slots (32 B each)
 
-template <class U>
-ZK_D Fu<U> p_load_raw(const uint32_t *p, size_t i) {  // the stored words as they are: canonical Fr, or a Montgomery value written by p_store_raw
-    const uint4 *q = reinterpret_cast<const uint4 *>(p) + 2 * i;
-    const uint4 a = q[0], b = q[1];
-    const uint32_t s[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return fu_unpack<U>(s);
-}
-template <class U>
-ZK_D void p_store_raw(uint32_t *p, size_t i, const Fu<U> &x) {  // x normalised, < 2^256: stored as it is
-    uint32_t s[8];
-    fu_pack<U>(s, x);
-    uint4 *q = reinterpret_cast<uint4 *>(p) + 2 * i;
-    q[0] = make_uint4(s[0], s[1], s[2], s[3]);
-    q[1] = make_uint4(s[4], s[5], s[6], s[7]);
-}
-template <class U>
-ZK_D Fu<U> from_mont(const Fu<U> &x) {  // Montgomery -> canonical representative
-    Fu<U> one = Fu<U>::zero();
-    one.v[0] = 1;
-    return fu_cond_sub_p(fu_mul(x, one));
-}
-template <class U>
-ZK_D Fu<U> mmul(const Fu<U> &a, const Fu<U> &b) { return fu_cond_sub_p(fu_mul(a, b)); }
 // a value < 3p (a sum of canonical terms) -> canonical
 template <class U>
 ZK_D Fu<U> reduce3(const Fu<U> &a) { return fu_cond_sub_p(fu_cond_sub_p(a)); }
@@ -87,11 +64,11 @@ ZK_UNROLL
         if (ty) oy = get(ly, t + d);
         __syncthreads();
         if (tx) {
-            x = mmul(x, ox);
+            x = fu_mulm(x, ox);
             put(lx, t, x);
         }
         if (ty) {
-            y = mmul(y, oy);
+            y = fu_mulm(y, oy);
             put(ly, t, y);
         }
         __syncthreads();
@@ -121,15 +98,15 @@ struct PermRows {
     size_t n;
     uint32_t *gv, *hv;  // the g_v / h_v vectors (canonical, k x n), or null
     ZK_D void operator()(size_t row, const uint32_t *consts, Fu<U> &nm, Fu<U> &dn) const {
-        const Fu<U> beta = p_load_raw<U>(consts, C_BETA_M), gamma = p_load_raw<U>(consts, C_GAMMA);
-        nm = p_load_raw<U>(consts, C_ACC_NOM);
-        dn = p_load_raw<U>(consts, C_ACC_DEN);
+        const Fu<U> beta = fu_load8<U>(consts, C_BETA_M), gamma = fu_load8<U>(consts, C_GAMMA);
+        nm = fu_load8<U>(consts, C_ACC_NOM);
+        dn = fu_load8<U>(consts, C_ACC_DEN);
         for (uint32_t i = 0; i < k; ++i) {
-            const Fu<U> cg = fu_add(p_load_raw<U>(cols[i], row), gamma);
-            const Fu<U> g = reduce3(fu_add(mmul(p_load_raw<U>(sid[i], row), beta), cg));
-            const Fu<U> h = reduce3(fu_add(mmul(p_load_raw<U>(ssig[i], row), beta), cg));
-            if (gv) p_store_raw<U>(gv, (size_t)i * n + row, g);
-            if (hv) p_store_raw<U>(hv, (size_t)i * n + row, h);
+            const Fu<U> cg = fu_add(fu_load8<U>(cols[i], row), gamma);
+            const Fu<U> g = reduce3(fu_add(fu_mulm(fu_load8<U>(sid[i], row), beta), cg));
+            const Fu<U> h = reduce3(fu_add(fu_mulm(fu_load8<U>(ssig[i], row), beta), cg));
+            if (gv) fu_store8<U>(gv, (size_t)i * n + row, g);
+            if (hv) fu_store8<U>(hv, (size_t)i * n + row, h);
             nm = fu_mul(nm, g);
             dn = fu_mul(dn, h);
         }
@@ -145,15 +122,15 @@ struct LookupRows {
     uint32_t k_in, k_val, k_sorted;
     size_t n;
     ZK_D void operator()(size_t row, const uint32_t *consts, Fu<U> &nm, Fu<U> &dn) const {
-        const Fu<U> beta = p_load_raw<U>(consts, C_BETA_M), gamma = p_load_raw<U>(consts, C_GAMMA), part1 = p_load_raw<U>(consts, C_PART1);
+        const Fu<U> beta = fu_load8<U>(consts, C_BETA_M), gamma = fu_load8<U>(consts, C_GAMMA), part1 = fu_load8<U>(consts, C_PART1);
         const size_t next = row + 1 == n ? 0 : row + 1;
-        nm = p_load_raw<U>(consts, C_ACC_NOM);
-        dn = p_load_raw<U>(consts, C_ACC_DEN);
-        for (uint32_t i = 0; i < k_in; ++i) nm = fu_mul(nm, fu_add(gamma, p_load_raw<U>(in[i], row)));
+        nm = fu_load8<U>(consts, C_ACC_NOM);
+        dn = fu_load8<U>(consts, C_ACC_DEN);
+        for (uint32_t i = 0; i < k_in; ++i) nm = fu_mul(nm, fu_add(gamma, fu_load8<U>(in[i], row)));
         for (uint32_t i = 0; i < k_val; ++i)
-            nm = fu_mul(nm, fu_add(fu_add(part1, p_load_raw<U>(val[i], row)), mmul(p_load_raw<U>(val[i], next), beta)));
+            nm = fu_mul(nm, fu_add(fu_add(part1, fu_load8<U>(val[i], row)), fu_mulm(fu_load8<U>(val[i], next), beta)));
         for (uint32_t i = 0; i < k_sorted; ++i)
-            dn = fu_mul(dn, fu_add(fu_add(part1, p_load_raw<U>(sorted[i], row)), mmul(p_load_raw<U>(sorted[i], next), beta)));
+            dn = fu_mul(dn, fu_add(fu_add(part1, fu_load8<U>(sorted[i], row)), fu_mulm(fu_load8<U>(sorted[i], next), beta)));
     }
 };
 
@@ -173,8 +150,8 @@ __global__ __launch_bounds__(PERM_THREADS) void gp_rows(Rows rows_of, size_t row
         atomicMin(first_zero, (uint32_t)row);
         dn = Fu<U>::one();
     }
-    p_store_raw<U>(nom, perm_slot(row), nm);
-    p_store_raw<U>(den, perm_slot(row), dn);
+    fu_store8<U>(nom, perm_slot(row), nm);
+    fu_store8<U>(den, perm_slot(row), dn);
 }
 
 // the row functor's two products as CANONICAL vectors in natural order: prod_i g_i and prod_i h_i of the permutation argument on whatever domain
@@ -187,8 +164,8 @@ __global__ __launch_bounds__(PERM_THREADS) void gp_products(Rows rows_of, size_t
     if (row >= rows) return;
     Fu<U> nm, dn;
     rows_of(row, consts, nm, dn);
-    p_store_raw<U>(out_n, row, from_mont(fu_cond_sub_p(nm)));
-    p_store_raw<U>(out_d, row, from_mont(fu_cond_sub_p(dn)));
+    fu_store8<U>(out_n, row, fu_from_mont(fu_cond_sub_p(nm)));
+    fu_store8<U>(out_d, row, fu_from_mont(fu_cond_sub_p(dn)));
 }
 
 // pass 1: every lane takes PERM_CHUNK consecutive rows (rows >= `rows` count as 1 / 1): the products of their nominators and denominators,
@@ -204,18 +181,18 @@ __global__ __launch_bounds__(PERM_THREADS) void gp_local(size_t rows, const uint
     if (lo < rows) {
         const uint32_t cnt = (uint32_t)(rows - lo < PERM_CHUNK ? rows - lo : PERM_CHUNK);
         for (uint32_t r = 0; r < cnt; ++r) {
-            ln = mmul(ln, p_load_raw<U>(nom, perm_slot(lo + r)));
-            ld = mmul(ld, p_load_raw<U>(den, perm_slot(lo + r)));
+            ln = fu_mulm(ln, fu_load8<U>(nom, perm_slot(lo + r)));
+            ld = fu_mulm(ld, fu_load8<U>(den, perm_slot(lo + r)));
         }
     }
     Fu<U> x = ln, y = ld;
     block_scan_pair<U>(lds, x, y, t);
     Fu<U> ex, ey;
     block_exclusive<U>(lds, t, ex, ey);
-    p_store_raw<U>(lane_pre, lane, ex);
-    p_store_raw<U>(lane_suf, lane, ey);
-    if (t == PERM_THREADS - 1) p_store_raw<U>(blk_nom, blockIdx.x, x);  // inclusive prefix of the last lane = the workgroup's total
-    if (t == 0) p_store_raw<U>(blk_den, blockIdx.x, y);                 // inclusive suffix of the first lane likewise
+    fu_store8<U>(lane_pre, lane, ex);
+    fu_store8<U>(lane_suf, lane, ey);
+    if (t == PERM_THREADS - 1) fu_store8<U>(blk_nom, blockIdx.x, x);  // inclusive prefix of the last lane = the workgroup's total
+    if (t == 0) fu_store8<U>(blk_den, blockIdx.x, y);                 // inclusive suffix of the first lane likewise
 }
 
 // pass 2 (one workgroup; every lane takes `per` consecutive workgroup totals): exclusive prefix products of the nominator totals, exclusive
@@ -227,8 +204,8 @@ __global__ __launch_bounds__(PERM_THREADS) void gp_top(uint32_t *__restrict__ bl
     const uint32_t t = threadIdx.x, lo = t * per;
     Fu<U> ln = Fu<U>::one(), ld = Fu<U>::one();
     for (uint32_t i = lo; i < lo + per && i < nblk; ++i) {
-        ln = mmul(ln, p_load_raw<U>(blk_nom, i));
-        ld = mmul(ld, p_load_raw<U>(blk_den, i));
+        ln = fu_mulm(ln, fu_load8<U>(blk_nom, i));
+        ld = fu_mulm(ld, fu_load8<U>(blk_den, i));
     }
     Fu<U> x = ln, y = ld;
     block_scan_pair<U>(lds, x, y, t);
@@ -237,23 +214,23 @@ __global__ __launch_bounds__(PERM_THREADS) void gp_top(uint32_t *__restrict__ bl
     // the lane's own totals: prefix forward, suffix backward
     Fu<U> run = ex;
     for (uint32_t i = lo; i < lo + per && i < nblk; ++i) {
-        const Fu<U> mine = p_load_raw<U>(blk_nom, i);
-        p_store_raw<U>(blk_nom, i, run);
-        run = mmul(run, mine);
+        const Fu<U> mine = fu_load8<U>(blk_nom, i);
+        fu_store8<U>(blk_nom, i, run);
+        run = fu_mulm(run, mine);
     }
     run = ey;
     const uint32_t hi = lo + per < nblk ? lo + per : nblk;
     for (uint32_t i = hi; i-- > lo;) {
-        const Fu<U> mine = p_load_raw<U>(blk_den, i);
-        p_store_raw<U>(blk_den, i, run);
-        run = mmul(run, mine);
+        const Fu<U> mine = fu_load8<U>(blk_den, i);
+        fu_store8<U>(blk_den, i, run);
+        run = fu_mulm(run, mine);
     }
     if (t < 64) {  // the first wave, every lane the same value: y of lane 0 is the grand total (no zero among its factors)
         Fu<U> total;
 ZK_UNROLL
         for (int l = 0; l < U::L; ++l) total.v[l] = lds[(U::L + l) * PERM_THREADS];
         const Fu<U> inv = fu_inv_gcd<U>(total);  // safegcd: ~15 k instructions on the call's critical path (Fermat: 70 k)
-        if (t == 0) p_store_raw<U>(consts, C_SLOTS - 1, inv);
+        if (t == 0) fu_store8<U>(consts, C_SLOTS - 1, inv);
     }
 }
 
@@ -270,23 +247,23 @@ __global__ __launch_bounds__(PERM_THREADS) void gp_apply(const uint32_t *__restr
     const uint32_t cnt = (uint32_t)(n - lo < PERM_CHUNK ? n - lo : PERM_CHUNK);
     const size_t z = *first_zero, last = rows < z ? rows : z;  // the last row that holds a value
     if (lo > last) {
-        for (uint32_t r = 0; r < cnt; ++r) p_store_raw<U>(vp, lo + r, Fu<U>::zero());
+        for (uint32_t r = 0; r < cnt; ++r) fu_store8<U>(vp, lo + r, Fu<U>::zero());
         return;
     }
     // suffix products of the lane's own denominators (rows >= `rows` hold none: 1)
     Fu<U> suf[PERM_CHUNK];
-    Fu<U> s = mmul(mmul(p_load_raw<U>(blk_suf, blockIdx.x), p_load_raw<U>(lane_suf, lane)), p_load_raw<U>(consts, C_SLOTS - 1));
+    Fu<U> s = fu_mulm(fu_mulm(fu_load8<U>(blk_suf, blockIdx.x), fu_load8<U>(lane_suf, lane)), fu_load8<U>(consts, C_SLOTS - 1));
     for (uint32_t r = cnt; r-- > 0;) {
-        if (lo + r < rows) s = mmul(s, p_load_raw<U>(den, perm_slot(lo + r)));
+        if (lo + r < rows) s = fu_mulm(s, fu_load8<U>(den, perm_slot(lo + r)));
         suf[r] = s;
     }
-    Fu<U> run = mmul(p_load_raw<U>(blk_pre, blockIdx.x), p_load_raw<U>(lane_pre, lane));
+    Fu<U> run = fu_mulm(fu_load8<U>(blk_pre, blockIdx.x), fu_load8<U>(lane_pre, lane));
     for (uint32_t r = 0; r < cnt; ++r) {
         if (lo + r <= last) {
-            p_store_raw<U>(vp, lo + r, from_mont(mmul(run, suf[r])));
-            if (lo + r < rows) run = mmul(run, p_load_raw<U>(nom, perm_slot(lo + r)));
+            fu_store8<U>(vp, lo + r, fu_from_mont(fu_mulm(run, suf[r])));
+            if (lo + r < rows) run = fu_mulm(run, fu_load8<U>(nom, perm_slot(lo + r)));
         } else {
-            p_store_raw<U>(vp, lo + r, Fu<U>::zero());
+            fu_store8<U>(vp, lo + r, Fu<U>::zero());
         }
     }
 }
@@ -297,20 +274,20 @@ template <class U>
 __global__ void gp_setup(const uint32_t *__restrict__ in, uint32_t *__restrict__ out, uint32_t f_nom, uint32_t f_den, uint32_t pow_opb, uint32_t *__restrict__ first_zero) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     *first_zero = 0xffffffffu;
-    const Fu<U> beta = mmul(p_load_raw<U>(in, 0), Fu<U>::r2()), gamma_m = mmul(p_load_raw<U>(in, 1), Fu<U>::r2());
-    const Fu<U> opb = fu_cond_sub_p(fu_add(Fu<U>::one(), beta));
+    const Fu<U> beta = fu_mulm(fu_load8<U>(in, 0), Fu<U>::r2()), gamma_m = fu_mulm(fu_load8<U>(in, 1), Fu<U>::r2());
+    const Fu<U> opb = fu_addm(Fu<U>::one(), beta);
     auto r_pow = [](uint32_t m) {  // R^(m + 1): the Montgomery one times R, m times
         Fu<U> t = Fu<U>::one();
-        for (uint32_t i = 0; i < m; ++i) t = mmul(t, Fu<U>::r2());
+        for (uint32_t i = 0; i < m; ++i) t = fu_mulm(t, Fu<U>::r2());
         return t;
     };
     Fu<U> an = r_pow(f_nom);
-    for (uint32_t i = 0; i < pow_opb; ++i) an = mmul(an, opb);
-    p_store_raw<U>(out, C_BETA_M, beta);
-    p_store_raw<U>(out, C_GAMMA, p_load_raw<U>(in, 1));
-    p_store_raw<U>(out, C_ACC_NOM, an);
-    p_store_raw<U>(out, C_ACC_DEN, r_pow(f_den));
-    p_store_raw<U>(out, C_PART1, from_mont(mmul(opb, gamma_m)));
+    for (uint32_t i = 0; i < pow_opb; ++i) an = fu_mulm(an, opb);
+    fu_store8<U>(out, C_BETA_M, beta);
+    fu_store8<U>(out, C_GAMMA, fu_load8<U>(in, 1));
+    fu_store8<U>(out, C_ACC_NOM, an);
+    fu_store8<U>(out, C_ACC_DEN, r_pow(f_den));
+    fu_store8<U>(out, C_PART1, fu_from_mont(fu_mulm(opb, gamma_m)));
 }
 
 struct RowsHead {  // what a row functor reads: its device pointer table and the constants of gp_setup
@@ -429,20 +406,20 @@ __global__ __launch_bounds__(PERM_THREADS) void md_local(const uint32_t *__restr
     if (lo < count) {
         const uint32_t cnt = (uint32_t)(count - lo < PERM_CHUNK ? count - lo : PERM_CHUNK);
         for (uint32_t r = 0; r < cnt; ++r) {
-            Fu<U> x = mmul(p_load_raw<U>(c, lo + r), Fu<U>::r2());
+            Fu<U> x = fu_mulm(fu_load8<U>(c, lo + r), Fu<U>::r2());
             if (x.limbs_zero()) x = Fu<U>::zero();  // marked: md_apply writes 0 for the row and skips it in the products
-            p_store_raw<U>(cm, lo + r, x);
-            if (!x.limbs_zero()) l = mmul(l, x);
+            fu_store8<U>(cm, lo + r, x);
+            if (!x.limbs_zero()) l = fu_mulm(l, x);
         }
     }
     Fu<U> x = l, y = l;
     block_scan_pair<U>(lds, x, y, t);
     Fu<U> ex, ey;
     block_exclusive<U>(lds, t, ex, ey);
-    p_store_raw<U>(lane_pre, lane, ex);
-    p_store_raw<U>(lane_suf, lane, ey);
-    if (t == PERM_THREADS - 1) p_store_raw<U>(blk_pre, blockIdx.x, x);
-    if (t == 0) p_store_raw<U>(blk_suf, blockIdx.x, y);
+    fu_store8<U>(lane_pre, lane, ex);
+    fu_store8<U>(lane_suf, lane, ey);
+    if (t == PERM_THREADS - 1) fu_store8<U>(blk_pre, blockIdx.x, x);
+    if (t == 0) fu_store8<U>(blk_suf, blockIdx.x, y);
 }
 template <class U>
 __global__ __launch_bounds__(PERM_THREADS) void md_apply(const uint32_t *a, const uint32_t *b, const uint32_t *__restrict__ cm, const uint32_t *__restrict__ lane_pre,
@@ -454,22 +431,22 @@ __global__ __launch_bounds__(PERM_THREADS) void md_apply(const uint32_t *a, cons
     // suf[r] = product of the lane's c behind row r, times everything behind the lane, times 1 / total, times R (so that the last product below
     // leaves the canonical value: a b are multiplied in as they are)
     Fu<U> suf[PERM_CHUNK], cs[PERM_CHUNK];
-    Fu<U> s = mmul(mmul(mmul(p_load_raw<U>(blk_suf, blockIdx.x), p_load_raw<U>(lane_suf, lane)), p_load_raw<U>(consts, C_SLOTS - 1)), Fu<U>::r2());
+    Fu<U> s = fu_mulm(fu_mulm(fu_mulm(fu_load8<U>(blk_suf, blockIdx.x), fu_load8<U>(lane_suf, lane)), fu_load8<U>(consts, C_SLOTS - 1)), Fu<U>::r2());
     for (uint32_t r = cnt; r-- > 0;) {
-        cs[r] = p_load_raw<U>(cm, lo + r);
+        cs[r] = fu_load8<U>(cm, lo + r);
         suf[r] = s;
-        if (!cs[r].limbs_zero()) s = mmul(s, cs[r]);
+        if (!cs[r].limbs_zero()) s = fu_mulm(s, cs[r]);
     }
-    Fu<U> run = mmul(p_load_raw<U>(blk_pre, blockIdx.x), p_load_raw<U>(lane_pre, lane));
+    Fu<U> run = fu_mulm(fu_load8<U>(blk_pre, blockIdx.x), fu_load8<U>(lane_pre, lane));
     for (uint32_t r = 0; r < cnt; ++r) {
         if (cs[r].limbs_zero()) {
-            p_store_raw<U>(out, lo + r, Fu<U>::zero());
+            fu_store8<U>(out, lo + r, Fu<U>::zero());
             continue;
         }
         // a b / R (canonical operands) -> times prefix (Montgomery) -> a b prefix / R -> times suf (Montgomery value times R^2) -> canonical a b / c
-        const Fu<U> ab = fu_mul(p_load_raw<U>(a, lo + r), p_load_raw<U>(b, lo + r));
-        p_store_raw<U>(out, lo + r, mmul(fu_mul(ab, run), suf[r]));
-        run = mmul(run, cs[r]);
+        const Fu<U> ab = fu_mul(fu_load8<U>(a, lo + r), fu_load8<U>(b, lo + r));
+        fu_store8<U>(out, lo + r, fu_mulm(fu_mul(ab, run), suf[r]));
+        run = fu_mulm(run, cs[r]);
     }
 }
 

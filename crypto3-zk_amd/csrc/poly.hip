@@ -74,11 +74,11 @@ __global__ void fri_fold_setup(const uint32_t *__restrict__ alpha_c, const uint3
     const Fu<U> w = fu_cond_sub_p(fu_from_canonical<U>(omega_c));
     Fu<U> winv = Fu<U>::one(), sq = w;
     for (uint32_t k = 0; k < log_size; ++k) {
-        winv = fu_cond_sub_p(fu_mul(winv, sq));
-        sq = fu_cond_sub_p(fu_mul(sq, sq));
+        winv = fu_mulm(winv, sq);
+        sq = fu_mulm(sq, sq);
     }
     const Fu<U> one = fu_cond_sub_p(Fu<U>::one());
-    const Fu<U> check = fu_cond_sub_p(fu_mul(winv, w));
+    const Fu<U> check = fu_mulm(winv, w);
     bool ok = true;
 #pragma unroll
     for (int l = 0; l < U::L; ++l) ok = ok && check.v[l] == one.v[l];
@@ -104,11 +104,7 @@ __global__ __launch_bounds__(256) void fri_fold(const uint32_t *__restrict__ f, 
     if (i0 >= half) return;
     const Fu<U> winv = fu_load<U>(consts + U::SL), half_inv = fu_load<U>(consts + 2 * U::SL);
     const Fu<U> one = fu_cond_sub_p(Fu<U>::one());
-    Fu<U> acc = fu_load<U>(consts), pw = winv;  // acc = alpha w^-i0
-    for (uint32_t e = i0; e; e >>= 1) {
-        if (e & 1) acc = fu_mul(acc, pw);
-        pw = fu_mul(pw, pw);
-    }
+    Fu<U> acc = fu_pow_onto(fu_load<U>(consts), winv, i0);  // alpha w^-i0
     const uint32_t hi = min(half, i0 + FOLD_CHUNK);
     for (uint32_t i = i0; i < hi; ++i) {
         acc = fu_cond_sub_p(acc);                                  // alpha w^-i, Montgomery, canonical
@@ -133,9 +129,9 @@ __global__ __launch_bounds__(256) void fr_vec_op(const uint32_t *__restrict__ a,
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     Fu<U> x = fu_unpack<U>(a + i * U::NL), y = fu_unpack<U>(b + i * U::NL), r;
-    if (op == 0) r = fu_cond_sub_p(fu_add(x, y));
+    if (op == 0) r = fu_addm(x, y);
     else if (op == 1) r = fu_cond_sub_p(fu_cond_sub_p(fu_sub<2>(x, y)));  // x + 2p - y in (p, 3p)
-    else r = fu_cond_sub_p(fu_mul(fu_mul(x, y), Fu<U>::r2()));  // (x y / R) R^2 / R
+    else r = fu_mulm(fu_mul(x, y), Fu<U>::r2());  // (x y / R) R^2 / R
     fu_pack<U>(out + i * U::NL, r);
 }
 
@@ -150,10 +146,10 @@ __global__ __launch_bounds__(256) void fr_vec_affine(const uint32_t *__restrict_
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     const Fu<U> am = fu_mul(fu_unpack<U>(a.w), Fu<U>::r2());  // a R: (a R) x / R = a x
-    Fu<U> r = fu_cond_sub_p(fu_add(fu_cond_sub_p(fu_mul(am, fu_unpack<U>(x + i * U::NL))), fu_unpack<U>(c.w)));
+    Fu<U> r = fu_addm(fu_mulm(am, fu_unpack<U>(x + i * U::NL)), fu_unpack<U>(c.w));
     if (y) {
         const Fu<U> bm = fu_mul(fu_unpack<U>(b.w), Fu<U>::r2());
-        r = fu_cond_sub_p(fu_add(r, fu_cond_sub_p(fu_mul(bm, fu_unpack<U>(y + i * U::NL)))));
+        r = fu_addm(r, fu_mulm(bm, fu_unpack<U>(y + i * U::NL)));
     }
     fu_pack<U>(out + i * U::NL, r);
 }
@@ -168,9 +164,7 @@ __global__ __launch_bounds__(256) void fr_vec_prod(const uint32_t *const *__rest
     // (x_k R^2 / R = x_k R) and multiplied in ((acc R)(x_k R) / R = acc x_k R); one last product by the plain 1 drops the R.
     Fu<U> acc = fu_mul(fu_unpack<U>(ptrs[0] + i * U::NL), Fu<U>::r2());
     for (uint32_t k = 1; k < count; ++k) acc = fu_mul(acc, fu_mul(fu_unpack<U>(ptrs[k] + i * U::NL), Fu<U>::r2()));
-    Fu<U> one = Fu<U>::zero();
-    one.v[0] = 1;
-    fu_pack<U>(out + i * U::NL, fu_cond_sub_p(fu_mul(acc, one)));
+    fu_pack<U>(out + i * U::NL, fu_from_mont(acc));
 }
 
 // f / (X^n - 1) in coefficient form: the quotient of placeholder's `F_consolidated_normal / common_data.Z` (prover.hpp:273-275; Z is the
@@ -185,10 +179,10 @@ __global__ __launch_bounds__(256) void poly_div_vanishing(const uint32_t *__rest
     const size_t top = (len - 1 - i) / n;  // f[i + top n] is the column's last coefficient
     Fu<U> s = Fu<U>::zero();
     for (size_t k = top; k >= 1; --k) {
-        s = fu_cond_sub_p(fu_add(s, fu_unpack<U>(f + (i + k * n) * U::NL)));
+        s = fu_addm(s, fu_unpack<U>(f + (i + k * n) * U::NL));
         fu_pack<U>(quot + (i + (k - 1) * n) * U::NL, s);
     }
-    const Fu<U> r = fu_cond_sub_p(fu_add(s, fu_unpack<U>(f + i * U::NL)));
+    const Fu<U> r = fu_addm(s, fu_unpack<U>(f + i * U::NL));
     if (!r.limbs_zero()) atomicAdd(bad, 1u);
 }
 
@@ -211,14 +205,6 @@ __global__ __launch_bounds__(256) void poly_subsample(const uint4 *__restrict__ 
     const size_t s = (b << log_n) + (i << (log_n - log_out));
     out[2 * e] = in[2 * s];
     out[2 * e + 1] = in[2 * s + 1];
-}
-
-// canonical -> Montgomery (canonical representative) for a short table of constants
-template <class U>
-__global__ void fr_table_to_mont(const uint32_t *__restrict__ canon, uint32_t count, uint32_t *__restrict__ mont) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    fu_store<U>(mont + (size_t)i * U::SL, fu_cond_sub_p(fu_from_canonical<U>(canon + (size_t)i * U::NL)));
 }
 
 // Horner machinery shared by evaluation and division by (X - z).  A lane owns HORNER_CHUNK consecutive
@@ -266,7 +252,7 @@ ZK_D Fu<U> horner_block_scan(uint32_t *lds, Fu<U> v, uint32_t t, const uint32_t 
         if (has) add = fu_mul(fu_load<U>(lds + (size_t)(t + d) * U::SL), fu_load<U>(zp + (size_t)k * U::SL));
         __syncthreads();
         if (has) {
-            v = fu_cond_sub_p(fu_mul(fu_add(v, add), Fu<U>::one()));  // back under p: the next level adds again
+            v = fu_mulm(fu_add(v, add), Fu<U>::one());  // back under p: the next level adds again
             fu_store<U>(lds + (size_t)t * U::SL, v);
         }
         __syncthreads();
@@ -283,7 +269,7 @@ __global__ __launch_bounds__(256) void poly_block_horner(const uint32_t *__restr
     const uint32_t *f = polys + (size_t)poly * stride * U::NL;
     const uint32_t *zp = zpow + (size_t)p * 10 * U::SL;
     Fu<U> s = horner_chunk<U>(f, n, (size_t)b * HORNER_BLOCK + (size_t)t * HORNER_CHUNK, fu_load<U>(zp + 9 * U::SL));
-    Fu<U> v = horner_block_scan<U>(lds, fu_cond_sub_p(fu_mul(s, Fu<U>::one())), t, zp);
+    Fu<U> v = horner_block_scan<U>(lds, fu_mulm(s, Fu<U>::one()), t, zp);
     if (t == 0) fu_store<U>(part + (((size_t)poly * npoints + p) * nblk + b) * U::SL, v);
 }
 
@@ -298,7 +284,7 @@ __global__ void poly_block_carry(const uint32_t *__restrict__ part, uint32_t nbl
     Fu<U> acc = Fu<U>::zero();
     for (int b = (int)nblk - 1; b >= 0; --b) {
         if (carry) fu_store<U>(carry + ((size_t)g * nblk + b) * U::SL, acc);
-        acc = fu_cond_sub_p(fu_mul(fu_add(fu_mul(acc, zb), fu_load<U>(part + ((size_t)g * nblk + b) * U::SL)), Fu<U>::one()));
+        acc = fu_mulm(fu_add(fu_mul(acc, zb), fu_load<U>(part + ((size_t)g * nblk + b) * U::SL)), Fu<U>::one());
     }
     fu_pack<U>(values + (size_t)g * U::NL, acc);
 }
@@ -312,7 +298,7 @@ __global__ __launch_bounds__(256) void poly_div_finish(const uint32_t *f, size_t
     const size_t start = (size_t)b * HORNER_BLOCK + (size_t)t * HORNER_CHUNK;
     const Fu<U> z = fu_load<U>(zpow + 9 * U::SL);
     Fu<U> s = horner_chunk<U>(f, n, start, z);
-    horner_block_scan<U>(lds, fu_cond_sub_p(fu_mul(s, Fu<U>::one())), t, zpow);
+    horner_block_scan<U>(lds, fu_mulm(s, Fu<U>::one()), t, zpow);
     // G at the end of this lane's chunk: V_{t+1} + z^(C (255 - t)) * carry-in of the workgroup
     Fu<U> cin = fu_load<U>(carry + (size_t)b * U::SL);
     Fu<U> pw = fu_cond_sub_p(Fu<U>::one());
@@ -323,7 +309,7 @@ __global__ __launch_bounds__(256) void poly_div_finish(const uint32_t *f, size_t
     for (int j = HORNER_CHUNK - 1; j >= 0; --j) {
         size_t e = start + j;
         if (e >= n) continue;  // beyond the top coefficient: G = 0 there, g is still 0
-        g = fu_cond_sub_p(fu_mul(fu_add(fu_mul(g, z), fu_unpack<U>(f + e * U::NL)), Fu<U>::one()));
+        g = fu_mulm(fu_add(fu_mul(g, z), fu_unpack<U>(f + e * U::NL)), Fu<U>::one());
         fu_pack<U>(out + e * U::NL, g);
     }
 }
@@ -350,7 +336,7 @@ __global__ __launch_bounds__(256) void poly_lincomb(const uint32_t *const *__res
             }
         }
     }
-    fu_pack<U>(acc_out + j * U::NL, fu_cond_sub_p(fu_mul(acc, Fu<U>::one())));
+    fu_pack<U>(acc_out + j * U::NL, fu_mulm(acc, Fu<U>::one()));
 }
 
 

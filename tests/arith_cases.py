@@ -15,6 +15,10 @@ MASK = (1 << B) - 1
 # lazy 29-bit-limb types (hosttest.hip / arith_ops.h ids): modulus, limbs L, saturated words NL, largest spread K of field_consts.hpp
 TYPES = {6: (po.BLS12_381.p, 14, 12, 128), 7: (po.BN254.p, 10, 8, 128), 8: (po.BLS12_381.r, 9, 8, 64), 9: (po.BN254.r, 9, 8, 128)}
 OP_MUL, OP_SQR, OP_MUL2, OP_ADD, OP_COND_SUB, OP_CANON, OP_IS_ZERO, OP_INV, OP_INV_GCD, OP_PACK, OP_UNPACK = range(11)
+# the element layer of the scalar-field kernels (fu.hpp: fu_mulm .. fu_load8); OP_IO8 and OP_POW_WIDE exist for the 8-word types only
+OP_MULM, OP_ADDM, OP_FROM_MONT, OP_POW, OP_POW_ONTO, OP_IO8, OP_POW_WIDE = range(30, 37)
+# exponents of the 64-bit powers: 0 .. 3, 2^k and 2^k - 1 around the word boundary and at the top bit, all ones
+POW_EXPONENTS = [0, 1, 2, 3] + [x for k in (31, 32, 33, 63) for x in (1 << k, (1 << k) - 1)] + [(1 << 64) - 1]
 
 
 def op_sub(k):
@@ -253,6 +257,42 @@ def inv_cases(t, rng):
     return out
 
 
+def addm_cases(t, rng):
+    """fu_addm: normalised operands, a + b < 2p -- the canonical edges against each other and add_cases' pairs that stay below 2p"""
+    p, L = TYPES[t][0], TYPES[t][1]
+    edges = canonical_edges(t)
+    out = [(split(x, L), split(y, L)) for x in edges for y in (0, 1, p - 1, p - x if x else 0, edges[-1])]
+    out += [(a, b) for a, b in add_cases(t, rng) if value(a) + value(b) < 2 * p]
+    out += [(split(2 * p - 1, L), split(0, L)), (split(p, L), split(p - 1, L))]
+    assert all(normalised(a) and normalised(b) and value(a) + value(b) < 2 * p for a, b in out)
+    return out
+
+
+def pow_cases(t, rng):
+    """fu_pow_onto(seed, base, e) -- fu_pow is the seed R mod p: the products' operand contract along the whole chain, base base < R p,
+    seed base < R p and seed < R / 2 (a later power of the base is < 2p).  (seed, base) from mul_cases' pairs at the product's bounds
+    and the canonical edges; every pair meets every exponent of POW_EXPONENTS once over the list"""
+    p, L = TYPES[t][0], TYPES[t][1]
+    R = 1 << (B * L)
+    pairs = [(b, a) for a, b in mul_cases(t, rng) if value(a) ** 2 < rp(t) and value(b) < R // 2]
+    edges = canonical_edges(t)
+    pairs += [(split(edges[(3 * i + 1) % len(edges)], L), split(x, L)) for i, x in enumerate(edges)]
+    out = []
+    for i, (seed, base) in enumerate(pairs):
+        mul_ok(t, base, base)
+        mul_ok(t, seed, base)
+        assert value(seed) < R // 2
+        for j in range(3):  # three exponents per pair, walking the list
+            out.append((seed, base, POW_EXPONENTS[(3 * i + j) % len(POW_EXPONENTS)]))
+    return out
+
+
+def exp_words(e, L):
+    """an exponent as saturated u32 words in an L-word operand slot"""
+    assert e < 1 << 256
+    return [(e >> (32 * i)) & 0xFFFFFFFF for i in range(8)] + [0] * (L - 8)
+
+
 def scalar_edges(r, c, rng):
     """0, 1, (r - 1)/2, (r + 1)/2 (the fold boundary), r - 1, r, r + 1, 2^256 - 1, every window at 2^(c-1) for c-bit windows
     (uniform and the balanced cuts), random"""
@@ -307,7 +347,7 @@ def check_raw(t, op, a, b, c, d, r, k=None):
     elif op == OP_ADD:
         if not (got == va + value(b) and normalised(r)):
             return "exact sum"
-    elif op >= 21:
+    elif 21 <= op <= 27:
         if not (got == va + k * p - value(b) and normalised(r)):
             return "exact a + Kp - b"
     elif op == OP_COND_SUB:
@@ -332,6 +372,27 @@ def check_raw(t, op, a, b, c, d, r, k=None):
         x = sum(int(w) << (32 * i) for i, w in enumerate(a[:NL]))
         if r != split(x, L):
             return "unpack"
+    elif op == OP_MULM:
+        if not (got == va * value(b) * Ri % p and normalised(r)):
+            return "canonical product"
+    elif op == OP_ADDM:
+        if not (got == (va + value(b)) % p and normalised(r)):
+            return "canonical sum"
+    elif op == OP_FROM_MONT:
+        if not (got == va * Ri % p and normalised(r)):
+            return "out of Montgomery form"
+    elif op in (OP_POW, OP_POW_ONTO, OP_POW_WIDE):
+        e = sum(int(w) << (32 * i) for i, w in enumerate(b[:8 if op == OP_POW_WIDE else 2]))
+        seed = c if op == OP_POW_ONTO else split(R % p, L)
+        if got % p != value(seed) * pow(va * Ri % p, e, p) % p:
+            return "power residue"
+        if e == 0 and list(r) != list(seed):
+            return "power: e = 0 leaves the seed as it is"
+        if e and not (normalised(r) and got < 2 * p):
+            return "postcondition: normalised, < 2p"
+    elif op == OP_IO8:
+        if list(r) != list(a):
+            return "16-byte store / load round trip"
     return None
 
 
@@ -353,4 +414,15 @@ def raw_suite(t, seed=0):
              (OP_UNPACK, None, [(sat_words(value(a), L, NL), z, z, z) for a in pack_cases(t, rng)])]
     for k in spreads(t):
         suite.append((op_sub(k), k, [(a, b, z, z) for a, b in sub_cases(t, k, rng)]))
+    powers = pow_cases(t, rng)
+    suite += [(OP_MULM, None, [(a, b, z, z) for a, b in mul_cases(t, rng)]),
+              (OP_ADDM, None, [(a, b, z, z) for a, b in addm_cases(t, rng)]),
+              (OP_FROM_MONT, None, [(a, z, z, z) for a in canon_cases(t, rng)]),
+              (OP_POW, None, [(base, exp_words(e, L), z, z) for _, base, e in powers]),
+              (OP_POW_ONTO, None, [(base, exp_words(e, L), seed, z) for seed, base, e in powers])]
+    if NL == 8:
+        p = TYPES[t][0]
+        wide = [p - 1, 0, 1, 1 << 64, (1 << 64) + 1, (1 << 256) - 1]
+        suite += [(OP_IO8, None, [(a, z, z, z) for a in pack_cases(t, rng)]),
+                  (OP_POW_WIDE, None, [(split(x, L), exp_words(e, L), z, z) for e in wide for x in canonical_edges(t)[:12 if e == p - 1 else 3]])]
     return suite
