@@ -238,7 +238,7 @@ struct zkhip_ctx {
     int opt_msm_sort_tile_log = 14;  // 14: 2^14-entry sort tiles (the MSM owns the GPU); 12: 2^12 (kernels of another context run alongside)
     int opt_ec_ntt_table_lanes = 0;  // EC-NTT: lanes per multiplication launch = window tables held at once (0: as many as fit 1 GiB)
     int opt_msm_share_sort = 1;    // batches: consecutive members over the same scalars and table geometry share one sort (msm_same_entries)
-    int opt_msm_tail_quads = 1;    // group law over lane quads in the tail of small bucket sets (fu_quad.hpp); 0: pairs everywhere
+    int opt_msm_tail_quads = 1;    // the tail's latency-bound group law.  0: lane pairs everywhere; 1: lane quads in the tail of small bucket sets (fu_quad.hpp) and one point per wave in level 2 of a lone MSM's two-level tail (fu_wide.hpp); any other value: the quads alone
     int opt_msm_tail_fold = 16;    // two-level tail (msm_core.hpp: row / column sums of the bucket index, then the old tail over 2 sets of ~sqrt(B) buckets) for table-backed sets of >= 2^k buckets; 0: off
     int opt_msm_tail_fold_g2 = 1;  // the two-level tail for G2 sets too (same threshold): a lone G2 MSM measures the same either way, a proof whose G2 MSM runs under its G1 MSMs gains the issue slots the shorter tail frees (Groth16 +2.6 %)
     int opt_msm_fold_run = 0;      // two-level tail: buckets a lane sums before the workgroup's tree (a power of two; 0: auto)

@@ -44,6 +44,7 @@
 //   msm_final         (Horner over the windows when there are no tables,) XYZZ -> Jacobian, Montgomery -> canonical
 //   msm_final_fold    the same after msm_fold: COL sum + 2^log2(C) ROW sum
 //   msm_final_batch   the same for every member of a batch
+//   msm_wide_weigh / msm_wide_tree / msm_wide_final   level 2 after msm_fold for G1, one point per wave (fu_wide.hpp), in place of the four above
 // (msm_final, msm_final_fold and msm_write_infinity store through xyzz_store_canonical_jacobian.  msm_final_batch and jac_sum_k keep the three
 // stores spelled out, msm_bucket_large its own copy of block_tree_sum's loop, and the three batch inversions their back-substitution step: with
 // the shared helper those kernels compiled to other register / scratch counts.)
@@ -65,6 +66,7 @@
 #include "msm_bucket_acc.hpp"
 #include "fu_pair.hpp"
 #include "fu_quad.hpp"
+#include "fu_wide.hpp"
 
 namespace {
 
@@ -725,6 +727,74 @@ __global__ __launch_bounds__(64) void msm_final_fold(const uint32_t *__restrict_
     xyzz_store_canonical_jacobian<F>(outs ? outs[blockIdx.x] : out, acc);
 }
 
+// ---- level 2 of the two-level tail with one point per wave (fu_wide.hpp) ---------------------------------------------------------------
+// The same sums in the same shape -- every point times its digit value, a binary tree over each set, log2(C) doublings of the second set's sum,
+// one addition, the canonical store -- but an operation is ~2.4 us of a wave instead of the quad's ~6.8, and the launches are cut so that a SIMD
+// holds at most two waves while the chain runs.  Workgroups of MSM_WIDE_WAVES waves, a point per wave, LDS trees between them:
+//   msm_wide_weigh   point b of a set times (b + 1), then the tree over the workgroup's MSM_WIDE_WAVES points   C / MSM_WIDE_WAVES partials per set
+//   msm_wide_tree    2 MSM_WIDE_WAVES consecutive partials to one (launched while a set has more than MSM_WIDE_WAVES partials)
+//   msm_wide_final   one workgroup per MSM, half its waves per set: the last tree levels, the doublings, the addition, the canonical store
+constexpr uint32_t MSM_WIDE_WAVES = 8;  // 512 lanes: two waves per SIMD while every wave of a workgroup works, one from the first tree level on
+
+// tree over the nw (power of two) waves of a group that starts at LDS slot 0 of `lds`; wave 0 of the group returns the sum
+template <class U>
+ZK_D XYZZ<FuW<U>> wide_tree_sum(uint32_t *lds, XYZZ<FuW<U>> acc, uint32_t w, uint32_t nw) {
+    constexpr uint32_t PW = 4 * U::SL;
+    wide_store<U>(lds + w * PW, acc);
+    __syncthreads();
+    for (uint32_t d = nw / 2; d >= 1; d >>= 1) {
+        if (w < d) {
+            acc = xyzz_add(wide_load<U>(lds + w * PW), wide_load<U>(lds + (w + d) * PW));
+            wide_store<U>(lds + w * PW, acc);
+        }
+        __syncthreads();
+    }
+    return acc;
+}
+
+// grid = points / MSM_WIDE_WAVES; point s C + b is bucket b of set s (C a power of two and a multiple of MSM_WIDE_WAVES: a workgroup stays inside a set)
+template <class U>
+__global__ __launch_bounds__(MSM_WIDE_WAVES * 64) void msm_wide_weigh(const uint32_t *__restrict__ points, uint32_t C, uint32_t *__restrict__ partial) {
+    constexpr uint32_t PW = 4 * U::SL;
+    __shared__ uint32_t lds[MSM_WIDE_WAVES * PW];
+    const uint32_t w = threadIdx.x >> 6, i = blockIdx.x * MSM_WIDE_WAVES + w;
+    XYZZ<FuW<U>> acc = xyzz_mul_small(wide_load<U>(points + (size_t)i * PW), (i & (C - 1)) + 1);
+    acc = wide_tree_sum<U>(lds, acc, w, MSM_WIDE_WAVES);
+    if (w == 0) wide_store<U>(partial + (size_t)blockIdx.x * PW, acc);
+}
+
+// grid = points / (2 MSM_WIDE_WAVES): out[j] = in[2 W j] + ... + in[2 W j + 2 W - 1], W = MSM_WIDE_WAVES
+template <class U>
+__global__ __launch_bounds__(MSM_WIDE_WAVES * 64) void msm_wide_tree(const uint32_t *__restrict__ in, uint32_t *__restrict__ out) {
+    constexpr uint32_t PW = 4 * U::SL;
+    __shared__ uint32_t lds[MSM_WIDE_WAVES * PW];
+    const uint32_t w = threadIdx.x >> 6;
+    const uint32_t *src = in + ((size_t)blockIdx.x * 2 * MSM_WIDE_WAVES + w) * PW;
+    XYZZ<FuW<U>> acc = xyzz_add(wide_load<U>(src), wide_load<U>(src + (size_t)MSM_WIDE_WAVES * PW));
+    acc = wide_tree_sum<U>(lds, acc, w, MSM_WIDE_WAVES);
+    if (w == 0) wide_store<U>(out + (size_t)blockIdx.x * PW, acc);
+}
+
+// grid = MSMs; partial[(2 i + k) m + j], j < m (a power of two): out[i] = sum_j partial[2 i][j] + 2^shift sum_j partial[2 i + 1][j] as canonical Jacobian;
+// outs == nullptr: the single output `out`.  The first half of the waves takes the second set (whose sum the doublings wait for).
+template <class U>
+__global__ __launch_bounds__(MSM_WIDE_WAVES * 64) void msm_wide_final(const uint32_t *__restrict__ partial, uint32_t m, uint32_t shift, uint32_t *const *__restrict__ outs,
+                                                                      uint32_t *__restrict__ out) {
+    constexpr uint32_t PW = 4 * U::SL, HALF = MSM_WIDE_WAVES / 2;
+    __shared__ uint32_t lds[MSM_WIDE_WAVES * PW];
+    const uint32_t w = threadIdx.x >> 6, half = w / HALF, q = w % HALF;
+    const uint32_t *src = partial + ((size_t)2 * blockIdx.x + (1 - half)) * m * PW;
+    XYZZ<FuW<U>> acc = XYZZ<FuW<U>>::infinity();
+    for (uint32_t j = q; j < m; j += HALF) acc = xyzz_add(acc, wide_load<U>(src + (size_t)j * PW));
+    acc = wide_tree_sum<U>(lds + half * HALF * PW, acc, q, HALF);
+    if (w != 0) return;
+    if (!acc.is_inf())
+        for (uint32_t i = 0; i < shift; ++i) acc = xyzz_dbl(acc);
+    acc = xyzz_add(acc, wide_load<U>(lds + HALF * PW));
+    const XYZZ<FuQ<U>> whole = wide_gather<U>(acc);
+    if (wide_lane() < 4) xyzz_store_canonical_jacobian<FuQ<U>>(outs ? outs[blockIdx.x] : out, whole);  // one quad: the conversion is the quad tail's
+}
+
 // result = sum_w 2^off(w) winsum[w]  (Horner from the top window; a single set with tables), emitted as canonical Jacobian
 template <class F, int LPB>
 __global__ __launch_bounds__(64) void msm_final(const uint32_t *__restrict__ winsum, int W, MsmWindows win, uint32_t *__restrict__ out_jac) {
@@ -1045,7 +1115,8 @@ struct MsmFoldBuffers {
     MsmFoldBuffers() = default;
     MsmFoldBuffers(const zkhip_ctx *ctx, uint32_t B, size_t nsets_) : g(msm_fold_geom(ctx, B)), nsets(nsets_) {}
     size_t level2_words() const { return nsets * 2 * g.C * PW; }
-    size_t segsum_blocks() const { return nsets * 2 * ((g.C + 63) / 64); }  // segments of >= 1 bucket, >= 64 of them per workgroup
+    // segments of >= 1 bucket, >= 64 of them per workgroup; the wide tail (lone MSM): a partial per MSM_WIDE_WAVES points
+    size_t segsum_blocks() const { return nsets * 2 * std::max<size_t>((g.C + 63) / 64, WideLane<F>::AVAILABLE && nsets == 1 ? g.C / MSM_WIDE_WAVES : 0); }
     template <class Arena>
     void layout(Arena &a) {
         a.take(level2, level2_words());
@@ -1053,6 +1124,40 @@ struct MsmFoldBuffers {
         a.take(winsum, nsets * 2 * PW);
     }
 };
+
+// Level 2 on the wide lane: level2[2 nsets][C] -> nsets canonical Jacobian results.  The partial sums alternate between segsum and level2 (whose
+// points msm_wide_weigh has read by then).  Applies to the LONE MSM (2 C waves: two per SIMD at C = 2^10) where a set holds at least a workgroup's
+// points.  A batch keeps the quads / pairs: its level 2 has waves enough to fill the chip, and there an operation's issue slots count, not its latency.
+template <class F>
+bool msm_tail_wide_applies(const zkhip_ctx *ctx, size_t nsets, uint32_t C) {
+    return WideLane<F>::AVAILABLE && ctx->opt_msm_tail_quads == 1 && nsets == 1 && C >= MSM_WIDE_WAVES;
+}
+template <class F>
+int msm_tail_wide(zkhip_ctx *ctx, const MsmFoldBuffers<F> &fb, uint32_t *const *d_outs, uint32_t *d_out) {
+    if constexpr (WideLane<F>::AVAILABLE) {
+        typedef typename F::params U;
+        const uint32_t C = fb.g.C;
+        const size_t sets = 2 * fb.nsets;
+        uint32_t m = C / MSM_WIDE_WAVES;  // partials per set
+        if (sets * m > fb.segsum_blocks()) {
+            ctx->last_error = "wide MSM tail of " + std::to_string(sets * m) + " workgroups over a partial-sum buffer for " + std::to_string(fb.segsum_blocks());
+            return ZKHIP_ERR_RANGE;
+        }
+        uint32_t *from = fb.segsum, *to = fb.level2;
+        ZK_LAUNCH(ctx, "msm_wide_weigh", (msm_wide_weigh<U>), dim3((unsigned)(sets * m)), dim3(MSM_WIDE_WAVES * 64), 0, fb.level2, C, from);
+        while (m > MSM_WIDE_WAVES) {
+            m /= 2 * MSM_WIDE_WAVES;
+            ZK_LAUNCH(ctx, "msm_wide_tree", (msm_wide_tree<U>), dim3((unsigned)(sets * m)), dim3(MSM_WIDE_WAVES * 64), 0, from, to);
+            std::swap(from, to);
+        }
+        ZK_LAUNCH(ctx, "msm_wide_final", (msm_wide_final<U>), dim3((unsigned)fb.nsets), dim3(MSM_WIDE_WAVES * 64), 0, from, m, fb.g.log_c, d_outs, d_out);
+        return 0;
+    } else {
+        (void)fb, (void)d_outs, (void)d_out;
+        ctx->last_error = "no wide lane for this field";
+        return ZKHIP_ERR_INVALID;
+    }
+}
 
 // sets[nsets][B] merged buckets -> nsets canonical Jacobian results (d_outs: device array of output pointers, or the one output d_out):
 // msm_fold, then the tail over the 2 nsets level-2 sets.  Lane: the lane shape of that tail when the quads do not apply.
@@ -1077,6 +1182,7 @@ int msm_fold_tail(zkhip_ctx *ctx, const uint32_t *sets, const MsmFoldBuffers<F> 
             return 0;
         });
     };
+    if (msm_tail_wide_applies<F>(ctx, nsets, g.C)) return msm_tail_wide<F>(ctx, fb, d_outs, d_out);
     if (QuadLane<F>::AVAILABLE && ctx->opt_msm_tail_quads && 2 * nsets * g.C <= ((size_t)1 << 18)) return level2(QuadLane<F>());
     return level2(Lane());
 }
