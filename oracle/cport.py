@@ -2,7 +2,9 @@
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this.
 All field elements cross as canonical little-endian u64 limbs in numpy uint64 arrays:
-  Fr: 4 limbs; BLS12-381 Fq: 6 limbs; BN254 Fq: 4 limbs; G1 affine = 2 Fq; G2 affine = 2 Fq2 = 4 Fq.
+  Fr: 4 limbs; BLS12-381 Fq: 6 limbs; BN254, Pallas and Vesta Fq: 4 limbs; G1 affine = 2 Fq; G2 affine = 2 Fq2 = 4 Fq.
+Curve ids as include/zkhip.h: 0 BLS12-381, 1 BN254, 2 Pallas, 3 Vesta.  The Pasta ids have G1 and their scalar field only: a G2 or Groth16
+call with one of them, and any call with an id the library has no table for, raises.
 """
 from __future__ import annotations
 
@@ -15,12 +17,20 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
-BLS12_381, BN254 = 0, 1
+BLS12_381, BN254, PALLAS, VESTA = 0, 1, 2, 3
 G1, G2 = 1, 2
-FQ_LIMBS = {BLS12_381: 6, BN254: 4}
+FQ_LIMBS = {BLS12_381: 6, BN254: 4, PALLAS: 4, VESTA: 4}
+HAS_G2 = (BLS12_381, BN254)
+
+
+def _ok(rc: int):
+    if rc != 0:
+        raise ValueError("liboracle refused the call: a curve id it has no table for, a group the curve does not have, or a bad size")
 
 
 def point_limbs(curve: int, group: int) -> int:
+    if curve not in FQ_LIMBS or group not in (G1, G2) or (group == G2 and curve not in HAS_G2):
+        raise ValueError(f"no group {group} on curve id {curve}")
     return 2 * FQ_LIMBS[curve] * group
 
 
@@ -91,7 +101,7 @@ def set_threads(t: int):
 
 def random_fr(curve: int, seed: int, n: int) -> np.ndarray:
     out = np.empty((n, 4), dtype=np.uint64)
-    lib().zko_random_fr(curve, ctypes.c_uint64(seed), ctypes.c_size_t(n), _p(out))
+    _ok(lib().zko_random_fr(curve, ctypes.c_uint64(seed), ctypes.c_size_t(n), _p(out)))
     return out
 
 
@@ -129,6 +139,7 @@ class Bases:
         bases = _u64(bases)
         self.curve, self.group, self.n = curve, group, bases.shape[0]
         infp = _p(np.ascontiguousarray(inf, dtype=np.uint8)) if inf is not None else None
+        point_limbs(curve, group)
         self.h = ctypes.c_void_p(lib().zko_bases_new(curve, group, _p(bases), infp, ctypes.c_size_t(self.n)))
         assert self.h
 
@@ -161,6 +172,18 @@ def point_add(curve, group, a, a_inf, b, b_inf):
     return out, int(oinf[0])
 
 
+def bases_fold(curve: int, lo, hi, c, lo_inf=None, hi_inf=None):
+    """out[i] = c * hi[i] + lo[i] on G1: (points (n, L), inf (n,)); c one canonical scalar"""
+    lo, hi = _u64(lo), _u64(hi)
+    n = lo.shape[0]
+    assert hi.shape == lo.shape == (n, point_limbs(curve, G1))
+    out = np.zeros_like(lo)
+    inf = np.zeros(n, dtype=np.uint8)
+    infp = lambda f: _p(np.ascontiguousarray(f, dtype=np.uint8)) if f is not None else None
+    _ok(lib().zko_bases_fold(curve, _p(lo), infp(lo_inf), _p(hi), infp(hi_inf), _p(_u64(c)), ctypes.c_size_t(n), _p(out), _p(inf)))
+    return out, inf
+
+
 def ntt(curve: int, data: np.ndarray, log_m: int, omega: np.ndarray, inverse=False, coset=None) -> np.ndarray:
     """data: (batch, m, 4) canonical; returns a transformed copy."""
     d = _u64(data).copy()
@@ -190,13 +213,13 @@ def domain_fft(curve: int, kind: int, data: np.ndarray, omega, shift=None, inver
 def fr_horner(curve: int, coeffs: np.ndarray, x: np.ndarray) -> np.ndarray:
     coeffs = _u64(coeffs)
     out = np.zeros(4, dtype=np.uint64)
-    lib().zko_fr_horner(curve, _p(coeffs), ctypes.c_size_t(coeffs.shape[0]), _p(_u64(x)), _p(out))
+    _ok(lib().zko_fr_horner(curve, _p(coeffs), ctypes.c_size_t(coeffs.shape[0]), _p(_u64(x)), _p(out)))
     return out
 
 
 def fr_mul(curve: int, a, b) -> np.ndarray:
     out = np.zeros(4, dtype=np.uint64)
-    lib().zko_fr_mul(curve, _p(_u64(a)), _p(_u64(b)), _p(out))
+    _ok(lib().zko_fr_mul(curve, _p(_u64(a)), _p(_u64(b)), _p(out)))
     return out
 
 
@@ -207,7 +230,8 @@ class Groth16:
         self.curve = curve
         self.h = ctypes.c_void_p(lib().zko_g16_new(curve, ctypes.c_size_t(num_constraints),
                                                    ctypes.c_size_t(num_inputs), ctypes.c_uint64(seed)))
-        assert self.h
+        if not self.h:
+            raise ValueError(f"no Groth16 over curve id {curve}")
         self._dims()
 
     def _dims(self):
@@ -284,8 +308,10 @@ class Groth16:
 # arguments are for.  Polynomials are (len, 4) uint64 arrays of canonical limbs: DFS vectors or coefficient vectors as named.
 # ---------------------------------------------------------------------------------------------------------------------------
 _R = {BLS12_381: 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001,
-      BN254: 21888242871839275222246405745257275088548364400416034343698204186575808495617}
-_GEN = {BLS12_381: 7, BN254: 5}
+      BN254: 21888242871839275222246405745257275088548364400416034343698204186575808495617,
+      PALLAS: 0x40000000000000000000000000000000224698fc0994a8dd8c46eb2100000001,
+      VESTA: 0x40000000000000000000000000000000224698fc094cf91b992d30ed00000001}
+_GEN = {BLS12_381: 7, BN254: 5, PALLAS: 5, VESTA: 5}
 
 
 def _limbs(v: int) -> np.ndarray:

@@ -302,6 +302,8 @@ typedef Fp<6, 0> FqBLS;
 typedef Fp<4, 1> FrBLS;
 typedef Fp<4, 2> FqBN;
 typedef Fp<4, 3> FrBN;
+typedef Fp<4, 4> FpPasta;  // Pallas base field = Vesta scalar field
+typedef Fp<4, 5> FqPasta;  // Pallas scalar field = Vesta base field
 
 static const uint64_t BLS_P[6] = {0xb9feffffffffaaabULL, 0x1eabfffeb153ffffULL, 0x6730d2a0f6b0f624ULL,
                                   0x64774b84f38512bfULL, 0x4b1ba7b6434bacd7ULL, 0x1a0111ea397fe69aULL};
@@ -311,6 +313,9 @@ static const uint64_t BN_P[4] = {0x3c208c16d87cfd47ULL, 0x97816a916871ca8dULL, 0
                                  0x30644e72e131a029ULL};
 static const uint64_t BN_R[4] = {0x43e1f593f0000001ULL, 0x2833e84879b97091ULL, 0xb85045b68181585dULL,
                                  0x30644e72e131a029ULL};
+// the Pasta cycle: both primes are 2^254 + a 126-bit tail
+static const uint64_t PASTA_P[4] = {0x992d30ed00000001ULL, 0x224698fc094cf91bULL, 0, 0x4000000000000000ULL};
+static const uint64_t PASTA_Q[4] = {0x8c46eb2100000001ULL, 0x224698fc0994a8ddULL, 0, 0x4000000000000000ULL};
 // standard generators (canonical limbs, little-endian)
 static const uint64_t BLS_G1[12] = {0xfb3af00adb22c6bbULL, 0x6c55e83ff97a1aefULL, 0xa14e3a3f171bac58ULL,
                                     0xc3688c4f9774b905ULL, 0x2695638c4fa9ac0fULL, 0x17f1d3a73197d794ULL,
@@ -330,6 +335,10 @@ static const uint64_t BN_G2[16] = {
     0x4ce6cc0166fa7daaULL, 0xe3d1e7690c43d37bULL, 0x4aab71808dcb408fULL, 0x12c85ea5db8c6debULL,
     0x55acdadcd122975bULL, 0xbc4b313370b38ef3ULL, 0xec9e99ad690c3395ULL, 0x090689d0585ff075ULL};
 
+// (p - 1, 2) on y^2 = x^3 + 5 over each prime
+static const uint64_t PALLAS_G1[8] = {0x992d30ed00000000ULL, 0x224698fc094cf91bULL, 0, 0x4000000000000000ULL, 2, 0, 0, 0};
+static const uint64_t VESTA_G1[8] = {0x8c46eb2100000000ULL, 0x224698fc0994a8ddULL, 0, 0x4000000000000000ULL, 2, 0, 0, 0};
+
 static void init_fields() {
     static bool done = false;
     if (done) return;
@@ -337,6 +346,8 @@ static void init_fields() {
     FrBLS::init(BLS_R);
     FqBN::init(BN_P);
     FrBN::init(BN_R);
+    FpPasta::init(PASTA_P);
+    FqPasta::init(PASTA_Q);
     done = true;
 }
 struct Init {
@@ -374,6 +385,32 @@ struct Tr<1, 2> {
     static constexpr int FL = 8;
     static const uint64_t *gen() { return BN_G2; }
 };
+
+// Pallas (id 2) and Vesta (id 3): a cycle, each curve's scalar field is the other's coordinate field.  No G2, no Groth16.
+template <>
+struct Tr<2, 1> {
+    typedef FpPasta F;
+    typedef FqPasta S;
+    static constexpr int FL = 4;
+    static const uint64_t *gen() { return PALLAS_G1; }
+};
+template <>
+struct Tr<3, 1> {
+    typedef FqPasta F;
+    typedef FpPasta S;
+    static constexpr int FL = 4;
+    static const uint64_t *gen() { return VESTA_G1; }
+};
+// the scalar-field modulus of a curve id, nullptr for an id without a table
+static const uint64_t *scalar_modulus(int curve) {
+    switch (curve) {
+        case 0: return BLS_R;
+        case 1: return BN_R;
+        case 2: return PASTA_Q;
+        case 3: return PASTA_P;
+    }
+    return nullptr;
+}
 
 template <class F>
 struct IO;
@@ -1194,7 +1231,8 @@ struct G16 {
 
 // ------------------------------------------------------------------------------------------------
 // extern "C" surface for ctypes (tests / bench cpu_baseline only)
-// curve: 0 = BLS12-381, 1 = BN254; group: 1 = G1, 2 = G2.  All field elements canonical LE u64 limbs.
+// curve: 0 = BLS12-381, 1 = BN254, 2 = Pallas, 3 = Vesta (G1 only; the scalar field of an id is its group's order); group: 1 = G1, 2 = G2.
+// All field elements canonical LE u64 limbs.  Every entry point returns -1 (or a null handle) for an id it has no table for.
 // ------------------------------------------------------------------------------------------------
 #define DISPATCH_CG(curve, group, ...)     \
     do {                                    \
@@ -1210,8 +1248,24 @@ struct G16 {
         } else if (curve == 1 && group == 2) { \
             typedef Tr<1, 2> T;             \
             __VA_ARGS__;                    \
+        } else if (curve == 2 && group == 1) { \
+            typedef Tr<2, 1> T;             \
+            __VA_ARGS__;                    \
+        } else if (curve == 3 && group == 1) { \
+            typedef Tr<3, 1> T;             \
+            __VA_ARGS__;                    \
         } else                              \
             return -1;                      \
+    } while (0)
+
+// run(S()) over the scalar field of the curve id; an id without a table is refused
+#define DISPATCH_S(curve, run)             \
+    do {                                    \
+        if (curve == 0) run(FrBLS());       \
+        else if (curve == 1) run(FrBN());   \
+        else if (curve == 2) run(FqPasta()); \
+        else if (curve == 3) run(FpPasta()); \
+        else return -1;                     \
     } while (0)
 
 template <class T>
@@ -1274,6 +1328,18 @@ static void poly_mul_t(const uint64_t *a, size_t na, const uint64_t *b, size_t n
     const S minv = S::from_u64(m).inv();
     for (size_t i = 0; i < no; ++i) (x[i] * minv).to_canonical(out + 4 * i);
 }
+template <class T>
+static void bases_fold_t(const uint64_t *lo, const uint8_t *lo_inf, const uint64_t *hi, const uint8_t *hi_inf, const uint64_t *c, size_t n, uint64_t *out,
+                         uint8_t *out_inf) {
+    typedef typename T::F F;
+#pragma omp parallel for schedule(static)
+    for (size_t i = 0; i < n; ++i) {
+        const Affine<F> l = load_affine<F>(lo + i * 2 * T::FL, lo_inf ? lo_inf[i] != 0 : false);
+        const Affine<F> h = load_affine<F>(hi + i * 2 * T::FL, hi_inf ? hi_inf[i] != 0 : false);
+        const Jac<F> r = Jac<F>::from_affine(h).mul(c, 4).madd(l);
+        store_affine<F>(out + i * 2 * T::FL, out_inf + i, r.to_affine());
+    }
+}
 extern "C" {
 
 int zko_num_threads() {
@@ -1301,6 +1367,8 @@ void *zko_bases_new(int curve, int group, const uint64_t *affine, const uint8_t 
     else if (curve == 0 && group == 2) mk(Tr<0, 2>());
     else if (curve == 1 && group == 1) mk(Tr<1, 1>());
     else if (curve == 1 && group == 2) mk(Tr<1, 2>());
+    else if (curve == 2 && group == 1) mk(Tr<2, 1>());
+    else if (curve == 3 && group == 1) mk(Tr<3, 1>());
     else {
         delete h;
         return nullptr;
@@ -1366,6 +1434,13 @@ int zko_jac_to_affine(int curve, int group, const uint64_t *jac, uint64_t *out, 
     return 0;
 }
 
+// out[i] = c * hi[i] + lo[i] over n rows (the generator fold of an inner-product argument's round), rows spread over the threads
+int zko_bases_fold(int curve, const uint64_t *lo, const uint8_t *lo_inf, const uint64_t *hi, const uint8_t *hi_inf, const uint64_t *c, size_t n,
+                   uint64_t *out, uint8_t *out_inf) {
+    DISPATCH_CG(curve, 1, bases_fold_t<T>(lo, lo_inf, hi, hi_inf, c, n, out, out_inf));
+    return 0;
+}
+
 // a + b on affine points (test helper for linearity properties)
 int zko_point_add(int curve, int group, const uint64_t *a, int a_inf, const uint64_t *b, int b_inf, uint64_t *out,
                   uint8_t *out_inf) {
@@ -1379,16 +1454,18 @@ int zko_point_add(int curve, int group, const uint64_t *a, int a_inf, const uint
 
 int zko_ntt(int curve, uint64_t *data, size_t log_m, size_t batch, const uint64_t *omega, int inverse,
             const uint64_t *coset) {
-    if (curve == 0) ntt_batch<FrBLS>(data, log_m, batch, omega, inverse, coset);
-    else if (curve == 1) ntt_batch<FrBN>(data, log_m, batch, omega, inverse, coset);
-    else return -1;
+    auto run = [&](auto tag) { ntt_batch<decltype(tag)>(data, log_m, batch, omega, inverse, coset); };
+    DISPATCH_S(curve, run);
     return 0;
 }
 
 // Fr helpers: out = a*b, a+b, a^e mod r  (tests use them to build large inputs fast)
 int zko_fr_mul(int curve, const uint64_t *a, const uint64_t *b, uint64_t *out) {
-    if (curve == 0) (FrBLS::from_canonical(a) * FrBLS::from_canonical(b)).to_canonical(out);
-    else (FrBN::from_canonical(a) * FrBN::from_canonical(b)).to_canonical(out);
+    auto run = [&](auto tag) {
+        typedef decltype(tag) S;
+        (S::from_canonical(a) * S::from_canonical(b)).to_canonical(out);
+    };
+    DISPATCH_S(curve, run);
     return 0;
 }
 // Horner evaluation of a polynomial (coefficients canonical) at x: random-point check of big NTTs
@@ -1410,14 +1487,14 @@ int zko_fr_horner(int curve, const uint64_t *coeffs, size_t n, const uint64_t *x
         for (auto &p : part) r = r + p;
         r.to_canonical(out);
     };
-    if (curve == 0) run(FrBLS());
-    else run(FrBN());
+    DISPATCH_S(curve, run);
     return 0;
 }
 // seeded uniform Fr elements (SplitMix64 stream: element i uses draws 4i..4i+3 of one stream)
 int zko_random_fr(int curve, uint64_t seed, size_t n, uint64_t *out) {
     SplitMix64 rng{seed};
-    const uint64_t *mod = curve == 0 ? BLS_R : BN_R;
+    const uint64_t *mod = scalar_modulus(curve);
+    if (!mod) return -1;
     for (size_t i = 0; i < n; ++i) rng.next_mod(mod, out + 4 * i);
     return 0;
 }
@@ -1430,9 +1507,8 @@ int zko_random_fr(int curve, uint64_t seed, size_t n, uint64_t *out) {
 // out (na + nb - 1 coefficients) = a * b by transforms over 2^log_m >= na + nb - 1 points, omega the primitive 2^log_m-th root
 int zko_poly_mul(int curve, const uint64_t *a, size_t na, const uint64_t *b, size_t nb, const uint64_t *omega, size_t log_m, uint64_t *out) {
     if (na == 0 || nb == 0 || ((size_t)1 << log_m) < na + nb - 1) return -1;
-    if (curve == 0) poly_mul_t<FrBLS>(a, na, b, nb, omega, log_m, out);
-    else if (curve == 1) poly_mul_t<FrBN>(a, na, b, nb, omega, log_m, out);
-    else return -1;
+    auto run = [&](auto tag) { poly_mul_t<decltype(tag)>(a, na, b, nb, omega, log_m, out); };
+    DISPATCH_S(curve, run);
     return 0;
 }
 // one transform of one vector, threads over the butterflies (cport's dfs <-> coefficients at 2^16 .. 2^20)
@@ -1448,9 +1524,7 @@ int zko_ntt_wide(int curve, uint64_t *data, size_t log_m, const uint64_t *omega,
 #pragma omp parallel for schedule(static)
         for (size_t i = 0; i < m; ++i) (a[i] * minv).to_canonical(data + 4 * i);
     };
-    if (curve == 0) run(FrBLS());
-    else if (curve == 1) run(FrBN());
-    else return -1;
+    DISPATCH_S(curve, run);
     return 0;
 }
 // pointwise over n elements: op 0 a + b, 1 a - b, 2 a b, 3 a b[0] (scale), 4 a b / c (one inversion per element, as the reference's loops)
@@ -1472,9 +1546,7 @@ int zko_fr_vec(int curve, int op, const uint64_t *a, const uint64_t *b, const ui
         }
     };
     if (op < 0 || op > 4) return -1;
-    if (curve == 0) run(FrBLS());
-    else if (curve == 1) run(FrBN());
-    else return -1;
+    DISPATCH_S(curve, run);
     return 0;
 }
 // detail::fold_polynomial, DFS form (commitments/detail/polynomial/fold_polynomial.hpp:68-93):
@@ -1500,9 +1572,7 @@ int zko_fri_fold(int curve, const uint64_t *f, size_t log_size, const uint64_t *
             }
         }
     };
-    if (curve == 0) run(FrBLS());
-    else if (curve == 1) run(FrBN());
-    else return -1;
+    DISPATCH_S(curve, run);
     return 0;
 }
 // synthetic division of f (n coefficients) by (X - z): quot (n - 1 coefficients) and the remainder f(z) -- one step of poly_divmod by a
@@ -1519,9 +1589,7 @@ int zko_poly_div_linear(int curve, const uint64_t *f, size_t n, const uint64_t *
         carry.to_canonical(rem);
     };
     if (n == 0) return -1;
-    if (curve == 0) run(FrBLS());
-    else if (curve == 1) run(FrBN());
-    else return -1;
+    DISPATCH_S(curve, run);
     return 0;
 }
 // the tests' stand-in for the caller's Merkle tree: (per_leaf + sum_i (i + 1) v_i) mod r over the concatenated leaves
@@ -1542,9 +1610,7 @@ int zko_toy_root(int curve, const uint64_t *leaves, size_t count, uint64_t per_l
         for (auto &p : part) r = r + p;
         r.to_canonical(out);
     };
-    if (curve == 0) run(FrBLS());
-    else if (curve == 1) run(FrBN());
-    else return -1;
+    DISPATCH_S(curve, run);
     return 0;
 }
 // permutation_argument.hpp:103-136: g_v / h_v (k x n each) and V_P by the row-by-row recurrence, one inversion per row (the inversions
@@ -1574,9 +1640,7 @@ int zko_perm_grand_product(int curve, size_t k, size_t n, const uint64_t *cols, 
             v = v * ratio[j];
         }
     };
-    if (curve == 0) run(FrBLS());
-    else if (curve == 1) run(FrBN());
-    else return -1;
+    DISPATCH_S(curve, run);
     return 0;
 }
 // compute_V_L, lookup_argument.hpp:375-409: V[0] = 1, V[k] = V[k - 1] g(k - 1) / h(k - 1) for k <= usable_rows, zero behind
@@ -1605,9 +1669,7 @@ int zko_lookup_grand_product(int curve, size_t k_in, size_t k_val, size_t k_sort
         }
     };
     if (usable_rows >= n) return -1;
-    if (curve == 0) run(FrBLS());
-    else if (curve == 1) run(FrBN());
-    else return -1;
+    DISPATCH_S(curve, run);
     return 0;
 }
 // f (len coefficients) = q (X^n - 1) + rem: q[i] = f[i + n] + q[i + n] top down; returns the number of non-zero remainder coefficients
@@ -1622,9 +1684,7 @@ int zko_poly_div_vanishing(int curve, const uint64_t *f, size_t len, size_t n, u
         for (size_t i = 0; i < std::min(n, len); ++i) nz += !a[i].is_zero();
         *nonzero_rem = nz;
     };
-    if (curve == 0) run(FrBLS());
-    else if (curve == 1) run(FrBN());
-    else return -1;
+    DISPATCH_S(curve, run);
     return 0;
 }
 
@@ -1711,9 +1771,7 @@ int zko_domain_fft(int curve, int kind, size_t m, const uint64_t *omega, const u
         else d.fft(a);
         for (size_t i = 0; i < m; ++i) a[i].to_canonical(data + 4 * i);
     };
-    if (curve == 0) run(typename Tr<0, 1>::S());
-    else if (curve == 1) run(typename Tr<1, 1>::S());
-    else return -1;
+    DISPATCH_S(curve, run);
     return 0;
 }
 int zko_g16_is_satisfied(void *hv) {

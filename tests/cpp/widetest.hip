@@ -1,5 +1,5 @@
 // The one-point-per-wave group law (csrc/fu_wide.hpp) against the one-lane formulas of csrc/curve.hpp and the one-lane product of csrc/fu.hpp, on
-// arbitrary field elements (the formulas are algebraic identities; no curve membership needed): BLS12-381, BN254 and Pallas base fields.
+// arbitrary field elements (the formulas are algebraic identities; no curve membership needed): BLS12-381, BN254, Pallas and Vesta base fields.
 // One wave per case; every lane computes the one-lane reference, the wave computes the wide result, coordinates compared after canonicalisation
 // (products: limb for limb too -- fu_wide.hpp promises the very limbs of fu_mul).  Cases by wave: random operands; P + P; P + (-P); infinity on
 // either side; coordinates 0, 1 and p - 1; in every wave the product at the limb bound of the contract (all limbs 2^30 - 1), a chain of 64
@@ -154,6 +154,6 @@ unsigned run(const char *name) {
 }
 
 int main() {
-    const unsigned a = run<BlsFqU>("BLS12-381 Fq"), b = run<BnFqU>("BN254 Fq"), c = run<PallasFqU>("Pallas Fq");
-    return (a | b | c) ? 1 : 0;
+    const unsigned a = run<BlsFqU>("BLS12-381 Fq"), b = run<BnFqU>("BN254 Fq"), c = run<PallasFqU>("Pallas Fq"), d = run<VestaFqU>("Vesta Fq");
+    return (a | b | c | d) ? 1 : 0;
 }

@@ -6,7 +6,8 @@ scalar pattern (uniform, zeros / ones heavy, r - 1, few distinct values = large 
 as a batch whose members share a sort, NTT size / batch / direction / coset, evaluation domain of any kind, Groth16 witness map over the
 domain make_evaluation_domain picks, whole Groth16 proofs through the C++ shim, the grand products / pointwise kernels behind placeholder's
 permutation and lookup arguments on vectors of any length, the gate argument's flat-program kernel on random programs, the device group's MSM / NTT over
-1 .. 5 members and every transport -- and compares bit for bit.  Exit code 0 and a JSON line with the counts = no difference."""
+1 .. 5 members and every transport, and for Pallas and Vesta (ids 2 and 3: G1 and the scalar field only) the MSM, the NTT and the generator fold of the
+inner-product argument -- and compares bit for bit.  Every leg runs once before the random draws start, so every counter is positive whatever the seed.  Exit code 0 and a JSON line with the counts = no difference."""
 import argparse
 import json
 import os
@@ -21,6 +22,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import bench  # noqa: E402
 import cport as cp  # noqa: E402
+import pasta_util as pu  # noqa: E402  (ids 2 and 3 in util.CURVES)
 import pyoracle as po  # noqa: E402
 from util import CURVES, limbs, qap_domains  # noqa: E402
 
@@ -44,8 +46,8 @@ def scalars(rng, curve, n, pattern):
     return np.ascontiguousarray(s)
 
 
-def fuzz_msm(zk, ctx, rng, stats):
-    curve, group = int(rng.integers(0, 2)), int(rng.integers(1, 3))
+def fuzz_msm(zk, ctx, rng, stats, pasta=False):
+    curve, group = (int(rng.integers(2, 4)), 1) if pasta else (int(rng.integers(0, 2)), int(rng.integers(1, 3)))
     n = int(rng.integers(1, (6000 if group == 1 else 1500) * SCALE))
     # the two-level bucket reduction (G1, window tables) starts at 2^16 buckets by default: draw its threshold, its run length and -- one call in
     # three -- a window size that gives it 2^9 ... 2^17 buckets to fold
@@ -94,11 +96,49 @@ def fuzz_msm(zk, ctx, rng, stats):
     b.free()
     ctx.set_option("msm_tail_fold", 16)
     ctx.set_option("msm_fold_run", 0)
-    stats["msm"] += len(got)
+    stats["pasta_msm" if pasta else "msm"] += len(got)
 
 
-def fuzz_ntt(zk, ctx, rng, stats):
-    curve = int(rng.integers(0, 2))
+def fuzz_pasta_msm(zk, ctx, rng, stats):
+    """fuzz_msm's windows, folds, runs, scalar patterns and batch modes over Pallas / Vesta G1"""
+    fuzz_msm(zk, ctx, rng, stats, pasta=True)
+
+
+def fuzz_pasta_ntt(zk, ctx, rng, stats):
+    fuzz_ntt(zk, ctx, rng, stats, pasta=True)
+
+
+def fuzz_ipa_fold(zk, ctx, rng, stats):
+    """zkhip_bases_fold, out[i] = c hi[i] + lo[i], over Pallas / Vesta: half up to 2^12, lo and hi anywhere in one bases object (overlapping too), points
+    at infinity on either side, rows that cancel and rows that double, c uniform / 0 / 1 / r - 1 / tiny -- every row against the oracle"""
+    curve = int(rng.integers(2, 4))
+    r = CURVES[curve].r
+    half = int(rng.integers(1, (1 << 12) + 1))
+    n = half + int(rng.integers(half, 2 * half + 1))
+    off_lo, off_hi = int(rng.integers(0, n - half + 1)), int(rng.integers(0, n - half + 1))
+    c = [po.from_limbs(cp.random_fr(curve, int(rng.integers(1, 1 << 30)), 1)[0]), 0, 1, r - 1, int(rng.integers(0, 1 << 16))][int(rng.integers(0, 5)) if rng.random() < 0.4 else 0]
+    ks = [po.from_limbs(k) for k in cp.random_fr(curve, int(rng.integers(1, 1 << 30)), n)]
+    for _ in range(int(rng.integers(0, 12))):
+        ks[int(rng.integers(0, n))] = 0
+    if off_lo + half <= off_hi or off_hi + half <= off_lo:        # disjoint ranges: rows whose sum is infinity, rows that are a doubling
+        for _ in range(int(rng.integers(0, 12))):
+            i = int(rng.integers(0, half))
+            ks[off_lo + i] = (c if rng.random() < 0.5 else r - c) * ks[off_hi + i] % r
+    from util import fr_arr
+    b = ctx.bases_from_scalars(curve, 1, fr_arr(ks))
+    pts, inf = b.download()
+    out = ctx.bases_fold(b, off_lo, off_hi, half, limbs(c, 4))
+    got, ginf = out.download()
+    exp, einf = cp.bases_fold(curve, pts[off_lo:off_lo + half], pts[off_hi:off_hi + half], limbs(c, 4), inf[off_lo:off_lo + half], inf[off_hi:off_hi + half])
+    out.free()
+    b.free()
+    if not (np.asarray(ginf) == einf).all() or not (got == exp).all():
+        raise SystemExit("bases_fold differs: curve %d half %d lo %d hi %d c %#x" % (curve, half, off_lo, off_hi, c))
+    stats["ipa_fold"] += 1
+
+
+def fuzz_ntt(zk, ctx, rng, stats, pasta=False):
+    curve = int(rng.integers(2, 4)) if pasta else int(rng.integers(0, 2))
     C = CURVES[curve]
     log_m, batch = int(rng.integers(0, 15 + (3 if SCALE > 1 else 0))), int(rng.integers(1, 5))
     w = limbs(C.root_of_unity(log_m), 4)
@@ -108,7 +148,7 @@ def fuzz_ntt(zk, ctx, rng, stats):
     exp = cp.ntt(curve, a, log_m, w, inverse=inverse, coset=coset)
     if not (got == exp).all():
         raise SystemExit("NTT differs: curve %d log_m %d batch %d inverse %d coset %d" % (curve, log_m, batch, inverse, coset is not None))
-    stats["ntt"] += 1
+    stats["pasta_ntt" if pasta else "ntt"] += 1
 
 
 def fuzz_domain(zk, ctx, rng, stats):
@@ -459,9 +499,13 @@ def main():
     zk = bench.load_pkg()
     ctx = zk.Context(0)
     rng = np.random.default_rng(a.seed)
-    stats = {"msm": 0, "ntt": 0, "domain": 0, "domain_skipped": 0, "witness_map": 0, "groth16_proof": 0, "argument_kernels": 0}
-    legs = [fuzz_msm, fuzz_msm, fuzz_ntt, fuzz_domain, fuzz_witness, fuzz_proof, fuzz_arguments, fuzz_gate, fuzz_group, fuzz_lpc_group, fuzz_kzg_group]
+    stats = {"msm": 0, "ntt": 0, "domain": 0, "domain_skipped": 0, "witness_map": 0, "groth16_proof": 0, "argument_kernels": 0, "pasta_msm": 0, "pasta_ntt": 0,
+             "ipa_fold": 0}
+    legs = [fuzz_msm, fuzz_msm, fuzz_ntt, fuzz_domain, fuzz_witness, fuzz_proof, fuzz_arguments, fuzz_gate, fuzz_group, fuzz_lpc_group, fuzz_kzg_group, fuzz_pasta_msm,
+            fuzz_pasta_ntt, fuzz_ipa_fold]
     t0 = time.time()
+    for leg in dict.fromkeys(legs):        # every leg once, whatever the seed and the budget; then the draws
+        leg(zk, ctx, rng, stats)
     while time.time() - t0 < a.seconds:
         legs[int(rng.integers(0, len(legs)))](zk, ctx, rng, stats)
     ctx.close()

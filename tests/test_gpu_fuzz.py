@@ -18,3 +18,4 @@ def test_randomised_shapes_against_the_oracle(seed):
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])  # librccl announces itself on stdout at exit, after our line
     assert out["differences"] == 0 and out["compared"]["msm"] > 0 and out["compared"]["ntt"] > 0 and out["compared"]["witness_map"] > 0
+    assert out["compared"]["pasta_msm"] > 0 and out["compared"]["pasta_ntt"] > 0 and out["compared"]["ipa_fold"] > 0

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import cport as cp
+import pasta_util  # noqa: F401  (ids 2 and 3 in util.CURVES)
 import pyoracle as po
 from util import CURVES, fr_arr, fr_ints, jac_to_affine_py, limbs, pt_from_limbs, pt_limbs, pts_arr, qap_domains
 
@@ -47,7 +48,8 @@ def test_reference_kat_vectors(ctx):
 
 
 @pytest.mark.parametrize("curve,group,sizes", [(0, 1, (1, 2, 17, 256, 4096)), (1, 1, (1, 17, 300, 2048)),
-                                               (0, 2, (1, 2, 17, 200)), (1, 2, (1, 17, 200))])
+                                               (0, 2, (1, 2, 17, 200)), (1, 2, (1, 17, 200)),
+                                               (2, 1, (1, 17, 300, 4097)), (3, 1, (1, 17, 300, 4097))])
 def test_msm_matches_oracle(ctx, curve, group, sizes):
     C = CURVES[curve]
     nmax = max(sizes)
@@ -134,7 +136,7 @@ def test_msm_edge_cases(ctx, curve, group):
     bases.free()
 
 
-@pytest.mark.parametrize("curve,group,n", [(0, 1, 20000), (1, 1, 9000), (0, 2, 9000)])
+@pytest.mark.parametrize("curve,group,n", [(0, 1, 20000), (1, 1, 9000), (0, 2, 9000), (2, 1, 9000), (3, 1, 9000)])
 def test_msm_skewed_scalars(ctx, curve, group, n):
     """most scalars identical: every window has one bucket with thousands of entries, which is cut into several
     tasks (msm_bucket_large) whose partial sums are folded by msm_large_combine."""
@@ -148,7 +150,7 @@ def test_msm_skewed_scalars(ctx, curve, group, n):
     bases.free()
 
 
-@pytest.mark.parametrize("curve,group,n", [(0, 2, 300), (1, 2, 1500), (0, 1, 1500)])
+@pytest.mark.parametrize("curve,group,n", [(0, 2, 300), (1, 2, 1500), (0, 1, 1500), (2, 1, 1500), (3, 1, 1500)])
 def test_msm_over_device_generated_bases(ctx, curve, group, n):
     """bases built on the device (zkhip_bases_from_scalars, and the window tables above 1024 points) hold lazily reduced
     coordinates -- for G2 up to 10p -- unlike uploaded ones (< 2p): the bucket kernels must accept both."""
@@ -218,7 +220,7 @@ def test_msm_full_size_bls12_381_g1(ctx):
     bases.free()
 
 
-@pytest.mark.parametrize("curve,group,n", [(0, 1, 3000), (0, 2, 700)])
+@pytest.mark.parametrize("curve,group,n", [(0, 1, 3000), (0, 2, 700), (2, 1, 3000), (3, 1, 3000)])
 def test_msm_repeated_calls_replay_graph(ctx, zk, curve, group, n):
     """the third identical call (same bases, same device buffers) is captured into a HIP graph and later ones replay it:
     the CONTENT of the scalar buffer changes between calls and every result must follow it; same through the batch
@@ -602,7 +604,7 @@ def test_two_level_tail_equals_running_sums(zk, ctx, curve, group, n):
             ctx.free(d)
 
 
-@pytest.mark.parametrize("curve,group", [(0, 1), (1, 1), (0, 2)])
+@pytest.mark.parametrize("curve,group", [(0, 1), (1, 1), (0, 2), (2, 1), (3, 1)])
 def test_two_level_tail_degenerate_buckets(zk, ctx, curve, group):
     """Row and column sums over buckets that hold THE SAME point (every base equal, scalar v once for v = 1 ... : each addition of the runs and of
     the trees is a doubling), its negative (scalars r - v: rows cancel to infinity), and mostly nothing (a handful of entries in 2^12 buckets):

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import cport as cp
+import pasta_util  # noqa: F401  (ids 2 and 3 in util.CURVES)
 from util import CURVES, fr_arr, jac_to_affine_py, pt_from_limbs
 
 pytestmark = pytest.mark.gpu
@@ -18,11 +19,11 @@ WIDE, QUADS = 1, 2    # values of msm_tail_quads
 
 def test_wide_group_law_unit(ctx):
     """product, sum, difference (limb for limb, at the limb bounds too), addition, doubling, small multiple, a chain of 64 operations, P + P,
-    P + (-P), infinity on either side, coordinates 0 / 1 / p - 1, the load / store layout: BLS12-381, BN254 and Pallas base fields"""
+    P + (-P), infinity on either side, coordinates 0 / 1 / p - 1, the load / store layout: BLS12-381, BN254, Pallas and Vesta base fields"""
     exe = os.path.join(ROOT, "tests", "cpp", "widetest")
     assert os.path.exists(exe), "tests/cpp/widetest is missing: python -c 'import __graft_entry__ as g; g.build()'"
     out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300, text=True)
-    assert out.returncode == 0 and out.stdout.count("mismatch mask 0x0 ") == 3, out.stdout
+    assert out.returncode == 0 and out.stdout.count("mismatch mask 0x0 ") == 4, out.stdout
 
 
 def both_tails(ctx, bases, sc, tree=False):
@@ -61,7 +62,8 @@ def scalar_cases(curve, n, c):
 
 # window bits c: 2^(c - 1) buckets, level-2 sets of C = 2^(c // 2) points, C / 8 partial sums per set after msm_wide_weigh; c = 15 is the
 # smallest with more than 8 of them (16), which msm_wide_tree folds before the final kernel (and the partial sums change buffers)
-@pytest.mark.parametrize("curve,log_n,c", [(0, 10, 11), (0, 12, 13), (1, 12, 12), (0, 13, 15)])
+@pytest.mark.parametrize("curve,log_n,c", [(0, 10, 11), (0, 12, 13), (1, 12, 12), (0, 13, 15), (2, 10, 11), (3, 12, 13), (3, 12, 12), (2, 13, 15),
+                                           (3, 13, 15)])
 def test_msm_wide_tail_equals_quads_and_oracle(ctx, curve, log_n, c):
     n = 1 << log_n
     try:

@@ -5,19 +5,20 @@ import numpy as np
 import pytest
 
 import cport as cp
+import pasta_util  # noqa: F401  (ids 2 and 3 in util.CURVES)
 import pyoracle as po
 from util import CURVES, fr_arr, fr_ints, limbs, qap_domains
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("curve", [0, 1])
+@pytest.mark.parametrize("curve", [0, 1, 2, 3])
 def test_ntt_all_small_sizes(ctx, curve):
     C = CURVES[curve]
     g = limbs(C.fr_generator, 4)
     for log_m in range(0, 14):
         m = 1 << log_m
-        batch = 3 if log_m < 12 else 1
+        batch = 3 if log_m < 12 or curve >= 2 else 1
         w = limbs(C.root_of_unity(log_m), 4)
         a = cp.random_fr(curve, 1000 + log_m, batch * m).reshape(batch, m, 4)
         exp = cp.ntt(curve, a, log_m, w)
@@ -34,12 +35,21 @@ def test_ntt_all_small_sizes(ctx, curve):
 
 
 def test_ntt_pass_structure_options(ctx):
-    C = po.BLS12_381
+    _pass_structure_options(ctx, 0)
+
+
+def test_ntt_pass_structure_options_pasta(ctx):
+    """the same grid over Vesta's scalar field (the 9-limb role of the prime that is Pallas's 10-limb coordinate field)"""
+    _pass_structure_options(ctx, 3)
+
+
+def _pass_structure_options(ctx, curve):
+    C = CURVES[curve]
     log_m = 11
     m = 1 << log_m
     w = limbs(C.root_of_unity(log_m), 4)
-    a = cp.random_fr(0, 9, 2 * m).reshape(2, m, 4)
-    exp = cp.ntt(0, a, log_m, w)
+    a = cp.random_fr(curve, 9, 2 * m).reshape(2, m, 4)
+    exp = cp.ntt(curve, a, log_m, w)
     try:
         for radix in (1, 2, 3, 4, 5, 6, 8, 10):
             for tile in (0, 1, 3, 4):
@@ -47,12 +57,12 @@ def test_ntt_pass_structure_options(ctx):
                     ctx.set_option("ntt_radix_log", radix)
                     ctx.set_option("ntt_tile_log", tile)
                     ctx.set_option("ntt_pair", pair)
-                    assert (ctx.ntt(0, a, log_m, w) == exp).all(), (radix, tile, pair)
-        a4 = cp.random_fr(0, 10, 4 * m).reshape(4, m, 4)
+                    assert (ctx.ntt(curve, a, log_m, w) == exp).all(), (radix, tile, pair)
+        a4 = cp.random_fr(curve, 10, 4 * m).reshape(4, m, 4)
         ctx.set_option("ntt_radix_log", 6)
         ctx.set_option("ntt_pair", 2)
-        assert (ctx.ntt(0, a4, log_m, w) == cp.ntt(0, a4, log_m, w)).all()
-        assert (ctx.ntt(0, a4[:3], log_m, w) == cp.ntt(0, a4[:3], log_m, w)).all()  # odd batch: falls back to one per workgroup
+        assert (ctx.ntt(curve, a4, log_m, w) == cp.ntt(curve, a4, log_m, w)).all()
+        assert (ctx.ntt(curve, a4[:3], log_m, w) == cp.ntt(curve, a4[:3], log_m, w)).all()  # odd batch: falls back to one per workgroup
     finally:
         ctx.set_option("ntt_radix_log", 8)
         ctx.set_option("ntt_tile_log", 3)
@@ -61,7 +71,16 @@ def test_ntt_pass_structure_options(ctx):
 
 def test_ntt_edge_values(ctx):
     """all-zero, all-(r-1), delta and constant vectors; non-standard omega (another primitive root)."""
-    C = po.BLS12_381
+    _edge_values(ctx, 0)
+
+
+@pytest.mark.parametrize("curve", [2, 3])
+def test_ntt_edge_values_pasta(ctx, curve):
+    _edge_values(ctx, curve)
+
+
+def _edge_values(ctx, curve):
+    C = CURVES[curve]
     log_m = 9
     m = 1 << log_m
     w0 = C.root_of_unity(log_m)
@@ -70,8 +89,8 @@ def test_ntt_edge_values(ctx):
     vecs[1, :] = limbs(C.r - 1, 4)
     vecs[2, 0] = limbs(C.r - 1, 4)
     vecs[3, :] = limbs(7, 4)
-    exp = cp.ntt(0, vecs, log_m, w)
-    assert (ctx.ntt(0, vecs, log_m, w) == exp).all()
+    exp = cp.ntt(curve, vecs, log_m, w)
+    assert (ctx.ntt(curve, vecs, log_m, w) == exp).all()
     assert fr_ints(exp[3])[0] == 7 * m % C.r and all(v == 0 for v in fr_ints(exp[3])[1:])
 
 
@@ -160,7 +179,8 @@ def test_lpc_resize_and_fold(ctx, zk, curve, log_n, expand):
 
 
 @pytest.mark.parametrize("curve,log_n,expand,batch", [(0, 1, 1, 1), (0, 3, 4, 2), (1, 8, 1, 1), (0, 9, 2, 5), (1, 10, 3, 2), (0, 13, 3, 1), (0, 16, 2, 3), (1, 17, 1, 1),
-                                                      (0, 17, 4, 1), (0, 18, 1, 2), (0, 5, 5, 1)])
+                                                      (0, 17, 4, 1), (0, 18, 1, 2), (0, 5, 5, 1),
+                                                      (2, 1, 3, 4), (3, 1, 3, 4), (2, 9, 2, 5), (3, 9, 2, 5), (2, 13, 3, 1), (3, 13, 3, 1)])
 def test_poly_resize_coset_extension(ctx, curve, log_n, expand, batch):
     """zkhip_poly_resize_dev growing n -> K n (round 5): the n known values copied to their places + the K - 1 new cosets by n-point
     transforms that store straight into theirs (K <= 16; K = 32 takes the old path) -- against the oracle's inverse transform, zero

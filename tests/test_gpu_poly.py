@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import cport as cp
+import pasta_util  # noqa: F401  (ids 2 and 3 in util.CURVES)
 import pyoracle as po
 from util import CURVES, fr_arr, fr_ints, limbs
 
@@ -44,7 +45,8 @@ def test_fr_vec_ops(ctx, curve):
         ctx.free(p)
 
 
-@pytest.mark.parametrize("curve,n", [(0, 1), (0, 33), (0, 8192), (0, 8193), (1, 20011), (0, 70000)])
+@pytest.mark.parametrize("curve,n", [(0, 1), (0, 33), (0, 8192), (0, 8193), (1, 20011), (0, 70000),
+                                     (2, 8192), (3, 8192), (2, 8193), (3, 8193), (2, 20011), (3, 20011)])
 def test_poly_eval_and_div(ctx, curve, n):
     r = CURVES[curve].r
     batch = 3
@@ -163,7 +165,8 @@ def test_fr_vec_affine_and_mul_div(ctx, curve):
         ctx.free(p)
 
 
-@pytest.mark.parametrize("curve,n,usable,k_in,k_val", [(0, 64, 61, 1, 1), (1, 8, 4, 0, 2), (0, 2051, 2040, 2, 0), (0, 4096, 4095, 1, 2)])
+@pytest.mark.parametrize("curve,n,usable,k_in,k_val", [(0, 64, 61, 1, 1), (1, 8, 4, 0, 2), (0, 2051, 2040, 2, 0), (0, 4096, 4095, 1, 2),
+                                                       (2, 2051, 2040, 2, 0), (3, 2051, 2040, 2, 0), (2, 4096, 4095, 1, 2), (3, 4096, 4095, 1, 2)])
 def test_lookup_grand_product_abi(ctx, curve, n, usable, k_in, k_val):
     """zkhip_lookup_grand_product_dev through the C ABI on RANDOM vectors (no closing product needed: the recurrence is what is checked)
     against the oracle's row-by-row loop (compute_V_L, lookup_argument.hpp:375-409): sizes that are no power of two or multiple of the
@@ -190,7 +193,7 @@ def test_lookup_grand_product_abi(ctx, curve, n, usable, k_in, k_val):
         ctx.free(p)
 
 
-@pytest.mark.parametrize("curve", [0, 1])
+@pytest.mark.parametrize("curve", [0, 1, 2, 3])
 def test_grand_products_zero_denominator(ctx, curve):
     """one inversion per CALL must not change what a zero denominator does.  The reference inverts per row (0^-1 = 0 in
     its field type): the row's ratio is 0, V keeps its values up to that row and is zero behind it; a zero c[j] of a b / c zeroes out[j] alone.
@@ -271,7 +274,7 @@ def _lookup_sort_on_device(ctx, inputs, values, n, usable):
     return got, flags.value
 
 
-@pytest.mark.parametrize("curve", [0, 1])
+@pytest.mark.parametrize("curve", [0, 1, 2, 3])
 @pytest.mark.parametrize("log_n,k_in,k_val", [(6, 1, 1), (7, 2, 1), (8, 3, 2), (10, 2, 2), (12, 1, 1), (14, 2, 1), (14, 1, 3)])
 def test_lookup_sort_polynomials_genuine(ctx, curve, log_n, k_in, k_val):
     """zkhip_lookup_sort_dev = sort_polynomials (lookup_argument.hpp:565-638) on GENUINE instances (tests/util.lookup_instance: every table
@@ -421,7 +424,7 @@ def test_block_cache_behind_malloc_free(ctx):
     assert not third._live and q not in zk.zkhip._BLOCK_HOLDER
 
 
-@pytest.mark.parametrize("curve,log_size", [(0, 6), (1, 9), (0, 14), (1, 16)])
+@pytest.mark.parametrize("curve,log_size", [(0, 6), (1, 9), (0, 14), (1, 16), (2, 9), (3, 9), (2, 14), (3, 14)])
 def test_gate_eval_flat_program(zk, ctx, curve, log_size):
     """zkhip_gate_eval_dev: the gate argument's sum as ONE launch over a flat program (gates_argument.hpp:93-121, 203-216 once the
     expressions are monomials) against the same sum from big integers / the oracle's pointwise arithmetic: gates with and without a
