@@ -437,3 +437,7 @@ int zk_ntt_run(zkhip_ctx *ctx, int curve, uint32_t *d_data, size_t log_m, size_t
 int zk_ntt_extend(zkhip_ctx *ctx, int curve, uint32_t *d_coeffs, size_t log_m, size_t batch, const uint64_t *omega, uint32_t *d_out, size_t log_k,
                   const uint64_t *omega_big);
 int zk_msm_host_reserve(zkhip_ctx *ctx, size_t n);  // zkhip.hip: ctx->msm_host_buf holds 512 B of result + n scalars
+bool zk_fr_canonical(int curve, const uint64_t *c);  // ipa.hip: c (4 limbs) below the modulus of the curve's scalar field?
+// ecntt.hip: slot 0 of dst (2^log_m G1 points, allocated) <- the inverse group DFT of src's points offset .. offset + 2^log_m; arguments checked by the caller.
+// glv = false takes the plain 65-window ladder (the measurement's other arm)
+int zk_bases_lagrange(zkhip_ctx *ctx, const zkhip_bases *src, size_t offset, size_t log_m, const uint64_t *omega, bool glv, zkhip_bases *dst);

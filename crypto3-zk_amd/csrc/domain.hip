@@ -47,6 +47,19 @@ static size_t ceil_log2(size_t n) {
     return r;
 }
 
+// omega^(m/2) = -1 <=> primitive m-th root: the power is not 1 and its square is
+template <class U>
+static bool primitive_root(const uint64_t *omega, size_t log_m) {
+    if (log_m == 0) return is_one(omega);
+    uint64_t t1[4], t2[4];
+    h_pow<U>(omega, (uint64_t)1 << (log_m - 1), t1);
+    h_mul<U>(t1, t1, t2);
+    return !is_one(t1) && is_one(t2);
+}
+bool zk_dom_primitive_root(int curve, const uint64_t *omega, size_t log_m) {
+    return fr_dispatch(curve, [&](auto u) -> int { return primitive_root<typename decltype(u)::type>(omega, log_m) ? 1 : 0; }) == 1;
+}
+
 int zk_dom_two_adicity(int curve) { return curve == CURVE_BN254 ? 28 : zk_curve_known(curve) ? 32 : -1; }
 
 bool zk_dom_choice(size_t min_size, size_t s, int *kind, size_t *m) {
@@ -176,11 +189,9 @@ static int dom_get_tables(zkhip_ctx *ctx, int curve, const ZkDomain &d, const ui
     });
     if (*out) return 0;
     // the roots must be what the domain says they are: anything else transforms over another point set
-    uint64_t t1[4], t2[4];
+    uint64_t t1[4];
     if (d.kind == ZKHIP_DOMAIN_STEP_RADIX2) {
-        h_pow<U>(d.omega, d.n0, t1);  // omega^big = -1 <=> primitive (2 big)-th root
-        h_mul<U>(t1, t1, t2);
-        if (is_one(t1) || !is_one(t2)) {
+        if (!primitive_root<U>(d.omega, ceil_log2(d.n0) + 1)) {  // omega^big = -1
             ctx->last_error = "step_radix2 domain: omega is not a primitive 2^" + std::to_string(ceil_log2(d.n0) + 1) + "-th root of unity";
             return ZKHIP_ERR_INVALID;
         }

@@ -13,6 +13,8 @@ struct ZkDomain {
 };
 
 int zk_dom_two_adicity(int curve);
+// omega (canonical) of order exactly 2^log_m in the curve's scalar field: omega^m = 1, and omega^(m/2) = -1 for m > 1.  On the host.
+bool zk_dom_primitive_root(int curve, const uint64_t *omega, size_t log_m);
 // make_evaluation_domain(min_size)'s choice over a field of two-adicity s; false: none of the radix-2 family fits
 bool zk_dom_choice(size_t min_size, size_t s, int *kind, size_t *m);
 int zk_dom_parse(int curve, const zkhip_domain *d, ZkDomain *out);

@@ -18,11 +18,16 @@
 //   * the 1/m of the inverse transform is folded into the LAST stage (u / m + (w^k / m) v: its own record table) -- m
 //     multiplications in one parallel pass instead of m / 2 in the stage and m more afterwards.
 //
-// Boundary form: canonical Jacobian points (X, Y, Z; Z = 0 for infinity), as zkhip_msm_dev returns them.
+// Boundary forms, one pair of load / store kernels each around the same stage network:
+//   zkhip_ec_ntt_dev       canonical Jacobian points (X, Y, Z; Z = 0 for infinity), as zkhip_msm_dev returns them, in place;
+//   zkhip_bases_lagrange   (zkhip.hip; zk_bases_lagrange below) the affine points of a bases object in, always the inverse transform, affine
+//                          points into a new bases object out: one inversion per lane over a chunk of points (Montgomery's trick).
+//                          kimchi_pedersen::params_type::add_lagrange_basis (kimchi_pedersen.hpp:92-105), G1 of all four curve ids.
 #include <algorithm>
 
 #include "ctx.hpp"
 #include "curve.hpp"
+#include "glv.hpp"
 
 using namespace zkhip;
 
@@ -30,78 +35,7 @@ namespace {
 
 constexpr int REC_WORDS = 12;  // a twiddle record: GLV  [0..4] nibbles of |k1|, [5..9] nibbles of |k2|, [10] bit h = half h negative
                                //                   plain [0..8] nibbles of k (65 used), [10] = 0
-
-// ---- GLV constants: lambda^2 + lambda + 1 = 0 (mod r), phi(P) = (beta x, y) = lambda P, lattice basis (a1, b1), (a2, b2) with
-// a + b lambda = 0 (mod r); c1 = floor(k g1 / 2^256), c2 = floor(k g2 / 2^256) (g1 = floor(2^256 |b2| / r), g2 = floor(2^256 |b1| / r)),
-//   k1 = k - c1 |a1| - c2 |a2|,  k2 = + c1 |b1| - c2 |b2|     (the signs below are those of both bases as chosen here)
-// Any (c1, c2) gives k1 + k2 lambda = k (mod r); these keep |k1|, |k2| below 2^128 (checked over 3 x 10^5 scalars and the corners).
-struct NoGlv {
-    static constexpr bool ENABLED = false;
-};
-struct BlsGlv {  // lambda = z^2 - 1 = 0xac45a4010001a40200000000ffffffff; basis (lambda, -1), (1, lambda + 1)
-    static constexpr bool ENABLED = true;
-    ZK_HD static uint32_t g1(int i) { constexpr uint32_t t[5] = {0xf6cfee30u, 0x63f6e522u, 0xe01faaddu, 0x7c6becf1u, 0x00000001u}; return t[i]; }
-    ZK_HD static uint32_t g2(int i) { constexpr uint32_t t[5] = {0x00000002u, 0, 0, 0, 0}; return t[i]; }
-    ZK_HD static uint32_t a1(int i) { constexpr uint32_t t[5] = {0xffffffffu, 0x00000000u, 0x0001a402u, 0xac45a401u, 0}; return t[i]; }
-    ZK_HD static uint32_t a2(int i) { constexpr uint32_t t[5] = {0x00000001u, 0, 0, 0, 0}; return t[i]; }
-    ZK_HD static uint32_t b1(int i) { constexpr uint32_t t[5] = {0x00000001u, 0, 0, 0, 0}; return t[i]; }
-    ZK_HD static uint32_t b2(int i) { constexpr uint32_t t[5] = {0x00000000u, 0x00000001u, 0x0001a402u, 0xac45a401u, 0}; return t[i]; }
-    ZK_HD static uint32_t beta(int i) {  // canonical, 12 words
-        constexpr uint32_t t[12] = {0x0000aaacu, 0x8bfd0000u, 0x4f49fffdu, 0x409427ebu, 0x0fb85f9bu, 0x897d2965u,
-                                    0x89759ad4u, 0xaa0d857du, 0x63d4de85u, 0xec024086u, 0x397fe699u, 0x1a0111eau};
-        return t[i];
-    }
-};
-struct BnGlv {  // lambda = 0xb3c4d79d41a917585bfc41088d8daaa78b17ea66b99c90dd; basis (a1, -b1), (a2, b2) from the extended Euclid on (r, lambda)
-    static constexpr bool ENABLED = true;
-    ZK_HD static uint32_t g1(int i) { constexpr uint32_t t[5] = {0xc7e0b3d7u, 0xd91d232eu, 0x00000002u, 0, 0}; return t[i]; }
-    ZK_HD static uint32_t g2(int i) { constexpr uint32_t t[5] = {0x391eb18du, 0x7a7bd9d4u, 0xa773d2cfu, 0x4ccef014u, 0x00000002u}; return t[i]; }
-    ZK_HD static uint32_t a1(int i) { constexpr uint32_t t[5] = {0x94d213e3u, 0x89d32568u, 0, 0, 0}; return t[i]; }
-    ZK_HD static uint32_t a2(int i) { constexpr uint32_t t[5] = {0x1221250bu, 0x0be4e154u, 0xeeb859fdu, 0x6f4d8248u, 0}; return t[i]; }
-    ZK_HD static uint32_t b1(int i) { constexpr uint32_t t[5] = {0x7d4f1128u, 0x8211bbebu, 0xeeb859fcu, 0x6f4d8248u, 0}; return t[i]; }
-    ZK_HD static uint32_t b2(int i) { constexpr uint32_t t[5] = {0x94d213e3u, 0x89d32568u, 0, 0, 0}; return t[i]; }
-    ZK_HD static uint32_t beta(int i) {  // canonical, 8 words
-        constexpr uint32_t t[8] = {0x77fffffeu, 0x57634731u, 0xacdb5c4fu, 0xd4f263f1u, 0xa0d48bacu, 0x59e26bceu, 0, 0};
-        return t[i];
-    }
-};
-
-// t (6 words) +/-= a (5 words) * b (5 words)   modulo 2^192
-ZK_D void acc_mul_192(uint32_t *t, const uint32_t *a, const uint32_t *b, bool subtract) {
-    uint32_t prod[6] = {0, 0, 0, 0, 0, 0};
-    for (int i = 0; i < 5; ++i) {
-        uint64_t carry = 0;
-        for (int j = 0; i + j < 6 && j < 5; ++j) {
-            const uint64_t cur = (uint64_t)prod[i + j] + (uint64_t)a[i] * b[j] + carry;
-            prod[i + j] = (uint32_t)cur;
-            carry = cur >> 32;
-        }
-        if (i + 5 < 6) prod[i + 5] = (uint32_t)carry;
-    }
-    uint64_t c = subtract ? 1 : 0;  // t - prod = t + ~prod + 1
-    for (int i = 0; i < 6; ++i) {
-        const uint64_t cur = (uint64_t)t[i] + (subtract ? (uint32_t)~prod[i] : prod[i]) + c;
-        t[i] = (uint32_t)cur;
-        c = cur >> 32;
-    }
-}
-
-// words 8..12 of k (8 words) * g (5 words)
-template <class GetG>
-ZK_D void mul_hi_256(uint32_t *out5, const uint32_t *k, GetG g) {
-    uint32_t t[13];
-    for (int i = 0; i < 13; ++i) t[i] = 0;
-    for (int i = 0; i < 8; ++i) {
-        uint64_t carry = 0;
-        for (int j = 0; j < 5; ++j) {
-            const uint64_t cur = (uint64_t)t[i + j] + (uint64_t)k[i] * g(j) + carry;
-            t[i + j] = (uint32_t)cur;
-            carry = cur >> 32;
-        }
-        t[i + 5] = (uint32_t)carry;
-    }
-    for (int i = 0; i < 5; ++i) out5[i] = t[8 + i];
-}
+// The GLV constants and the split k -> (k1, k2) are glv.hpp's (BlsGlv, BnGlv, PallasGlv, VestaGlv; NoGlv: the plain ladder).
 
 // signed 4-bit windows of an unsigned magnitude: digit w in [-8, 7] as a two's-complement nibble, sum_w d_w 16^w = mag
 ZK_D void recode_nibbles(uint32_t *out, int out_words, const uint32_t *mag, int mag_words, int windows) {
@@ -144,32 +78,10 @@ __global__ __launch_bounds__(256) void ec_ntt_records(const uint32_t *__restrict
     fu_to_canonical<U>(k, acc);
     uint32_t *out = rec + (size_t)j * REC_WORDS;
     if constexpr (G::ENABLED) {
-        uint32_t c1[5], c2[5], cst[5], k1[6], k2[6] = {0, 0, 0, 0, 0, 0};
-        mul_hi_256(c1, k, [](int i) { return G::g1(i); });
-        mul_hi_256(c2, k, [](int i) { return G::g2(i); });
-        for (int i = 0; i < 6; ++i) k1[i] = k[i];  // k modulo 2^192: k1 and k2 are small, the arithmetic is exact in two's complement
-        for (int i = 0; i < 5; ++i) cst[i] = G::a1(i);
-        acc_mul_192(k1, c1, cst, true);
-        for (int i = 0; i < 5; ++i) cst[i] = G::a2(i);
-        acc_mul_192(k1, c2, cst, true);
-        for (int i = 0; i < 5; ++i) cst[i] = G::b1(i);
-        acc_mul_192(k2, c1, cst, false);
-        for (int i = 0; i < 5; ++i) cst[i] = G::b2(i);
-        acc_mul_192(k2, c2, cst, true);
-        uint32_t signs = 0;
-        uint32_t *half[2] = {k1, k2};
-        for (int h = 0; h < 2; ++h) {
-            if (half[h][5] >> 31) {  // negative: take the magnitude
-                signs |= 1u << h;
-                uint64_t c = 1;
-                for (int i = 0; i < 6; ++i) {
-                    const uint64_t cur = (uint64_t)(uint32_t)~half[h][i] + c;
-                    half[h][i] = (uint32_t)cur;
-                    c = cur >> 32;
-                }
-            }
-            recode_nibbles(out + 5 * h, 5, half[h], 6, 33);
-        }
+        uint32_t k1[6], k2[6];
+        const uint32_t signs = glv_split<G>(k, k1, k2);
+        recode_nibbles(out, 5, k1, 6, 33);
+        recode_nibbles(out + 5, 5, k2, 6, 33);
         out[10] = signs;
         out[11] = 0;
     } else {
@@ -242,6 +154,7 @@ __global__ __launch_bounds__(64, G::ENABLED ? 2 : 1) void ec_ntt_mul_pass(uint32
         xyzz_store<F>(entry(7), xyzz_add(e2, p));
     }
     if constexpr (G::ENABLED) {
+        static_assert(G::BETA_WORDS == O::CANON_WORDS, "beta is an element of this coordinate field");
         uint32_t bc[O::CANON_WORDS];
         for (int i = 0; i < O::CANON_WORDS; ++i) bc[i] = G::beta(i);
         const F beta = O::from_canonical(bc);
@@ -296,9 +209,57 @@ __global__ __launch_bounds__(64) void ec_ntt_store(const uint32_t *__restrict__ 
     O::to_canonical(o + 2 * CW, j.Z);
 }
 
+// ---- the boundary of zkhip_bases_lagrange: the affine rows of a bases object (internal form, 2 coordinates each), no canonical round trip
+// affine -> device XYZZ at the bit-reversed position
+template <class F>
+__global__ __launch_bounds__(64) void ec_ntt_load_affine(const uint32_t *__restrict__ aff, uint32_t log_m, uint32_t *__restrict__ pts) {
+    constexpr int NL = FieldOps<F>::WORDS;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, m = 1u << log_m;
+    if (i >= m) return;
+    const uint32_t r = log_m ? (__brev(i) >> (32 - log_m)) : 0;
+    xyzz_store<F>(pts + (size_t)r * (4 * NL), XYZZ<F>::from_affine(affine_load<F>(aff + (size_t)i * (2 * NL))));
+}
+
+constexpr uint32_t STORE_MAX_CHUNK = 8;       // points per lane that share one inversion, at most
+constexpr size_t STORE_TARGET_LANES = 16384;  // below this many lanes the chunk shrinks (an inversion is serial: lanes are what hides it)
+
+// device XYZZ -> affine.  A lane takes `chunk` consecutive points: the running product of their denominators ZZ ZZZ goes to `pre` (one field
+// element per point), ONE inversion serves the chunk (Montgomery's trick), points at infinity are skipped -- as ipa_bases_fold and
+// bases_mul_fixed end.
+template <class F>
+__global__ __launch_bounds__(64) void ec_ntt_store_affine(const uint32_t *__restrict__ pts, uint32_t m, uint32_t chunk, uint32_t *__restrict__ aff,
+                                                          uint32_t *__restrict__ pre_buf) {
+    typedef FieldOps<F> O;
+    constexpr int NL = O::WORDS;
+    const size_t first = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * chunk;
+    if (first >= m) return;
+    const uint32_t cnt = m - first < chunk ? (uint32_t)(m - first) : chunk;
+    F pre = F::one();
+    for (uint32_t k = 0; k < cnt; ++k) {
+        const size_t i = first + k;
+        const XYZZ<F> q = xyzz_load<F>(pts + i * (4 * NL));
+        if (!q.is_inf()) pre = O::mul(pre, O::mul(q.ZZ, q.ZZZ));
+        O::store(pre_buf + i * NL, pre);
+    }
+    F inv = O::inv(pre);
+    for (uint32_t k = cnt; k-- > 0;) {
+        const size_t i = first + k;
+        const XYZZ<F> q = xyzz_load<F>(pts + i * (4 * NL));
+        if (q.is_inf()) {
+            affine_store<F>(aff + i * (2 * NL), Affine<F>::infinity());
+            continue;
+        }
+        const F before = k > 0 ? O::load(pre_buf + (i - 1) * NL) : F::one();
+        const F dinv = O::mul(inv, before);
+        inv = O::mul(inv, O::mul(q.ZZ, q.ZZZ));
+        const Affine<F> a = {O::mul(q.X, O::mul(dinv, q.ZZZ)), O::mul(q.Y, O::mul(dinv, q.ZZ))};
+        affine_store<F>(aff + i * (2 * NL), a);
+    }
+}
+
 struct EcNttBuffers {  // sizes in u32 words
-    size_t pts_words, rec_words, tbl_words;
-    uint32_t *pts, *rec, *rec_last, *consts, *tbl;
+    size_t pts_words, rec_words, tbl_words, aux_words;
+    uint32_t *pts, *rec, *rec_last, *consts, *tbl, *aux;
     template <class Arena>
     void layout(Arena &a) {
         a.take(pts, pts_words);
@@ -306,17 +267,20 @@ struct EcNttBuffers {  // sizes in u32 words
         a.take(rec_last, rec_words);
         a.take(consts, 128);
         a.take(tbl, tbl_words);
+        a.take(aux, aux_words);
     }
 };
-template <class F, class U, class G>
-int ec_ntt_t(zkhip_ctx *ctx, uint32_t *d_jac, size_t log_m, const uint64_t *omega, int inverse) {
+// The stage network between a load and a store stage: load(pts) enqueues the kernel that fills the 2^log_m XYZZ points (bit-reversed),
+// store(pts, aux) the one that takes them away (natural order); aux: `aux_words` words of the workspace for the store stage.
+template <class F, class U, class G, class Load, class Store>
+int ec_ntt_run(zkhip_ctx *ctx, size_t log_m, const uint64_t *omega, int inverse, size_t aux_words, Load load, Store store) {
     constexpr int NL = FieldOps<F>::WORDS, PW = 4 * NL, HALVES = G::ENABLED ? 2 : 1;
     const uint32_t m = 1u << log_m, ntw = std::max<uint32_t>(1, m / 2);
     // table slots: the lanes of one multiplication launch (<= 1 GiB of tables; a pass over more lanes runs in several launches)
     const size_t slot_bytes = (size_t)8 * HALVES * PW * 4;
     const size_t slot_cap = ctx->opt_ec_ntt_table_lanes ? (((size_t)ctx->opt_ec_ntt_table_lanes + 63) & ~(size_t)63) : ((size_t)1 << 30) / slot_bytes / 64 * 64;
     const uint32_t slots = (uint32_t)std::max<size_t>(64, std::min<size_t>(((size_t)m + 63) & ~(size_t)63, slot_cap));
-    EcNttBuffers w = {(size_t)m * PW, (size_t)ntw * REC_WORDS, (size_t)slots * slot_bytes / 4};
+    EcNttBuffers w = {(size_t)m * PW, (size_t)ntw * REC_WORDS, (size_t)slots * slot_bytes / 4, aux_words};
     ZK_TRY(ws_place(ctx, w));
     uint32_t *pts = w.pts, *rec = w.rec, *rec_last = w.rec_last, *consts = w.consts, *tbl = w.tbl;
     uint32_t *d_w = consts + 32, *d_one = consts + 48, *rec_minv = consts + 64;
@@ -329,7 +293,7 @@ int ec_ntt_t(zkhip_ctx *ctx, uint32_t *d_jac, size_t log_m, const uint64_t *omeg
         ZK_LAUNCH(ctx, "ec_ntt_records", (ec_ntt_records<U, G>), grid_1d(ntw), dim3(256), 0, consts, consts + U::NL, ntw, rec_last);
         ZK_LAUNCH(ctx, "ec_ntt_records", (ec_ntt_records<U, G>), dim3(1), dim3(256), 0, d_one, consts + U::NL, 1u, rec_minv);
     }
-    ZK_LAUNCH(ctx, "ec_ntt_load", ec_ntt_load<F>, grid_1d(m, 64), dim3(64), 0, d_jac, (uint32_t)log_m, pts);
+    ZK_TRY(load(pts));
     for (uint32_t s = 1; s <= log_m; ++s) {
         const int mode = (inverse && s == log_m) ? 1 : 0;
         const uint32_t total = mode ? m : m / 2;
@@ -341,14 +305,62 @@ int ec_ntt_t(zkhip_ctx *ctx, uint32_t *d_jac, size_t log_m, const uint64_t *omeg
             }
         ZK_LAUNCH(ctx, "ec_ntt_butterflies", ec_ntt_butterflies<F>, grid_1d(m / 2, 64), dim3(64), 0, pts, (uint32_t)log_m, s);
     }
-    ZK_LAUNCH(ctx, "ec_ntt_store", ec_ntt_store<F>, grid_1d(m, 64), dim3(64), 0, pts, m, d_jac);
-    return ZKHIP_OK;
+    return store(pts, w.aux);
+}
+
+template <class F, class U, class G>
+int ec_ntt_t(zkhip_ctx *ctx, uint32_t *d_jac, size_t log_m, const uint64_t *omega, int inverse) {
+    const uint32_t m = 1u << log_m;
+    return ec_ntt_run<F, U, G>(
+        ctx, log_m, omega, inverse, 0,
+        [&](uint32_t *pts) -> int {
+            ZK_LAUNCH(ctx, "ec_ntt_load", ec_ntt_load<F>, grid_1d(m, 64), dim3(64), 0, d_jac, (uint32_t)log_m, pts);
+            return ZKHIP_OK;
+        },
+        [&](uint32_t *pts, uint32_t *) -> int {
+            ZK_LAUNCH(ctx, "ec_ntt_store", ec_ntt_store<F>, grid_1d(m, 64), dim3(64), 0, pts, m, d_jac);
+            return ZKHIP_OK;
+        });
+}
+
+// slot 0 of dst <- the inverse transform of src's rows offset .. offset + 2^log_m
+template <class F, class U, class G>
+int bases_lagrange_t(zkhip_ctx *ctx, const zkhip_bases *src, size_t offset, size_t log_m, const uint64_t *omega, zkhip_bases *dst) {
+    constexpr int NL = FieldOps<F>::WORDS;
+    const uint32_t m = 1u << log_m;
+    uint32_t chunk = 1;
+    while (chunk < STORE_MAX_CHUNK && (m + chunk - 1) / chunk > STORE_TARGET_LANES) chunk <<= 1;
+    const uint32_t *in = src->d + offset * src->stride_u32;  // slot 0: the points themselves, whatever tables the object carries
+    return ec_ntt_run<F, U, G>(
+        ctx, log_m, omega, 1, (size_t)m * NL,
+        [&](uint32_t *pts) -> int {
+            ZK_LAUNCH(ctx, "ec_ntt_load_affine", ec_ntt_load_affine<F>, grid_1d(m, 64), dim3(64), 0, in, (uint32_t)log_m, pts);
+            return ZKHIP_OK;
+        },
+        [&](uint32_t *pts, uint32_t *pre) -> int {
+            ZK_LAUNCH(ctx, "ec_ntt_store_affine", ec_ntt_store_affine<F>, grid_1d((m + chunk - 1) / chunk, 64), dim3(64), 0, pts, m, chunk, dst->d.p, pre);
+            return ZKHIP_OK;
+        });
 }
 
 }  // namespace
 
+int zk_bases_lagrange(zkhip_ctx *ctx, const zkhip_bases *src, size_t offset, size_t log_m, const uint64_t *omega, bool glv, zkhip_bases *dst) {
+    typedef CurveTraits<CURVE_PALLAS, GROUP_G1>::F PallasF;
+    typedef CurveTraits<CURVE_VESTA, GROUP_G1>::F VestaF;
+    if (src->group != GROUP_G1 || dst->n != (size_t)1 << log_m || dst->stride_u32 != src->stride_u32) return ZKHIP_ERR_INVALID;
+    if (src->curve == CURVE_PALLAS) return glv ? bases_lagrange_t<PallasF, PallasFrU, PallasGlv>(ctx, src, offset, log_m, omega, dst) : bases_lagrange_t<PallasF, PallasFrU, NoGlv>(ctx, src, offset, log_m, omega, dst);
+    if (src->curve == CURVE_VESTA) return glv ? bases_lagrange_t<VestaF, VestaFrU, VestaGlv>(ctx, src, offset, log_m, omega, dst) : bases_lagrange_t<VestaF, VestaFrU, NoGlv>(ctx, src, offset, log_m, omega, dst);
+    if (!glv) return ZKHIP_ERR_INVALID;  // the plain ladder is kept for the two curves it was measured on (tools/bench_lagrange.py)
+    if (src->curve == CURVE_BLS12_381) return bases_lagrange_t<CurveTraits<CURVE_BLS12_381, GROUP_G1>::F, BlsFrU, BlsGlv>(ctx, src, offset, log_m, omega, dst);
+    if (src->curve == CURVE_BN254) return bases_lagrange_t<CurveTraits<CURVE_BN254, GROUP_G1>::F, BnFrU, BnGlv>(ctx, src, offset, log_m, omega, dst);
+    return ZKHIP_ERR_INVALID;
+}
+
 extern "C" int zkhip_ec_ntt_dev(zkhip_ctx *ctx, int curve, int group, void *d_jacobian, size_t log_m, const uint64_t *omega, int inverse) {
-    ZK_ARGS_PAIRING(ctx, curve);  // G1 splits its twiddles with the curve's GLV constants, which exist for the two pairing curves only
+    // The pairing curves only.  (Pallas and Vesta have their GLV constants too -- glv.hpp -- and their group DFT is zkhip_bases_lagrange, over
+    // bases objects; this entry point keeps to the curves whose powers-of-tau ceremony it serves.)
+    ZK_ARGS_PAIRING(ctx, curve);
     if (!d_jacobian || !omega) return ZKHIP_ERR_INVALID;
     if (log_m > 26) return ZKHIP_ERR_RANGE;
     ZK_ENTER(ctx);
@@ -359,3 +371,4 @@ extern "C" int zkhip_ec_ntt_dev(zkhip_ctx *ctx, int curve, int group, void *d_ja
     if (curve == CURVE_BN254 && group == GROUP_G2) return ec_ntt_t<CurveTraits<CURVE_BN254, GROUP_G2>::F, BnFrU, NoGlv>(ctx, d, log_m, omega, inverse);
     return ZKHIP_ERR_INVALID;
 }
+

@@ -1,5 +1,5 @@
 // TEST SHIM (never loaded by the product path): runs the __host__ __device__ field / curve / recoding
-// code of fp.hpp, fu.hpp, curve.hpp and msm_recode.hpp on the CPU so the no-GPU test-suite can compare the
+// code of fp.hpp, fu.hpp, curve.hpp, msm_recode.hpp and glv.hpp on the CPU so the no-GPU test-suite can compare the
 // exact device arithmetic against the oracle, and the SHA2-256 core of sha256.hpp (the Merkle kernels' hash) and the proof-of-work
 // candidate function of pow.hpp (the grinding kernel's) against hashlib.
 // Built with --offload-host-only into libzkhip_hosttest.so.
@@ -8,6 +8,7 @@
 
 #define ZK_NOINLINE_MUL 1  // keeps this shim's build time short; fu_sqr is reached through op 9
 #include "arith_ops.h"
+#include "glv.hpp"
 #include "msm_recode.hpp"
 #include "pow.hpp"
 #include "sha256.hpp"
@@ -151,6 +152,40 @@ int zkt_pow_grind_cpu(const uint8_t *state, uint32_t start, uint32_t mask, uint6
     if (k == total) return 1;
     *nonce = start + (uint32_t)k;
     return 0;
+}
+
+// The GLV split of the EC-NTT's twiddle records (glv.hpp), curve 0 BLS12-381, 1 BN254, 2 Pallas, 3 Vesta: k (8 words, below r) -> the
+// magnitudes of k1 and k2 (6 words each) and *signs (bit h: half h is negative).
+int zkt_glv_split(int curve, const uint32_t *k, uint32_t *k1, uint32_t *k2, uint32_t *signs) {
+    if (!k || !k1 || !k2 || !signs) return -1;
+    switch (curve) {
+        case CURVE_BLS12_381: *signs = glv_split<BlsGlv>(k, k1, k2); return 0;
+        case CURVE_BN254: *signs = glv_split<BnGlv>(k, k1, k2); return 0;
+        case CURVE_PALLAS: *signs = glv_split<PallasGlv>(k, k1, k2); return 0;
+        case CURVE_VESTA: *signs = glv_split<VestaGlv>(k, k1, k2); return 0;
+        default: return -1;
+    }
+}
+// the constants the split and the ladder were compiled with: g1, g2, a1, a2, b1, b2 (5 words each, magnitudes), then beta (12 words, canonical)
+int zkt_glv_consts(int curve, uint32_t *out42) {
+    if (!out42) return -1;
+#define GLV_CONSTS(G)                                                                 \
+    {                                                                                 \
+        for (int i = 0; i < 5; ++i) {                                                 \
+            out42[i] = G::g1(i), out42[5 + i] = G::g2(i), out42[10 + i] = G::a1(i);   \
+            out42[15 + i] = G::a2(i), out42[20 + i] = G::b1(i), out42[25 + i] = G::b2(i); \
+        }                                                                             \
+        for (int i = 0; i < 12; ++i) out42[30 + i] = i < G::BETA_WORDS ? G::beta(i) : 0; \
+        return 0;                                                                     \
+    }
+    switch (curve) {
+        case CURVE_BLS12_381: GLV_CONSTS(BlsGlv)
+        case CURVE_BN254: GLV_CONSTS(BnGlv)
+        case CURVE_PALLAS: GLV_CONSTS(PallasGlv)
+        case CURVE_VESTA: GLV_CONSTS(VestaGlv)
+        default: return -1;
+    }
+#undef GLV_CONSTS
 }
 
 // SHA2-256 of a byte string: what zkhip_sha256_host computes

@@ -186,8 +186,9 @@ struct ChallengeBuffers {  // zkhip_fr_challenge_products_dev: the challenges as
     }
 };
 
-// c below the modulus of the curve's scalar field?
-bool fr_canonical(int curve, const uint64_t *c) {
+}  // namespace
+
+bool zk_fr_canonical(int curve, const uint64_t *c) {
     return fr_sat_dispatch(curve, [&](auto fr) -> int {
                using P = typename decltype(fr)::type;
                for (int j = 3; j >= 0; --j) {
@@ -198,15 +199,13 @@ bool fr_canonical(int curve, const uint64_t *c) {
            }) == 1;
 }
 
-}  // namespace
-
 extern "C" {
 
 int zkhip_bases_fold(zkhip_ctx *ctx, const zkhip_bases *b, size_t offset_lo, size_t offset_hi, size_t half, const uint64_t *c, zkhip_bases **out) {
     if (!b || !c || !out) return ZKHIP_ERR_INVALID;
     ZK_ARGS(ctx, b->curve);
     *out = nullptr;
-    if (b->group != GROUP_G1 || !fr_canonical(b->curve, c)) return ZKHIP_ERR_INVALID;
+    if (b->group != GROUP_G1 || !zk_fr_canonical(b->curve, c)) return ZKHIP_ERR_INVALID;
     if (offset_lo > b->n || half > b->n - offset_lo || offset_hi > b->n || half > b->n - offset_hi || half >= ((size_t)1 << 31)) return ZKHIP_ERR_RANGE;
     ZK_ENTER(ctx);
     // the result: the points alone (slot 0), no window tables -- it feeds two MSMs and the next fold

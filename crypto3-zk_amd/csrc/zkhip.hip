@@ -4,6 +4,7 @@
 #include <cstdlib>
 
 #include "ctx.hpp"
+#include "domain.hpp"
 #include "field_consts.hpp"
 #include "msm_recode.hpp"
 #include "zk_defs.hpp"
@@ -551,6 +552,34 @@ int zkhip_bases_spread(zkhip_ctx *ctx, const zkhip_bases *src, const uint32_t *d
         }
     }
     return bases_finish(ctx, b, out);
+}
+
+// The Lagrange basis of a range of an SRS (include/zkhip.h): every refusal before any launch, the transform into slot 0 of a new object (ecntt.hip),
+// then the window tables as every constructor builds them.
+static int bases_lagrange(zkhip_ctx *ctx, const zkhip_bases *b, size_t offset, size_t log_m, const uint64_t *omega, bool glv, zkhip_bases **out) {
+    if (out) *out = nullptr;
+    if (!b || !omega || !out) return ZKHIP_ERR_INVALID;
+    ZK_ARGS(ctx, b->curve);
+    if (b->group != GROUP_G1 || !zk_fr_canonical(b->curve, omega)) return ZKHIP_ERR_INVALID;
+    if (log_m > 26 || offset > b->n || ((size_t)1 << log_m) > b->n - offset) return ZKHIP_ERR_RANGE;
+    if (!zk_dom_primitive_root(b->curve, omega, log_m)) {
+        ctx->last_error = "zkhip_bases_lagrange: omega is not a primitive 2^" + std::to_string(log_m) + "-th root of unity";
+        return ZKHIP_ERR_INVALID;
+    }
+    ZK_TRY(check_device(ctx));
+    std::unique_ptr<zkhip_bases> r;
+    ZK_TRY(bases_alloc(ctx, b->curve, b->group, (size_t)1 << log_m, r));
+    ZK_TRY(zk_bases_lagrange(ctx, b, offset, log_m, omega, glv, r.get()));
+    return bases_finish(ctx, r, out);
+}
+
+int zkhip_bases_lagrange(zkhip_ctx *ctx, const zkhip_bases *b, size_t offset, size_t log_m, const uint64_t *omega, zkhip_bases **out) {
+    return bases_lagrange(ctx, b, offset, log_m, omega, true, out);
+}
+// Not part of the ABI (no declaration in include/zkhip.h): the same constructor over the plain 65-window ladder, Pallas and Vesta only --
+// the other arm of the measurement that chose GLV (tools/bench_lagrange.py, DESIGN.md section on the IPA).
+int zkhip_bench_bases_lagrange_plain(zkhip_ctx *ctx, const zkhip_bases *b, size_t offset, size_t log_m, const uint64_t *omega, zkhip_bases **out) {
+    return bases_lagrange(ctx, b, offset, log_m, omega, false, out);
 }
 
 int zkhip_bases_download(zkhip_ctx *ctx, const zkhip_bases *b, size_t offset, size_t n, uint64_t *affine_xy, uint8_t *is_infinity) {

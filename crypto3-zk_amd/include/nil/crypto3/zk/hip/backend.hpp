@@ -400,6 +400,30 @@ public:
         check(zkhip_bases_spread(ctx_->get(), b_, static_cast<const std::uint32_t *>(d_rows), first, n_total, &r.b_), "zkhip_bases_spread", ctx_->get());
         return r;
     }
+    /// the Lagrange basis of the rows offset .. offset + 2^log_m, out[j] = (1/m) sum_i omega^(-i j) row[offset + i], as a new object with
+    /// window tables (zkhip_bases_lagrange; G1); omega: the primitive 2^log_m-th root of unity of the domain
+    device_bases lagrange(std::size_t offset, std::size_t log_m, const typename adapter::scalar_value_type &omega) const {
+        static_assert(Group == ZKHIP_G1, "zkhip_bases_lagrange serves G1");
+        std::uint64_t w[4];
+        adapter::scalar_to_limbs(omega, w);
+        device_bases r;
+        r.ctx_ = ctx_;
+        r.size_ = (std::size_t)1 << log_m;
+        check(zkhip_bases_lagrange(ctx_->get(), b_, offset, log_m, w, &r.b_), "zkhip_bases_lagrange", ctx_->get());
+        return r;
+    }
+    /// host copies of all entries as group values (one download)
+    std::vector<typename std::conditional<Group == ZKHIP_G1, typename adapter::g1_value_type, typename adapter::g2_value_type>::type> download() const {
+        typedef typename std::conditional<Group == ZKHIP_G1, typename adapter::g1_value_type, typename adapter::g2_value_type>::type G;
+        const std::size_t cl = Group == ZKHIP_G1 ? adapter::g1_coord_limbs : adapter::g2_coord_limbs;
+        std::vector<std::uint64_t> xy(std::max<std::size_t>(1, size_) * 2 * cl);
+        std::vector<std::uint8_t> inf(std::max<std::size_t>(1, size_));
+        if (size_) check(zkhip_bases_download(ctx_->get(), b_, 0, size_, xy.data(), inf.data()), "zkhip_bases_download", ctx_->get());
+        std::vector<G> out;
+        out.reserve(size_);
+        for (std::size_t i = 0; i < size_; ++i) out.push_back(G::from_affine(&xy[i * 2 * cl], inf[i] != 0));
+        return out;
+    }
     /// host copy of entry i as a group value
     typename std::conditional<Group == ZKHIP_G1, typename adapter::g1_value_type, typename adapter::g2_value_type>::type at(std::size_t i) const {
         typedef typename std::conditional<Group == ZKHIP_G1, typename adapter::g1_value_type, typename adapter::g2_value_type>::type G;

@@ -5,6 +5,9 @@
 //   commitment(params, poly, bound)                                          (:334-383)  one MSM per chunk over sub-ranges of the resident g
 //   proof_eval(params, group_map, plms, elm, polyscale, evalscale, sponge)   (:385-559)  a, b, g stay on the device for the whole opening
 //   verify_eval(params, group_map, batches)                                  (:645-755)  one MSM over the resident [g ..., h] + one small one
+//   params.add_lagrange_basis(domain)                                        (:92-105)   the inverse DFT over group elements of g[0 .. n) on the
+//                                                                                        device; the result stays resident and is downloaded once
+//   commitment_evaluations(params, evals)                                    (no counterpart) one MSM of a column's evaluations over that basis
 // What stays the CALLER's, as the transcript does for the KZG and LPC shims (duck-typed template parameters):
 //   SpongeType    copyable;  absorb_fr(scalar), absorb_g(g1 value), challenge_fq() -> whatever GroupMapType::to_group takes,
 //                 squeeze_challenge(endo_r) -> scalar (never zero: it is inverted), and shift_scalar(scalar) -> scalar -- kimchi_functions'
@@ -20,7 +23,9 @@
 #define ZKHIP_SHIM_KIMCHI_PEDERSEN_HPP
 
 #include <memory>
+#include <stdexcept>
 #include <tuple>
+#include <unordered_map>
 #include <vector>
 
 #include "multiexp.hpp"
@@ -59,6 +64,25 @@ struct kimchi_pedersen_hip {
         scalar_value_type endo_r;
         std::size_t padded = 1;                       ///< |g| rounded up to a power of two
         device_bases<CurveType, ZKHIP_G1> srs;        ///< h is its row `padded`: the one-point range (padded, 1) is the resident h
+        /// the reference's member (:71): the Lagrange-basis SRS per domain size, a host copy downloaded once (pickles/verifier.hpp:78-79 reads it)
+        std::unordered_map<std::size_t, std::vector<group_value_type>> lagrange_bases;
+        /// the same bases resident, with window tables: what commitment_evaluations multiplies against
+        std::unordered_map<std::size_t, device_bases<CurveType, ZKHIP_G1>> lagrange_resident;
+
+        /// :92-105: lagrange_bases[n] = inverse_fft over group elements of g[0 .. n), on the device (zkhip_bases_lagrange).  Domain: size() and
+        /// omega -- evaluation_domain_hip of the basic kind, or the reference's basic_radix2_domain.  A size that is already there returns at
+        /// once (no launch); throws where the reference asserts (n > |g|), and for a size that is not a power of two.
+        template <typename Domain>
+        void add_lagrange_basis(const Domain &domain) {
+            const std::size_t n = domain.size();
+            if (lagrange_bases.find(n) != lagrange_bases.end()) return;
+            if (n == 0 || (n & (n - 1)) != 0) throw std::invalid_argument("kimchi_pedersen: add_lagrange_basis needs a radix-2 domain");
+            if (n > g.size()) throw std::invalid_argument("kimchi_pedersen: add_lagrange_basis: the domain is larger than the SRS");
+            std::size_t log_n = 0;
+            while (((std::size_t)1 << log_n) < n) ++log_n;
+            const auto at = lagrange_resident.emplace(n, srs.lagrange(0, log_n, domain.omega)).first;
+            lagrange_bases[n] = at->second.download();
+        }
     };
 
     template <typename value_type>
@@ -157,6 +181,18 @@ struct kimchi_pedersen_hip {
             blind_res.shifted = w;
         }
         return blinded_commitment_type(res, blind_res);
+    }
+
+    /// The NON-HIDING commitment of the polynomial whose evaluations over the domain of size evals.size() are given: one MSM over the
+    /// resident Lagrange bases of that size into unshifted[0], no inverse NTT.  No blinding, no degree bound and no chunking (the domain is
+    /// no larger than the SRS); the hiding variant is `commitment`'s masking loop, unshifted[0] + w h, and is the caller's one line.
+    /// Throws if add_lagrange_basis was not called for that size.
+    static commitment_type commitment_evaluations(const params_type &params, const std::vector<scalar_value_type> &evals) {
+        const auto at = params.lagrange_resident.find(evals.size());
+        if (at == params.lagrange_resident.end()) throw std::invalid_argument("kimchi_pedersen: commitment_evaluations: no Lagrange basis of this size was added");
+        commitment_type res;
+        res.unshifted.push_back(multiexp<CurveType, ZKHIP_G1>(params.ctx, at->second, 0, evals.begin(), evals.end()));
+        return res;
     }
 
     /// :385-559

@@ -21,7 +21,7 @@ EXPORTS = [
     "zkhip_domain_choice", "zkhip_domain_fft_dev", "zkhip_domain_lagrange_dev",
     "zkhip_r1cs_upload", "zkhip_r1cs_free", "zkhip_r1cs_set_domain", "zkhip_r1cs_domain_size", "zkhip_r1cs_domain_kind", "zkhip_groth16_scratch_bytes", "zkhip_groth16_witness_h_dev", "zkhip_groth16_witness_h_domain_dev", "zkhip_fr_gather_dev", "zkhip_poly_resize_dev", "zkhip_fri_fold_dev", "zkhip_fri_leaves_dev", "zkhip_ec_ntt_dev",
     "zkhip_fr_vec_op_dev", "zkhip_fr_vec_affine_dev", "zkhip_fr_vec_mul_div_dev", "zkhip_fr_vec_prod_dev", "zkhip_poly_shift_dev", "zkhip_poly_eval_dev", "zkhip_poly_div_linear_dev", "zkhip_poly_div_vanishing_dev", "zkhip_poly_lincomb_dev", "zkhip_perm_grand_product_dev", "zkhip_lookup_grand_product_dev", "zkhip_lookup_sort_dev", "zkhip_perm_factor_products_dev", "zkhip_gate_eval_dev",
-    "zkhip_bases_fold", "zkhip_fr_inner_product_dev", "zkhip_fr_powers_lincomb_dev", "zkhip_fr_challenge_products_dev",
+    "zkhip_bases_fold", "zkhip_bases_lagrange", "zkhip_fr_inner_product_dev", "zkhip_fr_powers_lincomb_dev", "zkhip_fr_challenge_products_dev",
     "zkhip_merkle_build_dev", "zkhip_merkle_build_fri_dev", "zkhip_merkle_leaves", "zkhip_merkle_depth", "zkhip_merkle_root", "zkhip_merkle_digests", "zkhip_merkle_paths",
     "zkhip_merkle_free", "zkhip_pow_grind", "zkhip_sha256_host",
     "zkhip_group_init", "zkhip_group_destroy", "zkhip_group_size", "zkhip_group_ctx", "zkhip_group_last_error", "zkhip_group_set_transport", "zkhip_group_transport",
@@ -290,6 +290,14 @@ class Context:
         self._check(self.lib.zkhip_bases_fold(self.h, bases.h, ctypes.c_size_t(offset_lo), ctypes.c_size_t(offset_hi), ctypes.c_size_t(half),
                                               _p(_u64(c).reshape(4)), ctypes.byref(h)), "zkhip_bases_fold")
         return Bases(self, h, bases.curve, bases.group, half)
+
+    def bases_lagrange(self, bases: "Bases", offset: int, log_m: int, omega) -> "Bases":
+        """out[j] = (1/m) sum_i omega^(-i j) bases[offset + i], i, j < m = 2^log_m: the Lagrange basis of that range of an SRS, a new bases
+        object with window tables as an upload of the same points would carry (zkhip_bases_lagrange)"""
+        h = ctypes.c_void_p()
+        self._check(self.lib.zkhip_bases_lagrange(self.h, bases.h, ctypes.c_size_t(offset), ctypes.c_size_t(log_m), _p(_u64(omega).reshape(4)),
+                                                  ctypes.byref(h)), "zkhip_bases_lagrange")
+        return Bases(self, h, bases.curve, bases.group, 1 << log_m)
 
     # ---- inner-product argument: scalar vectors
     def fr_inner_product_dev(self, curve: int, d_a: int, d_b: int, n: int, d_out: int):

@@ -42,8 +42,8 @@ typedef struct zkhip_bases zkhip_bases;
  *   ZKHIP_VESTA:  points of y^2 = x^3 + 5 over F_q (generator (q - 1, 2)); its "Fr" is F_p.
  * A placeholder proof over pallas::base_field_type (= F_p) therefore runs under ZKHIP_VESTA.
  * Both have 4-limb Fq and Fr, G1 only (ZKHIP_G2 with either id is ZKHIP_ERR_INVALID), two-adicity 32.  The entry points that need a
- * pairing-friendly curve -- zkhip_r1cs_* / zkhip_groth16_*, zkhip_bases_upload_compressed (the wire format) and zkhip_ec_ntt_dev (GLV
- * constants) -- answer ZKHIP_ERR_INVALID for them. */
+ * pairing-friendly curve -- zkhip_r1cs_* / zkhip_groth16_*, zkhip_bases_upload_compressed (the wire format) and zkhip_ec_ntt_dev (the
+ * powers-of-tau transform; their group DFT is zkhip_bases_lagrange, over bases objects) -- answer ZKHIP_ERR_INVALID for them. */
 enum zkhip_curve { ZKHIP_BLS12_381 = 0, ZKHIP_BN254 = 1, ZKHIP_PALLAS = 2, ZKHIP_VESTA = 3 };
 enum zkhip_group { ZKHIP_G1 = 1, ZKHIP_G2 = 2 };
 enum zkhip_status {
@@ -444,6 +444,20 @@ int zkhip_poly_lincomb_dev(zkhip_ctx *ctx, int curve, size_t count, const void *
  * would cost more than they save; an MSM over it combines the windows by the Horner pass.  Free it with zkhip_bases_free. */
 int zkhip_bases_fold(zkhip_ctx *ctx, const zkhip_bases *b, size_t offset_lo, size_t offset_hi, size_t half, const uint64_t *c /* 4 limbs */,
                      zkhip_bases **out);
+/* kimchi_pedersen::params_type::add_lagrange_basis (kimchi_pedersen.hpp:92-105): a NEW bases object of m = 2^log_m points,
+ *     out[j] = (1/m) sum_{i<m} omega^(-i j) b[offset + i]
+ * omega = the primitive m-th root of unity of the curve's scalar field (canonical, 4 limbs): the inverse DFT over group elements of a
+ * range of the SRS, so that the MSM of a column's EVALUATIONS over `out` is the commitment of the column (no inverse NTT).  G1 of every
+ * curve id (0-3; the twiddles are split by the curve's endomorphism, GLV, on all four); bases of ZKHIP_G2 are ZKHIP_ERR_INVALID as for
+ * zkhip_bases_fold.  b is left as it is and only its points are read, whatever window tables it carries; points at infinity among the
+ * inputs are ordinary.  `out` holds affine points in the internal form and, unlike the output of zkhip_bases_fold, carries window tables
+ * exactly as a zkhip_bases_upload of the same points would under the context's current "msm_precompute" / "msm_window_bits" options: it
+ * is built once and multiplied against many times.  Like every constructor of bases it returns with the stream drained; free with
+ * zkhip_bases_free.  log_m = 0: out[0] = b[offset].  "ec_ntt_table_lanes" applies as for zkhip_ec_ntt_dev.
+ * Errors, before anything is launched, with *out = null: a null ctx / b / omega / out or an unknown curve -> ZKHIP_ERR_INVALID; omega not
+ * below r, or not of order exactly 2^log_m (omega^m = 1, and omega^(m/2) = -1 for m > 1) -> ZKHIP_ERR_INVALID; log_m > 26 or
+ * offset + m > zkhip_bases_size(b) -> ZKHIP_ERR_RANGE. */
+int zkhip_bases_lagrange(zkhip_ctx *ctx, const zkhip_bases *b, size_t offset, size_t log_m, const uint64_t *omega /* 4 limbs */, zkhip_bases **out);
 /* d_out[0] = sum_{i < n} d_a[i] d_b[i] (algebra::inner_product, :472-475, :500-506), one canonical Fr element on the device; n < 2^39,
  * n = 0 gives zero.  The additions form a fixed tree (per wave, per workgroup, one last workgroup; no atomics). */
 int zkhip_fr_inner_product_dev(zkhip_ctx *ctx, int curve, const void *d_a, const void *d_b, size_t n, void *d_out);
