@@ -201,14 +201,33 @@ ZK_HD void point_chain(const uint32_t *pts, const uint8_t *inf, const uint8_t *n
     if (mode == 1) acc = xyzz_add(acc, acc2);
     if (mode == 2) acc = xyzz_mul_small(acc, k);
     if (mode == 3) {
-        Jacobian<F> j = xyzz_to_jacobian(acc);
-        O::to_canonical(out, j.X);
-        O::to_canonical(out + CW, j.Y);
-        O::to_canonical(out + 2 * CW, j.Z);
+        xyzz_store_canonical_jacobian<F>(out, acc);
         *out_inf = acc.is_inf() ? 1 : 0;
         return;
     }
     store_aff<F>(out, out_inf, acc);
+}
+
+// ---- the shared inversion (zkt_parked_affine / zkd_parked_affine) ----------------------------------------------------------------
+// Entry k = the xyzz_madd chain over pts[0..k] (inf / neg as point_chain's).  All n entries are parked with xyzz_park, then
+// xyzz_parked_to_affine turns them into n affine points: out = n canonical (x | y), out_inf = n flags.  layout 0: interleaved entries of 5
+// field elements (X, Y, ZZ, ZZZ, prefix product); 1: the points in one array, the prefixes in another.  work: 7 n WORDS words (5 n for the
+// parked entries, 2 n for the affine results in device form).
+template <class F>
+ZK_HD void parked_affine(const uint32_t *pts, const uint8_t *inf, const uint8_t *neg, size_t n, int layout, uint32_t *work, uint32_t *out,
+                         uint8_t *out_inf) {
+    typedef FieldOps<F> O;
+    constexpr int CW = O::CANON_WORDS, NL = O::WORDS;
+    auto pt = [&](uint32_t k) { return work + (size_t)k * (layout ? 4 : 5) * NL; };
+    auto pre = [&](uint32_t k) { return layout ? work + (4 * n + k) * NL : work + ((size_t)k * 5 + 4) * NL; };
+    XYZZ<F> acc = XYZZ<F>::infinity();
+    F prod = F::one();
+    for (size_t i = 0; i < n; ++i) {
+        acc = xyzz_madd(acc, load_aff<F>(pts + i * 2 * CW, inf ? inf[i] : 0), neg ? neg[i] != 0 : false);
+        xyzz_park(pt((uint32_t)i), pre((uint32_t)i), acc, prod);
+    }
+    xyzz_parked_to_affine(prod, (uint32_t)n, pt, pre, [&](uint32_t k) { return work + (5 * n + 2 * k) * NL; });
+    for (size_t i = 0; i < n; ++i) store_aff<F>(out + i * 2 * CW, out_inf + i, XYZZ<F>::from_affine(affine_load<F>(work + (5 * n + 2 * i) * NL)));
 }
 
 }  // namespace arith

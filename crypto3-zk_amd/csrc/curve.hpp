@@ -20,6 +20,7 @@
 //       (fu_mul2) and the result is < 2p; the other field types compute sub<K1>(a b, c d)
 #pragma once
 #include "fu.hpp"
+#include "glv.hpp"
 
 namespace zkhip {
 
@@ -202,6 +203,53 @@ ZK_HD void xyzz_store(uint32_t *p, const XYZZ<F> &a) {
     O::store(p + 3 * W, a.ZZZ);
 }
 
+// what a group element leaves the device as: XYZZ -> Jacobian, Montgomery -> canonical (X | Y | Z, CANON_WORDS each; Z = 0: infinity)
+template <class F>
+ZK_HD void xyzz_store_canonical_jacobian(uint32_t *dst, const XYZZ<F> &p) {
+    constexpr int CW = FieldOps<F>::CANON_WORDS;
+    Jacobian<F> j = xyzz_to_jacobian(p);
+    FieldOps<F>::to_canonical(dst, j.X);
+    FieldOps<F>::to_canonical(dst + CW, j.Y);
+    FieldOps<F>::to_canonical(dst + 2 * CW, j.Z);
+}
+
+// ---- XYZZ -> affine for many points with ONE inversion (Montgomery's trick) ---------------------------------------------------------------
+// A lane PARKS its points in memory: entry k is a point (4 field elements at pt(k)) and, at pre(k), the product of the denominators ZZ ZZZ of the finite
+// entries 0..k.  It inverts the last product (pre_all) and walks back: 1 / (ZZ_k ZZZ_k) = inv * prefix(k - 1), then inv *= ZZ_k ZZZ_k drops the factor.
+// Entries at infinity take no part and come out as Affine::infinity().  pt, pre and out map an entry to its address: the memory layout is the caller's.
+template <class F>
+ZK_HD void xyzz_park(uint32_t *pt, uint32_t *pre_slot, const XYZZ<F> &q, F &pre) {
+    typedef FieldOps<F> O;
+    xyzz_store<F>(pt, q);
+    if (!q.is_inf()) pre = O::mul(pre, O::mul(q.ZZ, q.ZZZ));
+    O::store(pre_slot, pre);
+}
+template <class F, class Pt, class Pre, class Out>
+ZK_HD void xyzz_parked_to_affine(const F &pre_all, uint32_t cnt, Pt pt, Pre pre, Out out) {
+    typedef FieldOps<F> O;
+    F inv = O::inv(pre_all);
+    for (uint32_t k = cnt; k-- > 0;) {
+        XYZZ<F> q = xyzz_load<F>(pt(k));
+        if (q.is_inf()) {
+            affine_store<F>(out(k), Affine<F>::infinity());
+            continue;
+        }
+        F before = k > 0 ? O::load(pre(k - 1)) : F::one();
+        F dinv = O::mul(inv, before);
+        inv = O::mul(inv, O::mul(q.ZZ, q.ZZZ));
+        Affine<F> a = {O::mul(q.X, O::mul(dinv, q.ZZZ)), O::mul(q.Y, O::mul(dinv, q.ZZ))};
+        affine_store<F>(out(k), a);
+    }
+}
+// Points per lane for the kernels that end in the walk above: 8 while that leaves 2^14 lanes, halving below (what precedes the inversion in a
+// lane is serial: lanes are what hides it).
+constexpr uint32_t AFFINE_MAX_CHUNK = 8;
+inline uint32_t affine_chunk(size_t points) {
+    uint32_t chunk = 1;
+    while (chunk < AFFINE_MAX_CHUNK && (points + chunk - 1) / chunk > 16384) chunk <<= 1;
+    return chunk;
+}
+
 // (curve, group) -> coordinate field the kernels compute in
 template <int CURVE, int GROUP>
 struct CurveTraits;
@@ -229,5 +277,28 @@ template <>
 struct CurveTraits<CURVE_VESTA, GROUP_G1> {
     typedef vesta_fqu F;
 };
+
+// G1 of a curve id: its coordinate field F, the traits U of its scalar field and the constants Glv of its endomorphism (glv.hpp)
+template <int CURVE, class FrU, class G>
+struct G1CurveOf {
+    static constexpr int ID = CURVE;
+    typedef typename CurveTraits<CURVE, GROUP_G1>::F F;
+    typedef FrU U;
+    typedef G Glv;
+};
+template <int CURVE> struct G1Curve;
+template <> struct G1Curve<CURVE_BLS12_381> : G1CurveOf<CURVE_BLS12_381, BlsFrU, BlsGlv> {};
+template <> struct G1Curve<CURVE_BN254> : G1CurveOf<CURVE_BN254, BnFrU, BnGlv> {};
+template <> struct G1Curve<CURVE_PALLAS> : G1CurveOf<CURVE_PALLAS, PallasFrU, PallasGlv> {};
+template <> struct G1Curve<CURVE_VESTA> : G1CurveOf<CURVE_VESTA, VestaFrU, VestaGlv> {};
+// A curve id to its G1Curve, in the shape of fr_dispatch (fu.hpp): g1_dispatch(curve, [&](auto c) -> int { using C = decltype(c); ... })
+template <class Fn>
+inline int g1_dispatch(int curve, Fn &&f) {
+    if (curve == CURVE_BLS12_381) return f(G1Curve<CURVE_BLS12_381>{});
+    if (curve == CURVE_BN254) return f(G1Curve<CURVE_BN254>{});
+    if (curve == CURVE_PALLAS) return f(G1Curve<CURVE_PALLAS>{});
+    if (curve == CURVE_VESTA) return f(G1Curve<CURVE_VESTA>{});
+    return FR_UNKNOWN_CURVE;
+}
 
 }  // namespace zkhip

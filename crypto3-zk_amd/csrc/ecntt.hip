@@ -220,12 +220,9 @@ __global__ __launch_bounds__(64) void ec_ntt_load_affine(const uint32_t *__restr
     xyzz_store<F>(pts + (size_t)r * (4 * NL), XYZZ<F>::from_affine(affine_load<F>(aff + (size_t)i * (2 * NL))));
 }
 
-constexpr uint32_t STORE_MAX_CHUNK = 8;       // points per lane that share one inversion, at most
-constexpr size_t STORE_TARGET_LANES = 16384;  // below this many lanes the chunk shrinks (an inversion is serial: lanes are what hides it)
-
-// device XYZZ -> affine.  A lane takes `chunk` consecutive points: the running product of their denominators ZZ ZZZ goes to `pre` (one field
-// element per point), ONE inversion serves the chunk (Montgomery's trick), points at infinity are skipped -- as ipa_bases_fold and
-// bases_mul_fixed end.
+// device XYZZ -> affine.  A lane takes `chunk` consecutive points (affine_chunk): the running product of their denominators ZZ ZZZ goes to `pre`
+// (one field element per point), ONE inversion serves the chunk (Montgomery's trick), points at infinity are skipped.  The walk is curve.hpp's
+// xyzz_parked_to_affine spelled out: through the helper the kernel measured slower (EXPERIMENTS 22).
 template <class F>
 __global__ __launch_bounds__(64) void ec_ntt_store_affine(const uint32_t *__restrict__ pts, uint32_t m, uint32_t chunk, uint32_t *__restrict__ aff,
                                                           uint32_t *__restrict__ pre_buf) {
@@ -327,9 +324,7 @@ int ec_ntt_t(zkhip_ctx *ctx, uint32_t *d_jac, size_t log_m, const uint64_t *omeg
 template <class F, class U, class G>
 int bases_lagrange_t(zkhip_ctx *ctx, const zkhip_bases *src, size_t offset, size_t log_m, const uint64_t *omega, zkhip_bases *dst) {
     constexpr int NL = FieldOps<F>::WORDS;
-    const uint32_t m = 1u << log_m;
-    uint32_t chunk = 1;
-    while (chunk < STORE_MAX_CHUNK && (m + chunk - 1) / chunk > STORE_TARGET_LANES) chunk <<= 1;
+    const uint32_t m = 1u << log_m, chunk = affine_chunk(m);
     const uint32_t *in = src->d + offset * src->stride_u32;  // slot 0: the points themselves, whatever tables the object carries
     return ec_ntt_run<F, U, G>(
         ctx, log_m, omega, 1, (size_t)m * NL,
@@ -346,15 +341,14 @@ int bases_lagrange_t(zkhip_ctx *ctx, const zkhip_bases *src, size_t offset, size
 }  // namespace
 
 int zk_bases_lagrange(zkhip_ctx *ctx, const zkhip_bases *src, size_t offset, size_t log_m, const uint64_t *omega, bool glv, zkhip_bases *dst) {
-    typedef CurveTraits<CURVE_PALLAS, GROUP_G1>::F PallasF;
-    typedef CurveTraits<CURVE_VESTA, GROUP_G1>::F VestaF;
     if (src->group != GROUP_G1 || dst->n != (size_t)1 << log_m || dst->stride_u32 != src->stride_u32) return ZKHIP_ERR_INVALID;
-    if (src->curve == CURVE_PALLAS) return glv ? bases_lagrange_t<PallasF, PallasFrU, PallasGlv>(ctx, src, offset, log_m, omega, dst) : bases_lagrange_t<PallasF, PallasFrU, NoGlv>(ctx, src, offset, log_m, omega, dst);
-    if (src->curve == CURVE_VESTA) return glv ? bases_lagrange_t<VestaF, VestaFrU, VestaGlv>(ctx, src, offset, log_m, omega, dst) : bases_lagrange_t<VestaF, VestaFrU, NoGlv>(ctx, src, offset, log_m, omega, dst);
-    if (!glv) return ZKHIP_ERR_INVALID;  // the plain ladder is kept for the two curves it was measured on (tools/bench_lagrange.py)
-    if (src->curve == CURVE_BLS12_381) return bases_lagrange_t<CurveTraits<CURVE_BLS12_381, GROUP_G1>::F, BlsFrU, BlsGlv>(ctx, src, offset, log_m, omega, dst);
-    if (src->curve == CURVE_BN254) return bases_lagrange_t<CurveTraits<CURVE_BN254, GROUP_G1>::F, BnFrU, BnGlv>(ctx, src, offset, log_m, omega, dst);
-    return ZKHIP_ERR_INVALID;
+    return g1_dispatch(src->curve, [&](auto c) -> int {
+        using C = decltype(c);
+        if (glv) return bases_lagrange_t<typename C::F, typename C::U, typename C::Glv>(ctx, src, offset, log_m, omega, dst);
+        // the plain ladder is kept for the two curves it was measured on (tools/bench_lagrange.py)
+        if constexpr (C::ID == CURVE_PALLAS || C::ID == CURVE_VESTA) return bases_lagrange_t<typename C::F, typename C::U, NoGlv>(ctx, src, offset, log_m, omega, dst);
+        return ZKHIP_ERR_INVALID;
+    });
 }
 
 extern "C" int zkhip_ec_ntt_dev(zkhip_ctx *ctx, int curve, int group, void *d_jacobian, size_t log_m, const uint64_t *omega, int inverse) {
@@ -365,9 +359,13 @@ extern "C" int zkhip_ec_ntt_dev(zkhip_ctx *ctx, int curve, int group, void *d_ja
     if (log_m > 26) return ZKHIP_ERR_RANGE;
     ZK_ENTER(ctx);
     uint32_t *d = (uint32_t *)d_jacobian;
-    if (curve == CURVE_BLS12_381 && group == GROUP_G1) return ec_ntt_t<CurveTraits<CURVE_BLS12_381, GROUP_G1>::F, BlsFrU, BlsGlv>(ctx, d, log_m, omega, inverse);
+    if (group == GROUP_G1)
+        return g1_dispatch(curve, [&](auto c) -> int {
+            using C = decltype(c);
+            if constexpr (C::ID == CURVE_BLS12_381 || C::ID == CURVE_BN254) return ec_ntt_t<typename C::F, typename C::U, typename C::Glv>(ctx, d, log_m, omega, inverse);
+            return ZKHIP_ERR_INVALID;
+        });
     if (curve == CURVE_BLS12_381 && group == GROUP_G2) return ec_ntt_t<CurveTraits<CURVE_BLS12_381, GROUP_G2>::F, BlsFrU, NoGlv>(ctx, d, log_m, omega, inverse);
-    if (curve == CURVE_BN254 && group == GROUP_G1) return ec_ntt_t<CurveTraits<CURVE_BN254, GROUP_G1>::F, BnFrU, BnGlv>(ctx, d, log_m, omega, inverse);
     if (curve == CURVE_BN254 && group == GROUP_G2) return ec_ntt_t<CurveTraits<CURVE_BN254, GROUP_G2>::F, BnFrU, NoGlv>(ctx, d, log_m, omega, inverse);
     return ZKHIP_ERR_INVALID;
 }

@@ -76,11 +76,21 @@ int zkt_fu_raw(int type, int op, size_t n, const uint32_t *a, const uint32_t *b,
 #undef FU_RAW
 }
 
+// the scalar fields have no curve over them here
+static bool is_coord_field(int field) { return !(field == 1 || field == 3 || field == 8 || field == 9 || field == 13 || field == 15 || field == 18 || field == 19); }
 // coordinate field id as above (0/2/4/5/12/14 saturated, 6/7/10/11/16/17 lazy)
 int zkt_point_chain(int field, const uint32_t *pts, const uint8_t *inf, const uint8_t *neg, size_t n, int mode, uint32_t k,
                     uint32_t *out, uint8_t *out_inf) {
-    if (field == 1 || field == 3 || field == 8 || field == 9 || field == 13 || field == 15 || field == 18 || field == 19) return -1;
+    if (!is_coord_field(field)) return -1;
     FIELD_SWITCH(field, point_chain<F>(pts, inf, neg, n, mode, k, out, out_inf); return 0);
+    return -1;
+}
+
+// arith_ops.h's parked_affine: the n partial sums of the madd chain, parked and normalised with ONE inversion (curve.hpp: xyzz_park,
+// xyzz_parked_to_affine).  layout 0 / 1; out: n canonical affine points, out_inf: n flags.  Coordinate field ids as zkt_point_chain's.
+int zkt_parked_affine(int field, const uint32_t *pts, const uint8_t *inf, const uint8_t *neg, size_t n, int layout, uint32_t *out, uint8_t *out_inf) {
+    if (!is_coord_field(field) || (layout != 0 && layout != 1)) return -1;
+    FIELD_SWITCH(field, std::vector<uint32_t> work(7 * n * FieldOps<F>::WORDS + 1); parked_affine<F>(pts, inf, neg, n, layout, work.data(), out, out_inf); return 0);
     return -1;
 }
 
@@ -158,34 +168,20 @@ int zkt_pow_grind_cpu(const uint8_t *state, uint32_t start, uint32_t mask, uint6
 // magnitudes of k1 and k2 (6 words each) and *signs (bit h: half h is negative).
 int zkt_glv_split(int curve, const uint32_t *k, uint32_t *k1, uint32_t *k2, uint32_t *signs) {
     if (!k || !k1 || !k2 || !signs) return -1;
-    switch (curve) {
-        case CURVE_BLS12_381: *signs = glv_split<BlsGlv>(k, k1, k2); return 0;
-        case CURVE_BN254: *signs = glv_split<BnGlv>(k, k1, k2); return 0;
-        case CURVE_PALLAS: *signs = glv_split<PallasGlv>(k, k1, k2); return 0;
-        case CURVE_VESTA: *signs = glv_split<VestaGlv>(k, k1, k2); return 0;
-        default: return -1;
-    }
+    return g1_dispatch(curve, [&](auto c) -> int { *signs = glv_split<typename decltype(c)::Glv>(k, k1, k2); return 0; }) == 0 ? 0 : -1;
 }
 // the constants the split and the ladder were compiled with: g1, g2, a1, a2, b1, b2 (5 words each, magnitudes), then beta (12 words, canonical)
 int zkt_glv_consts(int curve, uint32_t *out42) {
     if (!out42) return -1;
-#define GLV_CONSTS(G)                                                                 \
-    {                                                                                 \
-        for (int i = 0; i < 5; ++i) {                                                 \
-            out42[i] = G::g1(i), out42[5 + i] = G::g2(i), out42[10 + i] = G::a1(i);   \
-            out42[15 + i] = G::a2(i), out42[20 + i] = G::b1(i), out42[25 + i] = G::b2(i); \
-        }                                                                             \
-        for (int i = 0; i < 12; ++i) out42[30 + i] = i < G::BETA_WORDS ? G::beta(i) : 0; \
-        return 0;                                                                     \
-    }
-    switch (curve) {
-        case CURVE_BLS12_381: GLV_CONSTS(BlsGlv)
-        case CURVE_BN254: GLV_CONSTS(BnGlv)
-        case CURVE_PALLAS: GLV_CONSTS(PallasGlv)
-        case CURVE_VESTA: GLV_CONSTS(VestaGlv)
-        default: return -1;
-    }
-#undef GLV_CONSTS
+    return g1_dispatch(curve, [&](auto c) -> int {
+        using G = typename decltype(c)::Glv;
+        for (int i = 0; i < 5; ++i) {
+            out42[i] = G::g1(i), out42[5 + i] = G::g2(i), out42[10 + i] = G::a1(i);
+            out42[15 + i] = G::a2(i), out42[20 + i] = G::b1(i), out42[25 + i] = G::b2(i);
+        }
+        for (int i = 0; i < 12; ++i) out42[30 + i] = i < G::BETA_WORDS ? G::beta(i) : 0;
+        return 0;
+    }) == 0 ? 0 : -1;
 }
 
 // SHA2-256 of a byte string: what zkhip_sha256_host computes

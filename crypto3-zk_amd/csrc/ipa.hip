@@ -21,16 +21,6 @@ using namespace zkhip;
 
 namespace {
 
-// A curve id to the coordinate field of its G1, as a type (fu.hpp's fr_dispatch does the same for the scalar field)
-template <class Fn>
-inline int g1_dispatch(int curve, Fn &&f) {
-    if (curve == CURVE_BLS12_381) return f(FieldTag<CurveTraits<CURVE_BLS12_381, GROUP_G1>::F>{});
-    if (curve == CURVE_BN254) return f(FieldTag<CurveTraits<CURVE_BN254, GROUP_G1>::F>{});
-    if (curve == CURVE_PALLAS) return f(FieldTag<CurveTraits<CURVE_PALLAS, GROUP_G1>::F>{});
-    if (curve == CURVE_VESTA) return f(FieldTag<CurveTraits<CURVE_VESTA, GROUP_G1>::F>{});
-    return FR_UNKNOWN_CURVE;
-}
-
 // ---- the generator fold ---------------------------------------------------------------------------------------------------------------
 // The scalar of a fold, recoded once on the host and passed by value: its words and the index of its top set bit (-1: the scalar is zero).
 // Every lane multiplies by the same scalar, so the double-and-add schedule is uniform over the wave: no lane waits for another's addition.
@@ -46,12 +36,9 @@ ZK_D uint32_t fold_word(const FoldScalar &c, int i) {
     return v;
 }
 
-constexpr uint32_t FOLD_MAX_CHUNK = 8;      // points per lane that share one inversion, at most
-constexpr size_t FOLD_TARGET_LANES = 16384; // below this many lanes the chunk shrinks: the scalar multiplication is serial, lanes are what hides it
-
-// out[i] = c * hi[i] + lo[i].  A lane takes `chunk` consecutive points: double-and-add from the top bit over the affine hi point, a mixed
-// addition of lo (complete: doubling, cancellation and either operand at infinity), the XYZZ sums parked in `tmp` (5 field elements per
-// entry: X, Y, ZZ, ZZZ, prefix product) and ONE inversion for the chunk (Montgomery's trick), as bases_mul_fixed does (msm_core.hpp).
+// out[i] = c * hi[i] + lo[i].  A lane takes `chunk` consecutive points (affine_chunk): double-and-add from the top bit over the affine hi point,
+// a mixed addition of lo (complete: doubling, cancellation and either operand at infinity), the XYZZ sums parked in `tmp` (5 field elements
+// per entry: X, Y, ZZ, ZZZ, prefix product) and ONE inversion for the chunk (curve.hpp: xyzz_parked_to_affine).
 template <class F>
 __global__ __launch_bounds__(64) void ipa_bases_fold(const uint32_t *__restrict__ lo_pts, const uint32_t *__restrict__ hi_pts, uint32_t half, uint32_t chunk,
                                                      FoldScalar c, uint32_t *__restrict__ out, uint32_t *__restrict__ tmp) {
@@ -73,25 +60,11 @@ __global__ __launch_bounds__(64) void ipa_bases_fold(const uint32_t *__restrict_
         }
         acc = xyzz_madd(acc, affine_load<F>(lo_pts + i * (2 * NL)));
         uint32_t *slot = tmp + i * (5 * NL);
-        xyzz_store<F>(slot, acc);
-        if (!acc.is_inf()) pre = O::mul(pre, O::mul(acc.ZZ, acc.ZZZ));
-        O::store(slot + 4 * NL, pre);
+        xyzz_park(slot, slot + 4 * NL, acc, pre);
     }
-    F inv = O::inv(pre);
-    for (uint32_t k = cnt; k-- > 0;) {
-        const size_t i = first + k;
-        const uint32_t *slot = tmp + i * (5 * NL);
-        XYZZ<F> q = xyzz_load<F>(slot);
-        if (q.is_inf()) {
-            affine_store<F>(out + i * (2 * NL), Affine<F>::infinity());
-            continue;
-        }
-        F before = k > 0 ? O::load(tmp + (i - 1) * (5 * NL) + 4 * NL) : F::one();
-        F dinv = O::mul(inv, before);
-        inv = O::mul(inv, O::mul(q.ZZ, q.ZZZ));
-        Affine<F> a = {O::mul(q.X, O::mul(dinv, q.ZZZ)), O::mul(q.Y, O::mul(dinv, q.ZZ))};
-        affine_store<F>(out + i * (2 * NL), a);
-    }
+    xyzz_parked_to_affine(
+        pre, cnt, [&](uint32_t k) { return tmp + (first + k) * (5 * NL); }, [&](uint32_t k) { return tmp + (first + k) * (5 * NL) + 4 * NL; },
+        [&](uint32_t k) { return out + (first + k) * (2 * NL); });
 }
 
 // ---- scalar-field kernels -------------------------------------------------------------------------------------------------------------
@@ -221,13 +194,12 @@ int zkhip_bases_fold(zkhip_ctx *ctx, const zkhip_bases *b, size_t offset_lo, siz
         s.top = -1;
         for (int i = 255; i >= 0 && s.top < 0; --i)
             if ((s.w[i >> 5] >> (i & 31)) & 1) s.top = i;
-        uint32_t chunk = 1;
-        while (chunk < FOLD_MAX_CHUNK && (half + chunk - 1) / chunk > FOLD_TARGET_LANES) chunk <<= 1;
+        const uint32_t chunk = affine_chunk(half);
         WsOne<uint32_t> w = {half * 5 * r->stride_u32 / 2};
         ZK_TRY(ws_place(ctx, w));
         const uint32_t *pts = b->d;  // slot 0: the points themselves, whatever tables the object carries
-        ZK_TRY(g1_dispatch(b->curve, [&](auto f) -> int {
-            using F = typename decltype(f)::type;
+        ZK_TRY(g1_dispatch(b->curve, [&](auto g) -> int {
+            using F = typename decltype(g)::F;
             ZK_LAUNCH(ctx, "ipa_bases_fold", ipa_bases_fold<F>, grid_1d((half + chunk - 1) / chunk, 64), dim3(64), 0, pts + offset_lo * b->stride_u32,
                       pts + offset_hi * b->stride_u32, (uint32_t)half, chunk, s, r->d.p, w.p);
             return ZKHIP_OK;

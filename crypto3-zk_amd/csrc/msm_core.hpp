@@ -45,9 +45,9 @@
 //   msm_final_fold    the same after msm_fold: COL sum + 2^log2(C) ROW sum
 //   msm_final_batch   the same for every member of a batch
 //   msm_wide_weigh / msm_wide_tree / msm_wide_final   level 2 after msm_fold for G1, one point per wave (fu_wide.hpp), in place of the four above
-// (msm_final, msm_final_fold and msm_write_infinity store through xyzz_store_canonical_jacobian.  msm_final_batch and jac_sum_k keep the three
-// stores spelled out, msm_bucket_large its own copy of block_tree_sum's loop, and the three batch inversions their back-substitution step: with
-// the shared helper those kernels compiled to other register / scratch counts.)
+// (msm_final, msm_final_fold and msm_write_infinity store through curve.hpp's xyzz_store_canonical_jacobian.  msm_final_batch and jac_sum_k keep the three
+// stores spelled out, msm_bucket_large its own copy of block_tree_sum's loop, and the three batch inversions their walk back from the inversion, which is
+// curve.hpp's xyzz_parked_to_affine written in place: through the shared helper an instance of each compiled worse or measured slower -- EXPERIMENTS 14, 22.)
 // Point order inside a bucket depends on LDS-atomic arrival order; the group law is exact, so the sum
 // (compared in affine) does not.
 #pragma once
@@ -704,16 +704,6 @@ __global__ __launch_bounds__(MSM_TAIL_THREADS, ZK_TAIL_WAVES) void msm_fold(cons
     }
 }
 
-// what every MSM result leaves the device as: XYZZ -> Jacobian, Montgomery -> canonical (X | Y | Z, CANON_WORDS each)
-template <class F>
-ZK_D void xyzz_store_canonical_jacobian(uint32_t *dst, const XYZZ<F> &p) {
-    constexpr int CW = FieldOps<F>::CANON_WORDS;
-    Jacobian<F> j = xyzz_to_jacobian(p);
-    FieldOps<F>::to_canonical(dst, j.X);
-    FieldOps<F>::to_canonical(dst + CW, j.Y);
-    FieldOps<F>::to_canonical(dst + 2 * CW, j.Z);
-}
-
 // out[i] = winsum[2 i] + 2^shift winsum[2 i + 1] as canonical Jacobian; outs == nullptr: the single output `out`
 template <class F, int LPB>
 __global__ __launch_bounds__(64) void msm_final_fold(const uint32_t *__restrict__ winsum, uint32_t count, uint32_t shift, uint32_t *const *__restrict__ outs,
@@ -890,7 +880,7 @@ __global__ __launch_bounds__(64) void bases_fixed_table(const uint32_t *__restri
 }
 // pts[i] = scalars[i] * base = sum_w tab[w][byte w of the scalar]: at most 32 mixed additions per point instead of 256 doublings + ~128
 // additions.  A lane takes FIXED_CHUNK consecutive points, parks their XYZZ sums in `tmp` and shares ONE inversion among them.
-constexpr uint32_t FIXED_CHUNK = 8;
+constexpr uint32_t FIXED_CHUNK = AFFINE_MAX_CHUNK;
 template <class F>
 __global__ __launch_bounds__(64) void bases_mul_fixed(uint32_t *__restrict__ pts, const uint32_t *__restrict__ tab, const uint32_t *__restrict__ scalars,
                                                       uint32_t n, uint32_t *__restrict__ tmp) {

@@ -201,6 +201,26 @@ int chain(const uint32_t *pts, const uint8_t *inf, const uint8_t *neg, size_t n,
     return m.finish();
 }
 
+// ---- the shared inversion over parked points (arith_ops.h: parked_affine), one lane ---------------------------------------------------
+template <class F>
+__global__ void k_parked(const uint32_t *pts, const uint8_t *inf, const uint8_t *neg, size_t n, int layout, uint32_t *work, uint32_t *out, uint8_t *out_inf) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) parked_affine<F>(pts, inf, neg, n, layout, work, out, out_inf);
+}
+
+template <class F>
+int parked(const uint32_t *pts, const uint8_t *inf, const uint8_t *neg, size_t n, int layout, uint32_t *out, uint8_t *out_inf) {
+    constexpr int CW = FieldOps<F>::CANON_WORDS;
+    if (n > 16 || (layout != 0 && layout != 1)) return -1;
+    Dev m;
+    const uint32_t *dp = m.in(pts, n * 2 * CW * 4);
+    const uint8_t *di = m.in(inf, n), *dn = m.in(neg, n);
+    uint32_t *dw = m.in<uint32_t>(nullptr, 7 * n * FieldOps<F>::WORDS * 4);
+    uint32_t *dout = m.out(out, n * 2 * CW * 4);
+    uint8_t *dinf = m.out(out_inf, n);
+    if (m.err == hipSuccess && n) hipLaunchKernelGGL(k_parked<F>, dim3(1), dim3(64), 0, 0, dp, di, dn, n, layout, dw, dout, dinf);
+    return m.finish();
+}
+
 template <class U>
 int chain_pair(const uint32_t *pts, const uint8_t *inf, const uint8_t *neg, size_t n, uint32_t *out, uint8_t *out_inf) {
     Dev m;
@@ -281,6 +301,17 @@ int zkd_point_chain(int field, const uint32_t *pts, const uint8_t *inf, const ui
         case 7: return chain<bn_fqu>(pts, inf, neg, n, mode, k, out, out_inf);
         case 10: return chain<bls_fqu2>(pts, inf, neg, n, mode, k, out, out_inf);
         case 11: return chain<bn_fqu2>(pts, inf, neg, n, mode, k, out, out_inf);
+        default: return -1;
+    }
+}
+
+// zkt_parked_affine for the lazy coordinate fields 6, 7, 10, 11 (one lane, n <= 16)
+int zkd_parked_affine(int field, const uint32_t *pts, const uint8_t *inf, const uint8_t *neg, size_t n, int layout, uint32_t *out, uint8_t *out_inf) {
+    switch (field) {
+        case 6: return parked<bls_fqu>(pts, inf, neg, n, layout, out, out_inf);
+        case 7: return parked<bn_fqu>(pts, inf, neg, n, layout, out, out_inf);
+        case 10: return parked<bls_fqu2>(pts, inf, neg, n, layout, out, out_inf);
+        case 11: return parked<bn_fqu2>(pts, inf, neg, n, layout, out, out_inf);
         default: return -1;
     }
 }

@@ -55,4 +55,13 @@ int zkdp_point_chain(int field, const uint32_t *pts, const uint8_t *inf, const u
     }
 }
 
+// zkt_parked_affine for the two coordinate fields (one lane, n <= 16)
+int zkdp_parked_affine(int field, const uint32_t *pts, const uint8_t *inf, const uint8_t *neg, size_t n, int layout, uint32_t *out, uint8_t *out_inf) {
+    switch (field) {
+        case 16: return parked<pallas_fqu>(pts, inf, neg, n, layout, out, out_inf);
+        case 17: return parked<vesta_fqu>(pts, inf, neg, n, layout, out, out_inf);
+        default: return -1;
+    }
+}
+
 }  // extern "C"

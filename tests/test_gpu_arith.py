@@ -286,3 +286,18 @@ def test_point_chains_on_device(dev, curve, group, field):
     assert pt_from_limbs(curve, group, out, oinf) == G.mul(G.add(P0, P1), 2)
     out, oinf = _chain(f, field, curve, group, pts, [0] * 4, [0, 0, 1, 1], 1)
     assert oinf == 1
+
+
+@pytest.mark.parametrize("curve,group,field", [(0, 1, 6), (0, 2, 10), (1, 1, 7), (1, 2, 11)])
+def test_parked_points_share_one_inversion_on_device(dev, host, curve, group, field):
+    """xyzz_park / xyzz_parked_to_affine (curve.hpp) on one lane: parked_cases.py's chains -- every prefix against big integers, both
+    layouts -- and limb for limb what the host build of the same code gives"""
+    import parked_cases
+    C = CURVES[curve]
+    G = C.g1 if group == 1 else C.g2
+    rng = po.SplitMix64(curve * 10 + group + 300)
+    base = G.batch_mul_gen([rng.next_mod(C.r) for _ in range(4)])
+    got = parked_cases.check(dev.zkd_parked_affine, field, curve, group, G, base)
+    ref = parked_cases.check(host.zkt_parked_affine, field, curve, group, G, base)
+    for (o, i), (ho, hi) in zip(got, ref):
+        assert (o == ho).all() and (i == hi).all()

@@ -153,6 +153,28 @@ def test_past_one_tile(ctx, curve):
     b.free()
 
 
+@pytest.mark.parametrize("curve,log_m", [(2, 15), (0, 15), (3, 17)])
+def test_shared_inversion_chunks(ctx, curve, log_m):
+    """ec_ntt_store_affine with more than one point per lane: 2^15 is the smallest size with two (the chunk is 1 up to 2^14 points), 2^17 has
+    the full eight.  The OUTPUT exponents e_j are chosen first -- zeros at the first, the last and a middle row of a lane's chunk and over one
+    whole chunk -- and the input is (NTT e) G, so the inverse transform must return e_j G, with infinity exactly at the chosen rows.  Rows are
+    compared with bases_from_scalars(e), which test_gpu_msm.py::test_bases_from_scalars pins to the oracle."""
+    m, w = 1 << log_m, limbs(CURVES[curve].root_of_unity(log_m), 4)
+    chunk = m >> 14
+    e = cp.random_fr(curve, 8900 + log_m, m)
+    zero = [10 * chunk, 21 * chunk - 1, 30 * chunk + chunk // 2] + list(range(40 * chunk, 41 * chunk))
+    e[zero] = 0
+    ks = cp.ntt(curve, e.reshape(1, m, 4), log_m, w)[0]
+    b = ctx.bases_from_scalars(curve, 1, ks)
+    out = ctx.bases_lagrange(b, 0, log_m, w)
+    ref = ctx.bases_from_scalars(curve, 1, e)
+    (got, ginf), (exp, einf) = out.download(), ref.download()
+    assert sorted(np.flatnonzero(einf).tolist()) == sorted(set(zero))
+    assert (np.asarray(ginf) == np.asarray(einf)).all() and (got == exp).all()
+    for x in (out, ref, b):
+        x.free()
+
+
 @pytest.mark.parametrize("curve", [2, 3])
 def test_result_is_a_first_class_bases_object(zk, curve):
     """window tables as an upload would build them under the context's options: the MSM over the object equals the oracle's MSM over its

@@ -165,12 +165,13 @@ def test_msm_over_device_generated_bases(ctx, curve, group, n):
     b.free()
 
 
-@pytest.mark.parametrize("curve,group,n", [(0, 1, 500), (1, 2, 60), (0, 1, 4101), (1, 2, 4101)])
+@pytest.mark.parametrize("curve,group,n", [(0, 1, 500), (1, 2, 60), (0, 1, 4101), (1, 2, 4101), (1, 1, 4101), (0, 2, 4101), (2, 1, 4101), (3, 1, 4101)])
 def test_bases_from_scalars(ctx, curve, group, n):
     """device-side fixed-base batch exponentiation (generator.hpp:187-214) against the oracle.
     n = 4101 is past the 4096-point switch to the fixed-base table and no multiple of the 8 points that share one
     inversion there; zero scalars (points at infinity, left out of the shared inversion) sit first, last and in the
-    middle of a chunk, fill a whole chunk, and fall into the short last chunk."""
+    middle of a chunk, fill a whole chunk, and fall into the short last chunk.  Every (curve, group) the library
+    builds the two fixed-base kernels for runs at that size."""
     ks = cp.random_fr(curve, 42, n)
     ks[0] = 0
     ks[1] = [1, 0, 0, 0]

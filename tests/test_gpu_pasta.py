@@ -111,6 +111,18 @@ def test_point_chains_on_device(dev, curve):
 
 
 @pytest.mark.parametrize("curve", [2, 3])
+def test_parked_points_share_one_inversion_on_device(dev, host, curve):
+    """xyzz_park / xyzz_parked_to_affine (curve.hpp) on one lane: parked_cases.py's chains -- every prefix against big integers, both
+    layouts -- and limb for limb what the host build of the same code gives"""
+    import parked_cases
+    G, base = pu.CURVES[curve].g1, pu.random_points(curve, 307, 4)
+    got = parked_cases.check(dev.zkdp_parked_affine, pu.LAZY_FQ[curve], curve, 1, G, base)
+    ref = parked_cases.check(host.zkt_parked_affine, pu.LAZY_FQ[curve], curve, 1, G, base)
+    for (o, i), (ho, hi) in zip(got, ref):
+        assert (o == ho).all() and (i == hi).all()
+
+
+@pytest.mark.parametrize("curve", [2, 3])
 def test_recode_on_device(dev, host, curve):
     r = pu.CURVES[curve].r
     for c in range(2, 22):

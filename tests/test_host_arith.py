@@ -178,6 +178,23 @@ def test_xyzz_group_law(shim, curve, group, lazy):
     assert oinf == 1
 
 
+@pytest.mark.parametrize("lazy", [0, 1])
+@pytest.mark.parametrize("curve,group", [(0, 1), (0, 2), (1, 1), (1, 2)])
+def test_parked_points_share_one_inversion(shim, curve, group, lazy):
+    """xyzz_park / xyzz_parked_to_affine (curve.hpp), the end of the kernels that turn a lane's chunk of XYZZ points into affine ones: every
+    prefix sum of parked_cases.py's chains -- infinite entries first, inside, last, adjacent, alone -- against big integers, both layouts"""
+    import parked_cases
+    C = CURVES[curve]
+    G = C.g1 if group == 1 else C.g2
+    rng = po.SplitMix64(curve * 10 + group + 200)
+    base = G.batch_mul_gen([rng.next_mod(C.r) for _ in range(4)])
+    parked_cases.check(shim.zkt_parked_affine, COORD_FIELDS[(curve, group)][lazy], curve, group, G, base)
+    z = np.zeros(64, dtype=np.uint32)
+    P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    assert shim.zkt_parked_affine(8, P(z), P(z), P(z), ctypes.c_size_t(0), 0, P(z), P(z)) == -1  # a scalar field
+    assert shim.zkt_parked_affine(6, P(z), P(z), P(z), ctypes.c_size_t(0), 2, P(z), P(z)) == -1  # no such layout
+
+
 @pytest.mark.parametrize("c", [2, 3, 5, 8, 11, 13, 16])
 def test_signed_digit_recoding(shim, c):
     r = po.BLS12_381.r

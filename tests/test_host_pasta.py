@@ -183,6 +183,16 @@ def test_xyzz_group_law(shim, curve, lazy):
         assert shim.zkt_point_chain(scalar_field, P(arr), P(arr), P(arr), ctypes.c_size_t(0), 0, ctypes.c_uint32(0), P(arr), P(arr)) == -1
 
 
+@pytest.mark.parametrize("lazy", [0, 1])
+@pytest.mark.parametrize("curve", [2, 3])
+def test_parked_points_share_one_inversion(shim, curve, lazy):
+    """xyzz_park / xyzz_parked_to_affine over the Pasta coordinate fields: every prefix sum of parked_cases.py's chains against big
+    integers, both layouts"""
+    import parked_cases
+    field = (pu.LAZY_FQ if lazy else pu.SAT_FQ)[curve]
+    parked_cases.check(shim.zkt_parked_affine, field, curve, 1, pu.CURVES[curve].g1, pu.random_points(curve, 207, 4))
+
+
 def check_recoding(digits_of, r, c, vals):
     tb = r.bit_length()
     W = (tb + c - 1) // c
