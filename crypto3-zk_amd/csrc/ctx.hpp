@@ -441,3 +441,7 @@ bool zk_fr_canonical(int curve, const uint64_t *c);  // ipa.hip: c (4 limbs) bel
 // ecntt.hip: slot 0 of dst (2^log_m G1 points, allocated) <- the inverse group DFT of src's points offset .. offset + 2^log_m; arguments checked by the caller.
 // glv = false takes the plain 65-window ladder (the measurement's other arm)
 int zk_bases_lagrange(zkhip_ctx *ctx, const zkhip_bases *src, size_t offset, size_t log_m, const uint64_t *omega, bool glv, zkhip_bases *dst);
+// ecntt.hip: slot 0 of dst (n points of src's curve and group, allocated) <- s_i * (src's point offset + i); the scalars are the n resident 8-word values at
+// d_scalars or, when that is null, coeff * ratio^(e0 + i) (coeff nullable: 1).  Arguments checked by the caller.
+int zk_bases_scale(zkhip_ctx *ctx, const zkhip_bases *src, size_t offset, size_t n, const uint32_t *d_scalars, const uint64_t *ratio, const uint64_t *coeff,
+                   uint32_t e0, zkhip_bases *dst);

@@ -23,6 +23,11 @@
 //   zkhip_bases_lagrange   (zkhip.hip; zk_bases_lagrange below) the affine points of a bases object in, always the inverse transform, affine
 //                          points into a new bases object out: one inversion per lane over a chunk of points (Montgomery's trick).
 //                          kimchi_pedersen::params_type::add_lagrange_basis (kimchi_pedersen.hpp:92-105), G1 of all four curve ids.
+//
+// The same ladder WITHOUT the network -- out[i] = s_i P_i, a different scalar per resident point (zkhip_bases_scale_dev / zkhip_bases_scale_geometric;
+// zk_bases_scale below): the contribution to a powers-of-tau accumulator (powers_of_tau/accumulator.hpp:89-121) and the delta^-1 scaling of the
+// Groth16 MPC (r1cs_gg_ppzksnark_mpc/crs_operations.hpp:116-123).  Records from resident scalars or from coeff ratio^i, one bases_scale_pass
+// per slice of table slots, the same affine store.
 #include <algorithm>
 
 #include "ctx.hpp"
@@ -33,21 +38,8 @@ using namespace zkhip;
 
 namespace {
 
-constexpr int REC_WORDS = 12;  // a twiddle record: GLV  [0..4] nibbles of |k1|, [5..9] nibbles of |k2|, [10] bit h = half h negative
-                               //                   plain [0..8] nibbles of k (65 used), [10] = 0
-// The GLV constants and the split k -> (k1, k2) are glv.hpp's (BlsGlv, BnGlv, PallasGlv, VestaGlv; NoGlv: the plain ladder).
-
-// signed 4-bit windows of an unsigned magnitude: digit w in [-8, 7] as a two's-complement nibble, sum_w d_w 16^w = mag
-ZK_D void recode_nibbles(uint32_t *out, int out_words, const uint32_t *mag, int mag_words, int windows) {
-    for (int i = 0; i < out_words; ++i) out[i] = 0;
-    uint32_t carry = 0;
-    for (int w = 0; w < windows; ++w) {
-        const int word = w >> 3;
-        uint32_t d = (word < mag_words ? (mag[word] >> ((w & 7) * 4)) & 15u : 0u) + carry;
-        carry = d >= 8 ? 1 : 0;  // d - 16 in [-8, 0]: the nibble (d & 15) read as two's complement
-        out[word] |= (d & 15u) << ((w & 7) * 4);
-    }
-}
+// The GLV constants, the split k -> (k1, k2) and the window record of a scalar (REC_WORDS words, scalar_record) are glv.hpp's (BlsGlv, BnGlv,
+// PallasGlv, VestaGlv; NoGlv: the plain ladder).
 
 // consts: [0] = effective root (omega, or omega^-1 for the inverse) canonical; [1] = 1/m canonical
 template <class U>
@@ -61,33 +53,33 @@ __global__ void ec_ntt_setup(const uint32_t *__restrict__ omega_c, uint32_t log_
     fu_to_canonical<U>(consts + U::NL, fu_inv(mm));
 }
 
-// rec[j] = the window record of w^j (times `scale` when given) for j < count: square-and-multiply over the bits of j, then the
-// GLV split (G1) and the signed-nibble recoding
+// rec[j] = the window record of w^(e0 + j) (times `scale` when given) for j < count: square-and-multiply over the bits of the exponent
+// (e0 + j < 2^32; w^0 = 1 whatever w is, zero included), then the GLV split (G1) and the signed-nibble recoding.  The twiddles of the group
+// DFT (e0 = 0) and the geometric scalars coeff ratio^(e0 + j) of zkhip_bases_scale_geometric.
 template <class U, class G>
-__global__ __launch_bounds__(256) void ec_ntt_records(const uint32_t *__restrict__ consts, const uint32_t *__restrict__ scale_c, uint32_t count,
+__global__ __launch_bounds__(256) void ec_ntt_records(const uint32_t *__restrict__ consts, const uint32_t *__restrict__ scale_c, uint32_t e0, uint32_t count,
                                                        uint32_t *__restrict__ rec) {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= count) return;
     Fu<U> pw = fu_from_canonical<U>(consts), acc = Fu<U>::one();
-    for (uint32_t e = j; e; e >>= 1) {
+    for (uint32_t e = e0 + j; e; e >>= 1) {
         if (e & 1) acc = fu_mul_call(acc, pw);
         pw = fu_mul_call(pw, pw);
     }
     if (scale_c) acc = fu_mul_call(acc, fu_from_canonical<U>(scale_c));
     uint32_t k[8];
     fu_to_canonical<U>(k, acc);
-    uint32_t *out = rec + (size_t)j * REC_WORDS;
-    if constexpr (G::ENABLED) {
-        uint32_t k1[6], k2[6];
-        const uint32_t signs = glv_split<G>(k, k1, k2);
-        recode_nibbles(out, 5, k1, 6, 33);
-        recode_nibbles(out + 5, 5, k2, 6, 33);
-        out[10] = signs;
-        out[11] = 0;
-    } else {
-        recode_nibbles(out, 9, k, 8, 65);
-        out[9] = out[10] = out[11] = 0;
-    }
+    scalar_record<G>(rec + (size_t)j * REC_WORDS, k);
+}
+
+// rec[j] = the window record of the resident scalar j (8 canonical words; a value that is not below r is taken mod r, as the MSM takes it)
+template <class U, class G>
+__global__ __launch_bounds__(256) void scale_records_from_scalars(const uint32_t *__restrict__ scalars, uint32_t count, uint32_t *__restrict__ rec) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= count) return;
+    uint32_t k[8];
+    fu_pack<U>(k, fu_reduce(fu_load8<U>(scalars, j)));
+    scalar_record<G>(rec + (size_t)j * REC_WORDS, k);
 }
 
 // canonical Jacobian -> device XYZZ at the bit-reversed position
@@ -111,34 +103,13 @@ ZK_D XYZZ<F> xyzz_dbl4(XYZZ<F> a) {
     return xyzz_dbl(a);
 }
 
-// The multiplication pass.  mode 0: stage s (1-based) of the decimation-in-time network, lane t = butterfly t multiplies its lower
-// input v by w^(k stride) (k = 0: nothing to do); mode 1: the last stage of the INVERSE transform, lane t = point t, upper inputs take
-// 1/m, lower inputs w^k / m.  Lanes first .. first + gridDim.x * 64 of `total`; `tbl` holds 8 * HALVES points per lane of the launch.
+// The fixed 4-bit signed-window ladder of one lane: out <- rec P for a finite point P and a window record (glv.hpp: scalar_record).  T: the lane's table,
+// 8 * HALVES points of the launch's table slots -- e P for e = 1 .. 8 (and phi(e P) behind them); every entry is re-read from memory where it is
+// needed again.  The body of both multiplication kernels below.
 template <class F, class G>
-__global__ __launch_bounds__(64, G::ENABLED ? 2 : 1) void ec_ntt_mul_pass(uint32_t *__restrict__ pts, const uint32_t *__restrict__ rec_stage, const uint32_t *__restrict__ rec_last,
-                                                      const uint32_t *__restrict__ rec_minv, uint32_t log_m, uint32_t s, int mode, uint32_t first,
-                                                      uint32_t total, uint32_t *__restrict__ tbl) {
+ZK_D void ec_ladder(const XYZZ<F> &p, const uint32_t *rec, uint32_t *T, uint32_t *out) {
     typedef FieldOps<F> O;
     constexpr int NL = O::WORDS, PW = 4 * NL, HALVES = G::ENABLED ? 2 : 1, NW = G::ENABLED ? 33 : 65;
-    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x, t = first + slot;
-    if (t >= total) return;
-    const uint32_t half = 1u << (s - 1);
-    uint32_t j;
-    const uint32_t *rec;
-    if (mode == 0) {
-        const uint32_t k = t & (half - 1);
-        if (k == 0) return;
-        j = ((t >> (s - 1)) << s) + k + half;
-        rec = rec_stage + (size_t)(k << (log_m - s)) * REC_WORDS;
-    } else {
-        j = t;
-        rec = (t & half) ? rec_last + (size_t)(t & (half - 1)) * REC_WORDS : rec_minv;
-    }
-    uint32_t *pj = pts + (size_t)j * PW;
-    const XYZZ<F> p = xyzz_load<F>(pj);
-    if (p.is_inf()) return;
-    // the lane's table: e P for e = 1 .. 8 (and phi(e P) behind them); every entry is re-read from memory where it is needed again
-    uint32_t *T = tbl + (size_t)slot * (8 * HALVES) * PW;
     auto entry = [&](int e) { return T + (size_t)(e - 1) * PW; };
     {
         xyzz_store<F>(entry(1), p);
@@ -178,7 +149,53 @@ __global__ __launch_bounds__(64, G::ENABLED ? 2 : 1) void ec_ntt_mul_pass(uint32
             }
         }
     }
-    xyzz_store<F>(pj, acc);
+    xyzz_store<F>(out, acc);
+}
+
+// The multiplication pass.  mode 0: stage s (1-based) of the decimation-in-time network, lane t = butterfly t multiplies its lower
+// input v by w^(k stride) (k = 0: nothing to do); mode 1: the last stage of the INVERSE transform, lane t = point t, upper inputs take
+// 1/m, lower inputs w^k / m.  Lanes first .. first + gridDim.x * 64 of `total`; `tbl` holds 8 * HALVES points per lane of the launch.
+template <class F, class G>
+__global__ __launch_bounds__(64, G::ENABLED ? 2 : 1) void ec_ntt_mul_pass(uint32_t *__restrict__ pts, const uint32_t *__restrict__ rec_stage, const uint32_t *__restrict__ rec_last,
+                                                      const uint32_t *__restrict__ rec_minv, uint32_t log_m, uint32_t s, int mode, uint32_t first,
+                                                      uint32_t total, uint32_t *__restrict__ tbl) {
+    constexpr int NL = FieldOps<F>::WORDS, PW = 4 * NL, HALVES = G::ENABLED ? 2 : 1;
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x, t = first + slot;
+    if (t >= total) return;
+    const uint32_t half = 1u << (s - 1);
+    uint32_t j;
+    const uint32_t *rec;
+    if (mode == 0) {
+        const uint32_t k = t & (half - 1);
+        if (k == 0) return;
+        j = ((t >> (s - 1)) << s) + k + half;
+        rec = rec_stage + (size_t)(k << (log_m - s)) * REC_WORDS;
+    } else {
+        j = t;
+        rec = (t & half) ? rec_last + (size_t)(t & (half - 1)) * REC_WORDS : rec_minv;
+    }
+    uint32_t *pj = pts + (size_t)j * PW;
+    const XYZZ<F> p = xyzz_load<F>(pj);
+    if (p.is_inf()) return;
+    ec_ladder<F, G>(p, rec, tbl + (size_t)slot * (8 * HALVES) * PW, pj);
+}
+
+// out[i] = s_i P_i over the affine rows of a bases object (zkhip_bases_scale_*): lane `slot` of a launch takes point first + slot of `total`, reads
+// it from `aff` (internal form, 2 coordinates), runs the ladder over record first + slot and leaves the XYZZ product at pts[first + slot].  A
+// point at infinity gives infinity without a ladder; a zero scalar's record is all zero nibbles and leaves the accumulator where it starts.
+template <class F, class G>
+__global__ __launch_bounds__(64, G::ENABLED ? 2 : 1) void bases_scale_pass(const uint32_t *__restrict__ aff, const uint32_t *__restrict__ rec, uint32_t first,
+                                                                          uint32_t total, uint32_t *__restrict__ pts, uint32_t *__restrict__ tbl) {
+    constexpr int NL = FieldOps<F>::WORDS, PW = 4 * NL, HALVES = G::ENABLED ? 2 : 1;
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x, i = first + slot;
+    if (i >= total) return;
+    const XYZZ<F> p = XYZZ<F>::from_affine(affine_load<F>(aff + (size_t)i * (2 * NL)));
+    uint32_t *pi = pts + (size_t)i * PW;
+    if (p.is_inf()) {
+        xyzz_store<F>(pi, XYZZ<F>::infinity());
+        return;
+    }
+    ec_ladder<F, G>(p, rec + (size_t)i * REC_WORDS, tbl + (size_t)slot * (8 * HALVES) * PW, pi);
 }
 
 // the butterflies of stage s: (u, v) at distance 2^(s-1) -> (u + v, u - v)
@@ -254,6 +271,13 @@ __global__ __launch_bounds__(64) void ec_ntt_store_affine(const uint32_t *__rest
     }
 }
 
+// table slots: the lanes of one multiplication launch over `lanes` points (<= 1 GiB of tables, or "ec_ntt_table_lanes"; a pass over more lanes
+// runs in several launches)
+inline uint32_t ec_table_slots(const zkhip_ctx *ctx, size_t lanes, size_t slot_bytes) {
+    const size_t slot_cap = ctx->opt_ec_ntt_table_lanes ? (((size_t)ctx->opt_ec_ntt_table_lanes + 63) & ~(size_t)63) : ((size_t)1 << 30) / slot_bytes / 64 * 64;
+    return (uint32_t)std::max<size_t>(64, std::min<size_t>((lanes + 63) & ~(size_t)63, slot_cap));
+}
+
 struct EcNttBuffers {  // sizes in u32 words
     size_t pts_words, rec_words, tbl_words, aux_words;
     uint32_t *pts, *rec, *rec_last, *consts, *tbl, *aux;
@@ -273,10 +297,8 @@ template <class F, class U, class G, class Load, class Store>
 int ec_ntt_run(zkhip_ctx *ctx, size_t log_m, const uint64_t *omega, int inverse, size_t aux_words, Load load, Store store) {
     constexpr int NL = FieldOps<F>::WORDS, PW = 4 * NL, HALVES = G::ENABLED ? 2 : 1;
     const uint32_t m = 1u << log_m, ntw = std::max<uint32_t>(1, m / 2);
-    // table slots: the lanes of one multiplication launch (<= 1 GiB of tables; a pass over more lanes runs in several launches)
     const size_t slot_bytes = (size_t)8 * HALVES * PW * 4;
-    const size_t slot_cap = ctx->opt_ec_ntt_table_lanes ? (((size_t)ctx->opt_ec_ntt_table_lanes + 63) & ~(size_t)63) : ((size_t)1 << 30) / slot_bytes / 64 * 64;
-    const uint32_t slots = (uint32_t)std::max<size_t>(64, std::min<size_t>(((size_t)m + 63) & ~(size_t)63, slot_cap));
+    const uint32_t slots = ec_table_slots(ctx, m, slot_bytes);
     EcNttBuffers w = {(size_t)m * PW, (size_t)ntw * REC_WORDS, (size_t)slots * slot_bytes / 4, aux_words};
     ZK_TRY(ws_place(ctx, w));
     uint32_t *pts = w.pts, *rec = w.rec, *rec_last = w.rec_last, *consts = w.consts, *tbl = w.tbl;
@@ -284,11 +306,11 @@ int ec_ntt_run(zkhip_ctx *ctx, size_t log_m, const uint64_t *omega, int inverse,
     uint32_t one[8] = {1, 0, 0, 0, 0, 0, 0, 0};
     ZK_TRY(ws_upload(ctx, d_w, omega, 32));
     ZK_LAUNCH(ctx, "ec_ntt_setup", ec_ntt_setup<U>, dim3(1), dim3(64), 0, d_w, (uint32_t)log_m, inverse, consts);
-    ZK_LAUNCH(ctx, "ec_ntt_records", (ec_ntt_records<U, G>), grid_1d(ntw), dim3(256), 0, consts, (const uint32_t *)nullptr, ntw, rec);
+    ZK_LAUNCH(ctx, "ec_ntt_records", (ec_ntt_records<U, G>), grid_1d(ntw), dim3(256), 0, consts, (const uint32_t *)nullptr, 0u, ntw, rec);
     if (inverse && log_m > 0) {
         ZK_TRY(ws_upload(ctx, d_one, one, 32));
-        ZK_LAUNCH(ctx, "ec_ntt_records", (ec_ntt_records<U, G>), grid_1d(ntw), dim3(256), 0, consts, consts + U::NL, ntw, rec_last);
-        ZK_LAUNCH(ctx, "ec_ntt_records", (ec_ntt_records<U, G>), dim3(1), dim3(256), 0, d_one, consts + U::NL, 1u, rec_minv);
+        ZK_LAUNCH(ctx, "ec_ntt_records", (ec_ntt_records<U, G>), grid_1d(ntw), dim3(256), 0, consts, consts + U::NL, 0u, ntw, rec_last);
+        ZK_LAUNCH(ctx, "ec_ntt_records", (ec_ntt_records<U, G>), dim3(1), dim3(256), 0, d_one, consts + U::NL, 0u, 1u, rec_minv);
     }
     ZK_TRY(load(pts));
     for (uint32_t s = 1; s <= log_m; ++s) {
@@ -338,7 +360,60 @@ int bases_lagrange_t(zkhip_ctx *ctx, const zkhip_bases *src, size_t offset, size
         });
 }
 
+// ---- zkhip_bases_scale_dev / zkhip_bases_scale_geometric: slot 0 of dst <- s_i * (row offset + i of src), i < n
+struct ScaleBuffers {  // sizes in u32 words
+    size_t pts_words, rec_words, tbl_words, pre_words;
+    uint32_t *pts, *rec, *consts, *tbl, *pre;
+    template <class Arena>
+    void layout(Arena &a) {
+        a.take(pts, pts_words);
+        a.take(rec, rec_words);
+        a.take(consts, 32);
+        a.take(tbl, tbl_words);
+        a.take(pre, pre_words);
+    }
+};
+// The records come from d_scalars (n resident 8-word scalars) or, when that is null, are those of coeff ratio^(e0 + i) (coeff nullable: 1).
+template <class F, class U, class G>
+int bases_scale_t(zkhip_ctx *ctx, const zkhip_bases *src, size_t offset, size_t n, const uint32_t *d_scalars, const uint64_t *ratio, const uint64_t *coeff,
+                  uint32_t e0, zkhip_bases *dst) {
+    constexpr int NL = FieldOps<F>::WORDS, PW = 4 * NL, HALVES = G::ENABLED ? 2 : 1;
+    const uint32_t total = (uint32_t)n, chunk = affine_chunk(n);
+    const size_t slot_bytes = (size_t)8 * HALVES * PW * 4;
+    const uint32_t slots = ec_table_slots(ctx, n, slot_bytes);
+    ScaleBuffers w = {n * PW, n * REC_WORDS, (size_t)slots * slot_bytes / 4, n * NL};
+    ZK_TRY(ws_place(ctx, w));
+    if (d_scalars) {
+        ZK_LAUNCH(ctx, "scale_records_from_scalars", (scale_records_from_scalars<U, G>), grid_1d(n), dim3(256), 0, d_scalars, total, w.rec);
+    } else {
+        ZK_TRY(ws_upload(ctx, w.consts, ratio, 32));
+        if (coeff) ZK_TRY(ws_upload(ctx, w.consts + 8, coeff, 32));
+        ZK_LAUNCH(ctx, "scale_records_geometric", (ec_ntt_records<U, G>), grid_1d(n), dim3(256), 0, w.consts, coeff ? w.consts + 8 : (const uint32_t *)nullptr, e0,
+                  total, w.rec);
+    }
+    const uint32_t *in = src->d + offset * src->stride_u32;  // slot 0: the points themselves, whatever tables the object carries
+    for (uint32_t first = 0; first < total; first += slots) {
+        const uint32_t lanes = std::min(slots, total - first);
+        ZK_LAUNCH(ctx, "bases_scale_pass", (bases_scale_pass<F, G>), grid_1d(lanes, 64), dim3(64), 0, in, w.rec, first, total, w.pts, w.tbl);
+    }
+    ZK_LAUNCH(ctx, "ec_ntt_store_affine", ec_ntt_store_affine<F>, grid_1d((n + chunk - 1) / chunk, 64), dim3(64), 0, w.pts, total, chunk, dst->d.p, w.pre);
+    return ZKHIP_OK;
+}
+
 }  // namespace
+
+int zk_bases_scale(zkhip_ctx *ctx, const zkhip_bases *src, size_t offset, size_t n, const uint32_t *d_scalars, const uint64_t *ratio, const uint64_t *coeff,
+                   uint32_t e0, zkhip_bases *dst) {
+    if (dst->n != n || dst->stride_u32 != src->stride_u32 || dst->group != src->group) return ZKHIP_ERR_INVALID;
+    if (src->group == GROUP_G1)
+        return g1_dispatch(src->curve, [&](auto c) -> int {
+            using C = decltype(c);
+            return bases_scale_t<typename C::F, typename C::U, typename C::Glv>(ctx, src, offset, n, d_scalars, ratio, coeff, e0, dst);
+        });
+    if (src->curve == CURVE_BLS12_381) return bases_scale_t<CurveTraits<CURVE_BLS12_381, GROUP_G2>::F, BlsFrU, NoGlv>(ctx, src, offset, n, d_scalars, ratio, coeff, e0, dst);
+    if (src->curve == CURVE_BN254) return bases_scale_t<CurveTraits<CURVE_BN254, GROUP_G2>::F, BnFrU, NoGlv>(ctx, src, offset, n, d_scalars, ratio, coeff, e0, dst);
+    return ZKHIP_ERR_INVALID;
+}
 
 int zk_bases_lagrange(zkhip_ctx *ctx, const zkhip_bases *src, size_t offset, size_t log_m, const uint64_t *omega, bool glv, zkhip_bases *dst) {
     if (src->group != GROUP_G1 || dst->n != (size_t)1 << log_m || dst->stride_u32 != src->stride_u32) return ZKHIP_ERR_INVALID;

@@ -146,4 +146,36 @@ ZK_HD uint32_t glv_split(const uint32_t *k, uint32_t *k1, uint32_t *k2) {
     return signs;
 }
 
+// ---- the window record of a scalar: what the fixed 4-bit ladder of ecntt.hip reads (the group DFT's twiddles, zkhip_bases_scale_*'s scalars)
+constexpr int REC_WORDS = 12;  // GLV  [0..4] nibbles of |k1|, [5..9] nibbles of |k2|, [10] bit h = half h negative
+                               // plain [0..8] nibbles of k (65 used), [10] = 0
+
+// signed 4-bit windows of an unsigned magnitude: digit w in [-8, 7] as a two's-complement nibble, sum_w d_w 16^w = mag
+ZK_HD void recode_nibbles(uint32_t *out, int out_words, const uint32_t *mag, int mag_words, int windows) {
+    for (int i = 0; i < out_words; ++i) out[i] = 0;
+    uint32_t carry = 0;
+    for (int w = 0; w < windows; ++w) {
+        const int word = w >> 3;
+        uint32_t d = (word < mag_words ? (mag[word] >> ((w & 7) * 4)) & 15u : 0u) + carry;
+        carry = d >= 8 ? 1 : 0;  // d - 16 in [-8, 0]: the nibble (d & 15) read as two's complement
+        out[word] |= (d & 15u) << ((w & 7) * 4);
+    }
+}
+
+// k (8 words, below r) -> its record: the GLV split (G1) and the signed-nibble recoding
+template <class G>
+ZK_HD void scalar_record(uint32_t *out, const uint32_t *k) {
+    if constexpr (G::ENABLED) {
+        uint32_t k1[6], k2[6];
+        const uint32_t signs = glv_split<G>(k, k1, k2);
+        recode_nibbles(out, 5, k1, 6, 33);
+        recode_nibbles(out + 5, 5, k2, 6, 33);
+        out[10] = signs;
+        out[11] = 0;
+    } else {
+        recode_nibbles(out, 9, k, 8, 65);
+        out[9] = out[10] = out[11] = 0;
+    }
+}
+
 }  // namespace zkhip

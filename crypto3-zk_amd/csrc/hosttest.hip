@@ -184,6 +184,20 @@ int zkt_glv_consts(int curve, uint32_t *out42) {
     }) == 0 ? 0 : -1;
 }
 
+// The window record the scaling ladder reads (glv.hpp: scalar_record) of ANY 8-word scalar, as ecntt.hip's scale_records_from_scalars builds it: the
+// scalar reduced mod r (fu_reduce; k_out, 8 words), then -- glv != 0 -- split by the curve's endomorphism and recoded into 33 signed nibbles per half,
+// or -- glv = 0, the G2 ladder -- recoded into 65 signed nibbles.  rec: REC_WORDS words.
+int zkt_scale_record(int curve, int glv, const uint32_t *scalar, uint32_t *k_out, uint32_t *rec) {
+    if (!scalar || !k_out || !rec) return -1;
+    return g1_dispatch(curve, [&](auto c) -> int {
+        using C = decltype(c);
+        fu_pack<typename C::U>(k_out, fu_reduce(fu_unpack<typename C::U>(scalar)));
+        if (glv) scalar_record<typename C::Glv>(rec, k_out);
+        else scalar_record<NoGlv>(rec, k_out);
+        return 0;
+    }) == 0 ? 0 : -1;
+}
+
 // SHA2-256 of a byte string: what zkhip_sha256_host computes
 int zkt_sha256_bytes(const uint8_t *msg, size_t len, uint8_t *digest) {
     if (!digest || (!msg && len)) return -1;

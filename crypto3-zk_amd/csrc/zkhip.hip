@@ -360,7 +360,7 @@ int zkhip_memcpy_2d_d2d_async(zkhip_ctx *ctx, void *dst, size_t dst_pitch, const
 }
 
 // ---- bases ------------------------------------------------------------------------------------------
-static int bases_alloc(zkhip_ctx *ctx, int curve, int group, size_t n, std::unique_ptr<zkhip_bases> &out) {
+static int bases_alloc(zkhip_ctx *ctx, int curve, int group, size_t n, std::unique_ptr<zkhip_bases> &out, bool tables = true) {
     if (!zk_curve_group_known(curve, group)) return ZKHIP_ERR_INVALID;
     std::unique_ptr<zkhip_bases> b(new zkhip_bases());
     b->curve = curve;
@@ -368,7 +368,7 @@ static int bases_alloc(zkhip_ctx *ctx, int curve, int group, size_t n, std::uniq
     b->n = n;
     b->stride_u32 = zk_point_words(curve, group);
     const bool shard = ctx->opt_msm_shard_world > 1;
-    if (ctx->opt_msm_precompute && n >= (size_t)ctx->opt_msm_precompute_min) {
+    if (tables && ctx->opt_msm_precompute && n >= (size_t)ctx->opt_msm_precompute_min) {
         b->c_tab = ctx->opt_msm_window_bits > 0 ? std::max(2, std::min(ZK_MSM_MAX_C, ctx->opt_msm_window_bits)) : zk_msm_auto_window(n);
         b->ntab = msm_windows(zk_scalar_bits(curve), b->c_tab);
         if (shard) {
@@ -580,6 +580,36 @@ int zkhip_bases_lagrange(zkhip_ctx *ctx, const zkhip_bases *b, size_t offset, si
 // the other arm of the measurement that chose GLV (tools/bench_lagrange.py, DESIGN.md section on the IPA).
 int zkhip_bench_bases_lagrange_plain(zkhip_ctx *ctx, const zkhip_bases *b, size_t offset, size_t log_m, const uint64_t *omega, zkhip_bases **out) {
     return bases_lagrange(ctx, b, offset, log_m, omega, false, out);
+}
+
+// out[i] = s_i * b[offset + i] (include/zkhip.h): every refusal before any launch, the products into slot 0 of a new object (ecntt.hip), then the
+// window tables when the caller asked for them.  d_scalars null: the geometric scalars coeff ratio^(e0 + i).
+static int bases_scale(zkhip_ctx *ctx, const zkhip_bases *b, size_t offset, size_t n, const void *d_scalars, const uint64_t *ratio, const uint64_t *coeff,
+                       uint64_t e0, int flags, zkhip_bases **out) {
+    if (out) *out = nullptr;
+    if (!b || !out || (!d_scalars && !ratio)) return ZKHIP_ERR_INVALID;
+    ZK_ARGS(ctx, b->curve);
+    if (!zk_curve_group_known(b->curve, b->group) || (flags & ~ZKHIP_SCALE_TABLES)) return ZKHIP_ERR_INVALID;
+    if (!d_scalars && (!zk_fr_canonical(b->curve, ratio) || (coeff && !zk_fr_canonical(b->curve, coeff)))) return ZKHIP_ERR_INVALID;
+    if (n == 0 || n >= ((size_t)1 << 31) || offset > b->n || n > b->n - offset) return ZKHIP_ERR_RANGE;
+    if (!d_scalars && (e0 > ((uint64_t)1 << 32) || n > ((uint64_t)1 << 32) - e0)) return ZKHIP_ERR_RANGE;
+    ZK_TRY(check_device(ctx));
+    std::unique_ptr<zkhip_bases> r;
+    ZK_TRY(bases_alloc(ctx, b->curve, b->group, n, r, (flags & ZKHIP_SCALE_TABLES) != 0));
+    ZK_TRY(zk_bases_scale(ctx, b, offset, n, (const uint32_t *)d_scalars, ratio, coeff, (uint32_t)e0, r.get()));
+    return bases_finish(ctx, r, out);
+}
+
+int zkhip_bases_scale_dev(zkhip_ctx *ctx, const zkhip_bases *b, size_t offset, size_t n, const void *d_scalars, int flags, zkhip_bases **out) {
+    if (out) *out = nullptr;
+    if (!d_scalars) return ZKHIP_ERR_INVALID;
+    return bases_scale(ctx, b, offset, n, d_scalars, nullptr, nullptr, 0, flags, out);
+}
+int zkhip_bases_scale_geometric(zkhip_ctx *ctx, const zkhip_bases *b, size_t offset, size_t n, const uint64_t *ratio, const uint64_t *coeff, uint64_t first_exponent,
+                                int flags, zkhip_bases **out) {
+    if (out) *out = nullptr;
+    if (!ratio) return ZKHIP_ERR_INVALID;
+    return bases_scale(ctx, b, offset, n, nullptr, ratio, coeff, first_exponent, flags, out);
 }
 
 int zkhip_bases_download(zkhip_ctx *ctx, const zkhip_bases *b, size_t offset, size_t n, uint64_t *affine_xy, uint8_t *is_infinity) {

@@ -412,6 +412,20 @@ public:
         check(zkhip_bases_lagrange(ctx_->get(), b_, offset, log_m, w, &r.b_), "zkhip_bases_lagrange", ctx_->get());
         return r;
     }
+    /// out[i] = coeff * ratio^(first_exponent + i) * row[offset + i], i < n (coeff == nullptr: 1), as a new object (zkhip_bases_scale_geometric:
+    /// one scalar multiplication per point on the device); without window tables unless flags has ZKHIP_SCALE_TABLES
+    device_bases scale_geometric(std::size_t offset, std::size_t n, const typename adapter::scalar_value_type &ratio,
+                                 const typename adapter::scalar_value_type *coeff = nullptr, std::uint64_t first_exponent = 0, int flags = 0) const {
+        std::uint64_t r[4], c[4];
+        adapter::scalar_to_limbs(ratio, r);
+        if (coeff) adapter::scalar_to_limbs(*coeff, c);
+        device_bases out;
+        out.ctx_ = ctx_;
+        out.size_ = n;
+        check(zkhip_bases_scale_geometric(ctx_->get(), b_, offset, n, r, coeff ? c : nullptr, first_exponent, flags, &out.b_), "zkhip_bases_scale_geometric",
+              ctx_->get());
+        return out;
+    }
     /// host copies of all entries as group values (one download)
     std::vector<typename std::conditional<Group == ZKHIP_G1, typename adapter::g1_value_type, typename adapter::g2_value_type>::type> download() const {
         typedef typename std::conditional<Group == ZKHIP_G1, typename adapter::g1_value_type, typename adapter::g2_value_type>::type G;

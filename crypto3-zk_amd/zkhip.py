@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 BLS12_381, BN254, PALLAS, VESTA = 0, 1, 2, 3    # an id names a group and ITS scalar field: Fr of PALLAS is the Vesta base field and vice versa (zkhip.h)
 G1, G2 = 1, 2
 HASH_SHA2_256 = 0
+SCALE_TABLES = 1  # zkhip_scale_flags
 _FQ = {BLS12_381: 6, BN254: 4, PALLAS: 4, VESTA: 4}
 
 EXPORTS = [
@@ -21,7 +22,7 @@ EXPORTS = [
     "zkhip_domain_choice", "zkhip_domain_fft_dev", "zkhip_domain_lagrange_dev",
     "zkhip_r1cs_upload", "zkhip_r1cs_free", "zkhip_r1cs_set_domain", "zkhip_r1cs_domain_size", "zkhip_r1cs_domain_kind", "zkhip_groth16_scratch_bytes", "zkhip_groth16_witness_h_dev", "zkhip_groth16_witness_h_domain_dev", "zkhip_fr_gather_dev", "zkhip_poly_resize_dev", "zkhip_fri_fold_dev", "zkhip_fri_leaves_dev", "zkhip_ec_ntt_dev",
     "zkhip_fr_vec_op_dev", "zkhip_fr_vec_affine_dev", "zkhip_fr_vec_mul_div_dev", "zkhip_fr_vec_prod_dev", "zkhip_poly_shift_dev", "zkhip_poly_eval_dev", "zkhip_poly_div_linear_dev", "zkhip_poly_div_vanishing_dev", "zkhip_poly_lincomb_dev", "zkhip_perm_grand_product_dev", "zkhip_lookup_grand_product_dev", "zkhip_lookup_sort_dev", "zkhip_perm_factor_products_dev", "zkhip_gate_eval_dev",
-    "zkhip_bases_fold", "zkhip_bases_lagrange", "zkhip_fr_inner_product_dev", "zkhip_fr_powers_lincomb_dev", "zkhip_fr_challenge_products_dev",
+    "zkhip_bases_fold", "zkhip_bases_scale_dev", "zkhip_bases_scale_geometric", "zkhip_bases_lagrange", "zkhip_fr_inner_product_dev", "zkhip_fr_powers_lincomb_dev", "zkhip_fr_challenge_products_dev",
     "zkhip_merkle_build_dev", "zkhip_merkle_build_fri_dev", "zkhip_merkle_leaves", "zkhip_merkle_depth", "zkhip_merkle_root", "zkhip_merkle_digests", "zkhip_merkle_paths",
     "zkhip_merkle_free", "zkhip_pow_grind", "zkhip_sha256_host",
     "zkhip_group_init", "zkhip_group_destroy", "zkhip_group_size", "zkhip_group_ctx", "zkhip_group_last_error", "zkhip_group_set_transport", "zkhip_group_transport",
@@ -290,6 +291,23 @@ class Context:
         self._check(self.lib.zkhip_bases_fold(self.h, bases.h, ctypes.c_size_t(offset_lo), ctypes.c_size_t(offset_hi), ctypes.c_size_t(half),
                                               _p(_u64(c).reshape(4)), ctypes.byref(h)), "zkhip_bases_fold")
         return Bases(self, h, bases.curve, bases.group, half)
+
+    def bases_scale_dev(self, bases: "Bases", offset: int, n: int, d_scalars: int, flags: int = 0) -> "Bases":
+        """out[i] = s_i * bases[offset + i], i < n, s_i the i-th of n scalars resident at d_scalars (taken mod r): a new bases object, without
+        window tables unless flags has SCALE_TABLES (zkhip_bases_scale_dev)"""
+        h = ctypes.c_void_p()
+        self._check(self.lib.zkhip_bases_scale_dev(self.h, bases.h, ctypes.c_size_t(offset), ctypes.c_size_t(n), ctypes.c_void_p(d_scalars or None),
+                                                   ctypes.c_int(flags), ctypes.byref(h)), "zkhip_bases_scale_dev")
+        return Bases(self, h, bases.curve, bases.group, n)
+
+    def bases_scale_geometric(self, bases: "Bases", offset: int, n: int, ratio, coeff=None, first_exponent: int = 0, flags: int = 0) -> "Bases":
+        """out[i] = coeff * ratio^(first_exponent + i) * bases[offset + i], i < n (coeff None: 1): a new bases object, without window tables
+        unless flags has SCALE_TABLES (zkhip_bases_scale_geometric)"""
+        h = ctypes.c_void_p()
+        c = _u64(coeff).reshape(4) if coeff is not None else None
+        self._check(self.lib.zkhip_bases_scale_geometric(self.h, bases.h, ctypes.c_size_t(offset), ctypes.c_size_t(n), _p(_u64(ratio).reshape(4)), _p(c),
+                                                         ctypes.c_uint64(first_exponent), ctypes.c_int(flags), ctypes.byref(h)), "zkhip_bases_scale_geometric")
+        return Bases(self, h, bases.curve, bases.group, n)
 
     def bases_lagrange(self, bases: "Bases", offset: int, log_m: int, omega) -> "Bases":
         """out[j] = (1/m) sum_i omega^(-i j) bases[offset + i], i, j < m = 2^log_m: the Lagrange basis of that range of an SRS, a new bases

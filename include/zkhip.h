@@ -444,6 +444,34 @@ int zkhip_poly_lincomb_dev(zkhip_ctx *ctx, int curve, size_t count, const void *
  * would cost more than they save; an MSM over it combines the windows by the Horner pass.  Free it with zkhip_bases_free. */
 int zkhip_bases_fold(zkhip_ctx *ctx, const zkhip_bases *b, size_t offset_lo, size_t offset_hi, size_t half, const uint64_t *c /* 4 limbs */,
                      zkhip_bases **out);
+/* ---- a different scalar per resident point: the powers-of-tau contribution and the Groth16 MPC phase 2 ----
+ * powers_of_tau_accumulator::transform (commitments/detail/polynomial/powers_of_tau/accumulator.hpp:89-121: naive_batch_exp /
+ * naive_batch_exp_with_coeff over tau_powers_g1, tau_powers_g2, alpha_tau_powers_g1, beta_tau_powers_g1 with the exponents tau^i,
+ * alpha tau^i, beta tau^i) and the delta^-1 scaling of H_query / L_query in r1cs_gg_ppzksnark's mpc contribution
+ * (crs_operations.hpp:116-123) are one operation: a NEW bases object of n points,
+ *     out[i] = s_i * b[offset + i],   0 < n < 2^31,
+ * one variable-base scalar multiplication per point (a fixed 4-bit signed-window ladder over a per-point table; on G1 the scalar is
+ * split by the curve's endomorphism, GLV).  G1 of every curve id, G2 of ZKHIP_BLS12_381 and ZKHIP_BN254 (a bases object of ZKHIP_G2 with
+ * a Pasta id cannot be built: ZKHIP_ERR_INVALID).  b is left as it is and only its points are read, whatever window tables it carries.  A
+ * point at infinity or a scalar of zero gives the point at infinity.  `out` holds affine points in the internal form and, as for
+ * zkhip_bases_fold, carries NO window tables -- a ceremony's output is downloaded or scaled again, and tables would cost more than they
+ * save -- unless ZKHIP_SCALE_TABLES is set in `flags`: then it carries them exactly as a zkhip_bases_upload of the same points would
+ * under the context's current "msm_precompute" / "msm_window_bits" options.  Like every constructor of bases both calls return with the
+ * stream drained; free with zkhip_bases_free.  "ec_ntt_table_lanes" applies as for zkhip_ec_ntt_dev: a range of more points than one
+ * launch holds tables for runs as several launches, with the same result.
+ *   zkhip_bases_scale_dev        s_i = the i-th of n scalars resident on the device (4 limbs each, 16-byte aligned).  A scalar that is not
+ *                                below r is taken mod r, exactly as zkhip_msm_dev takes it (the reference's field type cannot hold one).
+ *   zkhip_bases_scale_geometric  s_i = coeff * ratio^(first_exponent + i), ratio and coeff on the host (4 limbs, canonical; coeff NULL: 1),
+ *                                first_exponent + n <= 2^32.  ratio^0 = 1 also for ratio = 0, as the reference's running product has it.
+ *                                ratio = 1 is the one-scalar case (every point times coeff: delta^-1).
+ * Errors, before anything is launched, with *out = null: a null ctx / b / out / d_scalars / ratio, an unknown curve or an unknown bit of
+ * `flags` -> ZKHIP_ERR_INVALID; ratio or coeff not below r -> ZKHIP_ERR_INVALID; n = 0, n >= 2^31, offset + n > zkhip_bases_size(b) or
+ * first_exponent + n > 2^32 -> ZKHIP_ERR_RANGE. */
+enum zkhip_scale_flags { ZKHIP_SCALE_TABLES = 1 };
+int zkhip_bases_scale_dev(zkhip_ctx *ctx, const zkhip_bases *b, size_t offset, size_t n, const void *d_scalars /* device, n x 4 canonical */, int flags,
+                          zkhip_bases **out);
+int zkhip_bases_scale_geometric(zkhip_ctx *ctx, const zkhip_bases *b, size_t offset, size_t n, const uint64_t *ratio /* 4 limbs */,
+                                const uint64_t *coeff /* nullable = 1 */, uint64_t first_exponent, int flags, zkhip_bases **out);
 /* kimchi_pedersen::params_type::add_lagrange_basis (kimchi_pedersen.hpp:92-105): a NEW bases object of m = 2^log_m points,
  *     out[j] = (1/m) sum_{i<m} omega^(-i j) b[offset + i]
  * omega = the primitive m-th root of unity of the curve's scalar field (canonical, 4 limbs): the inverse DFT over group elements of a
