@@ -1,6 +1,6 @@
 // Curve-independent host side of the MSM family: window selection, dispatch to the per-(curve, group) translation
-// units (msm_bls_g1.hip, msm_bls_g2.hip, msm_bn_g1.hip, msm_bn_g2.hip, msm_pallas_g1.hip, msm_vesta_g1.hip; kernels and per-call logic in msm_core.hpp),
-// batching, and the optional HIP-graph replay of repeated calls.
+// units (msm_bls_g1.hip, msm_bls_g2.hip, msm_bn_g1.hip, msm_bn_g2.hip, msm_pallas_g1.hip, msm_vesta_g1.hip; kernels and per-call logic in msm_core.hpp,
+// the field-free entries stage they all call in msm_entries.hip), batching, and the optional HIP-graph replay of repeated calls.
 #include <algorithm>
 #include <cstdlib>
 #include <string>
