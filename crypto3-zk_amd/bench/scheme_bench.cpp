@@ -513,6 +513,134 @@ int zkhip_bench_lpc_proof_eval_grinding(int device, size_t log_n, size_t cols, s
     }
 }
 
+/* Whole opening proofs (hip/lpc.hpp: proof_eval_full = proof_eval + query_phase) on the instance above, device tree builder, SHA2-256 transcript,
+ * `lambda` queries, next to the path a caller of proof_eval alone has to take for the same answers: download every round polynomial
+ * (fri_round_polynomial) and every coefficient form (coefficients), evaluate every committed polynomial at the 2 lambda query points on the host.
+ *   ms       steps x {proof_eval alone, proof_eval_full, query_phase alone -- timed by part: re-extension, gathers, paths, host part}  (7 per step);
+ *   caller   {download ms of the round polynomials, download ms of the coefficient forms, host evaluation ms of `eval_polys` of the cols
+ *            polynomials on ONE thread, host evaluation ms of all cols polynomials on `threads` threads}, measured once (eval_polys 0: the
+ *            one-thread figure is skipped);
+ *   launches (nullable, cap bytes) the profiler's dump -- "name ms count" lines -- of the kernels the LAST step's query_phase launched (that step
+ *            runs with the per-kernel events on: keep it out of a median);
+ *   *verified: verify_eval accepted the last proof. */
+int zkhip_bench_lpc_query_phase(int device, size_t log_n, size_t cols, size_t expand, int steps, size_t lambda, unsigned threads, size_t eval_polys, double *ms,
+                                double *caller, char *launches, size_t cap, int *verified) {
+    try {
+        typedef lpc_commitment_scheme_hip<C, sha256_transcript<C>, device_merkle_builder<>> base_type;
+        struct scheme_type : base_type {    // the scheme with its query-phase stopwatch in reach
+            using base_type::base_type;
+            void time_query_phase(bool on) { this->_time_query_phase = on; }
+            const typename base_type::query_phase_times &last_query_times() const { return this->_last_query_times; }
+        };
+        const size_t n = (size_t)1 << log_n;
+        context ctx(device);
+        fri_params_hip<C> params;
+        params.max_degree = n - 1;
+        params.log_domain = log_n + expand;
+        params.step_list.assign(log_n + expand - 4, 1);
+        params.root_of_unity = bls_root;
+        params.lambda = lambda;
+        splitmix sm {15};
+        std::vector<polynomial_dfs<C>> polys(cols);
+        for (auto &p : polys) {
+            p.values.resize(n);
+            for (auto &v : p.values) v = sm.nonzero();
+        }
+        std::vector<std::reference_wrapper<const polynomial_dfs<C>>> lent(polys.begin(), polys.end());
+        const Fr y = sm.nonzero(), w = bls_root(log_n);
+        scheme_type scheme(ctx, params, device_merkle_builder<>());
+        scheme.append_to_batch(0, lent);
+        const auto root = scheme.commit(0);
+        scheme.append_eval_point(0, y);
+        scheme.append_eval_point(0, y * w);
+        scheme_type::proof_type proof;
+        for (int rep = 0; rep < steps; ++rep) {
+            double *out = ms + 7 * rep;
+            {
+                sha256_transcript<C> tr;
+                const auto t0 = std::chrono::steady_clock::now();
+                proof = scheme.proof_eval(tr);
+                out[0] = ms_since(t0);
+            }
+            {
+                sha256_transcript<C> tr;
+                const auto t0 = std::chrono::steady_clock::now();
+                proof = scheme.proof_eval_full(tr);
+                out[1] = ms_since(t0);
+            }
+            {
+                sha256_transcript<C> tr;
+                proof = scheme.proof_eval(tr);
+                ctx.sync();
+                scheme.time_query_phase(true);
+                const bool profile = launches && rep == steps - 1;
+                if (profile) {
+                    check(zkhip_profile_enable(ctx.get(), 1), "zkhip_profile_enable", ctx.get());
+                    check(zkhip_profile_reset(ctx.get()), "zkhip_profile_reset", ctx.get());
+                }
+                const auto t0 = std::chrono::steady_clock::now();
+                scheme.query_phase(tr, proof);
+                out[2] = ms_since(t0);
+                if (profile) {
+                    zkhip_profile_dump(ctx.get(), launches, cap);
+                    check(zkhip_profile_enable(ctx.get(), 0), "zkhip_profile_enable", ctx.get());
+                }
+                scheme.time_query_phase(false);
+                out[3] = scheme.last_query_times().reextend_ms;
+                out[4] = scheme.last_query_times().gather_ms;
+                out[5] = scheme.last_query_times().paths_ms;
+                out[6] = scheme.last_query_times().host_ms;
+            }
+        }
+        {
+            sha256_transcript<C> tr;
+            std::map<std::size_t, scheme_type::commitment_type> commitments;
+            commitments[0] = root;
+            *verified = scheme.verify_eval(proof, commitments, tr) ? 1 : 0;
+        }
+        /* the caller's path: everything the query phase reads, brought to the host, and the evaluations at the query points */
+        auto t0 = std::chrono::steady_clock::now();
+        std::size_t sink = 0;
+        for (std::size_t i = 1; i < params.step_list.size(); ++i) sink += scheme.fri_round_polynomial(i).values.size();
+        caller[0] = ms_since(t0);
+        t0 = std::chrono::steady_clock::now();
+        std::vector<std::vector<Fr>> coeffs(cols);
+        for (std::size_t p = 0; p < cols; ++p) coeffs[p] = scheme.coefficients(0, p);
+        caller[1] = ms_since(t0);
+        std::vector<Fr> at(2 * lambda);
+        for (auto &x : at) x = sm.nonzero();
+        std::vector<Fr> values(cols * at.size());
+        auto evaluate = [&](std::size_t lo, std::size_t hi) {    // math::polynomial::evaluate: Horner, (polynomial, point) pairs [lo, hi)
+            for (std::size_t k = lo; k < hi; ++k) {
+                const std::vector<Fr> &c = coeffs[k / at.size()];
+                const Fr &x = at[k % at.size()];
+                Fr acc = Fr::zero();
+                for (std::size_t j = c.size(); j-- > 0;) acc = acc * x + c[j];
+                values[k] = acc;
+            }
+        };
+        caller[2] = 0;
+        if (eval_polys) {
+            t0 = std::chrono::steady_clock::now();
+            evaluate(0, std::min(eval_polys, cols) * at.size());
+            caller[2] = ms_since(t0);
+        }
+        t0 = std::chrono::steady_clock::now();
+        {
+            std::vector<std::thread> th;
+            const std::size_t total = values.size();
+            for (unsigned k = 0; k < threads; ++k) th.emplace_back(evaluate, total * k / threads, total * (k + 1) / threads);
+            for (auto &t : th) t.join();
+        }
+        caller[3] = ms_since(t0);
+        if (sink == 0 || values.empty()) return -2;
+        return 0;
+    } catch (const std::exception &e) {
+        fprintf(stderr, "zkhip_bench_lpc_query_phase: %s\n", e.what());
+        return -1;
+    }
+}
+
 /* placeholder's quotient chain at size (hip/placeholder_quotient.hpp; prover.hpp:220-277, 314-317, gates_argument.hpp:203-216), every
  * column RESIDENT: a gate theta * q * w0 * w1(next row) * w2 over the 4n-point extended domain (4 resizes + one 4-way product + the
  * mask), a second part w1 * w2 - w3 over 2n points, F_consolidated = alpha_0 G + alpha_1 F1, its coefficients, the division by

@@ -5,10 +5,15 @@
 //                                fri_leaf_gather's index arithmetic (poly.hip) and hashes them as it goes -- the leaf layout is never written
 //   zkhip_merkle_build_dev       the tree over a leaf layout that already lies on the device
 //   zkhip_merkle_root / _digests / _paths   what a transcript and a query phase read
+//   zkhip_fri_query_dev / zkhip_merkle_paths_multi   the FRI query phase's answers (basic_fri.hpp:747-930): the evaluation pairs calculate_s walks
+//                                from every query index over several sets of resident polynomials, and the paths of every query in several
+//                                trees -- each one launch and one copy to the host
 //
 // Conventions: include/zkhip.h ("Merkle trees") and sha256.hpp.  The tree is one array of (2L - 1) digests of 32 bytes in their external
 // byte order: the L leaf digests, then every level above, the root last; level l starts at digest 2L - (2L >> l).
+#include <algorithm>
 #include <new>
+#include <vector>
 
 #include "ctx.hpp"
 #include "sha256.hpp"
@@ -76,6 +81,57 @@ __global__ __launch_bounds__(256) void merkle_path_gather(const uint4 *__restric
     out[t] = tree[2 * (merkle_level_offset(leaves, l) + sibling) + (t & 1)];
 }
 
+// zkhip_fri_query_dev: one set of resident evaluations as the gather sees it; `end` closes the set's range of output elements
+struct FriQuerySet {
+    const uint4 *polys;
+    uint32_t log_d, batch, step;
+    size_t end;
+};
+
+// One lane per 16 bytes of the output (neighbouring lanes write neighbouring halves of an element).  Element e of set t is
+// [q][p][i][side]: with x = indices[q] mod D, s_0 = x and s_(2^l + j) = s_j + D / (4 * 2^l) mod D as in merkle_fri_leaf_hash, the pair i is
+// (f[min(s_i, s_i + D/2 mod D)], f[max(...)]) (calculate_s and the ind0 / ind1 rule, basic_fri.hpp:585-614, 815-818).
+__global__ __launch_bounds__(256) void fri_query_gather(const FriQuerySet *__restrict__ sets, uint32_t n_sets, const uint64_t *__restrict__ indices, size_t total,
+                                                        uint4 *__restrict__ out) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const size_t e = t >> 1;
+    uint32_t u = 0;
+    while (u + 1 < n_sets && e >= sets[u].end) ++u;
+    const FriQuerySet set = sets[u];
+    const size_t local = e - (u ? sets[u - 1].end : 0), per_query = (size_t)set.batch << set.step;
+    const size_t q = local / per_query, rem = local % per_query;
+    const size_t p = rem >> set.step, i = (rem & (((size_t)1 << set.step) - 1)) >> 1, side = rem & 1;
+    const size_t D = (size_t)1 << set.log_d;
+    size_t s = (size_t)indices[q] & (D - 1);
+    for (uint32_t l = 0; l + 1 < set.step; ++l)
+        if ((i >> l) & 1) s += D >> (2 + l);
+    s &= D - 1;
+    const size_t s2 = (s + (D >> 1)) & (D - 1);
+    const size_t src = side ? max(s, s2) : min(s, s2);
+    out[t] = set.polys[2 * ((p << set.log_d) + src) + (t & 1)];
+}
+
+// zkhip_merkle_paths_multi: one tree as the gather sees it; `end` closes the tree's range of output digests
+struct PathTree {
+    const uint4 *d;
+    size_t leaves, depth, end;
+};
+
+// one lane per 16 bytes of the output: digest (k * depth + l) of tree t is the sibling of leaf (indices[k] mod leaves)'s ancestor on level l
+__global__ __launch_bounds__(256) void merkle_path_gather_multi(const PathTree *__restrict__ trees, uint32_t n_trees, const uint64_t *__restrict__ indices,
+                                                                size_t total, uint4 *__restrict__ out) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const size_t node = t >> 1;
+    uint32_t u = 0;
+    while (u + 1 < n_trees && node >= trees[u].end) ++u;  // a one-leaf tree has an empty range and is stepped over
+    const PathTree tree = trees[u];
+    const size_t local = node - (u ? trees[u - 1].end : 0), k = local / tree.depth, l = local % tree.depth;
+    const size_t sibling = (((size_t)indices[k] & (tree.leaves - 1)) >> l) ^ 1;
+    out[t] = tree.d[2 * (merkle_level_offset(tree.leaves, l) + sibling) + (t & 1)];
+}
+
 // the levels above the leaf digests, bottom up
 static int merkle_levels(zkhip_ctx *ctx, zkhip_merkle *t) {
     for (size_t l = 1; l <= t->depth; ++l) {
@@ -136,6 +192,32 @@ struct PathBuffers {  // zkhip_merkle_paths: the leaf indices and the gathered d
     }
 };
 
+struct QueryBuffers {  // zkhip_fri_query_dev: the set table, the query indices and the gathered elements (two uint4 each)
+    size_t n_sets, count, elements;
+    FriQuerySet *sets;
+    uint64_t *idx;
+    uint4 *out;
+    template <class Arena>
+    void layout(Arena &a) {
+        a.take(sets, n_sets);
+        a.take(idx, count);
+        a.take(out, elements * 2);
+    }
+};
+
+struct MultiPathBuffers {  // zkhip_merkle_paths_multi: the tree table, the query indices and the gathered digests (two uint4 each)
+    size_t n_trees, count, nodes;
+    PathTree *trees;
+    uint64_t *idx;
+    uint4 *out;
+    template <class Arena>
+    void layout(Arena &a) {
+        a.take(trees, n_trees);
+        a.take(idx, count);
+        a.take(out, nodes * 2);
+    }
+};
+
 extern "C" {
 
 int zkhip_merkle_build_dev(zkhip_ctx *ctx, int hash, const void *d_leaves, size_t n_leaves, size_t elements_per_leaf, zkhip_merkle **out) {
@@ -191,6 +273,65 @@ int zkhip_merkle_paths(zkhip_ctx *ctx, const zkhip_merkle *t, const uint64_t *le
               w.out);
     ZK_HIP_CHECK(ctx, hipMemcpyAsync(out, w.out, nodes * 32, hipMemcpyDeviceToHost, ctx->stream));
     ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // the digests are in `out` when the call returns
+    return ZKHIP_OK;
+}
+
+int zkhip_fri_query_dev(zkhip_ctx *ctx, const zkhip_fri_query_set *sets, size_t n_sets, const uint64_t *x_indices, size_t count, uint64_t *out) {
+    if (!ctx) return ZKHIP_ERR_INVALID;
+    if (count == 0 || n_sets == 0) return ZKHIP_OK;
+    if (!sets || !x_indices || !out) return ZKHIP_ERR_INVALID;
+    for (size_t t = 0; t < n_sets; ++t)
+        if (!sets[t].d_polys || sets[t].batch == 0) return ZKHIP_ERR_INVALID;
+    if (count >= ((size_t)1 << 32) || n_sets >= ((size_t)1 << 32)) return ZKHIP_ERR_RANGE;
+    size_t max_log = 0, elements = 0;
+    std::vector<FriQuerySet> table(n_sets);
+    for (size_t t = 0; t < n_sets; ++t) {
+        const zkhip_fri_query_set &s = sets[t];
+        if (s.fri_step < 1 || s.fri_step > s.log_domain || s.log_domain > 32 || s.batch >= ((size_t)1 << 31)) return ZKHIP_ERR_RANGE;
+        max_log = std::max(max_log, s.log_domain);
+        // the answers are a few elements per query: 2^38 of them and more is not a query phase.  Held against what is left of that bound before
+        // the product is formed (batch < 2^31 and fri_step <= 32 keep the shift below 2^63; times count it could wrap)
+        const size_t per_query = s.batch << s.fri_step, limit = (size_t)1 << 38;
+        if (per_query > (limit - 1 - elements) / count) return ZKHIP_ERR_RANGE;
+        elements += count * per_query;
+        table[t] = {(const uint4 *)s.d_polys, (uint32_t)s.log_domain, (uint32_t)s.batch, (uint32_t)s.fri_step, elements};
+    }
+    for (size_t q = 0; q < count; ++q)
+        if (x_indices[q] >> max_log) return ZKHIP_ERR_RANGE;
+    ZK_ENTER(ctx);
+    QueryBuffers w = {n_sets, count, elements};
+    ZK_TRY(ws_place(ctx, w));
+    ZK_TRY(ws_upload(ctx, w.sets, table.data(), n_sets * sizeof(FriQuerySet)));
+    ZK_TRY(ws_upload(ctx, w.idx, x_indices, count * 8));
+    ZK_LAUNCH(ctx, "fri_query_gather", fri_query_gather, grid_1d(elements * 2), dim3(256), 0, w.sets, (uint32_t)n_sets, w.idx, elements * 2, w.out);
+    ZK_HIP_CHECK(ctx, hipMemcpyAsync(out, w.out, elements * 32, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // the answers are in `out`, and `table` has been read, when the call returns
+    return ZKHIP_OK;
+}
+
+int zkhip_merkle_paths_multi(zkhip_ctx *ctx, const zkhip_merkle *const *trees, size_t n_trees, const uint64_t *x_indices, size_t count, uint8_t *out) {
+    if (!ctx || (n_trees && !trees)) return ZKHIP_ERR_INVALID;
+    for (size_t t = 0; t < n_trees; ++t)
+        if (!trees[t]) return ZKHIP_ERR_INVALID;
+    if (count == 0 || n_trees == 0) return ZKHIP_OK;
+    if (!x_indices) return ZKHIP_ERR_INVALID;
+    if (count >= ((size_t)1 << 32) || n_trees >= ((size_t)1 << 32)) return ZKHIP_ERR_RANGE;
+    size_t nodes = 0;
+    std::vector<PathTree> table(n_trees);
+    for (size_t t = 0; t < n_trees; ++t) {
+        nodes += count * trees[t]->depth;
+        table[t] = {(const uint4 *)trees[t]->d, trees[t]->leaves, trees[t]->depth, nodes};
+    }
+    if (nodes == 0) return ZKHIP_OK;  // one-leaf trees only: no bytes
+    if (!out) return ZKHIP_ERR_INVALID;
+    ZK_ENTER(ctx);
+    MultiPathBuffers w = {n_trees, count, nodes};
+    ZK_TRY(ws_place(ctx, w));
+    ZK_TRY(ws_upload(ctx, w.trees, table.data(), n_trees * sizeof(PathTree)));
+    ZK_TRY(ws_upload(ctx, w.idx, x_indices, count * 8));
+    ZK_LAUNCH(ctx, "merkle_path_gather_multi", merkle_path_gather_multi, grid_1d(nodes * 2), dim3(256), 0, w.trees, (uint32_t)n_trees, w.idx, nodes * 2, w.out);
+    ZK_HIP_CHECK(ctx, hipMemcpyAsync(out, w.out, nodes * 32, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // the digests are in `out`, and `table` has been read, when the call returns
     return ZKHIP_OK;
 }
 

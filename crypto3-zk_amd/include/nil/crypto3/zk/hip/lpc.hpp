@@ -27,10 +27,21 @@
 //             span       b(ptr, total_elements, elements_per_leaf) over a page-locked buffer the scheme keeps (one copy at link speed);
 //             vector     b(const std::vector<value_type> &leaves, elements_per_leaf), as round 2 (a vector the scheme keeps).
 //           transcript:
-//           duck-typed on VALUES like kzg_v2.hpp (transcript(root), transcript.challenge()); the QUERY phase of
-//           proof_eval<FRI> (basic_fri.hpp:747-930: lambda Merkle openings at transcript-derived indices) reads only
-//           trees and a few evaluations and is left to the caller, who finds everything it needs through
-//           trees() / fri_trees() / fri_round_polynomial(i) / fri_alphas().
+//           duck-typed on VALUES like kzg_v2.hpp (transcript(root), transcript.challenge()).
+//   device  the QUERY phase of proof_eval<FRI> (basic_fri.hpp:747-930: fri_params.lambda openings at transcript-derived indices), behind names of
+//           its own -- proof_eval keeps its statements, its transcript traffic and its result:
+//             query_phase(transcript, proof)   after proof_eval on the same object; fills proof.fri_proof.query_proofs.  Everything it reads is
+//                        resident -- the coefficient forms of every batch, every round polynomial, every tree -- and only the answers cross PCIe:
+//                        per batch its polynomials are re-extended to D[0] into the commit's scratch and ONE zkhip_fri_query_dev gathers the
+//                        pairs calculate_s walks from every query index; one more gathers y of every round; zkhip_merkle_paths_multi opens
+//                        all batch trees, and all round trees, in one pass each (a host tree answers through its proof(i)).  The host keeps
+//                        the domain indices (detail::domain_index: a walk down the 2-power subgroups, not the reference's scan of D[0]) and
+//                        the final polynomial at +-x^2.
+//             proof_eval_full(transcript)      proof_eval, then query_phase: a proof a verifier can check.
+//             verify_eval(proof, commitments, transcript)   lpc.hpp:202-300 over basic_fri.hpp:933-1154, host only; for the device builder,
+//                        whose leaf and node hashing include/zkhip.h states.
+//           A caller that runs its own query phase still finds what it needs through trees() / fri_trees() / fri_round_polynomial(i) /
+//           coefficients(batch, i) / fri_alphas().
 //   device  grinding (basic_fri.hpp:743-745), when fri_params.use_grinding is set: the proof of work between the commit and the query phase
 //           is searched on the GPU (hip/proof_of_work.hpp: proof_of_work_hip over the transcript's state()) and returned in
 //           fri_proof.proof_of_work.  It needs the SHA2-256 sequential transcript (hip/transcript.hpp, or any type with its state()); without
@@ -82,6 +93,11 @@ struct fri_params_hip {
     /// basic_fri.hpp:123-124, defaults as :156-157 (trailing, so that aggregate initialisation of the members above stays as it was)
     bool use_grinding = false;
     std::uint32_t grinding_parameter = 0xFFFF;    // the mask a nonce's int_challenge must clear
+    /// the number of queries (basic_fri.hpp:122); 0: the scheme stops after the commit phase (proof_eval), query_phase refuses.  Trailing too.
+    std::size_t lambda = 0;
+    /// the degree bound the proof is about (basic_fri.hpp:228: every committed polynomial has degree <= max_degree); read by verify_eval
+    /// alone, which refuses to run without it (0: unset).  Trailing too.
+    std::size_t max_degree = 0;
     /// the roots the reference's domains D[i] = make_evaluation_domain(2^(log_domain - i)) carry (fri params, basic_fri.hpp:84-118),
     /// from the curve adapter's field constants
     static fri_params_hip standard(std::size_t log_domain, std::vector<std::size_t> step_list) {
@@ -132,6 +148,84 @@ namespace detail {
     struct tree_builder_result<B, V, tree_builder_kind::vector> {
         typedef typename std::decay<decltype(std::declval<B &>()(std::declval<const std::vector<V> &>(), std::size_t()))>::type type;
     };
+
+    // ---- the query phase (basic_fri.hpp:747-930) ----
+    /// a host tree that can open a leaf: proof(std::size_t)
+    template <typename Tree, typename = void>
+    struct has_proof : std::false_type { };
+    template <typename Tree>
+    struct has_proof<Tree, std::void_t<decltype(std::declval<const Tree &>().proof(std::size_t()))>> : std::true_type { };
+    /// what stands for the path of a host tree that cannot open a leaf (query_phase does not compile for it)
+    struct no_merkle_path { };
+    /// the path a query proof carries: the device tree's path_type (hip/merkle.hpp's device_merkle_path), or whatever a host tree's proof(i) returns
+    template <typename Tree, bool Device, bool HasProof>
+    struct merkle_path_of {
+        typedef no_merkle_path type;
+    };
+    template <typename Tree, bool HasProof>
+    struct merkle_path_of<Tree, true, HasProof> {
+        typedef typename Tree::path_type type;
+    };
+    template <typename Tree>
+    struct merkle_path_of<Tree, false, true> {
+        typedef typename std::decay<decltype(std::declval<const Tree &>().proof(std::size_t()))>::type type;
+    };
+
+    /// base^e, e as four little-endian 64-bit limbs
+    template <typename V>
+    V pow_limbs(const V &base, const std::uint64_t *e) {
+        V acc = V::one();
+        for (int bit = 255; bit >= 0; --bit) {
+            acc = acc * acc;
+            if ((e[bit / 64] >> (bit % 64)) & 1) acc = acc * base;
+        }
+        return acc;
+    }
+    template <typename V>
+    V pow_index(const V &base, std::size_t e) {
+        const std::uint64_t limbs[4] = {e, 0, 0, 0};
+        return pow_limbs(base, limbs);
+    }
+    /// The index of x in the domain of 2^log_domain points: the e with omega^e = x, omega = root_of_unity(log_domain).  Where the reference scans
+    /// the whole domain (basic_fri.hpp:781-786), this walks down the tower of 2-power subgroups: x^(2^j) lies in the subgroup of order
+    /// 2^(log_domain - j), so from j = log_domain - 1 down to 0 each level fixes one more bit of e, lowest first -- log_domain squarings of x and of
+    /// omega, then a product of at most log_domain known powers per bit.  Same index as the scan's.  An x outside the domain (0, or an element of
+    /// larger order: the reference's scan would run off the domain's end) throws.
+    template <typename V, typename RootFn>
+    std::size_t domain_index(const V &x, std::size_t log_domain, const RootFn &root_of_unity) {
+        std::vector<V> xs(log_domain + 1), ws(log_domain + 1);    // xs[j] = x^(2^j), ws[j] = omega^(2^j)
+        xs[0] = x;
+        ws[0] = root_of_unity(log_domain);
+        for (std::size_t j = 0; j < log_domain; ++j) {
+            xs[j + 1] = xs[j] * xs[j];
+            ws[j + 1] = ws[j] * ws[j];
+        }
+        if (!(xs[log_domain] == V::one())) throw std::runtime_error("lpc query phase: the challenge does not map into the domain");
+        std::size_t e = 0;
+        for (std::size_t k = 0; k < log_domain; ++k) {    // bit k of e, read off x^(2^j) = omega^(2^j e) with j = log_domain - 1 - k
+            const std::size_t j = log_domain - 1 - k;
+            V low = V::one();    // omega^(2^j (e mod 2^k))
+            for (std::size_t b = 0; b < k; ++b)
+                if ((e >> b) & 1) low = low * ws[j + b];
+            if (xs[j] == low) continue;
+            if (!(xs[j] == low * ws[j + k])) throw std::runtime_error("lpc query phase: the challenge does not map into the domain");
+            e |= (std::size_t)1 << k;
+        }
+        return e;
+    }
+    /// calculate_s's walk (basic_fri.hpp:585-614) as positions: pair j of the 2^(fri_step - 1) pairs read from x over the 2^log_n-point domain is
+    /// (f[p_j], f[p_j + N/2]) with p_j = (x + the offsets N/4, N/8, ... picked by the bits of j) mod N/2 -- the smaller index of the pair
+    inline std::vector<std::size_t> pair_positions(std::size_t x, std::size_t log_n, std::size_t fri_step) {
+        const std::size_t N = (std::size_t)1 << log_n, half = (std::size_t)1 << (fri_step - 1);
+        std::vector<std::size_t> pos(half);
+        for (std::size_t j = 0; j < half; ++j) {
+            std::size_t s = x;
+            for (std::size_t l = 0; l + 1 < fri_step; ++l)
+                if ((j >> l) & 1) s += N >> (2 + l);
+            pos[j] = s & ((N >> 1) - 1);
+        }
+        return pos;
+    }
 }    // namespace detail
 
 /// `PolynomialType`: as for the KZG schemes (batched_commitment.hpp:56-64) -- size() and operator[] over contiguous scalars.
@@ -156,11 +250,26 @@ public:
     typedef typename detail::tree_builder_result<TreeBuilder, value_type, builder_kind>::type precommitment_type;
     typedef typename std::decay<decltype(std::declval<const precommitment_type &>().root())>::type commitment_type;
     typedef std::map<std::size_t, std::vector<value_type>> preprocessed_data_type;
+    /// the path a query proof carries (basic_fri.hpp:228-290): device_merkle_path with the device builder, a host tree's proof(i) otherwise
+    typedef typename detail::merkle_path_of<precommitment_type, builder_kind == detail::tree_builder_kind::device,
+                                            detail::has_proof<precommitment_type>::value>::type merkle_path_type;
+    struct initial_proof_type {
+        std::vector<std::vector<std::array<value_type, 2>>> values;    // [polynomial][pair], in calculate_s's order from the query's x
+        merkle_path_type p;
+    };
+    struct round_proof_type {
+        std::vector<std::array<value_type, 2>> y;
+        merkle_path_type p;
+    };
+    struct query_proof_type {
+        std::map<std::size_t, initial_proof_type> initial_proof;
+        std::vector<round_proof_type> round_proofs;
+    };
     struct fri_proof_type {
         std::vector<commitment_type> fri_roots;
         std::vector<value_type> final_polynomial;    // coefficients (math::polynomial(f.coefficients()), basic_fri.hpp:736-742)
         std::uint32_t proof_of_work = 0;             // the grinding nonce (basic_fri.hpp:296, 743-745); 0 without use_grinding
-        /* query_proofs: the caller's (see the header) */
+        std::vector<query_proof_type> query_proofs;  // lambda of them after query_phase / proof_eval_full; proof_eval leaves it empty
     };
     struct proof_type {
         eval_storage_type z;
@@ -545,6 +654,333 @@ public:
         return proof;
     }
 
+    /// The query phase of proof_eval<FRI> (basic_fri.hpp:747-930), after proof_eval on this object (which still holds the round polynomials,
+    /// the trees and the coefficient forms): fills proof.fri_proof.query_proofs with fri_params.lambda query proofs.  All lambda challenges
+    /// are drawn first -- the reference draws one per query and absorbs nothing in between, so the transcript sees the same calls in the same
+    /// order -- and the device answers all queries together:
+    ///   per committed batch, in map order: its polynomials re-extended to D[0] from the resident coefficient forms into the commit's scratch
+    ///     (a zero-padded copy per polynomial, one batched NTT), then ONE zkhip_fri_query_dev over them;
+    ///   ONE zkhip_merkle_paths_multi over the batch trees;  ONE zkhip_fri_query_dev over fs[i + 1] of every round but the last;  ONE
+    ///     zkhip_merkle_paths_multi over the round trees (a host tree answers through proof(i) instead);
+    ///   the last round's y: the final polynomial at +-x^2, on the host.
+    /// Refuses (std::invalid_argument, the transcript untouched): lambda == 0, a step list that does not end in 1 (check_step_list, :566), no
+    /// proof_eval before.  A challenge that does not map into D[0] (c = 0) throws std::runtime_error.
+    void query_phase(transcript_type &transcript, proof_type &proof) {
+        static_assert(builder_kind == detail::tree_builder_kind::device || detail::has_proof<precommitment_type>::value,
+                      "lpc query_phase: the host tree builder's tree has no proof(std::size_t) to open a leaf with");
+        const std::vector<std::size_t> &steps = _fri_params.step_list;
+        const std::size_t lambda = _fri_params.lambda, n = _fri_params.log_domain, R = steps.size();
+        if (lambda == 0) throw std::invalid_argument("lpc query_phase: fri_params.lambda is 0");
+        if (steps.empty() || steps.back() != 1) throw std::invalid_argument("lpc query_phase: the step list must end in 1");
+        if (_fs.size() != R + 1 || _fri_trees.size() != R || proof.fri_proof.final_polynomial.empty())
+            throw std::invalid_argument("lpc query_phase: proof_eval has not run on this scheme object");
+        typedef std::chrono::steady_clock clock;
+        query_phase_times times;
+        auto tp = clock::now();
+        auto lap = [&](double &slot) {
+            if (!_time_query_phase) return;
+            const auto now = clock::now();
+            slot += std::chrono::duration<double, std::milli>(now - tp).count();
+            tp = now;
+        };
+
+        /* x = challenge^((r - 1) / |D[0]|) and its index in D[0] (basic_fri.hpp:779-786) */
+        std::uint64_t e[4];
+        cofactor_exponent(e);
+        std::vector<std::uint64_t> xi(lambda);
+        for (std::size_t q = 0; q < lambda; ++q) xi[q] = detail::domain_index(detail::pow_limbs(transcript.challenge(), e), n, _fri_params.root_of_unity);
+        std::vector<query_proof_type> &qps = proof.fri_proof.query_proofs;
+        qps.assign(lambda, query_proof_type());
+        lap(times.host_ms);
+
+        /* Initial proofs (:793-861): the values of every committed polynomial over D[0] at the pairs calculate_s walks from x */
+        const std::size_t D0 = domain_size(0), pairs0 = (std::size_t)1 << (steps[0] - 1);
+        std::uint64_t w0[4], one[4];
+        adapter::scalar_to_limbs(_fri_params.root_of_unity(n), w0);
+        adapter::scalar_to_limbs(value_type::one(), one);
+        std::vector<std::uint64_t> answers;
+        for (const auto &it : _dev) {
+            const device_batch &db = it.second;
+            const std::size_t count = db.len.size();
+            for (std::size_t q = 0; q < lambda; ++q) qps[q].initial_proof[it.first].values.assign(count, std::vector<std::array<value_type, 2>>(pairs0));
+            if (count == 0) continue;
+            char *d_ext = static_cast<char *>(_scratch_ext.reserve(_ctx, count * D0 * 32));
+            for (std::size_t p = 0; p < count; ++p) {    // the zero-padded copy: 1 * coefficients below len, zero behind
+                const void *src = db.at(p);
+                check(zkhip_poly_lincomb_dev(_ctx.get(), adapter::id, 1, &src, &db.len[p], one, 1, d_ext + 32 * p * D0, D0, 0), "zkhip_poly_lincomb_dev", _ctx.get());
+            }
+            check(zkhip_ntt_dev(_ctx.get(), adapter::id, d_ext, n, count, w0, 0, nullptr), "zkhip_ntt_dev", _ctx.get());
+            if (_time_query_phase) _ctx.sync();
+            lap(times.reextend_ms);
+            const zkhip_fri_query_set set = {d_ext, n, count, steps[0]};
+            answers.resize(4 * lambda * (count << steps[0]));
+            check(zkhip_fri_query_dev(_ctx.get(), &set, 1, xi.data(), lambda, answers.data()), "zkhip_fri_query_dev", _ctx.get());
+            lap(times.gather_ms);
+            const std::uint64_t *at = answers.data();
+            for (std::size_t q = 0; q < lambda; ++q) {
+                auto &values = qps[q].initial_proof[it.first].values;
+                for (std::size_t p = 0; p < count; ++p)
+                    for (std::size_t j = 0; j < pairs0; ++j, at += 8) values[p][j] = {adapter::scalar_from_limbs(at), adapter::scalar_from_limbs(at + 4)};
+            }
+            lap(times.host_ms);
+        }
+        {    /* the paths of leaf x mod (|D[0]| / 2^step_list[0]) in every batch tree (:857-860) */
+            std::vector<const precommitment_type *> trees;
+            for (const auto &it : _trees) trees.push_back(&it.second);
+            auto paths = open_paths(trees, std::vector<std::size_t>(trees.size(), n - steps[0]), xi);
+            std::size_t t = 0;
+            for (const auto &it : _trees) {
+                for (std::size_t q = 0; q < lambda; ++q) qps[q].initial_proof[it.first].p = std::move(paths[t][q]);
+                ++t;
+            }
+            lap(times.paths_ms);
+        }
+
+        /* Round proofs (:863-920): y of round i is fs[i + 1] at the pairs walked from x mod |D[t_(i+1)]| */
+        for (std::size_t q = 0; q < lambda; ++q) qps[q].round_proofs.assign(R, round_proof_type());
+        if (R > 1) {
+            std::vector<zkhip_fri_query_set> sets;
+            std::size_t t = steps[0], elements = 0;
+            const std::size_t log_first = n - t;    // the largest domain among the sets: the indices go in reduced to it
+            for (std::size_t i = 0; i + 1 < R; ++i) {
+                sets.push_back({_fs[i + 1].data(), n - t, 1, steps[i + 1]});
+                elements += (std::size_t)1 << steps[i + 1];
+                t += steps[i + 1];
+            }
+            std::vector<std::uint64_t> xr(lambda);
+            for (std::size_t q = 0; q < lambda; ++q) xr[q] = xi[q] & (((std::uint64_t)1 << log_first) - 1);
+            answers.resize(4 * lambda * elements);
+            check(zkhip_fri_query_dev(_ctx.get(), sets.data(), sets.size(), xr.data(), lambda, answers.data()), "zkhip_fri_query_dev", _ctx.get());
+            lap(times.gather_ms);
+            const std::uint64_t *at = answers.data();
+            for (std::size_t i = 0; i + 1 < R; ++i)
+                for (std::size_t q = 0; q < lambda; ++q) {
+                    auto &y = qps[q].round_proofs[i].y;
+                    y.resize((std::size_t)1 << (steps[i + 1] - 1));
+                    for (auto &pair : y) {
+                        pair = {adapter::scalar_from_limbs(at), adapter::scalar_from_limbs(at + 4)};
+                        at += 8;
+                    }
+                }
+            lap(times.host_ms);
+        }
+        {    /* the paths of leaf x mod (|D[t_i]| / 2^step_list[i]) in the tree of round i (:868-874) */
+            std::vector<const precommitment_type *> trees;
+            std::vector<std::size_t> log_leaves;
+            std::size_t t = 0;
+            for (std::size_t i = 0; i < R; t += steps[i], ++i) {
+                trees.push_back(&_fri_trees[i]);
+                log_leaves.push_back(n - t - steps[i]);
+            }
+            auto paths = open_paths(trees, log_leaves, xi);
+            for (std::size_t i = 0; i < R; ++i)
+                for (std::size_t q = 0; q < lambda; ++q) qps[q].round_proofs[i].p = std::move(paths[i][q]);
+            lap(times.paths_ms);
+        }
+        {    /* the last round (:904-918): the final polynomial at x^2 and -x^2, x over the last round's domain, in the order the next round
+                -- of step 1 -- would hold them */
+            std::size_t r = 0;
+            for (std::size_t s : steps) r += s;
+            const std::size_t log_last = n - (r - 1), N = (std::size_t)1 << log_last;
+            const value_type w = _fri_params.root_of_unity(log_last);
+            for (std::size_t q = 0; q < lambda; ++q) {
+                const std::size_t x_index = xi[q] & (N - 1);
+                const value_type x = detail::pow_index(w, x_index), x2 = x * x;
+                const std::size_t ind = (x_index % (N / 2) < N / 4) ? 0 : 1;
+                auto &y = qps[q].round_proofs[R - 1].y;
+                y.resize(1);
+                y[0][ind] = horner(proof.fri_proof.final_polynomial, x2);
+                y[0][1 - ind] = horner(proof.fri_proof.final_polynomial, value_type::zero() - x2);
+            }
+            lap(times.host_ms);
+        }
+        _last_query_times = times;
+    }
+
+    /// a whole opening proof: proof_eval, then query_phase
+    proof_type proof_eval_full(transcript_type &transcript) {
+        proof_type proof = proof_eval(transcript);
+        query_phase(transcript, proof);
+        return proof;
+    }
+
+    /// verify_eval (lpc.hpp:202-300 over basic_fri.hpp:933-1154), in this shim's own words; host only, nothing is launched.  The verifier's
+    /// scheme object knows what the prover's knew: the evaluation points of every polynomial (set_batch_size + append_eval_point[s]), the fixed
+    /// batches (mark_batch_as_fixed) and their values at etha (setup).  Per query it checks
+    ///   the initial values against the batch roots (the leaf is the answered pairs in leaf order, hashed by include/zkhip.h's convention),
+    ///   the combined quotient they imply -- sum over the opening points of (sum theta^k g_k - U) / (X - point), as proof_eval builds it --
+    ///     against the first round's root,
+    ///   every round: the y values against the round's root, their fold with the round's alphas against the next round's y,
+    ///   the last y against the final polynomial at +-x^2;
+    /// before that the shape of the proof, the low-degree bound on the final polynomial (basic_fri.hpp:949-952: its degree, trailing zero
+    /// coefficients aside, is at most 2^(log2(max_degree + 1) - r + 1) - 1 -- without it a final polynomial as long as the last domain would
+    /// interpolate anything) and, with use_grinding, the proof of work.  Refuses (std::invalid_argument, before the transcript is touched)
+    /// lambda == 0, a step list that does not end in 1, and an unset fri_params.max_degree: there is no verifying without a degree bound.
+    /// It reads what a verifier has -- the parameters, the points, etha and the fixed values -- and nothing the prover's calls left behind.
+    /// Built for the device builder's instantiation: its leaf and node convention is the one include/zkhip.h states.
+    bool verify_eval(const proof_type &proof, const std::map<std::size_t, commitment_type> &commitments, transcript_type &transcript) const {
+        static_assert(builder_kind == detail::tree_builder_kind::device,
+                      "lpc verify_eval: built for the device tree builder, whose leaf and node hashing include/zkhip.h states");
+        const std::vector<std::size_t> &steps = _fri_params.step_list;
+        const std::size_t lambda = _fri_params.lambda, n = _fri_params.log_domain, R = steps.size();
+        if (lambda == 0) throw std::invalid_argument("lpc verify_eval: fri_params.lambda is 0");
+        if (steps.empty() || steps.back() != 1) throw std::invalid_argument("lpc verify_eval: the step list must end in 1");
+        if (_fri_params.max_degree == 0) throw std::invalid_argument("lpc verify_eval: fri_params.max_degree is not set: there is no degree bound to verify against");
+        std::size_t r = 0;
+        for (std::size_t s : steps) r += s;
+        const eval_storage_type &z = proof.z;
+        const fri_proof_type &fp = proof.fri_proof;
+
+        for (const auto &it : commitments) transcript(it.second);
+        const value_type theta = transcript.challenge();
+
+        /* what is opened where (lpc.hpp:212-252): per opening point the polynomials that have it, and U = sum theta^k z_k */
+        struct opening {
+            value_type point, U, theta0;    // theta0: the running power of theta at the opening's first polynomial
+            std::vector<std::pair<std::size_t, std::size_t>> polys;
+        };
+        std::vector<opening> openings;
+        value_type theta_acc = value_type::one();
+        for (std::size_t i : z.get_batches()) {
+            auto pt = _points.find(i);
+            if (!commitments.count(i) || pt == _points.end() || pt->second.size() != z.get_batch_size(i)) return false;
+            for (std::size_t j = 0; j < z.get_batch_size(i); ++j)
+                if (z.get_poly_points_number(i, j) != pt->second[j].size()) return false;
+        }
+        for (const auto &point : get_unique_points()) {
+            opening o {point, value_type::zero(), theta_acc, {}};
+            for (std::size_t i : z.get_batches())
+                for (std::size_t j = 0; j < z.get_batch_size(i); ++j) {
+                    const auto &pts = _points.at(i)[j];
+                    auto it = std::find(pts.begin(), pts.end(), point);
+                    if (it == pts.end()) continue;
+                    o.U = o.U + z.get(i, j, it - pts.begin()) * theta_acc;
+                    o.polys.emplace_back(i, j);
+                    theta_acc = theta_acc * theta;
+                }
+            if (!o.polys.empty()) openings.push_back(std::move(o));
+        }
+        for (std::size_t i : z.get_batches()) {    // the fixed batches at etha (lpc.hpp:241-252), batch by batch as proof_eval adds them
+            auto fx = _batch_fixed.find(i);
+            if (fx == _batch_fixed.end() || !fx->second) continue;
+            auto fv = _fixed_polys_values.find(i);
+            if (fv == _fixed_polys_values.end() || fv->second.size() != z.get_batch_size(i)) return false;
+            opening o {_etha, value_type::zero(), theta_acc, {}};
+            for (std::size_t j = 0; j < z.get_batch_size(i); ++j) {
+                o.U = o.U + fv->second[j] * theta_acc;
+                o.polys.emplace_back(i, j);
+                theta_acc = theta_acc * theta;
+            }
+            if (!o.polys.empty()) openings.push_back(std::move(o));
+        }
+        if (openings.empty()) return false;
+
+        /* the shape of the FRI proof, its roots and alphas (basic_fri.hpp:949-962), the proof of work (:964-966) */
+        if (fp.fri_roots.size() != R || fp.query_proofs.size() != lambda || fp.final_polynomial.empty() ||
+            fp.final_polynomial.size() > ((std::size_t)1 << (n - r)))
+            return false;
+        {   /* the low-degree bound (basic_fri.hpp:949-952): degree(final) <= 2^(log2(max_degree + 1) - r + 1) - 1, that is
+               (degree + 1) 2^r <= 2 (max_degree + 1); the degree is that of the highest non-zero coefficient */
+            std::size_t degree = fp.final_polynomial.size() - 1;
+            while (degree > 0 && fp.final_polynomial[degree] == value_type::zero()) --degree;
+            if (degree + 1 > ((_fri_params.max_degree + 1) >> (r - 1))) return false;    // r >= 1: the step list is not empty
+        }
+        std::vector<value_type> alphas;
+        for (std::size_t i = 0; i < R; ++i) {
+            transcript(fp.fri_roots[i]);
+            for (std::size_t s = 0; s < steps[i]; ++s) alphas.push_back(transcript.challenge());
+        }
+        if (_fri_params.use_grinding) {
+            if constexpr (detail::has_state<transcript_type>::value) {
+                if (!proof_of_work_hip<transcript_type>::verify(transcript, fp.proof_of_work, _fri_params.grinding_parameter)) return false;
+            } else {
+                throw std::invalid_argument("lpc verify_eval: use_grinding needs a transcript with state() (hip/transcript.hpp)");
+            }
+        }
+
+        std::uint64_t e[4];
+        cofactor_exponent(e);
+        const value_type w0 = _fri_params.root_of_unity(n), half = (value_type::one() + value_type::one()).inversed();
+        for (std::size_t q = 0; q < lambda; ++q) {
+            const query_proof_type &qp = fp.query_proofs[q];
+            const std::size_t x_index = detail::domain_index(detail::pow_limbs(transcript.challenge(), e), n, _fri_params.root_of_unity);
+            if (qp.round_proofs.size() != R || qp.initial_proof.size() != commitments.size()) return false;
+
+            /* initial proofs (:987-1006) */
+            const std::size_t pairs0 = (std::size_t)1 << (steps[0] - 1);
+            const std::vector<std::size_t> pos0 = detail::pair_positions(x_index, n, steps[0]);
+            for (const auto &it : qp.initial_proof) {
+                auto root = commitments.find(it.first);
+                if (root == commitments.end()) return false;
+                const initial_proof_type &ip = it.second;
+                for (const auto &v : ip.values)
+                    if (v.size() != pairs0) return false;
+                std::vector<const std::vector<std::array<value_type, 2>> *> rows;
+                for (const auto &v : ip.values) rows.push_back(&v);
+                if (!leaf_opens(rows, x_index, n, steps[0], ip.p, root->second)) return false;
+            }
+            /* the combined quotient at the same pairs (:1008-1038) */
+            std::vector<std::array<value_type, 2>> y(pairs0, {value_type::zero(), value_type::zero()});
+            for (const opening &o : openings)
+                for (std::size_t j = 0; j < pairs0; ++j)
+                    for (std::size_t side = 0; side < 2; ++side) {
+                        value_type acc = value_type::zero(), th = o.theta0;
+                        for (std::size_t k = 0; k < o.polys.size(); ++k) {
+                            auto ip = qp.initial_proof.find(o.polys[k].first);
+                            if (ip == qp.initial_proof.end() || o.polys[k].second >= ip->second.values.size()) return false;
+                            acc = acc + ip->second.values[o.polys[k].second][j][side] * th;
+                            th = th * theta;
+                        }
+                        const value_type denominator = detail::pow_index(w0, pos0[j] + side * (domain_size(0) / 2)) - o.point;
+                        if (denominator == value_type::zero()) return false;
+                        y[j][side] = y[j][side] + (acc - o.U) * denominator.inversed();
+                    }
+
+            /* round proofs (:1039-1139): the y of round i open its tree, fold to one value, and that value stands in the next y */
+            std::size_t t = 0;
+            for (std::size_t i = 0; i < R; ++i) {
+                const std::size_t log_n = n - t, N = (std::size_t)1 << log_n, xr = x_index & (N - 1);
+                if (y.size() != ((std::size_t)1 << (steps[i] - 1))) return false;
+                if (!leaf_opens({&y}, xr, log_n, steps[i], qp.round_proofs[i].p, fp.fri_roots[i])) return false;
+                std::map<std::size_t, value_type> cur;    // position in the current domain -> value
+                const std::vector<std::size_t> pos = detail::pair_positions(xr, log_n, steps[i]);
+                for (std::size_t j = 0; j < y.size(); ++j) {
+                    cur[pos[j]] = y[j][0];
+                    cur[pos[j] + N / 2] = y[j][1];
+                }
+                for (std::size_t s = 0; s < steps[i]; ++s, ++t) {    // fold_polynomial (fold_polynomial.hpp:68-93) on the positions held
+                    const std::size_t M = (std::size_t)1 << (n - t);
+                    const value_type w = _fri_params.root_of_unity(n - t);
+                    std::map<std::size_t, value_type> next;
+                    for (const auto &pv : cur) {
+                        if (pv.first >= M / 2) break;
+                        auto hi = cur.find(pv.first + M / 2);
+                        if (hi == cur.end()) return false;
+                        const value_type aw = alphas[t] * detail::pow_index(w, (M - pv.first) & (M - 1));    // alpha w^-p
+                        next[pv.first] = half * ((value_type::one() + aw) * pv.second + (value_type::one() - aw) * hi->second);
+                    }
+                    cur.swap(next);
+                }
+                if (cur.size() != 1) return false;
+                const std::size_t Nn = (std::size_t)1 << (n - t), xn = x_index & (Nn - 1);    // the next domain and x's index in it
+                if (cur.begin()->first != (xn & ((N >> steps[i]) - 1))) return false;
+                y = qp.round_proofs[i].y;
+                const std::size_t expect = i + 1 < R ? (std::size_t)1 << (steps[i + 1] - 1) : 1;
+                if (y.size() != expect) return false;
+                if (!(y[0][xn < Nn / 2 ? 0 : 1] == cur.begin()->second)) return false;
+            }
+            /* the final polynomial (:1141-1151) */
+            {
+                const std::size_t log_last = n - (r - 1), N = (std::size_t)1 << log_last, xl = x_index & (N - 1);
+                const value_type x = detail::pow_index(_fri_params.root_of_unity(log_last), xl), x2 = x * x;
+                const std::size_t ind = (xl % (N / 2) < N / 4) ? 0 : 1;
+                if (!(y[0][ind] == horner(fp.final_polynomial, x2))) return false;
+                if (!(y[0][1 - ind] == horner(fp.final_polynomial, value_type::zero() - x2))) return false;
+            }
+        }
+        return true;
+    }
+
     // ---- what the caller's query phase reads (basic_fri.hpp:747-930) ----
     const std::map<std::size_t, precommitment_type> &trees() const { return _trees; }
     const std::vector<precommitment_type> &fri_trees() const { return _fri_trees; }
@@ -561,6 +997,61 @@ public:
 
 protected:
     std::size_t domain_size(std::size_t t) const { return (std::size_t)1 << (_fri_params.log_domain - t); }
+    /// (r - 1) / |D[0]|, the exponent that takes a challenge into D[0] (basic_fri.hpp:780, 973); r is odd and |D[0]| divides r - 1
+    void cofactor_exponent(std::uint64_t *e) const {
+        adapter::scalar_modulus(e);
+        e[0] -= 1;
+        const std::size_t n = _fri_params.log_domain, limbs = n / 64, bits = n % 64;
+        for (std::size_t k = 0; k < 4; ++k) {
+            const std::uint64_t lo = k + limbs < 4 ? e[k + limbs] : 0, hi = k + limbs + 1 < 4 ? e[k + limbs + 1] : 0;
+            e[k] = bits ? (lo >> bits) | (hi << (64 - bits)) : lo;
+        }
+    }
+    /// math::polynomial::evaluate over a coefficient vector
+    static value_type horner(const std::vector<value_type> &coefficients, const value_type &x) {
+        value_type acc = value_type::zero();
+        for (std::size_t k = coefficients.size(); k-- > 0;) acc = acc * x + coefficients[k];
+        return acc;
+    }
+    /// the paths of leaf (x mod 2^log_leaves[t]) of tree t for every query: out[t][q].  Device trees answer all of it in one pass
+    /// (zkhip_merkle_paths_multi reduces the index by the tree's own leaf count, which is 2^log_leaves[t]); a host tree is asked leaf by leaf.
+    std::vector<std::vector<merkle_path_type>> open_paths(const std::vector<const precommitment_type *> &trees, const std::vector<std::size_t> &log_leaves,
+                                                          const std::vector<std::uint64_t> &xi) const {
+        if constexpr (builder_kind == detail::tree_builder_kind::device) {
+            return precommitment_type::paths_multi(_ctx, trees, xi);
+        } else {
+            std::vector<std::vector<merkle_path_type>> out(trees.size());
+            for (std::size_t t = 0; t < trees.size(); ++t)
+                for (std::uint64_t x : xi) out[t].push_back(trees[t]->proof((std::size_t)(x & (((std::uint64_t)1 << log_leaves[t]) - 1))));
+            return out;
+        }
+    }
+    /// verify_eval's Merkle check: `rows` (one per polynomial) hold the pairs answered for x over the 2^log_n-point domain in calculate_s's
+    /// order; put into the leaf's own order (get_correct_order, basic_fri.hpp:616-663: the walk from the leaf index instead of x), encoded and
+    /// hashed as include/zkhip.h states, they must lead to `root` along `path`
+    bool leaf_opens(const std::vector<const std::vector<std::array<value_type, 2>> *> &rows, std::size_t x, std::size_t log_n, std::size_t fri_step,
+                    const merkle_path_type &path, const commitment_type &root) const {
+        const std::size_t leaf = x & (((std::size_t)1 << (log_n - fri_step)) - 1);
+        if (path.leaf_index != leaf || path.siblings.size() != log_n - fri_step) return false;
+        const std::vector<std::size_t> asked = detail::pair_positions(x, log_n, fri_step), ordered = detail::pair_positions(leaf, log_n, fri_step);
+        std::vector<std::uint8_t> bytes;
+        for (const auto *row : rows) {
+            if (row->size() != asked.size()) return false;
+            for (std::size_t position : ordered) {
+                const std::size_t j = std::find(asked.begin(), asked.end(), position) - asked.begin();
+                if (j == asked.size()) return false;
+                for (const value_type &v : (*row)[j]) {
+                    std::uint64_t limbs[4];
+                    adapter::scalar_to_limbs(v, limbs);
+                    for (int k = 3; k >= 0; --k)
+                        for (int b = 7; b >= 0; --b) bytes.push_back(std::uint8_t(limbs[k] >> (8 * b)));    // the canonical integer, big-endian
+                }
+            }
+        }
+        commitment_type digest;
+        check(zkhip_sha256_host(bytes.data(), bytes.size(), digest.data()), "zkhip_sha256_host");
+        return path.root_from(digest) == root;
+    }
     /// the leaf layout of `batch` polynomials resident as evaluations over the 2^log_domain-point domain -> the caller's tree; a device
     /// builder takes the evaluations as they lie: no leaf layout, no copy to the host
     precommitment_type build_tree(const void *d_evals, std::size_t batch, std::size_t log_domain, std::size_t fri_step) const {
@@ -726,6 +1217,13 @@ protected:
         pinned_buffer pin[2];
         std::unique_ptr<context> up;    // the member's upload stream
     };
+    /// host wall time of the last query_phase by part, for a measuring subclass (the bench driver's): filled while _time_query_phase is set,
+    /// which costs a stream synchronisation per batch.  Not part of the scheme's interface.
+    struct query_phase_times {
+        double reextend_ms = 0, gather_ms = 0, paths_ms = 0, host_ms = 0;
+    };
+    bool _time_query_phase = false;
+    query_phase_times _last_query_times;
     const context &_ctx;
     const device_group *_group = nullptr;
     std::size_t _group_commits = 0, _last_owners = 0;

@@ -15,6 +15,7 @@
 #ifndef ZKHIP_SHIM_MERKLE_HPP
 #define ZKHIP_SHIM_MERKLE_HPP
 
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <memory>
@@ -27,11 +28,56 @@ namespace crypto3 {
 namespace zk {
 namespace hip {
 
+/// The authentication path of one leaf as a query proof carries it (merkle_proof in basic_fri.hpp's initial_proof_type / round_proof_type)
+struct device_merkle_path {
+    std::size_t leaf_index = 0;
+    std::vector<std::array<std::uint8_t, 32>> siblings;    // leaf level first
+    /// the root this path leads to from a leaf's digest: the node convention of include/zkhip.h, hashed on the host
+    std::array<std::uint8_t, 32> root_from(std::array<std::uint8_t, 32> digest) const {
+        std::uint8_t node[64];
+        for (std::size_t l = 0; l < siblings.size(); ++l) {
+            const bool right = (leaf_index >> l) & 1;
+            std::copy_n(digest.begin(), 32, node + (right ? 32 : 0));
+            std::copy_n(siblings[l].begin(), 32, node + (right ? 0 : 32));
+            check(zkhip_sha256_host(node, 64, digest.data()), "zkhip_sha256_host");
+        }
+        return digest;
+    }
+};
+
 /// A Merkle tree resident on the device (RAII over zkhip_merkle; copies share the tree).  The context must outlive it.
 class device_merkle_tree {
 public:
     typedef std::array<std::uint8_t, 32> digest_type;
     typedef std::vector<digest_type> proof_type;    // the sibling digests of a leaf's ancestors, leaf level first
+    typedef device_merkle_path path_type;
+
+    /// the paths of every query index in every tree (the trees of one context), tree t answering leaf x mod leaves(t): one device pass and one
+    /// copy for all of them (zkhip_merkle_paths_multi); out[t][q]
+    static std::vector<std::vector<device_merkle_path>> paths_multi(const context &ctx, const std::vector<const device_merkle_tree *> &trees,
+                                                                    const std::vector<std::uint64_t> &x_indices) {
+        std::vector<const zkhip_merkle *> handles;
+        std::size_t bytes = 0;
+        for (const device_merkle_tree *t : trees) {
+            handles.push_back(t->get());
+            bytes += x_indices.size() * t->depth() * 32;
+        }
+        std::vector<std::uint8_t> flat(bytes);
+        check(zkhip_merkle_paths_multi(ctx.get(), handles.data(), handles.size(), x_indices.data(), x_indices.size(), flat.data()), "zkhip_merkle_paths_multi",
+              ctx.get());
+        std::vector<std::vector<device_merkle_path>> out(trees.size());
+        const std::uint8_t *at = flat.data();
+        for (std::size_t t = 0; t < trees.size(); ++t) {
+            const std::size_t d = trees[t]->depth(), L = trees[t]->leaves();
+            out[t].resize(x_indices.size());
+            for (std::size_t q = 0; q < x_indices.size(); ++q) {
+                out[t][q].leaf_index = x_indices[q] % L;
+                out[t][q].siblings.resize(d);
+                for (std::size_t l = 0; l < d; ++l, at += 32) std::copy_n(at, 32, out[t][q].siblings[l].begin());
+            }
+        }
+        return out;
+    }
 
     device_merkle_tree() = default;
     /// takes the handle over; the root is fetched here, once

@@ -24,7 +24,7 @@ EXPORTS = [
     "zkhip_fr_vec_op_dev", "zkhip_fr_vec_affine_dev", "zkhip_fr_vec_mul_div_dev", "zkhip_fr_vec_prod_dev", "zkhip_poly_shift_dev", "zkhip_poly_eval_dev", "zkhip_poly_div_linear_dev", "zkhip_poly_div_vanishing_dev", "zkhip_poly_lincomb_dev", "zkhip_perm_grand_product_dev", "zkhip_lookup_grand_product_dev", "zkhip_lookup_sort_dev", "zkhip_perm_factor_products_dev", "zkhip_gate_eval_dev",
     "zkhip_bases_fold", "zkhip_bases_scale_dev", "zkhip_bases_scale_geometric", "zkhip_bases_lagrange", "zkhip_fr_inner_product_dev", "zkhip_fr_powers_lincomb_dev", "zkhip_fr_challenge_products_dev",
     "zkhip_merkle_build_dev", "zkhip_merkle_build_fri_dev", "zkhip_merkle_leaves", "zkhip_merkle_depth", "zkhip_merkle_root", "zkhip_merkle_digests", "zkhip_merkle_paths",
-    "zkhip_merkle_free", "zkhip_pow_grind", "zkhip_sha256_host",
+    "zkhip_merkle_free", "zkhip_fri_query_dev", "zkhip_merkle_paths_multi", "zkhip_pow_grind", "zkhip_sha256_host",
     "zkhip_group_init", "zkhip_group_destroy", "zkhip_group_size", "zkhip_group_ctx", "zkhip_group_last_error", "zkhip_group_set_transport", "zkhip_group_transport",
     "zkhip_group_all_gather", "zkhip_group_copy", "zkhip_group_sync", "zkhip_group_bases_upload", "zkhip_group_bases_from_scalars", "zkhip_group_bases_free",
     "zkhip_group_bases_size", "zkhip_group_bases_member", "zkhip_group_msm", "zkhip_group_ntt",
@@ -64,6 +64,11 @@ class GateProgram(ctypes.Structure):
     _fields_ = [("n_gates", ctypes.c_uint32), ("n_terms", ctypes.c_uint32), ("n_factors", ctypes.c_uint32), ("n_slots", ctypes.c_uint32),
                 ("gate_terms", ctypes.c_void_p), ("gate_selector", ctypes.c_void_p), ("gate_selector_rot", ctypes.c_void_p), ("term_factors", ctypes.c_void_p),
                 ("factor_slot", ctypes.c_void_p), ("factor_rot", ctypes.c_void_p), ("term_coeff", ctypes.c_void_p)]
+
+
+class FriQuerySet(ctypes.Structure):
+    """zkhip_fri_query_set"""
+    _fields_ = [("d_polys", ctypes.c_void_p), ("log_domain", ctypes.c_size_t), ("batch", ctypes.c_size_t), ("fri_step", ctypes.c_size_t)]
 
 
 def domain_choice(curve: int, min_size: int):
@@ -592,6 +597,29 @@ class Context:
         self._check(self.lib.zkhip_merkle_build_fri_dev(self.h, int(hash_id), ctypes.c_void_p(d_polys), ctypes.c_size_t(log_domain), ctypes.c_size_t(batch),
                                                         ctypes.c_size_t(fri_step), ctypes.byref(h)), "zkhip_merkle_build_fri_dev")
         return MerkleTree(self, h)
+
+    # ---- the FRI query phase's answers (zkhip_fri_query_dev, zkhip_merkle_paths_multi)
+    def fri_query(self, sets, x_indices):
+        """sets: (d_polys, log_domain, batch, fri_step) each; per set a (count, batch, 2^(fri_step - 1), 2, 4) u64 array: for every query index the
+        pairs calculate_s walks from x mod 2^log_domain, one launch and one copy for all sets"""
+        idx = np.ascontiguousarray(x_indices, dtype=np.uint64).reshape(-1)
+        table = (FriQuerySet * max(1, len(sets)))(*[FriQuerySet(int(d), int(ld), int(b), int(s)) for d, ld, b, s in sets])
+        sizes = [len(idx) * b << s for _, _, b, s in sets]
+        out = np.zeros((sum(sizes), 4), dtype=np.uint64)
+        self._check(self.lib.zkhip_fri_query_dev(self.h, table, ctypes.c_size_t(len(sets)), _p(idx), ctypes.c_size_t(len(idx)), _p(out)), "zkhip_fri_query_dev")
+        ends = np.cumsum([0] + sizes)
+        return [out[ends[t]:ends[t + 1]].reshape(len(idx), b, 1 << (s - 1), 2, 4) for t, (_, _, b, s) in enumerate(sets)]
+
+    def merkle_paths_multi(self, trees, x_indices):
+        """per tree a (count, depth, 32) u8 array: the path of leaf x mod leaves(tree) for every query index, one launch and one copy for all trees"""
+        idx = np.ascontiguousarray(x_indices, dtype=np.uint64).reshape(-1)
+        handles = (ctypes.c_void_p * max(1, len(trees)))(*[t.h for t in trees])
+        sizes = [len(idx) * t.depth * 32 for t in trees]
+        out = np.zeros(sum(sizes), dtype=np.uint8)
+        self._check(self.lib.zkhip_merkle_paths_multi(self.h, handles, ctypes.c_size_t(len(trees)), _p(idx), ctypes.c_size_t(len(idx)), _p(out)),
+                    "zkhip_merkle_paths_multi")
+        ends = np.cumsum([0] + sizes)
+        return [out[ends[t]:ends[t + 1]].reshape(len(idx), tr.depth, 32) for t, tr in enumerate(trees)]
 
     # ---- proof of work (FRI grinding) over the SHA2-256 sequential transcript (zkhip_pow_grind)
     def pow_grind(self, state: bytes, start: int, mask: int, max_tries: int = 0, chunk_log: int = 0, hash_id: int = HASH_SHA2_256):

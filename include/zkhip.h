@@ -317,6 +317,34 @@ int zkhip_merkle_paths(zkhip_ctx *ctx, const zkhip_merkle *t, const uint64_t *le
                        uint8_t *out /* host, count x depth x 32 */);
 void zkhip_merkle_free(zkhip_ctx *ctx, zkhip_merkle *t);
 
+/* ---- The FRI query phase's answers (basic_fri.hpp:747-930), read from what is resident --------------------------------
+ * Both entries take the queries' domain indices on the host and return the answers on the host; each is ONE launch and ONE
+ * device-to-host copy, synchronised: the answers are in `out` when the call returns.  Neither takes a curve id: both gather
+ * canonical 32-byte values and compute nothing.
+ *
+ * zkhip_fri_query_dev: a SET is `batch` vectors of D = 2^log_domain canonical 4-limb elements at d_polys, laid out as
+ * zkhip_fri_leaves_dev takes them.  For query q the set uses x = x_indices[q] mod D; its answer for (q, polynomial p) is the
+ * 2^(fri_step - 1) pairs calculate_s walks from x (basic_fri.hpp:585-614): s_0 = x, then for the offsets D/4, D/8, ...
+ * s_i = (offset + s_j) mod D over the already placed j, each pair being (f[min(s_i, s_i + D/2 mod D)], f[max(...)]) -- the
+ * ind0 / ind1 rule of :815-818 and :892-895.  As a set of values that is leaf (x mod (D >> fri_step)) of zkhip_fri_leaves_dev,
+ * and in that leaf's own order when x < (D >> fri_step).
+ *   out        set-major: set t holds [q][p][i][2] elements of 4 u64 limbs, at element offset count * sum_{u<t} batch_u 2^(fri_step_u);
+ *   errors     (all before anything is launched) a null ctx, or with work to do a null sets / x_indices / out / d_polys or
+ *              batch == 0 -> ZKHIP_ERR_INVALID; fri_step < 1, fri_step > log_domain, log_domain > 32, batch >= 2^31, count >= 2^32 or
+ *              an index >= 2^(the largest log_domain among the sets) -> ZKHIP_ERR_RANGE;
+ *   count == 0 or n_sets == 0: ZKHIP_OK, nothing launched. */
+typedef struct { const void *d_polys; size_t log_domain; size_t batch; size_t fri_step; } zkhip_fri_query_set;
+int zkhip_fri_query_dev(zkhip_ctx *ctx, const zkhip_fri_query_set *sets, size_t n_sets,
+                        const uint64_t *x_indices /* host */, size_t count, uint64_t *out /* host */);
+/* zkhip_merkle_paths over several trees of the context at once: tree t answers leaf x_indices[q] mod leaves(t) -- the reduction
+ * get_folded_index makes per round (basic_fri.hpp:857-860, 868-874).
+ *   out        tree-major: [t][q][depth_t][32], byte for byte what zkhip_merkle_paths writes per tree for the reduced indices; a
+ *              one-leaf tree contributes no bytes;
+ *   errors     a null ctx, trees or tree, or with digests to write a null x_indices / out -> ZKHIP_ERR_INVALID;
+ *              count >= 2^32 -> ZKHIP_ERR_RANGE;   count == 0 or n_trees == 0: ZKHIP_OK, nothing launched. */
+int zkhip_merkle_paths_multi(zkhip_ctx *ctx, const zkhip_merkle *const *trees, size_t n_trees,
+                             const uint64_t *x_indices /* host */, size_t count, uint8_t *out /* host */);
+
 /* ---- Proof of work (FRI grinding) over the SHA2-256 sequential transcript, searched on the device ---------------------
  * proof_of_work<hashes::sha2<256>, std::uint32_t>::generate (commitments/detail/polynomial/proof_of_work.hpp:47-68), which
  * proof_eval<FRI> calls between its commit and query phases when fri_params.use_grinding is set (basic_fri.hpp:743-745), over
