@@ -13,6 +13,7 @@
 #include <thread>
 #include <vector>
 
+#include <nil/crypto3/zk/hip/kzg_v2.hpp>
 #include <nil/crypto3/zk/hip/lpc.hpp>
 #include <nil/crypto3/zk/hip/merkle.hpp>
 #include <nil/crypto3/zk/hip/placeholder_lookup.hpp>

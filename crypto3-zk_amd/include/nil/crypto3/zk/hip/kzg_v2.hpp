@@ -1,9 +1,9 @@
 //---------------------------------------------------------------------------//
 // zkhip shim: the batched KZG commitment scheme placeholder plugs in as `commitment_scheme_type`, on the MI355X.
 //
-// Mirrors zk/commitments/polynomial/kzg_v2.hpp (class kzg_commitment_scheme_v2, :56-360) on top of
-// zk/commitments/batched_commitment.hpp (class polys_evaluator, :58-249) and
-// zk/commitments/detail/polynomial/eval_storage.hpp:36-95 -- same member names, same call order:
+// Mirrors zk/commitments/polynomial/kzg_v2.hpp (class kzg_commitment_scheme_v2, :56-360) on top of the polys_evaluator and
+// eval_storage of polys_evaluator.hpp (batched_commitment.hpp:58-249, eval_storage.hpp:36-95), which the LPC scheme stands on
+// too -- same member names, same call order:
 //   append_to_batch / commit(batch) / append_eval_point[s] / set_batch_size / mark_batch_as_fixed /
 //   preprocess / setup / proof_eval(transcript), public `_z`.
 // What changes: every committed polynomial is transformed to coefficient form ONCE (commit: one batched inverse
@@ -26,46 +26,19 @@
 
 #include <algorithm>
 #include <array>
-#include <deque>
 #include <functional>
-#include <iterator>
 #include <map>
 #include <memory>
-#include <set>
-#include <tuple>
 #include <vector>
 
 #include "fri.hpp"
 #include "kzg.hpp"
+#include "polys_evaluator.hpp"
 
 namespace nil {
 namespace crypto3 {
 namespace zk {
 namespace hip {
-
-/// eval_storage (eval_storage.hpp:36-95)
-template <typename CurveType>
-class eval_storage_hip {
-    typedef typename curve_adapter<CurveType>::scalar_value_type value_type;
-    std::map<std::size_t, std::vector<std::vector<value_type>>> z;
-
-public:
-    bool operator==(const eval_storage_hip &other) const { return z == other.z; }
-    std::vector<std::size_t> get_batches() const {
-        std::vector<std::size_t> b;
-        for (const auto &it : z) b.push_back(it.first);
-        return b;
-    }
-    std::size_t get_batches_num() const { return z.size(); }
-    std::size_t get_batch_size(std::size_t batch_id) const { return z.at(batch_id).size(); }
-    std::size_t get_poly_points_number(std::size_t batch_id, std::size_t poly_id) const { return z.at(batch_id)[poly_id].size(); }
-    const std::vector<std::vector<value_type>> &get(std::size_t batch_id) const { return z.at(batch_id); }
-    const std::vector<value_type> &get(std::size_t batch_id, std::size_t poly_id) const { return z.at(batch_id)[poly_id]; }
-    const value_type &get(std::size_t batch_id, std::size_t poly_id, std::size_t point_id) const { return z.at(batch_id)[poly_id][point_id]; }
-    void set_batch_size(std::size_t batch_id, std::size_t batch_size) { z[batch_id].assign(batch_size, {}); }
-    void set_poly_points_number(std::size_t batch_id, std::size_t poly_id, std::size_t n) { z[batch_id][poly_id].assign(n, value_type::zero()); }
-    void set(std::size_t batch_id, std::size_t poly_id, std::size_t point_id, const value_type &v) { z[batch_id][poly_id][point_id] = v; }
-};
 
 namespace detail {
     /// dense host polynomials of a few coefficients (U, V, diffpoly): math::polynomial as far as proof_eval uses it
@@ -146,77 +119,50 @@ typename curve_adapter<CurveType>::g1_value_type kzg_proof_eval(const kzg_params
     return multiexp_dev<CurveType, ZKHIP_G1>(ctx, params.commitment_key, 0, f.size() - 1, static_cast<const char *>(d.get()) + 32);
 }
 
-/// What kzg_commitment_scheme (kzg.hpp:636-873) and kzg_commitment_scheme_v2 (kzg_v2.hpp:56-360) share: the polys_evaluator
-/// state (batched_commitment.hpp:58-249), commit(batch) with the coefficient forms left resident, eval_polys, get_U,
-/// the transcript update and the device helpers of the opening proofs.
-/// `PolynomialType` as in the reference's polys_evaluator (batched_commitment.hpp:56-64; default: the shim's own polynomial_dfs):
-/// anything with size() and operator[] over contiguous scalar_value_type -- math::polynomial_dfs as placeholder_prover hands it
-/// over (prover.hpp:137-138, 316) included.
+/// What kzg_commitment_scheme (kzg.hpp:636-873) and kzg_commitment_scheme_v2 (kzg_v2.hpp:56-360) add to the polys_evaluator
+/// (polys_evaluator.hpp: the batches, the points, `_z`, eval_polys): the parameters, resident polynomials as batch members,
+/// commit(batch) with the coefficient forms left resident, get_U, the transcript update and the device helpers of the opening proofs.
 template <typename CurveType, typename TranscriptType, typename PolynomialType = polynomial_dfs<CurveType>>
-class kzg_polys_evaluator_hip {
+class kzg_polys_evaluator_hip : public polys_evaluator_hip<CurveType, PolynomialType> {
     ZKHIP_REQUIRE_PAIRING(CurveType, "KZG");
-protected:
-    /// a committed batch on the device: the coefficient forms of its polynomials, one behind the other
-    struct device_batch {
-        std::shared_ptr<void> data;
-        std::vector<std::size_t> offset, len;    // in elements
-        void *at(std::size_t i) const { return static_cast<char *>(data.get()) + 32 * offset[i]; }
-    };
+    typedef polys_evaluator_hip<CurveType, PolynomialType> base;
 
 public:
-    typedef curve_adapter<CurveType> adapter;
+    typedef typename base::adapter adapter;
     typedef CurveType curve_type;
-    typedef typename adapter::scalar_value_type scalar_value_type;
+    typedef typename base::scalar_value_type scalar_value_type;
     typedef typename adapter::g1_value_type single_commitment_type;
     typedef std::vector<single_commitment_type> commitment_type;
     typedef TranscriptType transcript_type;
     typedef kzg_params_hip<CurveType> params_type;
-    typedef PolynomialType poly_type;
-    typedef eval_storage_hip<CurveType> eval_storage_type;
+    typedef typename base::poly_type poly_type;
+    typedef typename base::eval_storage_type eval_storage_type;
     typedef bool preprocessed_data_type;
     /// primitive 2^log_n-th root of unity of the evaluation domains (math::make_evaluation_domain's choice)
     typedef std::function<scalar_value_type(std::size_t log_n)> root_of_unity_type;
 
-    eval_storage_type _z;
+    using base::_z;
 
     kzg_polys_evaluator_hip(const params_type &kzg_params, root_of_unity_type root_of_unity) :
-        _params(kzg_params), _root_of_unity(std::move(root_of_unity)) { }
+        base(kzg_params.ctx), _params(kzg_params), _root_of_unity(std::move(root_of_unity)) { }
     /// the reference's constructor argument list (kzg.hpp:667, kzg_v2.hpp:94: the parameters alone): the roots of unity from the curve adapter
     explicit kzg_polys_evaluator_hip(const params_type &kzg_params) :
-        _params(kzg_params), _root_of_unity([](std::size_t log_n) { return adapter::root_of_unity(log_n); }) { }
+        base(kzg_params.ctx), _params(kzg_params), _root_of_unity([](std::size_t log_n) { return adapter::root_of_unity(log_n); }) { }
     /// Over a DEVICE GROUP: commit(batch) deals the batch's columns over the group's members (each transforms and commits its columns
     /// against its replica of the key; only commitments and -- device to device -- the coefficient forms travel to member 0), the rest
     /// of the scheme runs on member 0.  The reference's commit is a loop over the batch inside the call (kzg_v2.hpp:208-226): so is this.
     typedef kzg_params_group_hip<CurveType> group_params_type;
     kzg_polys_evaluator_hip(const group_params_type &group_params, root_of_unity_type root_of_unity) :
-        _params(group_params.root()), _root_of_unity(std::move(root_of_unity)), _group_params(&group_params) { }
+        base(group_params.root().ctx), _params(group_params.root()), _root_of_unity(std::move(root_of_unity)), _group_params(&group_params) { }
     explicit kzg_polys_evaluator_hip(const group_params_type &group_params) :
-        _params(group_params.root()), _root_of_unity([](std::size_t log_n) { return adapter::root_of_unity(log_n); }), _group_params(&group_params) { }
+        base(group_params.root().ctx), _params(group_params.root()), _root_of_unity([](std::size_t log_n) { return adapter::root_of_unity(log_n); }), _group_params(&group_params) { }
 
     const params_type &get_commitment_params() const { return _params; }
     preprocessed_data_type preprocess(transcript_type &) const { return true; }
     void setup(transcript_type &, preprocessed_data_type = true) { }
     void mark_batch_as_fixed(std::size_t) { }
 
-    // ---- polys_evaluator (batched_commitment.hpp:197-247) ----
-    /// as the reference: the scheme keeps a COPY of the polynomial (batched_commitment.hpp:197-206)
-    void append_to_batch(std::size_t index, const poly_type &poly) { own(index, poly_type(poly)); }
-    template <typename ContainerType>
-    void append_to_batch(std::size_t index, const ContainerType &polys) {
-        for (const auto &p : polys) append_one(index, p);
-    }
-    /// a caller that is done with the polynomials hands them over instead (50 x 2^20 rows: 340 ms of host copying saved) ...
-    void append_to_batch(std::size_t index, poly_type &&poly) { own(index, std::move(poly)); }
-    void append_to_batch(std::size_t index, std::vector<poly_type> &&polys) {
-        for (auto &p : polys) own(index, std::move(p));
-        polys.clear();
-    }
-    /// ... and one that keeps them alive until commit(index) returns LENDS them: std::cref(poly), or a container of
-    /// std::reference_wrapper<const poly_type> -- nothing is copied on the host, commit reads the caller's vectors where they lie
-    void append_to_batch(std::size_t index, std::reference_wrapper<const poly_type> poly) {
-        if (_locked[index]) throw std::runtime_error("append_to_batch: batch already committed");
-        _polys[index].push_back(&poly.get());
-    }
+    using base::append_to_batch;    // the host polynomials: copied, handed over or lent (polys_evaluator.hpp)
     /// A polynomial that is ALREADY resident (device_polynomial_dfs, fri.hpp: the quotient parts of placeholder_quotient.hpp, a
     /// witness column built on the device) joins the batch where it lies: commit copies it device-to-device instead of crossing PCIe.
     /// Not in the reference's interface -- an addition for callers that keep their columns on the GPU.
@@ -239,22 +185,6 @@ public:
     void append_to_batch(std::size_t index, const std::vector<device_polynomial_coefficients<CurveType>> &polys) {
         for (const auto &p : polys) append_to_batch(index, p);
     }
-    void append_eval_point(std::size_t batch_id, const scalar_value_type &point) {
-        for (auto &pts : _points.at(batch_id)) pts.push_back(point);
-    }
-    void append_eval_point(std::size_t batch_id, std::size_t poly_id, const scalar_value_type &point) { _points.at(batch_id).at(poly_id).push_back(point); }
-    void append_eval_points(std::size_t batch_id, const std::vector<scalar_value_type> &points) {
-        for (auto &pts : _points.at(batch_id)) pts.insert(pts.end(), points.begin(), points.end());
-    }
-    void append_eval_points(std::size_t batch_id, std::size_t poly_id, const std::vector<scalar_value_type> &points) {
-        auto &pts = _points.at(batch_id).at(poly_id);
-        pts.insert(pts.end(), points.begin(), points.end());
-    }
-    void set_batch_size(std::size_t batch_id, std::size_t batch_size) {
-        _points[batch_id].resize(batch_size);
-        _locked[batch_id] = true;
-    }
-
     /// commit(index) (kzg_v2.hpp:208-226): one commitment per polynomial of the batch; the coefficient forms stay
     /// on the device for proof_eval.
     commitment_type commit(std::size_t index) {
@@ -263,22 +193,15 @@ public:
         const auto &resident_c = _resident_coefficients[index];    // ... and already in coefficient form
         const std::size_t count = polys.size(), jl = 3 * adapter::g1_coord_limbs;
         device_batch db;
-        std::size_t total = 0;
         for (std::size_t i = 0; i < count; ++i) {
             const std::size_t sz = polys[i] ? polys[i]->size() : is_coefficients(index, i) ? resident_c.at(i).size() : resident.at(i).size();
             if (sz == 0 || (sz & (sz - 1))) throw std::runtime_error("commit: polynomial_dfs size must be a power of two");
             if (sz > _params.commitment_key.size()) throw std::runtime_error("commit: polynomial longer than the commitment key");
-            db.offset.push_back(total);
-            db.len.push_back(sz);
-            total += sz;
+            db.append(sz);
         }
-        db.data = _params.ctx.alloc(std::max<std::size_t>(1, total) * 32);
-        /* the caller's root-of-unity function is called from THIS thread only (it need not be thread-safe): one root per distinct size, up front */
-        root_map roots;
-        for (std::size_t i = 0; i < count; ++i) {
-            const std::size_t log_n = detail::ceil_log2(db.len[i]);
-            if (!is_coefficients(index, i) && !roots.count(log_n)) adapter::scalar_to_limbs(_root_of_unity(log_n), roots[log_n].data());
-        }
+        db.data = _params.ctx.alloc(std::max<std::size_t>(1, db.total) * 32);
+        root_map roots;    // a column that is in coefficient form already is not transformed: no root for its size
+        detail::add_roots<adapter>(roots, db, _root_of_unity, [&](std::size_t i) { return is_coefficients(index, i); });
         std::vector<std::uint64_t> res(count * jl);    // the Jacobian commitments
         if (_group_params && _group_params->members.size() > 1) commit_group(index, db, roots, res);
         else {
@@ -301,8 +224,8 @@ public:
     }
 
 private:
-    typedef std::map<std::size_t, std::array<std::uint64_t, 4>> root_map;    // log_n -> the limbs of the primitive 2^log_n-th root
-
+    typedef typename base::device_batch device_batch;
+    typedef typename base::root_map root_map;
     /* what commit(index) asks of the batch's columns; .at(): commit() has created the batch's entries (the member threads read them) */
     bool is_coefficients(std::size_t index, std::size_t i) const { return _resident_coefficients.at(index).count(i) != 0; }
     /// known to be the zero polynomial: its commitment is the neutral element, no multiexp
@@ -330,11 +253,10 @@ private:
         const auto &resident_c = _resident_coefficients.at(index);
         const std::size_t jl = 3 * adapter::g1_coord_limbs;
         auto at = [&](std::size_t p) { return base + 32 * (db.offset[p] - db.offset[lo]); };
-        for (std::size_t i = lo; i < hi;) {
-            const std::size_t limit = i == lo ? first_chunk : chunk;
+        /* a chunk: columns of one length and one kind (to be transformed or in coefficient form already, known to be zero or not) */
+        auto same_kind = [&](std::size_t i, std::size_t j) { return resident_c.count(i) == resident_c.count(j) && is_zero(index, i) == is_zero(index, j); };
+        db.for_each_run(lo, hi, first_chunk, chunk, [&](std::size_t i, std::size_t j) {
             const bool coefficients = resident_c.count(i) != 0, zero = is_zero(index, i);
-            std::size_t j = i;
-            while (j < hi && db.len[j] == db.len[i] && (resident_c.count(j) != 0) == coefficients && is_zero(index, j) == zero && (limit == 0 || j - i < limit)) ++j;
             for (std::size_t p = i; p < j; ++p) {
                 if (polys[p]) upload_scalars<adapter>(up, at(p), detail::poly_data<adapter>(*polys[p]), polys[p]->size());
                 else if (copy_resident)
@@ -358,19 +280,12 @@ private:
                 }
                 check(zkhip_msm_batch_dev(ctx.get(), cnt, qb.data(), qo.data(), qn.data(), qs.data(), qr.data()), "zkhip_msm_batch_dev", ctx.get());
             }
-            i = j;
-        }
+        }, same_kind);
     }
 
-    /// state_commited (batched_commitment.hpp:163-166).  The host polynomials are not read again: lent ones may go; copies and
-    /// handed-over ones are released with the scheme (freeing gigabytes of host memory here costs ~100 ms: more than the upload)
     commitment_type commit_done(std::size_t index, device_batch &&db, commitment_type &&out) {
-        const std::size_t count = _polys[index].size();
         _ind_commitments[index] = std::move(out);
-        _dev[index] = std::move(db);
-        _locked[index] = true;
-        _points[index].resize(count);
-        _polys[index].clear();    // no pointer to a lent polynomial outlives the call
+        this->state_commited(index, std::move(db));
         _resident[index].clear();
         _resident_coefficients[index].clear();
         return _ind_commitments[index];
@@ -384,25 +299,13 @@ private:
     void commit_group(std::size_t index, const device_batch &db, const root_map &roots, std::vector<std::uint64_t> &res) {
         const group_params_type &gp = *_group_params;
         const device_group &group = gp.group;
-        const std::size_t world = gp.members.size(), count = db.len.size(), jl = 3 * adapter::g1_coord_limbs;
-        /* member k's columns [lo, hi): a contiguous range, so its coefficient forms are ONE contiguous piece of the batch buffer */
-        struct part {
-            std::size_t lo = 0, hi = 0, elems = 0;
-            std::shared_ptr<void> data, d_res;    // data: the member's own buffer (member 0 works in the batch buffer itself)
-            char *base = nullptr;
-        };
-        std::vector<part> parts(world);
+        const std::size_t world = gp.members.size(), jl = 3 * adapter::g1_coord_limbs;
+        std::vector<detail::group_part> parts(world);
+        std::vector<std::shared_ptr<void>> d_res(world);
         for (std::size_t k = 0; k < world; ++k) {
-            part &pt = parts[k];
-            std::tie(pt.lo, pt.hi) = detail::even_range(count, world, k);
-            if (pt.hi == pt.lo) continue;
-            pt.elems = (pt.hi < count ? db.offset[pt.hi] : db.offset.back() + db.len.back()) - db.offset[pt.lo];
-            if (k == 0) pt.base = static_cast<char *>(db.at(pt.lo));
-            else {
-                pt.data = group[k].alloc(pt.elems * 32);
-                pt.base = static_cast<char *>(pt.data.get());
-            }
-            pt.d_res = group[k].alloc((pt.hi - pt.lo) * jl * 8);
+            const detail::group_part &pt = parts[k] = detail::deal_columns(db, group, k);
+            if (pt.empty()) continue;
+            d_res[k] = group[k].alloc((pt.hi - pt.lo) * jl * 8);
             /* resident polynomials: off member 0's GPU, in the order of this (the group's) thread */
             for (std::size_t p = pt.lo; p < pt.hi; ++p) {
                 if (_polys.at(index)[p]) continue;
@@ -412,19 +315,18 @@ private:
         }
         _member_up.resize(world);
         group.for_each_member([&](std::size_t k) {
-            const part &pt = parts[k];
-            if (pt.hi == pt.lo) return;
+            const detail::group_part &pt = parts[k];
+            if (pt.empty()) return;
             const context &ctx = group[k];
             const std::size_t mine = pt.hi - pt.lo, chunk = upload_chunk ? std::max<std::size_t>(1, std::min(upload_chunk, (mine + 2) / 3)) : 0;
             const bool pipelined = chunk != 0 && mine > chunk && has_host_columns(index, pt.lo, pt.hi);
             if (pipelined && !_member_up[k]) _member_up[k].reset(new context(ctx.device()));
-            commit_columns(index, db, pt.lo, pt.hi, pt.base, ctx, pipelined ? *_member_up[k] : ctx, gp.members[k]->commitment_key.get(), pt.d_res.get(), roots,
+            commit_columns(index, db, pt.lo, pt.hi, pt.base, ctx, pipelined ? *_member_up[k] : ctx, gp.members[k]->commitment_key.get(), d_res[k].get(), roots,
                            pipelined ? chunk : 0, pipelined ? chunk : 0, false);
-            ctx.d2h(res.data() + pt.lo * jl, pt.d_res.get(), mine * jl * 8);    // synchronises this member's stream (its upload stream has drained: every upload is a synchronous copy)
+            ctx.d2h(res.data() + pt.lo * jl, d_res[k].get(), mine * jl * 8);    // synchronises this member's stream (its upload stream has drained: every upload is a synchronous copy)
         });
         /* the other members' coefficient forms join the batch on member 0 (xGMI peer copies; proof_eval reads them there) */
-        for (std::size_t k = 1; k < world; ++k)
-            if (parts[k].hi != parts[k].lo) group.copy(0, db.at(parts[k].lo), k, parts[k].base, parts[k].elems * 32);
+        for (std::size_t k = 1; k < world; ++k) detail::gather_form(db, group, k, parts[k]);
         _params.ctx.sync();    // the copies ran on member 0's stream: the members' buffers may go
     }
 public:
@@ -444,13 +346,6 @@ protected:
         if (!_upload_ctx) _upload_ctx.reset(new context(_params.ctx.device()));
         return *_upload_ctx;
     }
-    void own(std::size_t index, poly_type &&poly) {
-        if (_locked[index]) throw std::runtime_error("append_to_batch: batch already committed");
-        _owned[index].push_back(std::move(poly));
-        _polys[index].push_back(&_owned[index].back());
-    }
-    void append_one(std::size_t index, const poly_type &p) { own(index, poly_type(p)); }
-    void append_one(std::size_t index, std::reference_wrapper<const poly_type> p) { append_to_batch(index, p); }
     single_commitment_type commit_range(const void *d_coeffs, std::size_t len) const {
         if (len == 0) return single_commitment_type::zero();
         if (len > _params.commitment_key.size()) throw std::runtime_error("proof_eval: quotient longer than the commitment key");
@@ -515,45 +410,9 @@ protected:
         len -= 1;
     }
 
-    /// eval_polys (batched_commitment.hpp:168-183): every polynomial of a batch at the union of the batch's points
-    void eval_polys() {
-        const context &ctx = _params.ctx;
-        for (const auto &it : _dev) {
-            const std::size_t k = it.first;
-            const device_batch &db = it.second;
-            const auto &point = _points.at(k);
-            _z.set_batch_size(k, db.len.size());
-            std::vector<scalar_value_type> uni;
-            for (const auto &pl : point)
-                for (const auto &x : pl)
-                    if (std::find(uni.begin(), uni.end(), x) == uni.end()) uni.push_back(x);
-            std::vector<std::uint64_t> pts(4 * uni.size());
-            for (std::size_t j = 0; j < uni.size(); ++j) adapter::scalar_to_limbs(uni[j], &pts[4 * j]);
-            for (std::size_t i = 0; i < db.len.size();) {
-                std::size_t j = i;
-                while (j < db.len.size() && db.len[j] == db.len[i]) ++j;
-                std::vector<std::uint64_t> vals(4 * (j - i) * uni.size());
-                if (!uni.empty())
-                    check(zkhip_poly_eval_dev(ctx.get(), adapter::id, db.at(i), db.len[i], db.len[i], j - i, pts.data(), uni.size(), vals.data()),
-                          "zkhip_poly_eval_dev", ctx.get());
-                for (std::size_t p = i; p < j; ++p) {
-                    _z.set_poly_points_number(k, p, point[p].size());
-                    for (std::size_t q = 0; q < point[p].size(); ++q) {
-                        const std::size_t u = std::find(uni.begin(), uni.end(), point[p][q]) - uni.begin();
-                        _z.set(k, p, q, adapter::scalar_from_limbs(&vals[4 * ((p - i) * uni.size() + u)]));
-                    }
-                }
-                i = j;
-            }
-        }
-    }
     /// merge_eval_points (kzg_v2.hpp:121-130)
     void merge_eval_points() {
-        _merged_points.clear();
-        for (const auto &it : _points)
-            for (const auto &pl : it.second)
-                for (const auto &x : pl)
-                    if (std::find(_merged_points.begin(), _merged_points.end(), x) == _merged_points.end()) _merged_points.push_back(x);
+        _merged_points = this->unique_points();
         std::sort(_merged_points.begin(), _merged_points.end(), detail::limbs_less<scalar_value_type>);
     }
     /// set_difference_polynom (kzg_v2.hpp:132-148)
@@ -591,16 +450,15 @@ protected:
 
     const params_type &_params;
     root_of_unity_type _root_of_unity;
-    std::map<std::size_t, std::vector<const poly_type *>> _polys;    // in append order: copies held in _owned, or the caller's (lent)
-    std::map<std::size_t, std::deque<poly_type>> _owned;             // a deque: references stay valid as it grows
+    using base::_polys;    // a resident polynomial stands in it as nullptr, at its position
+    using base::_locked;
+    using base::_points;
+    using base::_dev;
+    using base::_upload_ctx;
     std::map<std::size_t, std::map<std::size_t, device_polynomial_dfs<CurveType>>> _resident;    // batch -> position -> resident polynomial
     std::map<std::size_t, std::map<std::size_t, device_polynomial_coefficients<CurveType>>> _resident_coefficients;    // ... in coefficient form
-    std::map<std::size_t, bool> _locked;
-    std::map<std::size_t, std::vector<std::vector<scalar_value_type>>> _points;
-    std::map<std::size_t, device_batch> _dev;
     std::map<std::size_t, commitment_type> _ind_commitments;
     std::vector<scalar_value_type> _merged_points;
-    mutable std::unique_ptr<context> _upload_ctx;
     std::vector<std::unique_ptr<context>> _member_up;    // over a device group: each member's upload stream (created on first use, same GPU)
     const group_params_type *_group_params = nullptr;    // set: commit(batch) deals its columns over this group's members
     mutable std::size_t _group_multiexps = 0;

@@ -2,8 +2,8 @@
 // zkhip shim: the LPC (list polynomial commitment, FRI-based) scheme placeholder plugs in as `commitment_scheme_type`,
 // with every polynomial-sized step on the MI355X.
 //
-// Mirrors zk/commitments/polynomial/lpc.hpp (class lpc_commitment_scheme, :50-300) on top of
-// zk/commitments/batched_commitment.hpp (polys_evaluator, :58-249) and the commit phase of
+// Mirrors zk/commitments/polynomial/lpc.hpp (class lpc_commitment_scheme, :50-300) on top of the polys_evaluator of
+// polys_evaluator.hpp (batched_commitment.hpp:58-249, shared with the KZG schemes of kzg_v2.hpp) and the commit phase of
 // algorithms::proof_eval<FRI> (zk/commitments/detail/polynomial/basic_fri.hpp:666-742) -- same member names, same call
 // order: append_to_batch / commit(batch) / append_eval_point[s] / set_batch_size / mark_batch_as_fixed /
 // preprocess / setup / proof_eval(transcript), public `_z`, `is_lpc()`.
@@ -27,7 +27,7 @@
 //             span       b(ptr, total_elements, elements_per_leaf) over a page-locked buffer the scheme keeps (one copy at link speed);
 //             vector     b(const std::vector<value_type> &leaves, elements_per_leaf), as round 2 (a vector the scheme keeps).
 //           transcript:
-//           duck-typed on VALUES like kzg_v2.hpp (transcript(root), transcript.challenge()).
+//           duck-typed on VALUES like the KZG schemes' (transcript(root), transcript.challenge()).
 //   device  the QUERY phase of proof_eval<FRI> (basic_fri.hpp:747-930: fri_params.lambda openings at transcript-derived indices), behind names of
 //           its own -- proof_eval keeps its statements, its transcript traffic and its result:
 //             query_phase(transcript, proof)   after proof_eval on the same object; fills proof.fri_proof.query_proofs.  Everything it reads is
@@ -62,19 +62,15 @@
 #include <cstdlib>
 #include <cstdio>
 #include <chrono>
-#include <deque>
 #include <functional>
-#include <iterator>
 #include <map>
 #include <memory>
-#include <set>
-#include <tuple>
 #include <type_traits>
 #include <utility>
 #include <vector>
 
 #include "fri.hpp"
-#include "kzg_v2.hpp"
+#include "polys_evaluator.hpp"
 #include "proof_of_work.hpp"
 
 namespace nil {
@@ -228,19 +224,22 @@ namespace detail {
     }
 }    // namespace detail
 
+/// The batches, the points, `_z` and eval_polys: polys_evaluator.hpp.  Host polynomials only: commit reads every one through its pointer.
 /// `PolynomialType`: as for the KZG schemes (batched_commitment.hpp:56-64) -- size() and operator[] over contiguous scalars.
 template <typename CurveType, typename TranscriptType, typename TreeBuilder, typename PolynomialType = polynomial_dfs<CurveType>>
-class lpc_commitment_scheme_hip {
+class lpc_commitment_scheme_hip : public polys_evaluator_hip<CurveType, PolynomialType> {
+    typedef polys_evaluator_hip<CurveType, PolynomialType> base;
+
 public:
     static constexpr bool is_lpc() { return true; }
 
-    typedef curve_adapter<CurveType> adapter;
+    typedef typename base::adapter adapter;
     typedef CurveType curve_type;
-    typedef typename adapter::scalar_value_type value_type;
+    typedef typename base::scalar_value_type value_type;
     typedef fri_params_hip<CurveType> params_type;
     typedef TranscriptType transcript_type;
-    typedef PolynomialType poly_type;
-    typedef eval_storage_hip<CurveType> eval_storage_type;
+    typedef typename base::poly_type poly_type;
+    typedef typename base::eval_storage_type eval_storage_type;
     static constexpr detail::tree_builder_kind builder_kind =
         detail::is_device_builder<TreeBuilder>::value
             ? detail::tree_builder_kind::device
@@ -276,10 +275,10 @@ public:
         fri_proof_type fri_proof;
     };
 
-    eval_storage_type _z;
+    using base::_z;
 
     lpc_commitment_scheme_hip(const context &ctx, const params_type &fri_params, TreeBuilder builder) :
-        _ctx(ctx), _fri_params(fri_params), _builder(std::move(builder)), _etha(value_type::zero()) {
+        base(ctx), _fri_params(fri_params), _builder(std::move(builder)), _etha(value_type::zero()) {
         std::size_t r = 0;
         for (std::size_t s : fri_params.step_list) r += s;
         if (fri_params.step_list.empty() || r > fri_params.log_domain) throw std::invalid_argument("lpc: step_list does not fit the domain");
@@ -302,7 +301,7 @@ public:
         preprocessed_data_type result;
         for (const auto &it : _batch_fixed) {
             if (!it.second) continue;
-            result[it.first] = evaluate_batch_at(it.first, etha);
+            result[it.first] = this->evaluate_batch_at(it.first, etha);
         }
         return result;
     }
@@ -313,73 +312,28 @@ public:
     /// Should be done after commitment (lpc.hpp:109-111)
     void mark_batch_as_fixed(std::size_t index) { _batch_fixed[index] = true; }
 
-    // ---- polys_evaluator (batched_commitment.hpp:197-247) ----
-    /// as the reference: the scheme keeps a COPY of the polynomial (batched_commitment.hpp:197-206)
-    void append_to_batch(std::size_t index, const poly_type &poly) { own(index, poly_type(poly)); }
-    template <typename ContainerType>
-    void append_to_batch(std::size_t index, const ContainerType &polys) {
-        for (const auto &p : polys) append_one(index, p);
-    }
-    /// hand the polynomials over instead of copying them, or LEND them (std::cref: alive until commit(index) returns) -- see kzg_v2.hpp
-    void append_to_batch(std::size_t index, poly_type &&poly) { own(index, std::move(poly)); }
-    void append_to_batch(std::size_t index, std::vector<poly_type> &&polys) {
-        for (auto &p : polys) own(index, std::move(p));
-        polys.clear();
-    }
-    void append_to_batch(std::size_t index, std::reference_wrapper<const poly_type> poly) {
-        if (_locked[index]) throw std::runtime_error("append_to_batch: batch already committed");
-        _polys[index].push_back(&poly.get());
-    }
-    void append_eval_point(std::size_t batch_id, const value_type &point) {
-        for (auto &pts : _points.at(batch_id)) pts.push_back(point);
-    }
-    void append_eval_point(std::size_t batch_id, std::size_t poly_id, const value_type &point) { _points.at(batch_id).at(poly_id).push_back(point); }
-    void append_eval_points(std::size_t batch_id, const std::vector<value_type> &points) {
-        for (auto &pts : _points.at(batch_id)) pts.insert(pts.end(), points.begin(), points.end());
-    }
-    void append_eval_points(std::size_t batch_id, std::size_t poly_id, const std::vector<value_type> &points) {
-        auto &pts = _points.at(batch_id).at(poly_id);
-        pts.insert(pts.end(), points.begin(), points.end());
-    }
-    void set_batch_size(std::size_t batch_id, std::size_t batch_size) {
-        _points[batch_id].resize(batch_size);
-        _locked[batch_id] = true;
-    }
-
     /// commit(index) (lpc.hpp:101-106): precommit<FRI>(polys, D[0], step_list.front()) -> the tree's root
     commitment_type commit(std::size_t index) {
         ZKHIP_PROFILE_SCOPE("Basic FRI Precommit time");    // commit = precommit<FRI> + root (lpc.hpp:101-106; the scope of basic_fri.hpp:449)
-        const std::vector<const poly_type *> &polys = _polys[index];
-        _locked[index] = true;    // state_commited (batched_commitment.hpp:163-166)
-        _points[index].resize(polys.size());
+        const std::vector<const poly_type *> &polys = this->_polys[index];
         device_batch db;
-        std::size_t total = 0;
         for (const poly_type *p : polys) {
             if (p->size() == 0 || (p->size() & (p->size() - 1)) || p->size() > domain_size(0)) throw std::runtime_error("lpc commit: bad polynomial size");
-            db.offset.push_back(total);
-            db.len.push_back(p->size());
-            total += p->size();
+            db.append(p->size());
         }
-        db.data = _ctx.alloc(std::max<std::size_t>(1, total) * 32);
+        db.data = _ctx.alloc(std::max<std::size_t>(1, db.total) * 32);
         const std::size_t D = domain_size(0), count = polys.size();
-        /* the caller's root-of-unity function is called from THIS thread only: one root per distinct size, up front */
-        root_map roots;
+        root_map roots;    // D[0]'s root first, then one per distinct size
         adapter::scalar_to_limbs(_fri_params.root_of_unity(_fri_params.log_domain), roots[_fri_params.log_domain].data());
-        for (std::size_t i = 0; i < count; ++i) {
-            const std::size_t log_n = detail::ceil_log2(db.len[i]);
-            if (!roots.count(log_n)) adapter::scalar_to_limbs(_fri_params.root_of_unity(log_n), roots[log_n].data());
-        }
+        detail::add_roots<adapter>(roots, db, _fri_params.root_of_unity);
         if (_group && _group->size() > 1 && count) commit_group(index, polys, db, roots);
         else {
             char *d_ext = static_cast<char *>(_scratch_ext.reserve(_ctx, std::max<std::size_t>(1, count) * D * 32));    // kept across commits: no GB-sized hipMalloc per batch
-            extend_columns(polys, db, 0, count, static_cast<char *>(db.data.get()), _ctx, _upload_ctx, d_ext, roots);
+            extend_columns(polys, db, 0, count, static_cast<char *>(db.data.get()), _ctx, this->_upload_ctx, d_ext, roots);
             _trees.erase(index);
             _trees.emplace(index, build_tree(d_ext, count, _fri_params.log_domain, _fri_params.step_list.front()));
         }
-        _dev[index] = std::move(db);
-        /* the host polynomials are not read again: lent ones may go; copies and handed-over ones are released with the scheme (freeing
-           gigabytes of host memory here would cost more than the commit's device work) */
-        _polys[index].clear();    // no pointer to a lent polynomial outlives the call
+        this->state_commited(index, std::move(db));
         return _trees.at(index).root();
     }
 
@@ -393,12 +347,11 @@ public:
     std::size_t leaf_slice_elements = (std::size_t)1 << 21;
 
 protected:
-    struct device_batch {
-        std::shared_ptr<void> data;    // after commit: the coefficient forms
-        std::vector<std::size_t> offset, len;
-        void *at(std::size_t i) const { return static_cast<char *>(data.get()) + 32 * offset[i]; }
-    };
-    typedef std::map<std::size_t, std::array<std::uint64_t, 4>> root_map;    // log_n -> the limbs of the primitive 2^log_n-th root
+    typedef typename base::device_batch device_batch;
+    typedef typename base::root_map root_map;
+    using base::_ctx;
+    using base::_points;
+    using base::_dev;
 
     /// poly.resize(D[0]->size()) (basic_fri.hpp:452-455) for polys [lo, hi) of a batch on `ctx`, one call per chunk of equally sized
     /// polynomials: uploaded into `base` (polynomial p at base + 32 (offset[p] - offset[lo])), where the call leaves the COEFFICIENTS proof_eval
@@ -411,17 +364,14 @@ protected:
         if (pipelined && !up) up.reset(new context(ctx.device()));
         const context &upc = pipelined ? *up : ctx;
         auto at = [&](std::size_t p) { return base + 32 * (db.offset[p] - db.offset[lo]); };
-        for (std::size_t i = lo; i < hi;) {
-            std::size_t j = i;
-            while (j < hi && db.len[j] == db.len[i] && (upload_chunk == 0 || j - i < upload_chunk)) ++j;
+        db.for_each_run(lo, hi, upload_chunk, upload_chunk, [&](std::size_t i, std::size_t j) {
             for (std::size_t p = i; p < j; ++p) upload_scalars<adapter>(upc, at(p), detail::poly_data<adapter>(*polys[p]), polys[p]->size());
             if (pipelined) ctx.wait_for(upc);
             const std::size_t log_n = detail::ceil_log2(db.len[i]);
             check(zkhip_poly_resize_dev(ctx.get(), adapter::id, at(i), log_n, j - i, roots.at(log_n).data(), d_ext + 32 * (i - lo) * D, _fri_params.log_domain,
                                         roots.at(_fri_params.log_domain).data()),
                   "zkhip_poly_resize_dev", ctx.get());
-            i = j;
-        }
+        });
     }
 
     /// commit(index) over the device group.  Member k takes the k-th contiguous range of the batch's polynomials: its host thread uploads them
@@ -440,33 +390,21 @@ protected:
         std::size_t log_owners = 0;    // owners: a power of two (the compact domain is one), every owner with at least one leaf
         while (((std::size_t)2 << log_owners) <= world && _fri_params.log_domain >= step + log_owners + 1) ++log_owners;
         const std::size_t owners = (std::size_t)1 << log_owners, Ds = D >> log_owners, seg = Ds >> step, rows_per_poly = (std::size_t)1 << step;
-        struct part {
-            std::size_t lo = 0, hi = 0, elems = 0;
-            std::shared_ptr<void> data;    // the member's own coefficient buffer (member 0 works in the batch buffer itself)
-            char *base = nullptr;
-        };
-        std::vector<part> parts(world);
+        std::vector<detail::group_part> parts(world);
         for (std::size_t k = 0; k < world; ++k) {
-            part &pt = parts[k];
-            std::tie(pt.lo, pt.hi) = detail::even_range(count, world, k);
             group_scratch &gs = _gs[k];
             if (k < owners) {
                 gs.cmp.reserve(group[k], count * Ds * 32);
                 gs.leaves.reserve(group[k], count * Ds * 32);
             }
-            if (pt.hi == pt.lo) continue;
-            pt.elems = (pt.hi < count ? db.offset[pt.hi] : db.offset.back() + db.len.back()) - db.offset[pt.lo];
-            if (k == 0) pt.base = static_cast<char *>(db.at(pt.lo));
-            else {
-                pt.data = group[k].alloc(pt.elems * 32);
-                pt.base = static_cast<char *>(pt.data.get());
-            }
+            const detail::group_part &pt = parts[k] = detail::deal_columns(db, group, k);
+            if (pt.empty()) continue;
             gs.ext.reserve(group[k], (pt.hi - pt.lo) * D * 32);
             gs.send.reserve(group[k], (pt.hi - pt.lo) * D * 32);    // owners blocks of (hi - lo) * Ds
         }
         group.for_each_member([&](std::size_t k) {
-            const part &pt = parts[k];
-            if (pt.hi == pt.lo) return;
+            const detail::group_part &pt = parts[k];
+            if (pt.empty()) return;
             const context &ctx = group[k];
             group_scratch &gs = _gs[k];
             const std::size_t mine = pt.hi - pt.lo;
@@ -482,14 +420,14 @@ protected:
         });
         /* the exchange, from this thread: blocks to their owners, coefficient forms to member 0 */
         for (std::size_t k = 0; k < world; ++k) {
-            const part &pt = parts[k];
-            if (pt.hi == pt.lo) continue;
+            const detail::group_part &pt = parts[k];
+            if (pt.empty()) continue;
             const std::size_t mine = pt.hi - pt.lo;
             for (std::size_t d = 0; d < owners; ++d)
                 if (d != k)
                     group.copy(d, static_cast<char *>(_gs[d].cmp.get()) + 32 * pt.lo * Ds, k, static_cast<const char *>(_gs[k].send.get()) + 32 * d * mine * Ds,
                                mine * Ds * 32);
-            if (k != 0) group.copy(0, db.at(pt.lo), k, pt.base, pt.elems * 32);
+            detail::gather_form(db, group, k, pt);
         }
         std::vector<const void *> d_leaves(owners);
         for (std::size_t d = 0; d < owners; ++d) {
@@ -517,7 +455,7 @@ public:
             std::fprintf(stderr, "lpc proof_eval phase %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - tp).count());
             tp = now;
         };
-        eval_polys();
+        this->eval_polys();
         lap("eval_polys");
         for (const auto &it : _trees) transcript(it.second.root());
 
@@ -553,7 +491,7 @@ public:
             }
             _ctx.sync();    // d_c is released on return
         };
-        for (const auto &point : get_unique_points()) {
+        for (const auto &point : this->unique_points()) {
             std::vector<const void *> ptrs;
             std::vector<std::size_t> lens;
             std::vector<std::uint64_t> coeffs;
@@ -847,7 +785,7 @@ public:
             for (std::size_t j = 0; j < z.get_batch_size(i); ++j)
                 if (z.get_poly_points_number(i, j) != pt->second[j].size()) return false;
         }
-        for (const auto &point : get_unique_points()) {
+        for (const auto &point : this->unique_points()) {
             opening o {point, value_type::zero(), theta_acc, {}};
             for (std::size_t i : z.get_batches())
                 for (std::size_t j = 0; j < z.get_batch_size(i); ++j) {
@@ -1148,69 +1086,6 @@ protected:
             return _conv.data();
         }
     }
-    void own(std::size_t index, poly_type &&poly) {
-        if (_locked[index]) throw std::runtime_error("append_to_batch: batch already committed");
-        _owned[index].push_back(std::move(poly));
-        _polys[index].push_back(&_owned[index].back());
-    }
-    void append_one(std::size_t index, const poly_type &p) { own(index, poly_type(p)); }
-    void append_one(std::size_t index, std::reference_wrapper<const poly_type> p) { append_to_batch(index, p); }
-    std::vector<value_type> evaluate_batch_at(std::size_t k, const value_type &x) const {
-        const device_batch &db = _dev.at(k);
-        std::vector<value_type> out(db.len.size());
-        std::uint64_t pt[4];
-        adapter::scalar_to_limbs(x, pt);
-        for (std::size_t i = 0; i < db.len.size();) {
-            std::size_t j = i;
-            while (j < db.len.size() && db.len[j] == db.len[i]) ++j;
-            std::vector<std::uint64_t> vals(4 * (j - i));
-            check(zkhip_poly_eval_dev(_ctx.get(), adapter::id, db.at(i), db.len[i], db.len[i], j - i, pt, 1, vals.data()), "zkhip_poly_eval_dev", _ctx.get());
-            for (std::size_t p = i; p < j; ++p) out[p] = adapter::scalar_from_limbs(&vals[4 * (p - i)]);
-            i = j;
-        }
-        return out;
-    }
-    /// eval_polys (batched_commitment.hpp:168-183)
-    void eval_polys() {
-        for (const auto &it : _dev) {
-            const std::size_t k = it.first;
-            const device_batch &db = it.second;
-            const auto &point = _points.at(k);
-            _z.set_batch_size(k, db.len.size());
-            std::vector<value_type> uni;
-            for (const auto &pl : point)
-                for (const auto &x : pl)
-                    if (std::find(uni.begin(), uni.end(), x) == uni.end()) uni.push_back(x);
-            std::vector<std::uint64_t> pts(4 * uni.size());
-            for (std::size_t j = 0; j < uni.size(); ++j) adapter::scalar_to_limbs(uni[j], &pts[4 * j]);
-            for (std::size_t i = 0; i < db.len.size();) {
-                std::size_t j = i;
-                while (j < db.len.size() && db.len[j] == db.len[i]) ++j;
-                std::vector<std::uint64_t> vals(4 * (j - i) * uni.size());
-                if (!uni.empty())
-                    check(zkhip_poly_eval_dev(_ctx.get(), adapter::id, db.at(i), db.len[i], db.len[i], j - i, pts.data(), uni.size(), vals.data()),
-                          "zkhip_poly_eval_dev", _ctx.get());
-                for (std::size_t p = i; p < j; ++p) {
-                    _z.set_poly_points_number(k, p, point[p].size());
-                    for (std::size_t q = 0; q < point[p].size(); ++q) {
-                        const std::size_t u = std::find(uni.begin(), uni.end(), point[p][q]) - uni.begin();
-                        _z.set(k, p, q, adapter::scalar_from_limbs(&vals[4 * ((p - i) * uni.size() + u)]));
-                    }
-                }
-                i = j;
-            }
-        }
-    }
-    /// get_unique_points (batched_commitment.hpp:113-129): first-seen order over batches, polynomials, points
-    std::vector<value_type> get_unique_points() const {
-        std::vector<value_type> result;
-        for (const auto &it : _points)
-            for (const auto &point_set : it.second)
-                for (const auto &point : point_set)
-                    if (std::find(result.begin(), result.end(), point) == result.end()) result.push_back(point);
-        return result;
-    }
-
     /// per member of the group, kept across commits: extensions, blocks to send, the owner's compact evaluations and its leaves
     struct group_scratch {
         device_scratch ext, send, cmp, leaves;
@@ -1224,22 +1099,16 @@ protected:
     };
     bool _time_query_phase = false;
     query_phase_times _last_query_times;
-    const context &_ctx;
     const device_group *_group = nullptr;
     std::size_t _group_commits = 0, _last_owners = 0;
     mutable std::unique_ptr<group_scratch[]> _gs;    // an array: the page-locked buffers neither copy nor move
     params_type _fri_params;
     mutable TreeBuilder _builder;
     value_type _etha;
-    std::map<std::size_t, std::vector<const poly_type *>> _polys;    // in append order: copies held in _owned, or the caller's (lent)
-    std::map<std::size_t, std::deque<poly_type>> _owned;
-    mutable std::unique_ptr<context> _upload_ctx;    // the second stream the uploads of commit() ride on
     mutable pinned_buffer _pin[2];
     mutable std::vector<value_type> _leaf_vec, _conv;
     mutable device_scratch _scratch_ext, _scratch_leaves;    // kept across commits (every use is ordered on _ctx's stream)
-    std::map<std::size_t, bool> _locked, _batch_fixed;
-    std::map<std::size_t, std::vector<std::vector<value_type>>> _points;
-    std::map<std::size_t, device_batch> _dev;
+    std::map<std::size_t, bool> _batch_fixed;
     std::map<std::size_t, precommitment_type> _trees;
     preprocessed_data_type _fixed_polys_values;
     std::vector<precommitment_type> _fri_trees;

@@ -21,6 +21,8 @@
 #include <nil/crypto3/zk/hip/proof_of_work.hpp>
 #include <nil/crypto3/zk/hip/transcript.hpp>
 
+#include "eval_polys_case.hpp"
+
 using namespace nil::crypto3::zk::hip;
 
 // every member of the placeholder classes, for both curves
@@ -224,6 +226,16 @@ int multiexp_t(const std::uint64_t *pts, const std::uint8_t *inf, const std::uin
     return 0;
 }
 
+/// eval_polys_case.hpp through lpc_commitment_scheme_hip (vector host builder, 2^6-point domain, step list {1, 1}, no grinding)
+template <typename Curve>
+int eval_polys_case_t(const std::uint64_t *evals, const std::uint64_t *points, std::uint64_t *out_z) {
+    typedef sha256_transcript<Curve> transcript_type;
+    context ctx(0);
+    lpc_commitment_scheme_hip<Curve, transcript_type, vector_builder<Curve>> scheme(ctx, fri_params_hip<Curve>::standard(6, {1, 1}), vector_builder<Curve>());
+    transcript_type tr(std::vector<std::uint8_t> {'e', 'v', 'a', 'l'});
+    return eval_polys_case::run(scheme, tr, evals, points, out_z);
+}
+
 }    // namespace
 
 #define PASTA_DISPATCH(curve, call)                     \
@@ -267,6 +279,13 @@ int pasta_lpc_run(int curve, int builder, const std::uint64_t *evals, std::size_
                   std::uint64_t *counts) {
     const lpc_out out = {commit_root, fri_roots, state, final_poly, alphas, z, counts, nonce};
 #define CALL(C) lpc_run_t<C>(builder, evals, npolys, log_rows, log_domain, steps, nsteps, point, init, init_len, mask, out)
+    PASTA_DISPATCH(curve, CALL)
+#undef CALL
+}
+
+/// the shared eval_polys case (eval_polys_case.hpp) through the LPC scheme: proof.z, 9 elements
+int pasta_eval_polys_case(int curve, const std::uint64_t *evals, const std::uint64_t *points, std::uint64_t *out_z) {
+#define CALL(C) eval_polys_case_t<C>(evals, points, out_z)
     PASTA_DISPATCH(curve, CALL)
 #undef CALL
 }

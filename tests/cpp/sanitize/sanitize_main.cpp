@@ -21,6 +21,7 @@
 #include <vector>
 
 #include <nil/crypto3/zk/hip/column_polynomial.hpp>
+#include <nil/crypto3/zk/hip/kzg_v2.hpp>
 #include <nil/crypto3/zk/hip/lpc.hpp>
 #include <nil/crypto3/zk/hip/marshalling.hpp>
 #include <nil/crypto3/zk/hip/placeholder_arguments.hpp>
@@ -204,6 +205,39 @@ struct stream_builder {
     toy_tree finish() { return t; }
 };
 
+/// The batch rules every scheme has from the shared polys_evaluator (polys_evaluator.hpp), on a fresh scheme object.  The stub computes
+/// nothing: this checks ownership and state only.
+template <typename Scheme, typename Poly>
+void batch_state_rules(Scheme &s, const Poly &poly) {
+    typedef typename Scheme::adapter::scalar_value_type Fr;
+    auto throws = [](auto call) {
+        try {
+            call();
+        } catch (const std::exception &) {
+            return true;
+        }
+        return false;
+    };
+    EXPECT(throws([&] { s.append_eval_point(0, Fr(1)); }));    // an uncommitted batch has no points yet (.at)
+    std::vector<Poly> handed(2, poly);
+    s.append_to_batch(0, std::move(handed));
+    EXPECT(handed.empty());    // vector &&: taken over
+    {   /* a lent polynomial may go as soon as commit has returned: proof_eval below must not read it (ASan) */
+        std::unique_ptr<Poly> lent(new Poly(poly));
+        s.append_to_batch(0, std::cref(*lent));
+        (void)s.commit(0);
+    }
+    EXPECT(throws([&] { s.append_to_batch(0, poly); }));    // a committed batch refuses every kind of append
+    EXPECT(throws([&] { s.append_to_batch(0, Poly(poly)); }));
+    EXPECT(throws([&] { s.append_to_batch(0, std::cref(poly)); }));
+    EXPECT(throws([&] { s.append_to_batch(0, std::vector<Poly>(1, poly)); }));
+    s.append_eval_point(0, Fr(9));
+    any_transcript tr;
+    (void)s.proof_eval(tr);
+    s.set_batch_size(4, 1);    // the verifier's way to size a batch: it locks it too
+    EXPECT(throws([&] { s.append_to_batch(4, poly); }));
+}
+
 template <typename Curve>
 void scheme_host_paths() {
     typedef curve_adapter<Curve> A;
@@ -307,6 +341,16 @@ void scheme_host_paths() {
     run_lpc_group(vec_builder<Fr>(), 2);
     run_lpc_group(span_builder<Fr>(), 3);
     run_lpc_group(stream_builder<Fr>(), 9);
+    {   /* the shared batch rules, scheme by scheme */
+        std::vector<typename A::g1_value_type> ck(600, A::g1_value_type::zero());
+        kzg_params_hip<Curve> params(ctx, ck.begin(), ck.end());
+        kzg_commitment_scheme_v2_hip<Curve, any_transcript> v2(params, root);
+        batch_state_rules(v2, polys[0]);
+        kzg_commitment_scheme_hip<Curve, any_transcript> v1(params, root);
+        batch_state_rules(v1, polys[0]);
+        lpc_commitment_scheme_hip<Curve, any_transcript, vec_builder<Fr>> lpc(ctx, fp, vec_builder<Fr>());
+        batch_state_rules(lpc, polys[0]);
+    }
 }
 
 /// the host logic of placeholder's arguments and quotient chain over the stub backend (device buffers are host memory the stub only sizes and

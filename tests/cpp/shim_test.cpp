@@ -27,6 +27,8 @@
 #include <nil/crypto3/zk/hip/r1cs_gg_ppzksnark.hpp>
 #include <nil/crypto3/zk/hip/r1cs_gg_ppzksnark_generator.hpp>
 
+#include "eval_polys_case.hpp"
+
 using namespace nil::crypto3::zk::hip;
 
 namespace {
@@ -2064,6 +2066,29 @@ int groth16_generate_prove_t(size_t M, size_t n, size_t N, const uint32_t *const
     return 0;
 }
 
+/// eval_polys_case.hpp through kzg_commitment_scheme_v2_hip and through lpc_commitment_scheme_hip (vector tree builder, 2^6-point domain, step
+/// list {1, 1}): the evaluations each proof carries.  challenges: three (theta and theta_2 of KZG; theta and two alphas of LPC)
+template <typename Curve>
+int eval_polys_case_t(const uint64_t *srs, size_t n_srs, const uint64_t *evals, const uint64_t *points, const uint64_t *challenges, uint64_t *out_kzg,
+                      uint64_t *out_lpc) {
+    typedef curve_adapter<Curve> A;
+    typedef typename A::g1_value_type G1;
+    const size_t L1 = 2 * A::g1_coord_limbs;
+    context ctx(0);
+    scripted_any_transcript<Curve> tr_kzg, tr_lpc;
+    for (size_t i = 0; i < 3; ++i) tr_kzg.challenges.push_back(A::scalar_from_limbs(challenges + 4 * i));
+    tr_lpc.challenges = tr_kzg.challenges;
+    std::vector<G1> ck;
+    for (size_t i = 0; i < n_srs; ++i) ck.push_back(G1::from_affine(srs + i * L1));
+    kzg_params_hip<Curve> params(ctx, ck.begin(), ck.end());
+    kzg_commitment_scheme_v2_hip<Curve, scripted_any_transcript<Curve>> kzg(params);
+    if (int rc = eval_polys_case::run(kzg, tr_kzg, evals, points, out_kzg)) return rc;
+    lpc_commitment_scheme_hip<Curve, scripted_any_transcript<Curve>, toy_tree_builder<Curve>> lpc(ctx, fri_params_hip<Curve>::standard(6, {1, 1}),
+                                                                                                 toy_tree_builder<Curve>());
+    if (int rc = eval_polys_case::run(lpc, tr_lpc, evals, points, out_lpc)) return rc - 100;
+    return 0;
+}
+
 extern "C" {
 
 int shim_host_small_poly(int curve, const uint64_t *xs, const uint64_t *ys, size_t k, const uint64_t *at, uint64_t *u_at, uint64_t *u_coeffs,
@@ -2270,6 +2295,11 @@ int shim_lpc_scheme(int curve, const uint64_t *evals, size_t npolys, const uint6
                     uint64_t *out_fri_roots, uint64_t *out_final, uint64_t *out_counts) {
     CURVE_CALL("shim_lpc_scheme", lpc_scheme_t, evals, npolys, log_n, log_domain, steps, nsteps, roots, points, challenges, nchallenges, out_roots, out_z,
                out_fri_roots, out_final, out_counts)
+}
+
+int shim_eval_polys_case(int curve, const uint64_t *srs, size_t n_srs, const uint64_t *evals, const uint64_t *points, const uint64_t *challenges, uint64_t *out_kzg,
+                         uint64_t *out_lpc) {
+    CURVE_CALL("shim_eval_polys_case", eval_polys_case_t, srs, n_srs, evals, points, challenges, out_kzg, out_lpc)
 }
 
 int shim_kzg_placeholder_contract(int curve, const uint64_t *srs, size_t n_srs, const uint64_t *evals, size_t npolys, size_t log_n, const uint64_t *roots,

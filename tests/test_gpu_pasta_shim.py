@@ -103,3 +103,13 @@ def test_multiexp_of_300_points(harness, curve):  # noqa: F811
     two = [pts[0], pts[0]]
     assert harness.pasta_multiexp(curve, P(pts_arr(curve, 1, two)), None, P(fr_arr([5, C.r - 5])), ctypes.c_size_t(2), P(out), ctypes.byref(oinf)) == 0
     assert oinf.value == 1
+
+
+def test_eval_polys_shared_case_lpc_pallas(harness):  # noqa: F811
+    """the eval_polys case tests/test_gpu_shim.py runs through KZG and LPC (tests/cpp/eval_polys_case.hpp), through LPC over Pallas: proof.z
+    equals po.poly_eval entry by entry"""
+    from util import eval_polys_case
+    evals, points, want = eval_polys_case(pu.CURVES[pu.PALLAS_ID], 8802)
+    out = np.zeros((len(want), 4), dtype=np.uint64)
+    assert harness.pasta_eval_polys_case(pu.PALLAS_ID, P(evals), P(points), P(out)) == 0
+    assert fr_ints(out) == want

@@ -1602,3 +1602,22 @@ def test_prepare_lookup_input_flat(shim, curve, log_n):
     assert [int(x) for x in sizes[0::2]] == [len(w) for w in want] == [2 * n, 4 * n, n]
     assert [int(x) for x in sizes[1::2]] == [2 * (n - 1), 3 * (n - 1), n - 1]
     assert (out == np.concatenate(want)).all()
+
+
+@pytest.mark.parametrize("curve", [0, 1])
+def test_eval_polys_shared_by_kzg_and_lpc(shim, curve):
+    """eval_polys of the polys_evaluator both commitment schemes stand on: the same polynomials and point sets (tests/cpp/eval_polys_case.hpp)
+    through kzg_commitment_scheme_v2_hip and through lpc_commitment_scheme_hip (vector tree builder, log_domain 6, step list {1, 1}); the
+    proof.z of each equals po.poly_eval entry by entry.  Batch 0: lengths 2^3, 2^3, 2^5, 2^3 (a run of two, broken, resumed) with ragged
+    point sets whose union is none of them; batch 2: one polynomial of 2^4 at a point of batch 0."""
+    from util import eval_polys_case
+    C = CURVES[curve]
+    evals, points, want = eval_polys_case(C, 8800 + curve)
+    rng = po.SplitMix64(8810 + curve)
+    challenges = fr_arr([rng.next_mod(C.r) for _ in range(3)])
+    srs = _srs(curve, 7, 64)
+    out_kzg = np.zeros((len(want), 4), dtype=np.uint64)
+    out_lpc = np.zeros((len(want), 4), dtype=np.uint64)
+    assert shim.shim_eval_polys_case(curve, P(srs), ctypes.c_size_t(64), P(evals), P(points), P(challenges), P(out_kzg), P(out_lpc)) == 0
+    assert fr_ints(out_kzg) == want
+    assert fr_ints(out_lpc) == want

@@ -126,3 +126,22 @@ def permutation_instance(C, rng, log_n, k, usable):
     cols = [[val[(i, j)] if j < usable else rng.next_mod(r) for j in range(n)] for i in range(k)]
     S_sigma = [[labels[sigma[(i, j)][0]][sigma[(i, j)][1]] if j < usable else labels[i][j] for j in range(n)] for i in range(k)]
     return cols, labels, S_sigma
+
+
+EVAL_POLYS_CASE_LOGS = (3, 3, 5, 3, 4)
+
+
+def eval_polys_case(C, seed):
+    """tests/cpp/eval_polys_case.hpp: five polynomials of 2^3, 2^3, 2^5, 2^3, 2^4 random evaluations, batch 0 = the first four opened at
+    {a, b}, {b}, {a, b, c}, {c, a}, batch 2 = the last opened at a.  -> (evaluations as limbs, a | b | c as limbs, the expected proof.z in
+    (batch, polynomial, point) order: the coefficient forms by the oracle's inverse transform, evaluated by po.poly_eval)"""
+    r = C.r
+    rng = po.SplitMix64(seed)
+    a, b, c = (rng.next_mod(r) for _ in range(3))
+    polys = [[rng.next_mod(r) for _ in range(1 << lg)] for lg in EVAL_POLYS_CASE_LOGS]
+    sets = [[a, b], [b], [a, b, c], [c, a], [a]]
+    want = []
+    for lg, e, s in zip(EVAL_POLYS_CASE_LOGS, polys, sets):
+        coeffs = po.intt(e, C.root_of_unity(lg), r)
+        want += [po.poly_eval(coeffs, x, r) for x in s]
+    return fr_arr([v for e in polys for v in e]), fr_arr([a, b, c]), want
