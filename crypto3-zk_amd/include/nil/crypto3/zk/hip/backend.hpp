@@ -74,6 +74,9 @@ inline void check(int rc, const char *what, const zkhip_ctx *ctx = nullptr) {
         throw std::runtime_error(msg);
     }
 }
+/// zkhip_fn(ctx.get(), args...) checked under the entry point's own name, `ctx` a context (a macro: only a macro takes the label from the
+/// callee).  Plain check() stays where the label is deliberate or there is no context object to name.
+#define ZKHIP_CALL(ctx, zkhip_fn, ...) ::nil::crypto3::zk::hip::check(zkhip_fn((ctx).get(), __VA_ARGS__), #zkhip_fn, (ctx).get())
 
 /// One context per GPU per process.  There is no CPU fallback: construction throws without a GPU.
 class context {
@@ -244,7 +247,7 @@ public:
     void *reserve(const context &ctx, std::size_t bytes) {
         if (bytes > cap_) {
             release();
-            check(zkhip_host_alloc(ctx.get(), bytes, &p_), "zkhip_host_alloc", ctx.get());
+            ZKHIP_CALL(ctx, zkhip_host_alloc, bytes, &p_);
             ctx_ = ctx.get();
             cap_ = bytes;
         }
@@ -367,7 +370,7 @@ public:
             }
         }
         size_ = inf.size();
-        check(zkhip_bases_upload(ctx.get(), adapter::id, Group, xy.data(), inf.data(), size_, &b_), "zkhip_bases_upload", ctx.get());
+        ZKHIP_CALL(ctx, zkhip_bases_upload, adapter::id, Group, xy.data(), inf.data(), size_, &b_);
     }
     /// bases[i] = scalars[i] * G computed on the device (fixed-base batch exponentiation, generator.hpp:187-214)
     template <typename ScalarIt>
@@ -380,7 +383,7 @@ public:
         device_bases r;
         r.ctx_ = &ctx;
         r.size_ = s.size() / 4;
-        check(zkhip_bases_from_scalars(ctx.get(), adapter::id, Group, nullptr, s.data(), r.size_, &r.b_), "zkhip_bases_from_scalars", ctx.get());
+        ZKHIP_CALL(ctx, zkhip_bases_from_scalars, adapter::id, Group, nullptr, s.data(), r.size_, &r.b_);
         return r;
     }
     /// from `n` compressed wire encodings (48 bytes per G1 point, 96 per G2 point), decoded on the device
@@ -388,7 +391,7 @@ public:
         device_bases r;
         r.ctx_ = &ctx;
         r.size_ = n;
-        check(zkhip_bases_upload_compressed(ctx.get(), adapter::id, Group, octets, n, &r.b_), "zkhip_bases_upload_compressed", ctx.get());
+        ZKHIP_CALL(ctx, zkhip_bases_upload_compressed, adapter::id, Group, octets, n, &r.b_);
         return r;
     }
     /// these points at the rows d_rows[j] (device array of size() u32; nullptr: the consecutive rows first + j) of an object of
@@ -397,7 +400,7 @@ public:
         device_bases r;
         r.ctx_ = ctx_;
         r.size_ = n_total;
-        check(zkhip_bases_spread(ctx_->get(), b_, static_cast<const std::uint32_t *>(d_rows), first, n_total, &r.b_), "zkhip_bases_spread", ctx_->get());
+        ZKHIP_CALL(*ctx_, zkhip_bases_spread, b_, static_cast<const std::uint32_t *>(d_rows), first, n_total, &r.b_);
         return r;
     }
     /// the Lagrange basis of the rows offset .. offset + 2^log_m, out[j] = (1/m) sum_i omega^(-i j) row[offset + i], as a new object with
@@ -409,7 +412,7 @@ public:
         device_bases r;
         r.ctx_ = ctx_;
         r.size_ = (std::size_t)1 << log_m;
-        check(zkhip_bases_lagrange(ctx_->get(), b_, offset, log_m, w, &r.b_), "zkhip_bases_lagrange", ctx_->get());
+        ZKHIP_CALL(*ctx_, zkhip_bases_lagrange, b_, offset, log_m, w, &r.b_);
         return r;
     }
     /// out[i] = coeff * ratio^(first_exponent + i) * row[offset + i], i < n (coeff == nullptr: 1), as a new object (zkhip_bases_scale_geometric:
@@ -422,8 +425,7 @@ public:
         device_bases out;
         out.ctx_ = ctx_;
         out.size_ = n;
-        check(zkhip_bases_scale_geometric(ctx_->get(), b_, offset, n, r, coeff ? c : nullptr, first_exponent, flags, &out.b_), "zkhip_bases_scale_geometric",
-              ctx_->get());
+        ZKHIP_CALL(*ctx_, zkhip_bases_scale_geometric, b_, offset, n, r, coeff ? c : nullptr, first_exponent, flags, &out.b_);
         return out;
     }
     /// host copies of all entries as group values (one download)
@@ -432,7 +434,7 @@ public:
         const std::size_t cl = Group == ZKHIP_G1 ? adapter::g1_coord_limbs : adapter::g2_coord_limbs;
         std::vector<std::uint64_t> xy(std::max<std::size_t>(1, size_) * 2 * cl);
         std::vector<std::uint8_t> inf(std::max<std::size_t>(1, size_));
-        if (size_) check(zkhip_bases_download(ctx_->get(), b_, 0, size_, xy.data(), inf.data()), "zkhip_bases_download", ctx_->get());
+        if (size_) ZKHIP_CALL(*ctx_, zkhip_bases_download, b_, 0, size_, xy.data(), inf.data());
         std::vector<G> out;
         out.reserve(size_);
         for (std::size_t i = 0; i < size_; ++i) out.push_back(G::from_affine(&xy[i * 2 * cl], inf[i] != 0));
@@ -444,7 +446,7 @@ public:
         const std::size_t cl = Group == ZKHIP_G1 ? adapter::g1_coord_limbs : adapter::g2_coord_limbs;
         std::vector<std::uint64_t> xy(2 * cl);
         std::uint8_t inf = 0;
-        check(zkhip_bases_download(ctx_->get(), b_, i, 1, xy.data(), &inf), "zkhip_bases_download", ctx_->get());
+        ZKHIP_CALL(*ctx_, zkhip_bases_download, b_, i, 1, xy.data(), &inf);
         return G::from_affine(xy.data(), inf != 0);
     }
     /// a copy of these bases on ANOTHER context -- another GPU of a device group (an SRS replicated over the members): through the
@@ -453,11 +455,11 @@ public:
         const std::size_t cl = Group == ZKHIP_G1 ? adapter::g1_coord_limbs : adapter::g2_coord_limbs;
         std::vector<std::uint64_t> xy(std::max<std::size_t>(1, size_) * 2 * cl);
         std::vector<std::uint8_t> inf(std::max<std::size_t>(1, size_));
-        if (size_) check(zkhip_bases_download(ctx_->get(), b_, 0, size_, xy.data(), inf.data()), "zkhip_bases_download", ctx_->get());
+        if (size_) ZKHIP_CALL(*ctx_, zkhip_bases_download, b_, 0, size_, xy.data(), inf.data());
         device_bases r;
         r.ctx_ = &other;
         r.size_ = size_;
-        check(zkhip_bases_upload(other.get(), adapter::id, Group, xy.data(), inf.data(), size_, &r.b_), "zkhip_bases_upload", other.get());
+        ZKHIP_CALL(other, zkhip_bases_upload, adapter::id, Group, xy.data(), inf.data(), size_, &r.b_);
         return r;
     }
     /// a second handle on the SAME resident points (they are read-only once built): for another prover lane on the same GPU

@@ -19,7 +19,7 @@
 #include <utility>
 #include <vector>
 
-#include "backend.hpp"
+#include "fr_vector.hpp"
 
 namespace nil {
 namespace crypto3 {
@@ -183,10 +183,8 @@ public:
     std::vector<value_type> evaluate_all_lagrange_polynomials(const context &ctx, const value_type &t) const {
         if (compute_vanishing_polynomial(t).is_zero()) throw std::invalid_argument("evaluate_all_lagrange_polynomials: t lies in the evaluation domain");
         const zkhip_domain d = c_desc();
-        std::uint64_t tl[4];
-        adapter::scalar_to_limbs(t, tl);
         auto d_u = ctx.alloc(m * 32);
-        check(zkhip_domain_lagrange_dev(ctx.get(), adapter::id, &d, tl, d_u.get()), "zkhip_domain_lagrange_dev", ctx.get());
+        ZKHIP_CALL(ctx, zkhip_domain_lagrange_dev, adapter::id, &d, limbs_of<adapter>(t).data(), d_u.get());
         std::vector<value_type> u;
         download_scalars<adapter>(ctx, d_u.get(), m, u);
         return u;
@@ -220,9 +218,7 @@ public:
 private:
     void run(const context &ctx, void *d_data, std::size_t batch, int inverse, const value_type *coset) const {
         const zkhip_domain d = c_desc();
-        std::uint64_t g[4];
-        if (coset) adapter::scalar_to_limbs(*coset, g);
-        check(zkhip_domain_fft_dev(ctx.get(), adapter::id, &d, d_data, batch, inverse, coset ? g : nullptr), "zkhip_domain_fft_dev", ctx.get());
+        ZKHIP_CALL(ctx, zkhip_domain_fft_dev, adapter::id, &d, d_data, batch, inverse, coset ? limbs_of<adapter>(*coset).data() : nullptr);
     }
     static void batch_invert(std::vector<value_type> &v) {
         std::vector<value_type> pre(v.size());

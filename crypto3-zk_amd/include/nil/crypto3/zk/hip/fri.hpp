@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "scoped_profiler.hpp"
+#include "fr_vector.hpp"
 #include "kzg.hpp"
 
 namespace nil {
@@ -36,6 +37,7 @@ public:
     typedef curve_adapter<CurveType> adapter;
     typedef typename adapter::scalar_value_type value_type;
     typedef std::function<value_type(std::size_t log_n)> root_of_unity_type;
+    typedef fr_vector<CurveType> fv;
 
     device_polynomial_dfs(const context &ctx, std::size_t size) :
         ctx_(&ctx), size_(size), degree_(size ? size - 1 : 0), d_(ctx.alloc(std::max<std::size_t>(1, size) * 32)) { }
@@ -95,7 +97,7 @@ public:
         clear_extension_cache();
         if (!view_) return;
         auto d_new = ctx_->alloc(std::max<std::size_t>(1, size_) * 32);
-        check(zkhip_memcpy_d2d_async(ctx_->get(), d_new.get(), d_.get(), size_ * 32), "zkhip_memcpy_d2d_async", ctx_->get());
+        fv::copy(*ctx_, d_new.get(), d_.get(), size_);
         d_ = d_new;    // the cache keeps the old buffer alive; the copy is ordered before whatever this stream does next
         view_ = false;
     }
@@ -114,17 +116,14 @@ public:
         const std::size_t lo = log2_exact(size_), ln = log2_exact(new_size);
         if (ln < lo && degree_ >= new_size) throw std::runtime_error("device_polynomial_dfs::resize: the polynomial's degree does not fit the smaller domain");
         auto d_new = ctx_->alloc(new_size * 32);
-        std::uint64_t wo[4], wn[4];
-        adapter::scalar_to_limbs(root(lo), wo);
-        adapter::scalar_to_limbs(root(ln), wn);
         /* growing consumes its input (zkhip_poly_resize_dev leaves the coefficients there) and copies of this object
            share the buffer: work on a private copy */
         std::shared_ptr<void> src = d_;
         if (ln > lo) {
             src = ctx_->alloc(size_ * 32);
-            check(zkhip_memcpy_d2d_async(ctx_->get(), src.get(), d_.get(), size_ * 32), "zkhip_memcpy_d2d_async", ctx_->get());
+            fv::copy(*ctx_, src.get(), d_.get(), size_);
         }
-        check(zkhip_poly_resize_dev(ctx_->get(), adapter::id, src.get(), lo, 1, wo, d_new.get(), ln, wn), "zkhip_poly_resize_dev", ctx_->get());
+        fv::resize(*ctx_, src.get(), lo, 1, root(lo), d_new.get(), ln, root(ln));
         ctx_->sync();    // the temporaries are released below
         d_ = d_new;
         size_ = new_size;
@@ -134,33 +133,29 @@ public:
     /// coefficients(): inverse NTT into a new device buffer of size() elements
     std::shared_ptr<void> coefficients(const root_of_unity_type &root) const {
         auto d_c = ctx_->alloc(std::max<std::size_t>(1, size_) * 32);
-        check(zkhip_memcpy_d2d_async(ctx_->get(), d_c.get(), d_.get(), size_ * 32), "zkhip_memcpy_d2d_async", ctx_->get());
-        std::uint64_t w[4];
-        adapter::scalar_to_limbs(root(log2_exact(size_)), w);
-        check(zkhip_ntt_dev(ctx_->get(), adapter::id, d_c.get(), log2_exact(size_), 1, w, 1, nullptr), "zkhip_ntt_dev", ctx_->get());
+        fv::copy(*ctx_, d_c.get(), d_.get(), size_);
+        fv::ntt(*ctx_, d_c.get(), log2_exact(size_), 1, root(log2_exact(size_)), true);
         return d_c;
     }
     /// from_coefficients(): the evaluations of the polynomial whose size() coefficients are at d_coeffs
     void from_coefficients(const void *d_coeffs, const root_of_unity_type &root) {
         make_writable();
-        check(zkhip_memcpy_d2d_async(ctx_->get(), d_.get(), d_coeffs, size_ * 32), "zkhip_memcpy_d2d_async", ctx_->get());
-        std::uint64_t w[4];
-        adapter::scalar_to_limbs(root(log2_exact(size_)), w);
-        check(zkhip_ntt_dev(ctx_->get(), adapter::id, d_.get(), log2_exact(size_), 1, w, 0, nullptr), "zkhip_ntt_dev", ctx_->get());
+        fv::copy(*ctx_, d_.get(), d_coeffs, size_);
+        fv::ntt(*ctx_, d_.get(), log2_exact(size_), 1, root(log2_exact(size_)), false);
         ctx_->sync();
     }
     device_polynomial_dfs &operator+=(const device_polynomial_dfs &o) {
         degree_ = std::max(degree_, o.degree_);
-        return pointwise(0, o);
+        return pointwise(fr_op::add, o);
     }
     device_polynomial_dfs &operator-=(const device_polynomial_dfs &o) {
         degree_ = std::max(degree_, o.degree_);
-        return pointwise(1, o);
+        return pointwise(fr_op::sub, o);
     }
     /// pointwise product on the shared domain (the caller resized first, as the reference's operator*= does internally)
     device_polynomial_dfs &operator*=(const device_polynomial_dfs &o) {
         degree_ = std::min(size_ ? size_ - 1 : 0, degree_ + o.degree_);
-        return pointwise(2, o);
+        return pointwise(fr_op::mul, o);
     }
 
 private:
@@ -169,10 +164,10 @@ private:
         if (n == 0 || ((std::size_t)1 << l) != n) throw std::runtime_error("device_polynomial_dfs: size must be a power of two");
         return l;
     }
-    device_polynomial_dfs &pointwise(int op, const device_polynomial_dfs &o) {
+    device_polynomial_dfs &pointwise(fr_op op, const device_polynomial_dfs &o) {
         make_writable();    // the values change in place: cached extensions go, a view gets its own buffer first
         if (o.size_ != size_) throw std::runtime_error("device_polynomial_dfs: operands must share the domain (resize first)");
-        check(zkhip_fr_vec_op_dev(ctx_->get(), adapter::id, op, d_.get(), o.d_.get(), d_.get(), size_), "zkhip_fr_vec_op_dev", ctx_->get());
+        fv::pointwise(*ctx_, op, d_.get(), o.d_.get(), d_.get(), size_);
         return *this;
     }
 
@@ -217,7 +212,6 @@ private:
 template <typename CurveType>
 device_polynomial_dfs<CurveType> polynomial_product(std::vector<device_polynomial_dfs<CurveType>> multipliers,
                                                     const typename device_polynomial_dfs<CurveType>::root_of_unity_type &root, std::size_t min_size = 0) {
-    typedef curve_adapter<CurveType> adapter;
     if (multipliers.empty()) throw std::invalid_argument("polynomial_product: no factors");
     const context &ctx = multipliers[0].ctx();
     std::size_t degree = 0, size = 1;
@@ -230,7 +224,7 @@ device_polynomial_dfs<CurveType> polynomial_product(std::vector<device_polynomia
     }
     device_polynomial_dfs<CurveType> out(ctx, size);
     out.set_degree(degree);
-    check(zkhip_fr_vec_prod_dev(ctx.get(), adapter::id, ptrs.size(), ptrs.data(), out.data(), size), "zkhip_fr_vec_prod_dev", ctx.get());
+    fr_vector<CurveType>::product(ctx, ptrs, out.data(), size);
     ctx.sync();    // the resized copies are released on return
     return out;
 }
@@ -245,8 +239,7 @@ device_polynomial_dfs<CurveType> polynomial_shift(const device_polynomial_dfs<Cu
     const std::size_t log_size = detail::ceil_log2(f.size());
     device_polynomial_dfs<CurveType> out(f.ctx(), f.size());
     out.set_degree(f.degree());
-    check(zkhip_poly_shift_dev(f.ctx().get(), f.data(), log_size, (std::int64_t)shift * (std::int64_t)(f.size() / domain_size), out.data()),
-          "zkhip_poly_shift_dev", f.ctx().get());
+    fr_vector<CurveType>::shift(f.ctx(), f.data(), log_size, (std::int64_t)shift * (std::int64_t)(f.size() / domain_size), out.data());
     return out;
 }
 
@@ -255,14 +248,102 @@ device_polynomial_dfs<CurveType> polynomial_shift(const device_polynomial_dfs<Cu
 template <typename CurveType>
 device_polynomial_dfs<CurveType> fold_polynomial(const device_polynomial_dfs<CurveType> &f, const typename curve_adapter<CurveType>::scalar_value_type &alpha,
                                                  const typename curve_adapter<CurveType>::scalar_value_type &omega) {
-    typedef curve_adapter<CurveType> adapter;
     const std::size_t log_size = detail::ceil_log2(f.size());
     device_polynomial_dfs<CurveType> out(f.ctx(), f.size() / 2);
-    std::uint64_t a[4], w[4];
-    adapter::scalar_to_limbs(alpha, a);
-    adapter::scalar_to_limbs(omega, w);
-    check(zkhip_fri_fold_dev(f.ctx().get(), adapter::id, f.data(), log_size, a, w, out.data()), "zkhip_fri_fold_dev", f.ctx().get());
+    fr_vector<CurveType>::fold(f.ctx(), f.data(), log_size, alpha, omega, out.data());
     return out;
+}
+
+/// the smallest power of two that holds a polynomial of this degree
+inline std::size_t pow2_holding(std::size_t degree) {
+    std::size_t size = 1;
+    while (size < degree + 1) size <<= 1;
+    return size;
+}
+
+namespace detail {
+    /// a op b on the larger of the two domains, into a buffer of its own (copies of a device_polynomial_dfs share their buffer: never in place)
+    template <typename CurveType>
+    device_polynomial_dfs<CurveType> combine(fr_op op, device_polynomial_dfs<CurveType> a, device_polynomial_dfs<CurveType> b,
+                                             const typename device_polynomial_dfs<CurveType>::root_of_unity_type &root) {
+        const std::size_t size = std::max(a.size(), b.size());
+        a.resize(size, root);
+        b.resize(size, root);
+        device_polynomial_dfs<CurveType> out(a.ctx(), size);
+        out.set_degree(std::max(a.degree(), b.degree()));
+        fr_vector<CurveType>::pointwise(a.ctx(), op, a.data(), b.data(), out.data(), size);
+        a.ctx().sync();    // a and b are released on return
+        return out;
+    }
+}    // namespace detail
+
+/// a + b on the larger of the two domains, into a buffer of its own
+template <typename CurveType>
+device_polynomial_dfs<CurveType> plus(const device_polynomial_dfs<CurveType> &a, const device_polynomial_dfs<CurveType> &b,
+                                      const typename device_polynomial_dfs<CurveType>::root_of_unity_type &root) {
+    return detail::combine(fr_op::add, a, b, root);
+}
+/// a - b likewise
+template <typename CurveType>
+device_polynomial_dfs<CurveType> minus(const device_polynomial_dfs<CurveType> &a, const device_polynomial_dfs<CurveType> &b,
+                                       const typename device_polynomial_dfs<CurveType>::root_of_unity_type &root) {
+    return detail::combine(fr_op::sub, a, b, root);
+}
+/// p *= c, in place (a view of a cached extension gets a buffer of its own first; p's own cached extensions go)
+template <typename CurveType>
+void scale(device_polynomial_dfs<CurveType> &p, const typename curve_adapter<CurveType>::scalar_value_type &c) {
+    p.make_writable();
+    fr_vector<CurveType>::scale(p.ctx(), p.data(), c, p.data(), p.size());
+}
+/// a x + b y + c over x's domain, into a buffer of its own; y may be null: a x + c
+template <typename CurveType>
+device_polynomial_dfs<CurveType> affine(const device_polynomial_dfs<CurveType> &x, const device_polynomial_dfs<CurveType> *y,
+                                        const typename curve_adapter<CurveType>::scalar_value_type &a, const typename curve_adapter<CurveType>::scalar_value_type &b,
+                                        const typename curve_adapter<CurveType>::scalar_value_type &c) {
+    if (y && y->size() != x.size()) throw std::invalid_argument("affine: operands must share the domain");
+    device_polynomial_dfs<CurveType> out(x.ctx(), x.size());
+    out.set_degree(y ? std::max(x.degree(), y->degree()) : x.degree());
+    fr_vector<CurveType>::affine(x.ctx(), x.data(), y ? y->data() : nullptr, a, b, c, out.data(), x.size());
+    return out;
+}
+/// every (size / n)-th evaluation of p: its values on the n-point sub-domain (lookup_argument.hpp:498-517, reduce_dfs_polynomial_domain).
+/// Unlike resize() this does not look at the degree; p itself where it already lives there.
+template <typename CurveType>
+device_polynomial_dfs<CurveType> subsample(const device_polynomial_dfs<CurveType> &p, std::size_t n) {
+    if (n == 0 || n > p.size() || p.size() % n) throw std::invalid_argument("subsample: not a sub-domain of the polynomial's");
+    if (p.size() == n) return p;
+    const std::size_t lp = detail::ceil_log2(p.size()), ln = detail::ceil_log2(n);
+    if (((std::size_t)1 << lp) != p.size() || ((std::size_t)1 << ln) != n) throw std::invalid_argument("subsample: sizes must be powers of two");
+    device_polynomial_dfs<CurveType> out(p.ctx(), n);
+    fr_vector<CurveType>::subsample(p.ctx(), p.data(), lp, out.data(), ln);
+    return out;
+}
+/// q_last + q_blind: on the n-point domain, or -- when both hold extension caches (preprocessed selectors) -- directly on the `size`-point one
+/// their sum is multiplied on afterwards: two cached extensions and one addition instead of a transform
+template <typename CurveType>
+device_polynomial_dfs<CurveType> selector_sum(const device_polynomial_dfs<CurveType> &q_last, const device_polynomial_dfs<CurveType> &q_blind, std::size_t size,
+                                              const typename device_polynomial_dfs<CurveType>::root_of_unity_type &root) {
+    const bool cached = q_last.extension_cache_enabled() && q_blind.extension_cache_enabled();
+    const device_polynomial_dfs<CurveType> a = cached ? q_last.extension(size, root) : q_last, b = cached ? q_blind.extension(size, root) : q_blind;
+    device_polynomial_dfs<CurveType> q(a.ctx(), a.size());
+    q.set_degree(std::max(q_last.degree(), q_blind.degree()));
+    fr_vector<CurveType>::pointwise(a.ctx(), fr_op::add, a.data(), b.data(), q.data(), a.size());
+    return q;
+}
+/// the intermediate polynomial of a part of the multi-part permutation / lookup arguments (ph/permutation_argument.hpp:193-199):
+/// current[j] = previous[j] g[j] / h[j] for j < usable_rows over the n-row domain (g, h subsampled to it), `fill`'s values behind them
+template <typename CurveType>
+device_polynomial_dfs<CurveType> multiplied_up(const device_polynomial_dfs<CurveType> &previous, const device_polynomial_dfs<CurveType> &fill,
+                                               const device_polynomial_dfs<CurveType> &g, const device_polynomial_dfs<CurveType> &h, std::size_t n,
+                                               std::size_t usable_rows) {
+    const context &ctx = previous.ctx();
+    device_polynomial_dfs<CurveType> current(ctx, n);
+    current.set_degree(n - 1);
+    fr_vector<CurveType>::copy(ctx, current.data(), fill.data(), n);
+    device_polynomial_dfs<CurveType> rg = subsample(g, n), rh = subsample(h, n);
+    fr_vector<CurveType>::mul_div(ctx, previous.data(), rg.data(), rh.data(), current.data(), usable_rows);
+    ctx.sync();    // rg, rh are released on return
+    return current;
 }
 
 /// The device part of algorithms::precommit<FRI>(poly, D, fri_step) (basic_fri.hpp:433-496): every polynomial is
@@ -279,8 +360,7 @@ std::vector<typename curve_adapter<CurveType>::scalar_value_type>
     std::vector<typename adapter::scalar_value_type> out;
     if (batch == 0) return out;
     auto d_ext = ctx.alloc(batch * D * 32);
-    std::uint64_t wd[4];
-    adapter::scalar_to_limbs(root(log_domain), wd);
+    const typename adapter::scalar_value_type wd = root(log_domain);
     /* runs of equally sized polynomials are extended by one batched call */
     for (std::size_t i = 0; i < batch;) {
         std::size_t j = i;
@@ -294,15 +374,13 @@ std::vector<typename curve_adapter<CurveType>::scalar_value_type>
         } else {
             auto d_in = ctx.alloc(n * (j - i) * 32);
             for (std::size_t p = i; p < j; ++p) upload_scalars<adapter>(ctx, static_cast<char *>(d_in.get()) + 32 * (p - i) * n, detail::poly_data<adapter>(polys[p]), n);
-            std::uint64_t wn[4];
-            adapter::scalar_to_limbs(root(log_n), wn);
-            check(zkhip_poly_resize_dev(ctx.get(), adapter::id, d_in.get(), log_n, j - i, wn, dst, log_domain, wd), "zkhip_poly_resize_dev", ctx.get());
+            fr_vector<CurveType>::resize(ctx, d_in.get(), log_n, j - i, root(log_n), dst, log_domain, wd);
             ctx.sync();
         }
         i = j;
     }
     auto d_leaves = ctx.alloc(batch * D * 32);
-    check(zkhip_fri_leaves_dev(ctx.get(), d_ext.get(), log_domain, batch, fri_step, d_leaves.get()), "zkhip_fri_leaves_dev", ctx.get());
+    ZKHIP_CALL(ctx, zkhip_fri_leaves_dev, d_ext.get(), log_domain, batch, fri_step, d_leaves.get());
     download_scalars<adapter>(ctx, d_leaves.get(), batch * D, out);
     return out;
 }

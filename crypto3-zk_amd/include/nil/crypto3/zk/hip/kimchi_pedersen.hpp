@@ -28,6 +28,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "fr_vector.hpp"
 #include "multiexp.hpp"
 
 namespace nil {
@@ -44,6 +45,7 @@ struct kimchi_pedersen_hip {
     typedef SpongeType sponge_type;
     typedef GroupMapType group_map_type;
     static constexpr std::size_t jac_limbs = 3 * adapter::g1_coord_limbs;
+    typedef fr_vector<CurveType> fv;
 
     /// params_type with the generators resident: ONE object [g_0 .. g_(n-1), infinity up to the next power of two, h] with window
     /// tables -- commitment reads sub-ranges of g, the opening's first round the padded g, verify_eval all of it.
@@ -199,7 +201,6 @@ struct kimchi_pedersen_hip {
     static proof_type proof_eval(const params_type &params, group_map_type &group_map, const poly_type &plms, const std::vector<scalar_value_type> &elm,
                                  const scalar_value_type &polyscale, const scalar_value_type &evalscale, sponge_type &sponge) {
         const context &ctx = params.ctx;
-        zkhip_ctx *c = ctx.get();
         proof_type res;
         std::vector<std::tuple<scalar_value_type, scalar_value_type>> blinders;
         const std::size_t n = params.g.size();
@@ -210,11 +211,11 @@ struct kimchi_pedersen_hip {
         std::vector<std::shared_ptr<void>> d_coeffs;
         std::vector<const void *> lo_ptr;
         std::vector<std::size_t> lo_len;
-        std::vector<std::uint64_t> lo_scale;
+        std::vector<scalar_value_type> lo_scale;
         struct shifted_term {
             const void *ptr;
             std::size_t len;
-            std::uint64_t scale[4];
+            scalar_value_type scale;
         };
         std::vector<shifted_term> shifted;
         scalar_value_type blinding_factor = scalar_value_type::zero(), scale = scalar_value_type::one();
@@ -228,27 +229,21 @@ struct kimchi_pedersen_hip {
                 const std::size_t seg = end > offset ? end - offset : 0;
                 const void *seg_ptr = static_cast<const char *>(d_coeffs.back().get()) + 32 * offset;
                 lo_ptr.push_back(seg_ptr), lo_len.push_back(seg);
-                lo_scale.resize(lo_scale.size() + 4);
-                adapter::scalar_to_limbs(scale, &lo_scale[lo_scale.size() - 4]);
+                lo_scale.push_back(scale);
                 blinding_factor = blinding_factor + polynom.commit.unshifted[j] * scale;
                 j += 1;
                 scale = scale * polyscale;
                 offset += n;
                 if (offset > polynom.bound) {
-                    shifted_term t = {seg_ptr, seg, {}};
-                    adapter::scalar_to_limbs(scale, t.scale);
-                    shifted.push_back(t);
+                    shifted.push_back({seg_ptr, seg, scale});
                     blinding_factor = blinding_factor + polynom.commit.shifted * scale;
                     scale = scale * polyscale;
                 }
             }
         }
-        check(zkhip_poly_lincomb_dev(c, adapter::id, lo_ptr.size(), lo_ptr.data(), lo_len.data(), lo_scale.data(), 1, d_a.get(), power_of_two, 0),
-              "zkhip_poly_lincomb_dev", c);
+        fv::lincomb(ctx, lo_ptr, lo_len, lo_scale, 1, d_a.get(), power_of_two, false);
         for (const shifted_term &t : shifted)
-            if (t.len)
-                check(zkhip_poly_lincomb_dev(c, adapter::id, 1, &t.ptr, &t.len, t.scale, 1, static_cast<char *>(d_a.get()) + 32 * (n - t.len), t.len, 1),
-                      "zkhip_poly_lincomb_dev", c);
+            if (t.len) fv::add_scaled(ctx, t.ptr, t.len, t.scale, static_cast<char *>(d_a.get()) + 32 * (n - t.len), t.len, true);
 
         /* b[i] = sum_e evalscale^e elm[e]^i */
         std::vector<std::uint64_t> pts(4 * elm.size()), scl(4 * elm.size());
@@ -258,13 +253,13 @@ struct kimchi_pedersen_hip {
             adapter::scalar_to_limbs(scale, &scl[4 * e]);
             scale = scale * evalscale;
         }
-        check(zkhip_fr_powers_lincomb_dev(c, adapter::id, pts.data(), scl.data(), elm.size(), d_b.get(), power_of_two), "zkhip_fr_powers_lincomb_dev", c);
+        ZKHIP_CALL(ctx, zkhip_fr_powers_lincomb_dev, adapter::id, pts.data(), scl.data(), elm.size(), d_b.get(), power_of_two);
 
         /* per-round scalars [rand_l, <a_hi, b_lo>, rand_r, <a_lo, b_hi>] and the four partial sums of L and R */
         auto d_sc = ctx.alloc(4 * 32), d_jac = ctx.alloc(6 * jac_limbs * 8);
         char *sc = static_cast<char *>(d_sc.get());
         std::uint64_t *jac = static_cast<std::uint64_t *>(d_jac.get());
-        check(zkhip_fr_inner_product_dev(c, adapter::id, d_a.get(), d_b.get(), power_of_two, sc), "zkhip_fr_inner_product_dev", c);
+        ZKHIP_CALL(ctx, zkhip_fr_inner_product_dev, adapter::id, d_a.get(), d_b.get(), power_of_two, sc);
         sponge.absorb_fr(sponge.shift_scalar(download_scalar(ctx, sc)));
         const group_value_type u = group_map.to_group(sponge.challenge_fq());
         /* [h, u] for the two-point sums rand h + <., .> u of every round, padded with infinity to the size from which an upload builds window
@@ -284,16 +279,16 @@ struct kimchi_pedersen_hip {
             const scalar_value_type rand_r = params.random();
             upload_scalars<adapter>(ctx, sc, &rand_l, 1);
             upload_scalars<adapter>(ctx, sc + 64, &rand_r, 1);
-            check(zkhip_fr_inner_product_dev(c, adapter::id, a + 32 * half, b, half, sc + 32), "zkhip_fr_inner_product_dev", c);
-            check(zkhip_fr_inner_product_dev(c, adapter::id, a, b + 32 * half, half, sc + 96), "zkhip_fr_inner_product_dev", c);
+            ZKHIP_CALL(ctx, zkhip_fr_inner_product_dev, adapter::id, a + 32 * half, b, half, sc + 32);
+            ZKHIP_CALL(ctx, zkhip_fr_inner_product_dev, adapter::id, a, b + 32 * half, half, sc + 96);
             /* l = <g_low, a_high> + rand_l h + <a_high, b_low> u,   r = <g_high, a_low> + rand_r h + <a_low, b_high> u */
             const zkhip_bases *qb[4] = {g_cur, hu_dev.get(), g_cur, hu_dev.get()};
             const std::size_t qo[4] = {0, 0, half, 0}, qn[4] = {half, 2, half, 2};
             const void *qs[4] = {a + 32 * half, sc, a, sc + 64};
             void *qr[4] = {jac, jac + jac_limbs, jac + 2 * jac_limbs, jac + 3 * jac_limbs};
-            check(zkhip_msm_batch_dev(c, 4, qb, qo, qn, qs, qr), "zkhip_msm_batch_dev", c);
-            check(zkhip_jacobian_sum_dev(c, adapter::id, ZKHIP_G1, jac, 2, jac + 4 * jac_limbs), "zkhip_jacobian_sum_dev", c);
-            check(zkhip_jacobian_sum_dev(c, adapter::id, ZKHIP_G1, jac + 2 * jac_limbs, 2, jac + 5 * jac_limbs), "zkhip_jacobian_sum_dev", c);
+            ZKHIP_CALL(ctx, zkhip_msm_batch_dev, 4, qb, qo, qn, qs, qr);
+            ZKHIP_CALL(ctx, zkhip_jacobian_sum_dev, adapter::id, ZKHIP_G1, jac, 2, jac + 4 * jac_limbs);
+            ZKHIP_CALL(ctx, zkhip_jacobian_sum_dev, adapter::id, ZKHIP_G1, jac + 2 * jac_limbs, 2, jac + 5 * jac_limbs);
             std::uint64_t lr_host[2 * jac_limbs];
             ctx.d2h(lr_host, jac + 4 * jac_limbs, sizeof(lr_host));
             const group_value_type l = normalised(adapter::g1_from_jacobian(lr_host)), r = normalised(adapter::g1_from_jacobian(lr_host + jac_limbs));
@@ -308,14 +303,11 @@ struct kimchi_pedersen_hip {
             chal_invs.push_back(u_scalar_inv);
 
             /* a = a_high u^-1 + a_low,  b = b_high u + b_low,  g = g_high u + g_low */
-            std::uint64_t cu[4], ci[4], one[4] = {1, 0, 0, 0}, zero[4] = {0, 0, 0, 0};
-            adapter::scalar_to_limbs(u_scalar, cu);
-            adapter::scalar_to_limbs(u_scalar_inv, ci);
-            check(zkhip_fr_vec_affine_dev(c, adapter::id, a + 32 * half, a, ci, one, zero, a, half), "zkhip_fr_vec_affine_dev", c);
-            check(zkhip_fr_vec_affine_dev(c, adapter::id, b + 32 * half, b, cu, one, zero, b, half), "zkhip_fr_vec_affine_dev", c);
+            fv::affine(ctx, a + 32 * half, a, u_scalar_inv, scalar_value_type::one(), scalar_value_type::zero(), a, half);
+            fv::affine(ctx, b + 32 * half, b, u_scalar, scalar_value_type::one(), scalar_value_type::zero(), b, half);
             zkhip_bases *next = nullptr;
-            check(zkhip_bases_fold(c, g_cur, 0, half, half, cu, &next), "zkhip_bases_fold", c);
-            folded = bases_handle(next, bases_free {c});
+            ZKHIP_CALL(ctx, zkhip_bases_fold, g_cur, 0, half, half, limbs_of<adapter>(u_scalar).data(), &next);
+            folded = bases_handle(next, bases_free {ctx.get()});
             g_cur = next;
         }
         const scalar_value_type a0 = download_scalar(ctx, a), b0 = download_scalar(ctx, b);
@@ -323,7 +315,7 @@ struct kimchi_pedersen_hip {
         {
             std::uint64_t xy[2 * adapter::g1_coord_limbs];
             std::uint8_t inf = 0;
-            check(zkhip_bases_download(c, g_cur, 0, 1, xy, &inf), "zkhip_bases_download", c);
+            ZKHIP_CALL(ctx, zkhip_bases_download, g_cur, 0, 1, xy, &inf);
             g0 = group_value_type::from_affine(xy, inf != 0);
         }
 
@@ -388,7 +380,6 @@ struct kimchi_pedersen_hip {
     /// zkhip_fr_challenge_products_dev and is scaled and added in place), those of the per-proof points on the host.
     static bool verify_eval(params_type &params, group_map_type &group_map, std::vector<batchproof_type> &batches) {
         const context &ctx = params.ctx;
-        zkhip_ctx *c = ctx.get();
         const std::size_t power_of_two = params.padded;
         std::vector<group_value_type> points;      // behind the resident ones
         std::vector<scalar_value_type> scalars;
@@ -421,11 +412,8 @@ struct kimchi_pedersen_hip {
             if (((std::size_t)1 << chals.size()) != power_of_two) return false;    // an opening of another size than this SRS
             std::vector<std::uint64_t> ch(4 * std::max<std::size_t>(1, chals.size()));
             for (std::size_t i = 0; i < chals.size(); ++i) adapter::scalar_to_limbs(chals[i], &ch[4 * i]);
-            check(zkhip_fr_challenge_products_dev(c, adapter::id, ch.data(), chals.size(), d_s.get()), "zkhip_fr_challenge_products_dev", c);
-            std::uint64_t sg[4], one[4] = {1, 0, 0, 0}, zero[4] = {0, 0, 0, 0};
-            adapter::scalar_to_limbs(sg_rand_base_i, sg);
-            check(zkhip_fr_vec_affine_dev(c, adapter::id, d_s.get(), first ? nullptr : d_scalars.get(), sg, first ? nullptr : one, zero, d_scalars.get(), power_of_two),
-                  "zkhip_fr_vec_affine_dev", c);
+            ZKHIP_CALL(ctx, zkhip_fr_challenge_products_dev, adapter::id, ch.data(), chals.size(), d_s.get());
+            fv::affine(ctx, d_s.get(), first ? nullptr : d_scalars.get(), sg_rand_base_i, scalar_value_type::one(), scalar_value_type::zero(), d_scalars.get(), power_of_two);
             first = false;
 
             const scalar_value_type neg_rand_base_i = scalar_value_type::zero() - rand_base_i;
@@ -518,7 +506,7 @@ private:
             qs[k] = static_cast<const char *>(d_scalars) + 32 * at[k];
             qr[k] = static_cast<std::uint64_t *>(d_res.get()) + k * jac_limbs;
         }
-        check(zkhip_msm_batch_dev(ctx.get(), count, bases.data(), offs.data(), ns.data(), qs.data(), qr.data()), "zkhip_msm_batch_dev", ctx.get());
+        ZKHIP_CALL(ctx, zkhip_msm_batch_dev, count, bases.data(), offs.data(), ns.data(), qs.data(), qr.data());
         std::vector<std::uint64_t> res(count * jac_limbs);
         ctx.d2h(res.data(), d_res.get(), res.size() * 8);
         std::vector<group_value_type> out;

@@ -16,6 +16,7 @@
 #include <memory>
 #include <vector>
 
+#include "fr_vector.hpp"
 #include "multiexp.hpp"
 
 namespace nil {
@@ -133,10 +134,8 @@ std::vector<typename curve_adapter<CurveType>::g1_value_type>
         if (polys[b].size() != n) throw std::runtime_error("kzg_commit_batch: ragged batch");
     auto d = ctx.alloc(n * batch * 32);
     for (std::size_t b = 0; b < batch; ++b) upload_scalars<adapter>(ctx, static_cast<char *>(d.get()) + 32 * b * n, detail::poly_data<adapter>(polys[b]), n);
-    std::uint64_t w[4];
-    adapter::scalar_to_limbs(omega, w);
     /* p.coefficients() for every polynomial of the batch (kzg.hpp:431) */
-    check(zkhip_ntt_dev(ctx.get(), adapter::id, d.get(), log_n, batch, w, 1, nullptr), "zkhip_ntt_dev", ctx.get());
+    fr_vector<CurveType>::ntt(ctx, d.get(), log_n, batch, omega, true);
     /* multiexp<multiexp_method>(commitment_key[0 .. n), coefficients, 1) for every column (kzg.hpp:433-434), as one
        batch: the columns' bucket reductions share one launch */
     const std::size_t jl = 3 * adapter::g1_coord_limbs;
@@ -149,7 +148,7 @@ std::vector<typename curve_adapter<CurveType>::g1_value_type>
         qs[b] = static_cast<const char *>(d.get()) + 32 * b * n;
         qr[b] = static_cast<std::uint64_t *>(d_res.get()) + b * jl;
     }
-    check(zkhip_msm_batch_dev(ctx.get(), batch, qb.data(), qo.data(), qn.data(), qs.data(), qr.data()), "zkhip_msm_batch_dev", ctx.get());
+    ZKHIP_CALL(ctx, zkhip_msm_batch_dev, batch, qb.data(), qo.data(), qn.data(), qs.data(), qr.data());
     std::vector<std::uint64_t> res(batch * jl);
     ctx.d2h(res.data(), d_res.get(), res.size() * 8);
     for (std::size_t b = 0; b < batch; ++b) out.push_back(adapter::g1_from_jacobian(&res[b * jl]));

@@ -134,18 +134,12 @@ kzg_batched_proof_eval(const kzg_params_hip<CurveType> &params, const std::vecto
         char *q_ptr = static_cast<char *>(d_q.get());
         std::size_t q_len = spare.size();
         for (const auto &s : public_key.S[i]) {
-            std::uint64_t zl[4], rem[4];
-            adapter::scalar_to_limbs(s, zl);
-            check(zkhip_poly_div_linear_dev(ctx.get(), adapter::id, q_ptr, q_len, zl, q_ptr, rem), "zkhip_poly_div_linear_dev", ctx.get());
-            if (rem[0] | rem[1] | rem[2] | rem[3]) throw std::runtime_error("proof_eval: (f - r) does not vanish on S");
+            if (!(fr_vector<CurveType>::div_linear(ctx, q_ptr, q_len, s, q_ptr) == Fr::zero())) throw std::runtime_error("proof_eval: (f - r) does not vanish on S");
             q_ptr += 32;
             q_len -= 1;
         }
         /* accum += spare_poly * factor (:581) */
-        std::uint64_t fl[4];
-        adapter::scalar_to_limbs(factor, fl);
-        const void *qp = q_ptr;
-        check(zkhip_poly_lincomb_dev(ctx.get(), adapter::id, 1, &qp, &q_len, fl, 1, d_acc.get(), acc_len, first ? 0 : 1), "zkhip_poly_lincomb_dev", ctx.get());
+        fr_vector<CurveType>::add_scaled(ctx, q_ptr, q_len, factor, d_acc.get(), acc_len, !first);
         first = false;
         ctx.sync();    // d_q is released at the end of the iteration
     }

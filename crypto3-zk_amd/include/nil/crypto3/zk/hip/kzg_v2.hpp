@@ -112,10 +112,9 @@ typename curve_adapter<CurveType>::g1_value_type kzg_proof_eval(const kzg_params
     for (std::size_t i = 0; i < f.size(); ++i) adapter::scalar_to_limbs(f[i], &host[4 * i]);
     auto d = ctx.alloc(host.size() * 8);
     ctx.h2d(d.get(), host.data(), host.size() * 8);
-    std::uint64_t zl[4];
-    adapter::scalar_to_limbs(z, zl);
-    /* q[0] -= f(z); q /= (X - z): the synthetic division drops the remainder f(z) by itself (kzg.hpp:163-169) */
-    check(zkhip_poly_div_linear_dev(ctx.get(), adapter::id, d.get(), f.size(), zl, d.get(), nullptr), "zkhip_poly_div_linear_dev", ctx.get());
+    /* q[0] -= f(z); q /= (X - z): the synthetic division drops the remainder f(z) by itself (kzg.hpp:163-169); it is not asked for
+       (fr_vector::div_linear would fetch it and synchronise) */
+    ZKHIP_CALL(ctx, zkhip_poly_div_linear_dev, adapter::id, d.get(), f.size(), limbs_of<adapter>(z).data(), d.get(), nullptr);
     return multiexp_dev<CurveType, ZKHIP_G1>(ctx, params.commitment_key, 0, f.size() - 1, static_cast<const char *>(d.get()) + 32);
 }
 
@@ -129,6 +128,7 @@ class kzg_polys_evaluator_hip : public polys_evaluator_hip<CurveType, Polynomial
 
 public:
     typedef typename base::adapter adapter;
+    typedef fr_vector<CurveType> fv;
     typedef CurveType curve_type;
     typedef typename base::scalar_value_type scalar_value_type;
     typedef typename adapter::g1_value_type single_commitment_type;
@@ -260,13 +260,12 @@ private:
             for (std::size_t p = i; p < j; ++p) {
                 if (polys[p]) upload_scalars<adapter>(up, at(p), detail::poly_data<adapter>(*polys[p]), polys[p]->size());
                 else if (copy_resident)
-                    check(zkhip_memcpy_d2d_async(up.get(), at(p), resident_c.count(p) ? resident_c.at(p).data() : resident.at(p).data(), db.len[p] * 32),
-                          "zkhip_memcpy_d2d_async", up.get());
+                    fv::copy(up, at(p), resident_c.count(p) ? resident_c.at(p).data() : resident.at(p).data(), db.len[p]);
             }
             if (&up != &ctx) ctx.wait_for(up);
             if (!coefficients) {
                 const std::size_t log_n = detail::ceil_log2(db.len[i]);
-                check(zkhip_ntt_dev(ctx.get(), adapter::id, at(i), log_n, j - i, roots.at(log_n).data(), 1, nullptr), "zkhip_ntt_dev", ctx.get());
+                ZKHIP_CALL(ctx, zkhip_ntt_dev, adapter::id, at(i), log_n, j - i, roots.at(log_n).data(), 1, nullptr);
             }
             if (!zero) {    // the coefficients of a known-zero polynomial still go into the batch (proof_eval reads them)
                 const std::size_t cnt = j - i;
@@ -278,7 +277,7 @@ private:
                     qs[c] = at(i + c);
                     qr[c] = static_cast<std::uint64_t *>(d_res) + (i + c - lo) * jl;
                 }
-                check(zkhip_msm_batch_dev(ctx.get(), cnt, qb.data(), qo.data(), qn.data(), qs.data(), qr.data()), "zkhip_msm_batch_dev", ctx.get());
+                ZKHIP_CALL(ctx, zkhip_msm_batch_dev, cnt, qb.data(), qo.data(), qn.data(), qs.data(), qr.data());
             }
         }, same_kind);
     }
@@ -372,7 +371,7 @@ protected:
                 group.copy(k, d_sc[k].get(), 0, sc, (hi - lo) * 32);
                 sc = d_sc[k].get();
             }
-            check(zkhip_msm_dev(group[k].get(), gp.members[k]->commitment_key.get(), lo, hi - lo, sc, d_part[k].get()), "zkhip_msm_dev", group[k].get());
+            ZKHIP_CALL(group[k], zkhip_msm_dev, gp.members[k]->commitment_key.get(), lo, hi - lo, sc, d_part[k].get());
             send[k] = d_part[k].get();
         }
         const context &root = group[0];
@@ -380,7 +379,7 @@ protected:
         recv[0] = d_all.get();
         group.all_gather(send, recv, jl * 8);
         void *d_sum = static_cast<char *>(d_all.get()) + world * jl * 8;
-        check(zkhip_jacobian_sum_dev(root.get(), adapter::id, ZKHIP_G1, d_all.get(), world, d_sum), "zkhip_jacobian_sum_dev", root.get());
+        ZKHIP_CALL(root, zkhip_jacobian_sum_dev, adapter::id, ZKHIP_G1, d_all.get(), world, d_sum);
         std::uint64_t jac[3 * adapter::g1_coord_limbs];
         root.d2h(jac, d_sum, sizeof(jac));
         group.sync();    // the members' scalar ranges and partial sums are released on return
@@ -396,16 +395,13 @@ protected:
         for (std::size_t i = 0; i < n; ++i) adapter::scalar_to_limbs(small[i], &h[4 * i]);
         auto tmp = ctx.alloc(n * 32);
         ctx.h2d(tmp.get(), h.data(), h.size() * 8);
-        check(zkhip_fr_vec_op_dev(ctx.get(), adapter::id, 0, d, tmp.get(), d, n), "zkhip_fr_vec_op_dev", ctx.get());
+        fv::pointwise(ctx, fr_op::add, d, tmp.get(), d, n);
         ctx.sync();
     }
     /// (ptr, len) <- quotient by (X - root); throws when the remainder is not zero
     void divide_in_place(char *&ptr, std::size_t &len, const scalar_value_type &root, const char *what) const {
         if (len == 0) return;
-        std::uint64_t zl[4], rem[4];
-        adapter::scalar_to_limbs(root, zl);
-        check(zkhip_poly_div_linear_dev(_params.ctx.get(), adapter::id, ptr, len, zl, ptr, rem), "zkhip_poly_div_linear_dev", _params.ctx.get());
-        if (rem[0] | rem[1] | rem[2] | rem[3]) throw std::runtime_error(what);
+        if (!(fv::div_linear(_params.ctx, ptr, len, root, ptr) == scalar_value_type::zero())) throw std::runtime_error(what);
         ptr += 32;
         len -= 1;
     }
@@ -471,6 +467,7 @@ class kzg_commitment_scheme_v2_hip : public kzg_polys_evaluator_hip<CurveType, T
 
 public:
     typedef typename base::adapter adapter;
+    typedef fr_vector<CurveType> fv;
     typedef typename base::curve_type curve_type;
     typedef typename base::scalar_value_type scalar_value_type;
     typedef typename base::single_commitment_type single_commitment_type;
@@ -541,8 +538,7 @@ public:
                 theta_i = theta_i * theta;
             }
             auto d_f = ctx.alloc(acc_len * 32);
-            check(zkhip_poly_lincomb_dev(ctx.get(), adapter::id, items.size(), ptrs.data(), lens.data(), coeffs.data(), taps, d_f.get(), acc_len, 0),
-                  "zkhip_poly_lincomb_dev", ctx.get());
+            fv::lincomb(ctx, ptrs, lens, coeffs, taps, d_f.get(), acc_len, false);
             add_low_coefficients(d_f.get(), corr, acc_len);
             /* f /= V, one root at a time (kzg_v2.hpp:266-267); the remainders are the BOOST_ASSERT */
             char *f_ptr = static_cast<char *>(d_f.get());
@@ -555,20 +551,19 @@ public:
             /* L = sum_i theta^i Z_{T\S_i}(theta_2) (f_i - U_i(theta_2)) - V(theta_2) f (kzg_v2.hpp:281-289) */
             ptrs.push_back(f_ptr);
             lens.push_back(f_len);
-            std::vector<std::uint64_t> c1((items.size() + 1) * 4, 0);
+            std::vector<scalar_value_type> c1;
             scalar_value_type l0 = scalar_value_type::zero();
             theta_i = scalar_value_type::one();
             for (std::size_t n = 0; n < items.size(); ++n) {
                 auto s = theta_i * SP::evaluate(items[n].diff, theta_2);
-                adapter::scalar_to_limbs(s, &c1[4 * n]);
+                c1.push_back(s);
                 l0 = l0 - s * SP::evaluate(items[n].U, theta_2);
                 theta_i = theta_i * theta;
             }
-            adapter::scalar_to_limbs(scalar_value_type::zero() - SP::evaluate(V, theta_2), &c1[4 * items.size()]);
+            c1.push_back(scalar_value_type::zero() - SP::evaluate(V, theta_2));
             const std::size_t l_len = std::max(max_len, f_len);
             auto d_l = ctx.alloc(std::max<std::size_t>(1, l_len) * 32);
-            check(zkhip_poly_lincomb_dev(ctx.get(), adapter::id, ptrs.size(), ptrs.data(), lens.data(), c1.data(), 1, d_l.get(), l_len, 0),
-                  "zkhip_poly_lincomb_dev", ctx.get());
+            fv::lincomb(ctx, ptrs, lens, c1, 1, d_l.get(), l_len, false);
             add_low_coefficients(d_l.get(), {l0}, l_len);
             /* L /= (X - theta_2) (kzg_v2.hpp:290-291) */
             char *l_ptr = static_cast<char *>(d_l.get());
@@ -613,6 +608,7 @@ class kzg_commitment_scheme_hip : public kzg_polys_evaluator_hip<CurveType, Tran
 
 public:
     typedef typename base::adapter adapter;
+    typedef fr_vector<CurveType> fv;
     typedef typename base::curve_type curve_type;
     typedef typename base::scalar_value_type scalar_value_type;
     typedef typename base::single_commitment_type single_commitment_type;
@@ -650,7 +646,7 @@ public:
             std::vector<scalar_value_type> pts;    // sorted
             std::vector<const void *> ptrs;
             std::vector<std::size_t> lens;
-            std::vector<std::uint64_t> coeffs;     // gamma^j, canonical limbs
+            std::vector<scalar_value_type> coeffs;  // gamma^j
             std::vector<scalar_value_type> u_sum;  // sum_j gamma^j U_j
             std::size_t max_len = 0;
         };
@@ -669,8 +665,7 @@ public:
                 }
                 g->ptrs.push_back(it.second.at(i));
                 g->lens.push_back(it.second.len[i]);
-                g->coeffs.resize(g->coeffs.size() + 4);
-                adapter::scalar_to_limbs(factor, g->coeffs.data() + g->coeffs.size() - 4);
+                g->coeffs.push_back(factor);
                 g->u_sum = SP::add(g->u_sum, SP::scale(get_U(k, i), factor));
                 g->max_len = std::max(g->max_len, it.second.len[i]);
                 factor = factor * gamma;
@@ -682,19 +677,15 @@ public:
         if (acc_len != 0) {
             auto d_acc = ctx.alloc(acc_len * 32);
             bool first = true;
-            const std::uint64_t one[4] = {1, 0, 0, 0};
             for (const auto &g : groups) {
                 if (g.max_len <= g.pts.size()) continue;    // deg f < |S|: f = U, the quotient is zero
                 auto d_g = ctx.alloc(g.max_len * 32);
-                check(zkhip_poly_lincomb_dev(ctx.get(), adapter::id, g.ptrs.size(), g.ptrs.data(), g.lens.data(), g.coeffs.data(), 1, d_g.get(), g.max_len, 0),
-                      "zkhip_poly_lincomb_dev", ctx.get());
+                fv::lincomb(ctx, g.ptrs, g.lens, g.coeffs, 1, d_g.get(), g.max_len, false);
                 add_low_coefficients(d_g.get(), SP::scale(g.u_sum, scalar_value_type::zero() - scalar_value_type::one()), g.max_len);
                 char *q_ptr = static_cast<char *>(d_g.get());
                 std::size_t q_len = g.max_len;
                 for (const auto &root : g.pts) divide_in_place(q_ptr, q_len, root, "proof_eval: (f - U) is not divisible by V");
-                const void *qp = q_ptr;
-                check(zkhip_poly_lincomb_dev(ctx.get(), adapter::id, 1, &qp, &q_len, one, 1, d_acc.get(), acc_len, first ? 0 : 1), "zkhip_poly_lincomb_dev",
-                      ctx.get());
+                fv::add_scaled(ctx, q_ptr, q_len, scalar_value_type::one(), d_acc.get(), acc_len, !first);
                 first = false;
                 ctx.sync();    // d_g is released at the end of the iteration
             }
@@ -730,8 +721,7 @@ protected:
 template <typename CurveType>
 struct scalar_be_packer {
     std::vector<std::uint8_t> operator()(const typename curve_adapter<CurveType>::scalar_value_type &v) const {
-        std::uint64_t l[4];
-        curve_adapter<CurveType>::scalar_to_limbs(v, l);
+        const auto l = limbs_of<curve_adapter<CurveType>>(v);
         std::vector<std::uint8_t> b(32);
         for (int i = 0; i < 32; ++i) b[31 - i] = (std::uint8_t)(l[i >> 3] >> (8 * (i & 7)));
         return b;

@@ -234,6 +234,7 @@ public:
     static constexpr bool is_lpc() { return true; }
 
     typedef typename base::adapter adapter;
+    typedef fr_vector<CurveType> fv;
     typedef CurveType curve_type;
     typedef typename base::scalar_value_type value_type;
     typedef fri_params_hip<CurveType> params_type;
@@ -324,7 +325,7 @@ public:
         db.data = _ctx.alloc(std::max<std::size_t>(1, db.total) * 32);
         const std::size_t D = domain_size(0), count = polys.size();
         root_map roots;    // D[0]'s root first, then one per distinct size
-        adapter::scalar_to_limbs(_fri_params.root_of_unity(_fri_params.log_domain), roots[_fri_params.log_domain].data());
+        roots[_fri_params.log_domain] = limbs_of<adapter>(_fri_params.root_of_unity(_fri_params.log_domain));
         detail::add_roots<adapter>(roots, db, _fri_params.root_of_unity);
         if (_group && _group->size() > 1 && count) commit_group(index, polys, db, roots);
         else {
@@ -368,9 +369,8 @@ protected:
             for (std::size_t p = i; p < j; ++p) upload_scalars<adapter>(upc, at(p), detail::poly_data<adapter>(*polys[p]), polys[p]->size());
             if (pipelined) ctx.wait_for(upc);
             const std::size_t log_n = detail::ceil_log2(db.len[i]);
-            check(zkhip_poly_resize_dev(ctx.get(), adapter::id, at(i), log_n, j - i, roots.at(log_n).data(), d_ext + 32 * (i - lo) * D, _fri_params.log_domain,
-                                        roots.at(_fri_params.log_domain).data()),
-                  "zkhip_poly_resize_dev", ctx.get());
+            ZKHIP_CALL(ctx, zkhip_poly_resize_dev, adapter::id, at(i), log_n, j - i, roots.at(log_n).data(), d_ext + 32 * (i - lo) * D, _fri_params.log_domain,
+                       roots.at(_fri_params.log_domain).data());    // the roots are packed once per batch (root_map), not per call
         });
     }
 
@@ -414,8 +414,7 @@ protected:
                pitch of D / 2^step in, seg out) -- straight into my own buffer where I am the owner */
             for (std::size_t d = 0; d < owners; ++d) {
                 char *dst = d == k ? static_cast<char *>(gs.cmp.get()) + 32 * pt.lo * Ds : static_cast<char *>(gs.send.get()) + 32 * d * mine * Ds;
-                check(zkhip_memcpy_2d_d2d_async(ctx.get(), dst, seg * 32, d_ext + 32 * d * seg, (D >> step) * 32, seg * 32, mine * rows_per_poly),
-                      "zkhip_memcpy_2d_d2d_async", ctx.get());
+                ZKHIP_CALL(ctx, zkhip_memcpy_2d_d2d_async, dst, seg * 32, d_ext + 32 * d * seg, (D >> step) * 32, seg * 32, mine * rows_per_poly);
             }
         });
         /* the exchange, from this thread: blocks to their owners, coefficient forms to member 0 */
@@ -431,8 +430,7 @@ protected:
         }
         std::vector<const void *> d_leaves(owners);
         for (std::size_t d = 0; d < owners; ++d) {
-            check(zkhip_fri_leaves_dev(group[d].get(), _gs[d].cmp.get(), _fri_params.log_domain - log_owners, count, step, _gs[d].leaves.get()),
-                  "zkhip_fri_leaves_dev", group[d].get());
+            ZKHIP_CALL(group[d], zkhip_fri_leaves_dev, _gs[d].cmp.get(), _fri_params.log_domain - log_owners, count, step, _gs[d].leaves.get());
             d_leaves[d] = _gs[d].leaves.get();
         }
         _trees.erase(index);
@@ -467,34 +465,30 @@ public:
             for (std::size_t l : it.second.len) max_len = std::max(max_len, l);
         auto d_combined = _ctx.alloc(max_len * 32), d_q = _ctx.alloc(max_len * 32);
         bool have_combined = false;
-        auto add_quotient = [&](const std::vector<const void *> &ptrs, const std::vector<std::size_t> &lens, const std::vector<std::uint64_t> &coeffs,
+        auto add_quotient = [&](const std::vector<const void *> &ptrs, const std::vector<std::size_t> &lens, const std::vector<value_type> &coeffs,
                                 const value_type &constant, const value_type &point) {
             if (ptrs.empty()) return;
             /* Q_normal = sum theta_acc g - sum theta_acc z;  Q_normal /= (X - point);  combined_Q_normal += Q_normal */
-            check(zkhip_poly_lincomb_dev(_ctx.get(), adapter::id, ptrs.size(), ptrs.data(), lens.data(), coeffs.data(), 1, d_q.get(), max_len, 0),
-                  "zkhip_poly_lincomb_dev", _ctx.get());
-            std::uint64_t c[4], z[4], rem[4];
-            adapter::scalar_to_limbs(value_type::zero() - constant, c);
+            fv::lincomb(_ctx, ptrs, lens, coeffs, 1, d_q.get(), max_len, false);
             auto d_c = _ctx.alloc(32);
-            _ctx.h2d(d_c.get(), c, 32);
-            check(zkhip_fr_vec_op_dev(_ctx.get(), adapter::id, 0, d_q.get(), d_c.get(), d_q.get(), 1), "zkhip_fr_vec_op_dev", _ctx.get());
-            adapter::scalar_to_limbs(point, z);
-            check(zkhip_poly_div_linear_dev(_ctx.get(), adapter::id, d_q.get(), max_len, z, d_q.get(), rem), "zkhip_poly_div_linear_dev", _ctx.get());
-            if (rem[0] | rem[1] | rem[2] | rem[3]) throw std::runtime_error("lpc proof_eval: a quotient does not divide (evaluation / point mismatch)");
+            _ctx.h2d(d_c.get(), limbs_of<adapter>(value_type::zero() - constant).data(), 32);
+            fv::pointwise(_ctx, fr_op::add, d_q.get(), d_c.get(), d_q.get(), 1);
+            if (!(fv::div_linear(_ctx, d_q.get(), max_len, point, d_q.get()) == value_type::zero()))
+                throw std::runtime_error("lpc proof_eval: a quotient does not divide (evaluation / point mismatch)");
             /* the quotient's max_len - 1 coefficients sit at d_q + 1; slot 0 held the (zero) remainder */
             void *q = static_cast<char *>(d_q.get()) + 32;
             if (!have_combined) {
-                check(zkhip_memcpy_d2d_async(_ctx.get(), d_combined.get(), q, (max_len - 1) * 32), "zkhip_memcpy_d2d_async", _ctx.get());
+                fv::copy(_ctx, d_combined.get(), q, max_len - 1);
                 have_combined = true;
             } else if (max_len > 1) {
-                check(zkhip_fr_vec_op_dev(_ctx.get(), adapter::id, 0, d_combined.get(), q, d_combined.get(), max_len - 1), "zkhip_fr_vec_op_dev", _ctx.get());
+                fv::pointwise(_ctx, fr_op::add, d_combined.get(), q, d_combined.get(), max_len - 1);
             }
             _ctx.sync();    // d_c is released on return
         };
         for (const auto &point : this->unique_points()) {
             std::vector<const void *> ptrs;
             std::vector<std::size_t> lens;
-            std::vector<std::uint64_t> coeffs;
+            std::vector<value_type> coeffs;
             value_type constant = value_type::zero();
             for (std::size_t i : _z.get_batches()) {
                 for (std::size_t j = 0; j < _z.get_batch_size(i); ++j) {
@@ -503,8 +497,7 @@ public:
                     if (it == pts.end()) continue;
                     ptrs.push_back(_dev.at(i).at(j));
                     lens.push_back(_dev.at(i).len[j]);
-                    coeffs.resize(coeffs.size() + 4);
-                    adapter::scalar_to_limbs(theta_acc, &coeffs[coeffs.size() - 4]);
+                    coeffs.push_back(theta_acc);
                     constant = constant + _z.get(i, j, it - pts.begin()) * theta_acc;
                     theta_acc = theta_acc * theta;
                 }
@@ -516,13 +509,12 @@ public:
             if (fx == _batch_fixed.end() || !fx->second) continue;
             std::vector<const void *> ptrs;
             std::vector<std::size_t> lens;
-            std::vector<std::uint64_t> coeffs;
+            std::vector<value_type> coeffs;
             value_type constant = value_type::zero();
             for (std::size_t j = 0; j < _z.get_batch_size(i); ++j) {
                 ptrs.push_back(_dev.at(i).at(j));
                 lens.push_back(_dev.at(i).len[j]);
-                coeffs.resize(coeffs.size() + 4);
-                adapter::scalar_to_limbs(theta_acc, &coeffs[coeffs.size() - 4]);
+                coeffs.push_back(theta_acc);
                 constant = constant + _fixed_polys_values.at(i).at(j) * theta_acc;
                 theta_acc = theta_acc * theta;
             }
@@ -535,18 +527,10 @@ public:
            D[0] is the NTT of the zero-padded coefficients */
         const std::size_t D0 = domain_size(0);
         device_polynomial_dfs<CurveType> f(_ctx, D0);
-        {    /* the zero-padded copy in one pass on the device: f[j] = 1 * combined[j] below max_len - 1, zero behind */
-            const void *src = d_combined.get();
-            const std::size_t len = max_len - 1;
-            std::uint64_t one[4];
-            adapter::scalar_to_limbs(value_type::one(), one);
-            check(zkhip_poly_lincomb_dev(_ctx.get(), adapter::id, 1, &src, &len, one, 1, f.data(), D0, 0), "zkhip_poly_lincomb_dev", _ctx.get());
-        }
-        {
-            std::uint64_t w[4];
-            adapter::scalar_to_limbs(_fri_params.root_of_unity(_fri_params.log_domain), w);
-            check(zkhip_ntt_dev(_ctx.get(), adapter::id, f.data(), _fri_params.log_domain, 1, w, 0, nullptr), "zkhip_ntt_dev", _ctx.get());
-        }
+        /* the zero-padded copy in one pass on the device: f[j] = 1 * combined[j] below max_len - 1, zero behind (one term even when
+           max_len - 1 == 0, which zero_padded_copy would pass as none) */
+        fv::add_scaled(_ctx, d_combined.get(), max_len - 1, value_type::one(), f.data(), D0, false);
+        fv::ntt(_ctx, f.data(), _fri_params.log_domain, 1, _fri_params.root_of_unity(_fri_params.log_domain), false);
         lap("extension to D[0]");
         precommitment_type precommitment = [&]() {
             ZKHIP_PROFILE_SCOPE("Basic FRI Precommit time");    // precommit(combined_Q, ...), lpc.hpp:196-198
@@ -633,9 +617,7 @@ public:
 
         /* Initial proofs (:793-861): the values of every committed polynomial over D[0] at the pairs calculate_s walks from x */
         const std::size_t D0 = domain_size(0), pairs0 = (std::size_t)1 << (steps[0] - 1);
-        std::uint64_t w0[4], one[4];
-        adapter::scalar_to_limbs(_fri_params.root_of_unity(n), w0);
-        adapter::scalar_to_limbs(value_type::one(), one);
+        const value_type w0 = _fri_params.root_of_unity(n);
         std::vector<std::uint64_t> answers;
         for (const auto &it : _dev) {
             const device_batch &db = it.second;
@@ -643,16 +625,13 @@ public:
             for (std::size_t q = 0; q < lambda; ++q) qps[q].initial_proof[it.first].values.assign(count, std::vector<std::array<value_type, 2>>(pairs0));
             if (count == 0) continue;
             char *d_ext = static_cast<char *>(_scratch_ext.reserve(_ctx, count * D0 * 32));
-            for (std::size_t p = 0; p < count; ++p) {    // the zero-padded copy: 1 * coefficients below len, zero behind
-                const void *src = db.at(p);
-                check(zkhip_poly_lincomb_dev(_ctx.get(), adapter::id, 1, &src, &db.len[p], one, 1, d_ext + 32 * p * D0, D0, 0), "zkhip_poly_lincomb_dev", _ctx.get());
-            }
-            check(zkhip_ntt_dev(_ctx.get(), adapter::id, d_ext, n, count, w0, 0, nullptr), "zkhip_ntt_dev", _ctx.get());
+            for (std::size_t p = 0; p < count; ++p) fv::zero_padded_copy(_ctx, db.at(p), db.len[p], d_ext + 32 * p * D0, D0);    // len >= 1: commit refuses less
+            fv::ntt(_ctx, d_ext, n, count, w0, false);
             if (_time_query_phase) _ctx.sync();
             lap(times.reextend_ms);
             const zkhip_fri_query_set set = {d_ext, n, count, steps[0]};
             answers.resize(4 * lambda * (count << steps[0]));
-            check(zkhip_fri_query_dev(_ctx.get(), &set, 1, xi.data(), lambda, answers.data()), "zkhip_fri_query_dev", _ctx.get());
+            ZKHIP_CALL(_ctx, zkhip_fri_query_dev, &set, 1, xi.data(), lambda, answers.data());
             lap(times.gather_ms);
             const std::uint64_t *at = answers.data();
             for (std::size_t q = 0; q < lambda; ++q) {
@@ -688,7 +667,7 @@ public:
             std::vector<std::uint64_t> xr(lambda);
             for (std::size_t q = 0; q < lambda; ++q) xr[q] = xi[q] & (((std::uint64_t)1 << log_first) - 1);
             answers.resize(4 * lambda * elements);
-            check(zkhip_fri_query_dev(_ctx.get(), sets.data(), sets.size(), xr.data(), lambda, answers.data()), "zkhip_fri_query_dev", _ctx.get());
+            ZKHIP_CALL(_ctx, zkhip_fri_query_dev, sets.data(), sets.size(), xr.data(), lambda, answers.data());
             lap(times.gather_ms);
             const std::uint64_t *at = answers.data();
             for (std::size_t i = 0; i + 1 < R; ++i)
@@ -999,7 +978,7 @@ protected:
     precommitment_type build_tree_host(const void *d_evals, std::size_t batch, std::size_t log_domain, std::size_t fri_step) const {
         const std::size_t D = (std::size_t)1 << log_domain, total = batch * D, per_leaf = batch * ((std::size_t)1 << fri_step);
         void *d_leaves = _scratch_leaves.reserve(_ctx, std::max<std::size_t>(1, total) * 32);
-        check(zkhip_fri_leaves_dev(_ctx.get(), d_evals, log_domain, batch, fri_step, d_leaves), "zkhip_fri_leaves_dev", _ctx.get());
+        ZKHIP_CALL(_ctx, zkhip_fri_leaves_dev, d_evals, log_domain, batch, fri_step, d_leaves);
         if constexpr (builder_kind == detail::tree_builder_kind::streaming) {
             /* slices of whole leaves through two page-locked buffers: the copy of slice k + 1 is in flight while the caller absorbs slice k */
             const std::size_t slice = std::max<std::size_t>(1, (leaf_slice_elements + per_leaf - 1) / std::max<std::size_t>(1, per_leaf)) * std::max<std::size_t>(1, per_leaf);

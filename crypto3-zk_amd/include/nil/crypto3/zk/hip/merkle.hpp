@@ -63,8 +63,7 @@ public:
             bytes += x_indices.size() * t->depth() * 32;
         }
         std::vector<std::uint8_t> flat(bytes);
-        check(zkhip_merkle_paths_multi(ctx.get(), handles.data(), handles.size(), x_indices.data(), x_indices.size(), flat.data()), "zkhip_merkle_paths_multi",
-              ctx.get());
+        ZKHIP_CALL(ctx, zkhip_merkle_paths_multi, handles.data(), handles.size(), x_indices.data(), x_indices.size(), flat.data());
         std::vector<std::vector<device_merkle_path>> out(trees.size());
         const std::uint8_t *at = flat.data();
         for (std::size_t t = 0; t < trees.size(); ++t) {
@@ -84,19 +83,19 @@ public:
     device_merkle_tree(const context &ctx, zkhip_merkle *tree) : ctx_(&ctx) {
         zkhip_ctx *c = ctx.get();
         tree_ = std::shared_ptr<zkhip_merkle>(tree, [c](zkhip_merkle *t) { zkhip_merkle_free(c, t); });
-        check(zkhip_merkle_root(c, tree, root_.data()), "zkhip_merkle_root", c);
+        ZKHIP_CALL(ctx, zkhip_merkle_root, tree, root_.data());
     }
     /// the tree over `batch` polynomials resident as evaluations over the 2^log_domain-point domain, leaves as precommit<FRI> lays them out
     static device_merkle_tree from_evaluations(const context &ctx, int hash, const void *d_evals, std::size_t batch, std::size_t log_domain,
                                                std::size_t fri_step) {
         zkhip_merkle *t = nullptr;
-        check(zkhip_merkle_build_fri_dev(ctx.get(), hash, d_evals, log_domain, batch, fri_step, &t), "zkhip_merkle_build_fri_dev", ctx.get());
+        ZKHIP_CALL(ctx, zkhip_merkle_build_fri_dev, hash, d_evals, log_domain, batch, fri_step, &t);
         return device_merkle_tree(ctx, t);
     }
     /// the tree over a leaf layout on the device: n_leaves leaves of elements_per_leaf elements
     static device_merkle_tree from_leaves(const context &ctx, int hash, const void *d_leaves, std::size_t n_leaves, std::size_t elements_per_leaf) {
         zkhip_merkle *t = nullptr;
-        check(zkhip_merkle_build_dev(ctx.get(), hash, d_leaves, n_leaves, elements_per_leaf, &t), "zkhip_merkle_build_dev", ctx.get());
+        ZKHIP_CALL(ctx, zkhip_merkle_build_dev, hash, d_leaves, n_leaves, elements_per_leaf, &t);
         return device_merkle_tree(ctx, t);
     }
 
@@ -112,7 +111,7 @@ public:
         const std::size_t d = depth();
         std::vector<std::uint64_t> idx(leaf_indices.begin(), leaf_indices.end());
         std::vector<std::uint8_t> flat(idx.size() * d * 32);
-        check(zkhip_merkle_paths(ctx_->get(), tree_.get(), idx.data(), idx.size(), flat.data()), "zkhip_merkle_paths", ctx_->get());
+        ZKHIP_CALL(*ctx_, zkhip_merkle_paths, tree_.get(), idx.data(), idx.size(), flat.data());
         std::vector<proof_type> out(idx.size(), proof_type(d));
         for (std::size_t k = 0; k < idx.size(); ++k)
             for (std::size_t l = 0; l < d; ++l) std::copy_n(flat.data() + (k * d + l) * 32, 32, out[k][l].begin());
@@ -121,7 +120,7 @@ public:
     /// every digest: the leaves() leaf digests, then each level above, the root last
     std::vector<digest_type> digests() const {
         std::vector<digest_type> out(2 * leaves() - 1);
-        check(zkhip_merkle_digests(ctx_->get(), tree_.get(), out.front().data()), "zkhip_merkle_digests", ctx_->get());
+        ZKHIP_CALL(*ctx_, zkhip_merkle_digests, tree_.get(), out.front().data());
         return out;
     }
 

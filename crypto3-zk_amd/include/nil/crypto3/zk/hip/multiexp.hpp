@@ -72,7 +72,7 @@ typename detail::jac_result<CurveType, Group>::type multiexp(const context &ctx,
     typedef detail::jac_result<CurveType, Group> R;
     std::vector<std::uint64_t> s = detail::pack_scalars<CurveType>(scalars_begin, scalars_end);
     std::uint64_t jac[R::limbs];
-    check(zkhip_msm(ctx.get(), bases.get(), offset, s.size() / 4, s.data(), jac), "zkhip_msm", ctx.get());
+    ZKHIP_CALL(ctx, zkhip_msm, bases.get(), offset, s.size() / 4, s.data(), jac);
     return R::make(jac);
 }
 
@@ -82,7 +82,7 @@ typename detail::jac_result<CurveType, Group>::type multiexp_dev(const context &
                                                                  std::size_t n, const void *d_scalars) {
     typedef detail::jac_result<CurveType, Group> R;
     auto d_out = ctx.alloc(R::limbs * 8);
-    check(zkhip_msm_dev(ctx.get(), bases.get(), offset, n, d_scalars, d_out.get()), "zkhip_msm_dev", ctx.get());
+    ZKHIP_CALL(ctx, zkhip_msm_dev, bases.get(), offset, n, d_scalars, d_out.get());
     std::uint64_t jac[R::limbs];
     ctx.d2h(jac, d_out.get(), sizeof(jac));
     return R::make(jac);

@@ -177,13 +177,13 @@ public:
         const std::size_t n = q_last.size();
         const value_type one = value_type::one(), zero = value_type::zero();
         /* mask_assignment = one - q_last - q_blind (:162-163) */
-        dfs_type mask_assignment = body::affine(q_last, &q_blind, zero - one, zero - one, one);
+        dfs_type mask_assignment = affine(q_last, &q_blind, zero - one, zero - one, one);
         const std::vector<dfs_type> lookup_value = prepare_lookup_value(mask_assignment);
         const std::vector<dfs_type> lookup_input = prepare_input(theta);
         /* 3. reduce, sort (:175-189) */
         std::vector<dfs_type> reduced_value, reduced_input;
-        for (const auto &p : lookup_value) reduced_value.push_back(body::reduce_dfs_polynomial_domain(p, n));
-        for (const auto &p : lookup_input) reduced_input.push_back(body::reduce_dfs_polynomial_domain(p, n));
+        for (const auto &p : lookup_value) reduced_value.push_back(subsample(p, n));
+        for (const auto &p : lookup_input) reduced_input.push_back(subsample(p, n));
         std::vector<dfs_type> sorted = body::sort_polynomials(ctx, reduced_input, reduced_value, n, usable_rows);
         for (auto &s : sorted) s.set_degree(n - 1);
         /* a looked-up value that is in no table / a table that overflows the sorted vectors: the reference's BOOST_ASSERTs (:583, :613-617).
@@ -246,23 +246,20 @@ public:
                 std::vector<dfs_type> cols;
                 std::vector<const void *> ptrs;
                 std::vector<std::size_t> lens;
-                std::vector<std::uint64_t> coeffs;
+                std::vector<value_type> coeffs;
                 value_type theta_acc = theta;
                 for (std::size_t i = 0; i < (std::size_t)l_table.columns_number; ++i) {
                     cols.push_back(detail::on_device<CurveType>(ctx, plonk_columns.constant(option[i].index)));
                     if (cols.back().size() != n) throw std::invalid_argument("lookup argument: a table column's size differs from the basic domain's");
                     ptrs.push_back(cols.back().data());
                     lens.push_back(n);
-                    coeffs.resize(coeffs.size() + 4);
-                    body::adapter::scalar_to_limbs(theta_acc, coeffs.data() + coeffs.size() - 4);
+                    coeffs.push_back(theta_acc);
                     theta_acc = theta_acc * theta;
                 }
                 dfs_type lin(ctx, n);
-                if (!cols.empty())
-                    check(zkhip_poly_lincomb_dev(ctx.get(), body::adapter::id, ptrs.size(), ptrs.data(), lens.data(), coeffs.data(), 1, lin.data(), n, 0), "zkhip_poly_lincomb_dev",
-                          ctx.get());
+                if (!cols.empty()) fr_vector<CurveType>::lincomb(ctx, ptrs, lens, coeffs, 1, lin.data(), n, false);
                 /* + (t_id + 1): x + c over the vector (a x with a = 0 when there is no column: the constant polynomial) */
-                dfs_type shifted = body::affine(cols.empty() ? mask_assignment : lin, nullptr, cols.empty() ? value_type::zero() : value_type::one(), value_type::zero(),
+                dfs_type shifted = affine<CurveType>(cols.empty() ? mask_assignment : lin, nullptr, cols.empty() ? value_type::zero() : value_type::one(), value_type::zero(),
                                                 value_type((std::uint64_t)(t_id + 1)));
                 shifted.set_degree(cols.empty() ? 0 : n - 1);
                 ctx.sync();

@@ -47,18 +47,8 @@ struct placeholder_lookup_hip {
         std::vector<dfs_type> parts_dfs;    // the intermediate polynomials of the multi-part form, in PERMUTATION_BATCH order behind V_L
     };
 
-    /// lookup_argument.hpp:498-517 -- unlike resize() this does not look at the degree: the result is the vector of values on the smaller domain
-    static dfs_type reduce_dfs_polynomial_domain(const dfs_type &p, std::size_t new_domain_size) {
-        if (new_domain_size > p.size() || p.size() % new_domain_size) throw std::invalid_argument("reduce_dfs_polynomial_domain: not a sub-domain");
-        if (p.size() == new_domain_size) return p;
-        const context &ctx = p.ctx();
-        dfs_type out(ctx, new_domain_size);
-        const std::size_t lp = detail::ceil_log2(p.size()), ln = detail::ceil_log2(new_domain_size);
-        if (((std::size_t)1 << lp) != p.size() || ((std::size_t)1 << ln) != new_domain_size) throw std::invalid_argument("lookup argument: sizes must be powers of two");
-        std::uint64_t unused[4] = {1, 0, 0, 0};
-        check(zkhip_poly_resize_dev(ctx.get(), adapter::id, p.data(), lp, 1, unused, out.data(), ln, unused), "zkhip_poly_resize_dev", ctx.get());
-        return out;
-    }
+    /// lookup_argument.hpp:498-517 (fri.hpp: subsample)
+    static dfs_type reduce_dfs_polynomial_domain(const dfs_type &p, std::size_t new_domain_size) { return subsample(p, new_domain_size); }
 
     /// sort_polynomials (:565-638) over the REDUCED vectors, on the device (zkhip_lookup_sort_dev): |input| + |value| vectors of domain_size
     /// entries that never leave HBM on their way to commit(LOOKUP_BATCH) and compute_V_L.  The reference counts in an unordered_map and
@@ -81,7 +71,7 @@ struct placeholder_lookup_hip {
             sorted.emplace_back(ctx, domain_size);
             ps.push_back(sorted.back().data());
         }
-        check(zkhip_lookup_sort_dev(ctx.get(), pi.size(), pi.data(), pv.size(), pv.data(), domain_size, usable_rows, ps.data()), "zkhip_lookup_sort_dev", ctx.get());
+        ZKHIP_CALL(ctx, zkhip_lookup_sort_dev, pi.size(), pi.data(), pv.size(), pv.data(), domain_size, usable_rows, ps.data());
         return sorted;
     }
 
@@ -99,12 +89,9 @@ struct placeholder_lookup_hip {
             return p;
         };
         const auto pi = ptrs(reduced_input), pv = ptrs(reduced_value), ps = ptrs(sorted);
-        std::uint64_t bl[4], gl[4];
-        adapter::scalar_to_limbs(beta, bl);
-        adapter::scalar_to_limbs(gamma, gl);
         dfs_type V_L(ctx, n);
-        check(zkhip_lookup_grand_product_dev(ctx.get(), adapter::id, pi.size(), pi.data(), pv.size(), pv.data(), ps.size(), ps.data(), n, usable_rows, bl, gl, V_L.data()),
-              "zkhip_lookup_grand_product_dev", ctx.get());
+        ZKHIP_CALL(ctx, zkhip_lookup_grand_product_dev, adapter::id, pi.size(), pi.data(), pv.size(), pv.data(), ps.size(), ps.data(), n, usable_rows,
+                   limbs_of<adapter>(beta).data(), limbs_of<adapter>(gamma).data(), V_L.data());
         return V_L;
     }
 
@@ -134,7 +121,6 @@ struct placeholder_lookup_hip {
                                                 const std::vector<dfs_type> &sorted, const dfs_type &q_last, const dfs_type &q_blind, const dfs_type &lagrange_0,
                                                 const value_type &beta, const value_type &gamma, std::size_t usable_rows, const root_of_unity_type &root,
                                                 std::vector<std::size_t> part_sizes, const std::vector<value_type> &part_alphas, const hooks_type &hooks) {
-        typedef placeholder_permutation_hip<CurveType> PA;    // the shared helpers: plus / minus / scale / multiplied_up
         if (part_sizes.empty()) part_sizes.push_back(sorted.size());
         std::size_t covered = 0;
         for (std::size_t sz : part_sizes) {
@@ -181,9 +167,9 @@ struct placeholder_lookup_hip {
            inside polynomial_product; V_L(omega X) is a rotation of that extension; likewise lagrange_0 and q_last */
         std::size_t deg_g = 0;
         for (const auto &g : gs) deg_g = std::max(deg_g, g.degree());
-        const dfs_type V = PA::extended(V_L, PA::pow2_holding(V_L.degree() + deg_g), root);
+        const dfs_type V = V_L.extension(pow2_holding(V_L.degree() + deg_g), root);
         const dfs_type V_shifted = polynomial_shift(V, 1, n);
-        const dfs_type L0 = PA::extended(lagrange_0, 2 * n, root), QL = PA::extended(q_last, 4 * n, root);
+        const dfs_type L0 = lagrange_0.extension(2 * n, root), QL = q_last.extension(4 * n, root);
         prover_result_type res {{dfs_type(ctx, 1), dfs_type(ctx, 1), dfs_type(ctx, 1), dfs_type(ctx, 1)}, V_L, {}};
         /* F_dfs[0] = lagrange_0 (1 - V_L) = lagrange_0 - lagrange_0 V_L */
         res.F_dfs[0] = minus(L0, polynomial_product<CurveType>({L0, V}, root, L0.size()), root);
@@ -191,24 +177,15 @@ struct placeholder_lookup_hip {
         res.F_dfs[1] = minus(polynomial_product<CurveType>({QL, V, V}, root), polynomial_product<CurveType>({QL, V}, root, QL.size()), root);
         /* F_dfs[2] = ((q_last + q_blind) - 1) T = q T - T,  T = V_L g - V_L_shifted h (one part),
            T = sum_i alpha_i (previous g_i - current h_i) + previous g_last - V_L_shifted h_last (several) */
-        dfs_type T(ctx, 1), previous = V_L, previous_ext = V;
+        multi_part_sum<CurveType> m = multi_part_sum<CurveType>::run(V_L, V, V_L, gs, hs, part_alphas, n, usable_rows, hooks.on_part, root);    // on_part: :267
+        res.parts_dfs = m.parts;
+        dfs_type T = std::move(m.sum);
         const std::size_t parts = part_sizes.size();
-        for (std::size_t p = 0; p + 1 < parts; ++p) {
-            dfs_type current = PA::multiplied_up(previous, V_L, gs[p], hs[p], n, usable_rows);
-            res.parts_dfs.push_back(current);
-            if (hooks.on_part) hooks.on_part(current);    // :267
-            const dfs_type current_ext = PA::extended(current, V.size(), root);    // once for current h_p and, as the next previous, for previous g_(p + 1)
-            dfs_type part = minus(polynomial_product<CurveType>({previous_ext, gs[p]}, root), polynomial_product<CurveType>({current_ext, hs[p]}, root), root);
-            PA::scale(part, part_alphas[p]);
-            T = p == 0 ? part : PA::plus(T, part, root);
-            previous = current;
-            previous_ext = current_ext;
-        }
         {
-            dfs_type last = minus(polynomial_product<CurveType>({previous_ext, gs[parts - 1]}, root), polynomial_product<CurveType>({V_shifted, hs[parts - 1]}, root), root);
-            T = parts == 1 ? last : PA::plus(T, last, root);
+            dfs_type last = minus(polynomial_product<CurveType>({m.last_ext, gs[parts - 1]}, root), polynomial_product<CurveType>({V_shifted, hs[parts - 1]}, root), root);
+            T = parts == 1 ? last : plus(T, last, root);
         }
-        const dfs_type q = PA::selector_sum(q_last, q_blind, PA::pow2_holding(std::max(q_last.degree(), q_blind.degree()) + T.degree()), root);
+        const dfs_type q = selector_sum(q_last, q_blind, pow2_holding(std::max(q_last.degree(), q_blind.degree()) + T.degree()), root);
         res.F_dfs[2] = minus(polynomial_product<CurveType>({q, T}, root), T, root);
         /* F_dfs[3] = sum_i alpha_i lagrange_0 (sorted[i + 1] - sorted[i](omega^usable_rows X)) */
         if (sorted.size() > 1) {
@@ -232,22 +209,10 @@ struct placeholder_lookup_hip {
         return res;
     }
 
-    /// a x + b y + c over x's domain, into a buffer of its own
+    /// a x + b y + c over x's domain, into a buffer of its own; y may be null (fri.hpp: affine)
     static dfs_type affine(const dfs_type &x, const dfs_type *y, const value_type &a, const value_type &b, const value_type &c) {
-        if (y && y->size() != x.size()) throw std::invalid_argument("lookup argument: operands must share the domain");
-        dfs_type out(x.ctx(), x.size());
-        out.set_degree(y ? std::max(x.degree(), y->degree()) : x.degree());
-        std::uint64_t al[4], bl[4], cl[4];
-        adapter::scalar_to_limbs(a, al);
-        adapter::scalar_to_limbs(b, bl);
-        adapter::scalar_to_limbs(c, cl);
-        check(zkhip_fr_vec_affine_dev(x.ctx().get(), adapter::id, x.data(), y ? y->data() : nullptr, al, y ? bl : nullptr, cl, out.data(), x.size()),
-              "zkhip_fr_vec_affine_dev", x.ctx().get());
-        return out;
+        return nil::crypto3::zk::hip::affine<CurveType>(x, y, a, b, c);
     }
-
-private:
-    static dfs_type minus(const dfs_type &a, const dfs_type &b, const root_of_unity_type &root) { return placeholder_permutation_hip<CurveType>::minus(a, b, root); }
 };
 
 }    // namespace hip

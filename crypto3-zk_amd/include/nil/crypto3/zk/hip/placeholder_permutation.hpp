@@ -32,12 +32,45 @@ namespace crypto3 {
 namespace zk {
 namespace hip {
 
+/// The loop both multi-part arguments run over all parts but the last (ph/permutation_argument.hpp:188-207, lookup_argument.hpp:252-276): part p
+/// gives the intermediate polynomial current_p = previous g_p / h_p over the usable rows (multiplied_up; `fill`'s values behind them), handed
+/// to `on_part` where the reference appends it to its batch, and the term alpha_p (previous g_p - current_p h_p) of the sum.  `previous_ext`:
+/// `previous` on the domain every current is extended to ONCE -- for current h_p and, as the next previous, for previous g_(p + 1).
+template <typename CurveType>
+struct multi_part_sum {
+    typedef device_polynomial_dfs<CurveType> dfs_type;
+    std::vector<dfs_type> parts;    // one per alpha, in batch order
+    dfs_type sum;                   // sum_p alpha_p (previous_p g_p - current_p h_p); a one-element placeholder without alphas
+    dfs_type last_ext;              // the last current (without alphas: previous) on previous_ext's domain, for the caller's last part
+
+    static multi_part_sum run(dfs_type previous, dfs_type previous_ext, const dfs_type &fill, const std::vector<dfs_type> &gs, const std::vector<dfs_type> &hs,
+                              const std::vector<typename dfs_type::value_type> &alphas, std::size_t n, std::size_t usable_rows,
+                              const std::function<void(const dfs_type &)> &on_part, const typename dfs_type::root_of_unity_type &root) {
+        std::vector<dfs_type> parts;
+        dfs_type sum(previous.ctx(), 1);
+        const std::size_t ext_size = previous_ext.size();
+        for (std::size_t p = 0; p < alphas.size(); ++p) {
+            dfs_type current = multiplied_up(previous, fill, gs[p], hs[p], n, usable_rows);
+            parts.push_back(current);
+            if (on_part) on_part(current);
+            const dfs_type current_ext = current.extension(ext_size, root);
+            dfs_type part = minus(polynomial_product<CurveType>({previous_ext, gs[p]}, root), polynomial_product<CurveType>({current_ext, hs[p]}, root), root);
+            scale(part, alphas[p]);
+            sum = p == 0 ? part : plus(sum, part, root);
+            previous = current;
+            previous_ext = current_ext;
+        }
+        return {std::move(parts), std::move(sum), std::move(previous_ext)};
+    }
+};
+
 template <typename CurveType>
 struct placeholder_permutation_hip {
     typedef curve_adapter<CurveType> adapter;
     typedef typename adapter::scalar_value_type value_type;
     typedef device_polynomial_dfs<CurveType> dfs_type;
     typedef typename dfs_type::root_of_unity_type root_of_unity_type;
+    typedef fr_vector<CurveType> fv;
 
     struct prover_result_type {
         std::array<dfs_type, 3> F_dfs;
@@ -100,11 +133,8 @@ struct placeholder_permutation_hip {
             pi.push_back(S_id[i].data());
             ps.push_back(S_sigma[i].data());
         }
-        std::uint64_t bl[4], gl[4];
-        adapter::scalar_to_limbs(beta, bl);
-        adapter::scalar_to_limbs(gamma, gl);
-        check(zkhip_perm_grand_product_dev(ctx.get(), adapter::id, k, pc.data(), pi.data(), ps.data(), n, bl, gl, d_g.get(), d_h.get(), V_P.data()),
-              "zkhip_perm_grand_product_dev", ctx.get());
+        const auto bl = limbs_of<adapter>(beta), gl = limbs_of<adapter>(gamma);
+        ZKHIP_CALL(ctx, zkhip_perm_grand_product_dev, adapter::id, k, pc.data(), pi.data(), ps.data(), n, bl.data(), gl.data(), d_g.get(), d_h.get(), V_P.data());
         V_P.set_degree(n - 1);
         if (hooks.on_V_P) hooks.on_V_P(V_P);    // 4. (:139)
         /* 5.: gs[p] = prod of the p-th group's g_v, hs[p] likewise */
@@ -117,18 +147,17 @@ struct placeholder_permutation_hip {
                 std::vector<dfs_type> ext;    // alive until the pass ran
                 std::vector<const void *> ec, ei, es;
                 for (std::size_t i = lo; i < hi; ++i) {
-                    ext.push_back(extended(columns[i], size, root));
+                    ext.push_back(columns[i].extension(size, root));
                     ec.push_back(ext.back().data());
-                    ext.push_back(extended(S_id[i], size, root));
+                    ext.push_back(S_id[i].extension(size, root));
                     ei.push_back(ext.back().data());
-                    ext.push_back(extended(S_sigma[i], size, root));
+                    ext.push_back(S_sigma[i].extension(size, root));
                     es.push_back(ext.back().data());
                 }
                 dfs_type g(ctx, size), h(ctx, size);
                 g.set_degree((hi - lo) * (n - 1));
                 h.set_degree((hi - lo) * (n - 1));
-                check(zkhip_perm_factor_products_dev(ctx.get(), adapter::id, hi - lo, ec.data(), ei.data(), es.data(), size, bl, gl, g.data(), h.data()),
-                      "zkhip_perm_factor_products_dev", ctx.get());
+                ZKHIP_CALL(ctx, zkhip_perm_factor_products_dev, adapter::id, hi - lo, ec.data(), ei.data(), es.data(), size, bl.data(), gl.data(), g.data(), h.data());
                 gs.push_back(std::move(g));
                 hs.push_back(std::move(h));
                 continue;
@@ -136,8 +165,8 @@ struct placeholder_permutation_hip {
             for (std::size_t i = lo; i < hi; ++i) {
                 g_v.emplace_back(ctx, n);
                 h_v.emplace_back(ctx, n);
-                check(zkhip_memcpy_d2d_async(ctx.get(), g_v.back().data(), static_cast<const char *>(d_g.get()) + i * n * 32, n * 32), "zkhip_memcpy_d2d_async", ctx.get());
-                check(zkhip_memcpy_d2d_async(ctx.get(), h_v.back().data(), static_cast<const char *>(d_h.get()) + i * n * 32, n * 32), "zkhip_memcpy_d2d_async", ctx.get());
+                fv::copy(ctx, g_v.back().data(), static_cast<const char *>(d_g.get()) + i * n * 32, n);
+                fv::copy(ctx, h_v.back().data(), static_cast<const char *>(d_h.get()) + i * n * 32, n);
             }
             gs.push_back(polynomial_product<CurveType>(std::move(g_v), root));
             hs.push_back(polynomial_product<CurveType>(std::move(h_v), root));
@@ -146,9 +175,9 @@ struct placeholder_permutation_hip {
            others inside polynomial_product; V_P(omega X) is a rotation of that extension; likewise lagrange_0 and q_last */
         std::size_t deg_g = 0;
         for (const auto &g : gs) deg_g = std::max(deg_g, g.degree());
-        const dfs_type V = extended(V_P, pow2_holding(V_P.degree() + deg_g), root);
+        const dfs_type V = V_P.extension(pow2_holding(V_P.degree() + deg_g), root);
         const dfs_type V_shifted = polynomial_shift(V, 1, n);
-        const dfs_type L0 = extended(lagrange_0, 2 * n, root), QL = extended(q_last, 4 * n, root);
+        const dfs_type L0 = lagrange_0.extension(2 * n, root), QL = q_last.extension(4 * n, root);
         prover_result_type res {{dfs_type(ctx, 1), dfs_type(ctx, 1), dfs_type(ctx, 1)}, V_P, {}};
         /* F_dfs[0] = lagrange_0 (1 - V_P) = lagrange_0 - lagrange_0 V_P */
         res.F_dfs[0] = minus(L0, polynomial_product<CurveType>({L0, V}, root, L0.size()), root);
@@ -161,19 +190,10 @@ struct placeholder_permutation_hip {
             res.F_dfs[1] = minus(T, polynomial_product<CurveType>({q, T}, root), root);
         } else {
             /* F_dfs[1] = (q - 1)(sum_i alpha_i (previous g_i - current h_i) + previous g_last - V_P_shifted h_last) = q S - S */
-            dfs_type previous = V_P, previous_ext = V, S(ctx, 1);
-            for (std::size_t p = 0; p + 1 < parts; ++p) {
-                dfs_type current = multiplied_up(previous, V_P, gs[p], hs[p], n, usable_rows);
-                res.parts_dfs.push_back(current);
-                if (hooks.on_part) hooks.on_part(current);    // :200
-                const dfs_type current_ext = extended(current, V.size(), root);    // once for current h_p and, as the next previous, for previous g_(p + 1)
-                dfs_type part = minus(polynomial_product<CurveType>({previous_ext, gs[p]}, root), polynomial_product<CurveType>({current_ext, hs[p]}, root), root);
-                scale(part, alphas[p]);
-                S = p == 0 ? part : plus(S, part, root);
-                previous = current;
-                previous_ext = current_ext;
-            }
-            dfs_type last = minus(polynomial_product<CurveType>({previous_ext, gs[parts - 1]}, root), polynomial_product<CurveType>({V_shifted, hs[parts - 1]}, root), root);
+            multi_part_sum<CurveType> m = multi_part_sum<CurveType>::run(V_P, V, V_P, gs, hs, alphas, n, usable_rows, hooks.on_part, root);    // on_part: :200
+            res.parts_dfs = m.parts;
+            dfs_type last = minus(polynomial_product<CurveType>({m.last_ext, gs[parts - 1]}, root), polynomial_product<CurveType>({V_shifted, hs[parts - 1]}, root), root);
+            dfs_type S = std::move(m.sum);
             S = plus(S, last, root);
             res.F_dfs[1] = minus(polynomial_product<CurveType>({q, S}, root), S, root);
         }
@@ -183,79 +203,8 @@ struct placeholder_permutation_hip {
         return res;
     }
 
-    /// q_last + q_blind: on the n-point domain, or -- when both hold extension caches (preprocessed selectors) -- directly on the `size`-point one
-    /// their sum is multiplied on afterwards: two cached extensions and one addition instead of a transform
-    static dfs_type selector_sum(const dfs_type &q_last, const dfs_type &q_blind, std::size_t size, const root_of_unity_type &root) {
-        const bool cached = q_last.extension_cache_enabled() && q_blind.extension_cache_enabled();
-        const dfs_type a = cached ? extended(q_last, size, root) : q_last, b = cached ? extended(q_blind, size, root) : q_blind;
-        dfs_type q(a.ctx(), a.size());
-        q.set_degree(std::max(q_last.degree(), q_blind.degree()));
-        check(zkhip_fr_vec_op_dev(a.ctx().get(), adapter::id, 0, a.data(), b.data(), q.data(), a.size()), "zkhip_fr_vec_op_dev", a.ctx().get());
-        return q;
-    }
-    /// a x + b y + c over the shared domain, into a buffer of its own
-    static dfs_type affine(const dfs_type &x, const dfs_type &y, const value_type &a, const value_type &b, const value_type &c) {
-        if (y.size() != x.size()) throw std::invalid_argument("permutation argument: operands must share the domain");
-        dfs_type out(x.ctx(), x.size());
-        std::uint64_t al[4], bl[4], cl[4];
-        adapter::scalar_to_limbs(a, al);
-        adapter::scalar_to_limbs(b, bl);
-        adapter::scalar_to_limbs(c, cl);
-        check(zkhip_fr_vec_affine_dev(x.ctx().get(), adapter::id, x.data(), y.data(), al, bl, cl, out.data(), x.size()), "zkhip_fr_vec_affine_dev", x.ctx().get());
-        return out;
-    }
-    /// the intermediate polynomial of a part (:193-199): current[j] = previous[j] reduced_g[j] / reduced_h[j] for j < usable_rows, `fill`'s values
-    /// behind them (V_P's, which `current_poly` starts as); reduced = every (size / n)-th evaluation (reduce_dfs_polynomial_domain)
-    static dfs_type multiplied_up(const dfs_type &previous, const dfs_type &fill, const dfs_type &g, const dfs_type &h, std::size_t n, std::size_t usable_rows) {
-        const context &ctx = previous.ctx();
-        dfs_type current(ctx, n);
-        current.set_degree(n - 1);
-        check(zkhip_memcpy_d2d_async(ctx.get(), current.data(), fill.data(), n * 32), "zkhip_memcpy_d2d_async", ctx.get());
-        dfs_type rg = reduced(g, n), rh = reduced(h, n);
-        check(zkhip_fr_vec_mul_div_dev(ctx.get(), adapter::id, previous.data(), rg.data(), rh.data(), current.data(), usable_rows), "zkhip_fr_vec_mul_div_dev", ctx.get());
-        ctx.sync();    // rg, rh are released on return
-        return current;
-    }
-    /// p on the `size`-point domain (a copy with a buffer of its own; p itself where it already lives there)
-    static dfs_type extended(const dfs_type &p, std::size_t size, const root_of_unity_type &root) { return p.extension(size, root); }
-    static std::size_t pow2_holding(std::size_t degree) {
-        std::size_t size = 1;
-        while (size < degree + 1) size <<= 1;
-        return size;
-    }
-    static dfs_type reduced(const dfs_type &p, std::size_t n) {
-        if (p.size() == n) return p;
-        if (p.size() < n || p.size() % n) throw std::invalid_argument("permutation argument: not an extension of the basic domain");
-        dfs_type out(p.ctx(), n);
-        const std::size_t lp = detail::ceil_log2(p.size()), ln = detail::ceil_log2(n);
-        std::uint64_t unused[4] = {1, 0, 0, 0};
-        check(zkhip_poly_resize_dev(p.ctx().get(), adapter::id, p.data(), lp, 1, unused, out.data(), ln, unused), "zkhip_poly_resize_dev", p.ctx().get());
-        return out;
-    }
-    /// a + b on the larger of the two domains, into a buffer of its own
-    static dfs_type plus(dfs_type a, dfs_type b, const root_of_unity_type &root) { return combine(0, a, b, root); }
-    /// a - b likewise (copies of a device_polynomial_dfs share their buffer: never in place)
-    static dfs_type minus(dfs_type a, dfs_type b, const root_of_unity_type &root) { return combine(1, a, b, root); }
-    /// p *= c, in place (a view of a cached extension gets a buffer of its own first; p's own cached extensions go)
-    static void scale(dfs_type &p, const value_type &c) {
-        p.make_writable();
-        std::uint64_t cl[4], zl[4];
-        adapter::scalar_to_limbs(c, cl);
-        adapter::scalar_to_limbs(value_type::zero(), zl);
-        check(zkhip_fr_vec_affine_dev(p.ctx().get(), adapter::id, p.data(), nullptr, cl, nullptr, zl, p.data(), p.size()), "zkhip_fr_vec_affine_dev", p.ctx().get());
-    }
-
-private:
-    static dfs_type combine(int op, dfs_type a, dfs_type b, const root_of_unity_type &root) {
-        const std::size_t size = std::max(a.size(), b.size());
-        a.resize(size, root);
-        b.resize(size, root);
-        dfs_type out(a.ctx(), size);
-        out.set_degree(std::max(a.degree(), b.degree()));
-        check(zkhip_fr_vec_op_dev(a.ctx().get(), adapter::id, op, a.data(), b.data(), out.data(), size), "zkhip_fr_vec_op_dev", a.ctx().get());
-        a.ctx().sync();    // a and b are released on return
-        return out;
-    }
+    /// p *= c, in place (fri.hpp: scale)
+    static void scale(dfs_type &p, const value_type &c) { nil::crypto3::zk::hip::scale<CurveType>(p, c); }
 };
 
 }    // namespace hip

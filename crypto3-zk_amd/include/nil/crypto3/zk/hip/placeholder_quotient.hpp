@@ -43,6 +43,7 @@ struct placeholder_quotient_hip {
     typedef typename adapter::scalar_value_type value_type;
     typedef device_polynomial_dfs<CurveType> dfs_type;
     typedef typename dfs_type::root_of_unity_type root_of_unity_type;
+    typedef fr_vector<CurveType> fv;
 
     /// A coefficient vector resident on the device (math::polynomial as far as this chain needs it)
     struct device_coefficients {
@@ -81,9 +82,7 @@ struct placeholder_quotient_hip {
         if (((std::size_t)1 << log_n) != n || ((std::size_t)1 << log_e) != extended_size || extended_size < n)
             throw std::invalid_argument("gate_argument: domain sizes must be powers of two, extended >= original");
         const std::int64_t stretch = (std::int64_t)(extended_size / n);    // one row of the original domain = this many of the extended one
-        std::uint64_t wn[4], we[4];
-        adapter::scalar_to_limbs(root(log_n), wn);
-        adapter::scalar_to_limbs(root(log_e), we);
+        const value_type wn = root(log_n), we = root(log_e);
         dfs_type F(ctx, extended_size);
         std::size_t F_degree = 0;
         const std::size_t max_slots = std::max<std::size_t>(2, slot_budget / (extended_size * 32));
@@ -125,10 +124,10 @@ struct placeholder_quotient_hip {
                 for (std::size_t b = 0; b < slots; ++b) {
                     const std::size_t u = batched[b];
                     const dfs_type &f = u < U ? *unique[u] : mask_polynomial;
-                    check(zkhip_memcpy_d2d_async(ctx.get(), static_cast<char *>(d_in.get()) + b * n * 32, f.data(), n * 32), "zkhip_memcpy_d2d_async", ctx.get());
+                    fv::copy(ctx, static_cast<char *>(d_in.get()) + b * n * 32, f.data(), n);
                     ext_of[u] = static_cast<const char *>(d_ext.get()) + b * extended_size * 32;
                 }
-                check(zkhip_poly_resize_dev(ctx.get(), adapter::id, d_in.get(), log_n, slots, wn, d_ext.get(), log_e, we), "zkhip_poly_resize_dev", ctx.get());
+                fv::resize(ctx, d_in.get(), log_n, slots, wn, d_ext.get(), log_e, we);
             }
             /* the flat program of the group */
             std::vector<std::uint32_t> gate_terms {0}, gate_sel, term_factors {0}, factor_slot;
@@ -151,8 +150,8 @@ struct placeholder_quotient_hip {
                     factor_rot.push_back((std::int32_t)(g.rotations[k] * stretch));
                 }
                 term_factors.push_back((std::uint32_t)factor_slot.size());
-                term_coeff.resize(term_coeff.size() + 4);
-                adapter::scalar_to_limbs(g.coefficient, term_coeff.data() + term_coeff.size() - 4);
+                const auto coefficient = limbs_of<adapter>(g.coefficient);
+                term_coeff.insert(term_coeff.end(), coefficient.begin(), coefficient.end());
             }
             gate_terms.push_back((std::uint32_t)(term_factors.size() - 1));
             zkhip_gate_program prog;
@@ -167,8 +166,7 @@ struct placeholder_quotient_hip {
             prog.factor_slot = factor_slot.data();
             prog.factor_rot = factor_rot.data();
             prog.term_coeff = term_coeff.data();
-            check(zkhip_gate_eval_dev(ctx.get(), adapter::id, &prog, ext_of.data(), log_e, last && mask_ptr ? ext_of[U] : nullptr, lo != 0 ? 1 : 0, F.data()),
-                  "zkhip_gate_eval_dev", ctx.get());
+            ZKHIP_CALL(ctx, zkhip_gate_eval_dev, adapter::id, &prog, ext_of.data(), log_e, last && mask_ptr ? ext_of[U] : nullptr, lo != 0 ? 1 : 0, F.data());
             lo = hi;
             ctx.sync();    // the group's extensions are released at the end of the iteration
         }
@@ -188,9 +186,7 @@ struct placeholder_quotient_hip {
         const std::size_t log_n = detail::ceil_log2(n), log_e = detail::ceil_log2(extended_size);
         if (((std::size_t)1 << log_n) != n || ((std::size_t)1 << log_e) != extended_size || extended_size < n)
             throw std::invalid_argument("gate_argument: domain sizes must be powers of two, extended >= original");
-        std::uint64_t wn[4], we[4];
-        adapter::scalar_to_limbs(root(log_n), wn);
-        adapter::scalar_to_limbs(root(log_e), we);
+        const value_type wn = root(log_n), we = root(log_e);
         /* Every DISTINCT (column, rotation) the gates name is extended ONCE (the reference's evaluator caches a variable's extension the same way):
            the distinct factors of a group of gates -- and, with the first group, the mask -- are laid side by side (the rotation of a factor
            writes straight into its slot) and extended by ONE call (a batched inverse NTT of n points + a batched NTT of extended_size points: the
@@ -247,13 +243,13 @@ struct placeholder_quotient_hip {
                 const dfs_type &f = u < U ? *unique[u].first : mask_polynomial;
                 const int rot = u < U ? unique[u].second : 0;
                 char *slot = static_cast<char *>(d_in.get()) + b * n * 32;
-                if (rot) check(zkhip_poly_shift_dev(ctx.get(), f.data(), log_n, (std::int64_t)rot, slot), "zkhip_poly_shift_dev", ctx.get());
-                else check(zkhip_memcpy_d2d_async(ctx.get(), slot, f.data(), n * 32), "zkhip_memcpy_d2d_async", ctx.get());
+                if (rot) fv::shift(ctx, f.data(), log_n, (std::int64_t)rot, slot);
+                else fv::copy(ctx, slot, f.data(), n);
                 ext_of[u] = static_cast<const char *>(d_ext.get()) + b * extended_size * 32;
             }
             if (slots) {
-                if (extended_size == n) check(zkhip_memcpy_d2d_async(ctx.get(), d_ext.get(), d_in.get(), slots * n * 32), "zkhip_memcpy_d2d_async", ctx.get());
-                else check(zkhip_poly_resize_dev(ctx.get(), adapter::id, d_in.get(), log_n, slots, wn, d_ext.get(), log_e, we), "zkhip_poly_resize_dev", ctx.get());
+                if (extended_size == n) fv::copy(ctx, d_ext.get(), d_in.get(), slots * n);
+                else fv::resize(ctx, d_in.get(), log_n, slots, wn, d_ext.get(), log_e, we);
             }
             dfs_type term(ctx, extended_size);
             for (std::size_t gi = lo; gi < hi; ++gi) {
@@ -265,26 +261,22 @@ struct placeholder_quotient_hip {
                     ptrs.push_back(ext_of[slot_of(g.factors[k], g.rotations[k])]);
                 }
                 if (degree >= extended_size) throw std::invalid_argument("gate_argument: the product's degree does not fit the extended domain");
-                check(zkhip_fr_vec_prod_dev(ctx.get(), adapter::id, ptrs.size(), ptrs.data(), term.data(), extended_size), "zkhip_fr_vec_prod_dev", ctx.get());
+                fv::product(ctx, ptrs, term.data(), extended_size);
                 /* F (+)= coefficient * term */
-                std::uint64_t c[4];
-                adapter::scalar_to_limbs(g.coefficient, c);
-                const void *tp = term.data();
                 const bool very_first = first && gi == lo;
-                check(zkhip_poly_lincomb_dev(ctx.get(), adapter::id, 1, &tp, &extended_size, c, 1, F.data(), extended_size, very_first ? 0 : 1), "zkhip_poly_lincomb_dev",
-                      ctx.get());
+                fv::add_scaled(ctx, term.data(), extended_size, g.coefficient, F.data(), extended_size, !very_first);
                 F.set_degree(very_first ? degree : std::max(F.degree(), degree));
             }
             if (first) {    // keep the extended mask for the final product
                 d_mask_ext = ctx.alloc(extended_size * 32);
-                check(zkhip_memcpy_d2d_async(ctx.get(), d_mask_ext.get(), ext_of[U], extended_size * 32), "zkhip_memcpy_d2d_async", ctx.get());
+                fv::copy(ctx, d_mask_ext.get(), ext_of[U], extended_size);
             }
             first = false;
             lo = hi;
             ctx.sync();    // d_in, d_ext and `term` are released at the end of the iteration
         }
         if (F.degree() + mask_polynomial.degree() >= extended_size) throw std::invalid_argument("gate_argument: mask * F does not fit the extended domain");
-        check(zkhip_fr_vec_op_dev(ctx.get(), adapter::id, 2, F.data(), d_mask_ext.get(), F.data(), extended_size), "zkhip_fr_vec_op_dev", ctx.get());    // gates_argument.hpp:215
+        fv::pointwise(ctx, fr_op::mul, F.data(), d_mask_ext.get(), F.data(), extended_size);    // gates_argument.hpp:215
         F.set_degree(F.degree() + mask_polynomial.degree());
         ctx.sync();
         return F;
@@ -311,42 +303,33 @@ struct placeholder_quotient_hip {
         std::vector<std::shared_ptr<void>> parts;
         std::vector<const void *> ptrs;
         std::vector<std::size_t> lens;
-        std::vector<std::uint64_t> coeffs;
-        std::uint64_t one_limbs[4];
-        adapter::scalar_to_limbs(value_type::one(), one_limbs);
         for (const auto &group : by_size) {
             const std::size_t gsize = group.first;
             std::vector<const void *> gp;
             std::vector<std::size_t> gl;
-            std::vector<std::uint64_t> gc;
+            std::vector<value_type> gc;
             for (std::size_t i : group.second) {
                 gp.push_back(F_dfs[i].data());
                 gl.push_back(gsize);
-                std::uint64_t a[4];
-                adapter::scalar_to_limbs(alphas[i], a);
-                gc.insert(gc.end(), a, a + 4);
+                gc.push_back(alphas[i]);
             }
             auto acc = ctx.alloc(gsize * 32);    // sum_i alpha_i F_i over this domain, then its coefficients in place
-            check(zkhip_poly_lincomb_dev(ctx.get(), adapter::id, gp.size(), gp.data(), gl.data(), gc.data(), 1, acc.get(), gsize, 0), "zkhip_poly_lincomb_dev", ctx.get());
+            fv::lincomb(ctx, gp, gl, gc, 1, acc.get(), gsize, false);
             const std::size_t log_g = detail::ceil_log2(gsize);
             if (((std::size_t)1 << log_g) != gsize) throw std::invalid_argument("quotient_polynomial: a part's size is not a power of two");
-            std::uint64_t w[4];
-            adapter::scalar_to_limbs(root(log_g), w);
-            check(zkhip_ntt_dev(ctx.get(), adapter::id, acc.get(), log_g, 1, w, 1, nullptr), "zkhip_ntt_dev", ctx.get());
+            fv::ntt(ctx, acc.get(), log_g, 1, root(log_g), true);
             parts.push_back(acc);
             ptrs.push_back(acc.get());
             lens.push_back(gsize);
-            coeffs.insert(coeffs.end(), one_limbs, one_limbs + 4);
         }
         dfs_type F(ctx, size);    // holds COEFFICIENTS from here on
-        check(zkhip_poly_lincomb_dev(ctx.get(), adapter::id, ptrs.size(), ptrs.data(), lens.data(), coeffs.data(), 1, F.data(), size, 0), "zkhip_poly_lincomb_dev",
-              ctx.get());
+        fv::lincomb(ctx, ptrs, lens, std::vector<value_type>(ptrs.size(), value_type::one()), 1, F.data(), size, false);
         /* T_consolidated = F_consolidated_normal / common_data.Z (:275) */
         device_coefficients T;
         T.size = size - rows_amount;
         T.data = ctx.alloc(T.size * 32);
         std::uint64_t bad = 0;
-        check(zkhip_poly_div_vanishing_dev(ctx.get(), adapter::id, F.data(), size, rows_amount, T.data.get(), &bad), "zkhip_poly_div_vanishing_dev", ctx.get());
+        ZKHIP_CALL(ctx, zkhip_poly_div_vanishing_dev, adapter::id, F.data(), size, rows_amount, T.data.get(), &bad);
         if (bad) throw std::runtime_error("quotient_polynomial: F_consolidated is not divisible by the vanishing polynomial");
         return T;
     }
@@ -362,17 +345,13 @@ struct placeholder_quotient_hip {
         if (dfs_size < rows_amount) throw std::invalid_argument("quotient_polynomial_split_dfs: dfs_size < rows_amount");
         std::vector<dfs_type> out;
         const std::size_t log_size = detail::ceil_log2(dfs_size);
-        std::uint64_t w[4];
-        adapter::scalar_to_limbs(root(log_size), w);
+        const value_type w = root(log_size);
         for (std::size_t k = 0; k < split_polynomial_size; ++k) {
             dfs_type p(ctx, dfs_size);
             const std::size_t lo = k * rows_amount, len = lo < T.size ? std::min(rows_amount, T.size - lo) : 0;
             /* zero-padded chunk -> evaluations (from_coefficients) */
-            const void *src = len ? T.at(lo) : nullptr;
-            std::uint64_t one[4];
-            adapter::scalar_to_limbs(value_type::one(), one);
-            check(zkhip_poly_lincomb_dev(ctx.get(), adapter::id, len ? 1 : 0, &src, &len, one, 1, p.data(), dfs_size, 0), "zkhip_poly_lincomb_dev", ctx.get());
-            check(zkhip_ntt_dev(ctx.get(), adapter::id, p.data(), log_size, 1, w, 0, nullptr), "zkhip_ntt_dev", ctx.get());
+            fv::zero_padded_copy(ctx, len ? T.at(lo) : nullptr, len, p.data(), dfs_size);
+            fv::ntt(ctx, p.data(), log_size, 1, w, false);
             p.set_degree(len ? len - 1 : 0);
             out.push_back(std::move(p));
         }
@@ -390,13 +369,10 @@ struct placeholder_quotient_hip {
         if (chunks > split_polynomial_size) throw std::invalid_argument("quotient_polynomial_split_coefficients: the quotient needs more parts than split_polynomial_size");
         if (dfs_size < rows_amount || (dfs_size & (dfs_size - 1))) throw std::invalid_argument("quotient_polynomial_split_coefficients: dfs_size must be a power of two >= rows_amount");
         std::vector<device_polynomial_coefficients<CurveType>> out;
-        std::uint64_t one[4];
-        adapter::scalar_to_limbs(value_type::one(), one);
         for (std::size_t k = 0; k < split_polynomial_size; ++k) {
             device_polynomial_coefficients<CurveType> p(ctx, dfs_size);
             const std::size_t lo = k * rows_amount, len = lo < T.size ? std::min(rows_amount, T.size - lo) : 0;
-            const void *src = len ? T.at(lo) : nullptr;
-            check(zkhip_poly_lincomb_dev(ctx.get(), adapter::id, len ? 1 : 0, &src, &len, one, 1, p.data(), dfs_size, 0), "zkhip_poly_lincomb_dev", ctx.get());
+            fv::zero_padded_copy(ctx, len ? T.at(lo) : nullptr, len, p.data(), dfs_size);
             p.set_known_zero(len == 0);    // a part beyond the quotient's length
             out.push_back(std::move(p));
         }

@@ -96,7 +96,7 @@ namespace detail {
     void add_roots(root_map &roots, const device_batch &db, const RootFn &root_of_unity, Skip skip = Skip()) {
         for (std::size_t i = 0; i < db.size(); ++i) {
             const std::size_t log_n = ceil_log2(db.len[i]);
-            if (!skip(i) && !roots.count(log_n)) Adapter::scalar_to_limbs(root_of_unity(log_n), roots[log_n].data());
+            if (!skip(i) && !roots.count(log_n)) roots[log_n] = limbs_of<Adapter>(root_of_unity(log_n));
         }
     }
 
@@ -222,9 +222,7 @@ protected:
     /// every polynomial of committed batch k at x
     std::vector<scalar_value_type> evaluate_batch_at(std::size_t k, const scalar_value_type &x) const {
         const device_batch &db = _dev.at(k);
-        std::uint64_t pt[4];
-        adapter::scalar_to_limbs(x, pt);
-        const std::vector<std::uint64_t> vals = evaluate_runs(db, pt, 1);
+        const std::vector<std::uint64_t> vals = evaluate_runs(db, limbs_of<adapter>(x).data(), 1);
         std::vector<scalar_value_type> out(db.size());
         for (std::size_t p = 0; p < db.size(); ++p) out[p] = adapter::scalar_from_limbs(&vals[4 * p]);
         return out;
@@ -256,8 +254,7 @@ private:
         std::vector<std::uint64_t> vals(4 * db.size() * count);
         if (count != 0)
             db.for_each_run(0, db.size(), 0, 0, [&](std::size_t i, std::size_t j) {
-                check(zkhip_poly_eval_dev(_ctx.get(), adapter::id, db.at(i), db.len[i], db.len[i], j - i, pts, count, &vals[4 * i * count]),
-                      "zkhip_poly_eval_dev", _ctx.get());
+                ZKHIP_CALL(_ctx, zkhip_poly_eval_dev, adapter::id, db.at(i), db.len[i], db.len[i], j - i, pts, count, &vals[4 * i * count]);
             });
         return vals;
     }

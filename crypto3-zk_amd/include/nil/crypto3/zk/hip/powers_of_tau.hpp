@@ -22,6 +22,7 @@
 #include <utility>
 #include <vector>
 
+#include "fr_vector.hpp"
 #include "multiexp.hpp"
 
 namespace nil {
@@ -45,9 +46,7 @@ std::vector<typename detail::jac_result<CurveType, Group>::type>
         if (adapter::point_to_affine_limbs(*it, &jac[i * R::limbs])) jac[i * R::limbs + 2 * cl] = 1;
     auto d = ctx.alloc(jac.size() * 8);
     ctx.h2d(d.get(), jac.data(), jac.size() * 8);
-    std::uint64_t w[4];
-    adapter::scalar_to_limbs(omega, w);
-    check(zkhip_ec_ntt_dev(ctx.get(), adapter::id, Group, d.get(), log_m, w, 1), "zkhip_ec_ntt_dev", ctx.get());
+    ZKHIP_CALL(ctx, zkhip_ec_ntt_dev, adapter::id, Group, d.get(), log_m, limbs_of<adapter>(omega).data(), 1);
     ctx.d2h(jac.data(), d.get(), jac.size() * 8);
     std::vector<typename R::type> out;
     for (i = 0; i < m; ++i) out.push_back(R::make(&jac[i * R::limbs]));
@@ -86,7 +85,7 @@ namespace detail {
         const std::size_t offsets[2] = {off1, off2}, ns[2] = {n, n};
         const void *scalars[2] = {d_scalars, d_scalars};
         void *outs[2] = {d_out.get(), static_cast<char *>(d_out.get()) + R::limbs * 8};
-        check(zkhip_msm_batch_dev(ctx.get(), 2, bases, offsets, ns, scalars, outs), "zkhip_msm_batch_dev", ctx.get());
+        ZKHIP_CALL(ctx, zkhip_msm_batch_dev, 2, bases, offsets, ns, scalars, outs);
         std::uint64_t jac[2 * R::limbs];
         ctx.d2h(jac, d_out.get(), sizeof(jac));
         return std::make_pair(R::make(jac), R::make(jac + R::limbs));

@@ -43,7 +43,7 @@ public:
         if (state.size() != 32) throw std::invalid_argument("proof_of_work_hip: the transcript's state is not a 32-byte digest");
         OutType proof_of_work = 0;
         /* nothing found in the whole 2^32 space (where the reference loops forever): ZKHIP_ERR_NOT_FOUND, thrown by check */
-        check(zkhip_pow_grind(ctx.get(), ZKHIP_HASH_SHA2_256, state.data(), start, mask, 0, 0, &proof_of_work, nullptr), "zkhip_pow_grind", ctx.get());
+        ZKHIP_CALL(ctx, zkhip_pow_grind, ZKHIP_HASH_SHA2_256, state.data(), start, mask, 0, 0, &proof_of_work, nullptr);
         if (!verify(transcript, proof_of_work, mask))
             throw std::logic_error("proof_of_work_hip: the transcript rejects the device's nonce (it is not the SHA2-256 sequential transcript)");
         return proof_of_work;

@@ -143,9 +143,8 @@ public:
                 rp[k].push_back((std::uint32_t)cl[k].size());
             }
         }
-        check(zkhip_r1cs_upload(ctx.get(), adapter::id, cs.num_constraints(), cs.num_inputs(), cs.num_variables(), rp[0].data(), cl[0].data(),
-                                cf[0].data(), rp[1].data(), cl[1].data(), cf[1].data(), rp[2].data(), cl[2].data(), cf[2].data(), &r_),
-              "zkhip_r1cs_upload", ctx.get());
+        ZKHIP_CALL(ctx, zkhip_r1cs_upload, adapter::id, cs.num_constraints(), cs.num_inputs(), cs.num_variables(), rp[0].data(), cl[0].data(), cf[0].data(),
+                   rp[1].data(), cl[1].data(), cf[1].data(), rp[2].data(), cl[2].data(), cf[2].data(), &r_);
     }
     /// a second handle on the same resident matrices (read-only after construction and set_domain), for another prover lane
     struct alias_tag { };
@@ -201,11 +200,8 @@ struct r1cs_to_qap_hip {
         ctx.h2d(d_assignment.get(), z.data(), z.size() * 8);
         auto d_h = ctx.alloc((m + 1) * 32);
         auto d_scratch = ctx.alloc(zkhip_groth16_scratch_bytes(cs.get()));
-        std::uint64_t g[4];
         const zkhip_domain dd = domain.c_desc();
-        adapter::scalar_to_limbs(dom.coset_generator, g);
-        check(zkhip_groth16_witness_h_domain_dev(ctx.get(), cs.get(), d_assignment.get(), &dd, g, d_h.get(), d_scratch.get()),
-              "zkhip_groth16_witness_h_domain_dev", ctx.get());
+        ZKHIP_CALL(ctx, zkhip_groth16_witness_h_domain_dev, cs.get(), d_assignment.get(), &dd, limbs_of<adapter>(dom.coset_generator).data(), d_h.get(), d_scratch.get());
         ctx.sync();    // d_scratch is released on return
         return d_h;
     }
@@ -398,7 +394,7 @@ public:
         d_cpa = ctx.alloc(cpa_elems * 32);
         {
             void *hp = nullptr;
-            check(zkhip_host_alloc(ctx.get(), cpa_elems * 32, &hp), "zkhip_host_alloc", ctx.get());
+            ZKHIP_CALL(ctx, zkhip_host_alloc, cpa_elems * 32, &hp);
             zkhip_ctx *c = ctx.get();
             h_cpa = std::shared_ptr<void>(hp, [c](void *p) { zkhip_host_free(c, p); });
         }
@@ -704,10 +700,10 @@ public:
             pk.ctx.wait_for(*pk.side);
             pk.ctx.set_option("msm_sort_tile_log", pk.saved_sort_tile_log);
         }
-        check(zkhip_memcpy_d2d_async(pk.ctx.get(), d_mine, pk.d_results.get(), partial_limbs() * 8), "zkhip_memcpy_d2d_async", pk.ctx.get());
+        ZKHIP_CALL(pk.ctx, zkhip_memcpy_d2d_async, d_mine, pk.d_results.get(), partial_limbs() * 8);
         /* kernels flag what they cannot signal otherwise; zkhip_device_status synchronises the stream: d_mine is complete after it */
-        check(zkhip_device_status(pk.ctx.get(), nullptr), "zkhip_device_status", pk.ctx.get());
-        if (pk.side) check(zkhip_device_status(pk.side->get(), nullptr), "zkhip_device_status", pk.side->get());
+        ZKHIP_CALL(pk.ctx, zkhip_device_status, nullptr);
+        if (pk.side) ZKHIP_CALL(*pk.side, zkhip_device_status, nullptr);
         guard.armed = false;    // both streams have drained
         all_gather();
         std::vector<std::uint64_t> all(pk.shard.world * partial_limbs());
@@ -767,8 +763,8 @@ public:
         /* kernels flag what they cannot signal otherwise; zkhip_device_status drains every member's streams */
         for (std::size_t k = 0; k < world; ++k) {
             const proving_key_type &pk = *gk.members[k];
-            check(zkhip_device_status(pk.ctx.get(), nullptr), "zkhip_device_status", pk.ctx.get());
-            if (pk.side) check(zkhip_device_status(pk.side->get(), nullptr), "zkhip_device_status", pk.side->get());
+            ZKHIP_CALL(pk.ctx, zkhip_device_status, nullptr);
+            if (pk.side) ZKHIP_CALL(*pk.side, zkhip_device_status, nullptr);
             guards[k]->armed = false;
         }
         const auto t3 = clock::now();
@@ -843,10 +839,9 @@ private:
             /* scalar values that ARE canonical limbs in memory: the auxiliary input goes out as it lies (0.3 ms per 2^20-constraint
                proof less than through the staging buffer) */
             static_assert(!detail::canonical_scalars<adapter>::value || sizeof(scalar_value_type) == 32, "canonical-limb scalars are 4 x u64");
-            check(zkhip_memcpy_h2d_async(ctx.get(), cpa, z, 32 * (1 + num_inputs)), "zkhip_memcpy_h2d_async", ctx.get());
+            ZKHIP_CALL(ctx, zkhip_memcpy_h2d_async, cpa, z, 32 * (1 + num_inputs));
             if (!auxiliary_input.empty())
-                check(zkhip_memcpy_h2d_async(ctx.get(), cpa + 32 * (1 + num_inputs), auxiliary_input.data(), 32 * auxiliary_input.size()),
-                      "zkhip_memcpy_h2d_async", ctx.get());
+                ZKHIP_CALL(ctx, zkhip_memcpy_h2d_async, cpa + 32 * (1 + num_inputs), auxiliary_input.data(), 32 * auxiliary_input.size());
         } else {
             const std::size_t aux = auxiliary_input.size(), slices = aux >= (std::size_t)1 << 16 ? 8 : 1, per = (aux + slices - 1) / slices;
             std::uint64_t *za = z + 4 * (1 + num_inputs);
@@ -856,13 +851,12 @@ private:
                     for (std::size_t i = k * per; i < std::min(aux, (k + 1) * per); ++i) adapter::scalar_to_limbs(auxiliary_input[i], &za[4 * i]);
                 }));
             for (std::size_t i = 0; i < std::min(aux, per); ++i) adapter::scalar_to_limbs(auxiliary_input[i], &za[4 * i]);
-            check(zkhip_memcpy_h2d_async(ctx.get(), cpa, z, 32 * (1 + num_inputs + std::min(aux, per))), "zkhip_memcpy_h2d_async", ctx.get());
+            ZKHIP_CALL(ctx, zkhip_memcpy_h2d_async, cpa, z, 32 * (1 + num_inputs + std::min(aux, per)));
             for (std::size_t k = 1; k < slices; ++k) {
                 ready[k - 1].get();
                 const std::size_t lo = k * per, hi = std::min(aux, (k + 1) * per);
                 if (hi > lo)
-                    check(zkhip_memcpy_h2d_async(ctx.get(), cpa + 32 * (1 + num_inputs + lo), za + 4 * lo, 32 * (hi - lo)), "zkhip_memcpy_h2d_async",
-                          ctx.get());
+                    ZKHIP_CALL(ctx, zkhip_memcpy_h2d_async, cpa + 32 * (1 + num_inputs + lo), za + 4 * lo, 32 * (hi - lo));
             }
         }
     }
@@ -880,14 +874,12 @@ private:
         char *cpa = static_cast<char *>(pk.d_cpa.get());
         std::uint64_t *d_res = static_cast<std::uint64_t *>(pk.d_results.get());
         /* qap_wit.coefficients_for_H, resident (prover.hpp:79-83) */
-        std::uint64_t g[4];
         const zkhip_domain dd = pk.evaluation_domain.c_desc();
-        adapter::scalar_to_limbs(pk.domain.coset_generator, g);
-        check(zkhip_groth16_witness_h_domain_dev(ctx.get(), pk.constraint_system.get(), cpa, &dd, g, pk.d_h.get(), pk.d_scratch.get()),
-              "zkhip_groth16_witness_h_domain_dev", ctx.get());
+        ZKHIP_CALL(ctx, zkhip_groth16_witness_h_domain_dev, pk.constraint_system.get(), cpa, &dd, limbs_of<adapter>(pk.domain.coset_generator).data(), pk.d_h.get(),
+                   pk.d_scratch.get());
         /* evaluation_Bt: kc_multiexp_with_mixed_addition over the sparse (G2, G1) query (prover.hpp:116-123); a sharded key
            holds a slice of the index list */
-        check(zkhip_fr_gather_dev(ctx.get(), cpa, num_variables + 1, pk.d_B_indices.get(), pk.B_count, pk.d_bs.get()), "zkhip_fr_gather_dev", ctx.get());
+        ZKHIP_CALL(ctx, zkhip_fr_gather_dev, cpa, num_variables + 1, pk.d_B_indices.get(), pk.B_count, pk.d_bs.get());
         if (pk.experiment_skip_g2) {
             /* EXPERIMENT ONLY (wrong proof): what a proof would cost if the G2 multiexp were free -- the ceiling of anything that could be
                gained on the second stream */
@@ -911,7 +903,7 @@ private:
                              pk.B_rows_aligned ? static_cast<const void *>(cpa) : pk.d_bs.get(),
                              static_cast<const char *>(pk.d_h.get()) + 32 * sh.H_lo};
         void *qr[4] = {d_res, d_res + 3 * jl1, d_res + jl1, d_res + 2 * jl1};
-        check(zkhip_msm_batch_dev(ctx.get(), 4, qb, qo, qn, qs, qr), "zkhip_msm_batch_dev", ctx.get());
+        ZKHIP_CALL(ctx, zkhip_msm_batch_dev, 4, qb, qo, qn, qs, qr);
     }
     /// the five partial sums of this rank, after the stream has drained
     static std::vector<std::uint64_t> collect(const proving_key_type &pk) {
@@ -922,8 +914,8 @@ private:
         }
         pk.ctx.d2h(res.data(), pk.d_results.get(), res.size() * 8);
         /* kernels flag what they cannot signal otherwise (a B-query index beyond the assignment, a plan overflow) */
-        check(zkhip_device_status(pk.ctx.get(), nullptr), "zkhip_device_status", pk.ctx.get());
-        if (pk.side) check(zkhip_device_status(pk.side->get(), nullptr), "zkhip_device_status", pk.side->get());
+        ZKHIP_CALL(pk.ctx, zkhip_device_status, nullptr);
+        if (pk.side) ZKHIP_CALL(*pk.side, zkhip_device_status, nullptr);
         return res;
     }
     /// fold the ranks' partial sums and build the proof (prover.hpp:141-157)

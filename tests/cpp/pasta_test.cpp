@@ -22,6 +22,7 @@
 #include <nil/crypto3/zk/hip/transcript.hpp>
 
 #include "eval_polys_case.hpp"
+#include "fr_vector_case.hpp"
 
 using namespace nil::crypto3::zk::hip;
 
@@ -236,6 +237,13 @@ int eval_polys_case_t(const std::uint64_t *evals, const std::uint64_t *points, s
     return eval_polys_case::run(scheme, tr, evals, points, out_z);
 }
 
+/// one case of fr_vector_case.hpp on a context of its own
+template <typename Curve>
+int fr_vector_t(int what, const std::uint64_t *a, const std::uint64_t *b, std::size_t n, const std::uint64_t *s, std::size_t m, int flag, std::uint64_t *out) {
+    context ctx(0);
+    return fr_vector_case::run<Curve>(ctx, what, a, b, n, s, m, flag, out);
+}
+
 }    // namespace
 
 #define PASTA_DISPATCH(curve, call)                     \
@@ -286,6 +294,13 @@ int pasta_lpc_run(int curve, int builder, const std::uint64_t *evals, std::size_
 /// the shared eval_polys case (eval_polys_case.hpp) through the LPC scheme: proof.z, 9 elements
 int pasta_eval_polys_case(int curve, const std::uint64_t *evals, const std::uint64_t *points, std::uint64_t *out_z) {
 #define CALL(C) eval_polys_case_t<C>(evals, points, out_z)
+    PASTA_DISPATCH(curve, CALL)
+#undef CALL
+}
+
+/// fr_vector (hip/fr_vector.hpp) member by member: the cases and their buffers are fr_vector_case.hpp's
+int pasta_fr_vector(int curve, int what, const std::uint64_t *a, const std::uint64_t *b, std::size_t n, const std::uint64_t *s, std::size_t m, int flag, std::uint64_t *out) {
+#define CALL(C) fr_vector_t<C>(what, a, b, n, s, m, flag, out)
     PASTA_DISPATCH(curve, CALL)
 #undef CALL
 }

@@ -7,7 +7,9 @@
 // boundary, oversized and zero counts, non-increasing / out-of-range B indices, random byte flips.  The parser must throw or
 // succeed; the sanitizers decide the rest.  Also the context's table cache (csrc/table_cache.hpp) over an entry type that counts its
 // constructions and destructions: eviction order, the drain before each eviction, a build abandoned before publish().  And the option table
-// (csrc/options.hpp) over a plain struct: unique names, set / get round trips, the admission rules, the ZKHIP_OPTIONS parser.
+// (csrc/options.hpp) over a plain struct: unique names, set / get round trips, the admission rules, the ZKHIP_OPTIONS parser.  And every member
+// of fr_vector (fr_vector.hpp) once, over buffers exactly as large as its contract says: the stub copies / touches the bytes each entry point
+// reads and writes, so an element count passed where bytes belong (or the reverse) is an ASan report.
 #include <chrono>
 #include <memory>
 #include <cstdio>
@@ -554,6 +556,46 @@ void bulk_transfers() {
     EXPECT(b.size() == pts.size());
 }
 
+/// every member of fr_vector once (section "fr_vector_layer"); each buffer holds exactly the elements the member's contract names
+template <typename Curve>
+void fr_vector_layer() {
+    typedef curve_adapter<Curve> A;
+    typedef typename A::scalar_value_type Fr;
+    typedef fr_vector<Curve> fv;
+    context ctx(0);
+    auto elements = [&ctx](std::size_t count) { return ctx.alloc(count * 32); };
+    auto a = elements(5), b = elements(5), out = elements(5);
+    fv::pointwise(ctx, fr_op::add, a.get(), b.get(), out.get(), 5);
+    fv::pointwise(ctx, fr_op::sub, a.get(), b.get(), out.get(), 5);
+    fv::pointwise(ctx, fr_op::mul, a.get(), b.get(), a.get(), 5);    // in place
+    fv::affine(ctx, a.get(), b.get(), Fr(2), Fr(3), Fr(4), out.get(), 5);
+    fv::affine(ctx, a.get(), nullptr, Fr(2), Fr(3), Fr(4), out.get(), 5);
+    fv::scale(ctx, a.get(), Fr(7), a.get(), 5);
+    fv::mul_div(ctx, a.get(), b.get(), a.get(), out.get(), 5);
+    fv::product(ctx, {a.get(), b.get(), out.get()}, out.get(), 5);
+    auto block = ctx.alloc(160);    // 5 elements, in bytes
+    fv::copy(ctx, block.get(), a.get(), 5);
+    auto eight = elements(8);
+    fv::zero_padded_copy(ctx, nullptr, 0, eight.get(), 8);
+    fv::zero_padded_copy(ctx, a.get(), 5, eight.get(), 8);
+    fv::add_scaled(ctx, a.get(), 5, Fr(3), eight.get(), 8, true);
+    fv::add_scaled(ctx, a.get(), 0, Fr(3), eight.get(), 8, false);
+    fv::lincomb(ctx, {a.get(), b.get()}, {5, 5}, std::vector<Fr> {Fr(1), Fr(2)}, 1, eight.get(), 8, false);
+    fv::lincomb(ctx, {a.get(), b.get()}, {5, 3}, std::vector<std::uint64_t>(2 * 3 * 4, 1), 3, eight.get(), 8, true);    // three taps: 5 + 3 - 1 <= 8
+    auto large = elements(64), small = elements(8), half = elements(4);
+    fv::subsample(ctx, large.get(), 6, small.get(), 3);
+    fv::resize(ctx, small.get(), 3, 1, Fr(2), large.get(), 6, Fr(3));
+    fv::resize(ctx, small.get(), 2, 2, Fr(2), large.get(), 5, Fr(3));    // a batch of two: 2 x 2^2 -> 2 x 2^5
+    fv::ntt(ctx, large.get(), 5, 2, Fr(3), true);
+    fv::ntt(ctx, small.get(), 3, 1, Fr(3), false);
+    fv::shift(ctx, small.get(), 3, -1, eight.get());
+    fv::fold(ctx, small.get(), 3, Fr(5), Fr(6), half.get());
+    EXPECT(fv::div_linear(ctx, a.get(), 5, Fr(9), out.get()) == Fr::zero());    // the stub's remainder
+    EXPECT(fv::div_linear(ctx, a.get(), 5, Fr(9), a.get()) == Fr::zero());      // in place
+    const std::array<std::uint64_t, 4> five = limbs_of<A>(Fr(5));
+    EXPECT(five[0] == 5 && five[1] == 0 && five[2] == 0 && five[3] == 0);
+}
+
 /// the helpers the group paths share (backend.hpp): the fan-out over a group's members, the even cut of a range, ceil_log2
 void group_helpers() {
     EXPECT(detail::ceil_log2(0) == 0 && detail::ceil_log2(1) == 0 && detail::ceil_log2(2) == 1 && detail::ceil_log2(3) == 2);
@@ -844,6 +886,10 @@ int main(int argc, char **argv) {
         bulk_transfers<converting_curve>();
         bulk_transfers<bls12_381>();
         group_helpers();
+    }
+    if (what == "all" || what == "fr_vector_layer") {
+        fr_vector_layer<bls12_381>();
+        fr_vector_layer<converting_curve>();
     }
     if (what == "all" || what == "fuzz") parser_fuzz();
     if (what == "all" || what == "table_cache") table_cache_protocol();

@@ -28,6 +28,7 @@
 #include <nil/crypto3/zk/hip/r1cs_gg_ppzksnark_generator.hpp>
 
 #include "eval_polys_case.hpp"
+#include "fr_vector_case.hpp"
 
 using namespace nil::crypto3::zk::hip;
 
@@ -2089,6 +2090,13 @@ int eval_polys_case_t(const uint64_t *srs, size_t n_srs, const uint64_t *evals, 
     return 0;
 }
 
+/// one case of fr_vector_case.hpp on a context of its own
+template <typename Curve>
+int fr_vector_t(int what, const uint64_t *a, const uint64_t *b, size_t n, const uint64_t *s, size_t m, int flag, uint64_t *out) {
+    context ctx(0);
+    return fr_vector_case::run<Curve>(ctx, what, a, b, n, s, m, flag, out);
+}
+
 extern "C" {
 
 int shim_host_small_poly(int curve, const uint64_t *xs, const uint64_t *ys, size_t k, const uint64_t *at, uint64_t *u_at, uint64_t *u_coeffs,
@@ -2300,6 +2308,11 @@ int shim_lpc_scheme(int curve, const uint64_t *evals, size_t npolys, const uint6
 int shim_eval_polys_case(int curve, const uint64_t *srs, size_t n_srs, const uint64_t *evals, const uint64_t *points, const uint64_t *challenges, uint64_t *out_kzg,
                          uint64_t *out_lpc) {
     CURVE_CALL("shim_eval_polys_case", eval_polys_case_t, srs, n_srs, evals, points, challenges, out_kzg, out_lpc)
+}
+
+/// fr_vector (hip/fr_vector.hpp) member by member: the cases and their buffers are fr_vector_case.hpp's
+int shim_fr_vector(int curve, int what, const uint64_t *a, const uint64_t *b, size_t n, const uint64_t *s, size_t m, int flag, uint64_t *out) {
+    CURVE_CALL("shim_fr_vector", fr_vector_t, what, a, b, n, s, m, flag, out)
 }
 
 int shim_kzg_placeholder_contract(int curve, const uint64_t *srs, size_t n_srs, const uint64_t *evals, size_t npolys, size_t log_n, const uint64_t *roots,

@@ -113,3 +113,10 @@ def test_eval_polys_shared_case_lpc_pallas(harness):  # noqa: F811
     out = np.zeros((len(want), 4), dtype=np.uint64)
     assert harness.pasta_eval_polys_case(pu.PALLAS_ID, P(evals), P(points), P(out)) == 0
     assert fr_ints(out) == want
+
+
+@pytest.mark.parametrize("n", [1, 5, 257])
+def test_fr_vector_layer(harness, n):  # noqa: F811
+    """the fr_vector cases tests/test_gpu_shim.py runs over BLS12-381 and BN254 (tests/cpp/fr_vector_case.hpp), over Pallas's scalar field"""
+    from util import run_fr_vector_cases
+    run_fr_vector_cases(harness.pasta_fr_vector, pu.PALLAS_ID, pu.CURVES[pu.PALLAS_ID].r, n, 9940 + n)

@@ -1621,3 +1621,16 @@ def test_eval_polys_shared_by_kzg_and_lpc(shim, curve):
     assert shim.shim_eval_polys_case(curve, P(srs), ctypes.c_size_t(64), P(evals), P(points), P(challenges), P(out_kzg), P(out_lpc)) == 0
     assert fr_ints(out_kzg) == want
     assert fr_ints(out_lpc) == want
+
+
+@pytest.mark.parametrize("n", [1, 5, 257])
+@pytest.mark.parametrize("curve", [0, 1])
+def test_fr_vector_layer(shim, curve, n):
+    """fr_vector (hip/fr_vector.hpp), the typed layer under the schemes, member by member against Python integers (util.fr_vector_cases;
+    tests/cpp/fr_vector_case.hpp): every fr_op including a - b with a < b, affine with and without y, scale by 0, 1 and r - 1, add_scaled
+    with and without accumulate and copy over n = 1, 5 and 257 elements (one past a 256-lane workgroup), first entries 0, 1, r - 1;
+    zero_padded_copy 0 -> 8, 5 -> 8, 8 -> 8 over a non-zero destination; subsample 2^6 -> 2^3 and 2^3 -> 2^3; div_linear of a degree-4
+    polynomial at a root and at a non-root with the remainder returned.  The dfs arithmetic above it would not notice add and sub
+    exchanged (c += b; c -= b returns to the start either way); this does."""
+    from util import run_fr_vector_cases
+    run_fr_vector_cases(shim.shim_fr_vector, curve, CURVES[curve].r, n, 9900 + 10 * curve + n)

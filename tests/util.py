@@ -145,3 +145,57 @@ def eval_polys_case(C, seed):
         coeffs = po.intt(e, C.root_of_unity(lg), r)
         want += [po.poly_eval(coeffs, x, r) for x in s]
     return fr_arr([v for e in polys for v in e]), fr_arr([a, b, c]), want
+
+
+def fr_vector_cases(r, n, seed):
+    """tests/cpp/fr_vector_case.hpp: every member of fr_vector over vectors of n elements whose first entries are 0, 1, r - 1 (b: the same
+    three rotated to 1, r - 1, 0, so that a - b runs below zero at index 0 and 1) and random ones behind, plus the cases whose sizes are
+    the contract's own.  Yields (label, what, a, b, n, scalars, m, flag, want): the entry's arguments as Python integers and the expected
+    output, computed here from Python integers alone."""
+    rng = po.SplitMix64(seed)
+    rand = lambda k: [rng.next_mod(r) for _ in range(k)]                                # noqa: E731
+    nonzero = lambda k: [1 + rng.next_mod(r - 1) for _ in range(k)]                       # noqa: E731
+    a = ([0, 1, r - 1] + rand(n))[:n]
+    b = ([1, r - 1, 0] + rand(n))[:n]
+    assert a[0] < b[0]
+    yield "add", 0, a, b, n, [], 0, 0, [(x + y) % r for x, y in zip(a, b)]
+    yield "sub", 1, a, b, n, [], 0, 0, [(x - y) % r for x, y in zip(a, b)]
+    yield "mul", 2, a, b, n, [], 0, 0, [x * y % r for x, y in zip(a, b)]
+    s = rand(3)
+    yield "affine with y", 3, a, b, n, s, 0, 1, [(s[0] * x + s[1] * y + s[2]) % r for x, y in zip(a, b)]
+    yield "affine without y", 3, a, b, n, s, 0, 0, [(s[0] * x + s[2]) % r for x in a]
+    for c in (0, 1, r - 1):
+        yield "scale by %d" % c, 4, a, [], n, [c], 0, 0, [c * x % r for x in a]
+    for c, accumulate in ((s[0], 0), (s[1], 1), (r - 1, 1)):
+        acc = nonzero(n + 3)
+        yield "add_scaled", 6, a, acc, n, [c], n + 3, accumulate, [((acc[j] if accumulate else 0) + (c * a[j] if j < n else 0)) % r for j in range(n + 3)]
+    fill = nonzero(n + 1)
+    yield "copy", 9, a, fill, n, [], 0, 0, a + fill[n:]
+    for length in (0, 5, 8):
+        src, dst = nonzero(length), nonzero(8)
+        yield "zero_padded_copy %d -> 8" % length, 5, src, dst, length, [], 8, 0, src + [0] * (8 - length)
+    for log_n in (6, 3):
+        v = rand(1 << log_n)
+        yield "subsample 2^%d -> 2^3" % log_n, 7, v, [], log_n, [], 3, 0, v[::1 << (log_n - 3)]
+    z, q = rng.next_mod(r), rand(4)
+    at_root = [(-z * q[0]) % r] + [(q[k - 1] - z * q[k]) % r for k in range(1, 4)] + [q[3]]    # (X - z) q(X), degree 4
+    for f in (at_root, rand(5)):
+        quotient = [0] * 4
+        for k in range(3, -1, -1):
+            quotient[k] = (f[k + 1] + (z * quotient[k + 1] if k < 3 else 0)) % r
+        remainder = (f[0] + z * quotient[0]) % r
+        assert (f is at_root) == (remainder == 0) and (f is not at_root or quotient == q)
+        yield "div_linear", 8, f, [], 5, [z], 0, 0, [remainder] + quotient + [remainder]
+
+
+def run_fr_vector_cases(entry, curve, r, n, seed):
+    """every case of fr_vector_cases through `entry` (shim_fr_vector / pasta_fr_vector of the C++ harnesses)"""
+    import ctypes
+    arr = lambda v: fr_arr(v) if v else np.zeros((1, 4), dtype=np.uint64)                  # noqa: E731
+    for label, what, a, b, count, scalars, m, flag, want in fr_vector_cases(r, n, seed):
+        out = np.full((len(want), 4), 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+        ins = [np.ascontiguousarray(arr(v)) for v in (a, b, scalars)]
+        rc = entry(curve, what, *(x.ctypes.data_as(ctypes.c_void_p) for x in ins[:2]), ctypes.c_size_t(count), ins[2].ctypes.data_as(ctypes.c_void_p),
+                   ctypes.c_size_t(m), flag, out.ctypes.data_as(ctypes.c_void_p))
+        assert rc == 0, (label, rc)
+        assert fr_ints(out) == want, label
