@@ -18,6 +18,7 @@ from .zkhip import (  # noqa: F401
     HASH_SHA2_256,
     MerkleTree,
     PALLAS,
+    PairingTerm,
     R1CS,
     VESTA,
     ZkhipError,

@@ -10,6 +10,7 @@
 #include "arith_ops.h"
 #include "glv.hpp"
 #include "msm_recode.hpp"
+#include "pairing.hpp"
 #include "pow.hpp"
 #include "sha256.hpp"
 
@@ -202,6 +203,63 @@ int zkt_scale_record(int curve, int glv, const uint32_t *scalar, uint32_t *k_out
 int zkt_sha256_bytes(const uint8_t *msg, size_t len, uint8_t *digest) {
     if (!digest || (!msg && len)) return -1;
     pow::hash_bytes(msg, len, digest);
+    return 0;
+}
+
+// Fq12 tower (fq12.hpp) on canonical limbs (72 u64 = 144 u32 per element).  op: 0 a * b, 1 a^2, 2 1 / a, 3 a^p (Frobenius), 4 conjugate,
+// 5 a * (l0 + l1 v + l4 v w) with the three Fq2 values l0, l1, l4 in b (72 u32), 6 final exponentiation
+int zkt_fq12_op(int op, const uint32_t *a, const uint32_t *b, uint32_t *out) {
+    if (!a || !out || ((op == 0 || op == 5) && !b)) return -1;
+    const bls_fq12 x = fq12_from_canonical<BlsFq>(a);
+    bls_fq12 r;
+    switch (op) {
+    case 0: r = x * fq12_from_canonical<BlsFq>(b); break;
+    case 1: r = fp_sqr(x); break;
+    case 2: r = fp_inv(x); break;
+    case 3: r = fq12_frobenius(x); break;
+    case 4: r = fq12_conj(x); break;
+    case 5: {
+        bls_fq2 l[3];
+        for (int k = 0; k < 3; ++k) {
+            bls_fq2 c;
+            for (int i = 0; i < 12; ++i) c.c0.v[i] = b[k * 24 + i], c.c1.v[i] = b[k * 24 + 12 + i];
+            l[k] = fp_to_mont(c);
+        }
+        r = fq12_mul_by_014(x, l[0], l[1], l[2]);
+        break;
+    }
+    case 6: r = pairing::final_exponentiation(x); break;
+    default: return -1;
+    }
+    fq12_to_canonical(out, r);
+    return 0;
+}
+
+// zkhip_pairing_products on the CPU: the same pairing.hpp bodies over canonical affine points (G1: 24 u32, G2: 48 u32 per point)
+// with infinity flags; term t covers pairs [start[t], start[t] + n[t]) of both arrays and is multiplied into output out[t].
+// Unlike the entry, a term indexes BOTH arrays from the same start, so this twin says nothing about the entry's separate offsets (the structured
+// expectation of tests/test_gpu_pairing.py covers those); like the entry, it checks neither that a point is on its curve nor in the order-r subgroup.
+int zkt_pairing_products(const uint32_t *g1, const uint8_t *g1_inf, const uint32_t *g2, const uint8_t *g2_inf, const uint64_t *start, const uint64_t *n,
+                         const uint32_t *out, size_t n_terms, size_t n_out, uint32_t *out_gt) {
+    if (!g1 || !g1_inf || !g2 || !g2_inf || !start || !n || !out || !out_gt || n_out == 0) return -1;
+    std::vector<bls_fq12> acc(n_out, bls_fq12::one());
+    for (size_t t = 0; t < n_terms; ++t) {
+        if (out[t] >= n_out) return -2;
+        for (uint64_t i = start[t]; i < start[t] + n[t]; ++i) {
+            if (g1_inf[i] || g2_inf[i]) continue;
+            bls_fq c[6];
+            for (int k = 0; k < 6; ++k) {
+                const uint32_t *src = k < 2 ? g1 + i * 24 + k * 12 : g2 + i * 48 + (k - 2) * 12;
+                bls_fq v;
+                for (int j = 0; j < 12; ++j) v.v[j] = src[j];
+                c[k] = fp_to_mont(v);
+            }
+            pairing::RegStore fs;
+            pairing::miller_loop(fs, c[0], c[1], bls_fq2{c[2], c[3]}, bls_fq2{c[4], c[5]});
+            acc[out[t]] = acc[out[t]] * fs.f;
+        }
+    }
+    for (size_t k = 0; k < n_out; ++k) fq12_to_canonical(out_gt + k * 144, pairing::final_exponentiation(acc[k]));
     return 0;
 }
 

@@ -273,6 +273,27 @@ struct group_value {
     }
 };
 
+/// An element of the pairing's target group as zkhip_pairing_products returns it: 72 canonical u64 limbs, the 12 Fq values of the
+/// reference's fq12(fq6(fq2, fq2, fq2), fq6(fq2, fq2, fq2)) in constructor order, 6 limbs each (BLS12-381, the one curve the entry serves).
+/// A value carrier: the shim compares and hands on what the device computed, it does no Fq12 arithmetic.
+template <int Curve>
+struct gt_value {
+    static constexpr std::size_t limb_count = 72;
+    std::array<std::uint64_t, limb_count> limbs {};
+    static gt_value one() {
+        gt_value r;
+        r.limbs[0] = 1;
+        return r;
+    }
+    static gt_value from_limbs(const std::uint64_t *in) {
+        gt_value r;
+        std::memcpy(r.limbs.data(), in, sizeof(r.limbs));
+        return r;
+    }
+    bool operator==(const gt_value &o) const { return limbs == o.limbs; }
+    bool operator!=(const gt_value &o) const { return !(*this == o); }
+};
+
 /// The concept the shim is written against.  `native_curve<C>` is the self-contained model.
 template <int Curve>
 struct native_curve {
@@ -280,6 +301,7 @@ struct native_curve {
     typedef fr_value<Curve> scalar_value_type;
     typedef group_value<Curve, ZKHIP_G1> g1_value_type;
     typedef group_value<Curve, ZKHIP_G2> g2_value_type;    // naming it is harmless; USING it on a curve without G2 is a compile-time error
+    typedef gt_value<Curve> gt_value_type;
     static constexpr bool has_g2 = detail::has_g2<Curve>::value;
 };
 
@@ -331,6 +353,10 @@ struct curve_adapter<native_curve<Curve>> {
     static bool point_to_affine_limbs(const G &p, std::uint64_t *out) { return p.to_affine(out); }
     static g1_value_type g1_from_jacobian(const std::uint64_t *xyz) { return g1_value_type::from_jacobian(xyz); }
     static g2_value_type g2_from_jacobian(const std::uint64_t *xyz) { return g2_value_type::from_jacobian(xyz); }
+    /// a target-group value from the 72 canonical limbs of zkhip_pairing_products (kzg_ipp2.hpp); an adapter over crypto3-algebra
+    /// hands the 12 Fq values to curve_type::gt_type::value_type's constructor in the order they come
+    typedef typename curve_type::gt_value_type gt_value_type;
+    static gt_value_type gt_from_limbs(const std::uint64_t *in) { return gt_value_type::from_limbs(in); }
 };
 
 namespace detail {

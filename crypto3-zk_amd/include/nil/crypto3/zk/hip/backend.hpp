@@ -491,6 +491,8 @@ public:
     device_bases &operator=(const device_bases &) = delete;
     const zkhip_bases *get() const { return b_; }
     std::size_t size() const { return size_; }
+    /// the context the points live on (null for a default-constructed object)
+    const context *owner_context() const { return ctx_; }
 
 private:
     const context *ctx_ = nullptr;

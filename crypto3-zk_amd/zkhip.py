@@ -22,7 +22,7 @@ EXPORTS = [
     "zkhip_domain_choice", "zkhip_domain_fft_dev", "zkhip_domain_lagrange_dev",
     "zkhip_r1cs_upload", "zkhip_r1cs_free", "zkhip_r1cs_set_domain", "zkhip_r1cs_domain_size", "zkhip_r1cs_domain_kind", "zkhip_groth16_scratch_bytes", "zkhip_groth16_witness_h_dev", "zkhip_groth16_witness_h_domain_dev", "zkhip_fr_gather_dev", "zkhip_poly_resize_dev", "zkhip_fri_fold_dev", "zkhip_fri_leaves_dev", "zkhip_ec_ntt_dev",
     "zkhip_fr_vec_op_dev", "zkhip_fr_vec_affine_dev", "zkhip_fr_vec_mul_div_dev", "zkhip_fr_vec_prod_dev", "zkhip_poly_shift_dev", "zkhip_poly_eval_dev", "zkhip_poly_div_linear_dev", "zkhip_poly_div_vanishing_dev", "zkhip_poly_lincomb_dev", "zkhip_perm_grand_product_dev", "zkhip_lookup_grand_product_dev", "zkhip_lookup_sort_dev", "zkhip_perm_factor_products_dev", "zkhip_gate_eval_dev",
-    "zkhip_bases_fold", "zkhip_bases_scale_dev", "zkhip_bases_scale_geometric", "zkhip_bases_lagrange", "zkhip_fr_inner_product_dev", "zkhip_fr_powers_lincomb_dev", "zkhip_fr_challenge_products_dev",
+    "zkhip_bases_fold", "zkhip_bases_scale_dev", "zkhip_bases_scale_geometric", "zkhip_bases_lagrange", "zkhip_fr_inner_product_dev", "zkhip_fr_powers_lincomb_dev", "zkhip_fr_challenge_products_dev", "zkhip_pairing_products",
     "zkhip_merkle_build_dev", "zkhip_merkle_build_fri_dev", "zkhip_merkle_leaves", "zkhip_merkle_depth", "zkhip_merkle_root", "zkhip_merkle_digests", "zkhip_merkle_paths",
     "zkhip_merkle_free", "zkhip_fri_query_dev", "zkhip_merkle_paths_multi", "zkhip_pow_grind", "zkhip_sha256_host",
     "zkhip_group_init", "zkhip_group_destroy", "zkhip_group_size", "zkhip_group_ctx", "zkhip_group_last_error", "zkhip_group_set_transport", "zkhip_group_transport",
@@ -64,6 +64,12 @@ class GateProgram(ctypes.Structure):
     _fields_ = [("n_gates", ctypes.c_uint32), ("n_terms", ctypes.c_uint32), ("n_factors", ctypes.c_uint32), ("n_slots", ctypes.c_uint32),
                 ("gate_terms", ctypes.c_void_p), ("gate_selector", ctypes.c_void_p), ("gate_selector_rot", ctypes.c_void_p), ("term_factors", ctypes.c_void_p),
                 ("factor_slot", ctypes.c_void_p), ("factor_rot", ctypes.c_void_p), ("term_coeff", ctypes.c_void_p)]
+
+
+class PairingTerm(ctypes.Structure):
+    """zkhip_pairing_term"""
+    _fields_ = [("g1", ctypes.c_void_p), ("g1_offset", ctypes.c_size_t), ("g2", ctypes.c_void_p), ("g2_offset", ctypes.c_size_t), ("n", ctypes.c_size_t),
+                ("out", ctypes.c_uint32)]
 
 
 class FriQuerySet(ctypes.Structure):
@@ -296,6 +302,17 @@ class Context:
         self._check(self.lib.zkhip_bases_fold(self.h, bases.h, ctypes.c_size_t(offset_lo), ctypes.c_size_t(offset_hi), ctypes.c_size_t(half),
                                               _p(_u64(c).reshape(4)), ctypes.byref(h)), "zkhip_bases_fold")
         return Bases(self, h, bases.curve, bases.group, half)
+
+    def pairing_products(self, terms, n_out: int, curve: int = BLS12_381) -> np.ndarray:
+        """out[k] = final_exponentiation(prod over the terms naming k of prod_i miller(g1[g1_offset + i], g2[g2_offset + i])) as n_out x 72 uint64
+        (canonical Fq12); terms: (g1 Bases, g1_offset, g2 Bases, g2_offset, n, out) each (zkhip_pairing_products)"""
+        arr = (PairingTerm * max(1, len(terms)))()
+        for t, (g1, o1, g2, o2, n, out) in zip(arr, terms):
+            t.g1, t.g1_offset, t.g2, t.g2_offset, t.n, t.out = getattr(g1.h, "value", g1.h), o1, getattr(g2.h, "value", g2.h), o2, n, out
+        res = np.zeros((n_out, 72), dtype=np.uint64)
+        self._check(self.lib.zkhip_pairing_products(self.h, ctypes.c_int(curve), arr, ctypes.c_size_t(len(terms)), ctypes.c_size_t(n_out), _p(res)),
+                    "zkhip_pairing_products")
+        return res
 
     def bases_scale_dev(self, bases: "Bases", offset: int, n: int, d_scalars: int, flags: int = 0) -> "Bases":
         """out[i] = s_i * bases[offset + i], i < n, s_i the i-th of n scalars resident at d_scalars (taken mod r): a new bases object, without

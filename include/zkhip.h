@@ -524,6 +524,40 @@ int zkhip_fr_powers_lincomb_dev(zkhip_ctx *ctx, int curve, const uint64_t *point
  * verify_eval.  chals: host, canonical Fr (nullable when rounds = 0: d_out[0] = 1); rounds <= 31. */
 int zkhip_fr_challenge_products_dev(zkhip_ctx *ctx, int curve, const uint64_t *chals, size_t rounds, void *d_out);
 
+/* ---- pairing products: the commitments and GIPA rounds of Groth16 aggregation (SnarkPack / TIPP-MIPP) --------------------------
+ * kzg_ipp2::pair and ::single (zk/commitments/polynomial/kzg_ipp2.hpp:216-283) and the z / t / u values of every GIPA round
+ * (systems/ppzksnark/r1cs_gg_ppzksnark/ipp2/prover.hpp:360-381, 584-593) are inner pairing products over vectors the device already
+ * holds as bases objects:
+ *     out_gt[k] = final_exponentiation( prod over the terms t with t.out == k of prod_{i < t.n} miller(g1[t.g1_offset + i], g2[t.g2_offset + i]) ),
+ * k < n_out.  `pair` is one call with four terms and two outputs, `single` one with two terms and two outputs, ip_ab one term.
+ * Conventions:
+ *   - ZKHIP_BLS12_381 ONLY.  ZKHIP_BN254 and the Pasta ids are ZKHIP_ERR_INVALID: BN254's optimal ate pairing needs a different Miller
+ *     loop (the parameter 6x + 2 and two Frobenius-twisted additions at its end), and the reference holds no vector to pin one to; the
+ *     Pasta curves have no pairing.
+ *   - The pairing is the ate pairing over |x| = 0xd201000000010000 (conjugated: x is negative) and final_exponentiation raises to
+ *     3 (p^12 - 1) / r: the x-chain formulas compute the hard part to that fixed multiple, and it is the power the reference's vectors
+ *     (r1cs_gg_ppzksnark_aggregation_conformity.cpp, bls381_commitment_test) hold.  Bilinearity and non-degeneracy are unaffected.
+ *   - out_gt: HOST, n_out x 72 u64: an Fq12 value as 12 canonical Fq values of 6 limbs in the order of the reference's constructor
+ *     fq12(fq6(fq2, fq2, fq2), fq6(fq2, fq2, fq2)), c0 before c1 at every level.
+ *   - A pair whose G1 or G2 point is the point at infinity contributes one; an output that no term names, or whose pairs are all such,
+ *     is one.  Points are taken as members of the order-r subgroups, as every constructor of bases delivers them.
+ *   - Only the points of the bases objects are read; their window tables play no part.  A term may start anywhere inside its objects,
+ *     several terms may feed one output, and terms may share objects.
+ *   - Terms are meant to be few and long (a commitment has two or four, a GIPA round a handful): every workgroup finds its term by a
+ *     linear walk of the term table, so a call with many small terms pays O(n_terms) per 64 pairs.
+ *   - The Miller loops and the products run on the device in a fixed order without atomics; the final exponentiation of the n_out
+ *     results runs on the host (~10^4 dependent Fq products each).  The call returns with the stream drained.
+ * Errors, before anything is launched: a null ctx / out_gt / terms (with n_terms > 0) / g1 / g2, an unknown or unsupported curve, bases
+ * of the wrong group or another curve -> ZKHIP_ERR_INVALID; g1_offset + n or g2_offset + n beyond the object's size, out >= n_out,
+ * n_out = 0, or 2^37 pairs or more in all -> ZKHIP_ERR_RANGE. */
+typedef struct zkhip_pairing_term {
+    const zkhip_bases *g1; size_t g1_offset;   /* ZKHIP_G1 bases */
+    const zkhip_bases *g2; size_t g2_offset;   /* ZKHIP_G2 bases */
+    size_t n;                                  /* pairs of this term */
+    uint32_t out;                              /* which output the term is multiplied into */
+} zkhip_pairing_term;
+int zkhip_pairing_products(zkhip_ctx *ctx, int curve, const zkhip_pairing_term *terms, size_t n_terms, size_t n_out, uint64_t *out_gt);
+
 /* ---- the gate argument's sum over a flat program -------------------------------------------------------------------------
  * placeholder's gates argument (ph/gates_argument.hpp:93-121, 203-216) computes, on the extended domain of 2^log_size points,
  *     F = mask * sum_gates selector_g * sum_constraints theta^k * constraint(columns, rotated).
