@@ -235,7 +235,7 @@ struct zkhip_ctx {
     // options (each is a row of options.hpp)
     int opt_msm_window_bits = 0;
     int opt_msm_sets = 0;          // bucket sets S with window tables (entry (i, w) -> set w mod S); 0: from the lane target
-    int opt_msm_sort_tile_log = 14;  // 14: 2^14-entry sort tiles (the MSM owns the GPU); 12: 2^12 (kernels of another context run alongside)
+    int opt_msm_sort_tile_log = 14;  // 14: 2^14-entry sort tiles (the MSM owns the GPU); 13: 2^13; 12: 2^12 (kernels of another context run alongside)
     int opt_ec_ntt_table_lanes = 0;  // EC-NTT: lanes per multiplication launch = window tables held at once (0: as many as fit 1 GiB)
     int opt_msm_share_sort = 1;    // batches: consecutive members over the same scalars and table geometry share one sort (msm_same_entries)
     int opt_msm_tail_quads = 1;    // the tail's latency-bound group law.  0: lane pairs everywhere; 1: lane quads in the tail of small bucket sets (fu_quad.hpp) and one point per wave in level 2 of a lone MSM's two-level tail (fu_wide.hpp); any other value: the quads alone

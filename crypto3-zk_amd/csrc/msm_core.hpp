@@ -29,10 +29,10 @@
 //   segsum / winsum                  per-workgroup weighted sums of the bucket reduction / per-set sums
 //
 // Kernels (all integer VALU; no MFMA -- this is modular arithmetic, not a dense contraction):
-//   (msm_entries.hip: msm_digits_only, msm_sort_*, msm_scan_*, msm_size_*, msm_plan_large -- dig, offs, idx, order and the large-bucket plan)
+//   (msm_entries.hip: msm_digits_only, msm_sort_*, msm_scan_*, msm_size_* -- dig, offs, idx, order and the large-bucket plan)
 //   msm_bucket_acc_lds  one lane per bucket (G1) or one even / odd lane pair per bucket (G2, fu2_pair.hpp): gather affine
 //                     points, XYZZ mixed additions, accumulator coordinates in LDS                          <- dominant
-//   msm_bucket_large / msm_large_combine   buckets far above the mean (msm_plan_large), one workgroup per 4096-entry task
+//   msm_bucket_large / msm_large_combine   buckets far above the mean (the plan: msm_size_scatter), one workgroup per 4096-entry task
 //   msm_bucket_merge  S > 1: fold the S equal-weight sets bucket by bucket (radix-4 tree)
 //   msm_fold          (round 5, table-backed sets of >= 2^16 buckets) row and column sums of the bucket index b = h C + l: the reduction
 //                     sum_b (b + 1) bucket[b] becomes sum_l (l + 1) COL[l] + C sum_h h ROW[h], i.e. the three kernels below over 2 sets of

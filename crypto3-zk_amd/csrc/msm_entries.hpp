@@ -27,7 +27,7 @@ struct SortGeom {
     uint32_t S;           // sets: set(w) = w % S
     uint32_t lowb;        // low key bits (pass 2)
     uint32_t nsuper;      // ceil(S * B / 2^lowb)
-    uint32_t tile;        // entries per tile
+    uint32_t tile;        // entries per tile: names the sort's tile shape (option "msm_sort_tile_log": 12, 13 or 14)
     uint32_t ntile;       // tiles per window
     uint32_t slot0;       // table slot of local window 0 (slot(lw) = slot0 + lw); all windows share slot 0 without tables
     uint32_t tables;      // 1: window lw reads table slot0 + lw; 0: every window reads the points themselves
@@ -40,8 +40,7 @@ struct SortGeom {
 struct MsmEntriesCall {
     MsmPlan P;
     SortGeom g;
-    bool big_tiles;               // the sort's tile shape (SortBig / SortSmall)
-    uint32_t nbh;                 // counters of the sort's (super-bucket, window, tile) histogram
+    uint32_t nbh;                // counters of the sort's (super-bucket, window, tile) histogram
     uint32_t sblk, nsh;           // size sort: workgroups of 1024 buckets, counters of its (bin, workgroup) histogram
     // large buckets: split threshold, and the worst-case plan (every entry in a large bucket)
     uint32_t large_thresh, large_cap, task_cap;
@@ -54,16 +53,17 @@ struct MsmEntriesBuffers {
     uint16_t *tmp_key;
     uint32_t *offs, *idx;
     uint32_t *sh, *so, *ssums, *order;  // size sort: histogram, its scan, block sums; bucket ids by descending size
-    uint32_t *plan, *tasks, *large;     // large buckets (msm_plan_large)
+    uint32_t *plan, *tasks, *large;     // large buckets: counters, tasks and buckets of the plan (written by msm_size_scatter)
 };
 
 }  // namespace zkhip
 
 // the geometry of the MSM over points offset .. offset + n of `bases`; ZKHIP_ERR_RANGE (with `error` set where the entries outgrow 32 bits)
 int zk_msm_entries_plan(const zkhip_ctx *ctx, const zkhip_bases *bases, size_t offset, size_t n, zkhip::MsmEntriesCall &c, std::string &error);
-// enqueue digits, sort and size order: dig, offs, idx and order are final when the stream reaches the end of it
+// enqueue digits, sort, size order and the plan of the buckets above c.large_thresh: dig, offs, idx, order, plan, tasks and large are final when
+// the stream reaches the end of it; a plan beyond its capacities raises ZK_STATUS_MSM_PLAN_OVERFLOW
 int zk_msm_entries(zkhip_ctx *ctx, int curve, const zkhip::MsmEntriesCall &c, const zkhip::MsmEntriesBuffers &w, const uint32_t *d_scalars);
-// enqueue the plan of the buckets above c.large_thresh (reads offs): plan, tasks, large; an overflow raises ZK_STATUS_MSM_PLAN_OVERFLOW
+// the point of the sequence from which callers read plan, tasks and large; enqueues nothing (the plan is the last kernel of zk_msm_entries)
 int zk_msm_large_plan(zkhip_ctx *ctx, const zkhip::MsmEntriesCall &c, const zkhip::MsmEntriesBuffers &w);
 // the size sort's bin of a bucket of `size` entries under the split threshold `large`: order lists the buckets by ascending bin
 uint32_t zk_msm_size_bin(uint32_t size, uint32_t large);
