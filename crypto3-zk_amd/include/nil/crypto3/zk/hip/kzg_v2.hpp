@@ -16,7 +16,8 @@
 //   transcript(const single_commitment_type &), transcript(const scalar_value_type &),
 //   scalar_value_type transcript.challenge().
 // kzg_commitment_scheme_v2_hip::commit() returns the vector of single commitments; the class placeholder takes as
-// `commitment_scheme_type` is kzg_commitment_scheme_v2_placeholder_hip below: its commit() returns the reference's byte
+// `commitment_scheme_type` is kzg_commitment_scheme_v2_placeholder_hip below (kzg_placeholder_adapter_hip over this scheme;
+// kzg_commitment_scheme_placeholder_hip is the same adapter over the first batched scheme): its commit() returns the reference's byte
 // blob (every single commitment through the caller's Packer, concatenated: kzg_v2.hpp:208-226 with nil::marshalling
 // behind the functor) and its verify_eval() hands (proof, commitments, transcript) to the caller's Verifier (the
 // pairing check of kzg_v2.hpp:312-395 is CPU-side reference code outside this backend).
@@ -153,9 +154,10 @@ public:
     /// of the scheme runs on member 0.  The reference's commit is a loop over the batch inside the call (kzg_v2.hpp:208-226): so is this.
     typedef kzg_params_group_hip<CurveType> group_params_type;
     kzg_polys_evaluator_hip(const group_params_type &group_params, root_of_unity_type root_of_unity) :
-        base(group_params.root().ctx), _params(group_params.root()), _root_of_unity(std::move(root_of_unity)), _group_params(&group_params) { }
+        base(group_params.root().ctx, group_params.members.size()), _params(group_params.root()), _root_of_unity(std::move(root_of_unity)), _group_params(&group_params) { }
     explicit kzg_polys_evaluator_hip(const group_params_type &group_params) :
-        base(group_params.root().ctx), _params(group_params.root()), _root_of_unity([](std::size_t log_n) { return adapter::root_of_unity(log_n); }), _group_params(&group_params) { }
+        base(group_params.root().ctx, group_params.members.size()), _params(group_params.root()), _root_of_unity([](std::size_t log_n) { return adapter::root_of_unity(log_n); }),
+        _group_params(&group_params) { }
 
     const params_type &get_commitment_params() const { return _params; }
     preprocessed_data_type preprocess(transcript_type &) const { return true; }
@@ -209,7 +211,7 @@ public:
             auto d_res = ctx.alloc(std::max<std::size_t>(1, count) * jl * 8);
             /* a batch that is resident already has nothing to overlap: one chunk, one shared tail over all its multiexps */
             const bool pipelined = upload_chunk != 0 && count > upload_chunk && has_host_columns(index, 0, count);
-            const context &up = pipelined ? upload_context() : ctx;
+            const context &up = pipelined ? this->upload_context(0, ctx) : ctx;
             /* a resident polynomial may still be in the making on ctx's stream (polynomial_product, resize do not synchronise): the stream that
                copies it waits for ctx once */
             if (pipelined && (!resident.empty() || !resident_c.empty())) up.wait_for(ctx);
@@ -312,15 +314,13 @@ private:
                 group.copy(k, pt.base + 32 * (db.offset[p] - db.offset[pt.lo]), 0, src, db.len[p] * 32);
             }
         }
-        _member_up.resize(world);
         group.for_each_member([&](std::size_t k) {
             const detail::group_part &pt = parts[k];
             if (pt.empty()) return;
             const context &ctx = group[k];
             const std::size_t mine = pt.hi - pt.lo, chunk = upload_chunk ? std::max<std::size_t>(1, std::min(upload_chunk, (mine + 2) / 3)) : 0;
             const bool pipelined = chunk != 0 && mine > chunk && has_host_columns(index, pt.lo, pt.hi);
-            if (pipelined && !_member_up[k]) _member_up[k].reset(new context(ctx.device()));
-            commit_columns(index, db, pt.lo, pt.hi, pt.base, ctx, pipelined ? *_member_up[k] : ctx, gp.members[k]->commitment_key.get(), d_res[k].get(), roots,
+            commit_columns(index, db, pt.lo, pt.hi, pt.base, ctx, pipelined ? this->upload_context(k, ctx) : ctx, gp.members[k]->commitment_key.get(), d_res[k].get(), roots,
                            pipelined ? chunk : 0, pipelined ? chunk : 0, false);
             ctx.d2h(res.data() + pt.lo * jl, d_res[k].get(), mine * jl * 8);    // synchronises this member's stream (its upload stream has drained: every upload is a synchronous copy)
         });
@@ -340,11 +340,6 @@ public:
     const std::map<std::size_t, commitment_type> &commitments() const { return _ind_commitments; }
 
 protected:
-    /// the second stream the uploads of commit() ride on (created on first use, same GPU)
-    const context &upload_context() const {
-        if (!_upload_ctx) _upload_ctx.reset(new context(_params.ctx.device()));
-        return *_upload_ctx;
-    }
     single_commitment_type commit_range(const void *d_coeffs, std::size_t len) const {
         if (len == 0) return single_commitment_type::zero();
         if (len > _params.commitment_key.size()) throw std::runtime_error("proof_eval: quotient longer than the commitment key");
@@ -432,7 +427,7 @@ protected:
     }
     /// WHAT the transcript absorbs.  These device schemes hand it VALUES (one call per commitment / scalar); the reference hands it
     /// BYTES: the batch's commitment blob in one call, every scalar and pi_1 / pi_2 through nil::marshalling::pack (kzg_v2.hpp:153-189,
-    /// 265-272, 296-304).  The placeholder-facing wrappers below override the three hooks to reproduce exactly that.
+    /// 265-272, 296-304).  The placeholder adapter below overrides the three hooks to reproduce exactly that.
     virtual void absorb_batch_commitments(std::size_t batch_ind, transcript_type &transcript) {
         for (const auto &c : _ind_commitments.at(batch_ind)) transcript(c);
     }
@@ -450,12 +445,10 @@ protected:
     using base::_locked;
     using base::_points;
     using base::_dev;
-    using base::_upload_ctx;
     std::map<std::size_t, std::map<std::size_t, device_polynomial_dfs<CurveType>>> _resident;    // batch -> position -> resident polynomial
     std::map<std::size_t, std::map<std::size_t, device_polynomial_coefficients<CurveType>>> _resident_coefficients;    // ... in coefficient form
     std::map<std::size_t, commitment_type> _ind_commitments;
     std::vector<scalar_value_type> _merged_points;
-    std::vector<std::unique_ptr<context>> _member_up;    // over a device group: each member's upload stream (created on first use, same GPU)
     const group_params_type *_group_params = nullptr;    // set: commit(batch) deals its columns over this group's members
     mutable std::size_t _group_multiexps = 0;
 };
@@ -737,10 +730,10 @@ struct scalar_be_packer {
 ///   ScalarPacker: std::vector<std::uint8_t>(const scalar_value_type &)     -- nil::marshalling::pack<endianness>(field element, status)
 /// With them the TRANSCRIPT sees what the reference's sees, byte for byte: the batch's commitment blob in one call, every evaluation
 /// and U coefficient packed, pi_1 and pi_2 packed (kzg_v2.hpp:150-190, 265-272, 296-304; tests/cpp/shim_test.cpp records the calls).
-template <typename CurveType, typename TranscriptType, typename Packer, typename Verifier, typename PolynomialType = polynomial_dfs<CurveType>,
-          typename ScalarPacker = scalar_be_packer<CurveType>>
-class kzg_commitment_scheme_v2_placeholder_hip : public kzg_commitment_scheme_v2_hip<CurveType, TranscriptType, PolynomialType> {
-    typedef kzg_commitment_scheme_v2_hip<CurveType, TranscriptType, PolynomialType> base;
+/// One adapter over either device scheme (`Base`); the two names placeholder is given are the aliases below.
+template <typename Base, typename Packer, typename Verifier, typename ScalarPacker>
+class kzg_placeholder_adapter_hip : public Base {
+    typedef Base base;
 
 public:
     typedef std::vector<std::uint8_t> commitment_type;
@@ -749,11 +742,11 @@ public:
     typedef typename base::params_type params_type;
     typedef typename base::root_of_unity_type root_of_unity_type;
 
-    kzg_commitment_scheme_v2_placeholder_hip(const params_type &kzg_params, root_of_unity_type root_of_unity, Packer packer, Verifier verifier,
-                                             ScalarPacker scalar_packer = ScalarPacker()) :
+    kzg_placeholder_adapter_hip(const params_type &kzg_params, root_of_unity_type root_of_unity, Packer packer, Verifier verifier,
+                                ScalarPacker scalar_packer = ScalarPacker()) :
         base(kzg_params, std::move(root_of_unity)), _packer(std::move(packer)), _verifier(std::move(verifier)), _scalar_packer(std::move(scalar_packer)) { }
 
-    /// kzg_v2.hpp:208-226: "Differs from static, because we pack the result into byte blob."
+    /// kzg_v2.hpp:208-226 (v1: kzg.hpp:748-765): "Differs from static, because we pack the result into byte blob."
     commitment_type commit(std::size_t index) {
         commitment_type result;
         for (const auto &single_commitment : base::commit(index)) {
@@ -784,52 +777,17 @@ private:
     std::map<std::size_t, commitment_type> _commitments;
 };
 
-/// The same for the FIRST batched scheme (kzg_commitment_scheme, kzg.hpp:636-873): `commit` packs the single commitments into the
-/// reference's byte blob (:748-765), `verify_eval` (:809-868) goes to the caller's pairing check, which finds commit_g2, the
-/// evaluation points and the per-polynomial commitments on this object.
+/// over kzg_commitment_scheme_v2 (kzg_v2.hpp:56-360) ...
 template <typename CurveType, typename TranscriptType, typename Packer, typename Verifier, typename PolynomialType = polynomial_dfs<CurveType>,
           typename ScalarPacker = scalar_be_packer<CurveType>>
-class kzg_commitment_scheme_placeholder_hip : public kzg_commitment_scheme_hip<CurveType, TranscriptType, PolynomialType> {
-    typedef kzg_commitment_scheme_hip<CurveType, TranscriptType, PolynomialType> base;
-
-public:
-    typedef std::vector<std::uint8_t> commitment_type;
-    typedef typename base::proof_type proof_type;
-    typedef typename base::transcript_type transcript_type;
-    typedef typename base::params_type params_type;
-    typedef typename base::root_of_unity_type root_of_unity_type;
-
-    kzg_commitment_scheme_placeholder_hip(const params_type &kzg_params, root_of_unity_type root_of_unity, Packer packer, Verifier verifier,
-                                          ScalarPacker scalar_packer = ScalarPacker()) :
-        base(kzg_params, std::move(root_of_unity)), _packer(std::move(packer)), _verifier(std::move(verifier)), _scalar_packer(std::move(scalar_packer)) { }
-
-    commitment_type commit(std::size_t index) {
-        commitment_type result;
-        for (const auto &single_commitment : base::commit(index)) {
-            const std::vector<std::uint8_t> bytes = _packer(single_commitment);
-            result.insert(result.end(), bytes.begin(), bytes.end());
-        }
-        _commitments[index] = result;
-        return result;
-    }
-    bool verify_eval(const proof_type &proof, const std::map<std::size_t, commitment_type> &commitments, transcript_type &transcript) {
-        return _verifier(*this, proof, commitments, transcript);
-    }
-    const std::map<std::size_t, commitment_type> &packed_commitments() const { return _commitments; }
-    const std::vector<typename base::scalar_value_type> &eval_points(std::size_t batch, std::size_t poly) const { return this->_points.at(batch).at(poly); }
-
-protected:
-    /* the reference's transcript traffic (kzg.hpp:695-738) */
-    void absorb_batch_commitments(std::size_t batch_ind, transcript_type &transcript) override { transcript(_commitments.at(batch_ind)); }
-    void absorb_scalar(const typename base::scalar_value_type &v, transcript_type &transcript) override { transcript(_scalar_packer(v)); }
-    void absorb_point(const typename base::single_commitment_type &p, transcript_type &transcript) override { transcript(_packer(p)); }
-
-private:
-    Packer _packer;
-    Verifier _verifier;
-    ScalarPacker _scalar_packer;
-    std::map<std::size_t, commitment_type> _commitments;
-};
+using kzg_commitment_scheme_v2_placeholder_hip =
+    kzg_placeholder_adapter_hip<kzg_commitment_scheme_v2_hip<CurveType, TranscriptType, PolynomialType>, Packer, Verifier, ScalarPacker>;
+/// ... and over the FIRST batched scheme (kzg_commitment_scheme, kzg.hpp:636-873; transcript traffic :695-738, verify_eval :809-868): the
+/// caller's pairing check finds commit_g2, the evaluation points and the per-polynomial commitments on the object
+template <typename CurveType, typename TranscriptType, typename Packer, typename Verifier, typename PolynomialType = polynomial_dfs<CurveType>,
+          typename ScalarPacker = scalar_be_packer<CurveType>>
+using kzg_commitment_scheme_placeholder_hip =
+    kzg_placeholder_adapter_hip<kzg_commitment_scheme_hip<CurveType, TranscriptType, PolynomialType>, Packer, Verifier, ScalarPacker>;
 
 }    // namespace hip
 }    // namespace zk

@@ -53,6 +53,9 @@
 // leaves and sends them to the host over ITS link while the caller hashes.  Same leaves, same order, same roots as on one device; the
 // coefficient forms are gathered on member 0, where proof_eval runs as before.  See commit_group.  A device tree builder over a group is
 // not supported (the leaf owners would each hold a subtree): the group constructor refuses it at compile time.
+// Lone or over a group, what a commit keeps across calls exists once per member -- its upload stream (polys_evaluator.hpp) and its scratch
+// (member_scratch; entry 0 is the lone context's) -- and a host builder gets its leaves through one function, deliver_leaves, over blocks of
+// laid-out leaves: one block on one context, or the owners' blocks on theirs.
 //---------------------------------------------------------------------------//
 #ifndef ZKHIP_SHIM_LPC_HPP
 #define ZKHIP_SHIM_LPC_HPP
@@ -279,19 +282,14 @@ public:
     using base::_z;
 
     lpc_commitment_scheme_hip(const context &ctx, const params_type &fri_params, TreeBuilder builder) :
-        base(ctx), _fri_params(fri_params), _builder(std::move(builder)), _etha(value_type::zero()) {
-        std::size_t r = 0;
-        for (std::size_t s : fri_params.step_list) r += s;
-        if (fri_params.step_list.empty() || r > fri_params.log_domain) throw std::invalid_argument("lpc: step_list does not fit the domain");
-    }
+        lpc_commitment_scheme_hip(ctx, 1, fri_params, std::move(builder)) { }
 
     /// the scheme over a device group: commit(batch) spreads over the members (commit_group), everything else runs on member 0
     lpc_commitment_scheme_hip(const device_group &group, const params_type &fri_params, TreeBuilder builder) :
-        lpc_commitment_scheme_hip(group.root(), fri_params, std::move(builder)) {
+        lpc_commitment_scheme_hip(group.root(), group.size(), fri_params, std::move(builder)) {
         static_assert(builder_kind != detail::tree_builder_kind::device,
                       "lpc over a device group takes a host tree builder: a device tree builder (hip/merkle.hpp) works on one context only");
         _group = &group;
-        _gs.reset(new group_scratch[group.size()]);
     }
 
     const params_type &get_commitment_params() const { return _fri_params; }
@@ -327,10 +325,12 @@ public:
         root_map roots;    // D[0]'s root first, then one per distinct size
         roots[_fri_params.log_domain] = limbs_of<adapter>(_fri_params.root_of_unity(_fri_params.log_domain));
         detail::add_roots<adapter>(roots, db, _fri_params.root_of_unity);
-        if (_group && _group->size() > 1 && count) commit_group(index, polys, db, roots);
-        else {
-            char *d_ext = static_cast<char *>(_scratch_ext.reserve(_ctx, std::max<std::size_t>(1, count) * D * 32));    // kept across commits: no GB-sized hipMalloc per batch
-            extend_columns(polys, db, 0, count, static_cast<char *>(db.data.get()), _ctx, this->_upload_ctx, d_ext, roots);
+        if (_group && _group->size() > 1 && count) {
+            /* host builders only: the group constructor, which alone sets _group, does not compile for a device builder */
+            if constexpr (builder_kind != detail::tree_builder_kind::device) commit_group(index, polys, db, roots);
+        } else {
+            char *d_ext = static_cast<char *>(_scratch[0].ext.reserve(_ctx, std::max<std::size_t>(1, count) * D * 32));    // kept across commits: no GB-sized hipMalloc per batch
+            extend_columns(polys, db, 0, count, static_cast<char *>(db.data.get()), _ctx, 0, d_ext, roots);
             _trees.erase(index);
             _trees.emplace(index, build_tree(d_ext, count, _fri_params.log_domain, _fri_params.step_list.front()));
         }
@@ -356,14 +356,13 @@ protected:
 
     /// poly.resize(D[0]->size()) (basic_fri.hpp:452-455) for polys [lo, hi) of a batch on `ctx`, one call per chunk of equally sized
     /// polynomials: uploaded into `base` (polynomial p at base + 32 (offset[p] - offset[lo])), where the call leaves the COEFFICIENTS proof_eval
-    /// reads later, and extended to d_ext + 32 (p - lo) D.  The chunks go up on a second in-order stream (`up`, created on first use, same
-    /// GPU): chunk c + 1 crosses PCIe while chunk c is transformed.  Enqueued only.
+    /// reads later, and extended to d_ext + 32 (p - lo) D.  The chunks go up on member `k`'s upload stream (upload_context: a second in-order
+    /// stream of ctx's GPU): chunk c + 1 crosses PCIe while chunk c is transformed.  Enqueued only.
     void extend_columns(const std::vector<const poly_type *> &polys, const device_batch &db, std::size_t lo, std::size_t hi, char *base, const context &ctx,
-                        std::unique_ptr<context> &up, char *d_ext, const root_map &roots) const {
+                        std::size_t k, char *d_ext, const root_map &roots) const {
         const std::size_t D = domain_size(0);
         const bool pipelined = upload_chunk != 0 && hi - lo > upload_chunk;
-        if (pipelined && !up) up.reset(new context(ctx.device()));
-        const context &upc = pipelined ? *up : ctx;
+        const context &upc = pipelined ? this->upload_context(k, ctx) : ctx;
         auto at = [&](std::size_t p) { return base + 32 * (db.offset[p] - db.offset[lo]); };
         db.for_each_run(lo, hi, upload_chunk, upload_chunk, [&](std::size_t i, std::size_t j) {
             for (std::size_t p = i; p < j; ++p) upload_scalars<adapter>(upc, at(p), detail::poly_data<adapter>(*polys[p]), polys[p]->size());
@@ -392,7 +391,7 @@ protected:
         const std::size_t owners = (std::size_t)1 << log_owners, Ds = D >> log_owners, seg = Ds >> step, rows_per_poly = (std::size_t)1 << step;
         std::vector<detail::group_part> parts(world);
         for (std::size_t k = 0; k < world; ++k) {
-            group_scratch &gs = _gs[k];
+            member_scratch &gs = _scratch[k];
             if (k < owners) {
                 gs.cmp.reserve(group[k], count * Ds * 32);
                 gs.leaves.reserve(group[k], count * Ds * 32);
@@ -406,10 +405,10 @@ protected:
             const detail::group_part &pt = parts[k];
             if (pt.empty()) return;
             const context &ctx = group[k];
-            group_scratch &gs = _gs[k];
+            member_scratch &gs = _scratch[k];
             const std::size_t mine = pt.hi - pt.lo;
             char *d_ext = static_cast<char *>(gs.ext.get());
-            extend_columns(polys, db, pt.lo, pt.hi, pt.base, ctx, gs.up, d_ext, roots);
+            extend_columns(polys, db, pt.lo, pt.hi, pt.base, ctx, k, d_ext, roots);
             /* per owner: the 2^step segments [d seg + j D / 2^step, + seg) of each of my polynomials, side by side (rows of seg elements at a
                pitch of D / 2^step in, seg out) -- straight into my own buffer where I am the owner */
             for (std::size_t d = 0; d < owners; ++d) {
@@ -424,17 +423,17 @@ protected:
             const std::size_t mine = pt.hi - pt.lo;
             for (std::size_t d = 0; d < owners; ++d)
                 if (d != k)
-                    group.copy(d, static_cast<char *>(_gs[d].cmp.get()) + 32 * pt.lo * Ds, k, static_cast<const char *>(_gs[k].send.get()) + 32 * d * mine * Ds,
+                    group.copy(d, static_cast<char *>(_scratch[d].cmp.get()) + 32 * pt.lo * Ds, k, static_cast<const char *>(_scratch[k].send.get()) + 32 * d * mine * Ds,
                                mine * Ds * 32);
             detail::gather_form(db, group, k, pt);
         }
-        std::vector<const void *> d_leaves(owners);
+        std::vector<leaf_block> blocks;
         for (std::size_t d = 0; d < owners; ++d) {
-            ZKHIP_CALL(group[d], zkhip_fri_leaves_dev, _gs[d].cmp.get(), _fri_params.log_domain - log_owners, count, step, _gs[d].leaves.get());
-            d_leaves[d] = _gs[d].leaves.get();
+            ZKHIP_CALL(group[d], zkhip_fri_leaves_dev, _scratch[d].cmp.get(), _fri_params.log_domain - log_owners, count, step, _scratch[d].leaves.get());
+            blocks.push_back({group[d], _scratch[d].leaves.get(), _scratch[d]});
         }
         _trees.erase(index);
-        _trees.emplace(index, build_tree_group(d_leaves, count * Ds, count * rows_per_poly));
+        _trees.emplace(index, deliver_leaves(blocks, count * Ds, count * rows_per_poly));
         group.sync();    // the members' own coefficient buffers go with `parts`: every copy out of them has finished
         ++_group_commits;
         _last_owners = owners;
@@ -624,7 +623,8 @@ public:
             const std::size_t count = db.len.size();
             for (std::size_t q = 0; q < lambda; ++q) qps[q].initial_proof[it.first].values.assign(count, std::vector<std::array<value_type, 2>>(pairs0));
             if (count == 0) continue;
-            char *d_ext = static_cast<char *>(_scratch_ext.reserve(_ctx, count * D0 * 32));
+            /* member 0's extension buffer, which commit_group fills too: both on member 0's stream, and reserve() drains it before it reallocates */
+            char *d_ext = static_cast<char *>(_scratch[0].ext.reserve(_ctx, count * D0 * 32));
             for (std::size_t p = 0; p < count; ++p) fv::zero_padded_copy(_ctx, db.at(p), db.len[p], d_ext + 32 * p * D0, D0);    // len >= 1: commit refuses less
             fv::ntt(_ctx, d_ext, n, count, w0, false);
             if (_time_query_phase) _ctx.sync();
@@ -969,79 +969,76 @@ protected:
         check(zkhip_sha256_host(bytes.data(), bytes.size(), digest.data()), "zkhip_sha256_host");
         return path.root_from(digest) == root;
     }
+    /// What a member keeps across commits: the extensions of its columns, the blocks it sends, an owner's compact evaluations and its leaves,
+    /// and the two page-locked buffers its leaves cross PCIe through.  Entry 0 is the lone context's (over a group: member 0's) and serves the
+    /// lone commit, proof_eval's round trees and query_phase's re-extension too: outside commit_group's member lambda every use of it is
+    /// enqueued on that context's stream from the calling thread, commit_group ends in group.sync(), and device_scratch::reserve drains the
+    /// stream before it reallocates.
+    struct member_scratch {
+        device_scratch ext, send, cmp, leaves;
+        pinned_buffer pin[2];
+    };
+    /// `block` laid-out leaf elements at `d_leaves` on `ctx`, the scratch entry of that member
+    struct leaf_block {
+        const context &ctx;
+        const void *d_leaves;
+        member_scratch &scratch;
+    };
     /// the leaf layout of `batch` polynomials resident as evaluations over the 2^log_domain-point domain -> the caller's tree; a device
     /// builder takes the evaluations as they lie: no leaf layout, no copy to the host
     precommitment_type build_tree(const void *d_evals, std::size_t batch, std::size_t log_domain, std::size_t fri_step) const {
         if constexpr (builder_kind == detail::tree_builder_kind::device) return _builder(_ctx, d_evals, batch, log_domain, fri_step);
-        else return build_tree_host(d_evals, batch, log_domain, fri_step);
-    }
-    precommitment_type build_tree_host(const void *d_evals, std::size_t batch, std::size_t log_domain, std::size_t fri_step) const {
-        const std::size_t D = (std::size_t)1 << log_domain, total = batch * D, per_leaf = batch * ((std::size_t)1 << fri_step);
-        void *d_leaves = _scratch_leaves.reserve(_ctx, std::max<std::size_t>(1, total) * 32);
-        ZKHIP_CALL(_ctx, zkhip_fri_leaves_dev, d_evals, log_domain, batch, fri_step, d_leaves);
-        if constexpr (builder_kind == detail::tree_builder_kind::streaming) {
-            /* slices of whole leaves through two page-locked buffers: the copy of slice k + 1 is in flight while the caller absorbs slice k */
-            const std::size_t slice = std::max<std::size_t>(1, (leaf_slice_elements + per_leaf - 1) / std::max<std::size_t>(1, per_leaf)) * std::max<std::size_t>(1, per_leaf);
-            _builder.begin(total, per_leaf);
-            if (total != 0) {
-                void *pin[2] = {_pin[0].reserve(_ctx, std::min(slice, total) * 32), _pin[1].reserve(_ctx, std::min(slice, total) * 32)};
-                const char *src = static_cast<const char *>(d_leaves);
-                _ctx.d2h_async(pin[0], src, std::min(slice, total) * 32);
-                _ctx.sync();
-                for (std::size_t at = 0, k = 0; at < total; at += slice, ++k) {
-                    const std::size_t cnt = std::min(slice, total - at), next = at + slice;
-                    if (next < total) _ctx.d2h_async(pin[(k + 1) & 1], src + 32 * next, std::min(slice, total - next) * 32);
-                    _builder.absorb(host_values(pin[k & 1], cnt), at, cnt);
-                    _ctx.sync();
-                }
-            }
-            return _builder.finish();
-        } else if constexpr (builder_kind == detail::tree_builder_kind::span) {
-            void *pin = _pin[0].reserve(_ctx, std::max<std::size_t>(1, total) * 32);
-            if (total != 0) {
-                _ctx.d2h_async(pin, d_leaves, total * 32);
-                _ctx.sync();
-            }
-            return _builder(host_values(pin, total), total, per_leaf);
-        } else {
-            _leaf_vec.clear();    // keeps its capacity: after the first commit no page of it is touched for the first time
-            download_scalars<adapter>(_ctx, d_leaves, total, _leaf_vec);    // one copy for canonical-limb scalar types (backend.hpp)
-            return _builder(_leaf_vec, per_leaf);
+        else {
+            const std::size_t total = batch << log_domain;
+            void *d_leaves = _scratch[0].leaves.reserve(_ctx, std::max<std::size_t>(1, total) * 32);
+            ZKHIP_CALL(_ctx, zkhip_fri_leaves_dev, d_evals, log_domain, batch, fri_step, d_leaves);
+            return deliver_leaves({{_ctx, d_leaves, _scratch[0]}}, total, batch << fri_step);
         }
     }
-    /// the same tree from leaves that lie in `d_leaves.size()` consecutive blocks of `block` elements, block d on member d of the group: every
-    /// owner's first slice is requested at once and its link stays one slice ahead of the caller, who absorbs the blocks in leaf order
-    precommitment_type build_tree_group(const std::vector<const void *> &d_leaves, std::size_t block, std::size_t per_leaf) const {
-        const device_group &group = *_group;
-        const std::size_t owners = d_leaves.size(), total = owners * block;
-        if constexpr (builder_kind == detail::tree_builder_kind::device) {
-            throw std::logic_error("lpc: a device tree builder over a device group is not supported");    // unreachable: the group constructor does not compile
-        } else if constexpr (builder_kind == detail::tree_builder_kind::streaming) {
-            const std::size_t slice = std::max<std::size_t>(1, (leaf_slice_elements + per_leaf - 1) / std::max<std::size_t>(1, per_leaf)) * std::max<std::size_t>(1, per_leaf);
+    /// The host builder's tree from leaves that lie in consecutive blocks of `block` elements (`per_leaf` to a leaf), block d on blocks[d].ctx:
+    /// the one block of a lone context, or the leaf owners' of a group.  Nothing below depends on which.
+    precommitment_type deliver_leaves(const std::vector<leaf_block> &blocks, std::size_t block, std::size_t per_leaf) const {
+        const std::size_t total = blocks.size() * block;
+        if constexpr (builder_kind == detail::tree_builder_kind::streaming) {
+            /* slices of whole leaves through two page-locked buffers per block: every block's first slice is requested at once, then the blocks
+               are absorbed in leaf order, the copy of a block's slice k + 1 in flight on its own link while the caller absorbs slice k */
+            const std::size_t leaf = std::max<std::size_t>(1, per_leaf), slice = std::max<std::size_t>(1, (leaf_slice_elements + leaf - 1) / leaf) * leaf;
             const std::size_t first = std::min(slice, block);
             _builder.begin(total, per_leaf);
-            for (std::size_t d = 0; d < owners; ++d) {
-                void *p0 = _gs[d].pin[0].reserve(group[d], first * 32);
-                _gs[d].pin[1].reserve(group[d], first * 32);
-                group[d].d2h_async(p0, d_leaves[d], first * 32);
-            }
-            for (std::size_t d = 0; d < owners; ++d) {
-                const char *src = static_cast<const char *>(d_leaves[d]);
-                void *pin[2] = {_gs[d].pin[0].get(), _gs[d].pin[1].get()};
-                group[d].sync();
-                for (std::size_t at = 0, k = 0; at < block; at += slice, ++k) {
-                    const std::size_t cnt = std::min(slice, block - at), next = at + slice;
-                    if (next < block) group[d].d2h_async(pin[(k + 1) & 1], src + 32 * next, std::min(slice, block - next) * 32);
-                    _builder.absorb(host_values(pin[k & 1], cnt), d * block + at, cnt);
-                    group[d].sync();
+            if (total != 0) {
+                for (const leaf_block &b : blocks) {
+                    void *p0 = b.scratch.pin[0].reserve(b.ctx, first * 32);
+                    b.scratch.pin[1].reserve(b.ctx, first * 32);
+                    b.ctx.d2h_async(p0, b.d_leaves, first * 32);
+                }
+                for (std::size_t d = 0; d < blocks.size(); ++d) {
+                    const leaf_block &b = blocks[d];
+                    const char *src = static_cast<const char *>(b.d_leaves);
+                    void *pin[2] = {b.scratch.pin[0].get(), b.scratch.pin[1].get()};
+                    b.ctx.sync();
+                    for (std::size_t at = 0, k = 0; at < block; at += slice, ++k) {
+                        const std::size_t cnt = std::min(slice, block - at), next = at + slice;
+                        if (next < block) b.ctx.d2h_async(pin[(k + 1) & 1], src + 32 * next, std::min(slice, block - next) * 32);
+                        _builder.absorb(host_values(pin[k & 1], cnt), d * block + at, cnt);
+                        b.ctx.sync();
+                    }
                 }
             }
             return _builder.finish();
         } else {
-            /* one page-locked buffer for all leaves (portable: every member's copy engine may write it), the owners' downloads side by side */
-            char *pin = static_cast<char *>(_pin[0].reserve(_ctx, std::max<std::size_t>(1, total) * 32));
-            for (std::size_t d = 0; d < owners; ++d) group[d].d2h_async(pin + 32 * d * block, d_leaves[d], block * 32);
-            for (std::size_t d = 0; d < owners; ++d) group[d].sync();
+            if constexpr (builder_kind == detail::tree_builder_kind::vector)
+                if (blocks.size() == 1) {    // straight into the vector: one copy for canonical-limb scalar types (backend.hpp)
+                    _leaf_vec.clear();       // keeps its capacity: after the first commit no page of it is touched for the first time
+                    download_scalars<adapter>(blocks[0].ctx, blocks[0].d_leaves, total, _leaf_vec);
+                    return _builder(_leaf_vec, per_leaf);
+                }
+            /* one page-locked buffer for all leaves (portable: every member's copy engine may write it), the blocks' downloads side by side.  The
+               vector builder goes through it only with several blocks: a pageable vector cannot be the target of several members' copy engines */
+            char *pin = static_cast<char *>(blocks[0].scratch.pin[0].reserve(blocks[0].ctx, std::max<std::size_t>(1, total) * 32));
+            if (total != 0) {
+                for (std::size_t d = 0; d < blocks.size(); ++d) blocks[d].ctx.d2h_async(pin + 32 * d * block, blocks[d].d_leaves, block * 32);
+                for (const leaf_block &b : blocks) b.ctx.sync();
+            }
             const value_type *values = host_values(pin, total);
             if constexpr (builder_kind == detail::tree_builder_kind::span) return _builder(values, total, per_leaf);
             else {
@@ -1065,12 +1062,14 @@ protected:
             return _conv.data();
         }
     }
-    /// per member of the group, kept across commits: extensions, blocks to send, the owner's compact evaluations and its leaves
-    struct group_scratch {
-        device_scratch ext, send, cmp, leaves;
-        pinned_buffer pin[2];
-        std::unique_ptr<context> up;    // the member's upload stream
-    };
+    /// what both public constructors come to: `members` upload streams (polys_evaluator.hpp) and scratch entries
+    lpc_commitment_scheme_hip(const context &ctx, std::size_t members, const params_type &fri_params, TreeBuilder &&builder) :
+        base(ctx, members), _scratch(new member_scratch[std::max<std::size_t>(1, members)]), _fri_params(fri_params), _builder(std::move(builder)),
+        _etha(value_type::zero()) {
+        std::size_t r = 0;
+        for (std::size_t s : fri_params.step_list) r += s;
+        if (fri_params.step_list.empty() || r > fri_params.log_domain) throw std::invalid_argument("lpc: step_list does not fit the domain");
+    }
     /// host wall time of the last query_phase by part, for a measuring subclass (the bench driver's): filled while _time_query_phase is set,
     /// which costs a stream synchronisation per batch.  Not part of the scheme's interface.
     struct query_phase_times {
@@ -1080,13 +1079,11 @@ protected:
     query_phase_times _last_query_times;
     const device_group *_group = nullptr;
     std::size_t _group_commits = 0, _last_owners = 0;
-    mutable std::unique_ptr<group_scratch[]> _gs;    // an array: the page-locked buffers neither copy nor move
+    mutable std::unique_ptr<member_scratch[]> _scratch;    // max(1, world) entries; an array: the page-locked buffers neither copy nor move
     params_type _fri_params;
     mutable TreeBuilder _builder;
     value_type _etha;
-    mutable pinned_buffer _pin[2];
     mutable std::vector<value_type> _leaf_vec, _conv;
-    mutable device_scratch _scratch_ext, _scratch_leaves;    // kept across commits (every use is ordered on _ctx's stream)
     std::map<std::size_t, bool> _batch_fixed;
     std::map<std::size_t, precommitment_type> _trees;
     preprocessed_data_type _fixed_polys_values;

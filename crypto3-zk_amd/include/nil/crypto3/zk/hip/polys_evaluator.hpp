@@ -140,7 +140,8 @@ public:
 
     eval_storage_type _z;
 
-    explicit polys_evaluator_hip(const context &ctx) : _ctx(ctx) { }
+    /// `members`: how many devices commit(batch) spreads over (a device group's world; 1: `ctx` alone)
+    explicit polys_evaluator_hip(const context &ctx, std::size_t members = 1) : _ctx(ctx), _upload(std::max<std::size_t>(1, members)) { }
 
     // ---- batched_commitment.hpp:197-247 ----
     /// as the reference: the scheme keeps a COPY of the polynomial (batched_commitment.hpp:197-206)
@@ -234,15 +235,25 @@ protected:
         return result;
     }
 
+    /// Member k's upload stream: the second in-order stream the uploads of commit() ride on, on the GPU of `on` (member k's context), created
+    /// on first use.  The slots are sized in the constructor and never resized: the member threads of for_each_member each touch their own
+    /// slot only, and none of them may see the vector move.
+    const context &upload_context(std::size_t k, const context &on) const {
+        std::unique_ptr<context> &up = _upload.at(k);
+        if (!up) up.reset(new context(on.device()));
+        return *up;
+    }
+
     const context &_ctx;
     std::map<std::size_t, std::vector<const poly_type *>> _polys;    // in append order: copies held in _owned, or the caller's (lent)
     std::map<std::size_t, std::deque<poly_type>> _owned;             // a deque: references stay valid as it grows
     std::map<std::size_t, bool> _locked;
     std::map<std::size_t, std::vector<std::vector<scalar_value_type>>> _points;
     std::map<std::size_t, device_batch> _dev;
-    mutable std::unique_ptr<context> _upload_ctx;    // the second stream the uploads of commit() ride on (created on first use, same GPU)
 
 private:
+    mutable std::vector<std::unique_ptr<context>> _upload;    // one slot per member, see upload_context
+
     static void add_unique(std::vector<scalar_value_type> &out, const std::vector<std::vector<scalar_value_type>> &point_sets) {
         for (const auto &point_set : point_sets)
             for (const auto &point : point_set)

@@ -200,11 +200,23 @@ struct span_builder {
 template <typename Fr>
 struct stream_builder {
     toy_tree t;
-    void begin(std::size_t, std::size_t) { t = toy_tree(); }
-    void absorb(const Fr *leaves, std::size_t, std::size_t count) {
+    std::size_t total = 0, per_leaf = 0, absorbed = 0;
+    void begin(std::size_t total_elements, std::size_t elements_per_leaf) {
+        t = toy_tree();
+        total = total_elements, per_leaf = elements_per_leaf, absorbed = 0;
+    }
+    /// the slices arrive in leaf order, each a positive number of whole leaves, nothing twice and nothing skipped
+    void absorb(const Fr *leaves, std::size_t first, std::size_t count) {
+        EXPECT(first == absorbed);
+        EXPECT(count > 0);
+        EXPECT(per_leaf != 0 && count % per_leaf == 0);
+        absorbed += count;
         for (std::size_t i = 0; i < count; ++i) t.r ^= leaves[i].limbs[0];
     }
-    toy_tree finish() { return t; }
+    toy_tree finish() {
+        EXPECT(absorbed == total);
+        return t;
+    }
 };
 
 /// The batch rules every scheme has from the shared polys_evaluator (polys_evaluator.hpp), on a fresh scheme object.  The stub computes
