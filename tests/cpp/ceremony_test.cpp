@@ -2,7 +2,7 @@
 // (powers_of_tau.hpp) on an accumulator with the reference's five members, starting from the reference's initial one (every entry the
 // generator) and applying one key after the other; power_pairs / merge_pairs with the caller's random scalars as a vector and as a random
 // source; contribute_randomness (r1cs_gg_ppzksnark_mpc.hpp) on a keypair with the members transform_keypair touches.
-// Built into libceremonytest.so by tests/cpp/ceremony.mk; driven by tests/test_gpu_ceremony_shim.py.
+// Built into libceremonytest.so by tests/cpp/Makefile; driven by tests/test_gpu_ceremony_shim.py.
 #include <cstdint>
 #include <cstdio>
 #include <stdexcept>
@@ -12,7 +12,12 @@
 #include <nil/crypto3/zk/hip/powers_of_tau.hpp>
 #include <nil/crypto3/zk/hip/r1cs_gg_ppzksnark_mpc.hpp>
 
+#include "harness_common.hpp"
+
 using namespace nil::crypto3::zk::hip;
+using harness::list_random;
+using harness::read_points;
+using harness::write_points;
 
 namespace {
 
@@ -48,32 +53,6 @@ template <typename Curve>
 struct mpc_private_key {
     typename curve_adapter<Curve>::scalar_value_type delta;
 };
-
-template <typename Curve>
-struct list_random {
-    typedef curve_adapter<Curve> A;
-    const std::uint64_t *values;
-    std::size_t count, pos = 0;
-    typename A::scalar_value_type operator()() {
-        if (pos >= count) throw std::out_of_range("list_random: out of draws");
-        return A::scalar_from_limbs(values + 4 * pos++);
-    }
-};
-
-template <typename G>
-std::vector<G> read_points(const std::uint64_t *xy, const std::uint8_t *inf, std::size_t n) {
-    std::vector<G> v;
-    for (std::size_t i = 0; i < n; ++i) v.push_back(G::from_affine(xy + i * 2 * G::coord_limbs, inf && inf[i]));
-    return v;
-}
-/// -> the position behind what was written: 2 coordinates per point into xy, one flag into inf
-template <typename G>
-void write_points(const std::vector<G> &v, std::uint64_t *&xy, std::uint8_t *&inf) {
-    for (const G &g : v) {
-        *inf++ = g.to_affine(xy) ? 0 : 1;
-        xy += 2 * G::coord_limbs;
-    }
-}
 
 template <typename Curve>
 int transform_t(std::size_t length, const std::uint64_t *gen1, const std::uint64_t *gen2, const std::uint64_t *keys, std::size_t nkeys, std::uint64_t *xy,
@@ -115,11 +94,7 @@ int pairs_t(int mode, std::size_t n, const std::uint64_t *v_xy, const std::uint8
     write_points(std::vector<G> {res.first, res.second}, xy, inf);
     // lengths that do not belong together throw
     r.pop_back();
-    try {
-        (void)power_pairs<Curve, Group>(ctx, v, r);
-        return -42;
-    } catch (const std::invalid_argument &) {
-    }
+    if (!harness::throws_invalid([&] { (void)power_pairs<Curve, Group>(ctx, v, r); })) return -42;
     return ctx.device_status() == 0 ? 0 : -43;
 }
 
@@ -145,16 +120,6 @@ int mpc_t(std::size_t nh, std::size_t nl, const std::uint64_t *h_xy, const std::
     return ctx.device_status() == 0 ? 0 : -52;
 }
 
-template <typename Fn>
-int guarded(const char *what, Fn fn) {
-    try {
-        return fn();
-    } catch (const std::exception &e) {
-        fprintf(stderr, "%s: %s\n", what, e.what());
-        return -100;
-    }
-}
-
 }    // namespace
 
 extern "C" {
@@ -164,35 +129,35 @@ extern "C" {
 /// alpha_tau_powers_g1, beta_tau_powers_g1 (length each), beta_g2, one after the other (a G2 point takes twice the limbs of a G1 point)
 int ceremony_transform(int curve, std::size_t length, const std::uint64_t *gen1, const std::uint64_t *gen2, const std::uint64_t *keys, std::size_t nkeys,
                        std::uint64_t *xy, std::uint8_t *inf) {
-    return guarded("ceremony_transform", [&]() -> int {
+    return harness::guarded(__func__, [&] {
         if (curve == ZKHIP_BLS12_381) return transform_t<bls12_381>(length, gen1, gen2, keys, nkeys, xy, inf);
         if (curve == ZKHIP_BN254) return transform_t<alt_bn128_254>(length, gen1, gen2, keys, nkeys, xy, inf);
         return -2;
-    });
+    }, -100);
 }
 
 /// mode 0 / 1: power_pairs over the n points with the n - 1 scalars as a vector / drawn from a random source; 2 / 3: merge_pairs over the
 /// ranges [0, n - 1) and [1, n) likewise.  xy / inf: the two sums
 int ceremony_pairs(int curve, int group, int mode, std::size_t n, const std::uint64_t *v_xy, const std::uint8_t *v_inf, const std::uint64_t *scalars,
                    std::uint64_t *xy, std::uint8_t *inf) {
-    return guarded("ceremony_pairs", [&]() -> int {
+    return harness::guarded(__func__, [&] {
         if (curve == ZKHIP_BLS12_381 && group == ZKHIP_G1) return pairs_t<bls12_381, ZKHIP_G1>(mode, n, v_xy, v_inf, scalars, xy, inf);
         if (curve == ZKHIP_BLS12_381 && group == ZKHIP_G2) return pairs_t<bls12_381, ZKHIP_G2>(mode, n, v_xy, v_inf, scalars, xy, inf);
         if (curve == ZKHIP_BN254 && group == ZKHIP_G1) return pairs_t<alt_bn128_254, ZKHIP_G1>(mode, n, v_xy, v_inf, scalars, xy, inf);
         if (curve == ZKHIP_BN254 && group == ZKHIP_G2) return pairs_t<alt_bn128_254, ZKHIP_G2>(mode, n, v_xy, v_inf, scalars, xy, inf);
         return -2;
-    });
+    }, -100);
 }
 
 /// contribute_randomness on a keypair with H_query (nh points), L_query (nl points), delta_g1 and delta_g2 (the proving key's and the
 /// verification key's copy start equal).  xy / inf: H_query, L_query, delta_g1, the proving key's delta_g2, the verification key's delta_g2
 int ceremony_mpc(int curve, std::size_t nh, std::size_t nl, const std::uint64_t *h_xy, const std::uint8_t *h_inf, const std::uint64_t *l_xy, const std::uint8_t *l_inf,
                  const std::uint64_t *delta_g1, const std::uint64_t *delta_g2, const std::uint64_t *delta, std::uint64_t *xy, std::uint8_t *inf) {
-    return guarded("ceremony_mpc", [&]() -> int {
+    return harness::guarded(__func__, [&] {
         if (curve == ZKHIP_BLS12_381) return mpc_t<bls12_381>(nh, nl, h_xy, h_inf, l_xy, l_inf, delta_g1, delta_g2, delta, xy, inf);
         if (curve == ZKHIP_BN254) return mpc_t<alt_bn128_254>(nh, nl, h_xy, h_inf, l_xy, l_inf, delta_g1, delta_g2, delta, xy, inf);
         return -2;
-    });
+    }, -100);
 }
 
 }    // extern "C"

@@ -3,7 +3,7 @@
 // paths, leaf indices, the challenges the transcript handed out -- goes back to the Python driver, which holds it against the oracle and
 // hashlib.  The verifier is run here, on a scheme object of its own that has only what a verifier has, on the proof and on copies with one
 // thing changed each.
-// Built into libfriquerytest.so by tests/cpp/fri_query.mk; driven by tests/test_gpu_fri_query_shim.py and tests/test_host_fri_query.py.
+// Built into libfriquerytest.so by tests/cpp/Makefile; driven by tests/test_gpu_fri_query_shim.py and tests/test_host_fri_query.py.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -15,6 +15,8 @@
 #include <nil/crypto3/zk/hip/lpc.hpp>
 #include <nil/crypto3/zk/hip/merkle.hpp>
 #include <nil/crypto3/zk/hip/transcript.hpp>
+
+#include "harness_common.hpp"
 
 using namespace nil::crypto3::zk::hip;
 
@@ -471,14 +473,11 @@ int fq_lpc_run(int curve, int mode, const std::uint64_t *evals, std::size_t npol
                std::uint64_t *y, std::uint64_t *round_leaf, std::uint8_t *round_paths, std::uint64_t *round_polys, std::uint32_t *flags) {
     const run_io io = {evals, npolys, log_n, log_domain, steps, nsteps, points, script, nscript, lambda, grind_mask, seed, seed_len, roots, fri_roots, z, final_poly,
                        nonce, counts, drawn, init_values, init_leaf, init_paths, y, round_leaf, round_paths, round_polys, flags};
-    try {
+    return harness::guarded(__func__, [&]() -> int {
 #define CALL(C) lpc_run_mode<C>(mode, io)
         FQ_DISPATCH(curve, CALL);
 #undef CALL
-    } catch (const std::exception &e) {
-        fprintf(stderr, "fq_lpc_run: %s\n", e.what());
-        return -1;
-    }
+    });
 }
 
 int fq_refusals(int curve, const std::uint64_t *evals, std::size_t npolys, const std::uint64_t *log_n, std::size_t log_domain, const std::uint64_t *points,
@@ -488,14 +487,11 @@ int fq_refusals(int curve, const std::uint64_t *evals, std::size_t npolys, const
     run_io io = {};
     io.evals = evals, io.npolys = npolys, io.log_n = log_n, io.log_domain = log_domain, io.steps = steps, io.nsteps = 2, io.points = points, io.script = script,
     io.nscript = nscript, io.lambda = lambda, io.seed = &seed, io.seed_len = 1;
-    try {
+    return harness::guarded(__func__, [&]() -> int {
 #define CALL(C) refusals<C>(io, flags)
         FQ_DISPATCH(curve, CALL);
 #undef CALL
-    } catch (const std::exception &e) {
-        fprintf(stderr, "fq_refusals: %s\n", e.what());
-        return -1;
-    }
+    });
 }
 
 }    // extern "C"

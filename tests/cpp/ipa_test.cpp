@@ -2,7 +2,7 @@
 // polynomials, opens them, verifies the opening and then three tampered copies of it -- with a sponge that answers from a list and records
 // every call, a group map that returns a fixed point and a random source that hands out a list, all given by the Python driver, which
 // holds everything that comes back against tests/ipa_model.py.
-// Built into libipatest.so by tests/cpp/ipa.mk; driven by tests/test_gpu_ipa_shim.py.
+// Built into libipatest.so by tests/cpp/Makefile; driven by tests/test_gpu_ipa_shim.py.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -11,7 +11,10 @@
 
 #include <nil/crypto3/zk/hip/kimchi_pedersen.hpp>
 
+#include "harness_common.hpp"
+
 using namespace nil::crypto3::zk::hip;
+using harness::list_random;
 
 namespace {
 
@@ -59,17 +62,6 @@ struct fixed_group_map {
     typename curve_adapter<Curve>::g1_value_type u;
     template <typename T>
     typename curve_adapter<Curve>::g1_value_type to_group(const T &) const { return u; }
-};
-
-template <typename Curve>
-struct list_random {
-    typedef curve_adapter<Curve> A;
-    const std::uint64_t *values;
-    std::size_t count, pos = 0;
-    typename A::scalar_value_type operator()() {
-        if (pos >= count) throw std::out_of_range("list_random: out of draws");
-        return A::scalar_from_limbs(values + 4 * pos++);
-    }
 };
 
 struct ipa_io {
@@ -205,14 +197,11 @@ int ipa_run(int curve, const std::uint64_t *sizes, const std::uint64_t *g_xy, co
     const ipa_io io = {sizes[0], g_xy,   g_inf,  h_xy,     u_xy,     endo_r,   sizes[1],   poly_len, poly_bound, coeffs, sizes[2], elm,    scales,  evals,
                        draws,    sizes[3], answers, sizes[4], comm_xy, comm_inf, comm_count, blind,    lr_xy,      lr_inf, tail_xy,  tail_inf, z,     log,
                        counts,   sizes[5]};
-    try {
+    return harness::guarded(__func__, [&] {
         if (curve == ZKHIP_PALLAS) return ipa_run_t<pallas>(io);
         if (curve == ZKHIP_VESTA) return ipa_run_t<vesta>(io);
         return -2;
-    } catch (const std::exception &e) {
-        fprintf(stderr, "ipa_run: %s\n", e.what());
-        return -100;
-    }
+    }, -100);
 }
 
 }    // extern "C"

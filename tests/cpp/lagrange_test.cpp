@@ -2,7 +2,7 @@
 // params_type::add_lagrange_basis for two domain sizes (an evaluation_domain_hip and a plain struct with size() and omega, as the
 // reference's basic_radix2_domain offers them), lagrange_bases[n] handed back whole, the launches a repeated call makes, what throws, and
 // commitment_evaluations next to commitment over the coefficients the Python driver computed for the same column.
-// Built into liblagrangetest.so by tests/cpp/lagrange.mk; driven by tests/test_gpu_lagrange_shim.py.
+// Built into liblagrangetest.so by tests/cpp/Makefile; driven by tests/test_gpu_lagrange_shim.py.
 #include <cstdint>
 #include <cstdio>
 #include <stdexcept>
@@ -11,23 +11,16 @@
 #include <nil/crypto3/zk/hip/evaluation_domain.hpp>
 #include <nil/crypto3/zk/hip/kimchi_pedersen.hpp>
 
+#include "harness_common.hpp"
+
 using namespace nil::crypto3::zk::hip;
+using harness::list_random;
+using harness::throws_invalid;
 
 namespace {
 
 struct no_sponge { };
 struct no_group_map { };
-
-template <typename Curve>
-struct list_random {
-    typedef curve_adapter<Curve> A;
-    const std::uint64_t *values;
-    std::size_t count, pos = 0;
-    typename A::scalar_value_type operator()() {
-        if (pos >= count) throw std::out_of_range("list_random: out of draws");
-        return A::scalar_from_limbs(values + 4 * pos++);
-    }
-};
 
 /// what add_lagrange_basis reads of a domain, and nothing else
 template <typename Fr>
@@ -77,17 +70,8 @@ int lagrange_run_t(const std::uint64_t *sizes, const std::uint64_t *g_xy, const 
     for (std::size_t i = 0; i < small; ++i) small_inf[i] = A::point_to_affine_limbs(ls[i], small_xy + 8 * i) ? 0 : 1;
 
     // a domain larger than |g|, and one that is not a power of two: both throw and add nothing
-    counts[3] = counts[4] = 0;
-    try {
-        params.add_lagrange_basis(plain_domain<Fr> {2 * params.padded, A::scalar_from_limbs(omegas + 4)});
-    } catch (const std::invalid_argument &) {
-        counts[3] = 1;
-    }
-    try {
-        params.add_lagrange_basis(plain_domain<Fr> {small + 1, A::scalar_from_limbs(omegas + 4)});
-    } catch (const std::invalid_argument &) {
-        counts[4] = 1;
-    }
+    counts[3] = throws_invalid([&] { params.add_lagrange_basis(plain_domain<Fr> {2 * params.padded, A::scalar_from_limbs(omegas + 4)}); });
+    counts[4] = throws_invalid([&] { params.add_lagrange_basis(plain_domain<Fr> {small + 1, A::scalar_from_limbs(omegas + 4)}); });
     if (params.lagrange_bases.size() != 2) return -32;
 
     // the column: its evaluations over the big domain through the Lagrange bases, its coefficients through commitment (hiding: + w h)
@@ -102,12 +86,7 @@ int lagrange_run_t(const std::uint64_t *sizes, const std::uint64_t *g_xy, const 
     A::scalar_to_limbs(blind.unshifted[0], commit_xy + 16);
     counts[7] = random.pos;
     // a size that was not added
-    counts[8] = 0;
-    try {
-        (void)scheme::commitment_evaluations(params, std::vector<Fr>(2 * small, Fr::one()));
-    } catch (const std::invalid_argument &) {
-        counts[8] = 1;
-    }
+    counts[8] = throws_invalid([&] { (void)scheme::commitment_evaluations(params, std::vector<Fr>(2 * small, Fr::one())); });
     counts[9] = ctx.device_status();
     return 0;
 }
@@ -123,14 +102,11 @@ extern "C" {
 int lagrange_run(int curve, const std::uint64_t *sizes, const std::uint64_t *g_xy, const std::uint64_t *h_xy, const std::uint64_t *omegas, const std::uint64_t *evals,
                  const std::uint64_t *coeffs, const std::uint64_t *draws, std::uint64_t *big_xy, std::uint8_t *big_inf, std::uint64_t *small_xy, std::uint8_t *small_inf,
                  std::uint64_t *commit_xy, std::uint64_t *counts) {
-    try {
+    return harness::guarded(__func__, [&] {
         if (curve == ZKHIP_PALLAS) return lagrange_run_t<pallas>(sizes, g_xy, h_xy, omegas, evals, coeffs, draws, big_xy, big_inf, small_xy, small_inf, commit_xy, counts);
         if (curve == ZKHIP_VESTA) return lagrange_run_t<vesta>(sizes, g_xy, h_xy, omegas, evals, coeffs, draws, big_xy, big_inf, small_xy, small_inf, commit_xy, counts);
         return -2;
-    } catch (const std::exception &e) {
-        fprintf(stderr, "lagrange_run: %s\n", e.what());
-        return -100;
-    }
+    }, -100);
 }
 
 }    // extern "C"

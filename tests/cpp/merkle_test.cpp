@@ -1,7 +1,7 @@
 // C++ shim test harness (test-only) of the device Merkle builder: lpc_commitment_scheme_hip driven twice over the same inputs and the same
 // scripted challenges -- once with device_merkle_builder (hip/merkle.hpp: every tree hashed on the GPU), once with a host builder that keeps
 // the leaves it is handed -- so that Python can hash the captured leaves (hashlib) and hold the device roots against them.
-// Built into libmerkletest.so by tests/cpp/merkle.mk; driven by tests/test_gpu_merkle_shim.py.
+// Built into libmerkletest.so by tests/cpp/Makefile; driven by tests/test_gpu_merkle_shim.py.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -11,6 +11,8 @@
 
 #include <nil/crypto3/zk/hip/lpc.hpp>
 #include <nil/crypto3/zk/hip/merkle.hpp>
+
+#include "harness_common.hpp"
 
 using namespace nil::crypto3::zk::hip;
 
@@ -158,16 +160,13 @@ extern "C" {
 int merkle_lpc_run(int curve, int device, const uint64_t *evals, size_t npolys, const uint64_t *log_n, size_t log_domain, const uint64_t *steps, size_t nsteps,
                    const uint64_t *points, const uint64_t *challenges, size_t nchallenges, uint8_t *out_roots, uint8_t *out_fri_roots, uint64_t *out_z,
                    uint64_t *out_alphas, uint64_t *out_final, uint64_t *out_counts) {
-    try {
+    return harness::guarded(__func__, [&] {
         if (curve == ZKHIP_BLS12_381)
             return lpc_run_t<bls12_381>(device, evals, npolys, log_n, log_domain, steps, nsteps, points, challenges, nchallenges, out_roots, out_fri_roots, out_z,
                                         out_alphas, out_final, out_counts);
         return lpc_run_t<alt_bn128_254>(device, evals, npolys, log_n, log_domain, steps, nsteps, points, challenges, nchallenges, out_roots, out_fri_roots, out_z,
                                         out_alphas, out_final, out_counts);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "merkle_lpc_run: %s\n", e.what());
-        return -1;
-    }
+    });
 }
 
 size_t merkle_captured_count() { return g_captured.size(); }

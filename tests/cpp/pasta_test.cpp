@@ -3,7 +3,7 @@
 // (streaming and vector shaped) that hash with the library's own SHA2-256.  Everything a run produces goes back to the Python driver, which
 // holds it against the oracle and hashlib.  The placeholder argument classes are instantiated in full for both curves (compile coverage; their
 // kernels are driven through the C ABI by tests/test_gpu_pasta.py).
-// Built into libpastatest.so by tests/cpp/pasta.mk; driven by tests/test_host_pasta.py and tests/test_gpu_pasta_shim.py.
+// Built into libpastatest.so by tests/cpp/Makefile; driven by tests/test_host_pasta.py and tests/test_gpu_pasta_shim.py.
 #include <array>
 #include <cstdint>
 #include <cstdio>

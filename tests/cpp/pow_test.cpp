@@ -1,6 +1,6 @@
 // C++ shim test harness (test-only) of the proof of work: hip/transcript.hpp's sha256_transcript, hip/proof_of_work.hpp's proof_of_work_hip
 // and lpc_commitment_scheme_hip::proof_eval with and without fri_params.use_grinding.  Everything a run produces goes back to the Python
-// driver, which holds it against hashlib.  Built into libpowtest.so by tests/cpp/pow.mk; driven by tests/test_gpu_pow_shim.py.
+// driver, which holds it against hashlib.  Built into libpowtest.so by tests/cpp/Makefile; driven by tests/test_gpu_pow_shim.py.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>

@@ -29,6 +29,7 @@
 
 #include "eval_polys_case.hpp"
 #include "fr_vector_case.hpp"
+#include "harness_common.hpp"
 
 using namespace nil::crypto3::zk::hip;
 
@@ -2097,6 +2098,10 @@ int fr_vector_t(int what, const uint64_t *a, const uint64_t *b, size_t n, const 
     return fr_vector_case::run<Curve>(ctx, what, a, b, n, s, m, flag, out);
 }
 
+/// the body of an entry that takes a curve id: fn<curve>(...) under harness::guarded with the entry's own name
+#define CURVE_CALL(fn, ...) \
+    return harness::guarded(__func__, [&] { return curve == ZKHIP_BLS12_381 ? fn<bls12_381>(__VA_ARGS__) : fn<alt_bn128_254>(__VA_ARGS__); });
+
 extern "C" {
 
 int shim_host_small_poly(int curve, const uint64_t *xs, const uint64_t *ys, size_t k, const uint64_t *at, uint64_t *u_at, uint64_t *u_coeffs,
@@ -2127,13 +2132,10 @@ int shim_host_devices_from_env(int *out, int cap) {
 }
 /* members of the calling thread's default device group (ZKHIP_DEVICES), 0 when there is none, -1 when making it throws */
 int shim_default_group_size() {
-    try {
+    return harness::guarded(__func__, [] {
         const device_group *g = default_group();
         return g ? (int)g->size() : 0;
-    } catch (const std::exception &e) {
-        fprintf(stderr, "shim_default_group_size: %s\n", e.what());
-        return -1;
-    }
+    });
 }
 void shim_set_world(int world) { g_world = world < 1 ? 1 : world; }
 void shim_set_gpus(int gpus) { g_gpus = gpus < 1 ? 1 : gpus; }
@@ -2153,108 +2155,55 @@ int shim_groth16_prove(int curve, size_t M, size_t n, size_t N, const uint32_t *
                        uint64_t *proof) {
     const uint32_t *rp[3] = {rpa, rpb, rpc}, *cl[3] = {cla, clb, clc};
     const uint64_t *cf[3] = {cfa, cfb, cfc};
-    try {
-        if (curve == ZKHIP_BLS12_381)
-            return groth16_prove_t<bls12_381>(M, n, N, rp, cl, cf, a_query, a_inf, b_g, b_h, b_inf, h_query, h_count, l_query, fixed_g1, fixed_g2,
-                                              assignment, omega, coset, r, s, proof);
-        return groth16_prove_t<alt_bn128_254>(M, n, N, rp, cl, cf, a_query, a_inf, b_g, b_h, b_inf, h_query, h_count, l_query, fixed_g1, fixed_g2,
-                                              assignment, omega, coset, r, s, proof);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "shim_groth16_prove: %s\n", e.what());
-        return -1;
-    }
+    CURVE_CALL(groth16_prove_t, M, n, N, rp, cl, cf, a_query, a_inf, b_g, b_h, b_inf, h_query, h_count, l_query, fixed_g1, fixed_g2, assignment, omega, coset, r, s,
+               proof)
 }
 
 /// the same commit with scalar values in a foreign memory layout (upload_scalars' converting path)
 int shim_kzg_commit_foreign(int curve, const uint64_t *srs, size_t n, const uint64_t *evals, size_t log_n, size_t batch, const uint64_t *omega,
                             uint64_t *out, uint8_t *out_inf) {
-    try {
+    return harness::guarded(__func__, [&] {
         if (curve == ZKHIP_BLS12_381) return kzg_commit_t<foreign_scalar_curve<ZKHIP_BLS12_381>>(srs, n, evals, log_n, batch, omega, out, out_inf);
         return kzg_commit_t<foreign_scalar_curve<ZKHIP_BN254>>(srs, n, evals, log_n, batch, omega, out, out_inf);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "shim_kzg_commit_foreign: %s\n", e.what());
-        return -1;
-    }
+    });
 }
 
 int shim_kzg_commit(int curve, const uint64_t *srs, size_t n, const uint64_t *evals, size_t log_n, size_t batch, const uint64_t *omega,
                     uint64_t *out, uint8_t *out_inf) {
-    try {
-        if (curve == ZKHIP_BLS12_381) return kzg_commit_t<bls12_381>(srs, n, evals, log_n, batch, omega, out, out_inf);
-        return kzg_commit_t<alt_bn128_254>(srs, n, evals, log_n, batch, omega, out, out_inf);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "shim_kzg_commit: %s\n", e.what());
-        return -1;
-    }
+    CURVE_CALL(kzg_commit_t, srs, n, evals, log_n, batch, omega, out, out_inf)
 }
 
 int shim_kzg_v2_proof_eval(int curve, const uint64_t *srs, size_t n_srs, size_t npolys, const uint64_t *batch_id, const uint64_t *log_n,
                            const uint64_t *evals, const uint64_t *npts, const uint64_t *points, const uint64_t *roots, const uint64_t *theta,
                            const uint64_t *theta2, uint64_t *commits, uint64_t *zvals, uint64_t *pi, uint64_t *absorbed) {
-    try {
-        if (curve == ZKHIP_BLS12_381)
-            return kzg_v2_t<bls12_381>(srs, n_srs, npolys, batch_id, log_n, evals, npts, points, roots, theta, theta2, commits, zvals, pi, absorbed);
-        return kzg_v2_t<alt_bn128_254>(srs, n_srs, npolys, batch_id, log_n, evals, npts, points, roots, theta, theta2, commits, zvals, pi, absorbed);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "shim_kzg_v2_proof_eval: %s\n", e.what());
-        return -1;
-    }
+    CURVE_CALL(kzg_v2_t, srs, n_srs, npolys, batch_id, log_n, evals, npts, points, roots, theta, theta2, commits, zvals, pi, absorbed)
 }
 
 int shim_kzg_v1_proof_eval(int curve, const uint64_t *srs, size_t n_srs, const uint64_t *vk, size_t n_vk, size_t npolys, const uint64_t *batch_id,
                            const uint64_t *log_n, const uint64_t *evals, const uint64_t *npts, const uint64_t *points, const uint64_t *roots,
                            const uint64_t *gamma, const uint64_t *g2_poly, size_t g2_poly_len, uint64_t *commits, uint64_t *zvals, uint64_t *proof_out,
                            uint64_t *g2_out, uint64_t *absorbed) {
-    try {
-        if (curve == ZKHIP_BLS12_381)
-            return kzg_v1_t<bls12_381>(srs, n_srs, vk, n_vk, npolys, batch_id, log_n, evals, npts, points, roots, gamma, g2_poly, g2_poly_len, commits, zvals,
-                                       proof_out, g2_out, absorbed);
-        return kzg_v1_t<alt_bn128_254>(srs, n_srs, vk, n_vk, npolys, batch_id, log_n, evals, npts, points, roots, gamma, g2_poly, g2_poly_len, commits, zvals,
-                                       proof_out, g2_out, absorbed);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "shim_kzg_v1_proof_eval: %s\n", e.what());
-        return -1;
-    }
+    CURVE_CALL(kzg_v1_t, srs, n_srs, vk, n_vk, npolys, batch_id, log_n, evals, npts, points, roots, gamma, g2_poly, g2_poly_len, commits, zvals, proof_out, g2_out,
+               absorbed)
 }
 
 int shim_kzg_batched(int curve, const uint64_t *srs, size_t n_srs, size_t npolys, const uint64_t *lens, const uint64_t *coeffs, const uint64_t *npts,
                      const uint64_t *points, const uint64_t *gamma, uint64_t *commits, uint64_t *merged, uint64_t *n_merged, uint64_t *proof_out,
                      uint64_t *absorbed) {
-    try {
-        if (curve == ZKHIP_BLS12_381) return kzg_batched_t<bls12_381>(srs, n_srs, npolys, lens, coeffs, npts, points, gamma, commits, merged, n_merged, proof_out, absorbed);
-        return kzg_batched_t<alt_bn128_254>(srs, n_srs, npolys, lens, coeffs, npts, points, gamma, commits, merged, n_merged, proof_out, absorbed);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "shim_kzg_batched: %s\n", e.what());
-        return -1;
-    }
+    CURVE_CALL(kzg_batched_t, srs, n_srs, npolys, lens, coeffs, npts, points, gamma, commits, merged, n_merged, proof_out, absorbed)
 }
 
 int shim_kzg_reference_arity(int curve, const uint64_t *srs, size_t n_srs, const uint64_t *vk, size_t n_vk, const uint64_t *f, size_t n, const uint64_t *g,
                              size_t ng, int own_context, uint64_t *out_g1, uint64_t *out_g2) {
-    try {
-        if (curve == ZKHIP_BLS12_381) return kzg_reference_arity_t<bls12_381>(srs, n_srs, vk, n_vk, f, n, g, ng, own_context, out_g1, out_g2);
-        return kzg_reference_arity_t<alt_bn128_254>(srs, n_srs, vk, n_vk, f, n, g, ng, own_context, out_g1, out_g2);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "shim_kzg_reference_arity: %s\n", e.what());
-        return -1;
-    }
+    CURVE_CALL(kzg_reference_arity_t, srs, n_srs, vk, n_vk, f, n, g, ng, own_context, out_g1, out_g2)
 }
-
-#define CURVE_CALL(name, fn, ...)                                   \
-    try {                                                           \
-        if (curve == ZKHIP_BLS12_381) return fn<bls12_381>(__VA_ARGS__); \
-        return fn<alt_bn128_254>(__VA_ARGS__);                      \
-    } catch (const std::exception &e) {                             \
-        fprintf(stderr, name ": %s\n", e.what());                   \
-        return -1;                                                  \
-    }
 
 int shim_host_qap_exponents(int curve, size_t M, size_t n, size_t N, const uint32_t *rpa, const uint32_t *cla, const uint64_t *cfa, const uint32_t *rpb,
                             const uint32_t *clb, const uint64_t *cfb, const uint32_t *rpc, const uint32_t *clc, const uint64_t *cfc,
                             const uint64_t *assignment, const uint64_t *trap, const uint64_t *omega, const uint64_t *r, const uint64_t *s, uint64_t *out) {
     const uint32_t *rp[3] = {rpa, rpb, rpc}, *cl[3] = {cla, clb, clc};
     const uint64_t *cf[3] = {cfa, cfb, cfc};
-    CURVE_CALL("shim_host_qap_exponents", host_qap_exponents_t, M, n, N, rp, cl, cf, assignment, trap, omega, r, s, out)
+    CURVE_CALL(host_qap_exponents_t, M, n, N, rp, cl, cf, assignment, trap, omega, r, s, out)
 }
 
 int shim_groth16_generate_prove(int curve, size_t M, size_t n, size_t N, const uint32_t *rpa, const uint32_t *cla, const uint64_t *cfa,
@@ -2263,159 +2212,110 @@ int shim_groth16_generate_prove(int curve, size_t M, size_t n, size_t N, const u
                                 const uint64_t *r, const uint64_t *s, uint64_t *proof, double *ms) {
     const uint32_t *rp[3] = {rpa, rpb, rpc}, *cl[3] = {cla, clb, clc};
     const uint64_t *cf[3] = {cfa, cfb, cfc};
-    CURVE_CALL("shim_groth16_generate_prove", groth16_generate_prove_t, M, n, N, rp, cl, cf, assignment, trap, omega, coset, r, s, proof, ms)
+    CURVE_CALL(groth16_generate_prove_t, M, n, N, rp, cl, cf, assignment, trap, omega, coset, r, s, proof, ms)
 }
 
 int shim_precommit_leaves(int curve, const uint64_t *evals, size_t npolys, const uint64_t *log_n, size_t log_domain, size_t fri_step,
                           const uint64_t *roots, uint64_t *out) {
-    CURVE_CALL("shim_precommit_leaves", precommit_leaves_t, evals, npolys, log_n, log_domain, fri_step, roots, out)
+    CURVE_CALL(precommit_leaves_t, evals, npolys, log_n, log_domain, fri_step, roots, out)
 }
 
 int shim_lpc_commit_leaves(int curve, const uint64_t *evals, size_t npolys, const uint64_t *log_n, size_t log_domain, size_t fri_step, size_t slice, uint64_t *out) {
-    CURVE_CALL("shim_lpc_commit_leaves", lpc_commit_leaves_t, evals, npolys, log_n, log_domain, fri_step, slice, out)
+    CURVE_CALL(lpc_commit_leaves_t, evals, npolys, log_n, log_domain, fri_step, slice, out)
 }
 
 int shim_gate_argument(int curve, const uint64_t *evals, size_t ncols, size_t log_n, const uint64_t *degrees, const uint64_t *mask_evals, size_t mask_degree,
                        const uint64_t *roots, size_t nprod, const uint64_t *coeffs, const uint64_t *nfac, const int64_t *fac, size_t log_ext, int variant,
                        uint64_t *out, uint64_t *out_degree) {
-    CURVE_CALL("shim_gate_argument", gate_argument_t, evals, ncols, log_n, degrees, mask_evals, mask_degree, roots, nprod, coeffs, nfac, fac, log_ext, variant, out,
+    CURVE_CALL(gate_argument_t, evals, ncols, log_n, degrees, mask_evals, mask_degree, roots, nprod, coeffs, nfac, fac, log_ext, variant, out,
                out_degree)
 }
 int shim_lookup_input_flat(int curve, const uint64_t *evals, size_t ncols, size_t log_n, const uint64_t *degrees, const uint64_t *roots, size_t ncons,
                            const uint64_t *cons, const uint64_t *expr_monos, const uint64_t *mono_coeffs, const uint64_t *mono_nfac, const int64_t *fac,
                            const uint64_t *theta, uint64_t *out, uint64_t *out_sizes) {
-    CURVE_CALL("shim_lookup_input_flat", lookup_input_flat_t, evals, ncols, log_n, degrees, roots, ncons, cons, expr_monos, mono_coeffs, mono_nfac, fac, theta, out,
+    CURVE_CALL(lookup_input_flat_t, evals, ncols, log_n, degrees, roots, ncons, cons, expr_monos, mono_coeffs, mono_nfac, fac, theta, out,
                out_sizes)
 }
 int shim_dfs_ops(int curve, const uint64_t *a_evals, const uint64_t *b_evals, size_t log_n, size_t log_big, const uint64_t *roots, const uint64_t *alpha,
                  uint64_t *out_prod, uint64_t *out_round, uint64_t *out_addsub, uint64_t *out_fold) {
-    CURVE_CALL("shim_dfs_ops", dfs_ops_t, a_evals, b_evals, log_n, log_big, roots, alpha, out_prod, out_round, out_addsub, out_fold)
+    CURVE_CALL(dfs_ops_t, a_evals, b_evals, log_n, log_big, roots, alpha, out_prod, out_round, out_addsub, out_fold)
 }
 
 int shim_dfs_product_shift(int curve, const uint64_t *evals, size_t count, const uint64_t *log_n, const uint64_t *degrees, const uint64_t *roots,
                            int64_t shift, size_t shift_domain, uint64_t *out_prod, uint64_t *out_prod_size, uint64_t *out_shift, uint64_t *out_small) {
-    CURVE_CALL("shim_dfs_product_shift", dfs_product_shift_t, evals, count, log_n, degrees, roots, shift, shift_domain, out_prod, out_prod_size, out_shift,
+    CURVE_CALL(dfs_product_shift_t, evals, count, log_n, degrees, roots, shift, shift_domain, out_prod, out_prod_size, out_shift,
                out_small)
 }
 
 int shim_lpc_scheme(int curve, const uint64_t *evals, size_t npolys, const uint64_t *log_n, size_t log_domain, const uint64_t *steps, size_t nsteps,
                     const uint64_t *roots, const uint64_t *points, const uint64_t *challenges, size_t nchallenges, uint64_t *out_roots, uint64_t *out_z,
                     uint64_t *out_fri_roots, uint64_t *out_final, uint64_t *out_counts) {
-    CURVE_CALL("shim_lpc_scheme", lpc_scheme_t, evals, npolys, log_n, log_domain, steps, nsteps, roots, points, challenges, nchallenges, out_roots, out_z,
+    CURVE_CALL(lpc_scheme_t, evals, npolys, log_n, log_domain, steps, nsteps, roots, points, challenges, nchallenges, out_roots, out_z,
                out_fri_roots, out_final, out_counts)
 }
 
 int shim_eval_polys_case(int curve, const uint64_t *srs, size_t n_srs, const uint64_t *evals, const uint64_t *points, const uint64_t *challenges, uint64_t *out_kzg,
                          uint64_t *out_lpc) {
-    CURVE_CALL("shim_eval_polys_case", eval_polys_case_t, srs, n_srs, evals, points, challenges, out_kzg, out_lpc)
+    CURVE_CALL(eval_polys_case_t, srs, n_srs, evals, points, challenges, out_kzg, out_lpc)
 }
 
 /// fr_vector (hip/fr_vector.hpp) member by member: the cases and their buffers are fr_vector_case.hpp's
 int shim_fr_vector(int curve, int what, const uint64_t *a, const uint64_t *b, size_t n, const uint64_t *s, size_t m, int flag, uint64_t *out) {
-    CURVE_CALL("shim_fr_vector", fr_vector_t, what, a, b, n, s, m, flag, out)
+    CURVE_CALL(fr_vector_t, what, a, b, n, s, m, flag, out)
 }
 
 int shim_kzg_placeholder_contract(int curve, const uint64_t *srs, size_t n_srs, const uint64_t *evals, size_t npolys, size_t log_n, const uint64_t *roots,
                                   const uint64_t *points, const uint64_t *challenges, size_t nchallenges, uint64_t *out_blob_sizes, uint64_t *out_pi) {
-    CURVE_CALL("shim_kzg_placeholder_contract", kzg_placeholder_contract_t, srs, n_srs, evals, npolys, log_n, roots, points, challenges, nchallenges,
+    CURVE_CALL(kzg_placeholder_contract_t, srs, n_srs, evals, npolys, log_n, roots, points, challenges, nchallenges,
                out_blob_sizes, out_pi)
 }
 
 int shim_placeholder_sequence(int curve, const uint64_t *srs, size_t n_srs, const uint64_t *evals, size_t npolys, size_t log_n, size_t nw,
                               const uint64_t *roots, const uint64_t *challenge, const uint64_t *thetas, uint64_t *out, size_t out_cap, uint64_t *out_len) {
-    try {
-        if (curve == ZKHIP_BLS12_381) return placeholder_sequence_t<bls12_381>(srs, n_srs, evals, npolys, log_n, nw, roots, challenge, thetas, out, out_cap, out_len);
-        return placeholder_sequence_t<alt_bn128_254>(srs, n_srs, evals, npolys, log_n, nw, roots, challenge, thetas, out, out_cap, out_len);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "shim_placeholder_sequence: %s\n", e.what());
-        return -1;
-    }
+    CURVE_CALL(placeholder_sequence_t, srs, n_srs, evals, npolys, log_n, nw, roots, challenge, thetas, out, out_cap, out_len)
 }
 int shim_placeholder_quotient(int curve, const uint64_t *srs, size_t n_srs, const uint64_t *evals, size_t log_n, const uint64_t *roots, const uint64_t *theta,
                               const uint64_t *alphas, uint64_t *out_T, uint64_t *out_parts, uint64_t *out_commits) {
-    try {
-        if (curve == ZKHIP_BLS12_381) return placeholder_quotient_t<bls12_381>(srs, n_srs, evals, log_n, roots, theta, alphas, out_T, out_parts, out_commits);
-        return placeholder_quotient_t<alt_bn128_254>(srs, n_srs, evals, log_n, roots, theta, alphas, out_T, out_parts, out_commits);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "shim_placeholder_quotient: %s\n", e.what());
-        return -1;
-    }
+    CURVE_CALL(placeholder_quotient_t, srs, n_srs, evals, log_n, roots, theta, alphas, out_T, out_parts, out_commits)
 }
 int shim_placeholder_transcript_bls(const uint64_t *srs, size_t n_srs, const uint64_t *evals, size_t npolys, size_t log_n, size_t nw, const uint64_t *roots,
                                     const uint64_t *challenge, const uint64_t *thetas, uint64_t *out, size_t out_cap, uint64_t *out_len) {
-    try {
-        return placeholder_transcript_bls(srs, n_srs, evals, npolys, log_n, nw, roots, challenge, thetas, out, out_cap, out_len);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "shim_placeholder_transcript_bls: %s\n", e.what());
-        return -1;
-    }
+    return harness::guarded(__func__, [&] { return placeholder_transcript_bls(srs, n_srs, evals, npolys, log_n, nw, roots, challenge, thetas, out, out_cap, out_len); });
 }
 int shim_placeholder_permutation(int curve, const uint64_t *evals, size_t k, size_t log_n, const uint64_t *roots, const uint64_t *beta, const uint64_t *gamma,
                                  size_t chunks, const uint64_t *alphas, size_t n_alphas, size_t usable_rows, uint64_t *out_vp, uint64_t *out_F, uint64_t *out_sizes,
                                  uint64_t *out_parts) {
-    try {
-        if (curve == ZKHIP_BLS12_381)
-            return placeholder_permutation_t<bls12_381>(evals, k, log_n, roots, beta, gamma, chunks, alphas, n_alphas, usable_rows, out_vp, out_F, out_sizes, out_parts);
-        return placeholder_permutation_t<alt_bn128_254>(evals, k, log_n, roots, beta, gamma, chunks, alphas, n_alphas, usable_rows, out_vp, out_F, out_sizes, out_parts);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "shim_placeholder_permutation: %s\n", e.what());
-        return -1;
-    }
+    CURVE_CALL(placeholder_permutation_t, evals, k, log_n, roots, beta, gamma, chunks, alphas, n_alphas, usable_rows, out_vp, out_F, out_sizes, out_parts)
 }
 int shim_column_polynomials(int curve, const uint64_t *evals, size_t count, int kind, size_t m, const uint64_t *omega, const uint64_t *shift, uint64_t *out) {
-    CURVE_CALL("shim_column_polynomials", column_polynomials_t, evals, count, kind, m, omega, shift, out)
+    CURVE_CALL(column_polynomials_t, evals, count, kind, m, omega, shift, out)
 }
 int shim_placeholder_round(int curve, const uint64_t *srs, size_t n_srs, const uint64_t *evals, size_t k, size_t log_n, size_t usable_rows, const uint64_t *roots,
                            const uint64_t *challenges, uint64_t *out_T, uint64_t *out_commits) {
-    try {
-        if (curve == ZKHIP_BLS12_381) return placeholder_round_t<bls12_381>(srs, n_srs, evals, k, log_n, usable_rows, roots, challenges, out_T, out_commits);
-        return placeholder_round_t<alt_bn128_254>(srs, n_srs, evals, k, log_n, usable_rows, roots, challenges, out_T, out_commits);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "shim_placeholder_round: %s\n", e.what());
-        return -1;
-    }
+    CURVE_CALL(placeholder_round_t, srs, n_srs, evals, k, log_n, usable_rows, roots, challenges, out_T, out_commits)
 }
 int shim_placeholder_lookup(int curve, const uint64_t *evals, size_t k_in, const uint64_t *in_logs, size_t k_val, size_t log_n, size_t usable_rows, const uint64_t *roots,
                             const uint64_t *beta, const uint64_t *gamma, const uint64_t *alphas, const uint64_t *part_sizes, size_t n_parts, const uint64_t *part_alphas,
                             uint64_t *out_vl, uint64_t *out_F, uint64_t *out_sizes, uint64_t *out_parts) {
-    try {
-        if (curve == ZKHIP_BLS12_381)
-            return placeholder_lookup_t<bls12_381>(evals, k_in, in_logs, k_val, log_n, usable_rows, roots, beta, gamma, alphas, part_sizes, n_parts, part_alphas, out_vl,
-                                                   out_F, out_sizes, out_parts);
-        return placeholder_lookup_t<alt_bn128_254>(evals, k_in, in_logs, k_val, log_n, usable_rows, roots, beta, gamma, alphas, part_sizes, n_parts, part_alphas, out_vl,
-                                                   out_F, out_sizes, out_parts);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "shim_placeholder_lookup: %s\n", e.what());
-        return -1;
-    }
+    CURVE_CALL(placeholder_lookup_t, evals, k_in, in_logs, k_val, log_n, usable_rows, roots, beta, gamma, alphas, part_sizes, n_parts, part_alphas, out_vl, out_F,
+               out_sizes, out_parts)
 }
 int shim_kc_multiexp(int curve, const uint64_t *g_pts, const uint64_t *h_pts, const uint64_t *indices, size_t count, size_t domain_size, size_t min_idx,
                      size_t max_idx, const uint64_t *scalars, size_t nscalars, uint64_t *out_g, uint64_t *out_h, uint8_t *out_inf) {
-    CURVE_CALL("shim_kc_multiexp", kc_multiexp_t, g_pts, h_pts, indices, count, domain_size, min_idx, max_idx, scalars, nscalars, out_g, out_h, out_inf)
+    CURVE_CALL(kc_multiexp_t, g_pts, h_pts, indices, count, domain_size, min_idx, max_idx, scalars, nscalars, out_g, out_h, out_inf)
 }
 
 int shim_lagrange_g1(int curve, const uint64_t *powers, size_t m, const uint64_t *omega, uint64_t *out, uint8_t *out_inf) {
-    CURVE_CALL("shim_lagrange_g1", lagrange_g1_t, powers, m, omega, out, out_inf)
+    CURVE_CALL(lagrange_g1_t, powers, m, omega, out, out_inf)
 }
 
 int shim_groth16_prove_from_bytes(const uint8_t *blob, size_t size, const uint64_t *assignment, size_t n, size_t N, const uint64_t *omega,
                                   const uint64_t *coset, const uint64_t *r, const uint64_t *s, uint64_t *proof) {
-    try {
-        return groth16_prove_from_bytes_t<bls12_381>(blob, size, assignment, n, N, omega, coset, r, s, proof);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "shim_groth16_prove_from_bytes: %s\n", e.what());
-        return -1;
-    }
+    return harness::guarded(__func__, [&] { return groth16_prove_from_bytes_t<bls12_381>(blob, size, assignment, n, N, omega, coset, r, s, proof); });
 }
 
 int shim_kzg_basic_proof(int curve, const uint64_t *srs, size_t n_srs, const uint64_t *coeffs, size_t n, const uint64_t *z, uint64_t *out) {
-    try {
-        if (curve == ZKHIP_BLS12_381) return kzg_basic_proof_t<bls12_381>(srs, n_srs, coeffs, n, z, out);
-        return kzg_basic_proof_t<alt_bn128_254>(srs, n_srs, coeffs, n, z, out);
-    } catch (const std::exception &e) {
-        fprintf(stderr, "shim_kzg_basic_proof: %s\n", e.what());
-        return -1;
-    }
+    CURVE_CALL(kzg_basic_proof_t, srs, n_srs, coeffs, n, z, out)
 }
 
 }    // extern "C"

@@ -9,6 +9,7 @@ permutation and lookup arguments on vectors of any length, the gate argument's f
 1 .. 5 members and every transport, and for Pallas and Vesta (ids 2 and 3: G1 and the scalar field only) the MSM, the NTT and the generator fold of the
 inner-product argument -- and compares bit for bit.  Every leg runs once before the random draws start, so every counter is positive whatever the seed.  Exit code 0 and a JSON line with the counts = no difference."""
 import argparse
+import functools
 import json
 import os
 import sys
@@ -22,6 +23,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import bench  # noqa: E402
 import cport as cp  # noqa: E402
+import harness  # noqa: E402
 import pasta_util as pu  # noqa: E402  (ids 2 and 3 in util.CURVES)
 import pyoracle as po  # noqa: E402
 from util import CURVES, limbs, qap_domains  # noqa: E402
@@ -189,22 +191,23 @@ def fuzz_witness(zk, ctx, rng, stats):
     stats["witness_map"] += 1
 
 
-_SHIM = {}
 SCALE = 1    # --scale: multiplies the size ranges (16: MSMs up to 96 000 points, NTTs up to 2^17, domains up to 320 000, witness maps up to 80 000 constraints)
+
+
+@functools.lru_cache(maxsize=None)
+def _shim():
+    return harness.library("libshimtest.so")
 
 
 def fuzz_proof(zk, ctx, rng, stats):
     """one whole Groth16 proof through the header-only shim (key from the oracle's generator, uploaded; prover on the device) against the
     oracle's prover -- random constraint count, input count, curve, evaluation domain (the reference's choice or the basic one)"""
-    import ctypes
     import test_gpu_shim as tgs
 
-    if "lib" not in _SHIM:
-        _SHIM["lib"] = ctypes.CDLL(os.path.join(ROOT, "tests", "cpp", "libshimtest.so"))
     curve, M, nin = int(rng.integers(0, 2)), int(rng.integers(13, 3000)), int(rng.integers(1, 12))
     domain = "ref" if rng.random() < 0.7 else "basic"
     try:
-        tgs._groth16_prover_shim(_SHIM["lib"], curve, M, nin, domain)
+        tgs._groth16_prover_shim(_shim(), curve, M, nin, domain)
     except AssertionError:
         raise SystemExit("Groth16 proof differs: curve %d M %d n %d domain %s" % (curve, M, nin, domain))
     del tgs._KEEP[:]
@@ -417,9 +420,7 @@ def fuzz_lpc_group(zk, ctx, rng, stats):
     import ctypes
     import torch
 
-    if "lib" not in _SHIM:
-        _SHIM["lib"] = ctypes.CDLL(os.path.join(ROOT, "tests", "cpp", "libshimtest.so"))
-    shim = _SHIM["lib"]
+    shim = _shim()
     curve = int(rng.integers(0, 2))
     C = CURVES[curve]
     log_domain = int(rng.integers(2, 13))
@@ -461,9 +462,7 @@ def fuzz_kzg_group(zk, ctx, rng, stats):
     import torch
     import test_gpu_shim as tgs
 
-    if "lib" not in _SHIM:
-        _SHIM["lib"] = ctypes.CDLL(os.path.join(ROOT, "tests", "cpp", "libshimtest.so"))
-    shim = _SHIM["lib"]
+    shim = _shim()
     curve = int(rng.integers(0, 2))
     r = CURVES[curve].r
     log_n = int(rng.integers(3, 10))

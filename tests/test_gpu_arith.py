@@ -11,12 +11,12 @@ import pytest
 
 import arith_cases as ac
 import pyoracle as po
+from harness import library
 from util import CURVES, FQ_LIMBS, jac_to_affine_py, pt_from_limbs, pts_arr
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV_SO = os.path.join(ROOT, "tests", "cpp", "libarithdev.so")
 HOST_SO = os.path.join(ROOT, "crypto3-zk_amd", "libzkhip_hosttest.so")
 RECODE_STRIDE = 130
 P = ac._ptr
@@ -24,8 +24,7 @@ P = ac._ptr
 
 @pytest.fixture(scope="module")
 def dev():
-    assert os.path.exists(DEV_SO), "tests/cpp/libarithdev.so is missing: python -c 'import __graft_entry__ as g; g.build()'"
-    return ctypes.CDLL(DEV_SO)
+    return library("libarithdev.so")
 
 
 @pytest.fixture(scope="module")

@@ -1,5 +1,5 @@
 """The setup ceremonies of the shim over the stand-in `bls12_381` / `alt_bn128_254` types on the GPU, driven through
-tests/cpp/ceremony_test.cpp -> libceremonytest.so (tests/cpp/ceremony.mk):
+tests/cpp/ceremony_test.cpp -> libceremonytest.so (a target of tests/cpp/Makefile):
 
   transform_accumulator  (hip/powers_of_tau.hpp; powers_of_tau_accumulator::transform, accumulator.hpp:89-121) from the reference's initial
                          accumulator -- every entry the generator -- so that after one key the entries are tau^i G1, tau^i G2, alpha tau^i G1,
@@ -10,30 +10,23 @@ tests/cpp/ceremony_test.cpp -> libceremonytest.so (tests/cpp/ceremony.mk):
 
 Every expected point is the oracle's multiple of the generator by the exponent computed here with Python integers."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import arith_cases as ac
 import cport as cp
+from harness import library
 from util import CURVES, FQ_LIMBS, fr_arr, fr_ints
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = ac._ptr
 Z = ctypes.c_size_t
 
 
 @pytest.fixture(scope="module")
 def harness():
-    d = os.path.join(ROOT, "tests", "cpp")
-    so = os.path.join(d, "libceremonytest.so")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(os.path.join(d, "ceremony_test.cpp")):
-        subprocess.check_call(["make", "-C", d, "-f", "ceremony.mk", "libceremonytest.so"])
-    return ctypes.CDLL(so)
+    return library("libceremonytest.so")
 
 
 def multiples(curve, group, exps):

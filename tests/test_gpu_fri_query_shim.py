@@ -1,13 +1,11 @@
 """Whole LPC opening proofs from the shim: lpc_commitment_scheme_hip::proof_eval_full (proof_eval, then the query phase answered on the
-device) and verify_eval, through tests/cpp/fri_query_test.cpp -> libfriquerytest.so (tests/cpp/fri_query.mk).
+device) and verify_eval, through tests/cpp/fri_query_test.cpp -> libfriquerytest.so (a target of tests/cpp/Makefile).
 
 Held against things the product does not compute: the query indices against a table of the domain, the initial values against the committed
 polynomials extended with the oracle's NTT (cport.ntt) at the restated calculate_s indices (fri_query_ref), every y against the round
 polynomial the commit phase kept, the last y against big-integer Horner over the final polynomial, and every path -- values put into leaf
 order, hashed with hashlib -- against the batch root or the round's root.  Every comparison is bit-exact."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,21 +15,17 @@ import fri_query_ref as fq
 import merkle_ref as mr
 import pasta_util  # noqa: F401  (adds Pallas and Vesta to util.CURVES)
 import pyoracle as po
+from harness import library
 from util import CURVES, fr_arr, fr_ints, limbs
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LAMBDA = 5
 DEVICE, HOST, HOST_GROUP = 0, 1, 2
 
 
 @pytest.fixture(scope="module")
 def harness():
-    d = os.path.join(ROOT, "tests", "cpp")
-    so = os.path.join(d, "libfriquerytest.so")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(os.path.join(d, "fri_query_test.cpp")):
-        subprocess.check_call(["make", "-C", d, "-f", "fri_query.mk"])
-    return ctypes.CDLL(so)
+    return library("libfriquerytest.so")
 
 
 def P(a):

@@ -200,10 +200,11 @@ def test_default_group_from_the_environment(value, expect):
     import subprocess
     import sys
 
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    import harness
+
     code = ("import ctypes, torch\n"
             "s = ctypes.CDLL(%r)\n"
-            "print('sizes', s.shim_default_group_size(), s.shim_default_group_size())\n") % os.path.join(root, "tests", "cpp", "libshimtest.so")
+            "print('sizes', s.shim_default_group_size(), s.shim_default_group_size())\n") % harness.path("libshimtest.so")
     env = dict(os.environ, ZKHIP_DEVICES=value)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -1,23 +1,18 @@
 """kimchi_pedersen_hip (crypto3-zk_amd/include/nil/crypto3/zk/hip/kimchi_pedersen.hpp) over the stand-in `pallas` / `vesta` types on the
-GPU, driven through tests/cpp/ipa_test.cpp -> libipatest.so (tests/cpp/ipa.mk) with a sponge that answers from a list, a fixed group map
+GPU, driven through tests/cpp/ipa_test.cpp -> libipatest.so (a target of tests/cpp/Makefile) with a sponge that answers from a list, a fixed group map
 and a list of draws: commitments, blinders and every part of the opening proof against the Python model (tests/ipa_model.py), the sponge
 calls and the draws in the model's number and order, the device's proof in the model's verifier equation, and the shim's own verify_eval
 on the proof and on three changed copies of it."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import arith_cases as ac
 import ipa_model as im
 import pasta_util as pu
+from harness import library
 from util import fr_arr, fr_ints, limbs, pt_from_limbs, pts_arr
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = ac._ptr
 KINDS = {0: "absorb_fr", 1: "challenge_fq", 2: "absorb_g", 3: "squeeze_challenge"}
 ENDO_R = 5
@@ -25,11 +20,7 @@ ENDO_R = 5
 
 @pytest.fixture(scope="module")
 def harness():
-    d = os.path.join(ROOT, "tests", "cpp")
-    so = os.path.join(d, "libipatest.so")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(os.path.join(d, "ipa_test.cpp")):
-        subprocess.check_call(["make", "-C", d, "-f", "ipa.mk", "libipatest.so"])
-    return ctypes.CDLL(so)
+    return library("libipatest.so")
 
 
 def u64(n, *shape):

@@ -1,5 +1,5 @@
 """The inner pairing product commitments of the shim (hip/kzg_ipp2.hpp) over the stand-in `bls12_381` types on the GPU, driven through
-tests/cpp/ipp2_test.cpp -> libipp2test.so (tests/cpp/ipp2.mk):
+tests/cpp/ipp2_test.cpp -> libipp2test.so (a target of tests/cpp/Makefile):
 
   kzg_ipp2_hip::single / ::pair  reproduce the reference's vectors (tests/golden/ref_ipp2_kat.json) through the shim's types -- keys built from
                                  the scalar powers on the device or from host values, the committed vectors as host values and as resident bases;
@@ -7,20 +7,17 @@ tests/cpp/ipp2_test.cpp -> libipp2test.so (tests/cpp/ipp2.mk):
   has_correct_len                every length mismatch throws std::invalid_argument, matching lengths do not."""
 import ctypes
 import json
-import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
 import pairing_ref as pr
+from harness import library
 from test_gpu_pairing import fq_limbs, fr_arr, gt_ints
 from test_pairing_ref import KAT
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 Z = ctypes.c_size_t
 ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)
 H = lambda s: int(s, 16)
@@ -28,11 +25,7 @@ H = lambda s: int(s, 16)
 
 @pytest.fixture(scope="module")
 def harness():
-    d = os.path.join(ROOT, "tests", "cpp")
-    so = os.path.join(d, "libipp2test.so")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(os.path.join(d, "ipp2_test.cpp")):
-        subprocess.check_call(["make", "-C", d, "-f", "ipp2.mk", "libipp2test.so"])
-    return ctypes.CDLL(so)
+    return library("libipp2test.so")
 
 
 @pytest.fixture(scope="module")

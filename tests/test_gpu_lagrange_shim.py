@@ -1,34 +1,25 @@
 """The Lagrange-basis SRS of kimchi_pedersen_hip (crypto3-zk_amd/include/nil/crypto3/zk/hip/kimchi_pedersen.hpp: params_type::
 add_lagrange_basis, lagrange_bases, commitment_evaluations) over the stand-in `pallas` / `vesta` types on the GPU, driven through
-tests/cpp/lagrange_test.cpp -> liblagrangetest.so (tests/cpp/lagrange.mk).  |g| = 2^9 generators k_i G, domains of 2^9 and 2^5 points:
+tests/cpp/lagrange_test.cpp -> liblagrangetest.so (a target of tests/cpp/Makefile).  |g| = 2^9 generators k_i G, domains of 2^9 and 2^5 points:
 every entry of both bases against the oracle (its inverse NTT of the k_i in the exponent), no launch when a size is added again, what
 throws, and the commitment of a column from its evaluations against the oracle's sum over the basis and against `commitment` of the
 column's coefficients minus its blinding term."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import arith_cases as ac
 import cport as cp
 import pasta_util as pu
+from harness import library
 from util import fr_arr, fr_ints, limbs, pt_from_limbs, pts_arr
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = ac._ptr
 
 
 @pytest.fixture(scope="module")
 def harness():
-    d = os.path.join(ROOT, "tests", "cpp")
-    so = os.path.join(d, "liblagrangetest.so")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(os.path.join(d, "lagrange_test.cpp")):
-        subprocess.check_call(["make", "-C", d, "-f", "lagrange.mk", "liblagrangetest.so"])
-    return ctypes.CDLL(so)
+    return library("liblagrangetest.so")
 
 
 def basis(curve, ks, log_m):

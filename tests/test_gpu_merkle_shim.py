@@ -1,10 +1,8 @@
 """lpc_commitment_scheme_hip with the device tree builder (hip/merkle.hpp: device_merkle_builder, SHA2-256 on the GPU) against the same
 scheme with a host builder that keeps the leaves it is handed: Python hashes the captured leaves with hashlib, and the commit roots and every
 FRI round root must be those; the evaluations, the FRI alphas and the final polynomial must not depend on who hashes.
-Harness: tests/cpp/merkle_test.cpp -> libmerkletest.so (tests/cpp/merkle.mk)."""
+Harness: tests/cpp/merkle_test.cpp -> libmerkletest.so (a target of tests/cpp/Makefile)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,19 +10,15 @@ import pytest
 import cport as cp
 import merkle_ref as mr
 import pyoracle as po
+from harness import library
 from util import CURVES, fr_arr
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def harness():
-    d = os.path.join(ROOT, "tests", "cpp")
-    so = os.path.join(d, "libmerkletest.so")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(os.path.join(d, "merkle_test.cpp")):
-        subprocess.check_call(["make", "-C", d, "-f", "merkle.mk"])
-    lib = ctypes.CDLL(so)
+    lib = library("libmerkletest.so")
     for f in (lib.merkle_captured_count, lib.merkle_captured_elements, lib.merkle_captured_per_leaf):
         f.restype = ctypes.c_size_t
     lib.merkle_captured_elements.argtypes = lib.merkle_captured_per_leaf.argtypes = [ctypes.c_size_t]

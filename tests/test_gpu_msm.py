@@ -9,6 +9,7 @@ import pytest
 import cport as cp
 import pasta_util  # noqa: F401  (ids 2 and 3 in util.CURVES)
 import pyoracle as po
+from harness import program
 from util import CURVES, fr_arr, fr_ints, jac_to_affine_py, limbs, pt_from_limbs, pt_limbs, pts_arr, qap_domains
 
 pytestmark = pytest.mark.gpu
@@ -404,9 +405,7 @@ def test_tail_group_law_over_lane_pairs_and_quads(ctx):
     addition, doubling, small multiples, both base fields (tests/cpp/quadtest.hip, a device-only unit test)"""
     import subprocess
 
-    exe = os.path.join(os.path.dirname(HERE), "tests", "cpp", "quadtest")
-    assert os.path.exists(exe), "tests/cpp/quadtest is missing: python -c 'import __graft_entry__ as g; g.build()'"
-    out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300, text=True)
+    out = subprocess.run([program("quadtest")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300, text=True)
     assert out.returncode == 0 and out.stdout.count("mismatch mask 0x0 ") == 2, out.stdout
 
 

@@ -6,14 +6,13 @@ tests/cpp/scantest.hip runs the scan primitive by itself; tests/cpp/entries_late
 of the three tile shapes, the two-launch scans, the merged plan, narrow super-buckets, and compares two runs of one input.  Each
 program runs once; the tests below read their parts of its output.  The MSMs over the same shapes are compared with the oracle as in
 test_gpu_msm.py."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import cport as cp
-from test_gpu_msm_entries import ROOT
+from harness import program
 
 pytestmark = pytest.mark.gpu
 SIZES = (1, 63, 64, 65, 1023, 1025, 2 ** 13 - 1, 2 ** 13 + 1, 2 ** 14 + 1)
@@ -22,9 +21,7 @@ N = 3000  # points of the MSMs below: above the 128-entry split threshold when a
 
 
 def run_program(name):
-    exe = os.path.join(ROOT, "tests", "cpp", name)
-    assert os.path.exists(exe), "tests/cpp/%s is missing: python -c 'import __graft_entry__ as g; g.build()'" % name
-    out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300, text=True)
+    out = subprocess.run([program(name)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300, text=True)
     return out.returncode, out.stdout
 
 

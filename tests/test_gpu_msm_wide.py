@@ -2,7 +2,6 @@
 msm_wide_final): the law itself against the one-lane formulas (tests/cpp/widetest.hip), and MSM results with it (msm_tail_quads = 1, the
 default) against the same call on the lane quads (msm_tail_quads = 2) and against the oracle -- bit-exact after the conversion to affine.
 msm_tail_fold is lowered so that 2^10 ... 2^13 points go through msm_fold and level 2; the profile tells which kernels ran."""
-import os
 import subprocess
 
 import numpy as np
@@ -10,19 +9,17 @@ import pytest
 
 import cport as cp
 import pasta_util  # noqa: F401  (ids 2 and 3 in util.CURVES)
+from harness import program
 from util import CURVES, fr_arr, jac_to_affine_py, pt_from_limbs
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WIDE, QUADS = 1, 2    # values of msm_tail_quads
 
 
 def test_wide_group_law_unit(ctx):
     """product, sum, difference (limb for limb, at the limb bounds too), addition, doubling, small multiple, a chain of 64 operations, P + P,
     P + (-P), infinity on either side, coordinates 0 / 1 / p - 1, the load / store layout: BLS12-381, BN254, Pallas and Vesta base fields"""
-    exe = os.path.join(ROOT, "tests", "cpp", "widetest")
-    assert os.path.exists(exe), "tests/cpp/widetest is missing: python -c 'import __graft_entry__ as g; g.build()'"
-    out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300, text=True)
+    out = subprocess.run([program("widetest")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300, text=True)
     assert out.returncode == 0 and out.stdout.count("mismatch mask 0x0 ") == 4, out.stdout
 
 

@@ -13,13 +13,13 @@ import arith_cases as ac
 import merkle_ref as mr
 import pasta_util as pu
 import pyoracle as po
+from harness import library
 from test_host_pasta import check_chains, check_recoding
 from util import fr_arr, fr_ints, jac_to_affine_py, limbs, lookup_instance, permutation_instance, pt_from_limbs, pt_limbs, pts_arr, qap_domains
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV_SO = os.path.join(ROOT, "tests", "cpp", "libarithdev_pasta.so")
 HOST_SO = os.path.join(ROOT, "crypto3-zk_amd", "libzkhip_hosttest.so")
 RECODE_STRIDE = 130
 P = ac._ptr
@@ -28,8 +28,7 @@ INVALID = -2
 
 @pytest.fixture(scope="module")
 def dev():
-    assert os.path.exists(DEV_SO), "tests/cpp/libarithdev_pasta.so is missing: python -c 'import __graft_entry__ as g; g.build()'"
-    return ctypes.CDLL(DEV_SO)
+    return library("libarithdev_pasta.so")
 
 
 @pytest.fixture(scope="module")

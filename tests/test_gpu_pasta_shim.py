@@ -1,4 +1,4 @@
-"""The header-only shim over `pallas` / `vesta` on the GPU (tests/cpp/pasta_test.cpp -> libpastatest.so, tests/cpp/pasta.mk):
+"""The header-only shim over `pallas` / `vesta` on the GPU (tests/cpp/pasta_test.cpp -> libpastatest.so, a target of tests/cpp/Makefile):
 lpc_commitment_scheme_hip over a sha256_transcript with grinding -- device tree builder, streaming and vector host builders -- against
 po.lpc_proof_eval with the transcript replayed by hashlib, every Merkle root against tests/merkle_ref.py and the nonce against
 tests/pow_ref.py; multiexp<multiexp_method_hip> on G1 against the oracle.

@@ -1,16 +1,16 @@
 """The shim's side of FRI's proof of work: sha256_transcript (hip/transcript.hpp), proof_of_work_hip (hip/proof_of_work.hpp) and
 lpc_commitment_scheme_hip::proof_eval with and without fri_params.use_grinding, against hashlib: Python replays every transcript from the
-roots a run returns.  Harness: tests/cpp/pow_test.cpp -> libpowtest.so (tests/cpp/pow.mk)."""
+roots a run returns.  Harness: tests/cpp/pow_test.cpp -> libpowtest.so (a target of tests/cpp/Makefile)."""
 import ctypes
 import hashlib
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import cport as cp
 import pyoracle as po
+from harness import library
 from pow_ref import cand, first_hit
 from util import fr_arr
 
@@ -21,11 +21,7 @@ H = lambda b: hashlib.sha256(b).digest()  # noqa: E731
 
 @pytest.fixture(scope="module")
 def harness():
-    d = os.path.join(ROOT, "tests", "cpp")
-    so = os.path.join(d, "libpowtest.so")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(os.path.join(d, "pow_test.cpp")):
-        subprocess.check_call(["make", "-C", d, "-f", "pow.mk"])
-    return ctypes.CDLL(so)
+    return library("libpowtest.so")
 
 
 def P(a):

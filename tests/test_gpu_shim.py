@@ -3,27 +3,21 @@
 driven with inputs from the oracle and compared bit-for-bit with the oracle's proof / commitments.
 BASELINE config 1 (Groth16 on alt_bn128, 2^10 constraints) runs here with the MSM / NTT on the GPU."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import cport as cp
 import pyoracle as po
+from harness import library
 from util import CURVES, FQ_LIMBS, fr_arr, fr_ints, limbs, lookup_instance, permutation_instance, pt_limbs
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def shim():
-    so = os.path.join(ROOT, "tests", "cpp", "libshimtest.so")
-    srcs = [os.path.join(ROOT, "tests", "cpp", f) for f in ("shim_test.cpp", "arguments_test.cpp")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in srcs):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "cpp")])
-    return ctypes.CDLL(so)
+    return library("libshimtest.so")
 
 
 _KEEP = []

@@ -1,8 +1,6 @@
 """Host side of the FRI query phase, no GPU: the tests' restatement of calculate_s (fri_query_ref) against the oracle's leaf layout, and the
 shim's host arithmetic -- detail::pair_positions and detail::domain_index (hip/lpc.hpp) -- through tests/cpp/fri_query_test.cpp."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -10,18 +8,13 @@ import pytest
 import fri_query_ref as fq
 import pasta_util  # noqa: F401  (adds Pallas and Vesta to util.CURVES)
 import pyoracle as po
+from harness import library
 from util import CURVES, limbs
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def harness():
-    d = os.path.join(ROOT, "tests", "cpp")
-    so = os.path.join(d, "libfriquerytest.so")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(os.path.join(d, "fri_query_test.cpp")):
-        subprocess.check_call(["make", "-C", d, "-f", "fri_query.mk"])
-    return ctypes.CDLL(so)
+    return library("libfriquerytest.so")
 
 
 def test_restated_walk_is_a_leaf_of_the_oracle():

@@ -13,6 +13,7 @@ import pytest
 import arith_cases as ac
 import pasta_util as pu
 import pyoracle as po
+from harness import library
 from util import fr_arr, jac_to_affine_py, limbs, pt_from_limbs, pt_limbs, pts_arr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,11 +30,7 @@ def shim():
 
 @pytest.fixture(scope="module")
 def harness():
-    d = os.path.join(ROOT, "tests", "cpp")
-    so = os.path.join(d, "libpastatest.so")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(os.path.join(d, "pasta_test.cpp")):
-        subprocess.check_call(["make", "-C", d, "-f", "pasta.mk", "libpastatest.so"])
-    return ctypes.CDLL(so)
+    return library("libpastatest.so")
 
 
 def _u32(v, n32=8):

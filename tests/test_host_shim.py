@@ -4,25 +4,19 @@ lines use on the host (prover.hpp:142-155), and the query slices of the sharded 
 oracle.  (tests/cpp/libshimtest.so links libzkhip.so but these entry points never touch the device.)"""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import cport as cp
 import pyoracle as po
+from harness import library
 from util import CURVES, fr_arr, fr_ints, limbs, pt_from_limbs, pt_limbs
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def shim():
-    so = os.path.join(ROOT, "tests", "cpp", "libshimtest.so")
-    src = os.path.join(ROOT, "tests", "cpp", "shim_test.cpp")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "cpp")])
-    return ctypes.CDLL(so)
+    return library("libshimtest.so")
 
 
 def P(a):
