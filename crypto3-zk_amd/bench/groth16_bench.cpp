@@ -171,15 +171,13 @@ int groth16_bench_t(int device, size_t rank, size_t world, all_gather_fn all_gat
        (msm_bucket_large 2.98 ms for empty launches), which distorted every share computed from it. */
     if (prof && prof_cap && !(g_partial_only && world > 1) && !g_gather_dev && !all_gather) {
         const bool was = dpk.overlap_g2;
-        auto side = std::move(dpk.side);    // without its second context the key's G2 multiexp runs on the main stream (process() looks at `side`)
-        dpk.overlap_g2 = false;
+        dpk.overlap_g2 = false;    // the key's G2 multiexp runs on the main stream (g2_context())
         (void)prover::process(dpk, primary, auxiliary, r, s);    // settle the serial arrangement, unprofiled
         zkhip_profile_enable(ctx.get(), 1);
         auto pv = prover::process(dpk, primary, auxiliary, r, s);
         zkhip_profile_dump(ctx.get(), prof, prof_cap);
         zkhip_profile_enable(ctx.get(), 0);
         dpk.overlap_g2 = was;
-        dpk.side = std::move(side);
         if (!(pv.g_A == first.g_A && pv.g_B == first.g_B && pv.g_C == first.g_C)) ++differing;
     }
     /* the throughput arrangement: g_lanes provers at once over the SAME resident key (lane keys alias its queries), one host thread each */

@@ -258,12 +258,34 @@ struct query_shard {
 /// delta_g2, A_query, B_query.{indices, values[i].{g, h}, domain_size_}, H_query, L_query, constraint_system -- a key
 /// object of the reference is consumed where it lies (its group / field values go through curve_adapter), the shim's
 /// own r1cs_gg_ppzksnark_proving_key is just the default.
+/// What a caller may tune on a device key before its first proof; a lane key inherits all of it.
+struct r1cs_gg_ppzksnark_tunables {
+    /// evaluation_At, evaluation_Bt.h and evaluation_Lt multiply by the SAME assignment vector (prover.hpp:108-139): with the three
+    /// queries laid out over the same N + 1 rows (L_query behind n + 1 points at infinity; the B query's G1 half spread over its index
+    /// list when all but 64 or at least 63 of 64 variables occur in it -- the padding is gathered, too) the device extracts and sorts the window
+    /// digits of the assignment once instead of three times (zkhip_bases_spread, "msm_share_sort").  Decided at the first proof.
+    /// Measured on a 2^20-constraint proof: the main stream's sort kernels 4.1 -> 1.8 ms, the proof itself 22.3 -> 22.2 ms (the sorts
+    /// it removes used to run under the G2 accumulation's multiply-adds), two provers sharing the GPU 51.3 -> 51.8 proofs/s.
+    bool share_sorts = true;
+    /// second in-order stream on the same GPU for the G2 multiexp (its own workspace); false: everything on `ctx`
+    bool overlap_g2 = true;
+    /// the B-query size from which that second stream (a context of its own) is created: it pays off for large queries only
+    std::size_t side_stream_min = (std::size_t)1 << 14;
+    /// scheduling priority of that second stream (< 0: above, > 0: below the main stream's; "stream_priority" in include/zkhip.h)
+    int side_stream_priority = 1;    // measured: 22.7 -> 22.4 ms per 2^20 proof with the G2 stream below the main one (tools/exp_stream_priority.sh)
+    /// send the auxiliary input as it lies in the caller's vector (taken only when the scalar type is canonical limbs in memory);
+    /// false: through the page-locked staging buffer, converted by host threads (any scalar representation)
+    bool direct_assignment_upload = true;
+};
+
 template <typename CurveType, typename KeyType = r1cs_gg_ppzksnark_proving_key<CurveType>>
-class r1cs_gg_ppzksnark_proving_key_hip {
+class r1cs_gg_ppzksnark_proving_key_hip : public r1cs_gg_ppzksnark_tunables {
     ZKHIP_REQUIRE_PAIRING(CurveType, "Groth16");
 public:
     typedef curve_adapter<CurveType> adapter;
     typedef KeyType host_key_type;
+    /// u64 words of one key's partial sums: A, B.h, H, L (G1) then B.g (G2), Jacobian
+    static constexpr std::size_t partial_limbs = 4 * 3 * adapter::g1_coord_limbs + 3 * adapter::g2_coord_limbs;
 
     /// Rank `rank` of `world`: uploads only this rank's slice of the four queries (and the whole constraint system:
     /// the witness map is replicated).  Proofs then go through prover::process_partial + an all-gather of the partial
@@ -321,14 +343,12 @@ public:
     /// 51-52 proofs/s against 44-45 one at a time (tools/groth16_two_provers.py).  `other` must outlive the lane and must not be
     /// proving while the lane is constructed.
     r1cs_gg_ppzksnark_proving_key_hip(const context &lane_ctx, const r1cs_gg_ppzksnark_proving_key_hip &other) :
-        ctx(lane_ctx), host(other.host), domain(other.domain), evaluation_domain(other.evaluation_domain),
+        r1cs_gg_ppzksnark_tunables(other), ctx(lane_ctx), host(other.host), domain(other.domain), evaluation_domain(other.evaluation_domain),
         A_query((other.align_rows(), device_bases<CurveType, ZKHIP_G1>::alias(other.A_query))),
         H_query(device_bases<CurveType, ZKHIP_G1>::alias(other.H_query)), L_query(device_bases<CurveType, ZKHIP_G1>::alias(other.L_query)),
         B_query_h(device_bases<CurveType, ZKHIP_G1>::alias(other.B_query_h)), B_query_g(device_bases<CurveType, ZKHIP_G2>::alias(other.B_query_g)),
         constraint_system(typename device_r1cs<CurveType>::alias_tag(), other.constraint_system), d_B_indices(other.d_B_indices),
-        B_count(other.B_count), shard(other.shard), share_sorts(other.share_sorts), L_rows_aligned(other.L_rows_aligned),
-        B_rows_aligned(other.B_rows_aligned), overlap_g2(other.overlap_g2), side_stream_priority(other.side_stream_priority),
-        direct_assignment_upload(other.direct_assignment_upload) {
+        B_count(other.B_count), shard(other.shard), L_rows_aligned(other.L_rows_aligned), B_rows_aligned(other.B_rows_aligned) {
         if (lane_ctx.device() != other.ctx.device()) throw std::invalid_argument("proving key lane: the lane's context is on another GPU than the key");
         other.lanes_taken_ = true;    // from here on `other` keeps its queries where they are (align_rows)
     }
@@ -349,31 +369,49 @@ public:
     std::size_t B_count = 0;
     query_shard shard;
 
-    /// per-proof device buffers, kept across proofs: (1, x, w), coefficients_for_H, witness-map scratch, gathered B
-    /// scalars, the five Jacobian MSM results
-    mutable std::shared_ptr<void> d_cpa, d_h, d_scratch, d_bs, d_results;
-    mutable std::shared_ptr<void> h_cpa;    // page-locked staging for (1, x, w): H2D at link speed, asynchronous
-    /// evaluation_At, evaluation_Bt.h and evaluation_Lt multiply by the SAME assignment vector (prover.hpp:108-139): with the three
-    /// queries laid out over the same N + 1 rows (L_query behind n + 1 points at infinity; the B query's G1 half spread over its index
-    /// list when all but 64 or at least 63 of 64 variables occur in it -- the padding is gathered, too) the device extracts and sorts the window
-    /// digits of the assignment once instead of three times (zkhip_bases_spread, "msm_share_sort").  Decided at the first proof.
-    /// Measured on a 2^20-constraint proof: the main stream's sort kernels 4.1 -> 1.8 ms, the proof itself 22.3 -> 22.2 ms (the sorts
-    /// it removes used to run under the G2 accumulation's multiply-adds), two provers sharing the GPU 51.3 -> 51.8 proofs/s.
-    bool share_sorts = true;
-    mutable bool L_rows_aligned = false, B_rows_aligned = false;
-    mutable bool lanes_taken_ = false;    // a lane key aliases this key's queries
-    /// second in-order stream on the same GPU for the G2 multiexp (its own workspace); false: everything on `ctx`
-    bool overlap_g2 = true;
-    /// scheduling priority of that second stream (< 0: above, > 0: below the main stream's; "stream_priority" in include/zkhip.h)
-    bool experiment_skip_g2 = false;    // timing experiments only: see enqueue()
-    int side_stream_priority = 1;    // measured: 22.7 -> 22.4 ms per 2^20 proof with the G2 stream below the main one (tools/exp_stream_priority.sh)
-    /// send the auxiliary input as it lies in the caller's vector (possible when the scalar type is canonical limbs in memory);
-    /// false: through the page-locked staging buffer, converted by host threads (any scalar representation)
-    bool direct_assignment_upload = detail::canonical_scalars<curve_adapter<CurveType>>::value;
+    bool experiment_skip_g2 = false;    // timing experiments only (see proof_run::compute); a lane does not inherit it
+    mutable bool L_rows_aligned = false, B_rows_aligned = false;    // the layout align_rows() gave L_query / B_query_h
     /// host wall time of the last proof's phases, ms: staging + launches | host products (device busy) | waiting for the device | assembly
     mutable double last_phase_ms[4] = {0, 0, 0, 0};
-    mutable std::unique_ptr<context> side;
-    mutable std::int64_t saved_sort_tile_log = 14;    // the caller's "msm_sort_tile_log", set aside for the duration of a proof
+
+    /// Everything of the key that belongs to the proof in flight (one at a time per key), kept across proofs so that a proof costs no
+    /// hipMalloc; the prover's proof_run works on it.
+    struct work_state {
+        /// (1, x, w), coefficients_for_H, witness-map scratch, gathered B scalars, the five Jacobian MSM results
+        std::shared_ptr<void> d_cpa, d_h, d_scratch, d_bs, d_results;
+        std::shared_ptr<void> h_cpa;    // page-locked staging for (1, x, w): H2D at link speed, asynchronous
+        std::unique_ptr<context> side;    // the second stream, once a proof has wanted it (g2_context())
+        std::int64_t saved_sort_tile_log = 14;    // the caller's "msm_sort_tile_log", set aside for the duration of a two-stream proof
+        std::size_t cpa_elems = 0;
+
+        /// buffers for an assignment of `elems` scalars (the constant one included); a no-op once they are large enough
+        void reserve(const r1cs_gg_ppzksnark_proving_key_hip &key, std::size_t elems) {
+            if (d_cpa && cpa_elems >= elems) return;
+            const context &ctx = key.ctx;
+            key.align_rows();
+            d_cpa = ctx.alloc(elems * 32);
+            void *hp = nullptr;
+            ZKHIP_CALL(ctx, zkhip_host_alloc, elems * 32, &hp);
+            h_cpa = std::shared_ptr<void>(hp, [c = ctx.get()](void *p) { zkhip_host_free(c, p); });
+            d_h = ctx.alloc((key.constraint_system.domain_size() + 1) * 32);
+            d_scratch = ctx.alloc(zkhip_groth16_scratch_bytes(key.constraint_system.get()));
+            d_bs = ctx.alloc(std::max<std::size_t>(1, key.B_count) * 32);
+            d_results = ctx.alloc(partial_limbs * 8);
+            if (key.overlap_g2 && !side && key.B_count >= key.side_stream_min) {
+                side.reset(new context(ctx.device()));
+                /* while two streams share the GPU the sorts use tiles small enough to sit next to the other stream's resident accumulation
+                   workgroups ("msm_sort_tile_log" in include/zkhip.h): set on the side context for good, on the CALLER's context only for
+                   the duration of a proof (proof_run's constructor sets it, its join() gives it back) */
+                side->set_option("msm_sort_tile_log", 12);
+                if (key.side_stream_priority != 0) side->set_option("stream_priority", key.side_stream_priority);
+            }
+            cpa_elems = elems;
+        }
+    };
+    mutable work_state work;
+    /// where the G2 multiexp of the next proof runs: the second stream if there is one and overlap_g2 still asks for it
+    const context &g2_context() const { return overlap_g2 && work.side ? *work.side : ctx; }
+
     /// lays L_query and (when dense) the B query's G1 half out over A_query's rows -- see share_sorts; once, before the first proof
     void align_rows() const {
         /* a lane aliases L_query / B_query_h by their device pointers: once one exists the layout is frozen -- a share_sorts switched
@@ -387,30 +425,6 @@ public:
             B_query_h = B_query_h.spread(d_B_indices.get(), 0, N + 1);
             B_rows_aligned = true;
         }
-    }
-    void reserve_work(std::size_t cpa_elems, std::size_t degree, std::size_t result_bytes) const {
-        if (d_cpa && work_cpa_ >= cpa_elems) return;
-        align_rows();
-        d_cpa = ctx.alloc(cpa_elems * 32);
-        {
-            void *hp = nullptr;
-            ZKHIP_CALL(ctx, zkhip_host_alloc, cpa_elems * 32, &hp);
-            zkhip_ctx *c = ctx.get();
-            h_cpa = std::shared_ptr<void>(hp, [c](void *p) { zkhip_host_free(c, p); });
-        }
-        d_h = ctx.alloc((degree + 1) * 32);
-        d_scratch = ctx.alloc(zkhip_groth16_scratch_bytes(constraint_system.get()));
-        d_bs = ctx.alloc(std::max<std::size_t>(1, B_count) * 32);
-        d_results = ctx.alloc(result_bytes);
-        if (overlap_g2 && !side && B_count >= ((std::size_t)1 << 14)) {    // pays off for large queries only
-            side.reset(new context(ctx.device()));
-            /* while two streams share the GPU the sorts use tiles small enough to sit next to the other stream's resident accumulation
-               workgroups ("msm_sort_tile_log" in include/zkhip.h): set on the side context for good, on the CALLER's context only for
-               the duration of a proof (sort_tiles_scope in enqueue / collect) */
-            side->set_option("msm_sort_tile_log", 12);
-            if (side_stream_priority != 0) side->set_option("stream_priority", side_stream_priority);
-        }
-        work_cpa_ = cpa_elems;
     }
 
 private:
@@ -471,7 +485,7 @@ private:
         if (!idx.empty()) ctx.h2d(d_B_indices.get(), idx.data(), idx.size() * 4);
         B_count = idx.size();
     }
-    mutable std::size_t work_cpa_ = 0;
+    mutable bool lanes_taken_ = false;    // a lane key aliases this key's queries
 };
 
 // ---- the same key over a device group ---------------------------------------------------------------------------------
@@ -525,6 +539,7 @@ public:
     typedef std::vector<scalar_value_type> primary_input_type;
     typedef std::vector<scalar_value_type> auxiliary_input_type;
     typedef r1cs_gg_ppzksnark_proving_key_hip<CurveType, KeyType> proving_key_type;
+    typedef r1cs_gg_ppzksnark_proving_key_group_hip<CurveType, KeyType> group_key_type;
     typedef ProofType proof_type;
 
     static proof_type process(const proving_key_type &proving_key, const primary_input_type &primary_input,
@@ -555,7 +570,7 @@ public:
     }
     /// drop the cached device key(s) of `proving_key` (and with them the resident queries); true if there was one
     static bool forget(const KeyType &proving_key) {
-        const bool one = device_key_cache().erase(&proving_key) != 0, many = group_key_cache().erase(&proving_key) != 0;
+        const bool one = device_key_cache().entries.erase(&proving_key) != 0, many = group_key_cache().entries.erase(&proving_key) != 0;
         return one || many;
     }
 
@@ -581,48 +596,44 @@ private:
             }
         return fp;
     }
-    struct cached_key {
-        std::vector<std::uint64_t> fingerprint;    // of the host key the device key was built from: another key in the same object is rebuilt
-        std::unique_ptr<proving_key_type> device;
+    /// host key -> the device key built from it, one cache per thread (like default_context(): a context is not thread-safe).  An entry is
+    /// rebuilt when another key lies in the same host object (the fingerprint) or when it lives somewhere else than asked for (`home`).
+    template <typename Device>
+    struct key_cache {
+        struct entry {
+            std::vector<std::uint64_t> fingerprint;
+            const void *home = nullptr;
+            std::unique_ptr<Device> device;
+        };
+        std::map<const KeyType *, entry> entries;
+        /// `owner()` names what the cached keys release their device memory THROUGH: it is constructed first, so that it dies last
+        /// (thread_local objects die in reverse order of construction; ADVICE r4: the keys once outlived the context they free into)
+        static key_cache &instance(void (*owner)()) {
+            owner();
+            thread_local key_cache cache;
+            return cache;
+        }
+        template <typename Make>
+        const Device &get(const KeyType &pk, const void *home, Make make) {
+            entry &e = entries[&pk];
+            std::vector<std::uint64_t> fp = key_fingerprint(pk);
+            if (!e.device || e.home != home || e.fingerprint != fp) {
+                e.device.reset();    // the old key's queries go first: two resident keys of 2^20 constraints are 1.5 GB
+                e.device.reset(make());
+                e.home = home;
+                e.fingerprint = std::move(fp);
+            }
+            return *e.device;
+        }
     };
-    static std::map<const KeyType *, cached_key> &device_key_cache() {
-        /* the context first: thread_local objects die in reverse order of construction, and the cached keys release their device memory
-           THROUGH the default context (with the cache constructed first, its keys outlived the context they free into) */
-        (void)default_context();
-        thread_local std::map<const KeyType *, cached_key> cache;    // per thread, like default_context(): a context is not thread-safe
-        return cache;
-    }
+    static key_cache<proving_key_type> &device_key_cache() { return key_cache<proving_key_type>::instance([] { (void)default_context(); }); }
+    static key_cache<group_key_type> &group_key_cache() { return key_cache<group_key_type>::instance([] { (void)default_group(); }); }
     static const proving_key_type &cached_device_key(const KeyType &pk) {
-        cached_key &e = device_key_cache()[&pk];
-        std::vector<std::uint64_t> fp = key_fingerprint(pk);
-        if (!e.device || e.fingerprint != fp) {
-            e.device.reset();    // the old key's queries go first: two resident keys of 2^20 constraints are 1.5 GB
-            e.device.reset(new proving_key_type(pk));
-            e.fingerprint = std::move(fp);
-        }
-        return *e.device;
+        return device_key_cache().get(pk, nullptr, [&pk] { return new proving_key_type(pk); });
     }
-
-    struct cached_group_key_entry {
-        std::vector<std::uint64_t> fingerprint;
-        const device_group *group = nullptr;    // the group the member keys live on: another default group rebuilds them
-        std::unique_ptr<r1cs_gg_ppzksnark_proving_key_group_hip<CurveType, KeyType>> device;
-    };
-    static std::map<const KeyType *, cached_group_key_entry> &group_key_cache() {
-        (void)default_group();    // constructed first, destroyed last: the cached keys release their device memory through its contexts
-        thread_local std::map<const KeyType *, cached_group_key_entry> cache;
-        return cache;
-    }
-    static const r1cs_gg_ppzksnark_proving_key_group_hip<CurveType, KeyType> &cached_group_key(const device_group &g, const KeyType &pk) {
-        cached_group_key_entry &e = group_key_cache()[&pk];
-        std::vector<std::uint64_t> fp = key_fingerprint(pk);
-        if (!e.device || e.group != &g || e.fingerprint != fp) {
-            e.device.reset();
-            e.device.reset(new r1cs_gg_ppzksnark_proving_key_group_hip<CurveType, KeyType>(g, pk));
-            e.group = &g;
-            e.fingerprint = std::move(fp);
-        }
-        return *e.device;
+    /// the member keys live on the group: another default group rebuilds them
+    static const group_key_type &cached_group_key(const device_group &g, const KeyType &pk) {
+        return group_key_cache().get(pk, &g, [&g, &pk] { return new group_key_type(g, pk); });
     }
 
 public:
@@ -630,40 +641,33 @@ public:
     static proof_type process(const proving_key_type &pk, const primary_input_type &primary_input, const auxiliary_input_type &auxiliary_input,
                               const scalar_value_type &r, const scalar_value_type &s) {
         if (pk.shard.world != 1) throw std::runtime_error("process: sharded key -- use process_partial / finish (or the all-gather overload)");
-        typedef std::chrono::steady_clock clock;
-        const auto t0 = clock::now();
-        drain_on_unwind guard {pk};
-        enqueue(pk, primary_input, auxiliary_input);
-        const auto t1 = clock::now();
+        phase_timer phase {pk.last_phase_ms};
+        proof_run run(pk, primary_input.size(), auxiliary_input.size());
+        run.upload(primary_input, auxiliary_input), run.compute();
+        phase.mark();
         /* host products that do not depend on the MSM results, computed while the GPU works (prover.hpp:142-155) */
         const host_terms t = host_products(pk, r, s);
-        const auto t2 = clock::now();
-        const std::vector<std::uint64_t> sums = collect(pk);    // the one synchronisation of the proof
-        guard.armed = false;
-        const auto t3 = clock::now();
+        phase.mark();
+        const std::vector<std::uint64_t> sums = run.results();    // the one synchronisation of the proof
+        phase.mark();
         proof_type proof = assemble(pk, sums, 1, r, s, t);
-        const clock::time_point marks[5] = {t0, t1, t2, t3, clock::now()};
-        for (int i = 0; i < 4; ++i) pk.last_phase_ms[i] = std::chrono::duration<double, std::milli>(marks[i + 1] - marks[i]).count();
+        phase.mark();
         return proof;
     }
 
     // ---- one proof sharded over several GPUs (one process per GPU) ---------------------------------------
     // Every rank holds a slice of each query (proving_key_type(ctx, pk, dom, rank, world)), runs the witness map in
     // full (replicated: 7 NTTs, no exchange) and the five MSMs over its slices; the only exchange is one all-gather
-    // of partial_limbs() u64 words per rank (4 G1 + 1 G2 Jacobian points, 864 bytes for BLS12-381), after which
+    // of partial_limbs() u64 words per rank (A, B.h, H, L in G1 then B.g in G2, Jacobian: 864 bytes for BLS12-381), after which
     // every rank can assemble the proof.
-
-    /// u64 words of one rank's partial sums: A, B.h, H, L (G1) then B.g (G2), Jacobian
-    static constexpr std::size_t partial_limbs() { return 4 * 3 * adapter::g1_coord_limbs + 3 * adapter::g2_coord_limbs; }
+    static constexpr std::size_t partial_limbs() { return proving_key_type::partial_limbs; }
 
     /// this rank's partial sums (synchronises)
     static std::vector<std::uint64_t> process_partial(const proving_key_type &pk, const primary_input_type &primary_input,
                                                       const auxiliary_input_type &auxiliary_input) {
-        drain_on_unwind guard {pk};
-        enqueue(pk, primary_input, auxiliary_input);
-        std::vector<std::uint64_t> sums = collect(pk);
-        guard.armed = false;
-        return sums;
+        proof_run run(pk, primary_input.size(), auxiliary_input.size());
+        run.upload(primary_input, auxiliary_input), run.compute();
+        return run.results();
     }
     /// `gathered`: world x partial_limbs() words, rank-major (what an all-gather of process_partial's result yields)
     static proof_type finish(const proving_key_type &pk, const std::vector<std::uint64_t> &gathered, const scalar_value_type &r,
@@ -676,11 +680,10 @@ public:
     template <typename AllGather>
     static proof_type process(const proving_key_type &pk, const primary_input_type &primary_input, const auxiliary_input_type &auxiliary_input,
                               const scalar_value_type &r, const scalar_value_type &s, AllGather all_gather) {
-        drain_on_unwind guard {pk};
-        enqueue(pk, primary_input, auxiliary_input);
+        proof_run run(pk, primary_input.size(), auxiliary_input.size());
+        run.upload(primary_input, auxiliary_input), run.compute();
         const host_terms t = host_products(pk, r, s);
-        const std::vector<std::uint64_t> mine = collect(pk);
-        guard.armed = false;
+        const std::vector<std::uint64_t> mine = run.results();
         std::vector<std::uint64_t> all(pk.shard.world * partial_limbs());
         all_gather(mine.data(), mine.size(), all.data());
         return assemble(pk, all, pk.shard.world, r, s, t);
@@ -693,18 +696,12 @@ public:
     template <typename AllGather>
     static proof_type process_device_gather(const proving_key_type &pk, const primary_input_type &primary_input, const auxiliary_input_type &auxiliary_input,
                                             const scalar_value_type &r, const scalar_value_type &s, void *d_mine, void *d_all, AllGather all_gather) {
-        drain_on_unwind guard {pk};
-        enqueue(pk, primary_input, auxiliary_input);
+        proof_run run(pk, primary_input.size(), auxiliary_input.size());
+        run.upload(primary_input, auxiliary_input), run.compute();
         const host_terms t = host_products(pk, r, s);
-        if (pk.side) {
-            pk.ctx.wait_for(*pk.side);
-            pk.ctx.set_option("msm_sort_tile_log", pk.saved_sort_tile_log);
-        }
-        ZKHIP_CALL(pk.ctx, zkhip_memcpy_d2d_async, d_mine, pk.d_results.get(), partial_limbs() * 8);
-        /* kernels flag what they cannot signal otherwise; zkhip_device_status synchronises the stream: d_mine is complete after it */
-        ZKHIP_CALL(pk.ctx, zkhip_device_status, nullptr);
-        if (pk.side) ZKHIP_CALL(*pk.side, zkhip_device_status, nullptr);
-        guard.armed = false;    // both streams have drained
+        run.join();
+        ZKHIP_CALL(pk.ctx, zkhip_memcpy_d2d_async, d_mine, pk.work.d_results.get(), partial_limbs() * 8);
+        run.finish();    // synchronises the stream: d_mine is complete after it
         all_gather();
         std::vector<std::uint64_t> all(pk.shard.world * partial_limbs());
         pk.ctx.d2h(all.data(), d_all, all.size() * 8);
@@ -712,8 +709,6 @@ public:
     }
 
     // ---- one proof over a device group: N GPUs, ONE caller, the exchange inside the library ---------------------------------------
-    typedef r1cs_gg_ppzksnark_proving_key_group_hip<CurveType, KeyType> group_key_type;
-
     static proof_type process(const group_key_type &gk, const primary_input_type &primary_input, const auxiliary_input_type &auxiliary_input) {
         return process(gk, primary_input, auxiliary_input, random_scalar(), random_scalar());
     }
@@ -722,37 +717,28 @@ public:
     /// or a staged copy, in stream order -- and ONE download + the host's assembly follow.
     static proof_type process(const group_key_type &gk, const primary_input_type &primary_input, const auxiliary_input_type &auxiliary_input,
                               const scalar_value_type &r, const scalar_value_type &s) {
-        typedef std::chrono::steady_clock clock;
         const std::size_t world = gk.members.size();
         if (world == 0) throw std::runtime_error("process: empty device group key");
-        const auto t0 = clock::now();
-        std::vector<std::unique_ptr<drain_on_unwind>> guards;
-        for (const auto &m : gk.members) guards.emplace_back(new drain_on_unwind {*m});
+        phase_timer phase {gk.last_phase_ms};
+        std::vector<proof_run> runs;
+        for (const auto &m : gk.members) runs.emplace_back(*m, primary_input.size(), auxiliary_input.size());    // moves as it grows: nothing is in flight yet
         /* The assignment crosses PCIe ONCE, to member 0; the other members pull it from there (peer copies over xGMI, each on its own
            stream behind an event that marks the end of member 0's upload -- NOT of its proof): a copy out of the caller's pageable vector
            blocks this thread for its duration, and eight of them in a row would cost more than the sharded proof itself. */
-        const std::size_t num_inputs = primary_input.size(), num_variables = primary_input.size() + auxiliary_input.size();
-        upload_assignment(*gk.members[0], primary_input, auxiliary_input);
-        for (std::size_t k = 1; k < world; ++k) {
-            const proving_key_type &pk = *gk.members[k];
-            pk.reserve_work(num_variables + 1, pk.constraint_system.domain_size(), partial_limbs() * 8);
-            gk.group.copy(k, pk.d_cpa.get(), 0, gk.members[0]->d_cpa.get(), 32 * (num_variables + 1));
-        }
+        runs[0].upload(primary_input, auxiliary_input);
+        const std::size_t cpa_bytes = 32 * (1 + primary_input.size() + auxiliary_input.size());
+        for (std::size_t k = 1; k < world; ++k) gk.group.copy(k, gk.members[k]->work.d_cpa.get(), 0, gk.members[0]->work.d_cpa.get(), cpa_bytes);
         /* ~60 launches per member: from three members on, every member but the first is enqueued by a host thread of its own (a context
            is used by one thread at a time: distinct contexts are independent), so that the last member does not start N x 0.3 ms late */
-        gk.group.for_each_member([&gk, num_inputs, num_variables](std::size_t k) { enqueue_compute(*gk.members[k], num_inputs, num_variables); }, world > 2);
-        const auto t1 = clock::now();
+        gk.group.for_each_member([&runs](std::size_t k) { runs[k].compute(); }, world > 2);
+        phase.mark();
         const host_terms t = host_products(*gk.members[0], r, s);
-        const auto t2 = clock::now();
+        phase.mark();
         std::vector<const void *> send(world);
         std::vector<void *> recv(world, nullptr);
         for (std::size_t k = 0; k < world; ++k) {
-            const proving_key_type &pk = *gk.members[k];
-            if (pk.side) {
-                pk.ctx.wait_for(*pk.side);
-                pk.ctx.set_option("msm_sort_tile_log", pk.saved_sort_tile_log);
-            }
-            send[k] = pk.d_results.get();
+            runs[k].join();
+            send[k] = gk.members[k]->work.d_results.get();
         }
         const context &root = gk.members[0]->ctx;
         if (!gk.d_all) gk.d_all = root.alloc(world * partial_limbs() * 8);
@@ -760,21 +746,24 @@ public:
         gk.group.all_gather(send, recv, partial_limbs() * 8);
         std::vector<std::uint64_t> all(world * partial_limbs());
         root.d2h(all.data(), gk.d_all.get(), all.size() * 8);    // the root's stream is behind the exchange
-        /* kernels flag what they cannot signal otherwise; zkhip_device_status drains every member's streams */
-        for (std::size_t k = 0; k < world; ++k) {
-            const proving_key_type &pk = *gk.members[k];
-            ZKHIP_CALL(pk.ctx, zkhip_device_status, nullptr);
-            if (pk.side) ZKHIP_CALL(*pk.side, zkhip_device_status, nullptr);
-            guards[k]->armed = false;
-        }
-        const auto t3 = clock::now();
+        for (proof_run &run : runs) run.finish();    // drains every member's streams
+        phase.mark();
         proof_type proof = assemble(*gk.members[0], all, world, r, s, t);
-        const clock::time_point marks[5] = {t0, t1, t2, t3, clock::now()};
-        for (int i = 0; i < 4; ++i) gk.last_phase_ms[i] = std::chrono::duration<double, std::milli>(marks[i + 1] - marks[i]).count();
+        phase.mark();
         return proof;
     }
 
 private:
+    /// fills a key's last_phase_ms: mark() closes one phase
+    struct phase_timer {
+        double *ms;
+        std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
+        void mark() {
+            const auto now = std::chrono::steady_clock::now();
+            *ms++ = std::chrono::duration<double, std::milli>(now - last).count();
+            last = now;
+        }
+    };
     /* What the proof needs besides the five multiexps (prover.hpp:141-155), regrouped so that everything that does not depend on
        a device result is computed while the device works:
            A = alpha + At + r delta                           B = beta + Bt + s delta     (G2; the G1 copy only feeds C)
@@ -782,24 +771,6 @@ private:
              = Ht + Lt + s At + r Bt_h + [s alpha + r beta_g1 + r s delta]
        -- the bracket and r delta, s delta_g2 are `host_terms`; s At and r Bt_h are the two products left for after the results
        arrive (`assemble` runs them on two threads). */
-    /// enqueue() leaves asynchronous copies out of the CALLER's vectors (and kernels over the key's buffers) in flight; if anything
-    /// throws before collect() has drained them -- a failed check, std::async out of threads -- the stack must not unwind under
-    /// that DMA: the guard waits for both streams (and gives the caller's context its sort-tile setting back) on the way out.
-    struct drain_on_unwind {
-        const proving_key_type &pk;
-        bool armed = true;
-        ~drain_on_unwind() {
-            if (!armed) return;
-            try {
-                pk.ctx.sync();
-                if (pk.side) {
-                    pk.side->sync();
-                    pk.ctx.set_option("msm_sort_tile_log", pk.saved_sort_tile_log);
-                }
-            } catch (...) {
-            }
-        }
-    };
     struct host_terms {
         typename adapter::g1_value_type r_delta, c_base;
         typename adapter::g2_value_type s_delta2;
@@ -812,112 +783,144 @@ private:
         return {r_delta, c_base, g2.get()};
     }
 
-    /// enqueue the whole device side of a proof on the context's stream (no synchronisation)
-    static void enqueue(const proving_key_type &pk, const primary_input_type &primary_input, const auxiliary_input_type &auxiliary_input) {
-        upload_assignment(pk, primary_input, auxiliary_input);
-        enqueue_compute(pk, primary_input.size(), primary_input.size() + auxiliary_input.size());
-    }
-    /// the key's work buffers (first use) and const_padded_assignment = (1, x, w) on its way to d_cpa (asynchronous)
-    static void upload_assignment(const proving_key_type &pk, const primary_input_type &primary_input, const auxiliary_input_type &auxiliary_input) {
-        const context &ctx = pk.ctx;
-        const std::size_t num_inputs = primary_input.size();
-        const std::size_t num_variables = primary_input.size() + auxiliary_input.size();
-        /* Everything below is enqueued on the context's stream without intermediate synchronisation; the device
-           buffers live in the key object (allocated on first use) so a proof costs no hipMalloc. */
-        pk.reserve_work(num_variables + 1, pk.constraint_system.domain_size(), partial_limbs() * 8);
-        char *cpa = static_cast<char *>(pk.d_cpa.get());
-
-        /* const_padded_assignment = (1, x, w) (prover.hpp:102-106) */
-        std::uint64_t *z = static_cast<std::uint64_t *>(pk.h_cpa.get());
-        z[0] = 1;
-        z[1] = z[2] = z[3] = 0;
-        for (std::size_t i = 0; i < num_inputs; ++i) adapter::scalar_to_limbs(primary_input[i], &z[4 * (1 + i)]);
-        /* the auxiliary input (almost all of the assignment) is converted into the page-locked staging buffer in
-           slices by a few host threads, and every slice is sent as soon as it is ready: the conversion of slice k + 1
-           overlaps the PCIe copy of slice k */
-        if (detail::canonical_scalars<adapter>::value && pk.direct_assignment_upload) {
-            /* scalar values that ARE canonical limbs in memory: the auxiliary input goes out as it lies (0.3 ms per 2^20-constraint
-               proof less than through the staging buffer) */
-            static_assert(!detail::canonical_scalars<adapter>::value || sizeof(scalar_value_type) == 32, "canonical-limb scalars are 4 x u64");
-            ZKHIP_CALL(ctx, zkhip_memcpy_h2d_async, cpa, z, 32 * (1 + num_inputs));
-            if (!auxiliary_input.empty())
-                ZKHIP_CALL(ctx, zkhip_memcpy_h2d_async, cpa + 32 * (1 + num_inputs), auxiliary_input.data(), 32 * auxiliary_input.size());
-        } else {
-            const std::size_t aux = auxiliary_input.size(), slices = aux >= (std::size_t)1 << 16 ? 8 : 1, per = (aux + slices - 1) / slices;
-            std::uint64_t *za = z + 4 * (1 + num_inputs);
-            std::vector<std::future<void>> ready;
-            for (std::size_t k = 1; k < slices; ++k)
-                ready.push_back(std::async(std::launch::async, [&, k]() {
-                    for (std::size_t i = k * per; i < std::min(aux, (k + 1) * per); ++i) adapter::scalar_to_limbs(auxiliary_input[i], &za[4 * i]);
-                }));
-            for (std::size_t i = 0; i < std::min(aux, per); ++i) adapter::scalar_to_limbs(auxiliary_input[i], &za[4 * i]);
-            ZKHIP_CALL(ctx, zkhip_memcpy_h2d_async, cpa, z, 32 * (1 + num_inputs + std::min(aux, per)));
-            for (std::size_t k = 1; k < slices; ++k) {
-                ready[k - 1].get();
-                const std::size_t lo = k * per, hi = std::min(aux, (k + 1) * per);
-                if (hi > lo)
-                    ZKHIP_CALL(ctx, zkhip_memcpy_h2d_async, cpa + 32 * (1 + num_inputs + lo), za + 4 * lo, 32 * (hi - lo));
+    /// ONE PROOF IN FLIGHT on one (member) key, over the key's work state.  The constructor refuses what does not fit and prepares the
+    /// key -- nothing is launched there --; upload() and compute() enqueue without synchronising; join() puts the main stream behind the
+    /// G2 stream; finish() reads both streams' status.  upload() leaves asynchronous copies out of the CALLER's vectors (and kernels over
+    /// the key's buffers) in flight: if anything throws before finish() -- a failed check, std::async out of threads -- the stack must not
+    /// unwind under that DMA, so the destructor of an unfinished run waits for both streams (and gives the caller's context its
+    /// sort-tile setting back).
+    class proof_run {
+    public:
+        proof_run(const proving_key_type &key, std::size_t inputs, std::size_t auxiliary) :
+            pk(&key), num_inputs(inputs), num_variables(inputs + auxiliary) {
+            const query_shard &sh = key.shard;
+            const std::size_t degree = key.constraint_system.domain_size();
+            /* the witness map reads every variable of the constraint system, the multiexps this key's slices */
+            if (num_variables < key.host.constraint_system.num_variables() || sh.A_lo + sh.A_n > num_variables + 1 || sh.H_lo + sh.H_n + 1 > degree ||
+                num_inputs + sh.L_lo + sh.L_n > num_variables)
+                throw std::runtime_error("prover: the key's query slices do not fit this assignment");
+            key.work.reserve(key, num_variables + 1);
+            if (&key.g2_context() != &key.ctx) {    // two streams: small sort tiles on the caller's context, for this proof only
+                side = &key.g2_context();
+                key.work.saved_sort_tile_log = key.ctx.get_option("msm_sort_tile_log");
+                key.ctx.set_option("msm_sort_tile_log", 12);
             }
         }
-    }
-    /// the witness map and the five multiexps over the assignment at d_cpa (enqueued only)
-    static void enqueue_compute(const proving_key_type &pk, std::size_t num_inputs, std::size_t num_variables) {
-        const context &ctx = pk.ctx;
-        const query_shard &sh = pk.shard;
-        const std::size_t degree = pk.constraint_system.domain_size();
-        const std::size_t jl1 = 3 * adapter::g1_coord_limbs;
-        pk.reserve_work(num_variables + 1, degree, partial_limbs() * 8);
-        if (pk.side) {    // for this proof only: collect() gives the caller's context its own setting back
-            pk.saved_sort_tile_log = ctx.get_option("msm_sort_tile_log");
-            ctx.set_option("msm_sort_tile_log", 12);
+        proof_run(proof_run &&o) : pk(o.pk), side(o.side), num_inputs(o.num_inputs), num_variables(o.num_variables), joined(o.joined), finished(o.finished) {
+            o.finished = true;    // what is in flight is the new object's to drain
         }
-        char *cpa = static_cast<char *>(pk.d_cpa.get());
-        std::uint64_t *d_res = static_cast<std::uint64_t *>(pk.d_results.get());
-        /* qap_wit.coefficients_for_H, resident (prover.hpp:79-83) */
-        const zkhip_domain dd = pk.evaluation_domain.c_desc();
-        ZKHIP_CALL(ctx, zkhip_groth16_witness_h_domain_dev, pk.constraint_system.get(), cpa, &dd, limbs_of<adapter>(pk.domain.coset_generator).data(), pk.d_h.get(),
-                   pk.d_scratch.get());
-        /* evaluation_Bt: kc_multiexp_with_mixed_addition over the sparse (G2, G1) query (prover.hpp:116-123); a sharded key
-           holds a slice of the index list */
-        ZKHIP_CALL(ctx, zkhip_fr_gather_dev, cpa, num_variables + 1, pk.d_B_indices.get(), pk.B_count, pk.d_bs.get());
-        if (pk.experiment_skip_g2) {
-            /* EXPERIMENT ONLY (wrong proof): what a proof would cost if the G2 multiexp were free -- the ceiling of anything that could be
-               gained on the second stream */
-        } else if (pk.side) {
-            /* the G2 part on the second stream, after the gather; the four G1 multiexps below do not depend on it */
-            pk.side->wait_for(ctx);
-            check(zkhip_msm_dev(pk.side->get(), pk.B_query_g.get(), 0, pk.B_count, pk.d_bs.get(), d_res + 4 * jl1), "zkhip_msm_dev(B.g)", pk.side->get());
-        } else {
-            check(zkhip_msm_dev(ctx.get(), pk.B_query_g.get(), 0, pk.B_count, pk.d_bs.get(), d_res + 4 * jl1), "zkhip_msm_dev(B.g)", ctx.get());
+        ~proof_run() {
+            if (finished) return;
+            try {
+                pk->ctx.sync();
+                if (side) {
+                    side->sync();
+                    pk->ctx.set_option("msm_sort_tile_log", pk->work.saved_sort_tile_log);
+                }
+            } catch (...) {
+            }
         }
-        /* the four G1 multiexps as one batch (their bucket reductions share one launch):
-           evaluation_At (prover.hpp:108-114), evaluation_Bt.h (:116-123), evaluation_Ht over H_query[0 .. degree - 1)
-           (:125-131), evaluation_Lt over the auxiliary part of the assignment (:133-139) -- each over this key's slice */
-        if (sh.A_n > num_variables + 1 - sh.A_lo || sh.H_n > degree - 1 - sh.H_lo || sh.L_n > num_variables - num_inputs - sh.L_lo)
-            throw std::runtime_error("prover: the key's query slices do not fit this assignment");
-        /* members over the same scalars and rows sit next to each other: the batch sorts the assignment's digits once for them */
-        const zkhip_bases *qb[4] = {pk.A_query.get(), pk.L_query.get(), pk.B_query_h.get(), pk.H_query.get()};
-        const std::size_t qo[4] = {0, 0, 0, 0};
-        const std::size_t qn[4] = {sh.A_n, pk.L_rows_aligned ? num_variables + 1 : sh.L_n, pk.B_rows_aligned ? num_variables + 1 : pk.B_count, sh.H_n};
-        const void *qs[4] = {cpa + 32 * sh.A_lo, pk.L_rows_aligned ? cpa : cpa + 32 * (num_inputs + 1 + sh.L_lo),
-                             pk.B_rows_aligned ? static_cast<const void *>(cpa) : pk.d_bs.get(),
-                             static_cast<const char *>(pk.d_h.get()) + 32 * sh.H_lo};
-        void *qr[4] = {d_res, d_res + 3 * jl1, d_res + jl1, d_res + 2 * jl1};
-        ZKHIP_CALL(ctx, zkhip_msm_batch_dev, 4, qb, qo, qn, qs, qr);
-    }
-    /// the five partial sums of this rank, after the stream has drained
-    static std::vector<std::uint64_t> collect(const proving_key_type &pk) {
-        std::vector<std::uint64_t> res(partial_limbs());
-        if (pk.side) {
-            pk.ctx.wait_for(*pk.side);
-            pk.ctx.set_option("msm_sort_tile_log", pk.saved_sort_tile_log);    // the caller's context gets its own sort tiles back
+
+        /// const_padded_assignment = (1, x, w) (prover.hpp:102-106) on its way to d_cpa (asynchronous)
+        void upload(const primary_input_type &primary_input, const auxiliary_input_type &auxiliary_input) {
+            const context &ctx = pk->ctx;
+            char *cpa = static_cast<char *>(pk->work.d_cpa.get());
+            std::uint64_t *z = static_cast<std::uint64_t *>(pk->work.h_cpa.get());
+            z[0] = 1, z[1] = z[2] = z[3] = 0;
+            for (std::size_t i = 0; i < num_inputs; ++i) adapter::scalar_to_limbs(primary_input[i], &z[4 * (1 + i)]);
+            if (detail::canonical_scalars<adapter>::value && pk->direct_assignment_upload) {
+                /* scalar values that ARE canonical limbs in memory: the auxiliary input goes out as it lies (0.3 ms per 2^20-constraint
+                   proof less than through the staging buffer) */
+                static_assert(!detail::canonical_scalars<adapter>::value || sizeof(scalar_value_type) == 32, "canonical-limb scalars are 4 x u64");
+                ZKHIP_CALL(ctx, zkhip_memcpy_h2d_async, cpa, z, 32 * (1 + num_inputs));
+                if (!auxiliary_input.empty())
+                    ZKHIP_CALL(ctx, zkhip_memcpy_h2d_async, cpa + 32 * (1 + num_inputs), auxiliary_input.data(), 32 * auxiliary_input.size());
+            } else {
+                /* the auxiliary input (almost all of the assignment) is converted into the page-locked staging buffer in
+                   slices by a few host threads, and every slice is sent as soon as it is ready: the conversion of slice k + 1
+                   overlaps the PCIe copy of slice k */
+                const std::size_t aux = auxiliary_input.size(), slices = aux >= (std::size_t)1 << 16 ? 8 : 1, per = (aux + slices - 1) / slices;
+                std::uint64_t *za = z + 4 * (1 + num_inputs);
+                std::vector<std::future<void>> ready;
+                for (std::size_t k = 1; k < slices; ++k)
+                    ready.push_back(std::async(std::launch::async, [&, k]() {
+                        for (std::size_t i = k * per; i < std::min(aux, (k + 1) * per); ++i) adapter::scalar_to_limbs(auxiliary_input[i], &za[4 * i]);
+                    }));
+                for (std::size_t i = 0; i < std::min(aux, per); ++i) adapter::scalar_to_limbs(auxiliary_input[i], &za[4 * i]);
+                ZKHIP_CALL(ctx, zkhip_memcpy_h2d_async, cpa, z, 32 * (1 + num_inputs + std::min(aux, per)));
+                for (std::size_t k = 1; k < slices; ++k) {
+                    ready[k - 1].get();
+                    const std::size_t lo = k * per, hi = std::min(aux, (k + 1) * per);
+                    if (hi > lo)
+                        ZKHIP_CALL(ctx, zkhip_memcpy_h2d_async, cpa + 32 * (1 + num_inputs + lo), za + 4 * lo, 32 * (hi - lo));
+                }
+            }
         }
-        pk.ctx.d2h(res.data(), pk.d_results.get(), res.size() * 8);
-        /* kernels flag what they cannot signal otherwise (a B-query index beyond the assignment, a plan overflow) */
-        ZKHIP_CALL(pk.ctx, zkhip_device_status, nullptr);
-        if (pk.side) ZKHIP_CALL(*pk.side, zkhip_device_status, nullptr);
-        return res;
-    }
+        /// the witness map and the five multiexps over the assignment at d_cpa (enqueued only)
+        void compute() {
+            const context &ctx = pk->ctx;
+            const query_shard &sh = pk->shard;
+            const auto &w = pk->work;
+            const std::size_t jl1 = 3 * adapter::g1_coord_limbs;
+            char *cpa = static_cast<char *>(w.d_cpa.get());
+            std::uint64_t *d_res = static_cast<std::uint64_t *>(w.d_results.get());
+            /* qap_wit.coefficients_for_H, resident (prover.hpp:79-83) */
+            const zkhip_domain dd = pk->evaluation_domain.c_desc();
+            ZKHIP_CALL(ctx, zkhip_groth16_witness_h_domain_dev, pk->constraint_system.get(), cpa, &dd, limbs_of<adapter>(pk->domain.coset_generator).data(),
+                       w.d_h.get(), w.d_scratch.get());
+            /* evaluation_Bt: kc_multiexp_with_mixed_addition over the sparse (G2, G1) query (prover.hpp:116-123); a sharded key
+               holds a slice of the index list */
+            ZKHIP_CALL(ctx, zkhip_fr_gather_dev, cpa, num_variables + 1, pk->d_B_indices.get(), pk->B_count, w.d_bs.get());
+            /* the G2 part, after the gather -- on the second stream when there is one: the four G1 multiexps below do not depend on it.
+               experiment_skip_g2 (a WRONG proof): what a proof would cost if the G2 multiexp were free -- the ceiling of anything that
+               could be gained on the second stream */
+            if (!pk->experiment_skip_g2) {
+                const context &g2 = side ? *side : ctx;
+                if (side) side->wait_for(ctx);
+                check(zkhip_msm_dev(g2.get(), pk->B_query_g.get(), 0, pk->B_count, w.d_bs.get(), d_res + 4 * jl1), "zkhip_msm_dev(B.g)", g2.get());
+            }
+            /* the four G1 multiexps as one batch (their bucket reductions share one launch):
+               evaluation_At (prover.hpp:108-114), evaluation_Bt.h (:116-123), evaluation_Ht over H_query[0 .. degree - 1)
+               (:125-131), evaluation_Lt over the auxiliary part of the assignment (:133-139) -- each over this key's slice;
+               members over the same scalars and rows sit next to each other: the batch sorts the assignment's digits once for them */
+            const zkhip_bases *qb[4] = {pk->A_query.get(), pk->L_query.get(), pk->B_query_h.get(), pk->H_query.get()};
+            const std::size_t qo[4] = {0, 0, 0, 0};
+            const std::size_t qn[4] = {sh.A_n, pk->L_rows_aligned ? num_variables + 1 : sh.L_n, pk->B_rows_aligned ? num_variables + 1 : pk->B_count, sh.H_n};
+            const void *qs[4] = {cpa + 32 * sh.A_lo, pk->L_rows_aligned ? cpa : cpa + 32 * (num_inputs + 1 + sh.L_lo),
+                                 pk->B_rows_aligned ? static_cast<const void *>(cpa) : w.d_bs.get(), static_cast<const char *>(w.d_h.get()) + 32 * sh.H_lo};
+            void *qr[4] = {d_res, d_res + 3 * jl1, d_res + jl1, d_res + 2 * jl1};
+            ZKHIP_CALL(ctx, zkhip_msm_batch_dev, 4, qb, qo, qn, qs, qr);
+        }
+        /// the main stream waits for the G2 stream and the caller's context gets its own sort tiles back; once
+        void join() {
+            if (joined || !side) return;
+            pk->ctx.wait_for(*side);
+            pk->ctx.set_option("msm_sort_tile_log", pk->work.saved_sort_tile_log);
+            joined = true;
+        }
+        /// kernels flag what they cannot signal otherwise (a B-query index beyond the assignment, a plan overflow): zkhip_device_status
+        /// synchronises the stream and throws what they flagged
+        void finish() {
+            ZKHIP_CALL(pk->ctx, zkhip_device_status, nullptr);
+            if (side) ZKHIP_CALL(*side, zkhip_device_status, nullptr);
+            finished = true;
+        }
+        /// the five partial sums of this key, after its streams have drained
+        std::vector<std::uint64_t> results() {
+            std::vector<std::uint64_t> res(partial_limbs());
+            join();
+            pk->ctx.d2h(res.data(), pk->work.d_results.get(), res.size() * 8);
+            finish();
+            return res;
+        }
+
+    private:
+        const proving_key_type *pk;
+        const context *side = nullptr;    // the G2 stream of this proof (null: everything on pk->ctx)
+        std::size_t num_inputs, num_variables;
+        bool joined = false, finished = false;
+    };
+
     /// fold the ranks' partial sums and build the proof (prover.hpp:141-157)
     static proof_type assemble(const proving_key_type &pk, const std::vector<std::uint64_t> &gathered, std::size_t world, const scalar_value_type &r,
                                const scalar_value_type &s, const host_terms &t) {

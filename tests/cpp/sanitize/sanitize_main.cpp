@@ -9,7 +9,8 @@
 // constructions and destructions: eviction order, the drain before each eviction, a build abandoned before publish().  And the option table
 // (csrc/options.hpp) over a plain struct: unique names, set / get round trips, the admission rules, the ZKHIP_OPTIONS parser.  And every member
 // of fr_vector (fr_vector.hpp) once, over buffers exactly as large as its contract says: the stub copies / touches the bytes each entry point
-// reads and writes, so an element count passed where bytes belong (or the reverse) is an ASan report.
+// reads and writes, so an element count passed where bytes belong (or the reverse) is an ASan report.  And a Groth16 proof that fails half way
+// (groth16_unwind: the stub fails one entry point once), on one key and on a member of a device group.
 #include <chrono>
 #include <memory>
 #include <cstdio>
@@ -168,6 +169,75 @@ void groth16_host_paths(std::size_t M) {
         r1cs_gg_ppzksnark_proving_key_hip<Curve> k(ctx, bad, dom);
         EXPECT(!"non-increasing B indices must be refused");
     } catch (const std::invalid_argument &) {
+    }
+}
+
+extern "C" void zkhip_stub_fail_once(const char *name, const zkhip_ctx *ctx);    // stub_backend.cpp
+
+/// A proof that fails half way (the stub fails the batched multiexp once): the exception reaches the caller, every stream of the proof is
+/// drained and the caller's sort-tile option is back on the way out, and the key proves again.  Keys with side_stream_min = 0: two streams.
+template <typename Curve>
+void groth16_unwind() {
+    typedef curve_adapter<Curve> A;
+    typedef typename A::scalar_value_type Fr;
+    typedef r1cs_gg_ppzksnark_prover_hip<Curve> prover;
+    const std::size_t M = 100, n = 10;
+    std::vector<Fr> full;
+    auto cs = example_cs<Curve>(M, n, full);
+    std::vector<Fr> primary(full.begin(), full.begin() + n), auxiliary(full.begin() + n, full.end());
+    domain_params<Curve> dom {Fr(7), Fr(5)};
+    r1cs_gg_ppzksnark_proving_key<Curve> pk;
+    pk.constraint_system = cs;
+    const std::size_t N = cs.num_variables(), m = evaluation_domain_hip<Curve>::make(dom, M + n + 1).m;
+    pk.A_query.assign(N + 1, A::g1_value_type::zero());
+    pk.H_query.assign(m - 1, A::g1_value_type::zero());
+    pk.L_query.assign(N - n, A::g1_value_type::zero());
+    for (std::size_t i = 0; i <= N; i += 2) {
+        pk.B_query.indices.push_back(i);
+        pk.B_query.values.push_back({A::g2_value_type::zero(), A::g1_value_type::zero()});
+    }
+    pk.B_query.domain_size_ = N + 1;
+    auto throws = [](auto call) {
+        try {
+            call();
+        } catch (const std::runtime_error &) {
+            return true;
+        }
+        return false;
+    };
+    {   /* one key */
+        context ctx(0);
+        ctx.set_option("msm_sort_tile_log", 13);
+        r1cs_gg_ppzksnark_proving_key_hip<Curve> dpk(ctx, pk, dom);
+        dpk.side_stream_min = 0;
+        (void)prover::process(dpk, primary, auxiliary, Fr(3), Fr(4));
+        EXPECT(dpk.work.side && &dpk.g2_context() == dpk.work.side.get() && ctx.get_option("msm_sort_tile_log") == 13);
+        zkhip_stub_fail_once("zkhip_msm_batch_dev", ctx.get());
+        EXPECT(throws([&] { (void)prover::process(dpk, primary, auxiliary, Fr(3), Fr(4)); }));
+        EXPECT(ctx.get_option("msm_sort_tile_log") == 13);
+        /* a short assignment is refused before anything is set aside or enqueued: the armed failure is still there afterwards */
+        zkhip_stub_fail_once("zkhip_msm_batch_dev", ctx.get());
+        std::vector<Fr> short_aux(auxiliary.begin(), auxiliary.end() - 1);
+        EXPECT(throws([&] { (void)prover::process(dpk, primary, short_aux, Fr(3), Fr(4)); }));
+        EXPECT(ctx.get_option("msm_sort_tile_log") == 13);
+        EXPECT(throws([&] { (void)prover::process_partial(dpk, primary, auxiliary); }));    // ... and fires here
+        (void)prover::process(dpk, primary, auxiliary, Fr(3), Fr(4));
+        EXPECT(ctx.get_option("msm_sort_tile_log") == 13);
+    }
+    {   /* a group of three: member 1, enqueued by a thread of the library, fails */
+        device_group grp({0, 0, 0});
+        r1cs_gg_ppzksnark_proving_key_group_hip<Curve> gk(grp, pk, dom);
+        for (std::size_t k = 0; k < 3; ++k) {
+            gk.members[k]->side_stream_min = 0;
+            grp[k].set_option("msm_sort_tile_log", 11 + (std::int64_t)k);
+        }
+        (void)prover::process(gk, primary, auxiliary, Fr(3), Fr(4));
+        zkhip_stub_fail_once("zkhip_msm_batch_dev", grp[1].get());
+        EXPECT(throws([&] { (void)prover::process(gk, primary, auxiliary, Fr(3), Fr(4)); }));
+        /* the option goes back only behind the drain of a member's two streams (proof_run's destructor) */
+        for (std::size_t k = 0; k < 3; ++k) EXPECT(gk.members[k]->work.side && grp[k].get_option("msm_sort_tile_log") == 11 + (std::int64_t)k);
+        (void)prover::process(gk, primary, auxiliary, Fr(3), Fr(4));
+        for (std::size_t k = 0; k < 3; ++k) EXPECT(grp[k].get_option("msm_sort_tile_log") == 11 + (std::int64_t)k);
     }
 }
 
@@ -902,6 +972,10 @@ int main(int argc, char **argv) {
     if (what == "all" || what == "fr_vector_layer") {
         fr_vector_layer<bls12_381>();
         fr_vector_layer<converting_curve>();
+    }
+    if (what == "all" || what == "groth16_unwind") {
+        groth16_unwind<bls12_381>();
+        groth16_unwind<converting_curve>();
     }
     if (what == "all" || what == "fuzz") parser_fuzz();
     if (what == "all" || what == "table_cache") table_cache_protocol();

@@ -5,12 +5,15 @@
 // tests/cpp/sanitize, and no result it produces is ever compared with anything.
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <mutex>
 #include <string>
 
 #include "../../../include/zkhip.h"
 
 struct zkhip_ctx {
     int device;
+    std::map<std::string, int64_t> options;    // what zkhip_set_option stored (a context is used by one thread at a time)
 };
 struct zkhip_bases {
     int curve, group;
@@ -21,6 +24,23 @@ struct zkhip_r1cs {
     size_t M, n, N, m;
 };
 
+// STUB ONLY: zkhip_stub_fail_once(name, ctx) makes the next call of the entry point `name` on `ctx` (null: on any context) return
+// ZKHIP_ERR_HIP -- the host code's way out of a proof that fails half way.  Entry points that can fail this way ask injected().
+static std::mutex g_fail_lock;
+static std::string g_fail_name;
+static const zkhip_ctx *g_fail_ctx = nullptr;
+extern "C" void zkhip_stub_fail_once(const char *name, const zkhip_ctx *ctx) {
+    std::lock_guard<std::mutex> hold(g_fail_lock);
+    g_fail_name = name ? name : "";
+    g_fail_ctx = ctx;
+}
+static bool injected(const char *name, const zkhip_ctx *ctx) {
+    std::lock_guard<std::mutex> hold(g_fail_lock);
+    if (g_fail_name != name || (g_fail_ctx && g_fail_ctx != ctx)) return false;
+    g_fail_name.clear();
+    return true;
+}
+
 static size_t coord_limbs(int curve, int group) { return (curve == ZKHIP_BLS12_381 ? 6 : 4) * (group == ZKHIP_G2 ? 2 : 1); }
 static size_t ceil_log2(size_t n) {
     size_t r = 0;
@@ -30,7 +50,7 @@ static size_t ceil_log2(size_t n) {
 
 extern "C" {
 int zkhip_init(int device, zkhip_ctx **out) {
-    *out = new zkhip_ctx {device};
+    *out = new zkhip_ctx {device, {}};
     return ZKHIP_OK;
 }
 void zkhip_destroy(zkhip_ctx *ctx) { delete ctx; }
@@ -44,9 +64,13 @@ int zkhip_device_status(zkhip_ctx *, uint32_t *flags) {
     if (flags) *flags = 0;
     return ZKHIP_OK;
 }
-int zkhip_set_option(zkhip_ctx *, const char *, int64_t) { return ZKHIP_OK; }
-int zkhip_get_option(const zkhip_ctx *, const char *, int64_t *value) {
-    *value = 14;
+int zkhip_set_option(zkhip_ctx *ctx, const char *name, int64_t value) {
+    ctx->options[name] = value;
+    return ZKHIP_OK;
+}
+int zkhip_get_option(const zkhip_ctx *ctx, const char *name, int64_t *value) {
+    const auto it = ctx->options.find(name);
+    *value = it == ctx->options.end() ? 14 : it->second;
     return ZKHIP_OK;
 }
 int zkhip_malloc(zkhip_ctx *, size_t bytes, void **dptr) {
@@ -132,10 +156,12 @@ int zkhip_msm(zkhip_ctx *, const zkhip_bases *b, size_t offset, size_t n, const 
     return ZKHIP_OK;
 }
 int zkhip_msm_dev(zkhip_ctx *ctx, const zkhip_bases *b, size_t offset, size_t n, const void *d_scalars, void *d_out) {
+    if (injected("zkhip_msm_dev", ctx)) return ZKHIP_ERR_HIP;
     return zkhip_msm(ctx, b, offset, n, (const uint64_t *)d_scalars, (uint64_t *)d_out);
 }
 int zkhip_msm_batch_dev(zkhip_ctx *ctx, size_t count, const zkhip_bases *const *bases, const size_t *offsets, const size_t *ns, const void *const *d_scalars,
                         void *const *d_out) {
+    if (injected("zkhip_msm_batch_dev", ctx)) return ZKHIP_ERR_HIP;
     for (size_t i = 0; i < count; ++i) {
         int rc = zkhip_msm_dev(ctx, bases[i], offsets[i], ns[i], d_scalars[i], d_out[i]);
         if (rc) return rc;
@@ -351,7 +377,7 @@ struct zkhip_device_group_stub {
 int zkhip_group_init(const int *device_ids, int n_dev, zkhip_device_group **out) {
     if (!device_ids || n_dev < 1) return ZKHIP_ERR_INVALID;
     auto *g = new zkhip_device_group_stub {n_dev, new zkhip_ctx *[n_dev], ZKHIP_GROUP_AUTO};
-    for (int k = 0; k < n_dev; ++k) g->members[k] = new zkhip_ctx {device_ids[k]};
+    for (int k = 0; k < n_dev; ++k) g->members[k] = new zkhip_ctx {device_ids[k], {}};
     *out = reinterpret_cast<zkhip_device_group *>(g);
     return ZKHIP_OK;
 }

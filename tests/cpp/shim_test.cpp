@@ -173,6 +173,16 @@ int groth16_prove_t(size_t M, size_t n, size_t N, const uint32_t *const rowptr[3
                                        std::memcpy(all, mine, words * 8);
                                    });
         if (!(pv2.g_A == pv.g_A) || !(pv2.g_B == pv.g_B) || !(pv2.g_C == pv.g_C)) return -102;
+        /* the same with the exchange on device buffers: d_all holds the other ranks' sums already, the "all-gather" adds rank 0's */
+        {
+            auto d_mine = ctx.alloc(prover::partial_limbs() * 8), d_all = ctx.alloc(gathered.size() * 8);
+            ctx.h2d(d_all.get(), gathered.data(), gathered.size() * 8);
+            auto pv3 = prover::process_device_gather(first, primary, auxiliary, A::scalar_from_limbs(r), A::scalar_from_limbs(s), d_mine.get(), d_all.get(), [&]() {
+                ZKHIP_CALL(ctx, zkhip_memcpy_d2d_async, d_all.get(), d_mine.get(), prover::partial_limbs() * 8);
+                ctx.sync();
+            });
+            if (!(pv3.g_A == pv.g_A) || !(pv3.g_B == pv.g_B) || !(pv3.g_C == pv.g_C)) return -128;
+        }
         /* THE DEVICE GROUP: g_world contexts behind one caller (members dealt over the box's GPUs, device 0 repeated on a one-GPU box), the
            exchange inside the library -- every transport the box offers must give the single-device proof bit for bit */
         {
@@ -216,6 +226,42 @@ int groth16_prove_t(size_t M, size_t n, size_t N, const uint32_t *const rowptr[3
     // the randomised overload must run too (its output is not comparable)
     auto p2 = r1cs_gg_ppzksnark_prover_hip<Curve>::process(dpk, primary, auxiliary);
     if (p2.g_A.is_zero()) return -101;
+    {
+        /* THE TWO-STREAM PROOF at this size (side_stream_min = 0: the G2 multiexp on a context of the key's own), on a caller's context
+           that has its own sort tiles: the same proof, and the caller's setting is back after every way out of a proof */
+        typedef r1cs_gg_ppzksnark_prover_hip<Curve> prover;
+        const Fr fr = A::scalar_from_limbs(r), fs = A::scalar_from_limbs(s);
+        const auto same = [&proof_v](const typename prover::proof_type &p) { return p.g_A == proof_v.g_A && p.g_B == proof_v.g_B && p.g_C == proof_v.g_C; };
+        const std::int64_t callers_tiles = ctx.get_option("msm_sort_tile_log");
+        r1cs_gg_ppzksnark_proving_key_hip<Curve> two(ctx, pk, dom);
+        two.side_stream_min = 0;
+        ctx.set_option("msm_sort_tile_log", 13);
+        if (!same(prover::process(two, primary, auxiliary, fr, fs))) return -130;
+        if (!two.work.side || &two.g2_context() != two.work.side.get() || ctx.get_option("msm_sort_tile_log") != 13) return -131;
+        /* an assignment one element short is refused on the host, before anything is launched; the key proves on */
+        const std::vector<Fr> short_auxiliary(auxiliary.begin(), auxiliary.end() - 1);
+        bool refused = false;
+        try {
+            (void)prover::process(two, primary, short_auxiliary, fr, fs);
+        } catch (const std::runtime_error &) {
+            refused = true;
+        }
+        if (!refused || ctx.get_option("msm_sort_tile_log") != 13) return -132;
+        if (!same(prover::process(two, primary, auxiliary, fr, fs))) return -133;
+        /* one stream on a key that owns a second one (the benchmark's profile pass) */
+        two.overlap_g2 = false;
+        if (&two.g2_context() != &ctx || !same(prover::process(two, primary, auxiliary, fr, fs)) || ctx.get_option("msm_sort_tile_log") != 13) return -134;
+        two.overlap_g2 = true;
+        /* the partial sums staying on the device for the exchange: at world 1 the "all-gather" is a copy */
+        const std::size_t bytes = prover::partial_limbs() * 8;
+        auto d_mine = ctx.alloc(bytes), d_all = ctx.alloc(bytes);
+        const auto pg = prover::process_device_gather(two, primary, auxiliary, fr, fs, d_mine.get(), d_all.get(), [&]() {
+            ZKHIP_CALL(ctx, zkhip_memcpy_d2d_async, d_all.get(), d_mine.get(), bytes);
+            ctx.sync();
+        });
+        if (!same(pg) || ctx.get_option("msm_sort_tile_log") != 13) return -135;
+        ctx.set_option("msm_sort_tile_log", callers_tiles);
+    }
     if (g_dom_kind < 0) {
         /* the reference's own argument lists: a key from (pk) alone, witness_map(cs, x, w) -- default context, the domain's constants from
            the curve adapter; the test's omega must be the adapter's root */

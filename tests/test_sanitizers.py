@@ -23,7 +23,7 @@ def _run(exe, what, env_extra):
     return out.returncode, out.stdout
 
 
-@pytest.mark.parametrize("what", ["threads", "fuzz", "table_cache", "options", "fr_vector_layer"])
+@pytest.mark.parametrize("what", ["threads", "fuzz", "table_cache", "options", "fr_vector_layer", "groth16_unwind"])
 def test_host_shim_under_asan_ubsan(what):
     rc, log = _run(_build("sanitize/sanitize_asan"), what, {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"})
     assert rc == 0 and "sanitize_main: ok" in log, log[-4000:]
@@ -37,7 +37,7 @@ def test_host_shim_under_asan_ubsan(what):
 
 
 def test_host_shim_under_tsan():
-    for what in ("threads", "table_cache", "options", "fr_vector_layer"):
+    for what in ("threads", "table_cache", "options", "fr_vector_layer", "groth16_unwind"):
         rc, log = _run(_build("sanitize/sanitize_tsan"), what, {"TSAN_OPTIONS": "halt_on_error=0"})
         assert rc == 0 and "sanitize_main: ok" in log, log[-4000:]
         assert "ThreadSanitizer" not in log, log[-4000:]
