@@ -7,8 +7,11 @@
 // (g16/marshalling.hpp:111-112, 178-201; pinned by the literal vectors of
 // test/systems/ppzksnark/r1cs_gg_ppzksnark/r1cs_gg_ppzksnark_aggregation_conformity.cpp:932-1010).
 // y is recovered from y^2 = x^3 + 4 (G1) or x^3 + 4 (1 + u) (G2); p = 3 mod 4, so a square root in Fq is one
-// exponentiation by (p + 1) / 4, and a square root in Fq2 = Fq[u]/(u^2 + 1) takes the "complex method" (two or three
-// Fq square roots and one inversion).  No subgroup check (the reference's deserializers do not make one either).
+// exponentiation by (p + 1) / 4, and a square root in Fq2 = Fq[u]/(u^2 + 1) takes the "complex method": the root of the
+// norm, then the root of (a0 + s) / 2 or of (a0 - s) / 2 (two or three Fq square roots, and two inversions: of 2 and of
+// 2 y0); an a = x^3 + b without imaginary part is (sqrt(a0), 0) or (0, sqrt(-a0)) (one or two roots, no inversion).
+// The candidate is squared and compared before it is accepted.  Of {y, -y} the larger one is the one whose c1 is above
+// (p - 1) / 2, or whose c0 is when c1 == 0.  No subgroup check (the reference's deserializers do not make one either).
 #include "ctx.hpp"
 #include "curve.hpp"
 

@@ -111,6 +111,45 @@ def test_structured_products(ctx, n):
         p.free(), q.free()
 
 
+def test_structured_product_that_cancels(ctx):
+    """n = 65 with b[64] chosen so that sum a_i b_i = 0 mod r: the pair that cancels the first workgroup's 64 sits in the second"""
+    n = 65
+    rnd = random.Random(55)
+    a = [rnd.randrange(1, R) for _ in range(n)]
+    b = [rnd.randrange(1, R) for _ in range(n - 1)]
+    b.append((-dot(a[:64], b)) * pow(a[64], -1, R) % R)
+    assert b[64] != 0 and dot(a, b) == 0 and dot(a[:64], b[:64]) != 0
+    p, q = ctx.bases_from_scalars(BLS, G1, fr_arr(a)), ctx.bases_from_scalars(BLS, G2, fr_arr(b))
+    try:
+        out = ctx.pairing_products([(p, 0, q, 0, n, 0), (p, 0, q, 0, 64, 1)], 2)
+        assert gt_ints(out[0]) == ONE
+        assert gt_ints(out[1]) == pr.structured_expectation(dot(a[:64], b[:64])) != ONE
+    finally:
+        p.free(), q.free()
+
+
+def test_explicit_pairs_that_cancel_and_a_repeated_pair(ctx):
+    """e(P, Q) e(-P, Q) = e(P, Q) e(P, -Q) = 1 with the negations made by hand on the coordinates (y, respectively y.c0 and y.c1), and
+    e(P, Q)^2 from the same pair twice"""
+    rnd = random.Random(56)
+    Pt, Q = g1.mul(g1.gen, rnd.randrange(1, R)), g2.mul(g2.gen, rnd.randrange(1, R))
+    neg_P = (Pt[0], pr.P - Pt[1])
+    neg_Q = (Q[0], (pr.P - Q[1][0], pr.P - Q[1][1]))
+    assert g1.on_curve(neg_P) and g2.on_curve(neg_Q) and g1.add(Pt, neg_P) is None and g2.add(Q, neg_Q) is None
+    p, q = upload_g1(ctx, [Pt, neg_P, Pt, Pt]), upload_g2(ctx, [Q, Q, neg_Q])
+    try:
+        # [(P, Q), (-P, Q)], [(P, Q), (P, -Q)], [(P, Q), (P, Q)], [(P, Q)]
+        out = ctx.pairing_products([(p, 0, q, 0, 2, 0), (p, 2, q, 1, 2, 1), (p, 2, q, 0, 2, 2), (p, 0, q, 0, 1, 3)], 4)
+        assert gt_ints(out[0]) == ONE and gt_ints(out[1]) == ONE
+        single = pr.pairing_product([(Pt, Q)])
+        assert gt_ints(out[3]) == single != ONE
+        assert gt_ints(out[2]) == pr.pairing_product([(Pt, Q), (Pt, Q)])
+        e = pr.from_canonical(single)
+        assert gt_ints(out[2]) == pr.to_canonical(pr.f12_mul(e, e))
+    finally:
+        p.free(), q.free()
+
+
 def test_infinity_placement(ctx):
     """infinity at the first, last and a middle index in G1, in G2, and in both at one index; an output whose pairs are all at infinity and
     one that no term names are one"""
