@@ -17,6 +17,7 @@ namespace arith {
 //     34 fu_pow_onto(c, a, e) -- e the 64-bit integer in b's first two words -- and, where NL = 8, 35 fu_store8 / fu_load8 of a through
 //     element 1 of a 16-byte aligned three-element buffer (out: the element read back, or all-ones limbs if a neighbour changed) and
 //     36 a^e for the 256-bit e in b's first 8 words: fu_pow_onto word by word from the top, fu_pow(r, 2^32) between.
+//     Where L = 9 (the scalar fields' compute form): 37 fu_reduce_small(a), the product-free reduction of an NTT's last store.
 // L u32 in per operand and L u32 out per case, exactly as a kernel holds them (no normalisation on the way in).
 template <class U>
 struct MaxSpread {  // largest K with a spread constant: every lazy type has 128 except the 255-bit scalar fields
@@ -39,6 +40,7 @@ template <class U>
 ZK_HD bool fu_raw_valid(int op) {
     if ((op >= 0 && op <= 10) || (op >= 30 && op <= 34)) return true;
     if (op == 35 || op == 36) return U::NL == 8;
+    if (op == 37) return U::L == 9;
     return op >= 21 && op <= 27 && (1 << (op - 20)) <= MaxSpread<U>::K;
 }
 
@@ -70,6 +72,13 @@ ZK_HD Fu<U> fu_raw_words8(int op, const Fu<U> &x, const uint32_t *b) {
     return r;
 }
 
+// op 37, which only the 9-limb types have
+template <class U>
+ZK_HD Fu<U> fu_raw_limbs9(const Fu<U> &x) {
+    if constexpr (U::L == 9) return fu_reduce_small(x);
+    return Fu<U>::zero();
+}
+
 template <class U>
 ZK_HD void fu_raw_one(int op, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d, uint32_t *out) {
     constexpr int L = U::L;
@@ -99,6 +108,7 @@ ZK_HD void fu_raw_one(int op, const uint32_t *a, const uint32_t *b, const uint32
         case 34: r = fu_pow_onto(z, x, (uint64_t)b[0] | ((uint64_t)b[1] << 32)); break;
         case 35:
         case 36: r = fu_raw_words8(op, x, b); break;
+        case 37: r = fu_raw_limbs9(x); break;
         case 21: r = sub_k<2>(x, y); break;
         case 22: r = sub_k<4>(x, y); break;
         case 23: r = sub_k<8>(x, y); break;

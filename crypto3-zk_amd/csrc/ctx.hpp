@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/zkhip.h"
+#include "ntt_plan.hpp"
 #include "options.hpp"
 #include "table_cache.hpp"
 #include "zk_defs.hpp"
@@ -161,7 +162,6 @@ struct ZkProfile {
 };
 
 // The device tables a context keeps across calls (the caches at the end of zkhip_ctx; protocol: table_cache.hpp)
-static constexpr int NTT_MAX_PASSES = 32;  // log_m <= 32 at radix 2
 struct NttTables {  // one radix-2 transform (ntt.hip: ntt_get_tables)
     int curve;
     size_t log_m;

@@ -10,6 +10,7 @@
 #include "arith_ops.h"
 #include "glv.hpp"
 #include "msm_recode.hpp"
+#include "ntt_plan.hpp"
 #include "pairing.hpp"
 #include "pow.hpp"
 #include "sha256.hpp"
@@ -75,6 +76,23 @@ int zkt_fu_raw(int type, int op, size_t n, const uint32_t *a, const uint32_t *b,
         default: return -1;
     }
 #undef FU_RAW
+}
+
+// The radix plan ntt.hip runs a 2^log_m transform with under the options ntt_radix_log = smax (1 .. 10) and ntt_tile_log (ntt_plan.hpp):
+// returns the number of passes, sv[i] and log_t[i] (NTT_MAX_PASSES ints each) the stages and the tile width of pass i; -1 for bad arguments
+int zkt_ntt_plan(size_t log_m, int smax, int tile_log, int *sv, int *log_t) {
+    if (!sv || !log_t || log_m == 0 || log_m > 32 || smax < 1 || smax > 10) return -1;
+    const NttPlan pl = ntt_plan(log_m, smax, tile_log);
+    for (int i = 0; i < pl.np; ++i) sv[i] = pl.sv[i], log_t[i] = pl.log_t[i];
+    return pl.np;
+}
+// the shape ntt_run_t launches a pass of s stages and a planned tile width with, over `count` polynomials of which pb (1, 2, 4) are wanted
+// per workgroup: out = {polynomials per workgroup, log2 of the tile width, bytes of LDS}
+int zkt_ntt_launch(int s, int log_t, int pb, size_t count, uint64_t *out) {
+    if (!out || s < 1 || s > 10 || log_t < 0 || log_t > 12 || (pb != 1 && pb != 2 && pb != 4) || count == 0) return -1;
+    const NttLaunchShape sh = ntt_launch_shape((uint32_t)s, (uint32_t)log_t, pb, count);
+    out[0] = (uint64_t)sh.pb, out[1] = sh.log_t, out[2] = sh.lds;
+    return 0;
 }
 
 // the scalar fields have no curve over them here

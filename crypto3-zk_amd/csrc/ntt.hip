@@ -7,7 +7,7 @@
 // Natural order in, natural order out, out[i] = sum_j in[j] omega^(ij): the result is the DFT itself,
 // so it is bit-identical to any correct radix-2 implementation.
 //
-// Algorithm: multi-pass Stockham autosort.  m = R_1 R_2 ... R_p, R_i = 2^(s_i), s_i <= 8.  Pass i with
+// Algorithm: multi-pass Stockham autosort.  m = R_1 R_2 ... R_p, R_i = 2^(s_i), s_i <= 10 (option "ntt_radix_log", 8 by default).  Pass i with
 // running sub-transform size Ns = R_1...R_(i-1) does, for every j in [0, m/R):
 //     k = j mod Ns;   u[t] = x[j + t m/R] * omega_(Ns R)^(k t);   v = DFT_R(u);   y[(j-k) R + k + t' Ns] = v[t']
 // The factor omega_(Ns R)^(k t) of pass i+1 is applied by pass i while it STORES (each stored element knows
@@ -17,7 +17,8 @@
 // One workgroup owns a tile of T consecutive j's x all R values of t, staged in LDS as 9 x 29-bit lazy limbs
 // (fu.hpp; three planes: 16 B + 16 B + 4 B per element, so every LDS access is conflict-free).  Rows are
 // written bit-reversed, the stages are decimation-in-time, (a, b) -> (a + w b, a - w b), so values grow by at
-// most 4p per stage (33p after 8 stages, inside the 6-7 bits of slack of R = 2^261) and are only carry-
+// most 4p per stage from the 2p they are loaded with (34p after the default 8 stages, 2p + 4p * 10 = 42p after the 10 the
+// plan admits: below the 64p that fu_reduce_small takes and inside the 6-7 bits of slack of R = 2^261) and are only carry-
 // normalised; the product at the store brings them back below 2p, one conditional subtraction makes them
 // canonical.  Global reads are runs of T*32 B, writes runs of >= T*32 B.
 //
@@ -29,17 +30,16 @@
 //   stage     omega_R^q, q < R/2, staged in LDS per workgroup without any arithmetic.
 // The tables are built once per (size, omega, direction, coset, radix plan) from a two-level power table and cached
 // in the context.  A last pass with nothing to multiply by (forward, no coset) brings its lazy values (< 64p) back
-// below p by a 7-bit quotient estimate instead of a product (fu_reduce_small).
+// below p by a 7-bit quotient estimate instead of a product (fu.hpp: fu_reduce_small).
 // Two radix-2 stages run per LDS round trip (a thread holds the four rows i0 + {0, h, 2h, 3h}: the same four products
 // as two separate stages, half the LDS traffic and barriers).
 #include <algorithm>
 
 #include "ctx.hpp"
 #include "fu.hpp"
+#include "ntt_plan.hpp"
 
 using namespace zkhip;
-
-static constexpr uint32_t NTT_PAD = 0;  // extra elements per LDS row (see lds_get)
 
 struct NttPass {
     const uint32_t *in;
@@ -139,7 +139,6 @@ ZK_D void lds_put(uint4 *lds, uint32_t slots, uint32_t e, const Fu<U> &x) {
     lds[slots + e] = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
     reinterpret_cast<uint32_t *>(lds + 2 * slots)[e] = x.v[8];
 }
-ZK_HD uint32_t ntt_tile_u4(uint32_t slots) { return 2 * slots + (slots + 3) / 4; }  // uint4 units of one tile's three planes
 
 // "limb form": the 9 x 29-bit limbs as they are -- limbs 0-7 in 32 bytes at element index i, limb 8 in a 4-byte plane
 // `planeb` words behind the array's base.  The factor tables and the intermediate vectors between passes use it: no
@@ -161,31 +160,6 @@ ZK_D void l_store(uint32_t *base, size_t planeb, size_t i, const Fu<U> &x) {
     q[0] = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
     q[1] = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
     base[planeb + i] = x.v[8];
-}
-
-// normalised limbs, value < 64 p  ->  [0, p), without a Montgomery product: q = floor(x / p) is estimated from the
-// top 13 bits of x with a 24-bit reciprocal (one short too low at most), x - q p < 2p, one conditional subtraction.
-template <class U>
-ZK_D Fu<U> fu_reduce_small(const Fu<U> &x) {
-    constexpr int L = U::L, B = U::B;
-    static_assert(L == 9 && B == 29, "sized for the 9 x 29-bit scalar fields");
-    // mu = floor(2^272 / p), p < 2^255  =>  mu < 2^24 for p > 2^248; t = x >> 248 < 2^13
-    constexpr uint32_t mu = U::MU272;
-    const uint32_t t = x.v[8] >> 16;
-    const uint32_t q = (uint32_t)(((uint64_t)t * mu) >> 24);
-    Fu<U> y;
-    uint64_t carry = 0;  // q p, limb by limb
-    uint32_t borrow = 0;
-#pragma unroll
-    for (int i = 0; i < L; ++i) {
-        carry += (uint64_t)q * U::mod(i);
-        const uint32_t qp = (uint32_t)carry & Fu<U>::MASK;
-        carry >>= B;
-        const uint32_t d = x.v[i] - qp - borrow;  // limbs < 2^30: bit 31 of d is its sign
-        borrow = i + 1 < L ? d >> 31 : 0;
-        y.v[i] = i + 1 < L ? d & Fu<U>::MASK : d;
-    }
-    return fu_cond_sub_p(y);
 }
 
 // tw[oi] for one pass boundary (output order of the pass being stored = input order of the next): the next pass's
@@ -368,23 +342,7 @@ __global__ __launch_bounds__(256) void ntt_pass(NttPass p) {
 }
 
 // ---- host side ------------------------------------------------------------------------------------
-// the radix plan: log_m split into np nearly equal radices (larger first), tile widths
-struct NttPlan {
-    int np;
-    int sv[NTT_MAX_PASSES], log_t[NTT_MAX_PASSES];
-};
-static NttPlan ntt_plan(size_t log_m, int smax, int tile_log) {
-    NttPlan pl;
-    pl.np = (int)((log_m + smax - 1) / smax);
-    for (int i = 0; i < pl.np; ++i) {
-        pl.sv[i] = (int)(log_m / pl.np) + (i < (int)(log_m % pl.np) ? 1 : 0);
-        const int log_cols = (int)log_m - pl.sv[i];  // log2(m / R)
-        pl.log_t[i] = std::min(std::max(0, tile_log), log_cols);
-        while (pl.sv[i] + pl.log_t[i] > 12 && pl.log_t[i] > 0) --pl.log_t[i];  // LDS budget: R * T * 36 B <= 144 KiB
-    }
-    return pl;
-}
-
+// (the radix plan and the shape of a pass's launch: ntt_plan.hpp)
 template <class U>
 static int ntt_get_tables(zkhip_ctx *ctx, int curve, size_t log_m, const uint64_t *omega, int inverse, const uint64_t *coset, int smax, int tile_log,
                           NttTables **out) {
@@ -536,7 +494,6 @@ static int ntt_run_t(zkhip_ctx *ctx, int curve, uint32_t *d_data, size_t log_m, 
         p.ext_k1 = ext ? ext->k1 : 0u;
         p.ext_log_k = ext ? ext->log_k : 0u;
         p.ext_pre = ext ? ext->pre : nullptr;
-        const size_t nhalf = std::max<size_t>(1, ((size_t)1 << p.s) / 2);
         // PB = 1, 2 or 4 polynomials of the batch per workgroup (they share indices, twiddle registers and the factor-table
         // reads) while the tiles leave room for a second workgroup on the CU; option "ntt_pair" = log2(PB) wanted.  A batch that PB
         // does not divide runs its remainder as one more launch of single polynomials (round 5: an odd batch -- a lone polynomial's
@@ -547,34 +504,31 @@ static int ntt_run_t(zkhip_ctx *ctx, int curve, uint32_t *d_data, size_t log_m, 
         auto launch = [&](NttPass q, int pb, size_t first, size_t count) -> int {
             if (count == 0) return 0;
             q.poly_base = (uint32_t)first;
-            // a narrower tile that lets the polynomials share a workgroup beats a wider one that does not (measured)
-            while (pb > 1 && q.log_t > 2 && ((size_t)pb * ntt_tile_u4((1u << q.s) * ((1u << q.log_t) + NTT_PAD)) + ntt_tile_u4((uint32_t)nhalf)) * 16 > 80 * 1024) {
-                --q.log_t;
-                q.tiles_per_poly <<= 1;
-            }
-            const size_t slots_p = ((size_t)1 << q.s) * (((size_t)1 << q.log_t) + NTT_PAD);
-            while (pb > 1 && (((size_t)pb * ntt_tile_u4((uint32_t)slots_p) + ntt_tile_u4((uint32_t)nhalf)) * 16 > 80 * 1024 || count % pb != 0)) pb >>= 1;
+            const NttLaunchShape sh = ntt_launch_shape(q.s, q.log_t, pb, count);
+            q.tiles_per_poly <<= q.log_t - sh.log_t;
+            q.log_t = sh.log_t;
+            pb = sh.pb;
             const size_t nelem_p = (size_t)1 << (q.s + q.log_t);
-            const size_t lds = ((size_t)pb * ntt_tile_u4((uint32_t)slots_p) + ntt_tile_u4((uint32_t)nhalf)) * 16;
+            const size_t lds = sh.lds;
             const size_t grid = count / pb * q.tiles_per_poly;
             if (grid >= (1ull << 31)) return ZKHIP_ERR_RANGE;
             const unsigned threads = (unsigned)std::min<size_t>(256, std::max<size_t>(64, nelem_p / 4));
             if (ext) {  // pairs or singles (four per workgroup is the slow shape: DESIGN.md section 5)
                 if (pb >= 2) {
-                    ZK_MAX_LDS(ctx, (ntt_pass<U, 2, true>), 160 * 1024);
+                    ZK_MAX_LDS(ctx, (ntt_pass<U, 2, true>), NTT_MAX_LDS);
                     ZK_LAUNCH(ctx, "ntt_pass_ext", (ntt_pass<U, 2, true>), dim3((unsigned)grid), dim3(threads), lds, q);
                 } else {
-                    ZK_MAX_LDS(ctx, (ntt_pass<U, 1, true>), 160 * 1024);
+                    ZK_MAX_LDS(ctx, (ntt_pass<U, 1, true>), NTT_MAX_LDS);
                     ZK_LAUNCH(ctx, "ntt_pass_ext", (ntt_pass<U, 1, true>), dim3((unsigned)grid), dim3(threads), lds, q);
                 }
             } else if (pb == 4) {
-                ZK_MAX_LDS(ctx, (ntt_pass<U, 4>), 160 * 1024);
+                ZK_MAX_LDS(ctx, (ntt_pass<U, 4>), NTT_MAX_LDS);
                 ZK_LAUNCH(ctx, "ntt_pass", (ntt_pass<U, 4>), dim3((unsigned)grid), dim3(threads), lds, q);
             } else if (pb == 2) {
-                ZK_MAX_LDS(ctx, (ntt_pass<U, 2>), 160 * 1024);
+                ZK_MAX_LDS(ctx, (ntt_pass<U, 2>), NTT_MAX_LDS);
                 ZK_LAUNCH(ctx, "ntt_pass", (ntt_pass<U, 2>), dim3((unsigned)grid), dim3(threads), lds, q);
             } else {
-                ZK_MAX_LDS(ctx, (ntt_pass<U, 1>), 160 * 1024);
+                ZK_MAX_LDS(ctx, (ntt_pass<U, 1>), NTT_MAX_LDS);
                 ZK_LAUNCH(ctx, "ntt_pass", (ntt_pass<U, 1>), dim3((unsigned)grid), dim3(threads), lds, q);
             }
             return 0;

@@ -17,6 +17,7 @@ TYPES = {6: (po.BLS12_381.p, 14, 12, 128), 7: (po.BN254.p, 10, 8, 128), 8: (po.B
 OP_MUL, OP_SQR, OP_MUL2, OP_ADD, OP_COND_SUB, OP_CANON, OP_IS_ZERO, OP_INV, OP_INV_GCD, OP_PACK, OP_UNPACK = range(11)
 # the element layer of the scalar-field kernels (fu.hpp: fu_mulm .. fu_load8); OP_IO8 and OP_POW_WIDE exist for the 8-word types only
 OP_MULM, OP_ADDM, OP_FROM_MONT, OP_POW, OP_POW_ONTO, OP_IO8, OP_POW_WIDE = range(30, 37)
+OP_REDUCE_SMALL = 37  # fu_reduce_small: the 9-limb scalar types only
 # exponents of the 64-bit powers: 0 .. 3, 2^k and 2^k - 1 around the word boundary and at the top bit, all ones
 POW_EXPONENTS = [0, 1, 2, 3] + [x for k in (31, 32, 33, 63) for x in (1 << k, (1 << k) - 1)] + [(1 << 64) - 1]
 
@@ -287,6 +288,26 @@ def pow_cases(t, rng):
     return out
 
 
+def reduce_small_cases(t):
+    """fu_reduce_small: normalised limbs, value < 64p.  k p + d for k = 0 .. 63 and d in {-1, 0, 1, p // 2, p - 1} (both sides of every multiple of
+    p the quotient estimate has to tell apart); both ends t 2^248 and (t + 1) 2^248 - 1 of every value t of the estimate's 13-bit input x >> 248
+    that a value below 64p can have; 64p - 1"""
+    p, L = TYPES[t][0], TYPES[t][1]
+    assert L == 9 and 1 << 248 < p < 1 << 255
+    vals = {k * p + d for k in range(64) for d in (-1, 0, 1, p // 2, p - 1)}
+    tops = range((64 * p - 1 >> 248) + 1)
+    assert tops[-1] < 1 << 13
+    vals |= {x for top in tops for x in (top << 248, (top + 1 << 248) - 1)}
+    vals.add(64 * p - 1)
+    out = []
+    for x in sorted(v for v in vals if 0 <= v < 64 * p):
+        v = split(x, L)
+        assert normalised(v) and v[8] >> 16 == x >> 248
+        out.append(v)
+    assert len(out) > 6000 and value(out[-1]) == 64 * p - 1
+    return out
+
+
 def exp_words(e, L):
     """an exponent as saturated u32 words in an L-word operand slot"""
     assert e < 1 << 256
@@ -390,6 +411,9 @@ def check_raw(t, op, a, b, c, d, r, k=None):
             return "power: e = 0 leaves the seed as it is"
         if e and not (normalised(r) and got < 2 * p):
             return "postcondition: normalised, < 2p"
+    elif op == OP_REDUCE_SMALL:
+        if r != split(va % p, L):
+            return "canonical limbs of x mod p"
     elif op == OP_IO8:
         if list(r) != list(a):
             return "16-byte store / load round trip"
@@ -420,6 +444,8 @@ def raw_suite(t, seed=0):
               (OP_FROM_MONT, None, [(a, z, z, z) for a in canon_cases(t, rng)]),
               (OP_POW, None, [(base, exp_words(e, L), z, z) for _, base, e in powers]),
               (OP_POW_ONTO, None, [(base, exp_words(e, L), seed, z) for seed, base, e in powers])]
+    if L == 9:
+        suite.append((OP_REDUCE_SMALL, None, [(a, z, z, z) for a in reduce_small_cases(t)]))
     if NL == 8:
         p = TYPES[t][0]
         wide = [p - 1, 0, 1, 1 << 64, (1 << 64) + 1, (1 << 256) - 1]

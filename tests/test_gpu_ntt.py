@@ -1,5 +1,6 @@
 """Parity of the HIP NTT (through the C ABI) against the oracle: every size 2^0..2^13, batches,
-forward / inverse / coset, the tunables that change the pass structure, and BASELINE config 3 (2^22 x 8)
+forward / inverse / coset, the tunables that change the pass structure (passes of 9 and 10 stages, every mode under non-default
+plans), the two- and three-pass sizes 2^14 .. 2^21, edge vectors through 8-stage passes, and BASELINE config 3 (2^22 x 8)
 through a bit-exact comparison plus round-trip and random-point (Horner) properties."""
 import numpy as np
 import pytest
@@ -92,6 +93,94 @@ def _edge_values(ctx, curve):
     exp = cp.ntt(curve, vecs, log_m, w)
     assert (ctx.ntt(curve, vecs, log_m, w) == exp).all()
     assert fr_ints(exp[3])[0] == 7 * m % C.r and all(v == 0 for v in fr_ints(exp[3])[1:])
+
+
+NTT_DEFAULTS = {"ntt_radix_log": 8, "ntt_tile_log": 3, "ntt_pair": 1}
+MODES = [dict(), dict(inverse=True), dict(coset=True), dict(inverse=True, coset=True)]
+
+
+def _set_plan(ctx, **opts):
+    """set the pass-structure options and read them back"""
+    for name, v in opts.items():
+        ctx.set_option(name, v)
+        assert ctx.get_option(name) == v, name
+
+
+def _modes_against_oracle(ctx, curve, a, log_m, modes, batches, tag=()):
+    """forward / inverse / coset / inverse coset of the batch `a` against the oracle, once per batch size (a prefix of `a`: one reference)"""
+    C = CURVES[curve]
+    w, g = limbs(C.root_of_unity(log_m), 4), limbs(C.fr_generator, 4)
+    for mode in modes:
+        kw = dict(inverse=mode.get("inverse", False), coset=g if mode.get("coset") else None)
+        exp = cp.ntt(curve, a, log_m, w, **kw)
+        for b in batches:
+            assert (ctx.ntt(curve, a[:b], log_m, w, **kw) == exp[:b]).all(), (curve, log_m, b, mode) + tuple(tag)
+
+
+@pytest.mark.parametrize("curve", [0, 3])
+@pytest.mark.parametrize("radix,log_m", [(9, 9), (9, 18), (10, 10), (10, 19), (10, 20)])
+def test_ntt_deep_passes(ctx, curve, radix, log_m):
+    """ntt_radix_log 9 and 10: passes of 9 and 10 stages, where the lazy values reach 2p + 4p * 9 = 38p and 42p before the store (the
+    file's bound is written for any count up to 10; the default plan stops at 8).  2^9 and 2^10: one pass, one column.  2^18: (9, 9),
+    8 columns per tile.  2^19, 2^20: (10, 9) and (10, 10) -- the 10-stage passes whose tile the planner narrows to 2 columns so that the
+    stage table fits behind it (tests/test_ntt_model.py walks the arithmetic).  One polynomial and three (a pair and a single launch per pass)."""
+    a = cp.random_fr(curve, 5000 + log_m, 3 << log_m).reshape(3, 1 << log_m, 4)
+    try:
+        _set_plan(ctx, ntt_radix_log=radix, ntt_tile_log=3, ntt_pair=1)
+        _modes_against_oracle(ctx, curve, a, log_m, MODES, (1, 3), (radix,))
+    finally:
+        _set_plan(ctx, **NTT_DEFAULTS)
+
+
+@pytest.mark.parametrize("curve", [0, 3])
+def test_ntt_modes_under_non_default_plans(ctx, curve):
+    """the grid of _pass_structure_options runs the forward transform only: here the inverse (1 / m folded into the first boundary's
+    table; the scale of a single pass), the coset (g^i at the first load) and the inverse coset ((1 / m) g^-i at the last store) under
+    plans of 11, 4, 3 and 2 passes, tiles of 1 and 16 columns, one and four polynomials wanted per workgroup, a batch of 2 and an odd one"""
+    log_m = 11
+    a = cp.random_fr(curve, 5011, 3 << log_m).reshape(3, 1 << log_m, 4)
+    try:
+        for radix in (1, 3, 5, 8):
+            for tile in (0, 4):
+                for pair in (0, 2):
+                    _set_plan(ctx, ntt_radix_log=radix, ntt_tile_log=tile, ntt_pair=pair)
+                    _modes_against_oracle(ctx, curve, a, log_m, MODES[1:], (2, 3), (radix, tile, pair))
+    finally:
+        _set_plan(ctx, **NTT_DEFAULTS)
+
+
+@pytest.mark.parametrize("curve", [0, 3])
+def test_ntt_edge_vectors_through_8_stage_passes(ctx, curve):
+    """all-zero, all-(r - 1), a delta at 0 and at m - 1 and the constant 7 at 2^16, the default plan (8, 8): _edge_values' 2^9 is planned
+    (5, 4).  Forward and inverse against the oracle.  The constant's transform is 7 m at index 0 and zero elsewhere: 2^16 - 1 values that
+    reach the last store as lazy multiples of p (up to 34p) and go through fu_reduce_small."""
+    C = CURVES[curve]
+    log_m = 16
+    m = 1 << log_m
+    assert ctx.get_option("ntt_radix_log") == 8 and ctx.get_option("ntt_tile_log") == 3
+    w = limbs(C.root_of_unity(log_m), 4)
+    vecs = np.zeros((5, m, 4), dtype=np.uint64)
+    vecs[1, :] = limbs(C.r - 1, 4)
+    vecs[2, 0] = limbs(C.r - 1, 4)
+    vecs[3, m - 1] = limbs(1, 4)
+    vecs[4, :] = limbs(7, 4)
+    got = ctx.ntt(curve, vecs, log_m, w)
+    assert (got == cp.ntt(curve, vecs, log_m, w)).all()
+    assert not got[0].any()
+    assert (got[4, 0] == np.array(limbs(7 * m % C.r, 4), dtype=np.uint64)).all() and not got[4, 1:].any()
+    assert (got[1, 0] == np.array(limbs((C.r - 1) * m % C.r, 4), dtype=np.uint64)).all() and not got[1, 1:].any()
+    assert (got[2] == np.array(limbs(C.r - 1, 4), dtype=np.uint64)).all()
+    inv = ctx.ntt(curve, vecs, log_m, w, inverse=True)
+    assert (inv == cp.ntt(curve, vecs, log_m, w, inverse=True)).all()
+    assert (ctx.ntt(curve, got, log_m, w, inverse=True) == vecs).all()
+
+
+@pytest.mark.parametrize("log_m", [14, 15, 16, 18, 19, 20, 21])
+def test_ntt_plain_sizes_between_the_tested_ones(ctx, log_m):
+    """zkhip_ntt itself at the two-pass sizes (7, 7) .. (8, 8) and the three-pass sizes (6, 6, 6) .. (7, 7, 7) that the suite reached only
+    through resize and the arguments: one polynomial, forward and inverse coset against the oracle"""
+    a = cp.random_fr(0, 5100 + log_m, 1 << log_m).reshape(1, 1 << log_m, 4)
+    _modes_against_oracle(ctx, 0, a, log_m, (MODES[0], MODES[3]), (1,))
 
 
 def test_ntt_full_size_2_22_batch_8(ctx):

@@ -5,7 +5,9 @@ Checked against the reference's own vectors (tests/golden/ref_ipp2_kat.json: kzg
 2 outputs), against the big-integer model (tests/pairing_ref.py) on unstructured pairs, and at larger sizes by structure: with
 P_i = a_i G1 and Q_i = b_i G2 built on the device, the product is the model's e(G1, G2)^(sum a_i b_i mod r) -- one exponentiation on the
 oracle side whatever n is.  Sizes: 63 / 64 / 65 around the 64-lane workgroup of the Miller kernel (one pair per lane), 257 (several
-workgroups, not a power of two), 1100 (more than the 16 tiles one workgroup of the product kernel takes: two partials for one output)."""
+workgroups, not a power of two), 1100 (more than the 16 tiles one workgroup of the product kernel takes: two partials for one output),
+1024 / 1025 (exactly 16 tiles and one more), and more than 64 partials -- 70 one-pair terms into three outputs, one term of 65537 pairs --
+where a lane of the final kernel multiplies several (tests/THRESHOLDS.md)."""
 import ctypes
 import json
 import random
@@ -109,6 +111,52 @@ def test_structured_products(ctx, n):
         assert gt_ints(ctx.pairing_products([(p, 0, q, 0, n, 0)], 1)[0]) == pr.structured_expectation(dot(a, b))
     finally:
         p.free(), q.free()
+
+
+@pytest.mark.parametrize("n", [1024, 1025])
+def test_structured_products_at_the_product_workgroup_boundary(ctx, n):
+    """a workgroup of pairing_product_blocks takes PROD_TILES = 16 tiles of 64 pairs: 1024 pairs fill one exactly, the 1025th opens a second
+    workgroup with one tile of one live lane"""
+    p, q, a, b = structured(ctx, 50 + n, n)
+    try:
+        assert gt_ints(ctx.pairing_products([(p, 0, q, 0, n, 0)], 1)[0]) == pr.structured_expectation(dot(a, b))
+    finally:
+        p.free(), q.free()
+
+
+def test_seventy_terms_into_three_outputs_with_empty_terms_in_the_table(ctx):
+    """70 terms of one pair each, term t into output t mod 3 of 4, with a zero-length term in front of them and one in the middle of the
+    table (find_term walks past a term without tiles to the one that owns the workgroup).  70 partials reach pairing_product_final: more
+    than its 64 lanes, so lanes 0 .. 5 take two each (the stride loop), and every lane skips the partials of the other outputs.  Output k is
+    e(G1, G2)^(sum of a_t b_t over its terms); output 3, which only an empty term names, is one."""
+    n = 70
+    p, q, a, b = structured(ctx, 170, n)
+    terms = [(p, t, q, t, 1, t % 3) for t in range(n)]
+    terms.insert(0, (p, 0, q, 0, 0, 3))
+    terms.insert(35, (p, 7, q, 9, 0, 1))
+    assert len(terms) == 72 and terms[0][4] == 0 and terms[35][4] == 0 and sum(t[4] for t in terms) == n
+    try:
+        out = ctx.pairing_products(terms, 4)
+        for k in range(3):
+            assert gt_ints(out[k]) == pr.structured_expectation(dot(a[k::3], b[k::3])) != ONE, k
+        assert gt_ints(out[3]) == ONE
+    finally:
+        p.free(), q.free()
+
+
+def test_one_term_of_65537_pairs(ctx):
+    """1025 tiles, 65 partials of ONE output: lane 0 of pairing_product_final multiplies two.  Then with infinity at pair 65536 -- the only
+    pair of the last tile, workgroup and partial, which is then one."""
+    n = 65537
+    p, q, a, b = structured(ctx, 171, n)
+    a2 = a[:n - 1] + [0]
+    p2 = ctx.bases_from_scalars(BLS, G1, fr_arr(a2))
+    try:
+        assert gt_ints(ctx.pairing_products([(p, 0, q, 0, n, 0)], 1)[0]) == pr.structured_expectation(dot(a, b))
+        got = gt_ints(ctx.pairing_products([(p2, 0, q, 0, n, 0)], 1)[0])
+        assert got == pr.structured_expectation(dot(a2, b)) == pr.structured_expectation(dot(a[:n - 1], b[:n - 1]))
+    finally:
+        p.free(), q.free(), p2.free()
 
 
 def test_structured_product_that_cancels(ctx):

@@ -250,6 +250,103 @@ def test_grand_products_zero_denominator(ctx, curve):
         ctx.free(p_)
 
 
+# ---- the grand products past 2^19 rows: a lane of gp_top owns more than one workgroup total -------------------------------------------------
+PERM_BLOCK = 256 * 8  # rows per workgroup of the scan kernels (perm.hip: PERM_THREADS * PERM_CHUNK)
+# 257 blocks: ceil(257 / 256) = 2 totals per lane of gp_top, lane 128 holds one and lanes 129 .. 255 none; 2^19 rows: 256 blocks, the last size with one each
+GP_TOP_SIZES = [257 * PERM_BLOCK - 3, 1 << 19]
+
+
+def _gp_top_rows(n):
+    """the last row of block 1, the first row of block 2 (lane 0 | lane 1 of gp_top where a lane owns two blocks), a row of the last block"""
+    nblk = -(-n // PERM_BLOCK)
+    assert nblk == {GP_TOP_SIZES[0]: 257, GP_TOP_SIZES[1]: 256}[n] and -(-nblk // 256) == {257: 2, 256: 1}[nblk]
+    return [2 * PERM_BLOCK - 1, 2 * PERM_BLOCK, (nblk - 1) * PERM_BLOCK + 5]
+
+
+def _dev(ctx, arr):
+    d = ctx.malloc(arr.nbytes)
+    ctx.h2d(d, np.ascontiguousarray(arr))
+    return d
+
+
+def _host(ctx, d, n):
+    out = np.zeros((n, 4), dtype=np.uint64)
+    ctx.d2h(out, d)
+    return out
+
+
+@pytest.mark.parametrize("curve", [0, 3])
+@pytest.mark.parametrize("n", GP_TOP_SIZES)
+def test_permutation_grand_product_past_the_top_scan_threshold(ctx, curve, n):
+    """zkhip_perm_grand_product_dev, one column of random values: V_P, g and h against the oracle's row-by-row recurrence; then with h = 0
+    forced at _gp_top_rows (the first decides: V_P holds a value there and is zero behind it)."""
+    r = CURVES[curve].r
+    beta, gamma = fr_ints(cp.random_fr(curve, 6400, 2))
+    cols, sid, ssig = (cp.random_fr(curve, 6410 + i, n).reshape(1, n, 4) for i in range(3))
+    d_g, d_h, d_v = ctx.malloc(n * 32), ctx.malloc(n * 32), ctx.malloc(n * 32)
+    rows = _gp_top_rows(n)
+    for variant in ("plain", "zero denominators"):
+        if variant != "plain":
+            for z in rows:
+                cols[0, z] = limbs((-(beta * fr_ints(ssig[0, z:z + 1])[0] + gamma)) % r, 4)            # h[z] = 0
+        eg, eh, ev = cp.permutation_grand_product(curve, list(cols), list(sid), list(ssig), beta, gamma)
+        if variant == "plain":
+            assert ev[n - 1].any()
+        else:
+            assert ev[rows[0]].any() and not ev[rows[0] + 1:].any() and not any(eh[0, z].any() for z in rows)
+        ptrs = [_dev(ctx, v[0]) for v in (cols, sid, ssig)]
+        ctx.perm_grand_product_dev(curve, ptrs[:1], ptrs[1:2], ptrs[2:], n, limbs(beta, 4), limbs(gamma, 4), d_g, d_h, d_v)
+        assert (_host(ctx, d_v, n) == ev).all(), variant
+        assert (_host(ctx, d_g, n) == eg[0]).all() and (_host(ctx, d_h, n) == eh[0]).all(), variant
+        for p_ in ptrs:
+            ctx.free(p_)
+        assert ctx.device_status() == 0
+    for p_ in (d_g, d_h, d_v):
+        ctx.free(p_)
+
+
+@pytest.mark.parametrize("curve", [0, 3])
+@pytest.mark.parametrize("n", GP_TOP_SIZES)
+def test_lookup_grand_product_past_the_top_scan_threshold(ctx, curve, n):
+    """zkhip_lookup_grand_product_dev with one input, one value and one sorted column, usable_rows = n - 2049: a whole trailing block of the
+    scan carries no ratio.  Against the oracle's row-by-row loop."""
+    usable = n - PERM_BLOCK - 1
+    beta, gamma = fr_ints(cp.random_fr(curve, 6500, 2))
+    inp, val, srt = (cp.random_fr(curve, 6510 + i, n) for i in range(3))
+    exp = cp.lookup_grand_product(curve, [inp], [val], [srt], beta, gamma, usable)
+    assert exp[usable].any() and not exp[usable + 1:].any()
+    ptrs = [_dev(ctx, v) for v in (inp, val, srt)]
+    d_v = ctx.malloc(n * 32)
+    ctx.lookup_grand_product_dev(curve, ptrs[:1], ptrs[1:2], ptrs[2:], n, usable, limbs(beta, 4), limbs(gamma, 4), d_v)
+    assert (_host(ctx, d_v, n) == exp).all()
+    for p_ in ptrs + [d_v]:
+        ctx.free(p_)
+    assert ctx.device_status() == 0
+
+
+@pytest.mark.parametrize("curve", [0, 3])
+@pytest.mark.parametrize("n", GP_TOP_SIZES)
+def test_fr_vec_mul_div_past_the_top_scan_threshold(ctx, curve, n):
+    """zkhip_fr_vec_mul_div_dev over `n` entries (mul_div_run shares gp_top with the grand products), zeros in c at _gp_top_rows (0^-1 = 0:
+    out is zero there, and the zero counts as 1 in the products around it), into a fourth vector and in place; against the oracle's
+    pointwise a b / c"""
+    a, b, c = (cp.random_fr(curve, 6600 + i, n) for i in range(3))
+    rows = _gp_top_rows(n)
+    c[rows] = 0
+    exp = cp.fr_vec(curve, 4, a, b, c)
+    assert not exp[rows].any() and exp[rows[0] - 1].any() and exp[n - 1].any()
+    d_a, d_b, d_c = (_dev(ctx, v) for v in (a, b, c))
+    d_o = ctx.malloc(n * 32)
+    ctx.fr_vec_mul_div_dev(curve, d_a, d_b, d_c, d_o, n)
+    assert (_host(ctx, d_o, n) == exp).all()
+    assert ctx.device_status() == 0
+    ctx.fr_vec_mul_div_dev(curve, d_a, d_b, d_c, d_a, n)                             # in place
+    assert (_host(ctx, d_a, n) == exp).all()
+    assert ctx.device_status() == 0
+    for p_ in (d_a, d_b, d_c, d_o):
+        ctx.free(p_)
+
+
 def _lookup_sort_on_device(ctx, inputs, values, n, usable):
     ptrs = []
     for v in inputs + values:
@@ -490,4 +587,89 @@ def test_gate_eval_flat_program(zk, ctx, curve, log_size):
     with pytest.raises(zk.ZkhipError):
         ctx.gate_eval_dev(curve, [((n_slots + 3, 0), [(1, [(0, 0)])])], d_slots, log_size, d_out)
     for p in d_slots + [d_mask, d_out]:
+        ctx.free(p)
+
+
+def _gate_expect(gates, ci, r, size, mask=None, prev=None):
+    """the program's sum from big integers, every row"""
+    out = []
+    for j in range(size):
+        tot = prev[j] if prev is not None else 0
+        for sel, terms in gates:
+            g = sum(c * reduce(lambda a, b: a * b % r, [ci[sl][(j + rot) % size] for sl, rot in fs], 1) for c, fs in terms) % r
+            tot += g * (ci[sel[0]][(j + sel[1]) % size] if sel is not None else 1)
+        out.append(tot * (mask[j] if mask is not None else 1) % r)
+    return out
+
+
+@pytest.mark.parametrize("curve", [0, 1])
+@pytest.mark.parametrize("log_size", [3, 5])
+def test_gate_eval_folds_the_running_total_across_gates(ctx, curve, log_size):
+    """gate_eval keeps the sum over the gates unreduced and folds it (a product by R mod p) when `total_pending + pending > 16`; no program
+    of test_gate_eval_flat_program gets there.  A gate's own sum folds at its 16th term and then counts as ONE summand, so
+      (a)   80 gates of 16 one-factor terms, no selector: every gate folds its own sum, the total folds at every 16th gate after the first;
+      (a15) 160 gates of 15 terms: the first leaves total_pending = 15 without a fold, every later gate folds the total first;
+      (b)   40 gates of one term under a selector (one summand each): the total folds at the 17th and the 33rd;
+      (c)   the three interleaved, accumulated onto a previous result and multiplied by a mask -- a random one and one of all r - 1.
+    Columns: four random, one of all r - 1, one of all zero; every fifth coefficient is r - 1.  Volume: a lazily reduced summand is a
+    Montgomery product's output, anywhere in [0, 2p); (a15) adds 2400 of them.  Without the fold their sum (some 1200 p on average)
+    leaves the 2^264 that nine limbs with a 32-bit top hold (1130 p for BLS12-381's r), and long before that the last product's operand
+    bound (total * mask < R p, R = 2^261 = 141 p) that keeps its result below 2p.  Every row against big integers."""
+    C = CURVES[curve]
+    r, size = C.r, 1 << log_size
+    cols = [cp.random_fr(curve, 900 + s, size) for s in range(4)] + [fr_arr([r - 1] * size), fr_arr([0] * size)]
+    ci = [fr_ints(c) for c in cols]
+    rng = po.SplitMix64(77 + log_size)
+    coeff = lambda i: r - 1 if i % 5 == 0 else rng.next_mod(r)
+    term = lambda i: (coeff(i), [(i % 6 if i % 11 else 4, (i % 5) - 2)])
+    prog_a = [(None, [term(16 * g + t) for t in range(16)]) for g in range(80)]
+    prog_a15 = [(None, [term(15 * g + t + 3) for t in range(15)]) for g in range(160)]
+    prog_b = [((g % 5, (g % 3) - 1), [term(7 * g + 1)]) for g in range(40)]
+    assert all(len(ts) == 16 for _, ts in prog_a) and sum(len(ts) for _, ts in prog_a) == 1280 and sum(len(ts) for _, ts in prog_a15) == 2400
+    prog_c = [g for i in range(160) for g in ([prog_a15[i]] + ([prog_a[i // 2]] if i % 2 == 0 else []) + ([prog_b[i // 4]] if i % 4 == 1 else []))]
+    assert len(prog_c) == 160 + 80 + 40
+    d_slots = [ctx.malloc(size * 32) for _ in cols]
+    for p, c in zip(d_slots, cols):
+        ctx.h2d(p, c)
+    d_mask, d_out = ctx.malloc(size * 32), ctx.malloc(size * 32)
+    out = np.zeros((size, 4), dtype=np.uint64)
+    for name, prog in (("a", prog_a), ("a15", prog_a15), ("b", prog_b)):
+        ctx.gate_eval_dev(curve, prog, d_slots, log_size, d_out)
+        ctx.d2h(out, d_out)
+        assert fr_ints(out) == _gate_expect(prog, ci, r, size), name
+    prev = cp.random_fr(curve, 950, size)
+    prev[0] = limbs(r - 1, 4)
+    for mask in (cp.random_fr(curve, 951, size), fr_arr([r - 1] * size)):
+        mask[-1] = 0
+        ctx.h2d(d_mask, mask)
+        ctx.h2d(d_out, prev)
+        ctx.gate_eval_dev(curve, prog_c, d_slots, log_size, d_out, d_mask, accumulate=True)
+        ctx.d2h(out, d_out)
+        assert fr_ints(out) == _gate_expect(prog_c, ci, r, size, mask=fr_ints(mask), prev=fr_ints(prev))
+    for p in d_slots + [d_mask, d_out]:
+        ctx.free(p)
+    assert ctx.device_status() == 0
+
+
+@pytest.mark.parametrize("curve", [0, 1])
+@pytest.mark.parametrize("log_size", [2, 3])
+def test_gate_eval_rotations_beyond_the_domain(ctx, curve, log_size):
+    """include/zkhip.h takes any int32 rotation, (j + r_f) mod 2^log_size: +-(size + 3) and +-2 size go round the domain more than once, in
+    factors and in a selector"""
+    C = CURVES[curve]
+    r, size = C.r, 1 << log_size
+    cols = [cp.random_fr(curve, 980 + s, size) for s in range(3)]
+    ci = [fr_ints(c) for c in cols]
+    gates = [((1, -(size + 3)), [(5, [(0, size + 3), (2, -2 * size)]), (r - 1, [(2, 2 * size), (0, -(size + 3))])]),
+             (None, [(3, [(1, size + 3)]), (7, [(1, -2 * size), (1, 2 * size)])]),
+             ((2, 2 * size), [(11, [(0, 0)])]), ((2, size + 3), [(13, [])])]
+    d_slots = [ctx.malloc(size * 32) for _ in cols]
+    for p, c in zip(d_slots, cols):
+        ctx.h2d(p, c)
+    d_out = ctx.malloc(size * 32)
+    ctx.gate_eval_dev(curve, gates, d_slots, log_size, d_out)
+    out = np.zeros((size, 4), dtype=np.uint64)
+    ctx.d2h(out, d_out)
+    assert fr_ints(out) == _gate_expect(gates, ci, r, size)
+    for p in d_slots + [d_out]:
         ctx.free(p)

@@ -108,6 +108,8 @@ def test_raw_limbs_at_the_contract_bounds(shim, t):
     assert ac.run_raw(shim.zkt_fu_raw, 5, 0, z)[0] == -1      # a saturated type has no raw limbs
     if t == 8:                                                # BLS12-381 r: no 128 p spread constant
         assert ac.run_raw(shim.zkt_fu_raw, t, ac.op_sub(128), z)[0] == -1
+    # fu_reduce_small is sized for the 9-limb scalar types: theirs ran above over every value of its quotient estimate's input
+    assert (ac.OP_REDUCE_SMALL in [op for op, _, _ in ac.raw_suite(t)]) == (L == 9) == (ac.run_raw(shim.zkt_fu_raw, t, ac.OP_REDUCE_SMALL, z)[0] == 0)
 
 
 def _chain(shim, field, curve, group, pts, infs, negs, mode, k=0):

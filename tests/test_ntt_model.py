@@ -154,3 +154,87 @@ def test_buffer_schedule():
                 assert dst != src
             src = dst
         assert src == "data"
+
+
+# ---- the planner itself (csrc/ntt_plan.hpp through libzkhip_hosttest.so) ----------------------------------------------------------
+MAX_LDS = 160 * 1024  # what a workgroup of ntt_pass may ask for
+
+
+def tile_u4(slots):
+    return 2 * slots + (slots + 3) // 4
+
+
+def lds_bytes(s, log_t, pb):
+    """bytes of LDS of one workgroup: pb tiles of 2^s x 2^log_t elements in three planes, the stage twiddles behind them"""
+    return (pb * tile_u4((1 << s) << log_t) + tile_u4(max(1, (1 << s) // 2))) * 16
+
+
+@pytest.fixture(scope="module")
+def shim():
+    import ctypes
+    import os
+    so = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "crypto3-zk_amd", "libzkhip_hosttest.so")
+    if not os.path.exists(so):
+        pytest.fail(f"{so} missing: run __graft_entry__.build()")
+    return ctypes.CDLL(so)
+
+
+def test_lds_arithmetic_of_the_deep_passes():
+    """the figures the planner's second bound rests on: a 2^12-element tile is 144 KiB; the stage table of a 10-stage pass is 18 KiB and
+    does not fit behind it, that of a 9-stage pass (9 KiB) does"""
+    assert tile_u4(4096) * 16 == 147456 == 144 * 1024
+    assert lds_bytes(10, 2, 1) == 147456 + 18432 == 165888 > MAX_LDS
+    assert lds_bytes(9, 3, 1) == 147456 + 9216 == 156672 <= MAX_LDS
+    assert lds_bytes(10, 1, 1) == 73728 + 18432 <= MAX_LDS
+
+
+def test_planner_walk_every_launch_fits_the_lds_and_radix_up_to_9_is_unchanged(shim):
+    """ntt_plan and ntt_launch_shape over log_m 1 .. 32 x ntt_radix_log 1 .. 10 x ntt_tile_log 0 .. 5 x 1, 2, 4 polynomials wanted per
+    workgroup (even and odd counts): every launch asks for at most 160 KiB of LDS -- before the planner counted the stage table the
+    10-stage passes at tile_log >= 2 (2^19, 2^20, 2^28 .. 2^30 at radix 10) asked for 165 888 B -- covers its polynomials, and keeps its
+    tile inside the pass's columns.  Up to radix 9 the plan is pass for pass (stages, tile width) what plan() above, the planner as it
+    stood before that bound, gives: the default path's launches have not moved."""
+    import ctypes
+    sv, lt = (ctypes.c_int * 32)(), (ctypes.c_int * 32)()
+    out = (ctypes.c_uint64 * 3)()
+    narrowed = []
+    for log_m in range(1, 33):
+        for radix in range(1, 11):
+            for tile_log in range(0, 6):
+                np_ = shim.zkt_ntt_plan(ctypes.c_size_t(log_m), radix, tile_log, sv, lt)
+                old = plan(log_m, radix, tile_log)
+                assert np_ == len(old) == (log_m + radix - 1) // radix
+                got = [(sv[i], lt[i]) for i in range(np_)]
+                assert sum(s for s, _ in got) == log_m and all(1 <= s <= radix and 0 <= t <= min(tile_log, log_m - s) for s, t in got)
+                if radix <= 9:
+                    assert got == [(s, t) for s, _, t in old], (log_m, radix, tile_log)
+                elif got != [(s, t) for s, _, t in old]:
+                    narrowed.append((log_m, tile_log))
+                    assert all((s, t) == (so, to) or (s == so == 10 and to == 2 and t == 1) for (s, t), (so, _, to) in zip(got, old))
+                for s, log_t in got:
+                    assert lds_bytes(s, log_t, 1) <= MAX_LDS, (log_m, radix, tile_log, s, log_t)
+                    for pb in (1, 2, 4):
+                        for count in (pb, 3 * pb, 1, 3, 6):
+                            assert shim.zkt_ntt_launch(s, log_t, pb, ctypes.c_size_t(count), out) == 0
+                            g_pb, g_t, g_lds = (int(x) for x in out)
+                            assert g_lds == lds_bytes(s, g_t, g_pb) <= MAX_LDS, (log_m, radix, tile_log, s, log_t, pb, count)
+                            assert g_pb in (1, 2, 4) and g_pb <= pb and count % g_pb == 0 and g_t <= log_t
+                            assert g_pb == 1 or g_lds <= 80 * 1024       # polynomials share a workgroup only beside a second one
+                            assert g_t == log_t or (pb > 1 and g_t >= 2)  # only sharing narrows a planned tile, never below 4 columns
+    assert sorted(set(m for m, _ in narrowed)) == [19, 20, 28, 29, 30] and all(t >= 2 for _, t in narrowed)
+    assert shim.zkt_ntt_plan(ctypes.c_size_t(20), 11, 3, sv, lt) == -1 and shim.zkt_ntt_plan(ctypes.c_size_t(33), 8, 3, sv, lt) == -1
+
+
+@pytest.mark.parametrize("log_m,smax,tile_log", [(9, 9, 3), (10, 10, 3), (11, 10, 0), (10, 9, 1)])
+def test_kernel_index_model_deep_passes(log_m, smax, tile_log):
+    """the index arithmetic of one 9- and one 10-stage pass (odd: stage 0 alone, then four round trips; even: five) and of the plans
+    (6, 5) and (5, 5) the radix options give small sizes"""
+    C = po.BLS12_381
+    r = C.r
+    random.seed(log_m * 100 + smax)
+    w = C.root_of_unity(log_m)
+    a = [random.randrange(r) for _ in range(1 << log_m)]
+    d = po.ntt(a, w, r)
+    assert model_ntt(a, log_m, w, r, smax=smax, tile_log=tile_log) == d
+    g = C.fr_generator
+    assert model_ntt(d, log_m, w, r, inverse=True, coset=g, smax=smax, tile_log=tile_log) == po.multiply_by_coset(a, pow(g, -1, r), r)
