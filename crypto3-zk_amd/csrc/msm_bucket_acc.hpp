@@ -11,6 +11,12 @@ namespace zkhip {
 // instead of VGPRs brings the G1 kernel under 168 registers (three waves per SIMD instead of two); the G2 kernel
 // runs on lane pairs (fu2_pair.hpp) that each hold half of every Fq2 coordinate, at two waves per SIMD.  ZZZ stays
 // in registers; the mixed addition reads the LDS coordinates where it uses them and writes the results back.
+// A bucket's sum starts as a table row, an AFFINE point.  On G1 a per-lane flag (`fresh`) remembers that, and the next addition leaves out
+// the four products by ZZ = ZZZ = one (curve.hpp xyzz_add_affine; ZZ = one is not written to LDS either): 8 of the 18 L^2 multiply-adds
+// of one addition, once per bucket with two or more entries -- 1.5 % of the kernel's VALU instructions at 2^20 points and 2^19 buckets
+// (EXPERIMENTS section 29).  The two branches share every product they have in common, so the kernel holds no second copy of the formula;
+// lanes of a wave that disagree run both sides of the two short branches, and the result does not depend on which lanes those are.
+// The entry index is loaded one iteration ahead: the row gather then waits on one dependent load, not two.
 template <class F>
 struct LimbView;  // the 29-bit limbs of a coordinate as one flat sequence
 template <class U>
@@ -76,22 +82,33 @@ __global__ __launch_bounds__(NT, WAVES) void msm_bucket_acc_lds(const uint32_t *
     enum { CX = 0, CY = 1, CZZ = 2 };
     F ZZZ = F::zero();
     bool inf = true;
+    // fresh: the running sum is its untouched first entry, an AFFINE point -- X, Y in LDS, ZZ = ZZZ = one implied (ZZ not even written).  The
+    // next addition is then xyzz_add_affine (curve.hpp): the same formula without the four products by one.  Lane pairs (LPB = 2) never set it.
+    bool fresh = false;
+    uint32_t e_next = lo < hi ? idx[lo] : 0u;  // one iteration ahead: the row gather waits on one dependent load, not two
     for (uint32_t k = lo; k < hi; ++k) {
-        const uint32_t e = idx[k];
+        const uint32_t e = e_next;
+        if (k + 1 < hi) e_next = idx[k + 1];
         Affine<F> p = affine_load<F>(bases + (size_t)(e & 0x7FFFFFFFu) * (2 * NL));  // entry = table row (slot * n + point) | sign
         if (p.is_inf()) continue;
         if (e >> 31) p.y = O::template sub<O::K1>(F::zero(), p.y);
         if (inf) {
             A.put(CX, p.x);
             A.put(CY, p.y);
-            A.put(CZZ, F::one());
+            if (LPB != 1) A.put(CZZ, F::one());
             ZZZ = F::one();
             inf = false;
+            fresh = LPB == 1;
             continue;
         }
-        // xyzz_madd (curve.hpp) with X, Y, ZZ fetched from LDS at their points of use
-        F Pd = O::template sub<O::K2>(O::mul(p.x, A.get(CZZ)), A.get(CX));
-        F R = O::template sub<O::K2>(O::mul(p.y, ZZZ), A.get(CY));
+        // xyzz_madd (curve.hpp) with X, Y, ZZ fetched from LDS at their points of use; a fresh sum skips the products by ZZ = ZZZ = one
+        F Pd = p.x, R = p.y;
+        if (!fresh) {
+            Pd = O::mul(p.x, A.get(CZZ));
+            R = O::mul(p.y, ZZZ);
+        }
+        Pd = O::template sub<O::K2>(Pd, A.get(CX));
+        R = O::template sub<O::K2>(R, A.get(CY));
         F PP = O::sqr(Pd);
         if (O::is_zero_product(PP)) {  // same x: doubling or cancellation (rare)
             if (O::is_zero(R)) {
@@ -103,6 +120,7 @@ __global__ __launch_bounds__(NT, WAVES) void msm_bucket_acc_lds(const uint32_t *
             } else {
                 inf = true;
             }
+            fresh = false;
             continue;
         }
         F PPP = O::mul(Pd, PP);
@@ -111,11 +129,17 @@ __global__ __launch_bounds__(NT, WAVES) void msm_bucket_acc_lds(const uint32_t *
         F Y3 = O::template mul_sub<O::K2>(R, O::template sub<O::K2>(Q, X3), A.get(CY), PPP);
         A.put(CX, X3);
         A.put(CY, Y3);
-        A.put(CZZ, O::mul(A.get(CZZ), PP));
-        ZZZ = O::mul(ZZZ, PPP);
+        if (fresh) {
+            A.put(CZZ, PP);
+            ZZZ = PPP;
+            fresh = false;
+        } else {
+            A.put(CZZ, O::mul(A.get(CZZ), PP));
+            ZZZ = O::mul(ZZZ, PPP);
+        }
     }
     XYZZ<F> out = XYZZ<F>::infinity();
-    if (!inf) out = {A.get(CX), A.get(CY), A.get(CZZ), ZZZ};
+    if (!inf) out = {A.get(CX), A.get(CY), fresh ? F::one() : A.get(CZZ), ZZZ};
     xyzz_store<F>(buckets + (size_t)g * (4 * NL), out);
 }
 

@@ -31,7 +31,8 @@
 // Kernels (all integer VALU; no MFMA -- this is modular arithmetic, not a dense contraction):
 //   (msm_entries.hip: msm_digits_only, msm_sort_*, msm_scan_*, msm_size_* -- dig, offs, idx, order and the large-bucket plan)
 //   msm_bucket_acc_lds  one lane per bucket (G1) or one even / odd lane pair per bucket (G2, fu2_pair.hpp): gather affine
-//                     points, XYZZ mixed additions, accumulator coordinates in LDS                          <- dominant
+//                     points, XYZZ mixed additions, accumulator coordinates in LDS; on G1 the first addition of a bucket is
+//                     affine + affine (xyzz_add_affine: no products by ZZ = ZZZ = one)                       <- dominant
 //   msm_bucket_large / msm_large_combine   buckets far above the mean (the plan: msm_size_scatter), one workgroup per 4096-entry task
 //   msm_bucket_merge  S > 1: fold the S equal-weight sets bucket by bucket (radix-4 tree)
 //   msm_fold          (round 5, table-backed sets of >= 2^16 buckets) row and column sums of the bucket index b = h C + l: the reduction
@@ -259,8 +260,8 @@ inline MsmFold msm_fold_geom(const zkhip_ctx *ctx, uint32_t B) {
 //   phase 1, bound by WORK: every point slot sums RUN buckets of its row / column with the lane shape FA (one lane per point for G1: an addition
 //            in the fewest issue slots), interleaved so that adjacent lanes read adjacent buckets, and leaves the sum in LDS;
 //   phase 2, bound by LATENCY: binary trees over the m partial sums of each row / column in LDS with the lane shape FT (G1: lane quads);
-//   level2[2 set][l] = COL[l], level2[2 set + 1][h - 1] = ROW[h] (row 0 has weight 0: dropped; entries R - 1 ... C - 1 of the second set stay
-//   empty = zeroed by the caller).
+//   level2[2 set][l] = COL[l], level2[2 set + 1][h - 1] = ROW[h] (row 0 has weight 0: dropped; entries R - 1 ... C - 1 of the second set are
+//   empty: the row half's workgroups zero them, dealt out among themselves, so every word of level2 is written here and the caller clears nothing).
 template <class FA, int LA, class FT, int LT>
 __global__ __launch_bounds__(MSM_TAIL_THREADS, ZK_TAIL_WAVES) void msm_fold(const uint32_t *__restrict__ buckets, MsmFold g, uint32_t *__restrict__ level2) {
     constexpr int NL = FieldOps<FA>::WORDS;
@@ -302,6 +303,12 @@ __global__ __launch_bounds__(MSM_TAIL_THREADS, ZK_TAIL_WAVES) void msm_fold(cons
         const uint32_t o = wg * G + i;  // row h / column l
         if (col || o != 0)
             xyzz_store<FT>(level2 + (((size_t)2 * w + (col ? 0 : 1)) * g.C + (col ? o : o - 1)) * PW, xyzz_load<FT>(lds + (size_t)i * m * PW));
+    }
+    if (!col) {  // the empty entries of the second set
+        for (uint32_t e = g.R - 1 + wg; e < g.C; e += half_wgs) {
+            uint32_t *z = level2 + (((size_t)2 * w + 1) * g.C + e) * PW;
+            for (uint32_t i = threadIdx.x; i < PW; i += MSM_TAIL_THREADS) z[i] = 0u;
+        }
     }
 }
 
@@ -761,7 +768,6 @@ int msm_fold_tail(zkhip_ctx *ctx, const uint32_t *sets, const MsmFoldBuffers<F> 
     constexpr int QL = QuadLane<F>::LANES;
     const MsmFold &g = fb.g;
     const size_t nsets = fb.nsets;
-    ZK_HIP_CHECK(ctx, hipMemsetAsync(fb.level2, 0, fb.level2_words() * 4, ctx->stream));  // empty buckets (the second set's upper part stays so)
     const size_t lds = (size_t)MSM_TAIL_THREADS / LPB * 4 * NL * 4;
     ZK_MAX_LDS(ctx, (msm_fold<FL, LPB, TQ, QL>), lds);
     ZK_LAUNCH(ctx, "msm_fold", (msm_fold<FL, LPB, TQ, QL>), dim3((unsigned)(nsets * (g.B / (MSM_TAIL_THREADS / LPB * g.run)) * 2)), dim3(MSM_TAIL_THREADS), lds,
