@@ -13,20 +13,13 @@
 
 #include <nil/crypto3/zk/hip/r1cs_gg_ppzksnark_generator.hpp>
 
+#include "bench_instance.hpp"
+
 using namespace nil::crypto3::zk::hip;
+using zkhip_bench::SplitMix;
+using zkhip_bench::build_instance;
 
 namespace {
-
-struct SplitMix {
-    uint64_t s;
-    uint64_t next() {
-        s += 0x9E3779B97F4A7C15ULL;
-        uint64_t z = s;
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-        return z ^ (z >> 31);
-    }
-};
 
 // Groth16 prover throughput on an instance of the reference's example family
 // (generate_r1cs_example_with_field_input, r1cs_examples.hpp:77-140): constraint system, satisfying assignment and a
@@ -55,57 +48,6 @@ int g_dom_kind = -1;
 size_t g_dom_m = 0;
 uint64_t g_last_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // domain kind, domain points, A / B / H / L query sizes of this rank, N, n
 double g_last_instance_ms = 0;    // building the synthetic constraint system + assignment of the last run (not part of *setup_ms)
-
-/// the synthetic instance of both bench entry points: the reference's generate_r1cs_example_with_field_input family
-/// (r1cs_examples.hpp:77-140), M constraints, n public inputs, N = M + 2 variables; returns the generator state for (r, s)
-template <typename Curve>
-SplitMix build_instance(size_t M, size_t n, uint64_t seed, r1cs_constraint_system<Curve> &cs, std::vector<typename curve_adapter<Curve>::scalar_value_type> &full) {
-    typedef curve_adapter<Curve> A;
-    typedef typename A::scalar_value_type Fr;
-    SplitMix rng {seed};
-    auto rnd = [&]() {    // < 2^252 < r for both curves: canonical
-        uint64_t w[4] = {rng.next(), rng.next(), rng.next(), rng.next() & 0x0fffffffffffffffULL};
-        return A::scalar_from_limbs(w);
-    };
-    cs.primary_input_size = n;
-    cs.auxiliary_input_size = 2 + M - n;
-    Fr a = rnd(), b = rnd();
-    full.push_back(a);
-    full.push_back(b);
-    cs.constraints.reserve(M);
-    for (size_t i = 0; i + 1 < M; ++i) {
-        r1cs_constraint<Curve> c;
-        Fr tmp;
-        if (i % 2) {
-            c.a.add_term(i + 1, 1);
-            c.b.add_term(i + 2, 1);
-            tmp = a * b;
-        } else {
-            c.b.add_term(0, 1);
-            c.a.add_term(i + 1, 1);
-            c.a.add_term(i + 2, 1);
-            tmp = a + b;
-        }
-        c.c.add_term(i + 3, 1);
-        full.push_back(tmp);
-        a = b;
-        b = tmp;
-        cs.add_constraint(c);
-    }
-    {
-        r1cs_constraint<Curve> c;
-        Fr fin = Fr::zero();
-        for (size_t i = 1; i < cs.num_variables(); ++i) {
-            c.a.add_term(i, 1);
-            c.b.add_term(i, 1);
-            fin = fin + full[i - 1];
-        }
-        c.c.add_term(cs.num_variables(), 1);
-        cs.add_constraint(c);
-        full.push_back(fin * fin);
-    }
-    return rng;
-}
 
 template <typename Curve>
 int groth16_bench_t(int device, size_t rank, size_t world, all_gather_fn all_gather, size_t M, size_t n, uint64_t seed, int steps, const uint64_t *omega,

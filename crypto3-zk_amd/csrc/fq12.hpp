@@ -115,6 +115,31 @@ ZK_HD Fp12<P> fp_sqr(const Fp12<P> &a) {
     const Fp6<P> t = (a.c0 + a.c1) * (a.c0 + fq6_mul_v(a.c1));
     return {t - ab - fq6_mul_v(ab), ab + ab};
 }
+// (a + b s)^2 in Fq4 = Fq2[s] / (s^2 - (u + 1)): 3 Fq2 squarings
+template <class P>
+ZK_HD void fq4_sqr(Fp2<P> &c0, Fp2<P> &c1, const Fp2<P> &a, const Fp2<P> &b) {
+    const Fp2<P> t0 = fp_sqr(a), t1 = fp_sqr(b);
+    c0 = fq2_mul_xi(t1) + t0;
+    c1 = fp_sqr(a + b) - t0 - t1;
+}
+// a^2 for a in the cyclotomic subgroup (a^(p^6 + 1) = 1 after the easy part of the final exponentiation), by Granger and Scott
+// (eprint 2009/565, section 3.2): three Fq4 squarings = 18 Fq products instead of 36.  The same value as fp_sqr there, and only there.
+template <class P>
+ZK_FQ6_HD Fp12<P> fq12_cyclotomic_sqr(const Fp12<P> &a) {
+    Fp2<P> t0, t1, t2, t3, t4, t5;
+    fq4_sqr(t0, t1, a.c0.c0, a.c1.c1);
+    fq4_sqr(t2, t3, a.c1.c0, a.c0.c2);
+    fq4_sqr(t4, t5, a.c0.c1, a.c1.c2);
+    const Fp2<P> t5x = fq2_mul_xi(t5);
+    Fp12<P> r;
+    r.c0.c0 = fp_dbl(t0 - a.c0.c0) + t0;
+    r.c0.c1 = fp_dbl(t2 - a.c0.c1) + t2;
+    r.c0.c2 = fp_dbl(t4 - a.c0.c2) + t4;
+    r.c1.c0 = fp_dbl(t5x + a.c1.c0) + t5x;
+    r.c1.c1 = fp_dbl(t1 + a.c1.c1) + t1;
+    r.c1.c2 = fp_dbl(t3 + a.c1.c2) + t3;
+    return r;
+}
 // a * (l0 + l1 v + l4 v w), the shape of a line value (pairing.hpp): 13 Fq2 products = 39 Fq products
 template <class P>
 ZK_HD Fp12<P> fq12_mul_by_014(const Fp12<P> &a, const Fp2<P> &l0, const Fp2<P> &l1, const Fp2<P> &l4) {

@@ -9,6 +9,7 @@
 #define ZK_NOINLINE_MUL 1  // keeps this shim's build time short; fu_sqr is reached through op 9
 #include "arith_ops.h"
 #include "glv.hpp"
+#include "groth16_verify.hpp"
 #include "msm_recode.hpp"
 #include "ntt_plan.hpp"
 #include "pairing.hpp"
@@ -225,7 +226,8 @@ int zkt_sha256_bytes(const uint8_t *msg, size_t len, uint8_t *digest) {
 }
 
 // Fq12 tower (fq12.hpp) on canonical limbs (72 u64 = 144 u32 per element).  op: 0 a * b, 1 a^2, 2 1 / a, 3 a^p (Frobenius), 4 conjugate,
-// 5 a * (l0 + l1 v + l4 v w) with the three Fq2 values l0, l1, l4 in b (72 u32), 6 final exponentiation
+// 5 a * (l0 + l1 v + l4 v w) with the three Fq2 values l0, l1, l4 in b (72 u32), 6 final exponentiation, 7 cyclotomic squaring (the square
+// of a only where a^(p^6 + 1) = 1)
 int zkt_fq12_op(int op, const uint32_t *a, const uint32_t *b, uint32_t *out) {
     if (!a || !out || ((op == 0 || op == 5) && !b)) return -1;
     const bls_fq12 x = fq12_from_canonical<BlsFq>(a);
@@ -247,6 +249,7 @@ int zkt_fq12_op(int op, const uint32_t *a, const uint32_t *b, uint32_t *out) {
         break;
     }
     case 6: r = pairing::final_exponentiation(x); break;
+    case 7: r = fq12_cyclotomic_sqr(x); break;
     default: return -1;
     }
     fq12_to_canonical(out, r);
@@ -278,6 +281,45 @@ int zkt_pairing_products(const uint32_t *g1, const uint8_t *g1_inf, const uint32
         }
     }
     for (size_t k = 0; k < n_out; ++k) fq12_to_canonical(out_gt + k * 144, pairing::final_exponentiation(acc[k]));
+    return 0;
+}
+
+// zkhip_groth16_verify_batch on the CPU: the same groth16_verify.hpp / pairing.hpp bodies (make_key, accumulate, miller_loop3 over the prepared
+// lines, final_exponentiation, the comparison).  The key as zkhip_groth16_vk_upload takes it; a, c: n canonical affine G1 points (24 u32), b: G2
+// (48 u32), with infinity flags; inputs: n x n_inputs scalars of 8 u32.  out_gt (n x 144 u32) and out_neg_acc (n x 24 u32: -acc, canonical, all
+// zero = infinity) are nullable.
+int zkt_groth16_verify(const uint64_t *alpha_beta, const uint64_t *gamma_g2, const uint64_t *delta_g2, const uint64_t *abc_xy, const uint8_t *abc_inf, size_t n_abc,
+                       const uint32_t *a, const uint8_t *a_inf, const uint32_t *b, const uint8_t *b_inf, const uint32_t *c, const uint8_t *c_inf, size_t n,
+                       const uint32_t *inputs, size_t n_inputs, uint8_t *ok, uint32_t *out_gt, uint32_t *out_neg_acc) {
+    using namespace groth16v;
+    if (!alpha_beta || !gamma_g2 || !delta_g2 || !abc_xy || n_abc == 0 || !a || !a_inf || !b || !b_inf || !c || !c_inf || !ok || (n_inputs && !inputs)) return -1;
+    if (n_inputs > n_abc - 1) return -2;
+    const std::vector<uint32_t> words = make_key(alpha_beta, gamma_g2, delta_g2, abc_xy, abc_inf, n_abc);
+    const Groth16Key key = key_at(words.data());
+    const auto coord = [](const uint32_t *p) {
+        bls_fq v;
+        for (int j = 0; j < 12; ++j) v.v[j] = p[j];
+        return fp_to_mont(v);
+    };
+    for (size_t i = 0; i < n; ++i) {
+        uint32_t neg_acc[AFFINE_WORDS];
+        neg_affine(neg_acc, accumulate(key, inputs + i * n_inputs * 8, n_inputs));
+        if (out_neg_acc)
+            for (int k = 0; k < 2; ++k) {
+                const bls_fq v = fp_from_mont(fq_at(neg_acc + k * FQ_WORDS));
+                for (int j = 0; j < 12; ++j) out_neg_acc[i * 24 + k * 12 + j] = v.v[j];
+            }
+        ProofPoints p;
+        p.a_inf = a_inf[i], p.b_inf = b_inf[i], p.c_inf = c_inf[i];
+        p.ax = coord(a + i * 24), p.ay = coord(a + i * 24 + 12);
+        p.cx = coord(c + i * 24), p.cy = coord(c + i * 24 + 12);
+        p.bx = {coord(b + i * 48), coord(b + i * 48 + 12)}, p.by = {coord(b + i * 48 + 24), coord(b + i * 48 + 36)};
+        pairing::RegStore fs;
+        miller3(fs, key, p, neg_acc);
+        const bls_fq12 v = pairing::final_exponentiation(fs.f);
+        ok[i] = p.well_formed() && equals_alpha_beta(key, v);
+        if (out_gt) fq12_to_canonical(out_gt + i * 144, v);
+    }
     return 0;
 }
 

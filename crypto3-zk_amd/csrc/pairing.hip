@@ -21,21 +21,17 @@
 #include <vector>
 
 #include "ctx.hpp"
-#include "fu.hpp"
-#include "pairing.hpp"
+#include "pairing_dev.hpp"
 
 using namespace zkhip;
+using namespace zkhip::pairing_dev;
 using pairing::Fq;
 using pairing::Fq12;
 using pairing::Fq2;
 
 namespace {
 
-constexpr unsigned PAIR_LANES = 64;    // lanes per workgroup of all three kernels: one wave
-constexpr unsigned F12_WORDS = 144;    // u32 words of an Fq12 value
 constexpr unsigned PROD_TILES = 16;    // Miller tiles (of 64 values) per workgroup of pairing_product_blocks
-constexpr unsigned COORD_WORDS = BlsFqU::SL;  // a bases object holds its coordinates in the lazy form of the curve kernels: 16 words per Fq
-constexpr unsigned G1_WORDS = 2 * COORD_WORDS, G2_WORDS = 4 * COORD_WORDS;
 
 struct PairingTerm {  // device copy of a zkhip_pairing_term
     const uint32_t *g1, *g2;  // first point of the term (affine, lazy Montgomery form, all words zero = infinity)
@@ -44,43 +40,6 @@ struct PairingTerm {  // device copy of a zkhip_pairing_term
     uint32_t tile_start, tiles;    // its Miller workgroups: ceil(n / 64) from tile_start
     uint32_t block_start;          // its product workgroups: ceil(tiles / PROD_TILES) from block_start
 };
-
-// an Fq12 value in a word-major slot: word k at base[k * stride]
-struct StridedStore {
-    uint32_t *base;
-    ZK_D Fq12 load() const {
-        Fq12 r;
-        uint32_t *w = reinterpret_cast<uint32_t *>(&r);
-ZK_UNROLL
-        for (unsigned k = 0; k < F12_WORDS; ++k) w[k] = base[k * PAIR_LANES];
-        return r;
-    }
-    ZK_D void store(const Fq12 &a) {
-        const uint32_t *w = reinterpret_cast<const uint32_t *>(&a);
-ZK_UNROLL
-        for (unsigned k = 0; k < F12_WORDS; ++k) base[k * PAIR_LANES] = w[k];
-    }
-};
-static_assert(sizeof(Fq12) == F12_WORDS * 4, "an Fq12 value is 144 packed words");
-
-ZK_D bool words_all_zero(const uint32_t *p, unsigned count) {
-    uint32_t o = 0;
-    for (unsigned i = 0; i < count; i += 4) {
-        const uint4 t = *reinterpret_cast<const uint4 *>(p + i);
-        o |= t.x | t.y | t.z | t.w;
-    }
-    return o == 0;
-}
-
-// a coordinate of a bases object (lazy 29-bit limbs, R = 2^406) as the saturated Montgomery value the tower computes on: two products
-ZK_D Fq load_coord(const uint32_t *p) {
-    uint32_t sat[BlsFq::NL];
-    fu_to_canonical<BlsFqU>(sat, fu_load<BlsFqU>(p));
-    Fq c;
-ZK_UNROLL
-    for (int i = 0; i < BlsFq::NL; ++i) c.v[i] = sat[i];
-    return fp_to_mont(c);
-}
 
 // the term a workgroup index belongs to, by its `start` / `count` members.  A linear walk of the term table by every workgroup: priced for the
 // two to four terms of a commitment or a GIPA round (zkhip.h says so); a caller with thousands of small terms pays O(n_terms) per workgroup.

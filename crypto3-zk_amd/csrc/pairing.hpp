@@ -3,6 +3,9 @@
 //   miller_loop(fs, P, Q)      f_{|x|, Q}(P), conjugated because x = -0xd201000000010000 is negative.  The running value f lives
 //                              behind `fs` (load / store of a whole Fp12): registers on the host, an LDS slot per lane in the
 //                              Miller kernel (pairing.hip), which keeps only the running twist point and the line in registers.
+//   prepare_lines(out, Q)      the 68 line triples of a FIXED Q (a verification key's gamma, delta), computed once per key
+//   miller_loop3(fs, ...)      the product of three Miller values, the shape of a Groth16 verification (groth16_verify.hpp): one walked
+//                              pair and two pairs over prepared lines, with one squaring of f per step for all three
 //   final_exponentiation(f)    f^(3 (p^12 - 1) / r): the x-chain of Hayashida, Hayasaka and Teruya (eprint 2020/875) computes the
 //                              hard part to the fixed multiple 3, and that is the power the reference's values are (its vectors
 //                              come from bellperson; tests/test_pairing_ref.py settles it against (p^12 - 1)/r and its triple).
@@ -95,11 +98,66 @@ ZK_HD void miller_loop(FStore &fs, const Fq &xp, const Fq &yp, const Fq2 &xq, co
     fs.store(fq12_conj(fs.load()));
 }
 
-// a^x for a in the cyclotomic subgroup (where the inverse is the conjugate)
+// The lines of a FIXED G2 point (a verification key's gamma and delta), walked once when the key is made: per step l0 and the factors
+// of xP and of yP in l1 and l4, so a Miller loop over such a point keeps no twist point and only scales by its G1 point.
+static constexpr int PREPARED_LINES = 63 + 5;  // one doubling per bit below the top of |x|, one addition per set bit among them
+ZK_HD void prepare_lines(Line *out, const Fq2 &xq, const Fq2 &yq) {
+    TwistPoint t = {xq, yq, Fq2::one()};
+    const Fq one = Fq::one();
+    for (int i = 62; i >= 0; --i) {
+        *out++ = doubling_step(t, one, one);
+        if ((BLS_X_ABS >> i) & 1) *out++ = addition_step(t, xq, yq, one, one);
+    }
+}
+
+// The pairs of miller_loop3.  A pair that is not `live` (one of its points is at infinity) contributes one.
+struct WalkedPair {  // a G1 point and a G2 point whose multiples the loop walks
+    bool live;
+    Fq xp, yp;
+    Fq2 xq, yq;
+};
+struct PreparedPair {  // a G1 point and the prepared lines of a fixed G2 point
+    bool live;
+    Fq xp, yp;
+    const Line *lines;
+};
+
+// fs <- miller(P0, Q0) miller(P1, Q1) miller(P2, Q2), the shape of a Groth16 verification (Q1, Q2: the key's gamma and delta): one
+// squaring of f per step serves all three pairs, and only Q0's multiples are computed.
+template <class FStore>
+ZK_HD void miller_loop3(FStore &fs, const WalkedPair &w, const PreparedPair &p1, const PreparedPair &p2) {
+    TwistPoint t = {w.xq, w.yq, Fq2::one()};
+    const Line *n1 = p1.lines, *n2 = p2.lines;
+    const auto prepared = [&fs](const PreparedPair &p, const Line *&next) {
+        const Line &l = *next++;
+        if (p.live) fs.store(fq12_mul_by_014(fs.load(), l.l0, fq2_scale(l.l1, p.xp), fq2_scale(l.l4, p.yp)));
+    };
+    fs.store(Fq12::one());
+    for (int i = 62; i >= 0; --i) {
+        fs.store(fp_sqr(fs.load()));
+        if (w.live) {
+            const Line l = doubling_step(t, w.xp, w.yp);
+            fs.store(fq12_mul_by_014(fs.load(), l.l0, l.l1, l.l4));
+        }
+        prepared(p1, n1);
+        prepared(p2, n2);
+        if ((BLS_X_ABS >> i) & 1) {
+            if (w.live) {
+                const Line m = addition_step(t, w.xq, w.yq, w.xp, w.yp);
+                fs.store(fq12_mul_by_014(fs.load(), m.l0, m.l1, m.l4));
+            }
+            prepared(p1, n1);
+            prepared(p2, n2);
+        }
+    }
+    fs.store(fq12_conj(fs.load()));
+}
+
+// a^x for a in the cyclotomic subgroup (where the inverse is the conjugate, and the squaring is Granger and Scott's)
 ZK_HD Fq12 exp_by_x(const Fq12 &a) {
     Fq12 r = a;
     for (int i = 62; i >= 0; --i) {
-        r = fp_sqr(r);
+        r = fq12_cyclotomic_sqr(r);
         if ((BLS_X_ABS >> i) & 1) r = r * a;
     }
     return fq12_conj(r);

@@ -14,8 +14,10 @@
 // `deterministic_basic_process` takes the toxic waste (t, alpha, beta, gamma, delta) as arguments, exactly like the
 // reference's testing entry point; `basic_process` draws it from the operating system's CSPRNG.  The group
 // generators are the standard ones (the reference draws random generators, generator.hpp:161,172: any generator
-// yields a valid key).  gamma only enters the verification key, which this backend does not build (verifier and
-// pairings are out of scope); it is accepted for signature parity.
+// yields a valid key).  gamma only enters the verification key (generator.hpp:282-294, 368-376), which
+// deterministic_basic_process also returns when it is given a place for it (`vk_out`): gamma_ABC_g1 from the same QAP
+// evaluation after the same swap_AB_if_beneficial, gamma_g2 and delta_g2 from the device's fixed-base path, and
+// alpha_g1_beta_g2 as one zkhip_pairing_products call.  r1cs_gg_ppzksnark_verifier.hpp checks proofs against it.
 //---------------------------------------------------------------------------//
 #ifndef ZKHIP_SHIM_R1CS_GG_PPZKSNARK_GENERATOR_HPP
 #define ZKHIP_SHIM_R1CS_GG_PPZKSNARK_GENERATOR_HPP
@@ -29,7 +31,9 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "kzg_ipp2.hpp"
 #include "r1cs_gg_ppzksnark.hpp"
+#include "r1cs_gg_ppzksnark_verifier.hpp"
 
 namespace nil {
 namespace crypto3 {
@@ -126,8 +130,9 @@ public:
     static std::unique_ptr<generated_proving_key<CurveType>> deterministic_basic_process(const context &ctx, const constraint_system_type &constraint_system,
                                                                                          const domain_params<CurveType> &dom, const scalar_value_type &t,
                                                                                          const scalar_value_type &alpha, const scalar_value_type &beta,
-                                                                                         const scalar_value_type & /*gamma*/, const scalar_value_type &delta,
-                                                                                         std::size_t rank = 0, std::size_t world = 1) {
+                                                                                         const scalar_value_type &gamma, const scalar_value_type &delta,
+                                                                                         std::size_t rank = 0, std::size_t world = 1,
+                                                                                         r1cs_gg_ppzksnark_verification_key<CurveType> *vk_out = nullptr) {
         typedef scalar_value_type Fr;
         std::unique_ptr<generated_proving_key<CurveType>> key(new generated_proving_key<CurveType>());
         auto &pk = key->host;
@@ -181,6 +186,22 @@ public:
             pk.delta_g1 = f1.at(2);
             pk.beta_g2 = f2.at(1);
             pk.delta_g2 = f2.at(2);
+        }
+        /* the verification key (:282-294, 368-376): gamma_ABC_g1[i] = ((beta A_i + alpha B_i + C_i)(t) / gamma) G1 for i <= n */
+        if (vk_out) {
+            const Fr gamma_inverse = gamma.inversed();
+            std::vector<Fr> abc(n + 1), ab = {alpha}, bg = {beta, gamma, delta};
+            for (std::size_t i = 0; i <= n; ++i) abc[i] = (beta * qap.At[i] + alpha * qap.Bt[i] + qap.Ct[i]) * gamma_inverse;
+            const auto abc_g1 = device_bases<CurveType, ZKHIP_G1>::from_scalars(ctx, abc.begin(), abc.end());
+            const auto a_g1 = device_bases<CurveType, ZKHIP_G1>::from_scalars(ctx, ab.begin(), ab.end());
+            const auto g2 = device_bases<CurveType, ZKHIP_G2>::from_scalars(ctx, bg.begin(), bg.end());
+            vk_out->alpha_g1_beta_g2 = detail::pairing_products<CurveType>(ctx, {detail::pairing_term<CurveType>(a_g1, g2, 1, 0)}, 1)[0];
+            vk_out->gamma_g2 = g2.at(1);
+            vk_out->delta_g2 = g2.at(2);
+            vk_out->gamma_ABC_g1.first = abc_g1.at(0);
+            vk_out->gamma_ABC_g1.rest.clear();
+            for (std::size_t i = 1; i <= n; ++i) vk_out->gamma_ABC_g1.rest.push_back(abc_g1.at(i));
+            lap("verification key");
         }
         /* the five batch exponentiations (:339-366), left resident as the key's queries.  rank / world > 1: this process
            generates (and will hold) only its slice of every query -- the point-range partition of a sharded proof. */

@@ -23,6 +23,7 @@ EXPORTS = [
     "zkhip_r1cs_upload", "zkhip_r1cs_free", "zkhip_r1cs_set_domain", "zkhip_r1cs_domain_size", "zkhip_r1cs_domain_kind", "zkhip_groth16_scratch_bytes", "zkhip_groth16_witness_h_dev", "zkhip_groth16_witness_h_domain_dev", "zkhip_fr_gather_dev", "zkhip_poly_resize_dev", "zkhip_fri_fold_dev", "zkhip_fri_leaves_dev", "zkhip_ec_ntt_dev",
     "zkhip_fr_vec_op_dev", "zkhip_fr_vec_affine_dev", "zkhip_fr_vec_mul_div_dev", "zkhip_fr_vec_prod_dev", "zkhip_poly_shift_dev", "zkhip_poly_eval_dev", "zkhip_poly_div_linear_dev", "zkhip_poly_div_vanishing_dev", "zkhip_poly_lincomb_dev", "zkhip_perm_grand_product_dev", "zkhip_lookup_grand_product_dev", "zkhip_lookup_sort_dev", "zkhip_perm_factor_products_dev", "zkhip_gate_eval_dev",
     "zkhip_bases_fold", "zkhip_bases_scale_dev", "zkhip_bases_scale_geometric", "zkhip_bases_lagrange", "zkhip_fr_inner_product_dev", "zkhip_fr_powers_lincomb_dev", "zkhip_fr_challenge_products_dev", "zkhip_pairing_products",
+    "zkhip_groth16_vk_upload", "zkhip_groth16_vk_inputs", "zkhip_groth16_vk_free", "zkhip_groth16_verify_batch",
     "zkhip_merkle_build_dev", "zkhip_merkle_build_fri_dev", "zkhip_merkle_leaves", "zkhip_merkle_depth", "zkhip_merkle_root", "zkhip_merkle_digests", "zkhip_merkle_paths",
     "zkhip_merkle_free", "zkhip_fri_query_dev", "zkhip_merkle_paths_multi", "zkhip_pow_grind", "zkhip_sha256_host",
     "zkhip_group_init", "zkhip_group_destroy", "zkhip_group_size", "zkhip_group_ctx", "zkhip_group_last_error", "zkhip_group_set_transport", "zkhip_group_transport",
@@ -150,6 +151,9 @@ def load_library() -> ctypes.CDLL:
     lib.zkhip_merkle_depth.argtypes = [ctypes.c_void_p]
     lib.zkhip_merkle_free.restype = None
     lib.zkhip_merkle_free.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.zkhip_groth16_vk_inputs.restype = ctypes.c_size_t
+    lib.zkhip_groth16_vk_inputs.argtypes = [ctypes.c_void_p]
+    lib.zkhip_groth16_vk_free.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.zkhip_pow_grind.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_size_t,
                                     ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)]
     lib.zkhip_sha256_host.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p]
@@ -313,6 +317,29 @@ class Context:
         self._check(self.lib.zkhip_pairing_products(self.h, ctypes.c_int(curve), arr, ctypes.c_size_t(len(terms)), ctypes.c_size_t(n_out), _p(res)),
                     "zkhip_pairing_products")
         return res
+
+    def groth16_vk_upload(self, alpha_beta, gamma_g2, delta_g2, gamma_abc, gamma_abc_inf=None, curve: int = BLS12_381) -> "Groth16Vk":
+        """a resident Groth16 verification key: alpha_beta 72 uint64 (canonical Fq12), gamma_g2 / delta_g2 24 uint64 (affine), gamma_abc n_abc x 12
+        uint64 (gamma_ABC_g1.first, then .rest) with optional infinity flags (zkhip_groth16_vk_upload)"""
+        abc = _u64(gamma_abc).reshape(-1, 12)
+        infa = np.ascontiguousarray(gamma_abc_inf, dtype=np.uint8) if gamma_abc_inf is not None else None
+        h = ctypes.c_void_p()
+        self._check(self.lib.zkhip_groth16_vk_upload(self.h, ctypes.c_int(curve), _p(_u64(alpha_beta).reshape(72)), _p(_u64(gamma_g2).reshape(24)),
+                                                     _p(_u64(delta_g2).reshape(24)), _p(abc), _p(infa), ctypes.c_size_t(abc.shape[0]), ctypes.byref(h)),
+                    "zkhip_groth16_vk_upload")
+        return Groth16Vk(self, h)
+
+    def groth16_verify(self, vk: "Groth16Vk", a: "Bases", b: "Bases", c: "Bases", inputs, offset: int = 0, n=None, want_gt: bool = False):
+        """ok (n uint8, 1 = accepted) of the proofs (a[offset + i], b[offset + i], c[offset + i]) under the inputs row i of `inputs` (n x n_inputs x 4
+        uint64, n_inputs <= vk.n_inputs: missing inputs are zero); with want_gt also the compared values, n x 72 uint64 (zkhip_groth16_verify_batch)"""
+        n = a.n - offset if n is None else n
+        inputs = _u64(inputs).reshape(n, -1, 4) if n else np.zeros((0, 0, 4), dtype=np.uint64)
+        ok = np.zeros(n, dtype=np.uint8)
+        gt = np.zeros((n, 72), dtype=np.uint64) if want_gt else None
+        self._check(self.lib.zkhip_groth16_verify_batch(self.h, vk.h, a.h, b.h, c.h, ctypes.c_size_t(offset), ctypes.c_size_t(n),
+                                                        _p(inputs) if inputs.size else None, ctypes.c_size_t(inputs.shape[1]), _p(ok), _p(gt)),
+                    "zkhip_groth16_verify_batch")
+        return (ok, gt) if want_gt else ok
 
     def bases_scale_dev(self, bases: "Bases", offset: int, n: int, d_scalars: int, flags: int = 0) -> "Bases":
         """out[i] = s_i * bases[offset + i], i < n, s_i the i-th of n scalars resident at d_scalars (taken mod r): a new bases object, without
@@ -855,6 +882,25 @@ class GroupBases:
     def free(self):
         if self.h is not None and self.g.h:
             self.g.lib.zkhip_group_bases_free(self.g.h, self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Groth16Vk:
+    """Resident Groth16 verification key (zkhip_groth16_vk)."""
+
+    def __init__(self, ctx: Context, h):
+        self.ctx, self.h = ctx, h
+        self.n_inputs = ctx.lib.zkhip_groth16_vk_inputs(h)
+
+    def free(self):
+        if self.h is not None and self.ctx.h:
+            self.ctx.lib.zkhip_groth16_vk_free(self.ctx.h, self.h)
         self.h = None
 
     def __del__(self):

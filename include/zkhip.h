@@ -558,6 +558,51 @@ typedef struct zkhip_pairing_term {
 } zkhip_pairing_term;
 int zkhip_pairing_products(zkhip_ctx *ctx, int curve, const zkhip_pairing_term *terms, size_t n_terms, size_t n_out, uint64_t *out_gt);
 
+/* ---- Groth16 verification: batches of proofs against one key, up to and including the final exponentiation --------------------
+ * Per proof, r1cs_gg_ppzksnark_verifier_weak_input_consistency::process of the reference
+ * (systems/ppzksnark/r1cs_gg_ppzksnark/verifier.hpp:150-186):
+ *     acc = abc[0] + sum_{j < n_inputs} x_j abc[j + 1]
+ *     ok  = well_formed && final_exponentiation(miller(A, B) miller(-acc, gamma) miller(-C, delta)) == alpha_beta
+ * The reference divides by double_miller_loop(acc, gamma, C, delta) before its final exponentiation; negating the G1 points instead
+ * differs from that by factors of proper subfields only, which the final exponentiation removes, and an element of GT has one
+ * canonical form: the compared value is the reference's bit for bit.
+ * Conventions:
+ *   - ZKHIP_BLS12_381 ONLY; ZKHIP_BN254 and the Pasta ids are ZKHIP_ERR_INVALID, for the reasons zkhip_pairing_products gives.  The
+ *     pairing, the power 3 (p^12 - 1) / r and the layout of a GT value (72 u64) are zkhip_pairing_products'.
+ *   - A key is uploaded once (zkhip_groth16_vk_upload) and holds, on the device: alpha_beta, the 68 prepared line triples of gamma and
+ *     of delta each (19584 bytes per point), abc[0], and per input a fixed-base table of 4-bit windows: 64 windows x 15 affine points =
+ *     92160 bytes per input.  A proof's accumulation is at most 64 mixed additions per input (one per non-zero nibble of x_j) and no
+ *     doubling.  A key takes at most ZKHIP_GROTH16_VK_MAX_INPUTS = 2^15 inputs (2.8 GiB of tables); the tables are computed on one
+ *     host thread at upload, about a millisecond per input.
+ *   - alpha_beta: 72 u64, canonical, the order zkhip_pairing_products writes.  gamma_g2 / delta_g2: affine, 24 u64 each, not at
+ *     infinity.  gamma_abc_xy: n_abc >= 1 affine G1 points of 12 u64: gamma_ABC_g1.first, then .rest; gamma_abc_inf nullable.
+ *   - Proofs offset .. offset + n of three resident bases objects (a: ZKHIP_G1, b: ZKHIP_G2, c: ZKHIP_G1), so proofs can come from host
+ *     points, from scalars, or from the wire decoder.  Only the points are read; window tables play no part.
+ *   - inputs: HOST, n x n_inputs x 4 u64, canonical; n_inputs <= zkhip_groth16_vk_inputs(vk): missing inputs are zero (weak input
+ *     consistency).  ok: HOST, n bytes, 1 = accepted.  out_gt: nullable, HOST, n x 72 u64: the value that was compared with alpha_beta.
+ *   - well_formed is the reference's proof.is_well_formed(): A, B and C lie on their curves (or are at infinity).  The call checks it
+ *     itself, whatever constructor made the bases.  A pair with a point at infinity contributes one; acc may be at infinity.
+ *   - Membership of the order-r subgroups is not checked, as in the reference: for an on-curve point outside its subgroup ok (and
+ *     out_gt) are unspecified.  No input makes the call fault: the Miller formulas have no divisions.
+ *   - A rejected proof is not an error: the call returns ZKHIP_OK.  Three launches whatever n is; nothing proportional to n runs on
+ *     the host but the copies of inputs, ok and out_gt.  The call returns with the stream drained.
+ * Errors, before anything is launched:
+ *   ZKHIP_ERR_INVALID   a null ctx / vk / a / b / c / ok; inputs null with n_inputs > 0; a bases object of the wrong group or of another
+ *                       curve; a vk of another context's device.  Upload: a null ctx / alpha_beta / gamma_g2 / delta_g2 / out, a null
+ *                       gamma_abc_xy with n_abc > 0, a curve other than ZKHIP_BLS12_381.
+ *   ZKHIP_ERR_RANGE     offset + n beyond any of the three objects; n_inputs above the key's.  Upload: n_abc = 0 or more than
+ *                       ZKHIP_GROTH16_VK_MAX_INPUTS inputs.
+ *   ZKHIP_ERR_OOM       Upload: no host or device memory for the tables.
+ *   n = 0 is ZKHIP_OK with nothing launched. */
+#define ZKHIP_GROTH16_VK_MAX_INPUTS 32768
+typedef struct zkhip_groth16_vk zkhip_groth16_vk;
+int zkhip_groth16_vk_upload(zkhip_ctx *ctx, int curve, const uint64_t *alpha_beta, const uint64_t *gamma_g2, const uint64_t *delta_g2,
+                            const uint64_t *gamma_abc_xy, const uint8_t *gamma_abc_inf /* nullable */, size_t n_abc, zkhip_groth16_vk **out);
+size_t zkhip_groth16_vk_inputs(const zkhip_groth16_vk *vk);  /* n_abc - 1 */
+void zkhip_groth16_vk_free(zkhip_ctx *ctx, zkhip_groth16_vk *vk);
+int zkhip_groth16_verify_batch(zkhip_ctx *ctx, const zkhip_groth16_vk *vk, const zkhip_bases *a, const zkhip_bases *b, const zkhip_bases *c,
+                               size_t offset, size_t n, const uint64_t *inputs, size_t n_inputs, uint8_t *ok, uint64_t *out_gt /* nullable */);
+
 /* ---- the gate argument's sum over a flat program -------------------------------------------------------------------------
  * placeholder's gates argument (ph/gates_argument.hpp:93-121, 203-216) computes, on the extended domain of 2^log_size points,
  *     F = mask * sum_gates selector_g * sum_constraints theta^k * constraint(columns, rotated).
